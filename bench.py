@@ -19,6 +19,11 @@ Workload (BASELINE.json north_star; synthetic because no EuRoC data exists here 
   inputs (images, keypoints, priors) are resident in HBM before the timed region; nothing crosses PCIe inside it.
 Sequences are independent, so N GPUs = N x seqs sequences, no data-path collective ("scaling": "weak");
 RCCL is used only for the end-of-run reduction of {frames, seconds}.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps and the result line.  `--full` adds
+the side reports, each outside the timed region: the hipEvent-instrumented pass (`kernels`, `roofline`), the harder
+stream, the EuRoC-sized legs and the CPU port baselines.  `--dump-outputs DIR` writes what the timed path computed in
+its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -94,6 +99,12 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL over xGMI) for the real multi-GPU run; gloo rehearses the N > 1 control flow with "
                          "several ranks sharing one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side reports after the timed region: instrumented per-kernel pass + roofline, harder "
+                         "stream, EuRoC-sized legs, CPU port baselines (each still switchable off with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; rank 0's sequences)")
     return ap.parse_args()
 
 
@@ -433,6 +444,58 @@ def cpu_baseline(workload, kf_every, budget_s, threads=1):
     return frames / el, frames, el
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, wl, ba):
+    """--dump-outputs: the arrays the timed path hands its caller after its last step, as path/<name>.npy.
+      frame_xy / frame_status / frame_p3p_req  the tracking buffers of the last frame (kltTracking_dev; on a keyframe the
+                                               stereo matching of the same frame is their last writer)
+      kf_stereo_xy / kf_stereo_status          stereo matching of the last keyframe, when it runs on the mapper context
+      kf_corners_xy / kf_corner_count /        grid detector of the last keyframe (rows past a sequence's count are zero)
+      kf_detect_threshold
+      pnp_pose / pnp_outlier / pnp_ok          per-frame ceresPnP of the last frame (--pnp)
+      ba_kf_pose / ba_kf_state / ba_lm_xyz /   every sequence's device map after its last local-BA job (set-up + solve +
+      ba_lm_state / ba_map_sizes               update from the saved state), maps concatenated in sequence order
+    Every array is float32 or float64.  Past DUMP_CAP_BYTES in all, the long arrays keep a fixed seeded sample of their
+    rows (sorted; the row indices are written as <name>_rows.npy)."""
+    f32 = lambda x: np.ascontiguousarray(x, np.float32)
+    out = {"frame_xy": f32(wl.out_xy.get()), "frame_status": f32(wl.out_st.get()), "frame_p3p_req": f32(wl.p3p.get())}
+    if wl.mctx is not None:
+        out["kf_stereo_xy"], out["kf_stereo_status"] = f32(wl.m_out_xy.get()), f32(wl.m_out_st.get())
+    elif wl.detect:
+        n = wl.d_det_nout.get().astype(np.int64)
+        xy = wl.d_det_out.get()
+        xy[np.arange(xy.shape[1])[None, :] >= n[:, None]] = 0.0
+        out["kf_corners_xy"], out["kf_corner_count"] = f32(xy), f32(n)
+        out["kf_detect_threshold"] = np.ascontiguousarray(wl.d_det_thresh.get(), np.float64)
+    if wl.pnp:
+        q = wl.pnp
+        out["pnp_pose"], out["pnp_outlier"], out["pnp_ok"] = q["T"].get(), f32(q["outl"].get()), f32(q["ok"].get())
+    if isinstance(ba, BaPipeline):
+        tabs = [m.download() for ms in ba.maps for m in ms]
+        out["ba_kf_pose"] = np.concatenate([t["kf_pose"] for t in tabs])
+        out["ba_kf_state"] = f32(np.concatenate([t["kf_state"] for t in tabs]))
+        out["ba_lm_xyz"] = np.concatenate([t["lm_xyz"] for t in tabs])
+        out["ba_lm_state"] = f32(np.concatenate([t["lm_state"] for t in tabs]))
+        out["ba_map_sizes"] = np.asarray([[len(t["kf_pose"]), len(t["lm_xyz"])] for t in tabs], np.float64)
+    if sum(v.nbytes for v in out.values()) > DUMP_CAP_BYTES:
+        long_ = sorted(k for k, v in out.items() if len(v) > 4096)
+        short = sum(out[k].nbytes for k in out if k not in long_)
+        # a sampled row costs its own bytes + 8 for its index
+        keep = (0.95 * DUMP_CAP_BYTES - short) / sum(out[k].nbytes + 8 * len(out[k]) for k in long_)
+        rng = np.random.default_rng(12345)
+        for k in long_:
+            v = out[k]
+            rows = np.sort(rng.choice(len(v), max(1, int(keep * len(v))), replace=False))
+            out[k], out[k + "_rows"] = np.ascontiguousarray(v[rows]), rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        assert v.dtype in (np.float32, np.float64), k
+        np.save(os.path.join(path, k + ".npy"), v)
+    return sorted(out)
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -447,7 +510,8 @@ def main():
             share = len(os.sched_getaffinity(0))
         except Exception:
             share = os.cpu_count() or 1
-        procs = a.gen_procs if a.gen_procs > 0 else max(1, min(32, share // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", world)))))
+        # at most 16: the affinity mask can show far more cores than the process's CPU share (the windows do not depend on it)
+        procs = a.gen_procs if a.gen_procs > 0 else max(1, min(16, share // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", world)))))
         specs = synth_ba.sequence_window_specs(a.seqs, seed=20211 + 100003 * rank, n_kf=a.ba_kfs, n_lm=a.ba_lms, spread=a.ba_spread)
         t_gen = time.perf_counter()
         windows = synth_ba.make_windows_parallel(specs, procs)
@@ -611,7 +675,10 @@ def main():
         out["config"]["workload"] += (f"; localBA (set-up + solve + update) per keyframe job on {len(ba.flat)} DISTINCT device-resident "
                                       f"maps around {a.ba_kfs} KFs / {a.ba_lms} landmarks (+-{int(100 * a.ba_spread)} %)")
 
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, wl, ba)
+
+    if rank == 0 and a.full and not a.no_roofline:
         # second, instrumented pass over the same steps: every launch bracketed by hipEvents on the ctx stream
         ctx.kernel_timing(True)
         ctx.kernel_times()
@@ -709,7 +776,7 @@ def main():
         out["config"]["stream_priority"] = {"front_end": a.fe_priority, "local_ba": a.ba_priority}
         out["ms_per_frame_batch_instrumented"] = 1e3 * el_instr / n_instr
 
-    if rank == 0 and not a.no_roofline and not a.no_hard_stream:
+    if rank == 0 and a.full and not a.no_roofline and not a.no_hard_stream:
         # a HARDER stream beside the headline one (front-end alone, outside the timed region): three times the flow per
         # frame and priors 3 px off, so the LK passes iterate about twice as often -- how the rate degrades with difficulty
         hw = Workload(ctx, fe, synth, a.seqs, a.kps, 4, seed=synth.SEED_IMG + 101 * rank + 7, gap=3 * a.frame_gap,
@@ -737,7 +804,7 @@ def main():
                               "note": "same pipeline on a stream with 3x the flow and 3x the prior error; no BA worker beside it"}
         del hw
 
-    if rank == 0 and not a.no_roofline and not a.no_euroc_like:
+    if rank == 0 and a.full and not a.no_roofline and not a.no_euroc_like:
         # The size the reference actually runs (configs 2 / 3: <= 308 keypoints per frame = nmaxdist 35 on 752 x 480,
         # src/slam_params.cpp:107-110; windows of 10-30 keyframes / 1-3 k landmarks, ONE sequence): the same pipeline with
         # per-frame ceresPnP on the tracking stream and the whole local BA (set-up + solve + update) per keyframe beside it,
@@ -834,7 +901,7 @@ def main():
             except Exception as e:   # a side report: never lose the bench line to it
                 out["euroc_like"][f"{nseq}_seq"] = {"error": repr(e)}
 
-    do_cpu = rank == 0 and world == 1 and not a.no_cpu_baseline   # the CPU leg is reported at N = 1 only
+    do_cpu = a.full and rank == 0 and world == 1 and not a.no_cpu_baseline   # the CPU leg is reported at N = 1 only
     if do_cpu:
         from oracle import oracle_py as O
         native = O.use_native(True)        # same sources at -O3 -march=native for this host

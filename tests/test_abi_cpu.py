@@ -36,7 +36,7 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert set(_lib.SIGNATURES) <= set(names)
 
 
-def test_pod_layout_matches_c():
+def test_pod_layout_matches_c(tmp_path):
     """compile a tiny C program against the public header and compare sizeof/offsetof with the ctypes mirrors"""
     from ov2slam_amd import ba_types as T
     src = r'''
@@ -48,7 +48,7 @@ int main(void) {
   printf("%zu %zu %zu %zu\n", offsetof(ov2_ba_problem, pose), offsetof(ov2_ba_problem, res_sigma),
          offsetof(ov2_ba_options, jacobi_scaling), offsetof(ov2_ba_result, log));
   return 0; }'''
-    exe = "/tmp/ov2_layout_check"
+    exe = str(tmp_path / "ov2_layout_check")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     out = subprocess.check_output([exe]).decode().split()
     sizes = [int(x) for x in out]
