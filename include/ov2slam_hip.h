@@ -442,11 +442,16 @@ ov2_status ov2_map_remove_keyframe(ov2_map *m, int kfid);
  * src/map_manager.cpp:885-1019).  ov2_map_local_ba_setup squeezes them out (stable: the order of the live rows, and so
  * every result, is unchanged) when fewer than half of >= 4096 rows are live, so the table stays within 2x the live
  * observations over any sequence length; ov2_map_compact does it on request.  kfid / lmid are never reused by the
- * reference (nkfid_ / nlmid_ only grow), which is what makes a row of a removed keyframe or landmark dead for good. */
+ * reference (nkfid_ / nlmid_ only grow), which is what makes a row of a removed keyframe or landmark dead for good.
+ * A squeeze (automatic or ov2_map_compact) keeps every row that is live in the current state OR in a state saved by
+ * ov2_map_save_state of these very rows, and squeezes the saved flags with them: the saved state stays restorable.  With a
+ * saved state, the automatic squeeze waits until the table is twice the size its last squeeze left.  A squeeze, like a
+ * growth of the tables, ends what the last set-up can be updated from (ov2_map_local_ba_update_batch refuses it). */
 ov2_status ov2_map_compact(ov2_map *m, int *rows_before, int *rows_after);
 ov2_status ov2_map_obs_rows(const ov2_map *m, int *rows, int *capacity, int *compactions);
 
-/* The flat problem of one local BA, in pinned host memory owned by the map (valid until the next set-up call):
+/* The flat problem of one local BA, in pinned host memory owned by the map (the memory stays valid until the next set-up
+ * call; what ov2_map_local_ba_update_batch accepts is narrower, see there):
  * exactly the arrays ov2_ba_problem wants plus the reference ids behind the indices. */
 typedef struct ov2_local_ba_setup {
     int32_t aborted;                 /* nb3dkps < nmin_covscore  (src/optimizer.cpp:61-63) */
@@ -504,9 +509,26 @@ ov2_status ov2_map_local_ba_setup_batch(ov2_ctx *ctx, int B, ov2_map *const *map
  *    (K^-1 [u v 1] / rho) with the UPDATED anchor pose) via MapManager::updateMapPoint (:789-853),
  *  - the second culling pass over set_badlmids (:856-882).
  * MapPoint::kfid_ is taken to be the landmark's oldest observer (how MapManager::addMapPoint creates it and
- * MapPoint::removeKfObs maintains it; mergeMapPoints is out of scope).
+ * MapPoint::removeKfObs maintains it).
+ * Edits between set-up and update.  The reference solves without the map lock and reads its objects as they are when the
+ * update takes it (:741): so does this call.  Allowed between the set-up and the update, through the hooks above:
+ *  - ov2_map_add_keyframe: new keyframes, and rows appended to a keyframe already in the map (matchToMap / merges) --
+ *    within the capacities,
+ *  - ov2_map_remove_obs, ov2_map_set_obs_stereo, ov2_map_remove_landmarks, ov2_map_set_landmarks (isobs_ flips).
+ * The observers of every landmark of the window, its oldest observer (MapPoint::kfid_; with inverse depth: the keyframe
+ * whose solved pose and pixel turn rho into the world point, :822-838), isobs_ and liveness are read from the tables at
+ * the update; only the set-up's rows are checked for flagged blocks, and a row that died since is neither removed again
+ * nor reported.  NOT covered: ov2_map_remove_keyframe and MapManager::mergeMapPoints between set-up and update, poses set
+ * by ov2_map_set_poses (the solved poses overwrite them), a keyframe appended with an id older than a landmark's
+ * oldest observer (MapPoint::kfid_ would not move in the reference), and an inverse-depth landmark that the edits and the
+ * flagged blocks together leave without any observer while isobs_ is set (the reference then reads an empty Keypoint of
+ * its last anchor keyframe; here its point is left as it was and it goes to the second culling pass).
+ * Refused with OV2_ERR_INVALID, tables untouched: a map without a set-up, a map whose tables grew (a hook passed a
+ * capacity) or were squeezed (ov2_map_compact, or a set-up's squeeze) since its set-up, a map restored since
+ * (ov2_map_restore_state_batch), and a second update of the same set-up.
  * out == NULL: fully asynchronous.  out != NULL: one synchronisation; out[b] lists what the host must replay on its own
- * Frame / MapPoint objects (DEVICE arrays inside the map's block, valid until its next set-up; order arbitrary).
+ * Frame / MapPoint objects (DEVICE arrays inside the map's block, valid until its next set-up; order arbitrary; each
+ * observation at most once, and stereo_off only holds observations that survive as mono).
  */
 typedef struct ov2_local_ba_update {
     int32_t n_removed_lm, n_removed_obs, n_stereo_off;

@@ -40,11 +40,14 @@ struct ov2_map {
     // the last set-up (the update stage reads its scratch arrays and its flat problem where they were left)
     int last_hdr[16];                                               // host copy of its header
     int last_newkf, last_inv, last_valid;
+    int last_n_obs;                                                 // rows the last set-up saw (only they carry its obs_cnt / obs_off)
+    int last_updated;                                               // its update stage has been enqueued: a second one is refused
     int live_rows, live_known;                                      // live rows of the table as the last set-up counted them
     double last_K[4]; int have_K;                                   // left intrinsics (anchored inverse depth -> world point)
     // ov2_map_save_state / ov2_map_restore_state_batch
     double *snap_kf_pose, *snap_lm_xyz; unsigned char *snap_kf_state, *snap_lm_state, *snap_obs_flag;
     int snap_kf, snap_lm, snap_obs;
+    int snap_floor;                                                 // rows a squeeze kept for the saved state: no new squeeze below 2x
 };
 
 namespace {
@@ -132,6 +135,7 @@ __global__ __launch_bounds__(256) void map_edit_obs_kernel(int n_obs, const int 
 struct map_job {
     map_view M;
     int newkf, cur_kfid;
+    int last_n_obs;                              // update stage: rows of the set-up (rows appended since have no obs_cnt / obs_off)
     int *hdr, *cov, *kf_role, *kf_idx, *lm_nobs, *lm_sel, *lm_anchor, *lm_flag;
     unsigned long long *lm_pack, *lm_pidx;
     unsigned char *lm_new;
@@ -229,23 +233,33 @@ __global__ __launch_bounds__(256) void ms_count_kernel(const map_job *__restrict
 // Observations are appended and killed in place (tombstones), so a long sequence leaves mostly dead rows behind
 // (the reference erases them from its hash maps: src/map_manager.cpp:885-1019).  Dead rows (flag cleared, or keyframe /
 // landmark gone -- neither id is ever reused) are squeezed out by a stable scatter: the row order, and so every set-up
-// result, stays what it was.
-__global__ __launch_bounds__(256) void mc_mark_kernel(map_view M, int *__restrict__ keep)
+// result, stays what it was.  With a saved state (ov2_map_save_state), a row that is live in EITHER state is kept and the
+// saved observation flags are squeezed by the same scatter, so that ov2_map_restore_state_batch still rewinds the map.
+struct snap_view { const unsigned char *kf_state, *lm_state, *obs_flag; };   // obs_flag == nullptr: no saved state to keep
+
+__global__ __launch_bounds__(256) void mc_mark_kernel(map_view M, snap_view S, int *__restrict__ keep)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= M.n_obs) return;
     int kf, lm;
-    keep[i] = obs_live(M, i, kf, lm) ? 1 : 0;
+    bool k = obs_live(M, i, kf, lm);
+    if (!k && S.obs_flag) {
+        kf = M.obs_kf[i]; lm = M.obs_lm[i];
+        k = (S.obs_flag[i] & OBS_ALIVE) && S.kf_state[kf] && (S.lm_state[lm] & OV2_LM_ALIVE);
+    }
+    keep[i] = k ? 1 : 0;
 }
 
-struct obs_cols { int *kf, *lm, *scale; double *uv, *ruv; unsigned char *flag; };
+struct obs_cols { int *kf, *lm, *scale; double *uv, *ruv; unsigned char *flag, *snap_flag; };
 
-__global__ __launch_bounds__(256) void mc_scatter_kernel(map_view M, const int *__restrict__ keep, const int *__restrict__ pos, obs_cols O)
+__global__ __launch_bounds__(256) void mc_scatter_kernel(map_view M, const unsigned char *__restrict__ snap_flag, const int *__restrict__ keep,
+                                                         const int *__restrict__ pos, obs_cols O)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= M.n_obs || !keep[i]) return;
     const int j = pos[i];
     O.kf[j] = M.obs_kf[i]; O.lm[j] = M.obs_lm[i]; O.scale[j] = M.obs_scale[i]; O.flag[j] = M.obs_flag[i];
+    if (snap_flag) O.snap_flag[j] = snap_flag[i];
     reinterpret_cast<double2 *>(O.uv)[j] = reinterpret_cast<const double2 *>(M.obs_uv)[i];
     reinterpret_cast<double2 *>(O.ruv)[j] = reinterpret_cast<const double2 *>(M.obs_ruv)[i];
 }
@@ -314,8 +328,7 @@ __global__ __launch_bounds__(256) void ms_local_lm_kernel(const map_job *__restr
 }
 
 // observers of the local landmarks: outside keyframes become constant poses (:229-246), the first observer anchors
-// the landmark (:251-287).  The isBad() landmarks keep their oldest observer too (MapPoint::kfid_, which the culling
-// rule of the update stage reads, :810 / :871).
+// the landmark (:251-287).  (The update stage recounts observers and oldest observers from the table as it is then.)
 __global__ __launch_bounds__(256) void ms_observers_kernel(const map_job *__restrict__ J)
 {
     const map_job &j = J[blockIdx.y];
@@ -323,9 +336,7 @@ __global__ __launch_bounds__(256) void ms_observers_kernel(const map_job *__rest
     const int i = blockIdx.x * 256 + threadIdx.x;
     int kf, lm;
     if (j.hdr[MH_ABORT] || i >= M.n_obs || !obs_live(M, i, kf, lm)) return;
-    const int sel = j.lm_sel[lm];
-    if (sel == 2) { atomicMax(&j.lm_anchor[lm], ANCH_TOP - kf); return; }
-    if (sel != 1 || kf > j.hdr[MH_NMAXKF]) return;
+    if (j.lm_sel[lm] != 1 || kf > j.hdr[MH_NMAXKF]) return;
     if (j.kf_role[kf] == 0) j.kf_role[kf] = 2;     // every writer stores the same value
     atomicMax(&j.lm_anchor[lm], ANCH_TOP - kf);     // the smallest kfid wins
 }
@@ -580,24 +591,40 @@ __global__ __launch_bounds__(256) void me_all_kernel(const map_job *__restrict__
 
 // ---- update stage of Optimizer::localBA (src/optimizer.cpp:741-882) on the tables ---------------------------------
 // Inputs: the flat problem where the set-up left it (poses / landmarks now hold the solved states), the per residual block
-// outlier flags of the solve, and the set-up's scratch arrays (residual blocks per observation row, observers per
-// landmark, oldest observer per landmark), which stay valid until the map's next set-up.
+// outlier flags of the solve, and the set-up's residual blocks per observation row (obs_cnt / obs_off, rows
+// [0, last_n_obs) only).  The map may have been edited since the set-up (keyframes or observations appended, observations /
+// landmarks removed, isobs_ flipped: the other threads of the reference keep working while the solve runs); everything the
+// culling reads -- observers, oldest observer, isobs_, liveness -- is therefore read from the tables as they are NOW, as
+// the reference reads its MapPoint objects under the map lock (:789-882).
 //
-// pass 1, one thread per observation row: a flagged LEFT block removes the observation (MapManager::removeMapPointObs,
-// :753-764; an observation of the current frame also clears MapPoint::isobs_, removeObsFromCurFrameById), a flagged RIGHT
-// block demotes it to mono (Frame::removeStereoKeypointById, :743-751); both put the landmark into set_badlmids.
-__global__ __launch_bounds__(256) void mu_obs_kernel(const map_job *__restrict__ J, int inv)
+// pass 1, one thread per observation row of the set-up: a flagged LEFT block removes the observation
+// (MapManager::removeMapPointObs, :753-764; an observation of the current frame also clears MapPoint::isobs_,
+// removeObsFromCurFrameById), a flagged RIGHT block demotes it to mono (Frame::removeStereoKeypointById, :743-751); both put
+// the landmark into set_badlmids.  A row that died since the set-up is neither removed again nor reported.  The extra
+// blocks [gN, gN + gLM) clear the observer counts / oldest observer of the window's landmarks (local + isBad()) for pass 1b.
+__global__ __launch_bounds__(256) void mu_obs_kernel(const map_job *__restrict__ J, int gN, int inv)
 {
     const map_job &j = J[blockIdx.y];
     const map_view &M = j.M;
-    if (!j.outlier || j.hdr[MH_ABORT] || (int)blockIdx.x * 256 >= M.n_obs) return;   // uniform per workgroup
+    if (j.hdr[MH_ABORT]) return;
+    if ((int)blockIdx.x >= gN) {
+        const int idx = ((int)blockIdx.x - gN) * 256 + threadIdx.x, NL = j.hdr[MH_NLM], NB = j.hdr[MH_NBAD];
+        if (idx >= NL + NB) return;
+        const flat_out O = flat_of(j, inv);
+        const int l = idx < NL ? O.lm_lmid[idx] : O.bad_lmid[idx - NL];
+        j.lm_nobs[l] = 0;
+        j.lm_pack[l] = 0ull;            // free after the set-up's scan: the 64-bit oldest observer of pass 1b
+        atomicOr(&j.lm_sel[l], 16);     // counted by pass 1b
+        return;
+    }
+    if (!j.outlier || (int)blockIdx.x * 256 >= j.last_n_obs) return;   // uniform per workgroup
     __shared__ int s_cnt[2], s_base[2];
     if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     const int i = blockIdx.x * 256 + threadIdx.x;
     const flat_out O = flat_of(j, inv);
     bool left = false, right = false;
-    const int c = i < M.n_obs ? j.obs_cnt[i] : 0;
+    const int c = i < j.last_n_obs ? j.obs_cnt[i] : 0;
     if (c) {
         const int o = j.obs_off[i];
         for (int k = 0; k < c; ++k)
@@ -606,38 +633,45 @@ __global__ __launch_bounds__(256) void mu_obs_kernel(const map_job *__restrict__
                 if (t == OV2_BA_L_XYZ || t == OV2_BA_L_INV) left = true; else right = true;
             }
     }
+    int kf = 0, lm = 0;
+    const bool live = (left || right) && obs_live(M, i, kf, lm);
+    if (left || right) {
+        kf = M.obs_kf[i]; lm = M.obs_lm[i];
+        atomicOr(&j.lm_sel[lm], 4);
+        // removeObsFromCurFrameById runs whether or not the observation is still there; one observation per (keyframe,
+        // landmark) among the set-up's rows: one writer
+        if (left && kf == j.cur_kfid) j.lm_state_w[lm] = M.lm_state[lm] & ~OV2_LM_OBS;
+    }
+    const bool rm = left && live, demote = right && !left && live && (M.obs_flag[i] & OBS_STEREO);
     // the two report lists: ranks inside the workgroup from LDS counters, ONE global atomic per workgroup and list
     // (one per flagged row on the map's header line serialised the whole launch: 1.66 ms for 64 maps of 65 k rows)
-    const int rl = left ? atomicAdd(&s_cnt[0], 1) : 0, rr = right ? atomicAdd(&s_cnt[1], 1) : 0;
+    const int rl = rm ? atomicAdd(&s_cnt[0], 1) : 0, rr = demote ? atomicAdd(&s_cnt[1], 1) : 0;
     __syncthreads();
     if (threadIdx.x < 2 && s_cnt[threadIdx.x]) s_base[threadIdx.x] = atomicAdd(&j.hdr[threadIdx.x == 0 ? MH_NRM_OBS : MH_NST_OFF], s_cnt[threadIdx.x]);
     __syncthreads();
-    if (!left && !right) return;
-    const int kf = M.obs_kf[i], lm = M.obs_lm[i];
-    atomicOr(&j.lm_sel[lm], 4);
-    if (right) {
+    if (demote) {
         j.obs_flag_w[i] = M.obs_flag[i] & ~OBS_STEREO;
         O.st_off[s_base[1] + rr] = make_int2(kf, lm);
     }
-    if (left) {
+    if (rm) {
         j.obs_flag_w[i] = 0;
-        atomicSub(&j.lm_nobs[lm], 1);
         O.rm_obs[s_base[0] + rl] = make_int2(kf, lm);
-        if (kf == j.cur_kfid) j.lm_state_w[lm] = M.lm_state[lm] & ~OV2_LM_OBS;   // one observation per (keyframe, landmark): one writer
-        // the oldest observer is gone (XYZ only: an anchor observation carries no left block): MapPoint::removeKfObs moves
-        // kfid_ to the next one (src/map_point.cpp:124-126); pass 1b recounts it
-        if (j.lm_anchor[lm] == ANCH_TOP - kf) { j.lm_anchor[lm] = 0; atomicOr(&j.lm_sel[lm], 8); }
     }
 }
 
-__global__ __launch_bounds__(256) void mu_reanchor_kernel(const map_job *__restrict__ J)
+// pass 1b, one thread per row of the table as it is now (rows appended since the set-up included), after the removals:
+// live observers (MapPoint::set_kfids_.size()) and the oldest one (MapPoint::kfid_, which MapPoint::removeKfObs moves to
+// the oldest observer left, src/map_point.cpp:124-126) of the window's landmarks.  The oldest observer is packed as
+// (ANCH_TOP - kfid) << 32 | row under a 64-bit atomicMax: the row gives the new anchor's pixel (inverse depth).
+__global__ __launch_bounds__(256) void mu_recount_kernel(const map_job *__restrict__ J)
 {
     const map_job &j = J[blockIdx.y];
     const map_view &M = j.M;
     const int i = blockIdx.x * 256 + threadIdx.x;
     int kf, lm;
-    if (i >= M.n_obs || !obs_live(M, i, kf, lm)) return;
-    if (j.lm_sel[lm] & 8) atomicMax(&j.lm_anchor[lm], ANCH_TOP - kf);
+    if (j.hdr[MH_ABORT] || i >= M.n_obs || !obs_live(M, i, kf, lm) || !(j.lm_sel[lm] & 16)) return;
+    atomicAdd(&j.lm_nobs[lm], 1);
+    atomicMax(&j.lm_pack[lm], ((unsigned long long)(ANCH_TOP - kf) << 32) | (unsigned)i);
 }
 
 // rotation of the unit quaternion (x, y, z, w) applied to v, plus t: Twc * v
@@ -654,8 +688,8 @@ __device__ __forceinline__ void se3_apply(const double *T, const double *v, doub
 
 // pass 2: blocks [0, gP) write the solved poses of the non-constant keyframes (:767-786); the others take one landmark
 // each: the local landmarks (:789-853: isBad / culling / positive depth / new world point) and then, for the members of
-// set_badlmids -- the isBad() landmarks of the set-up and every landmark that lost an observation -- the second
-// culling pass (:856-882).
+// set_badlmids -- the isBad() landmarks of the set-up and every landmark that had a flagged block -- the second
+// culling pass (:856-882).  Observers and the oldest observer come from pass 1b, isobs_ / liveness from the tables now.
 __global__ __launch_bounds__(256) void mu_apply_kernel(const map_job *__restrict__ J, int gP, int inv)
 {
     const map_job &j = J[blockIdx.y];
@@ -680,8 +714,8 @@ __global__ __launch_bounds__(256) void mu_apply_kernel(const map_job *__restrict
     if (!(st & OV2_LM_ALIVE)) return;   // MapManager::getMapPoint returned nullptr
     const int nobs = j.lm_nobs[l];
     const bool isobs = st & OV2_LM_OBS;
-    const int anch = j.lm_anchor[l];
-    const int lm_kfid = anch ? ANCH_TOP - anch : -1;   // MapPoint::kfid_ = its oldest observer
+    const unsigned long long oldest = j.lm_pack[l];   // 0: no live observer left
+    const int lm_kfid = oldest ? ANCH_TOP - (int)(oldest >> 32) : -1;   // MapPoint::kfid_ = its oldest observer
     auto remove = [&]() { j.lm_state_w[l] = 0; O.rm_lm[atomicAdd(&j.hdr[MH_NRM_LM], 1)] = l; };
     auto is_bad = [&]() {   // MapPoint::isBad (src/map_point.cpp:215-234)
         if ((nobs < 2 && !isobs && (st & OV2_LM_3D)) || (nobs == 0 && !isobs)) { st &= ~OV2_LM_3D; return true; }
@@ -696,10 +730,13 @@ __global__ __launch_bounds__(256) void mu_apply_kernel(const map_job *__restrict
         if (inv) {
             const double rho = O.lm[idx], zanch = 1.0 / rho;
             if (zanch <= 0.0) { remove(); return; }
-            const int a = O.lm_anchor_pose[idx];
-            if (!M.kf_state[O.pose_kfid[a]]) { in_bad = true; have = false; }   // pkfanch == nullptr (:846-848)
+            // the landmark's anchor keyframe NOW (:822): the set-up's unless its observation went away; the solved inverse
+            // depth is applied to that keyframe's pose and pixel, as the reference does
+            const int r = (int)(oldest & 0xffffffffull), akf = oldest ? M.obs_kf[r] : -1;
+            const int a = akf >= 0 && j.kf_role[akf] ? j.kf_idx[akf] : -1;
+            if (a < 0 || !M.kf_state[akf]) { in_bad = true; have = false; }   // not in map_local_pkfs / pkfanch == nullptr (:822-848)
             else {
-                const double u = O.lm_anchor_uv[2 * idx], v = O.lm_anchor_uv[2 * idx + 1];
+                const double u = M.obs_uv[2 * r], v = M.obs_uv[2 * r + 1];
                 const double cam[3] = {zanch * (u - j.K[2]) / j.K[0], zanch * (v - j.K[3]) / j.K[1], zanch};
                 se3_apply(O.pose + 7 * a, cam, wpt);
             }
@@ -906,8 +943,14 @@ static ov2_status ensure_capacity(ov2_map *m, int need_kf, int need_lm, int need
     void *snap[] = {m->snap_kf_pose, m->snap_lm_xyz, m->snap_kf_state, m->snap_lm_state, m->snap_obs_flag};
     for (void *p : snap) if (p) (void)hipFree(p);
     m->snap_kf_pose = m->snap_lm_xyz = nullptr; m->snap_kf_state = m->snap_lm_state = m->snap_obs_flag = nullptr;
-    m->snap_kf = m->snap_lm = m->snap_obs = 0;
+    m->snap_kf = m->snap_lm = m->snap_obs = 0; m->snap_floor = 0;
     return OV2_OK;
+}
+
+// fewer than half of >= MAP_COMPACT_MIN_ROWS rows live (and, with a saved state, more than twice the rows its last squeeze kept)
+static bool squeeze_due(const ov2_map *m, long long live)
+{
+    return m->n_obs >= MAP_COMPACT_MIN_ROWS && 2 * std::max(live, (long long)m->snap_floor) < m->n_obs;
 }
 
 // squeezes the dead rows out of the observation table (stable); one synchronisation, fresh column arrays of the same capacity
@@ -919,12 +962,12 @@ static ov2_status compact_obs(ov2_map *m)
     if (N <= 0) return OV2_OK;
     // the fresh column arrays are released on every early return, kept once they have replaced the old ones
     struct fresh_cols {
-        obs_cols O = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        obs_cols O = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         bool committed = false;
         ~fresh_cols()
         {
             if (committed) return;
-            void *p[] = {O.kf, O.lm, O.scale, O.uv, O.ruv, O.flag};
+            void *p[] = {O.kf, O.lm, O.scale, O.uv, O.ruv, O.flag, O.snap_flag};
             for (void *q : p) if (q) (void)hipFree(q);
         }
     } F;
@@ -933,18 +976,22 @@ static ov2_status compact_obs(ov2_map *m)
     ov2_status s = OV2_OK;
 #define A(p, n) if (s == OV2_OK) s = dmalloc(c, &O.p, (n))
     A(kf, cap); A(lm, cap); A(scale, cap); A(uv, 2 * cap); A(ruv, 2 * cap); A(flag, cap);
+    // a saved state of exactly these rows and capacities (the only one ov2_map_restore_state_batch accepts) survives
+    const bool keep_snap = m->snap_kf_pose && m->snap_obs_flag && m->snap_obs == N && m->snap_kf == m->max_kf && m->snap_lm == m->max_lm;
+    if (keep_snap) A(snap_flag, (size_t)N);
 #undef A
     if (s != OV2_OK) return s;
     const map_view M = view_of(m);
+    const snap_view SV = {m->snap_kf_state, m->snap_lm_state, keep_snap ? m->snap_obs_flag : nullptr};
     const dim3 g((N + 255) / 256), b(256);
     job_table JT;
     if ((s = JT.begin(c, 1)) != OV2_OK) return s;
     JT.set(0, job_of(m, -1, -1));
     if ((s = JT.upload()) != OV2_OK) return s;
     OV2_HIP(c, hipMemsetAsync(O.flag, 0, cap, st));
-    OV2_LAUNCH(c, OV2_K_MAP, mc_mark_kernel, g, b, 0, st, M, m->obs_cnt);
+    OV2_LAUNCH(c, OV2_K_MAP, mc_mark_kernel, g, b, 0, st, M, SV, m->obs_cnt);
     if ((s = exclusive_scan<int>(c, JT, SC_LIVE, N)) != OV2_OK) return s;
-    OV2_LAUNCH(c, OV2_K_MAP, mc_scatter_kernel, g, b, 0, st, M, (const int *)m->obs_cnt, (const int *)m->obs_off, O);
+    OV2_LAUNCH(c, OV2_K_MAP, mc_scatter_kernel, g, b, 0, st, M, SV.obs_flag, (const int *)m->obs_cnt, (const int *)m->obs_off, O);
     OV2_HIP(c, hipMemcpyAsync(m->hdr_host, m->hdr, MH_N * sizeof(int), hipMemcpyDeviceToHost, st));
     OV2_HIP(c, hipStreamSynchronize(st));
     void *old[] = {m->obs_kf, m->obs_lm, m->obs_scale, m->obs_uv, m->obs_ruv, m->obs_flag};
@@ -955,7 +1002,13 @@ static ov2_status compact_obs(ov2_map *m)
     m->n_compactions++;
     m->last_valid = 0;   // the row indices of the last set-up's scratch arrays are gone
     m->live_rows = m->n_obs; m->live_known = 1;
-    if (m->snap_obs_flag) { (void)hipFree(m->snap_obs_flag); m->snap_obs_flag = nullptr; m->snap_obs = -1; }   // a saved state of the old rows
+    if (m->snap_obs_flag) (void)hipFree(m->snap_obs_flag);
+    if (keep_snap) {   // the saved flags, squeezed like the rows
+        m->snap_obs_flag = O.snap_flag; m->snap_obs = m->n_obs;
+        m->snap_floor = m->n_obs;   // rows that only the saved state keeps alive must not trigger a squeeze at every set-up
+    } else if (m->snap_obs_flag) {  // a saved state of other rows: it could not be restored before, it cannot now
+        m->snap_obs_flag = nullptr; m->snap_obs = -1; m->snap_floor = 0;
+    }
     return OV2_OK;
 }
 
@@ -1268,6 +1321,7 @@ ov2_status setup_pass(ov2_ctx *c, const std::vector<int> &sel, ov2_map *const *m
         ov2_map *m = maps[sel[b2]];
         memcpy(m->last_hdr, JT.hdr_host + (size_t)b2 * MH_N, MH_N * sizeof(int));
         m->last_newkf = newkf[sel[b2]]; m->last_inv = inv; m->last_valid = 1;
+        m->last_n_obs = m->n_obs; m->last_updated = 0;
         m->live_rows = m->last_hdr[MH_NLIVE]; m->live_known = 1;
     }
     return OV2_OK;
@@ -1289,7 +1343,7 @@ ov2_status setup_batch_impl(ov2_ctx *c, int B, ov2_map *const *maps, const int32
     if (squeeze_first)   // the batched form squeezes a mostly dead table BEFORE the chain: its update stage needs the row indices after it
         for (int b = 0; b < B; ++b) {
             ov2_map *m = maps[b];
-            if (m->live_known && m->n_obs >= MAP_COMPACT_MIN_ROWS && 2 * (long long)m->live_rows < m->n_obs) {
+            if (m->live_known && squeeze_due(m, m->live_rows)) {
                 const ov2_status cs = compact_obs(m);
                 if (cs != OV2_OK) return cs;
             }
@@ -1338,9 +1392,8 @@ extern "C" ov2_status ov2_map_local_ba_setup(ov2_map *m, int newkf, int nmin_cov
     ov2_status s = setup_batch_impl(c, 1, &m, &nk, nmin_covscore, nmin_cst_kfs, inv_depth ? 1 : 0, calib_l, false);
     if (s != OV2_OK) return s;
     const int *H = m->last_hdr;
-    const int N = m->n_obs;
     // mostly tombstones left: squeeze the table once this set-up has read it (amortised like a growth)
-    const bool squeeze = N >= MAP_COMPACT_MIN_ROWS && 2 * (long long)H[MH_NLIVE] < N;
+    const bool squeeze = squeeze_due(m, H[MH_NLIVE]);
     if (H[MH_ABORT]) { out->aborted = 1; return squeeze ? compact_obs(m) : OV2_OK; }
     // the host form: the arrays of the flat problem into the pinned mirror (second synchronisation)
     size_t off[FO_N];
@@ -1385,7 +1438,12 @@ extern "C" ov2_status ov2_map_local_ba_update_batch(ov2_ctx *c, int B, ov2_map *
         ov2_map *m = maps[b];
         if (!m || m->c != c) return ov2_set_err(c, OV2_ERR_INVALID, "map %d of the batch is null or belongs to another context", b);
         if (!m->last_valid)
-            return ov2_set_err(c, OV2_ERR_INVALID, "map %d: no set-up to update from (the table changed since, or none ran)", b);
+            return ov2_set_err(c, OV2_ERR_INVALID, "map %d: no set-up to update from (none ran, or the tables grew / were squeezed "
+                               "/ restored since)", b);
+        if (m->last_updated)
+            return ov2_set_err(c, OV2_ERR_INVALID, "map %d: the update stage of its last set-up has already run", b);
+        for (int q = 0; q < b; ++q)
+            if (maps[q] == m) return ov2_set_err(c, OV2_ERR_INVALID, "map %d appears twice in the batch", b);
         if (inv < 0) inv = m->last_inv;
         if (m->last_inv != inv) return ov2_set_err(c, OV2_ERR_INVALID, "the maps of a batch must share one landmark parametrisation (map %d)", b);
         if (inv && !m->have_K && !m->last_hdr[MH_ABORT])
@@ -1396,22 +1454,26 @@ extern "C" ov2_status ov2_map_local_ba_update_batch(ov2_ctx *c, int B, ov2_map *
     job_table JT;
     ov2_status s = JT.begin(c, B);
     if (s != OV2_OK) return s;
-    int nmax = 0, pmax = 0, lmax = 0;
+    int nset = 0, nnow = 0, pmax = 0, lmax = 0;
     for (int b = 0; b < B; ++b) {
         ov2_map *m = maps[b];
         map_job j = job_of(m, m->last_newkf, cur_kfid ? cur_kfid[b] : -1);
         j.outlier = d_outlier ? d_outlier[b] : nullptr;
+        j.last_n_obs = m->last_n_obs;
         JT.set(b, j);
         if (m->last_hdr[MH_ABORT]) continue;
-        nmax = std::max(nmax, m->n_obs); pmax = std::max(pmax, m->last_hdr[MH_NPOSE]);
+        nset = std::max(nset, m->last_n_obs); nnow = std::max(nnow, m->n_obs); pmax = std::max(pmax, m->last_hdr[MH_NPOSE]);
         lmax = std::max(lmax, m->last_hdr[MH_NLM] + m->last_hdr[MH_NBAD]);
     }
     if ((s = JT.upload()) != OV2_OK) return s;
-    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), b256(256);
+    // rows of the set-up (pass 1) vs rows now (pass 1b: appended rows are observers too)
+    const int gN = (nset + 255) / 256, gNow = (nnow + 255) / 256;
+    const dim3 b256(256);
     const int gP = (pmax + 255) / 256, gLM = (lmax + 255) / 256;
-    OV2_LAUNCH(c, OV2_K_MAP, mu_obs_kernel, gN, b256, 0, st, JT.dev, inv);
-    if (!inv) OV2_LAUNCH(c, OV2_K_MAP, mu_reanchor_kernel, gN, b256, 0, st, JT.dev);
+    if (gN + gLM > 0) OV2_LAUNCH(c, OV2_K_MAP, mu_obs_kernel, dim3(gN + gLM, B), b256, 0, st, JT.dev, gN, inv);
+    if (gNow > 0 && gLM > 0) OV2_LAUNCH(c, OV2_K_MAP, mu_recount_kernel, dim3(gNow, B), b256, 0, st, JT.dev);
     if (gP + gLM > 0) OV2_LAUNCH(c, OV2_K_MAP, mu_apply_kernel, dim3(gP + gLM, B), b256, 0, st, JT.dev, gP, inv);
+    for (int b = 0; b < B; ++b) maps[b]->last_updated = 1;
     if (!out) return OV2_OK;   // asynchronous: the caller did not ask for what to replay
     OV2_LAUNCH(c, OV2_K_MAP, mb_hdr_gather_kernel, dim3(1, B), dim3(64), 0, st, JT.dev);
     if ((s = JT.fetch_headers()) != OV2_OK) return s;
@@ -1454,7 +1516,7 @@ extern "C" ov2_status ov2_map_save_state(ov2_map *m)
     OV2_HIP(c, hipMemcpyAsync(m->snap_lm_state, m->lm_state, L, hipMemcpyDeviceToDevice, st));
     if (N) OV2_HIP(c, hipMemcpyAsync(m->snap_obs_flag, m->obs_flag, N, hipMemcpyDeviceToDevice, st));
     OV2_HIP(c, hipStreamSynchronize(st));
-    m->snap_kf = (int)K; m->snap_lm = (int)L; m->snap_obs = (int)N;
+    m->snap_kf = (int)K; m->snap_lm = (int)L; m->snap_obs = (int)N; m->snap_floor = 0;
     return OV2_OK;
 }
 

@@ -87,13 +87,14 @@ class DeviceMap:
         self.newkf = -1
 
     @classmethod
-    def from_problem(cls, ctx, prob, isobs="newest"):
+    def from_problem(cls, ctx, prob, isobs="newest", spare=(8, 8, 64)):
         """the map a flat BaProblem was read from: its keyframes, landmarks (at their initial world points) and
         observations.  isobs: 'all' (every MapPoint::isobs_ set, as tests/HostMap builds them), 'newest' (only the landmarks
-        the newest keyframe observes: what a live sequence looks like) or 'none'."""
+        the newest keyframe observes: what a live sequence looks like) or 'none'.  spare: capacity beyond the problem
+        (keyframes, landmarks, observation rows) before the tables have to grow."""
         kf, lm, un, st, run = observations_of(prob)
         nk, nl = len(prob.pose), len(prob.lm)
-        m = cls(ctx, nk + 8, nl + 8, len(kf) + 64)
+        m = cls(ctx, nk + spare[0], nl + spare[1], len(kf) + spare[2])
         m.prob, m.newkf = prob, nk - 1
         xyz = world_points_of(prob)
         state = np.full(nl, LM_ALIVE | LM_3D | LM_KP3D, np.uint8)
@@ -139,6 +140,29 @@ class DeviceMap:
     def remove_obs(self, kfid, lmid):
         k, l = np.ascontiguousarray(kfid, np.int32), np.ascontiguousarray(lmid, np.int32)
         _check(self.ctx.h, self.L.ov2_map_remove_obs(self.h, len(k), self._p(k), self._p(l)))
+
+    def remove_landmarks(self, lmid):
+        l = np.ascontiguousarray(lmid, np.int32)
+        _check(self.ctx.h, self.L.ov2_map_remove_landmarks(self.h, len(l), self._p(l)))
+
+    def set_isobs(self, lmid, isobs):
+        """MapPoint::isobs_ of live landmarks, the other state bits kept"""
+        l = np.ascontiguousarray(lmid, np.int32)
+        st = self.download()["lm_state"][l]
+        st = (st | LM_OBS) if isobs else (st & ~np.uint8(LM_OBS))
+        self.set_landmarks(l, None, st.astype(np.uint8))
+
+    def compact(self):
+        """ov2_map_compact: (rows before, rows after)"""
+        a, b = C.c_int(), C.c_int()
+        _check(self.ctx.h, self.L.ov2_map_compact(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def rows(self):
+        """ov2_map_obs_rows: (rows, capacity, compactions)"""
+        r, c, n = C.c_int(), C.c_int(), C.c_int()
+        _check(self.ctx.h, self.L.ov2_map_obs_rows(self.h, C.byref(r), C.byref(c), C.byref(n)))
+        return r.value, c.value, n.value
 
     def save_state(self):
         _check(self.ctx.h, self.L.ov2_map_save_state(self.h))
@@ -204,15 +228,36 @@ def problems_of(views, proto, inv_depth):
     return pcs, rcs
 
 
-def update_batch(ctx, maps, views, cur_kfid=None, want_lists=True):
-    """ov2_map_local_ba_update_batch with the outlier flags the solve left in the maps' blocks; returns per map
+def update_batch(ctx, maps, views, cur_kfid=None, want_lists=True, outliers=None):
+    """ov2_map_local_ba_update_batch with the outlier flags the solve left in the maps' blocks, or -- outliers[b], a host
+    array of n_res flags per map (None: the solve's) -- flags uploaded for the call; returns per map
     dict(removed_lmid, removed_obs (n x 2: kfid, lmid), stereo_off (n x 2)) or None (asynchronous)"""
     B = len(maps)
     hs = (C.c_void_p * B)(*[m.h for m in maps])
-    outl = (C.c_void_p * B)(*[None if v.aborted else v.res_outlier for v in views])
-    ck = None if cur_kfid is None else np.ascontiguousarray(cur_kfid, np.int32)
-    out = (UpdateC * B)() if want_lists else None
-    _check(ctx.h, ctx.lib.ov2_map_local_ba_update_batch(ctx.h, B, hs, outl, None if ck is None else ck.ctypes.data_as(C.c_void_p), out))
+    ptrs, owned = [], []
+    try:
+        for b, v in enumerate(views):
+            f = None if outliers is None else outliers[b]
+            if v.aborted or f is None:
+                ptrs.append(None if v.aborted else v.res_outlier)
+                continue
+            f = np.ascontiguousarray(f, np.uint8)
+            assert f.shape == (v.n_res,)
+            d = C.c_void_p()
+            _check(ctx.h, ctx.lib.ov2_dev_alloc(ctx.h, max(f.nbytes, 1), C.byref(d)))
+            owned.append(d)
+            if f.nbytes:
+                _check(ctx.h, ctx.lib.ov2_memcpy_h2d(ctx.h, d, f.ctypes.data_as(C.c_void_p), f.nbytes))
+            ptrs.append(d.value)
+        outl = (C.c_void_p * B)(*ptrs)
+        ck = None if cur_kfid is None else np.ascontiguousarray(cur_kfid, np.int32)
+        out = (UpdateC * B)() if want_lists else None
+        _check(ctx.h, ctx.lib.ov2_map_local_ba_update_batch(ctx.h, B, hs, outl, None if ck is None else ck.ctypes.data_as(C.c_void_p), out))
+    finally:
+        if owned:   # the update may still be reading them
+            ctx.lib.ov2_ctx_synchronize(ctx.h)
+            for d in owned:
+                ctx.lib.ov2_dev_free(ctx.h, d)
     if not want_lists:
         return None
     res = []

@@ -564,6 +564,38 @@ void MapManager::mergeMapPoints(int prevlmid, int newlmid)
 // ---------------------------------------------------------------------------------------------- device map mirror
 MapManager::~MapManager() { if (dev_) ov2_map_destroy(dev_); }
 
+static uint8_t lm_state_of(const MapManager &map, const MapPoint &lm);
+uint8_t MapManager::lmState(const MapPoint &lm) const { return lm_state_of(*this, lm); }
+
+ov2_status MapManager::addKeyframe(const std::shared_ptr<Frame> &kf)
+{
+    map_pkfs_[kf->kfid_] = kf;
+    for (const auto &kv : kf->mapkps_) {
+        auto plm = getMapPoint(kv.first);
+        if (!plm) continue;
+        for (int cokfid : plm->getKfObsSet()) {
+            auto pcokf = getKeyframe(cokfid);
+            if (pcokf && cokfid != kf->kfid_) { kf->addCovisibleKf(cokfid); pcokf->addCovisibleKf(kf->kfid_); }
+        }
+        plm->addKfObs(kf->kfid_);
+    }
+    return addKeyframeToDevice(*kf);
+}
+
+void MapManager::addMapPointKfObs(int kfid, const Keypoint &kp)
+{
+    auto pkf = getKeyframe(kfid);
+    auto plm = getMapPoint(kp.lmid_);
+    if (!pkf || !plm || pkf->isObservingKp(kp.lmid_)) return;
+    pkf->addKeypoint(kp);
+    for (int cokfid : plm->getKfObsSet()) {
+        auto pcokf = getKeyframe(cokfid);
+        if (pcokf && cokfid != kfid) { pkf->addCovisibleKf(cokfid); pcokf->addCovisibleKf(kfid); }
+    }
+    plm->addKfObs(kfid);
+    if (dev_ && dev_kfs_.count(kfid)) dev_add_obs_.emplace_back(kfid, kp.lmid_);
+}
+
 static uint8_t lm_state_of(const MapManager &map, const MapPoint &lm)
 {
     // Keypoint::is3d_ of its observations (all turned together by Frame::turnKeypoint3d): read it off the first observer

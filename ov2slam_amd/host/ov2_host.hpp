@@ -181,6 +181,13 @@ public:
     void updateFrameCovisibility(Frame &frame);   // src/map_manager.cpp:117-192: co-observation counts + the frame's local map
     void mergeMapPoints(int prevlmid, int newlmid);   // :801-882
     void setMapPointObs(int lmid);                    // :1053-1090 (the isobs_ flag; the point cloud colour is not mirrored)
+    // MapManager::addKeyframe (:621-634) for a frame whose keypoints are already in place: its observations enter the
+    // landmarks' observer sets (addMapPointKfObs, :769-799), covisibility both ways, and the mirror gets its rows
+    ov2_status addKeyframe(const std::shared_ptr<Frame> &kf);
+    // MapManager::addMapPointKfObs (:769-799): keypoint kp (of landmark kp.lmid_) joins keyframe kfid after the fact (the
+    // matchToMap / merge path); the mirror gets the row with the next flush
+    void addMapPointKfObs(int kfid, const Keypoint &kp);
+    uint8_t lmState(const MapPoint &lm) const;        // its OV2_LM_* bits as the mirror holds them
     // src/map_manager.cpp:367-611, statement by statement: priors (3D point reprojected into the right camera :398-413;
     // rectified rigs: getLineMinSAD on the coarsest level :419-436 = ov2_line_min_sad; otherwise the inverse-distance
     // weighted depth of the 3D neighbours :438-483), 3D keypoints whose map point is gone lose their observation (:414),

@@ -298,6 +298,125 @@ int ov2h_map_bad_lmids(void *p, int *out, int cap)
     return n;
 }
 
+// ---- the local BA in its three stages on the host objects, so that the map can be edited between set-up and update (the
+// reference's other threads keep working while Optimizer::localBA solves without the map lock, src/optimizer.cpp:741)
+static Keypoint make_kp(int lmid, const float *uv, int is_stereo, const float *ruv)
+{
+    Keypoint kp;
+    kp.lmid_ = lmid; kp.px_ = {uv[0], uv[1]}; kp.unpx_ = {uv[0], uv[1]}; kp.is3d_ = true;
+    kp.is_stereo_ = is_stereo != 0;
+    if (kp.is_stereo_) { kp.rpx_ = {ruv[0], ruv[1]}; kp.runpx_ = {ruv[0], ruv[1]}; }
+    return kp;
+}
+
+// solves the problem the last ov2h_local_ba_setup left, in place, as Optimizer::localBA's host branch does (robust solve +
+// flags + L2 refinement through ov2_ba_solve); outlier: n_res bytes out (may be NULL)
+int ov2h_local_ba_solve(void *p, void *ctx, int newkf, uint8_t *outlier, int *n_out1, int *n_out2)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(newkf);
+    if (!f || m->pb.aborted) return -1;
+    ov2_ba_problem pr = m->pb.view(*m->st, *f);
+    ov2_ba_options o;
+    ov2_ba_default_options(&o, m->st->robust_mono_th_);
+    o.l2_refine = m->st->apply_l2_after_robust_ ? 1 : 0;
+    std::vector<double> chi2(pr.n_res);
+    std::vector<uint8_t> depth(pr.n_res), flags(pr.n_res);
+    ov2_ba_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.chi2 = chi2.data(); r.depth_positive = depth.data(); r.outlier = flags.data();
+    const ov2_status s = ov2_ba_solve((ov2_ctx *)ctx, &pr, &o, &r);
+    if (s != OV2_OK) return (int)s;
+    if (outlier) std::copy(flags.begin(), flags.end(), outlier);
+    if (n_out1) *n_out1 = r.n_outliers_pass1;
+    if (n_out2) *n_out2 = r.n_outliers_pass2;
+    return 0;
+}
+
+// Optimizer::updateAfterLocalBA (:741-882) on that problem (its pose / lm arrays: as set up, or as ov2h_local_ba_solve left
+// them) with the given per residual block flags, against the map as it is now.  No GPU.
+int ov2h_local_ba_update(void *p, int newkf, int n_res, const uint8_t *outlier, int cur_frame_obs)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(newkf);
+    if (!f || m->pb.aborted || n_res != (int)m->pb.res_type.size() || (n_res && !outlier)) return -1;
+    ov2_ba_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.outlier = const_cast<uint8_t *>(outlier);
+    Optimizer opt(nullptr, m->st, m->map);
+    opt.updateAfterLocalBA(*f, m->pb, r, cur_frame_obs != 0);
+    return 0;
+}
+
+// a new keyframe with n observations of existing landmarks (MapManager::addKeyframe); uv / ruv: n x 2
+int ov2h_map_add_keyframe_obs(void *p, int kfid, const double *Twc7, int n, const int *lmid, const float *uv, const uint8_t *is_stereo,
+                              const float *ruv)
+{
+    HostMap *m = (HostMap *)p;
+    if (m->map->getKeyframe(kfid)) return -1;
+    auto f = std::make_shared<Frame>();
+    f->id_ = kfid; f->kfid_ = kfid;
+    f->pcalib_leftcam_ = m->cl; f->pcalib_rightcam_ = m->cr;
+    SE3 T;
+    for (int i = 0; i < 7; ++i) T.v[i] = Twc7[i];
+    f->setTwc(T);
+    for (int i = 0; i < n; ++i) {
+        if (!m->map->getMapPoint(lmid[i])) return -1;
+        f->addKeypoint(make_kp(lmid[i], uv + 2 * i, is_stereo[i], ruv + 2 * i));
+    }
+    return (int)m->map->addKeyframe(f);
+}
+
+// n more observations by the existing keyframe kfid (MapManager::addMapPointKfObs: the matchToMap / merge path)
+int ov2h_map_append_obs(void *p, int kfid, int n, const int *lmid, const float *uv, const uint8_t *is_stereo, const float *ruv)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kfid);
+    if (!f) return -1;
+    for (int i = 0; i < n; ++i) {
+        if (!m->map->getMapPoint(lmid[i]) || f->isObservingKp(lmid[i])) return -1;
+        m->map->addMapPointKfObs(kfid, make_kp(lmid[i], uv + 2 * i, is_stereo[i], ruv + 2 * i));
+    }
+    return 0;
+}
+
+// the whole host map keyed by ids, comparable with the device tables: live keyframe poses, live landmarks (point + OV2_LM_*
+// bits), live (kfid, lmid) observations (Frame::mapkps_ entries whose map point exists) with their stereo flag.  Returns
+// the three counts in n[3]; arrays are written up to their capacities (call with zero capacities for the sizes).
+int ov2h_map_export(void *p, int cap_kf, int cap_lm, int cap_obs, int *n, int *kf_id, double *kf_pose, int *lm_id, double *lm_xyz,
+                    uint8_t *lm_state, int *obs_kf, int *obs_lm, uint8_t *obs_stereo)
+{
+    HostMap *m = (HostMap *)p;
+    const MapManager &M = *m->map;
+    int nk = 0, nl = 0, no = 0;
+    for (const auto &kv : M.map_pkfs_) {
+        if (!kv.second) continue;
+        if (nk < cap_kf) {
+            kf_id[nk] = kv.first;
+            const SE3 T = kv.second->getTwc();
+            for (int i = 0; i < 7; ++i) kf_pose[7 * nk + i] = T.v[i];
+        }
+        ++nk;
+        for (const auto &kp : kv.second->mapkps_) {
+            if (!M.getMapPoint(kp.first)) continue;
+            if (no < cap_obs) { obs_kf[no] = kv.first; obs_lm[no] = kp.first; obs_stereo[no] = kp.second.is_stereo_ ? 1 : 0; }
+            ++no;
+        }
+    }
+    for (const auto &kv : M.map_plms_) {
+        if (!kv.second) continue;
+        if (nl < cap_lm) {
+            lm_id[nl] = kv.first;
+            const Vec3 x = kv.second->getPoint();
+            lm_xyz[3 * nl] = x.x; lm_xyz[3 * nl + 1] = x.y; lm_xyz[3 * nl + 2] = x.z;
+            lm_state[nl] = M.lmState(*kv.second);
+        }
+        ++nl;
+    }
+    n[0] = nk; n[1] = nl; n[2] = no;
+    return 0;
+}
+
 int ov2h_local_ba_get(void *p, int *pose_kfid, uint8_t *pose_const, double *pose, int *lm_lmid, double *lm,
                       int *lm_anchor_kfid, double *lm_anchor_uv, uint8_t *res_type, int *res_kfid, int *res_lmid,
                       double *res_uv)

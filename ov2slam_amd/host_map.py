@@ -43,6 +43,12 @@ def lib():
         L.ov2h_map_remove_landmark.argtypes = [C.c_void_p, C.c_int]
         L.ov2h_map_set_isobs.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ov2h_map_bad_lmids.argtypes = [C.c_void_p, ip, C.c_int]
+        fp = C.POINTER(C.c_float)
+        L.ov2h_local_ba_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, u8, ip, ip]
+        L.ov2h_local_ba_update.argtypes = [C.c_void_p, C.c_int, C.c_int, u8, C.c_int]
+        L.ov2h_map_add_keyframe_obs.argtypes = [C.c_void_p, C.c_int, dp, C.c_int, ip, fp, u8, fp]
+        L.ov2h_map_append_obs.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, fp, u8, fp]
+        L.ov2h_map_export.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, ip, dp, ip, dp, u8, ip, ip, u8]
         L.ov2h_local_ba_get.argtypes = [C.c_void_p, ip, u8, dp, ip, dp, ip, dp, u8, ip, ip, dp]
         L.ov2h_apply_local_ba.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, dp]
         L.ov2h_ba_worker_create.argtypes = [C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int]
@@ -235,6 +241,7 @@ class HostMap:
         rc = fn(self.h, self.newkf, C.byref(npose), C.byref(nlm), C.byref(nres))
         if rc < 0:
             raise RuntimeError(f"local BA set-up failed ({rc})")
+        self._n_res = nres.value
         return self._read_problem(rc, npose, nlm, nres)
 
     def setup_range_ba(self, kf_lo, kf_hi, kf_obs_max=2 ** 31 - 1, min_obs=0):
@@ -289,6 +296,63 @@ class HostMap:
                             _dp(out["lm_anchor_uv"]), out["res_type"].ctypes.data_as(u8), out["res_kfid"].ctypes.data_as(ip),
                             out["res_lmid"].ctypes.data_as(ip), _dp(out["res_uv"]))
         return out
+
+    # ---- Optimizer::localBA in its three stages, so that the map can be edited between set-up and update ----
+    def solve_local_ba(self, ctx):
+        """solves the problem of the last setup_local_ba() in place (Optimizer::localBA's host branch through ov2_ba_solve).
+        returns (per residual block outlier flags in the set-up's order, outliers pass 1, pass 2)"""
+        n = self._n_res
+        out, n1, n2 = np.zeros(max(n, 1), np.uint8), C.c_int(), C.c_int()
+        rc = lib().ov2h_local_ba_solve(self.h, ctx.h, self.newkf, out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(n1), C.byref(n2))
+        if rc != 0:
+            raise RuntimeError(f"local BA solve failed ({rc})")
+        return out[:n], n1.value, n2.value
+
+    def update_local_ba(self, outlier, cur_frame_obs=True):
+        """Optimizer::updateAfterLocalBA on the problem of the last setup_local_ba() (its states as set up or as
+        solve_local_ba left them) with the given flags (set-up order), against the map as it is now (CPU only)"""
+        f = np.ascontiguousarray(outlier, np.uint8)
+        rc = lib().ov2h_local_ba_update(self.h, self.newkf, len(f), f.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(cur_frame_obs)))
+        if rc != 0:
+            raise RuntimeError(f"local BA update failed ({rc})")
+
+    @staticmethod
+    def _obs_args(lmid, uv, stereo, ruv):
+        lmid = np.ascontiguousarray(lmid, np.int32)
+        n = len(lmid)
+        uv = np.ascontiguousarray(np.reshape(uv, (n, 2)), np.float32)
+        stereo = np.ascontiguousarray(np.zeros(n) if stereo is None else stereo, np.uint8)
+        ruv = np.ascontiguousarray(np.zeros((n, 2)) if ruv is None else np.reshape(ruv, (n, 2)), np.float32)
+        fp = C.POINTER(C.c_float)
+        return (n, lmid.ctypes.data_as(C.POINTER(C.c_int)), uv.ctypes.data_as(fp), stereo.ctypes.data_as(C.POINTER(C.c_uint8)),
+                ruv.ctypes.data_as(fp), (lmid, uv, stereo, ruv))
+
+    def add_keyframe_obs(self, kfid, Twc, lmid, uv, stereo=None, ruv=None):
+        """MapManager::addKeyframe: a new keyframe observing existing landmarks (uv / ruv: undistorted pixels, float)"""
+        n, pl, pu, ps, pr, _keep = self._obs_args(lmid, uv, stereo, ruv)
+        T = np.ascontiguousarray(Twc, np.float64)
+        assert lib().ov2h_map_add_keyframe_obs(self.h, int(kfid), _dp(T), n, pl, pu, ps, pr) == 0
+
+    def append_obs(self, kfid, lmid, uv, stereo=None, ruv=None):
+        """MapManager::addMapPointKfObs: observations joining an existing keyframe (the matchToMap / merge path)"""
+        n, pl, pu, ps, pr, _keep = self._obs_args(lmid, uv, stereo, ruv)
+        assert lib().ov2h_map_append_obs(self.h, int(kfid), n, pl, pu, ps, pr) == 0
+
+    def export(self):
+        """the whole map keyed by ids, as device_map.canonical_state gives a device map: ({kfid: pose}, {lmid: (xyz,
+        OV2_LM_* state)}, {(kfid, lmid): stereo flag (0 / 2)}) of the live keyframes / landmarks / observations"""
+        L, ip, u8 = lib(), C.POINTER(C.c_int), C.POINTER(C.c_uint8)
+        n = np.zeros(3, np.int32)
+        L.ov2h_map_export(self.h, 0, 0, 0, n.ctypes.data_as(ip), *([None] * 8))
+        nk, nl, no = (int(v) for v in n)
+        kid, kp, lid, lx = np.zeros(nk, np.int32), np.zeros((nk, 7)), np.zeros(nl, np.int32), np.zeros((nl, 3))
+        ls, ok, ol, os_ = np.zeros(nl, np.uint8), np.zeros(no, np.int32), np.zeros(no, np.int32), np.zeros(no, np.uint8)
+        L.ov2h_map_export(self.h, nk, nl, no, n.ctypes.data_as(ip), kid.ctypes.data_as(ip), _dp(kp), lid.ctypes.data_as(ip), _dp(lx),
+                          ls.ctypes.data_as(u8), ok.ctypes.data_as(ip), ol.ctypes.data_as(ip), os_.ctypes.data_as(u8))
+        kfs = {int(k): tuple(p) for k, p in zip(kid, kp)}
+        lms = {int(l): (tuple(x), int(s)) for l, x, s in zip(lid, lx, ls)}
+        obs = {(int(k), int(l)): 2 * int(s) for k, l, s in zip(ok, ol, os_)}
+        return kfs, lms, obs
 
     def apply_local_ba(self, ctx):
         """Estimator::applyLocalBA on the GPU. returns (status, outliers pass1, pass2, final cost)."""
