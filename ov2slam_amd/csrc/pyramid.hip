@@ -534,107 +534,148 @@ __global__ __launch_bounds__(256) void pyrdown_kernel(ov2_pyr_view pv, int l)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// level 0 (CLAHE path) AND the first pyrDown in one pass: the workgroup forms the CLAHE output of a 128 x 32 px tile
-// plus the 2-px ring the 5 x 5 binomial reaches into (36 rows x 36 dwords, columns x0-4 .. x0+139), keeps it in LDS,
+// level 0 (CLAHE path) AND the first pyrDown in one pass: the workgroup forms the CLAHE output of a 128 x 60 px tile
+// plus the 2-px ring the 5 x 5 binomial reaches into (64 rows x 34 dwords, columns x0-4 .. x0+131), keeps it in LDS,
 // writes the tile's own pixels to the level-0 plane (128-byte rows: whole lines) and then runs pyrdown_kernel's
 // arithmetic from LDS -- level 0 is not read back, one launch tail less.  Ring positions outside the image take the value
 // of their REFLECT_101 source pixel, which is what the padded plane holds there.
 // The interpolation makes ONE LDS read per pixel: for every interpolation cell the tile touches (the rectangle between
-// four neighbouring tile centres; <= 3 x 2 for EuRoC geometry) the four surrounding LUTs are interleaved into a
+// four neighbouring tile centres; <= 4 x 3 for EuRoC geometry) the four surrounding LUTs are interleaved into a
 // 256-entry table of byte quads, so a pixel value fetches all four taps with one dword read (v_cvt_f32_ubyte0..3 unpack
 // them); the per-pixel arithmetic is the expression of level0_kernel evaluated two taps at a time by the packed fp32
-// instructions (each product and sum rounded separately), so the bytes are the same.  The kernel is bound by vector
-// instruction issue, so tiles whose staged region lies inside the image and away from the plane's reflected border
-// (workgroup-uniform test) take a path without any reflect / clamp / edge-store logic, and every address is a uniform
-// base plus a 32-bit lane offset.
-template <bool INTERIOR>
-__device__ __forceinline__ void l0pd_stage(const unsigned char *__restrict__ sb, int w, int h, int sstride,
-                                           unsigned char *__restrict__ plane, int istride, int pad, float inv_tw, float inv_th,
-                                           int txA, int tyA, int ncellx, int ncelly, int x0, int y0,
-                                           unsigned int (*tile)[PD_DW], const unsigned int *quad)
-{
-    const int tid = threadIdx.x;
-    const int c = tid % PD_DW, g = tid / PD_DW;   // dword column of the staged region (252 threads busy), rows g, g + 7, ...
-    if (g >= 7) return;
-    const int x = x0 - 4 + 4 * c;
-    const bool col_live = INTERIOR || x < w + 4;          // columns further right feed no output
-    const bool col_in = INTERIOR || (x >= 0 && x + 3 < w);   // the four pixels are four consecutive source bytes
-    int xr[4];
-    unsigned cellx[4];   // byte offset of the pixel's cell column in the quad tables
+// instructions (each product and sum rounded separately), so the bytes are the same.
+// The kernel is bound by vector instruction issue, so everything that is not per pixel is hoisted out of the pixel loop:
+//   - a lane owns one dword column (4 px) for the whole tile: its reflected columns, x weights and quad-table cell
+//     offsets are computed once;
+//   - per staged row, the reflected source row, the y weights and the cell row live in a 16-byte LDS record (one per
+//     lane of each wave, the wave's own copy), read with one ds_read_b128 whose address is an immediate offset;
+//   - a wave works on row PAIRS (lanes 0-31 / 32-63 = own dword columns 1..32 of rows 2p, 2p+1), so the 30 own pairs
+//     and the 2 halo pairs are 8 per wave; the halo dword columns 0 and 33 of the 64 rows are a short pass of waves 0, 1;
+//   - edge tiles differ only in how a lane loads its four source bytes (two dwords + v_perm with a per-lane selector
+//     instead of one dword); the reflected copies of the plane border leave in a pass after the tile is complete.
+#define L0_TW 128
+#define L0_TH 60                 // even: the level-1 rows of a tile start at y0 / 2
+#define L0_ROWS (L0_TH + 4)      // staged rows y0-2 .. y0+L0_TH+1 = one row record per lane (the last row feeds nothing)
+#define L0_DW 36                 // LDS row stride in dwords (16-byte aligned rows for the pyrDown's uint4 reads); 0..33 used
+#define L0_RT_DW (4 * L0_ROWS)   // one wave's row records, dwords
+
+struct l0_cols {                 // one lane's four pixel columns
     float xa[4], xa1[4];
+    unsigned cellx[4];           // byte offset of the pixel's cell column in the quad tables
+    unsigned ws, sel;            // edge loads: 8-byte window start and the v_perm selector of the four bytes in it
+};
+
+__device__ __forceinline__ void l0_col_meta(int x, int w, float inv_tw, int txA, int ncellx, l0_cols &m)
+{
+    int xr[4], lo = w - 1;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        xr[i] = INTERIOR ? x + i : min(max(reflect101(x + i, w), 0), w - 1);
+        xr[i] = min(max(reflect101(x + i, w), 0), w - 1);
+        lo = min(lo, xr[i]);
         const float txf = (float)xr[i] * inv_tw - 0.5f;
         const float fl = floorf(txf);
-        xa[i] = txf - fl;
-        xa1[i] = 1.0f - xa[i];
-        cellx[i] = (unsigned)min(max((int)fl - txA, 0), ncellx - 1) * 1024u;
+        m.xa[i] = txf - fl;
+        m.xa1[i] = 1.0f - m.xa[i];
+        m.cellx[i] = (unsigned)min(max((int)fl - txA, 0), ncellx - 1) * 1024u;
     }
-    unsigned int raw[6];
-    {   // the source loads of all rows are in flight together
-        const int yfirst = y0 - 2 + g;
+    // the reflected bytes of a dword column that feeds an output span at most 8 bytes from their 4-aligned start; capping the
+    // start at the last full dword pair keeps both loads inside the row (the image stride is a multiple of 64 >= w).  Columns
+    // that feed nothing (far right of the last block) get clamped, in-bounds garbage.
+    m.ws = (unsigned)min(lo & ~3, ((w - 1) & ~3) - 4);
+    m.sel = 0;
 #pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const int r = g + 7 * k, y = yfirst + 7 * k;
-            raw[k] = 0;
-            if (INTERIOR) {
-                if (r < PD_ROWS) raw[k] = *reinterpret_cast<const unsigned int *>(sb + (unsigned)(y * sstride + x));
-            } else if (col_live && r < PD_ROWS && y < h + 2) {
-                const unsigned ro = (unsigned)(min(max(reflect101(y, h), 0), h - 1) * sstride);
-                if (col_in) raw[k] = *reinterpret_cast<const unsigned int *>(sb + (ro + (unsigned)x));
-                else
-                    for (int i = 0; i < 4; ++i) raw[k] |= (unsigned int)sb[ro + (unsigned)xr[i]] << (8 * i);
-            }
-        }
+    for (int i = 0; i < 4; ++i) m.sel |= ((unsigned)(xr[i] - (int)m.ws) & 7u) << (8 * i);
+}
+
+template <bool COLS_IN>
+__device__ __forceinline__ unsigned l0_load(const unsigned char *__restrict__ sb, unsigned rowoff, int x, const l0_cols &m)
+{
+    if (COLS_IN) return *reinterpret_cast<const unsigned int *>(sb + (rowoff + (unsigned)x));
+    const unsigned int *p = reinterpret_cast<const unsigned int *>(sb + (rowoff + m.ws));
+    return __builtin_amdgcn_perm(p[1], p[0], m.sel);
+}
+
+// four CLAHE pixels of one staged dword; rec = the row record (1 - ya, ya, cell row offset, source row offset)
+__device__ __forceinline__ unsigned l0_interp(unsigned raw, const l0_cols &m, uint4 rec, const unsigned char *qb)
+{
+    const v2f yw = {__uint_as_float(rec.x), __uint_as_float(rec.y)};
+    unsigned int rb[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        // ((tl xa1 + tr xa) ya1 + (bl xa1 + br xa) ya), every product and sum rounded on its own, two at a time
+        // (v_pk_mul_f32 / v_pk_add_f32); the result lies in [0, 255], so adding 2^23 leaves cvRound(res) in the
+        // low mantissa byte (round-to-nearest-even, like v_rndne)
+        const unsigned q = *reinterpret_cast<const unsigned int *>(qb + (rec.z + m.cellx[i] + 4u * ((raw >> (8 * i)) & 255u)));
+        const v2f left = {(float)(q & 255u), (float)((q >> 16) & 255u)}, right = {(float)((q >> 8) & 255u), (float)(q >> 24)};
+        const v2f xl = {m.xa1[i], m.xa1[i]}, xr2 = {m.xa[i], m.xa[i]};
+        const v2f tb = (left * xl + right * xr2) * yw;
+        rb[i] = __float_as_uint((tb.x + tb.y) + 8388608.0f);
     }
+    return __builtin_amdgcn_perm(__builtin_amdgcn_perm(rb[3], rb[2], 0x0c0c0400u),
+                                 __builtin_amdgcn_perm(rb[1], rb[0], 0x0c0c0400u), 0x05040100u);
+}
+
+// the own dword columns 1..32 of the 64 staged rows (row pairs p = wave + 4 k), own pixels stored to the level-0 plane
+template <bool COLS_IN>
+__device__ __forceinline__ void l0_rows(const unsigned char *__restrict__ sb, int w, int h, unsigned char *__restrict__ plane,
+                                        int istride, int pad, float inv_tw, int txA, int ncellx, int x0, int y0,
+                                        unsigned int (*tile)[L0_DW], const uint4 *rt, const unsigned char *qb)
+{
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int half = lane >> 5, cl = lane & 31, x = x0 + 4 * cl;
+    l0_cols m;
+    l0_col_meta(x, w, inv_tw, txA, ncellx, m);
+    const uint4 *rl = rt + 2 * wv + half;                 // row 2 p + half = 2 wv + half + 8 k
+    unsigned int raw[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) raw[k] = l0_load<COLS_IN>(sb, rl[8 * k].w, x, m);   // all rows' loads in flight together
     __syncthreads();   // quad tables complete
-    const bool own_col = c >= 1 && c <= PD_TW / 4 && (INTERIOR || x < w);
-    const unsigned char *qb = reinterpret_cast<const unsigned char *>(quad);
+    const bool xin = x < w;
+    const bool yfull = y0 + L0_TH <= h;
+    unsigned char *pl = plane + (unsigned)((y0 - 2 + pad + 2 * wv + half) * istride + OV2_LM + x);
+    unsigned int *tl = &tile[2 * wv + half][1 + cl];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const int r = g + 7 * k, y = y0 - 2 + r;
-        if (r >= PD_ROWS) break;
-        unsigned int packed = 0;
-        if (INTERIOR || (col_live && y < h + 2)) {
-            const int yr = INTERIOR ? y : min(max(reflect101(y, h), 0), h - 1);
-            const float tyf = (float)yr * inv_th - 0.5f;
-            const float fl = floorf(tyf);
-            const float ya = tyf - fl;
-            const v2f yw = {1.0f - ya, ya};
-            const unsigned celly = (unsigned)(min(max((int)fl - tyA, 0), ncelly - 1) * ncellx) * 1024u;
-            unsigned int rb[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                // ((tl xa1 + tr xa) ya1 + (bl xa1 + br xa) ya), every product and sum rounded on its own, two at a time
-                // (v_pk_mul_f32 / v_pk_add_f32); the result lies in [0, 255], so adding 2^23 leaves cvRound(res) in the
-                // low mantissa byte (round-to-nearest-even, like v_rndne)
-                const unsigned q = *reinterpret_cast<const unsigned int *>(qb + (celly + cellx[i] + 4u * ((raw[k] >> (8 * i)) & 255u)));
-                const v2f left = {(float)(q & 255u), (float)((q >> 16) & 255u)}, right = {(float)((q >> 8) & 255u), (float)(q >> 24)};
-                const v2f xl = {xa1[i], xa1[i]}, xr2 = {xa[i], xa[i]};
-                const v2f tb = (left * xl + right * xr2) * yw;
-                rb[i] = __float_as_uint((tb.x + tb.y) + 8388608.0f);
-            }
-            packed = __builtin_amdgcn_perm(__builtin_amdgcn_perm(rb[3], rb[2], 0x0c0c0400u),
-                                           __builtin_amdgcn_perm(rb[1], rb[0], 0x0c0c0400u), 0x05040100u);
-            // the tile's own pixels go to the level-0 plane
-            if (own_col && r >= 2 && r < PD_TH + 2 && (INTERIOR || y < h)) {
-                const unsigned po = (unsigned)((y + pad) * istride + OV2_LM + x);
-                if (INTERIOR) {
-                    *reinterpret_cast<unsigned int *>(plane + po) = packed;
-                } else {
-                    const int nvalid = min(4, w - x);
-                    if (nvalid == 4) *reinterpret_cast<unsigned int *>(plane + po) = packed;
-                    else for (int i = 0; i < nvalid; ++i) plane[po + i] = (unsigned char)(packed >> (8 * i));
-                    const bool yedge = (y <= pad) || (y >= h - 1 - pad);
-                    const bool xedge = (x <= pad) || (x + 3 >= w - 1 - pad);
-                    if (yedge || xedge)
-                        for (int i = 0; i < nvalid; ++i)
-                            store_reflections(plane, istride, pad, w, h, x + i, y, (unsigned char)(packed >> (8 * i)), false);
-                }
-            }
-        }
-        tile[r][c] = packed;
+    for (int k = 0; k < 8; ++k) {
+        const int p = wv + 4 * k;
+        const unsigned packed = l0_interp(raw[k], m, rl[8 * k], qb);
+        // a dword of an own column that straddles the right edge holds the reflections of columns w .. w+2 (< w + pad)
+        if (p >= 1 && p <= L0_TH / 2 && xin && (yfull || y0 - 2 + 2 * p + half < h))
+            *reinterpret_cast<unsigned int *>(pl + (unsigned)(8 * k * istride)) = packed;
+        tl[8 * k * L0_DW] = packed;
+    }
+}
+
+// the REFLECT_101 copies of the tile's own pixels in the level-0 plane's border, from the finished LDS tile: the mirrored rows
+// of own rows (dwords over the own columns) and the mirrored columns of own and mirrored rows (bytes); same targets as
+// store_reflections applied to every own pixel
+__device__ __forceinline__ void l0_border(int w, int h, unsigned char *__restrict__ plane, int istride, int pad, int x0, int y0,
+                                          const unsigned int (*tile)[L0_DW])
+{
+    const int tid = threadIdx.x;
+    const int xe = min(x0 + L0_TW, w), ye = min(y0 + L0_TH, h), nown = ye - y0;
+    const int t_lo = max(y0, 1), nT = max(min(ye - 1, pad) - t_lo + 1, 0);                  // rows -> -y
+    const int b_lo = max(y0, h - 1 - pad), nB = max(min(ye - 1, h - 2) - b_lo + 1, 0);      // rows -> 2 (h-1) - y
+    const int l_lo = max(x0, 1), nL = max(min(xe - 1, pad) - l_lo + 1, 0);
+    const int r_lo = max(x0, w - 1 - pad), nR = max(min(xe - 1, w - 2) - r_lo + 1, 0);
+    const int nmy = nT + nB, nmx = nL + nR;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (int i = tid; i < nmy * 32; i += 256) {
+        const int m = i >> 5, c = i & 31, x = x0 + 4 * c;
+        if (x >= w) continue;
+        const int ys = m < nT ? t_lo + m : b_lo + m - nT, Y = m < nT ? -ys : 2 * (h - 1) - ys;
+        *reinterpret_cast<unsigned int *>(plane + (unsigned)((Y + pad) * istride + OV2_LM + x)) = tile[ys - y0 + 2][1 + c];
+    }
+    if (nmx == 0) return;
+    // item -> (row, column) through a float reciprocal: i < 92 * 32, so floor((i + 0.5) / nmx) is exact
+    const float inv = 1.0f / (float)nmx;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (int i = tid; i < (nown + nmy) * nmx; i += 256) {
+        const int ri = (int)(((float)i + 0.5f) * inv), ci = i - ri * nmx;
+        const int m = ri - nown;
+        const int ys = m < 0 ? y0 + ri : (m < nT ? t_lo + m : b_lo + m - nT);
+        const int Y = m < 0 ? ys : (m < nT ? -ys : 2 * (h - 1) - ys);
+        const int xs = ci < nL ? l_lo + ci : r_lo + ci - nL, X = ci < nL ? -xs : 2 * (w - 1) - xs;
+        plane[(unsigned)((Y + pad) * istride + OV2_LM + X)] = reinterpret_cast<const unsigned char *>(tile[ys - y0 + 2])[xs - x0 + 4];
     }
 }
 
@@ -644,20 +685,22 @@ __global__ __launch_bounds__(256) void level0_clahe_pyrdown_kernel(const unsigne
                                                                    int tiles_y, float inv_tw, float inv_th, ov2_pyr_view pv)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned int fl[];
-    unsigned int (*tile)[PD_DW] = reinterpret_cast<unsigned int (*)[PD_DW]>(fl);   // PD_ROWS x PD_DW
-    unsigned int *quad = fl + PD_ROWS * PD_DW;                                     // cells x 256 byte quads
-    const int tid = threadIdx.x, b = blockIdx.z;
-    const int x0 = blockIdx.x * PD_TW, y0 = blockIdx.y * PD_TH;
+    unsigned int (*tile)[L0_DW] = reinterpret_cast<unsigned int (*)[L0_DW]>(fl);   // L0_ROWS x L0_DW
+    uint4 *rt_all = reinterpret_cast<uint4 *>(fl + L0_ROWS * L0_DW);              // 4 waves x L0_ROWS row records
+    unsigned int *quad = fl + L0_ROWS * L0_DW + 4 * L0_RT_DW;                      // cells x 256 byte quads
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), b = blockIdx.z;
+    const int x0 = blockIdx.x * L0_TW, y0 = blockIdx.y * L0_TH;
     const int pad = pv.pad;
-    const int xmin = max(x0 - 4, 0), xmax = min(x0 + PD_TW + 11, w - 1);
-    const int ymin = max(y0 - 2, 0), ymax = min(y0 + PD_TH + 1, h - 1);
+    const int xmin = max(x0 - 4, 0), xmax = min(x0 + L0_TW + 3, w - 1);
+    const int ymin = max(y0 - 2, 0), ymax = min(y0 + L0_TH + 1, h - 1);
     const int txA = (int)floorf((float)xmin * inv_tw - 0.5f), txB = (int)floorf((float)xmax * inv_tw - 0.5f);
     const int tyA = (int)floorf((float)ymin * inv_th - 0.5f), tyB = (int)floorf((float)ymax * inv_th - 0.5f);
     const int ncellx = txB - txA + 1, ncelly = tyB - tyA + 1;
     // ---- byte-quad tables of the cells: item = (cell, group of four values); value v -> (tl | tr << 8 | bl << 16 | br << 24)
     const unsigned char *lb = lut + (size_t)b * tiles_x * tiles_y * 256;
-    for (int i = tid; i < ncellx * ncelly * 64; i += 256) {
-        const int cell = i >> 6, v4 = i & 63;
+    // a wave per cell, a lane per value group: the cell geometry is scalar work
+    for (int cell = wv; cell < ncellx * ncelly; cell += 4) {
+        const int v4 = lane;
         const int jy = cell / ncellx, jx = cell - jy * ncellx;
         const int c1 = min(max(txA + jx, 0), tiles_x - 1), c2 = min(max(txA + jx + 1, 0), tiles_x - 1);
         const int r1 = min(max(tyA + jy, 0), tiles_y - 1), r2 = min(max(tyA + jy + 1, 0), tiles_y - 1);
@@ -673,45 +716,65 @@ __global__ __launch_bounds__(256) void level0_clahe_pyrdown_kernel(const unsigne
         o.z = __builtin_amdgcn_perm(cd_hi, ab_hi, 0x05040100u); o.w = __builtin_amdgcn_perm(cd_hi, ab_hi, 0x07060302u);
         *reinterpret_cast<uint4 *>(quad + cell * 256 + 4 * v4) = o;
     }
+    // ---- row records, lane = staged row (each wave writes and reads only its own copy: no workgroup barrier needed)
+    uint4 *rt = rt_all + wv * L0_ROWS;
+    {
+        const int yr = min(max(reflect101(y0 - 2 + lane, h), 0), h - 1);   // rows past h + 1 feed nothing: clamped garbage
+        const float tyf = (float)yr * inv_th - 0.5f;
+        const float fy = floorf(tyf);
+        const float ya = tyf - fy;
+        rt[lane] = make_uint4(__float_as_uint(1.0f - ya), __float_as_uint(ya),
+                              (unsigned)(min(max((int)fy - tyA, 0), ncelly - 1) * ncellx) * 1024u, (unsigned)(yr * sstride));
+    }
+    __builtin_amdgcn_wave_barrier();
     const ov2_level_desc L = pv.lv[0];
     const unsigned char *sb = src + sbstride * b;
     unsigned char *plane = pv.base + L.img_off + L.img_bstride * b;
-    // staged region inside the image, own pixels clear of the rows / columns whose reflections the padded plane holds
-    const bool interior = x0 - 4 >= 0 && x0 + PD_TW + 11 < w && y0 - 2 >= 0 && y0 + PD_TH + 1 < h &&
-                          x0 > pad && x0 + PD_TW - 1 < w - 1 - pad && y0 > pad && y0 + PD_TH - 1 < h - 1 - pad;
-    if (interior) l0pd_stage<true>(sb, w, h, sstride, plane, L.istride, pad, inv_tw, inv_th, txA, tyA, ncellx, ncelly, x0, y0, tile, quad);
-    else l0pd_stage<false>(sb, w, h, sstride, plane, L.istride, pad, inv_tw, inv_th, txA, tyA, ncellx, ncelly, x0, y0, tile, quad);
-    __syncthreads();
-    // ---- pyrDown of the staged tile (pyrdown_kernel's second half, l = 0)
-    const ov2_level_desc N = pv.lv[1];
-    const int gx = tid & 15, ly = tid >> 4;
-    const int xo = (x0 >> 1) + 4 * gx, yo = (y0 >> 1) + ly;
-    if (yo >= N.h || xo >= N.w) return;
-    int acc[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const uint4 q = *reinterpret_cast<const uint4 *>(&tile[2 * ly + j][2 * gx]);
-        const unsigned d0 = __builtin_amdgcn_alignbyte(q.y, q.x, 2), d2 = __builtin_amdgcn_alignbyte(q.z, q.y, 2);
-        const unsigned wts = 0x04060401u;
-        int rr[4];
-        rr[0] = (int)__builtin_amdgcn_udot4(d0, wts, (q.y >> 16) & 255u, false);
-        rr[1] = (int)__builtin_amdgcn_udot4(q.y, wts, q.z & 255u, false);
-        rr[2] = (int)__builtin_amdgcn_udot4(d2, wts, (q.z >> 16) & 255u, false);
-        rr[3] = (int)__builtin_amdgcn_udot4(q.z, wts, q.w & 255u, false);
-        const int kj = (j == 0 || j == 4) ? 1 : ((j == 2) ? 6 : 4);
-#pragma unroll
-        for (int o = 0; o < 4; ++o) acc[o] += kj * rr[o];
+    const unsigned char *qb = reinterpret_cast<const unsigned char *>(quad);
+    if (x0 + L0_TW <= w) l0_rows<true>(sb, w, h, plane, L.istride, pad, inv_tw, txA, ncellx, x0, y0, tile, rt, qb);
+    else l0_rows<false>(sb, w, h, plane, L.istride, pad, inv_tw, txA, ncellx, x0, y0, tile, rt, qb);
+    if (tid < 128) {   // waves 0, 1: halo dword columns 0 and 33 of every staged row
+        const int r = tid >> 1, side = tid & 1, x = x0 - 4 + 4 * 33 * side;
+        l0_cols m;
+        l0_col_meta(x, w, inv_tw, txA, ncellx, m);
+        const uint4 rec = rt[r];
+        tile[r][33 * side] = l0_interp(l0_load<false>(sb, rec.w, x, m), m, rec, qb);
     }
-    const unsigned outp = (unsigned)((acc[0] + 128) >> 8) | ((unsigned)((acc[1] + 128) >> 8) << 8) |
-                          ((unsigned)((acc[2] + 128) >> 8) << 16) | ((unsigned)((acc[3] + 128) >> 8) << 24);
+    __syncthreads();
+    if (x0 <= pad || x0 + L0_TW - 1 >= w - 1 - pad || y0 <= pad || y0 + L0_TH - 1 >= h - 1 - pad)
+        l0_border(w, h, plane, L.istride, pad, x0, y0, tile);
+    // ---- pyrDown of the staged tile (pyrdown_kernel's second half, l = 0): 16 groups of four outputs x 30 rows
+    const ov2_level_desc N = pv.lv[1];
     unsigned char *nplane = pv.base + N.img_off + N.img_bstride * b;
-    const unsigned no = (unsigned)((yo + pad) * N.istride + OV2_LM + xo);
-    const int nv = min(4, N.w - xo);
-    if (nv == 4) *reinterpret_cast<unsigned int *>(nplane + no) = outp;
-    else for (int o = 0; o < nv; ++o) nplane[no + o] = (unsigned char)(outp >> (8 * o));
-    const bool edge = (xo <= pad) || (xo + 3 >= N.w - 1 - pad) || (yo <= pad) || (yo >= N.h - 1 - pad);
-    if (edge)
-        for (int o = 0; o < nv; ++o) store_reflections(nplane, N.istride, pad, N.w, N.h, xo + o, yo, (unsigned char)(outp >> (8 * o)), false);
+    for (int it = tid; it < (L0_TW / 8) * (L0_TH / 2); it += 256) {
+        const int gx = it & 15, ly = it >> 4;
+        const int xo = (x0 >> 1) + 4 * gx, yo = (y0 >> 1) + ly;
+        if (yo >= N.h || xo >= N.w) continue;
+        int acc[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(&tile[2 * ly + j][2 * gx]);
+            const unsigned d0 = __builtin_amdgcn_alignbyte(q.y, q.x, 2), d2 = __builtin_amdgcn_alignbyte(q.z, q.y, 2);
+            const unsigned wts = 0x04060401u;
+            int rr[4];
+            rr[0] = (int)__builtin_amdgcn_udot4(d0, wts, (q.y >> 16) & 255u, false);
+            rr[1] = (int)__builtin_amdgcn_udot4(q.y, wts, q.z & 255u, false);
+            rr[2] = (int)__builtin_amdgcn_udot4(d2, wts, (q.z >> 16) & 255u, false);
+            rr[3] = (int)__builtin_amdgcn_udot4(q.z, wts, q.w & 255u, false);
+            const int kj = (j == 0 || j == 4) ? 1 : ((j == 2) ? 6 : 4);
+#pragma unroll
+            for (int o = 0; o < 4; ++o) acc[o] += kj * rr[o];
+        }
+        const unsigned outp = (unsigned)((acc[0] + 128) >> 8) | ((unsigned)((acc[1] + 128) >> 8) << 8) |
+                              ((unsigned)((acc[2] + 128) >> 8) << 16) | ((unsigned)((acc[3] + 128) >> 8) << 24);
+        const unsigned no = (unsigned)((yo + pad) * N.istride + OV2_LM + xo);
+        const int nv = min(4, N.w - xo);
+        if (nv == 4) *reinterpret_cast<unsigned int *>(nplane + no) = outp;
+        else for (int o = 0; o < nv; ++o) nplane[no + o] = (unsigned char)(outp >> (8 * o));
+        const bool edge = (xo <= pad) || (xo + 3 >= N.w - 1 - pad) || (yo <= pad) || (yo >= N.h - 1 - pad);
+        if (edge)
+            for (int o = 0; o < nv; ++o) store_reflections(nplane, N.istride, pad, N.w, N.h, xo + o, yo, (unsigned char)(outp >> (8 * o)), false);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -865,12 +928,12 @@ extern "C" ov2_status ov2_pyramid_build_images(ov2_ctx *c, const ov2_images *im,
     size_t fused_lds = 0;
     if (use_clahe && v.nlevels >= 2) {
         const float tw = 1.0f / inv_tw, th = 1.0f / inv_th;
-        const int cells = ((int)((float)(PD_TW + 16) / tw) + 2) * ((int)((float)(PD_TH + 4) / th) + 2);
-        fused_lds = ((size_t)PD_ROWS * PD_DW + (size_t)cells * 256) * 4;
+        const int cells = ((int)((float)(L0_TW + 16) / tw) + 2) * ((int)((float)(L0_TH + 4) / th) + 2);
+        fused_lds = ((size_t)L0_ROWS * L0_DW + 4 * L0_RT_DW + (size_t)cells * 256) * 4;
     }
     static const bool no_fused = getenv("OV2_PYR_NO_FUSED") != nullptr;   // experiments: the two-kernel path
     if (use_clahe && v.nlevels >= 2 && fused_lds <= 64 * 1024 && im->w >= 8 && im->h >= 8 && !no_fused) {
-        OV2_LAUNCH_ON(c, OV2_K_LEVEL0, sp, level0_clahe_pyrdown_kernel, dim3((im->w + PD_TW - 1) / PD_TW, (im->h + PD_TH - 1) / PD_TH, B),
+        OV2_LAUNCH_ON(c, OV2_K_LEVEL0, sp, level0_clahe_pyrdown_kernel, dim3((im->w + L0_TW - 1) / L0_TW, (im->h + L0_TH - 1) / L0_TH, B),
                       dim3(256), fused_lds, sp, im->base, im->w, im->h, im->stride, im->bstride, buf->lut, tiles_x, tiles_y, inv_tw,
                       inv_th, v);
         first_down = 1;
