@@ -534,6 +534,186 @@ __global__ __launch_bounds__(256) void pyrdown_kernel(ov2_pyr_view pv, int l)
 }
 
 // ---------------------------------------------------------------------------------------------------
+// TWO pyrDowns in one launch: level l -> l+1 -> l+2, with no hand-off between workgroups.  A workgroup owns a
+// P2_TW x P2_TH tile of level l+2 and the level-(l+1) block [2X, 2X + 2 P2_TW) x [2Y, 2Y + 2 P2_TH) under it (the blocks
+// partition level l+1).  It stages level l for that block and the ring both binomials reach into, forms level l+1 over
+// the block plus a 2-px ring in LDS (the ring is recomputed by the neighbouring workgroups), writes the block's own
+// pixels, and forms its level-(l+2) tile from LDS.  Ring positions outside level l+1 take the value of their
+// REFLECT_101 source pixel (what the padded plane holds there), copied inside LDS from the in-image part; level-l reads
+// past the padded plane clamp and feed only those positions.  Arithmetic = pyrdown_kernel's.
+//   LDS level l:   rows 4Y-6 .. 4Y+4 P2_TH+4, columns from 4X-16 (16-byte loads; 16-byte aligned in the plane)
+//   LDS level l+1: rows 2Y-2 .. 2Y+2 P2_TH+1, groups of four columns from 2X-4 (group g = columns 2X-4+4g .. +3)
+// grid (ceil(w_{l+2}/P2_TW), ceil(h_{l+2}/P2_TH), batch), 256 threads.
+static_assert(OV2_LM % 16 == 0, "pyrdown2_kernel stages 16-byte chunks from column -16 of the tile");
+#ifndef P2_TW
+#define P2_TW 32
+#endif
+#ifndef P2_TH
+#define P2_TH 16
+#endif
+#define P2_R1 (2 * P2_TH + 4)                  // level-(l+1) rows in LDS
+#define P2_G1 (P2_TW / 2 + 2)                  // level-(l+1) dword groups per LDS row (the first and last feed the ring)
+#define P2_DW1 ((P2_G1 + 3) & ~3)              // level-(l+1) LDS row stride, dwords (16-byte rows)
+#define P2_R0 (2 * P2_R1 + 3)                  // level-l rows in LDS
+#define P2_Q0 ((2 * P2_G1 + 3 + 3) / 4)        // level-l 16-byte chunks per LDS row (group g reads dwords 2g+1 .. 2g+4)
+#define P2_DW0 (4 * P2_Q0)
+
+// four pyrDown outputs, packed: q[j] = 16 bytes of source row j whose bytes 2 .. 12 are columns 2 xo - 2 .. 2 xo + 8
+__device__ __forceinline__ unsigned pyr_down4(const uint4 (&q)[5])
+{
+    int acc[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        // output o takes bytes 2 + 2o .. 6 + 2o: v_dot4_u32_u8 with (1, 4, 6, 4) on the first four, the fifth as addend
+        const unsigned d0 = __builtin_amdgcn_alignbyte(q[j].y, q[j].x, 2), d2 = __builtin_amdgcn_alignbyte(q[j].z, q[j].y, 2);
+        const unsigned wts = 0x04060401u;
+        int r[4];
+        r[0] = (int)__builtin_amdgcn_udot4(d0, wts, (q[j].y >> 16) & 255u, false);
+        r[1] = (int)__builtin_amdgcn_udot4(q[j].y, wts, q[j].z & 255u, false);
+        r[2] = (int)__builtin_amdgcn_udot4(d2, wts, (q[j].z >> 16) & 255u, false);
+        r[3] = (int)__builtin_amdgcn_udot4(q[j].z, wts, q[j].w & 255u, false);
+        const int kj = (j == 0 || j == 4) ? 1 : ((j == 2) ? 6 : 4);
+#pragma unroll
+        for (int o = 0; o < 4; ++o) acc[o] += kj * r[o];
+    }
+    return (unsigned)((acc[0] + 128) >> 8) | ((unsigned)((acc[1] + 128) >> 8) << 8) |
+           ((unsigned)((acc[2] + 128) >> 8) << 16) | ((unsigned)((acc[3] + 128) >> 8) << 24);
+}
+
+// four packed pixels at (x, y) of level N (x a multiple of 4, inside the level); the border copies leave in lds_border
+__device__ __forceinline__ void store_group(unsigned char *plane, const ov2_level_desc &N, int pad, int x, int y, unsigned v)
+{
+    unsigned char *dp = plane + (size_t)(y + pad) * N.istride + OV2_LM + x;
+    const int nv = min(4, N.w - x);
+    if (nv == 4) *reinterpret_cast<unsigned int *>(dp) = v;
+    else for (int o = 0; o < nv; ++o) dp[o] = (unsigned char)(v >> (8 * o));
+}
+
+// the REFLECT_101 copies of a block's own pixels (x0 .. x0+BW-1, y0 .. y0+bh-1, clipped to the level) in the plane's border,
+// from the block in LDS (pixel (x, y) at src[(y - y0) * sstride + x - x0]): the mirrored rows of own rows (dwords over the
+// own columns, bytes where a dword straddles the right edge), then the mirrored columns of own and mirrored rows (bytes,
+// consecutive lanes on consecutive columns of one row).  Same targets as store_reflections applied to every own pixel, in
+// a few coalesced passes instead of scattered byte stores per pixel (those cost pyrdown2_kernel 6 of its 17 us).
+template <int BW>
+__device__ __forceinline__ void lds_border(const unsigned char *src, int sstride, int w, int h, int bh, unsigned char *plane,
+                                           int istride, int pad, int x0, int y0)
+{
+    const int tid = threadIdx.x;
+    const int xe = min(x0 + BW, w), ye = min(y0 + bh, h), nown = ye - y0;
+    const int t_lo = max(y0, 1), nT = max(min(ye - 1, pad) - t_lo + 1, 0);                  // rows -> -y
+    const int b_lo = max(y0, h - 1 - pad), nB = max(min(ye - 1, h - 2) - b_lo + 1, 0);      // rows -> 2 (h-1) - y
+    const int l_lo = max(x0, 1), nL = max(min(xe - 1, pad) - l_lo + 1, 0);
+    const int r_lo = max(x0, w - 1 - pad), nR = max(min(xe - 1, w - 2) - r_lo + 1, 0);
+    const int nmy = nT + nB, nmx = nL + nR;
+    for (int i = tid; i < nmy * (BW / 4); i += 256) {
+        const int m = i / (BW / 4), c = i - m * (BW / 4), x = x0 + 4 * c;
+        if (x >= w) continue;
+        const int ys = m < nT ? t_lo + m : b_lo + m - nT, Y = m < nT ? -ys : 2 * (h - 1) - ys;
+        const unsigned char *sp = src + (ys - y0) * sstride + 4 * c;
+        unsigned char *dp = plane + (size_t)(Y + pad) * istride + OV2_LM + x;
+        if (x + 3 < w) *reinterpret_cast<unsigned int *>(dp) = *reinterpret_cast<const unsigned int *>(sp);
+        else for (int o = 0; o < w - x; ++o) dp[o] = sp[o];
+    }
+    for (int i = tid; i < (nown + nmy) * nmx; i += 256) {
+        const int ri = i / nmx, ci = i - ri * nmx;
+        const int m = ri - nown;
+        const int ys = m < 0 ? y0 + ri : (m < nT ? t_lo + m : b_lo + m - nT);
+        const int Y = m < 0 ? ys : (m < nT ? -ys : 2 * (h - 1) - ys);
+        const int xs = ci < nL ? l_lo + ci : r_lo + ci - nL, X = ci < nL ? -xs : 2 * (w - 1) - xs;
+        plane[(size_t)(Y + pad) * istride + OV2_LM + X] = src[(ys - y0) * sstride + xs - x0];
+    }
+}
+
+__global__ __launch_bounds__(256) void pyrdown2_kernel(ov2_pyr_view pv, int l)
+{
+    __shared__ __attribute__((aligned(16))) unsigned int t0[P2_R0][P2_DW0];
+    __shared__ __attribute__((aligned(16))) unsigned int t1[P2_R1][P2_DW1];
+    __shared__ __attribute__((aligned(16))) unsigned int t2[P2_TH][P2_TW / 4];   // the level-(l+2) tile, for its border
+    const int tid = threadIdx.x, b = blockIdx.z;
+    const int X = blockIdx.x * P2_TW, Y = blockIdx.y * P2_TH;
+    const ov2_level_desc L = pv.lv[l], N = pv.lv[l + 1], M = pv.lv[l + 2];
+    const int pad = pv.pad;
+    const unsigned char *img = pv.base + L.img_off + L.img_bstride * b;
+    // all of a thread's loads in flight together (a guarded load per trip made each trip wait for the previous one): the
+    // last trip's surplus threads repeat the last chunk, the same bytes to the same place
+    constexpr int NLD = (P2_R0 * P2_Q0 + 255) / 256;
+    uint4 ld[NLD];
+    int lo[NLD];
+#pragma unroll
+    for (int k = 0; k < NLD; ++k) {
+        const int i = min(tid + 256 * k, P2_R0 * P2_Q0 - 1);
+        const int r = i / P2_Q0, c = i - r * P2_Q0;
+        const int row = min(max(4 * Y - 6 + r + pad, 0), L.h + 2 * pad - 1);          // pad < 6: the top ring clamps
+        const int q = min((OV2_LM + 4 * X - 16) / 16 + c, L.istride / 16 - 1);        // tiles hanging over the right edge
+        ld[k] = *reinterpret_cast<const uint4 *>(img + (size_t)row * L.istride + 16 * q);
+        lo[k] = r * P2_DW0 + 4 * c;
+    }
+#pragma unroll
+    for (int k = 0; k < NLD; ++k) *reinterpret_cast<uint4 *>(&t0[0][0] + lo[k]) = ld[k];
+    __syncthreads();
+    // ---- level l+1 over the block and its ring; the block's own groups (1 .. P2_TW/2, rows 2 .. 2 P2_TH+1) also to HBM
+    unsigned char *nplane = pv.base + N.img_off + N.img_bstride * b;
+    for (int it = tid; it < P2_R1 * P2_G1; it += 256) {
+        const int r = it / P2_G1, g = it - r * P2_G1;
+        uint4 q[5];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const unsigned int *p = &t0[2 * r + j][2 * g + 1];
+            q[j] = make_uint4(p[0], p[1], p[2], p[3]);
+        }
+        const unsigned v = pyr_down4(q);
+        t1[r][g] = v;
+        const int x1 = 2 * X - 4 + 4 * g, y1 = 2 * Y - 2 + r;
+        if (g >= 1 && g <= P2_TW / 2 && r >= 2 && r < 2 + 2 * P2_TH && x1 < N.w && y1 < N.h) store_group(nplane, N, pad, x1, y1, v);
+    }
+    __syncthreads();
+    // the level-(l+1) border copies of the block's own pixels (reads own pixels only: no barrier against the pass below)
+    if (2 * X <= pad || 2 * X + 2 * P2_TW - 1 >= N.w - 1 - pad || 2 * Y <= pad || 2 * Y + 2 * P2_TH - 1 >= N.h - 1 - pad)
+        lds_border<2 * P2_TW>(reinterpret_cast<const unsigned char *>(&t1[2][1]), 4 * P2_DW1, N.w, N.h, 2 * P2_TH, nplane, N.istride,
+                              pad, 2 * X, 2 * Y);
+    // ---- ring positions outside level l+1 (columns -2, -1, w, w+1 over the LDS rows; rows -2, -1, h, h+1 over the LDS
+    // columns) <- their REFLECT_101 source pixel.  Every source lies inside the level and inside this block's LDS region
+    // (2X <= w - 1, so w - 3 >= 2X - 2), and no source is a target: one pass.
+    if (X == 0 || 2 * X + 2 * P2_TW + 2 > N.w || Y == 0 || 2 * Y + 2 * P2_TH + 2 > N.h) {   // workgroup-uniform
+        unsigned char *b1 = reinterpret_cast<unsigned char *>(&t1[0][0]);
+        const int xlo = 2 * X - 2, xhi = 2 * X + 2 * P2_TW + 1, ylo = 2 * Y - 2, yhi = 2 * Y + 2 * P2_TH + 1;   // needed ring
+        for (int i = tid; i < 4 * P2_R1 + 4 * 4 * P2_G1; i += 256) {
+            int x1, y1;
+            if (i < 4 * P2_R1) {
+                const int k = i / P2_R1;
+                y1 = ylo + (i - k * P2_R1);
+                x1 = k < 2 ? k - 2 : N.w + k - 2;
+            } else {
+                const int j = i - 4 * P2_R1, k = j / (4 * P2_G1);
+                x1 = 2 * X - 4 + (j - k * 4 * P2_G1);
+                y1 = k < 2 ? k - 2 : N.h + k - 2;
+            }
+            if (x1 < max(xlo, -2) || x1 > min(xhi, N.w + 1) || y1 < max(ylo, -2) || y1 > min(yhi, N.h + 1)) continue;
+            const int rx = reflect101(x1, N.w), ry = reflect101(y1, N.h);
+            b1[(y1 - ylo) * 4 * P2_DW1 + x1 - (2 * X - 4)] = b1[(ry - ylo) * 4 * P2_DW1 + rx - (2 * X - 4)];
+        }
+        __syncthreads();
+    }
+    // ---- level l+2: P2_TW / 4 groups of four outputs x P2_TH rows
+    unsigned char *mplane = pv.base + M.img_off + M.img_bstride * b;
+    for (int it = tid; it < (P2_TW / 4) * P2_TH; it += 256) {
+        const int gx = it % (P2_TW / 4), ly = it / (P2_TW / 4);
+        const int xo = X + 4 * gx, yo = Y + ly;
+        if (yo >= M.h || xo >= M.w) continue;
+        uint4 q[5];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) q[j] = *reinterpret_cast<const uint4 *>(&t1[2 * ly + j][2 * gx]);
+        const unsigned v = pyr_down4(q);
+        t2[ly][gx] = v;
+        store_group(mplane, M, pad, xo, yo, v);
+    }
+    if (X <= pad || X + P2_TW - 1 >= M.w - 1 - pad || Y <= pad || Y + P2_TH - 1 >= M.h - 1 - pad) {   // workgroup-uniform
+        __syncthreads();
+        lds_border<P2_TW>(reinterpret_cast<const unsigned char *>(&t2[0][0]), P2_TW, M.w, M.h, P2_TH, mplane, M.istride, pad, X, Y);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // level 0 (CLAHE path) AND the first pyrDown in one pass: the workgroup forms the CLAHE output of a 128 x 60 px tile
 // plus the 2-px ring the 5 x 5 binomial reaches into (64 rows x 34 dwords, columns x0-4 .. x0+131), keeps it in LDS,
 // writes the tile's own pixels to the level-0 plane (128-byte rows: whole lines) and then runs pyrdown_kernel's
@@ -947,7 +1127,15 @@ extern "C" ov2_status ov2_pyramid_build_images(ov2_ctx *c, const ov2_images *im,
     }
     // pyrDown chain only: the gradient planes are written when a consumer asks for them (ov2_pyr_need_grad)
     { std::lock_guard<std::mutex> g(c->mu); buf->grad_built = false; }
-    for (int l = first_down; l + 1 < v.nlevels; ++l) {
+    // two levels per launch while two are left, then one; OV2_PYR_ONE_LEVEL (experiments): one level per launch throughout
+    static const bool one_level = getenv("OV2_PYR_ONE_LEVEL") != nullptr;
+    int l = first_down;
+    for (; !one_level && l + 2 < v.nlevels; l += 2) {
+        const ov2_level_desc &M = v.lv[l + 2];
+        OV2_LAUNCH_ON(c, OV2_K_LEVEL, sp, pyrdown2_kernel, dim3((M.w + P2_TW - 1) / P2_TW, (M.h + P2_TH - 1) / P2_TH, B), dim3(256), 0,
+                      sp, v, l);
+    }
+    for (; l + 1 < v.nlevels; ++l) {
         const ov2_level_desc &L = v.lv[l];
         OV2_LAUNCH_ON(c, OV2_K_LEVEL, sp, pyrdown_kernel, dim3((L.w + PD_TW - 1) / PD_TW, (L.h + PD_TH - 1) / PD_TH, B), dim3(256), 0, sp,
                       v, l);
