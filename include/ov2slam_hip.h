@@ -60,7 +60,8 @@ ov2_status ov2_timer_stop(ov2_ctx *ctx, float *elapsed_ms);   /* synchronises on
 ov2_status ov2_ktime_enable(ov2_ctx *ctx, int on);
 ov2_status ov2_ktime_report(ov2_ctx *ctx, int max_kernels, const char **names, double *total_ms,
                             long long *launches, int *n_out);
-/* raw device memory for callers that keep keypoints resident (C++ hosts without torch) */
+/* raw device memory for callers that keep keypoints resident (C++ hosts without torch); handed out zeroed (the call
+ * synchronises ctx's stream) */
 ov2_status ov2_dev_alloc(ov2_ctx *ctx, size_t bytes, void **dptr);
 ov2_status ov2_dev_free(ov2_ctx *ctx, void *dptr);
 ov2_status ov2_memcpy_h2d(ov2_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes);  /* sync */
@@ -368,6 +369,45 @@ ov2_status ov2_pnp_solve_batch_dev(ov2_ctx *ctx, int B, const int32_t *d_off, co
                                    int32_t *d_success, int32_t *d_iters);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Per-frame epipolar filter: 5-point RANSAC between the last keyframe and the current frame + the Sampson gate.
+ * Replaces MultiViewGeometry::compute5ptEssentialMatrix -> opengv5ptEssentialMatrix (src/multi_view_geometry.cpp:594-697,
+ * OpenGV Ransac<CentralRelativePoseSacProblem>, NISTER, probability 0.99) and the stereo gate of
+ * VisualFrontEnd::epipolar2d2dFiltering (src/visual_front_end.cpp:611-648: computeFundamentalMat12 :824-838,
+ * computeSampsonDistance :798-813), called per frame between kltTracking and computePose (:93).
+ * B independent frames per call, one workgroup each; frame b owns n_pairs[b] consecutive pairs and n_gate[b] consecutive
+ * gate points.  All pointers are HOST pointers; one synchronisation.
+ *   bv_kf, bv_cur  sum(n) x 3    bearing vectors of the keyframe / current frame (f1 / f2 of OpenGV)
+ *   gate_unpx_kf, gate_unpx_cur  sum(n_gate) x 2  undistorted pixels of the 2D keypoints the gate tests (n_gate NULL = none)
+ *   K       B x 4   fx fy cx cy; the RANSAC threshold is 2 (1 - cos(atan(errth / focal))) with focal = (fx + fy) / 2 and the
+ *                   quotient in float, atan / cos in double
+ *   seed    B       one 64-bit sampler seed per frame
+ *   R_kfc   B x 9, t_kfc B x 3   the model [R12 | t12] (X_kf = R X_cur + t), t of unit length; written when status >= 1
+ *   outlier sum(n)  1 = not within the threshold of the model (voutliersidx as a mask); written when status >= 1, else 0
+ *   gate_bad sum(n_gate)  1 = Sampson distance > errth under F = K^-T [t]x R K^-1; written when status == 2, else 0
+ *   status  B       0: the reference's false (< 8 pairs, no model, < 10 inliers); 1: a model with > 0.5 n outliers (nothing
+ *                   removed, :580); 2: applied
+ *   info    B x 4   (may be NULL) OpenGV iterations, skipped draws, index of the chosen draw (-1 = none), inlier count
+ * Deviations: OpenGV's sampler is not reproduced (the reference seeds it from the clock).  Draw d of a frame takes its 5
+ * distinct indices from h(seed, d, j), j = 0, 1, ... (a duplicate is redrawn; after 256 attempts the smallest unused index):
+ *   mix(z) = SplitMix64 finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31)
+ *   a = mix(seed + G (d + 1)), x = mix(a + G (j + 1)), G = 0x9E3779B97F4A7C15, index = ((x >> 32) * n) >> 32
+ * (64-bit wrapping arithmetic).  Candidates of one sample whose summed scores are within 1e-9 of the lowest are broken
+ * by the larger trace of R; t is returned of unit length.  Mono do_optimize (OpenGV's nonlinear refinement) is not built.
+ * nmaxiter outside [0, OV2_EPI_MAX_ITER] is OV2_ERR_INVALID (a launch evaluates at most 11 nmaxiter + 1 draws). */
+#define OV2_EPI_MAX_ITER (1 << 24)
+ov2_status ov2_epipolar_filter_batch(ov2_ctx *ctx, int B, const int *n_pairs, const double *bv_kf, const double *bv_cur,
+                                     const int *n_gate, const float *gate_unpx_kf, const float *gate_unpx_cur,
+                                     const double *K, int nmaxiter, float errth, const uint64_t *seed, double *R_kfc,
+                                     double *t_kfc, uint8_t *outlier, uint8_t *gate_bad, int *status, int *info);
+/* device-resident, asynchronous form: d_off / d_gate_off = B + 1 prefix offsets (d_gate_off NULL = no gate points), every
+ * other array as above but in HBM.  Nothing is synchronised. */
+ov2_status ov2_epipolar_filter_batch_dev(ov2_ctx *ctx, int B, const int32_t *d_off, const double *d_bv_kf,
+                                         const double *d_bv_cur, const int32_t *d_gate_off, const float *d_gate_unpx_kf,
+                                         const float *d_gate_unpx_cur, const double *d_K, int nmaxiter, float errth,
+                                         const uint64_t *d_seed, double *d_R_kfc, double *d_t_kfc, uint8_t *d_outlier,
+                                         uint8_t *d_gate_bad, int32_t *d_status, int32_t *d_info);
+
+/* ---------------------------------------------------------------------------------------------------
  * Pose graphs: Optimizer::localPoseGraph (src/optimizer.cpp:2346-2592, the loop closer's chain of
  * keyframes loop .. new + the loop edge) and Optimizer::fullPoseGraph (:2783-2870, the chain of all frames between
  * constant keyframes at the end of a run) = LeftSE3RelativePoseError (src/ceres_parametrization.cpp:30-102,
@@ -649,6 +689,10 @@ ov2_status ov2_match_to_map(ov2_ctx *ctx, const ov2_match_input *in, float fmaxp
  * a wave loads 16 bytes from a different row): a known byte count to calibrate rocprofv3's FETCH_SIZE on that pattern
  * (scripts/fetch_calib.sh).  d_out: nrows words.  Asynchronous. */
 ov2_status ov2_dbg_rowload16(ov2_ctx *ctx, const void *d_buf, size_t stride_bytes, size_t nrows, uint32_t *d_out);
+
+/* Runs the device 5-point solver of ov2_epipolar_filter_batch on n given samples: bv1, bv2 n x 5 x 3 (host), E n x 10 x 9
+ * (host, row-major, ||E||_F = 1, bv1^T E bv2 = 0 on the sample; rows past nsol[i] are zero), nsol n.  Synchronous. */
+ov2_status ov2_dbg_fivept(ov2_ctx *ctx, int n, const double *bv1, const double *bv2, double *E, int *nsol);
 
 #ifdef __cplusplus
 }

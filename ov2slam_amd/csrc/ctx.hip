@@ -178,6 +178,10 @@ extern "C" ov2_status ov2_dev_alloc(ov2_ctx *c, size_t bytes, void **dptr)
     OV2_HIP(c, hipSetDevice(c->device));
     hipError_t e = hipMalloc(dptr, bytes ? bytes : 1);
     if (e != hipSuccess) return ov2_set_err(c, OV2_ERR_NOMEM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
+    // handed out zeroed: memory the process freed earlier comes back with its old contents otherwise, and rows a kernel
+    // leaves unwritten (a detector's output past its count) would depend on what ran before
+    OV2_HIP(c, hipMemsetAsync(*dptr, 0, bytes ? bytes : 1, c->stream));
+    OV2_HIP(c, hipStreamSynchronize(c->stream));
     return OV2_OK;
 }
 
@@ -303,7 +307,8 @@ const char *ov2_kernel_names[OV2_K_MAX] = {"clahe_lut_kernel", "level0_kernel", 
                                            nullptr, nullptr, "detect_cell_kernels", "detect_mask_kernel", "subpix_kernel",
                                            "pnp_kernel", "klt_compact_kernel",
                                            "detect_list_kernels", "map_setup_kernels", "tri_kernel", "stereo_sad_kernel",
-                                           "stereo_gate_kernel", "brief_kernel", "match_kernels", "pose_graph_kernel"};
+                                           "stereo_gate_kernel", "brief_kernel", "match_kernels", "pose_graph_kernel",
+                                           "epipolar_kernel", "fivept_dbg_kernel"};
 
 static hipEvent_t ktime_event(ov2_ctx *c)
 {

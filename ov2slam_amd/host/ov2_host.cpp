@@ -945,6 +945,111 @@ bool MultiViewGeometry::ceresPnP(ov2_ctx *ctx, const std::vector<Vec2> &vunkps, 
     return ok != 0;
 }
 
+bool MultiViewGeometry::compute5ptEssentialMatrix(ov2_ctx *ctx, const std::vector<Vec3> &bvs1, const std::vector<Vec3> &bvs2,
+                                                  int nmaxiter, float errth, bool boptimize, uint64_t seed, float fx, float fy,
+                                                  double Rwc[9], double twc[3], std::vector<int> &voutliersidx, ov2_status *st)
+{   // src/multi_view_geometry.cpp:596-697
+    if (st) *st = OV2_OK;
+    if (boptimize) { if (st) *st = OV2_ERR_UNSUPPORTED; return false; }   // optimizeModelCoefficients (:676-683) is not built
+    if (bvs1.size() != bvs2.size()) return false;                         // the reference asserts (:622)
+    const int n = (int)bvs1.size();
+    const double K[4] = {fx, fy, 0., 0.};
+    std::vector<uint8_t> out((size_t)n + 1);
+    int status = 0;
+    const ov2_status s = ov2_epipolar_filter_batch(ctx, 1, &n, n ? &bvs1[0].x : nullptr, n ? &bvs2[0].x : nullptr, nullptr,
+                                                   nullptr, nullptr, K, nmaxiter, errth, &seed, Rwc, twc, out.data(), nullptr,
+                                                   &status, nullptr);
+    if (s != OV2_OK) { if (st) *st = s; return false; }
+    if (status < 1) return false;   // < 8 pairs, no model or < 10 inliers (:665)
+    for (int i = 0; i < n; ++i)
+        if (out[i]) voutliersidx.push_back(i);
+    return true;
+}
+
+ov2_status VisualFrontEnd::epipolar2d2dFiltering(EpiStats *stats)
+{   // src/visual_front_end.cpp:446-655
+    if (stats) *stats = EpiStats();
+    auto pkf = pmap_->getKeyframe(pcurframe_->kfid_);                    // :452-457 (the reference exits)
+    if (!pkf) return OV2_ERR_INVALID;
+    const size_t nbkps = pcurframe_->nbkps_;
+    if (nbkps < 8) return OV2_OK;                                        // :462-466
+    const SlamParams &S = *pslamstate_;
+    const bool epifrom3dkps = S.stereo_ && pcurframe_->nb3dkps_ > 30;   // :484-487
+    double Rkfw[9], Rwcur[9], Rkfcur[9];                                 // :490
+    pkf->getTcw().rotation(Rkfw);
+    pcurframe_->getTwc().rotation(Rwcur);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Rkfcur[3 * i + j] = Rkfw[3 * i] * Rwcur[j] + Rkfw[3 * i + 1] * Rwcur[3 + j] + Rkfw[3 * i + 2] * Rwcur[6 + j];
+    // the reference walks its unordered_map; ascending lmids make the pair order (and so the sampler's draws) defined
+    std::vector<int> order;
+    for (const auto &it : pcurframe_->mapkps_) order.push_back(it.first);
+    std::sort(order.begin(), order.end());
+    std::vector<Vec3> vkfbvs, vcurbvs;
+    std::vector<int> vkpsids;
+    size_t nbparallax = 0;
+    float avg_parallax = 0.f;
+    for (const int lmid : order) {                                       // :493-519
+        const Keypoint &kp = pcurframe_->mapkps_.at(lmid);
+        if (epifrom3dkps && !kp.is3d_) continue;
+        const Keypoint kfkp = pkf->getKeypointById(kp.lmid_);
+        if (kfkp.lmid_ != kp.lmid_) continue;
+        vkfbvs.push_back(kfkp.bv_);
+        vcurbvs.push_back(kp.bv_);
+        vkpsids.push_back(kp.lmid_);
+        const Vec3 b{Rkfcur[0] * kp.bv_.x + Rkfcur[1] * kp.bv_.y + Rkfcur[2] * kp.bv_.z,
+                     Rkfcur[3] * kp.bv_.x + Rkfcur[4] * kp.bv_.y + Rkfcur[5] * kp.bv_.z,
+                     Rkfcur[6] * kp.bv_.x + Rkfcur[7] * kp.bv_.y + Rkfcur[8] * kp.bv_.z};
+        const Vec3 px = pkf->pcalib_leftcam_->projectCamToImage(b);
+        const float dx = (float)px.x - kfkp.unpx_.x, dy = (float)px.y - kfkp.unpx_.y;   // cv::Point2f difference
+        avg_parallax = (float)((double)avg_parallax + std::sqrt((double)dx * dx + (double)dy * dy));   // float += cv::norm
+        nbparallax++;
+    }
+    if (nbkps < 8) return OV2_OK;                                        // :521-525, a repeat of the first test (kept as written)
+    avg_parallax /= (float)nbparallax;                                   // :528
+    if (avg_parallax < 2. * S.fransac_err_) return OV2_OK;               // :530-535
+    if (S.mono_ && pmap_->map_pkfs_.size() > 2 && pcurframe_->nb3dkps_ < 30)   // do_optimize (:537-544): not built
+        return OV2_ERR_UNSUPPORTED;
+    // the Sampson gate of :611-648 rides in the same launch: every 2D keypoint with the keyframe's keypoint of the same id
+    // (a default Keypoint, unpx (0, 0), where the keyframe lacks it -- the reference's getKeypointById)
+    std::vector<float> gkf, gcur;
+    std::vector<int> vgateids;
+    if (epifrom3dkps)
+        for (const int lmid : order) {
+            const Keypoint &kp = pcurframe_->mapkps_.at(lmid);
+            if (kp.is3d_) continue;
+            const Keypoint kfkp = pkf->getKeypointById(kp.lmid_);
+            gkf.push_back(kfkp.unpx_.x); gkf.push_back(kfkp.unpx_.y);
+            gcur.push_back(kp.unpx_.x); gcur.push_back(kp.unpx_.y);
+            vgateids.push_back(kp.lmid_);
+        }
+    const CameraCalibration &c = *pcurframe_->pcalib_leftcam_;
+    const double K[4] = {c.fx_, c.fy_, c.cx_, c.cy_};
+    uint64_t seed = S.epi_seed_;
+    if (S.bdo_random_) {   // a different stream per frame, reproducible from (epi_seed_, frame id)
+        uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)(int64_t)pcurframe_->id_ + 1);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        seed = z ^ (z >> 31);
+    }
+    const int n = (int)vkfbvs.size(), ng = (int)vgateids.size();
+    std::vector<uint8_t> out((size_t)n + 1), bad((size_t)ng + 1);
+    double R[9], t[3];
+    int status = 0;
+    const ov2_status s = ov2_epipolar_filter_batch(ctx_, 1, &n, n ? &vkfbvs[0].x : nullptr, n ? &vcurbvs[0].x : nullptr, &ng,
+                                                   ng ? gkf.data() : nullptr, ng ? gcur.data() : nullptr, K, S.nransac_iter_,
+                                                   S.fransac_err_, &seed, R, t, out.data(), bad.data(), &status, nullptr);
+    if (s != OV2_OK) return s;
+    if (stats) { stats->status = status; stats->pairs = n; }
+    if (status < 2) return OV2_OK;                                       // no model (:573-578) / too many outliers (:580-585)
+    int removed = 0, gate_removed = 0;
+    for (int i = 0; i < n; ++i)                                          // :587-590
+        if (out[i]) { pmap_->removeObsFromCurFrameById(vkpsids[i]); ++removed; }
+    for (int i = 0; i < ng; ++i)                                         // :641-643
+        if (bad[i]) { pmap_->removeObsFromCurFrameById(vgateids[i]); ++gate_removed; }
+    if (stats) { stats->removed = removed; stats->gate_removed = gate_removed; }
+    return OV2_OK;
+}
+
 ov2_status VisualFrontEnd::computePose()
 {   // src/visual_front_end.cpp:657-830
     const size_t nb3dkps = pcurframe_->nb3dkps_;

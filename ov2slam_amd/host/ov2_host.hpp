@@ -232,6 +232,13 @@ struct SlamParams {   // the subset of include/slam_params.hpp the path reads (Y
     double dmaxquality_ = 0.001;
     int nfast_th_ = 10;
     float finit_parallax_ = 20.f, fmax_reproj_err_ = 3.f;
+    // epipolar filter (src/slam_params.cpp:97,138-143): doepipolar_ above stays false by default; every parameter file sets
+    // doepipolar: 1, nransac_iter: 100, fransac_err: 3., bdo_random: 1.  epi_seed_: base seed of the sampler (bdo_random_
+    // mixes it with the frame id, otherwise every call uses it as is)
+    int nransac_iter_ = 100;
+    float fransac_err_ = 3.f;
+    bool bdo_random_ = true;
+    uint64_t epi_seed_ = 0;
 };
 
 struct Vec2 {
@@ -245,6 +252,17 @@ public:
                          const std::vector<int> &vscales, SE3 &Twc, int nmaxiter, float chi2th, bool buse_robust,
                          bool bapply_l2_after_robust, float fx, float fy, float cx, float cy,
                          std::vector<int> &voutliersidx);
+    // src/multi_view_geometry.cpp:596-697 (OpenGV 5-point RANSAC) through ov2_epipolar_filter_batch with B = 1: bvs1 = keyframe
+    // bearings, bvs2 = current-frame bearings; Rwc / twc = [R12 | t12], t of unit length.  boptimize (OpenGV's nonlinear
+    // refinement) is not built: *st = OV2_ERR_UNSUPPORTED.  The sampler seed replaces the reference's bdorandom clock seed.
+    static bool compute5ptEssentialMatrix(ov2_ctx *ctx, const std::vector<Vec3> &bvs1, const std::vector<Vec3> &bvs2,
+                                          int nmaxiter, float errth, bool boptimize, uint64_t seed, float fx, float fy,
+                                          double Rwc[9], double twc[3], std::vector<int> &voutliersidx, ov2_status *st);
+};
+
+struct EpiStats {   // what VisualFrontEnd::epipolar2d2dFiltering did on the last frame
+    int status = -1;         // -1 not run / returned before the RANSAC; else the ov2_epipolar_filter_batch status 0 / 1 / 2
+    int pairs = 0, removed = 0, gate_removed = 0;
 };
 
 // owning handle of an ov2_pyr (the std::vector<cv::Mat> pyramid of the reference)
@@ -290,7 +308,7 @@ private:
     std::vector<Point2f> detect(const Pyramid &pyr, int ncellsize, int mode, const std::vector<Point2f> &vcurkps, const int roi[4]);
 };
 
-class VisualFrontEnd {   // src/visual_front_end.cpp (preprocessImage + kltTracking)
+class VisualFrontEnd {   // src/visual_front_end.cpp (preprocessImage, kltTracking, epipolar2d2dFiltering, computePose)
 public:
     VisualFrontEnd(ov2_ctx *ctx, std::shared_ptr<SlamParams> pstate, std::shared_ptr<Frame> pframe,
                    std::shared_ptr<MapManager> pmap, std::shared_ptr<FeatureTracker> ptracker)
@@ -300,6 +318,9 @@ public:
     // :657-830 without the P3P-RANSAC branch (OpenGV, out of scope): when P3P is required (bp3preq_ or dop3p_) the
     // call returns OV2_ERR_UNSUPPORTED and leaves the frame untouched.
     ov2_status computePose();
+    // :446-655, one ov2_epipolar_filter_batch call (RANSAC + the Sampson gate of the 2D keypoints in the same launch); pairs
+    // in ascending lmid order.  The mono do_optimize branch (:537-544, :590-608) returns OV2_ERR_UNSUPPORTED.
+    ov2_status epipolar2d2dFiltering(EpiStats *stats = nullptr);
     bool bp3preq_ = false;
     Pyramid prev_pyr_, cur_pyr_;
     ov2_ctx *ctx_;

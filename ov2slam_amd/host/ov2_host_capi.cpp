@@ -555,6 +555,57 @@ int ov2h_compute_pose(void *p, void *ctx, int kfid, const double *Twc7_init, int
     return s;
 }
 
+// VisualFrontEnd::epipolar2d2dFiltering (:446-655) with keyframe kf_cur taken as the current frame and kf_prev as its previous
+// keyframe, nransac_iter / fransac_err as the YAML keys, bdo_random off (seed used as is).  removed[cap]: the ids the stage
+// removed from kf_cur, ascending; stats[4] (may be NULL): as ov2h_slam_epi_stats.  Returns the number of removed ids, or a
+// negative ov2_status (OV2_ERR_UNSUPPORTED: the mono do_optimize branch).
+int ov2h_epipolar_filtering(void *p, void *ctx, int kf_prev, int kf_cur, int nransac_iter, float fransac_err,
+                            unsigned long long seed, int cap, int *removed, double *stats)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kf_cur);
+    if (!f || !m->map->getKeyframe(kf_prev)) return (int)OV2_ERR_INVALID;
+    std::vector<int> before;
+    for (const auto &kv : f->mapkps_) before.push_back(kv.first);
+    std::sort(before.begin(), before.end());
+    SlamParams &S = *m->st;
+    S.nransac_iter_ = nransac_iter; S.fransac_err_ = fransac_err; S.bdo_random_ = false; S.epi_seed_ = (uint64_t)seed;
+    const int own = f->kfid_;
+    f->kfid_ = kf_prev;
+    m->map->pcurframe_ = f;
+    VisualFrontEnd fe((ov2_ctx *)ctx, m->st, f, m->map, nullptr);
+    EpiStats es;
+    const ov2_status s = fe.epipolar2d2dFiltering(&es);
+    f->kfid_ = own;
+    if (stats) { stats[0] = es.status; stats[1] = es.pairs; stats[2] = es.removed; stats[3] = es.gate_removed; }
+    if (s != OV2_OK) return (int)s;
+    int n = 0;
+    for (const int id : before)
+        if (!f->mapkps_.count(id)) { if (n < cap) removed[n] = id; ++n; }
+    return n;
+}
+
+// MultiViewGeometry::compute5ptEssentialMatrix (src/multi_view_geometry.cpp:596-697) with the reference's arguments:
+// returns its bool (0 / 1) or a negative ov2_status; R9 / t3 = [R12 | t12] when it returns 1, outidx[n] the voutliersidx
+// (count in *n_out)
+int ov2h_compute5pt(void *ctx, int n, const double *bvs1, const double *bvs2, int nmaxiter, float errth, int boptimize,
+                    float fx, float fy, unsigned long long seed, double *R9, double *t3, int *outidx, int *n_out)
+{
+    std::vector<Vec3> a((size_t)n), b((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        a[i] = Vec3{bvs1[3 * i], bvs1[3 * i + 1], bvs1[3 * i + 2]};
+        b[i] = Vec3{bvs2[3 * i], bvs2[3 * i + 1], bvs2[3 * i + 2]};
+    }
+    std::vector<int> out;
+    ov2_status st = OV2_OK;
+    const bool ok = MultiViewGeometry::compute5ptEssentialMatrix((ov2_ctx *)ctx, a, b, nmaxiter, errth, boptimize != 0, seed, fx,
+                                                                 fy, R9, t3, out, &st);
+    if (st != OV2_OK) return (int)st;
+    for (size_t i = 0; i < out.size(); ++i) outidx[i] = out[i];
+    *n_out = (int)out.size();
+    return ok ? 1 : 0;
+}
+
 int ov2h_get_pose(void *p, int kfid, double *Twc7)
 {
     auto f = ((HostMap *)p)->map->getKeyframe(kfid);
@@ -653,6 +704,25 @@ void ov2h_slam_set_brief(void *p, const int8_t *pattern, int use_brief, int trac
     S->pslamstate_->bdo_track_localmap_ = track_localmap != 0;
     if (fmax_desc_dist > 0.f) S->pslamstate_->fmax_desc_dist_ = fmax_desc_dist;
     if (fmax_proj_pxdist > 0.f) S->pslamstate_->fmax_proj_pxdist_ = fmax_proj_pxdist;
+}
+
+// VisualFrontEnd::epipolar2d2dFiltering in trackMono (YAML doepipolar, nransac_iter, fransac_err, bdo_random) + the sampler's
+// base seed (bdo_random: mixed with the frame id; otherwise used as is on every frame)
+void ov2h_slam_set_epipolar(void *p, int on, int nransac_iter, float fransac_err, int bdo_random, unsigned long long seed)
+{
+    SlamParams &S = *((SlamManager *)p)->pslamstate_;
+    S.doepipolar_ = on != 0;
+    S.nransac_iter_ = nransac_iter;
+    S.fransac_err_ = fransac_err;
+    S.bdo_random_ = bdo_random != 0;
+    S.epi_seed_ = (uint64_t)seed;
+}
+
+// out[4] of the last frame: RANSAC status (-1 = returned before it), pairs, outliers removed, 2D keypoints removed by the gate
+void ov2h_slam_epi_stats(void *p, double *out)
+{
+    const EpiStats &e = ((SlamManager *)p)->last_epi_;
+    out[0] = e.status; out[1] = e.pairs; out[2] = e.removed; out[3] = e.gate_removed;
 }
 
 // out[3] of the last frame (keyframes only): keypoints described, local map points offered to matchToMap, merges

@@ -9,7 +9,8 @@
 //   SlamManager::run (one image)     src/ov2slam.cpp:152-205    Estimator::applyLocalBA  src/estimator.cpp:67-98
 // The reference runs front-end, mapper and estimator on three threads; here one call processes one stereo frame to the
 // end (keyframe work included), i.e. the reference with bforce_realtime = 0 and an idle back-end: deterministic.
-// Out of scope and refused loudly where reached: P3P / 5-point RANSAC (OpenGV), loop closing, BRIEF map matching.
+// VisualFrontEnd::epipolar2d2dFiltering :446-655 runs with doepipolar_ (ov2_epipolar_filter_batch).
+// Out of scope and refused loudly where reached: P3P (OpenGV), the mono branch of the epipolar filter, loop closing.
 #pragma once
 #include "ov2_host.hpp"
 
@@ -80,6 +81,7 @@ public:
     MotionModel motion_model_;
     int frame_id_ = -1;
     SlamStats last_;
+    EpiStats last_epi_;   // epipolar2d2dFiltering on the last frame (doepipolar_)
     std::vector<SlamStats> stats_;
     std::vector<SE3> traj_;
 

@@ -68,6 +68,10 @@ def lib():
         L.ov2h_slam_set_brief.restype = None
         L.ov2h_slam_kf_stats.argtypes = [C.c_void_p, dp]
         L.ov2h_slam_kf_stats.restype = None
+        L.ov2h_slam_set_epipolar.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_ulonglong]
+        L.ov2h_slam_set_epipolar.restype = None
+        L.ov2h_slam_epi_stats.argtypes = [C.c_void_p, dp]
+        L.ov2h_slam_epi_stats.restype = None
         L.ov2h_slam_device_handle.argtypes = [C.c_void_p]
         L.ov2h_slam_device_handle.restype = C.c_void_p
         L.ov2h_slam_flush_device.argtypes = [C.c_void_p]
@@ -103,6 +107,10 @@ def lib():
         L.ov2h_slam_landmarks.argtypes = [C.c_void_p, C.c_int, ip, dp]
         L.ov2h_slam_destroy.argtypes, L.ov2h_slam_destroy.restype = [C.c_void_p], None
         L.ov2h_compute_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, ip]
+        L.ov2h_epipolar_filtering.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_ulonglong,
+                                              C.c_int, ip, dp]
+        L.ov2h_compute5pt.argtypes = [C.c_void_p, C.c_int, dp, dp, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
+                                      C.c_ulonglong, dp, dp, ip, ip]
         L.ov2h_get_pose.argtypes = [C.c_void_p, C.c_int, dp]
         L.ov2h_get_landmark.argtypes = [C.c_void_p, C.c_int, dp, ip]
         L.ov2h_count_keypoints.argtypes = [C.c_void_p, C.c_int, ip, ip, ip]
@@ -461,6 +469,10 @@ class CppSlam:
         lib().ov2h_slam_stats(self.h_, _dp(s))
         self.traj.append(T)
         self.stats.append(dict(zip(self.STAT_KEYS, s.tolist())))
+        if getattr(self, "epi_stats", None) is not None:
+            e = np.zeros(4)
+            lib().ov2h_slam_epi_stats(self.h_, _dp(e))
+            self.epi_stats.append(dict(status=int(e[0]), pairs=int(e[1]), removed=int(e[2]), gate_removed=int(e[3])))
         if getattr(self, "kf_stats", None) is not None and self.stats[-1]["kf"]:
             k = np.zeros(3)
             lib().ov2h_slam_kf_stats(self.h_, _dp(k))
@@ -474,6 +486,13 @@ class CppSlam:
         lib().ov2h_slam_set_brief(self.h_, None if pat is None else pat.ctypes.data, int(bool(use_brief)), int(bool(track_localmap)),
                                   float(fmax_desc_dist), float(fmax_proj_pxdist))
         self.kf_stats = []
+
+    def set_epipolar(self, on=True, nransac_iter=100, fransac_err=3.0, bdo_random=True, seed=0):
+        """doepipolar / nransac_iter / fransac_err / bdo_random of the YAML: trackMono runs VisualFrontEnd::epipolar2d2dFiltering
+        (ov2_epipolar_filter_batch) between kltTracking and computePose; seed = the sampler's base seed"""
+        lib().ov2h_slam_set_epipolar(self.h_, int(bool(on)), int(nransac_iter), float(fransac_err), int(bool(bdo_random)),
+                                     int(seed) & ((1 << 64) - 1))
+        self.epi_stats = []
 
     def check_map(self):
         """(violations of the host map's invariants, total) -- see ov2h_slam_check_map"""
@@ -618,6 +637,55 @@ class FrameLoop:
     def close(self):
         if getattr(self, "h", None):
             lib().ov2h_feloop_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def compute5pt_essential(ctx, bvs1, bvs2, nmaxiter, errth, boptimize, fx, fy, seed):
+    """the C++ MultiViewGeometry::compute5ptEssentialMatrix (src/multi_view_geometry.cpp:596-697) over the C ABI.
+    returns (success, R (3,3), t (3,), voutliersidx); a negative status raises"""
+    b1 = np.ascontiguousarray(bvs1, np.float64).reshape(-1, 3)
+    b2 = np.ascontiguousarray(bvs2, np.float64).reshape(-1, 3)
+    n = len(b1)
+    R, t, out, nout = np.zeros(9), np.zeros(3), np.zeros(max(n, 1), np.int32), C.c_int(0)
+    r = lib().ov2h_compute5pt(ctx.h, n, _dp(b1), _dp(b2), int(nmaxiter), float(errth), int(bool(boptimize)), float(fx), float(fy),
+                              int(seed), _dp(R), _dp(t), out.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nout))
+    if r < 0:
+        raise RuntimeError(f"compute5ptEssentialMatrix: status {r}")
+    return bool(r), R.reshape(3, 3), t, out[:nout.value].copy()
+
+
+class TwoViewMap:
+    """two keyframes of the C++ host mirror with chosen keypoints (pixels, 2D / 3D), to run
+    VisualFrontEnd::epipolar2d2dFiltering with one as the previous keyframe and the other as the current frame"""
+
+    def __init__(self, K, Twc_prev, Twc_cur, stereo=True, w=752, h=480):
+        L = lib()
+        K = np.ascontiguousarray(K, np.float64)
+        t_lr7 = np.ascontiguousarray([0.11, 0, 0, 0, 0, 0, 1.0])
+        self.h = L.ov2h_map_create(int(stereo), 1, _dp(K), _dp(K), _dp(t_lr7), w, h, 25)
+        for kfid, T in ((0, Twc_prev), (1, Twc_cur)):
+            L.ov2h_map_add_keyframe(self.h, kfid, _dp(np.ascontiguousarray(T, np.float64)))
+
+    def add_keypoint(self, kfid, lmid, px, is3d):
+        """kfid 0 = previous keyframe, 1 = current frame; px: undistorted pixel (float)"""
+        x = np.zeros(3)
+        assert lib().ov2h_map_add_kp(self.h, int(kfid), int(lmid), float(px[0]), float(px[1]), int(bool(is3d)), _dp(x)) == 0
+
+    def epipolar_filtering(self, ctx, nransac_iter=100, fransac_err=3.0, seed=0, cap=1 << 16):
+        """returns (removed ids ascending, stats dict); a negative status raises"""
+        rm, st = np.zeros(cap, np.int32), np.zeros(4)
+        n = lib().ov2h_epipolar_filtering(self.h, ctx.h, 0, 1, int(nransac_iter), float(fransac_err), int(seed), cap,
+                                          rm.ctypes.data_as(C.POINTER(C.c_int)), _dp(st))
+        if n < 0:
+            raise RuntimeError(f"epipolar2d2dFiltering: status {n}")
+        return rm[:n].copy(), dict(status=int(st[0]), pairs=int(st[1]), removed=int(st[2]), gate_removed=int(st[3]))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ov2h_map_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -86,3 +86,66 @@ class MultiViewGeometry:
                                               int(bool(bapply_l2_after_robust)), _vp(outl), _vp(ok), _vp(it)))
         off = np.concatenate([[0], np.cumsum(n_pts)])
         return ok[:B].astype(bool), T, [outl[off[b]:off[b + 1]].astype(bool) for b in range(B)], it[:B]
+
+    # -- per-frame epipolar filter (csrc/epipolar.hip) ------------------------------------------------------------------
+    def compute5ptEssentialMatrix(self, bvs1, bvs2, nmaxiter, errth, boptimize, bdorandom, fx, fy, seed=0):
+        """MultiViewGeometry::compute5ptEssentialMatrix (src/multi_view_geometry.cpp:596-611 -> opengv5ptEssentialMatrix
+        :614-697) through ov2_epipolar_filter_batch with B = 1.  bvs1 = keyframe bearings, bvs2 = current-frame bearings.
+        returns (success, Rwc (3,3), twc (3,) unit, voutliersidx (sorted int array)): success is the reference's return
+        (>= 8 pairs, a model, >= 10 inliers).  bdorandom only selects the seed in the C++ mirror (the caller passes it
+        here); boptimize = True (OpenGV's nonlinear refinement) is not built."""
+        if boptimize:
+            raise NotImplementedError("compute5ptEssentialMatrix: boptimize (OpenGV optimizeModelCoefficients) is not built")
+        r = self.compute5ptEssentialMatrix_batch([bvs1], [bvs2], nmaxiter, errth, np.array([[fx, fy, 0., 0.]]), [seed])
+        ok = r["status"][0] >= 1
+        return bool(ok), r["R"][0], r["t"][0], np.flatnonzero(r["outlier"][0]).astype(np.int32)
+
+    def compute5ptEssentialMatrix_batch(self, bvs1_list, bvs2_list, nmaxiter, errth, K, seeds, gate_kf_list=None,
+                                        gate_cur_list=None, R0=None, t0=None):
+        """B frames in one launch (ov2_epipolar_filter_batch): RANSAC on each frame's pairs and, where the frame ends with
+        status 2, the Sampson gate on its 2D points.  returns dict(status (B,), R (B,3,3), t (B,3), outlier [mask per frame],
+        gate_bad [mask per frame], info (B,4))."""
+        B = len(bvs1_list)
+        n = np.array([len(np.asarray(b).reshape(-1, 3)) for b in bvs1_list], np.int32)
+        if any(len(np.asarray(b).reshape(-1, 3)) != k for b, k in zip(bvs2_list, n)):
+            raise ValueError("bvs1.size() != bvs2.size()")       # the reference asserts (:622)
+        cat = lambda xs, k, dt: (np.concatenate([np.asarray(x, dt).reshape(-1, k) for x in xs]) if B and sum(
+            len(np.asarray(x).reshape(-1, k)) for x in xs) else np.zeros((1, k), dt))
+        b1, b2 = np.ascontiguousarray(cat(bvs1_list, 3, np.float64)), np.ascontiguousarray(cat(bvs2_list, 3, np.float64))
+        ng = np.zeros(B, np.int32) if gate_kf_list is None else \
+            np.array([len(np.asarray(g).reshape(-1, 2)) for g in gate_kf_list], np.int32)
+        g1 = np.ascontiguousarray(cat(gate_kf_list, 2, np.float32)) if gate_kf_list is not None else np.zeros((1, 2), np.float32)
+        g2 = np.ascontiguousarray(cat(gate_cur_list, 2, np.float32)) if gate_cur_list is not None else np.zeros((1, 2), np.float32)
+        K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(B, 4))
+        sd = np.ascontiguousarray(np.asarray(seeds, np.uint64).reshape(B))
+        R = np.ascontiguousarray(np.zeros((max(B, 1), 9)) if R0 is None else np.array(R0, np.float64).reshape(B, 9))
+        t = np.ascontiguousarray(np.zeros((max(B, 1), 3)) if t0 is None else np.array(t0, np.float64).reshape(B, 3))
+        outl, gb = np.zeros(max(int(n.sum()), 1), np.uint8), np.zeros(max(int(ng.sum()), 1), np.uint8)
+        st, info = np.zeros(max(B, 1), np.int32), np.zeros((max(B, 1), 4), np.int32)
+        c = self.ctx
+        _check(c.h, c.lib.ov2_epipolar_filter_batch(c.h, B, _vp(n), _vp(b1), _vp(b2), _vp(ng), _vp(g1), _vp(g2), _vp(K),
+                                                    int(nmaxiter), float(errth), _vp(sd), _vp(R), _vp(t), _vp(outl),
+                                                    _vp(gb), _vp(st), _vp(info)))
+        off, goff = np.concatenate([[0], np.cumsum(n)]), np.concatenate([[0], np.cumsum(ng)])
+        return dict(status=st[:B], R=R[:B].reshape(B, 3, 3), t=t[:B], info=info[:B],
+                    outlier=[outl[off[b]:off[b + 1]].astype(bool) for b in range(B)],
+                    gate_bad=[gb[goff[b]:goff[b + 1]].astype(bool) for b in range(B)])
+
+    def compute5ptEssentialMatrix_batch_dev(self, B, d_off, d_bv_kf, d_bv_cur, d_gate_off, d_gate_kf, d_gate_cur, d_K,
+                                            nmaxiter, errth, d_seed, d_R, d_t, d_outlier, d_gate_bad, d_status, d_info=None):
+        """device-resident, asynchronous form (ov2_epipolar_filter_batch_dev): DeviceArrays in, nothing synchronised."""
+        p = lambda a: None if a is None else a.ptr
+        c = self.ctx
+        _check(c.h, c.lib.ov2_epipolar_filter_batch_dev(c.h, int(B), p(d_off), p(d_bv_kf), p(d_bv_cur), p(d_gate_off),
+                                                        p(d_gate_kf), p(d_gate_cur), p(d_K), int(nmaxiter), float(errth),
+                                                        p(d_seed), p(d_R), p(d_t), p(d_outlier), p(d_gate_bad),
+                                                        p(d_status), p(d_info)))
+
+    def dbg_fivept(self, bv1, bv2):
+        """the device 5-point solver on n samples (ov2_dbg_fivept): bv1, bv2 (n,5,3) -> E (n,10,3,3), nsol (n,)"""
+        bv1, bv2 = np.ascontiguousarray(bv1, np.float64).reshape(-1, 5, 3), np.ascontiguousarray(bv2, np.float64).reshape(-1, 5, 3)
+        n = len(bv1)
+        E, ns = np.zeros((max(n, 1), 10, 9)), np.zeros(max(n, 1), np.int32)
+        c = self.ctx
+        _check(c.h, c.lib.ov2_dbg_fivept(c.h, n, _vp(bv1), _vp(bv2), _vp(E), _vp(ns)))
+        return E[:n].reshape(n, 10, 3, 3), ns[:n]
