@@ -408,6 +408,52 @@ ov2_status ov2_epipolar_filter_batch_dev(ov2_ctx *ctx, int B, const int32_t *d_o
                                          uint8_t *d_gate_bad, int32_t *d_status, int32_t *d_info);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The P3P stage of computePose: P3P LMedS / RANSAC on 2D-3D correspondences.
+ * Replaces MultiViewGeometry::p3pRansac (src/multi_view_geometry.cpp:144-163) -> opengvP3PLMeds (:257-343, use_lmeds != 0,
+ * OpenGV Lmeds<AbsolutePoseSacProblem>, KNEIP; what VisualFrontEnd::computePose calls, src/visual_front_end.cpp:718-782)
+ * or opengvP3PRansac (:168-254, use_lmeds == 0, OpenGV Ransac, probability 0.99; what LoopCloser calls).
+ * B independent frames per call; frame b owns n_pts[b] consecutive correspondences.  All pointers are HOST pointers; one
+ * synchronisation.
+ *   bvs     sum(n) x 3   bearing vectors of the current frame's keypoints (unit length)
+ *   wpts    sum(n) x 3   the world points they observe
+ *   K       B x 4   fx fy cx cy; the threshold is 1 - cos(atan(errth / focal)) with focal = (fx + fy) / 2 and the quotient
+ *                   in float, atan / cos in double (no factor 2, unlike the epipolar stage)
+ *   seed    B       one 64-bit sampler seed per frame
+ *   Twc     B x 7   [t, qx qy qz qw], camera to world: written when status == 1, untouched otherwise (the layout
+ *                   ov2_pnp_solve_batch_dev takes)
+ *   outlier sum(n)  1 = not an inlier of the chosen model (voutliersidx as a mask); 0 everywhere when status == 0
+ *   status  B       0: the reference's false (n < 4, no draw gave a model, < 5 inliers, or R fails Sophus::isOrthogonal:
+ *                   |R R^T - I|_F >= 1e-10); 1: a pose
+ *   info    B x 4   (may be NULL) counted draws (OpenGV iterations), skipped draws, index of the chosen draw (-1 = none),
+ *                   inlier count
+ * Model of a draw (4 distinct indices): Kneip's P3P on the first three gives up to four [R | t]; the fourth picks the one
+ * with the lowest 1 - f4 . p / |p|, p = R^T (X4 - t).  Distance of correspondence i: 1 - f_i . p_i / |p_i|.
+ * LMedS: draws d = 0, 1, ...; a draw without a model is skipped; the loop ends after nmaxiter counted draws or 10 nmaxiter
+ * skipped ones; penalty of a counted draw = sqrt of the median of its n sorted distances ((sqrt(d[n/2-1]) + sqrt(d[n/2])) / 2
+ * for even n); the first draw of the strictly lowest penalty wins; inliers d_i <= threshold.  RANSAC: OpenGV's stop rule
+ * as in ov2_epipolar_filter_batch with sample size 4; inliers d_i < threshold.
+ * Deviations: OpenGV's sampler is not reproduced (clock seed); draw d takes its 4 indices from the seeded counter hash
+ * documented at ov2_epipolar_filter_batch.  A distance is clamped below at 0, and a non-finite one (NaN in the bearing or
+ * the point, point at the camera centre) counts as +infinity: it sorts last and is never an inlier.  A ZERO bearing has the
+ * finite distance 1 - 0 . p / |p| = 1: above any threshold, so never an inlier, but it does not sort last; as the 4th point
+ * of a draw it scores 1 under every candidate, an exact tie that falls to the first candidate in root order (ascending
+ * cos(theta)).  Only real roots of Kneip's
+ * quartic give candidates (OpenGV takes the real parts of complex ones), and each candidate is polished on the three
+ * distance constraints.  OpenGV's nonlinear refinement (boptimize) is not built: the callers refuse it.
+ * nmaxiter outside [0, OV2_P3P_MAX_ITER] and B above OV2_P3P_MAX_BATCH are OV2_ERR_INVALID (a call looks at at most
+ * 11 nmaxiter + 1 draws per frame). */
+#define OV2_P3P_MAX_ITER (1 << 20)
+#define OV2_P3P_MAX_BATCH 65535
+ov2_status ov2_p3p_ransac_batch(ov2_ctx *ctx, int B, const int *n_pts, const double *bvs, const double *wpts,
+                                const double *K, int nmaxiter, float errth, int use_lmeds, const uint64_t *seed,
+                                double *Twc, uint8_t *outlier, int *status, int *info);
+/* device-resident, asynchronous form: d_off = B + 1 prefix offsets of the frames' correspondences, every other array as
+ * above but in HBM.  Nothing is synchronised or read back (the context's scratch block is grown first if it is too small). */
+ov2_status ov2_p3p_ransac_batch_dev(ov2_ctx *ctx, int B, const int32_t *d_off, const double *d_bvs, const double *d_wpts,
+                                    const double *d_K, int nmaxiter, float errth, int use_lmeds, const uint64_t *d_seed,
+                                    double *d_Twc, uint8_t *d_outlier, int32_t *d_status, int32_t *d_info);
+
+/* ---------------------------------------------------------------------------------------------------
  * Pose graphs: Optimizer::localPoseGraph (src/optimizer.cpp:2346-2592, the loop closer's chain of
  * keyframes loop .. new + the loop edge) and Optimizer::fullPoseGraph (:2783-2870, the chain of all frames between
  * constant keyframes at the end of a run) = LeftSE3RelativePoseError (src/ceres_parametrization.cpp:30-102,
@@ -693,6 +739,9 @@ ov2_status ov2_dbg_rowload16(ov2_ctx *ctx, const void *d_buf, size_t stride_byte
 /* Runs the device 5-point solver of ov2_epipolar_filter_batch on n given samples: bv1, bv2 n x 5 x 3 (host), E n x 10 x 9
  * (host, row-major, ||E||_F = 1, bv1^T E bv2 = 0 on the sample; rows past nsol[i] are zero), nsol n.  Synchronous. */
 ov2_status ov2_dbg_fivept(ov2_ctx *ctx, int n, const double *bv1, const double *bv2, double *E, int *nsol);
+/* Runs the device P3P solver of ov2_p3p_ransac_batch on n given samples: bv, X n x 3 x 3 (host), R n x 4 x 9 (row-major,
+ * camera to world), t n x 4 x 3, nsol n (0..4; unused slots are zero). */
+ov2_status ov2_dbg_p3p(ov2_ctx *ctx, int n, const double *bv, const double *X, double *R, double *t, int *nsol);
 
 #ifdef __cplusplus
 }

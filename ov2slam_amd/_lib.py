@@ -103,6 +103,9 @@ SIGNATURES = {
     "ov2_epipolar_filter_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp, vp,
                                                 vp, vp, vp, vp]),
     "ov2_dbg_fivept": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+    "ov2_p3p_ransac_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
+    "ov2_p3p_ransac_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
+    "ov2_dbg_p3p": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -37,6 +37,7 @@
 #include "ov2_internal.h"
 
 #define HD __host__ __device__
+#include "sac_common.h"   // the sampler (epi_hash, sac_draw) and OpenGV's iteration bound
 
 namespace {
 
@@ -49,41 +50,6 @@ HD inline double epi_sqrt(double x)
 #else
     return std::sqrt(x);
 #endif
-}
-
-// ---- sampler: SplitMix64 finaliser, draw d / attempt j of a frame's stream, multiply-shift reduction to [0, n) ----
-HD inline uint64_t epi_mix(uint64_t z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-HD inline uint32_t epi_hash(uint64_t seed, uint32_t d, uint32_t j, uint32_t n)
-{
-    const uint64_t a = epi_mix(seed + 0x9E3779B97F4A7C15ull * ((uint64_t)d + 1));
-    const uint64_t x = epi_mix(a + 0x9E3779B97F4A7C15ull * ((uint64_t)j + 1));
-    return (uint32_t)(((x >> 32) * (uint64_t)n) >> 32);
-}
-// 5 distinct indices of [0, n), n >= 5: attempt j = 0, 1, ...; a duplicate is redrawn; after 256 attempts the
-// smallest unused index is taken (never reached for n >= 8 in practice, keeps the worst case bounded)
-HD inline void epi_draw(uint64_t seed, int d, int n, int *idx)
-{
-    uint32_t j = 0;
-    for (int s = 0; s < 5; ++s) {
-        int v = -1;
-        while (v < 0 && j < 256) {
-            const int c = (int)epi_hash(seed, (uint32_t)d, j++, (uint32_t)n);
-            bool dup = false;
-            for (int q = 0; q < s; ++q) dup = dup || idx[q] == c;
-            if (!dup) v = c;
-        }
-        for (int c = 0; c < n && v < 0; ++c) {
-            bool dup = false;
-            for (int q = 0; q < s; ++q) dup = dup || idx[q] == c;
-            if (!dup) v = c;
-        }
-        idx[s] = v;
-    }
 }
 
 // ---- score of one pair (OpenGV getSelectedDistancesToModel: triangulate2 + normalised reprojections) ----
@@ -170,62 +136,8 @@ HD inline void pmul21_acc(const double q[10], const double l[4], double s, doubl
             for (int k = 0; k < 4; ++k) c[cidx(a, b, k)] += s * (q[pidx(a, b)] * l[k]);
 }
 
-// p(z) and p'(z), coefficients ascending
-HD inline double peval(const double *p, int n, double z, double *dp)
-{
-    double v = p[n], d = 0.;
-    for (int i = n - 1; i >= 0; --i) { d = d * z + v; v = v * z + p[i]; }
-    *dp = d;
-    return v;
-}
-
-// the single root of a polynomial that is monotone on [lo, hi] and changes sign there (safeguarded Newton)
-HD inline double root_bracket(const double *p, int n, double lo, double hi, double flo)
-{
-    double x = 0.5 * (lo + hi);
-    for (int it = 0; it < 200; ++it) {
-        double df;
-        const double f = peval(p, n, x, &df);
-        if (f == 0.) return x;
-        if ((f < 0.) == (flo < 0.)) lo = x; else hi = x;
-        double xn = x - f / df;
-        if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
-        if (hi - lo <= 4e-16 * fabs(x) || xn == x) return xn;
-        x = xn;
-    }
-    return x;
-}
-
-// real roots of w.u.rt.p (degree n <= 10, p[n] != 0) into w.u.rt.cp, ascending: the roots of p^(k) are isolated between
-// consecutive roots of p^(k+1) (k = n-1 .. 0), inside the Cauchy bound
-HD inline int real_roots(epi_ws &w, int n)
-{
-    double *p = w.u.rt.p, *q = w.u.rt.q, *cp = w.u.rt.cp, *nr = w.u.rt.nr;
-    double bound = 0.;
-    for (int i = 0; i < n; ++i) bound = fmax(bound, fabs(p[i] / p[n]));
-    bound += 1.;
-    int ncp = 0;
-    for (int k = n - 1; k >= 0; --k) {
-        const int deg = n - k;
-        for (int i = 0; i <= deg; ++i) {   // q = p^(k)
-            double f = 1.;
-            for (int m = 0; m < k; ++m) f *= (double)(i + k - m);
-            q[i] = p[i + k] * f;
-        }
-        int m = 0;
-        for (int s = 0; s <= ncp; ++s) {
-            const double a = s == 0 ? -bound : cp[s - 1], b = s == ncp ? bound : cp[s];
-            double dd;
-            const double fa = peval(q, deg, a, &dd), fb = peval(q, deg, b, &dd);
-            if (fb == 0.) { nr[m++] = b; continue; }
-            if (fa == 0. || (fa < 0.) == (fb < 0.)) continue;
-            nr[m++] = root_bracket(q, deg, a, b, fa);
-        }
-        for (int i = 0; i < m; ++i) cp[i] = nr[i];
-        ncp = m;
-    }
-    return ncp;
-}
+// real roots of w.u.rt.p (degree n <= 10, p[n] != 0) into w.u.rt.cp, ascending (sac_common.h)
+HD inline int real_roots(epi_ws &w, int n) { return sac_real_roots(w.u.rt.p, n, w.u.rt.q, w.u.rt.cp, w.u.rt.nr); }
 
 // Gauss-Newton on the 10 cubic constraints (2 E E^T E - tr(E E^T) E = 0, det E = 0) in the homogeneous coefficients
 // v of E = v0 X + v1 Y + v2 Z + v3 W, |v| = 1 (steps orthogonal to v): the degree-10 reduction loses digits on some
@@ -688,7 +600,7 @@ __global__ __launch_bounds__(EPI_THREADS) void epipolar_kernel(epi_args A)
     for (int d0 = 0; !S.done; d0 += EPI_ROUND) {
         if (tid < EPI_ROUND) {
             epi_ws &w = W[tid];
-            epi_draw(seed, d0 + tid, n, w.idx);
+            sac_draw<5>(seed, d0 + tid, n, w.idx);
             for (int s = 0; s < 5; ++s) load_pair(A, o0 + w.idx[s], w.f1[s], w.f2[s]);
             S.ok[tid] = epi_model(w, &S.model[tid][0], &S.model[tid][9]);
             S.cnt[tid] = 0;
@@ -716,11 +628,7 @@ __global__ __launch_bounds__(EPI_THREADS) void epipolar_kernel(epi_args A)
                     S.best_cnt = S.cnt[r];
                     S.best_d = d0 + r;
                     for (int e = 0; e < 12; ++e) S.best[e] = S.model[r][e];
-                    const double w = (double)S.best_cnt / (double)n;
-                    double pno = 1.0 - pow(w, 5.0);
-                    pno = fmax(2.220446049250313e-16, pno);
-                    pno = fmin(1.0 - 2.220446049250313e-16, pno);
-                    S.k = log(1.0 - 0.99) / log(pno);
+                    S.k = sac_ransac_k(S.best_cnt, n, 5.0);
                 }
                 ++S.iterations;
                 if (S.iterations > max_iter) S.done = 1;

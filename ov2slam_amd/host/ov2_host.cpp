@@ -966,6 +966,27 @@ bool MultiViewGeometry::compute5ptEssentialMatrix(ov2_ctx *ctx, const std::vecto
     return true;
 }
 
+bool MultiViewGeometry::p3pRansac(ov2_ctx *ctx, const std::vector<Vec3> &bvs, const std::vector<Vec3> &vwpts, int nmaxiter,
+                                  float errth, bool boptimize, bool bdorandom, float fx, float fy, SE3 &Twc,
+                                  std::vector<int> &voutliersidx, bool use_lmeds, uint64_t seed, ov2_status *st)
+{   // src/multi_view_geometry.cpp:144-163 -> opengvP3PLMeds :257-343 / opengvP3PRansac :168-254
+    (void)bdorandom;   // the reference's clock seed; here the caller derives `seed` from it
+    if (st) *st = OV2_OK;
+    if (boptimize) { if (st) *st = OV2_ERR_UNSUPPORTED; return false; }   // optimizeModelCoefficients (:320-324) is not built
+    if (bvs.size() != vwpts.size()) return false;                         // the reference asserts (:263)
+    const int n = (int)bvs.size();
+    const double K[4] = {fx, fy, 0., 0.};
+    std::vector<uint8_t> out((size_t)n + 1);
+    int status = 0;
+    const ov2_status s = ov2_p3p_ransac_batch(ctx, 1, &n, n ? &bvs[0].x : nullptr, n ? &vwpts[0].x : nullptr, K, nmaxiter, errth,
+                                              use_lmeds ? 1 : 0, &seed, Twc.v.data(), out.data(), &status, nullptr);
+    if (s != OV2_OK) { if (st) *st = s; return false; }
+    if (status != 1) return false;   // < 4 points, no model, < 5 inliers or a non-orthogonal R (:267, :309-315)
+    for (int i = 0; i < n; ++i)
+        if (out[i]) voutliersidx.push_back(i);
+    return true;
+}
+
 ov2_status VisualFrontEnd::epipolar2d2dFiltering(EpiStats *stats)
 {   // src/visual_front_end.cpp:446-655
     if (stats) *stats = EpiStats();
@@ -1050,22 +1071,35 @@ ov2_status VisualFrontEnd::epipolar2d2dFiltering(EpiStats *stats)
     return OV2_OK;
 }
 
-ov2_status VisualFrontEnd::computePose()
-{   // src/visual_front_end.cpp:657-830
+void VisualFrontEnd::resetFrame()
+{   // src/visual_front_end.cpp:1181-1203: the pose and the covisibility / local-map sets are kept
+    const auto mapkps = pcurframe_->mapkps_;
+    for (const auto &kpit : mapkps) pmap_->removeObsFromCurFrameById(kpit.first);
+    pcurframe_->mapkps_.clear();
+    pcurframe_->vgridkps_.assign(pcurframe_->nbwcells_ * pcurframe_->nbhcells_, {});
+    pcurframe_->nbkps_ = 0; pcurframe_->nb2dkps_ = 0; pcurframe_->nb3dkps_ = 0; pcurframe_->nb_stereo_kps_ = 0;
+    pcurframe_->noccupcells_ = 0;
+}
+
+ov2_status VisualFrontEnd::computePose(P3pStats *stats)
+{   // src/visual_front_end.cpp:659-851
+    if (stats) *stats = P3pStats();
     const size_t nb3dkps = pcurframe_->nb3dkps_;
-    if (nb3dkps < 4) return OV2_OK;                                        // :665-669
-    if (bp3preq_ || pslamstate_->dop3p_) return OV2_ERR_UNSUPPORTED;       // P3P-RANSAC branch :722-785 (OpenGV)
+    if (nb3dkps < 4) return OV2_OK;                                        // :667-671
+    const SlamParams &S = *pslamstate_;
     std::vector<Vec2> vkps;
-    std::vector<Vec3> vwpts;
+    std::vector<Vec3> vbvs, vwpts;
     std::vector<int> vkpids, voutliersidx, vscales;
+    const bool bdop3p = bp3preq_ || S.dop3p_;                              // :688
     std::vector<int> order;                                               // the reference walks its hash map; ascending ids make the
-    for (const auto &it : pcurframe_->mapkps_) order.push_back(it.first);  // summation order of the solve independent of the hash
-    std::sort(order.begin(), order.end());
-    for (const int id : order) {                                           // :688-708
+    for (const auto &it : pcurframe_->mapkps_) order.push_back(it.first);  // summation order of the solve (and the sampler's draws)
+    std::sort(order.begin(), order.end());                                // independent of the hash
+    for (const int id : order) {                                           // :691-712
         const Keypoint &kp = pcurframe_->mapkps_.at(id);
         if (!kp.is3d_) continue;
         auto plm = pmap_->getMapPoint(kp.lmid_);
         if (!plm) continue;
+        if (bdop3p) vbvs.push_back(kp.bv_);
         vkps.push_back({kp.unpx_.x, kp.unpx_.y});
         vwpts.push_back(plm->getPoint());
         vscales.push_back(kp.scale_);
@@ -1073,19 +1107,62 @@ ov2_status VisualFrontEnd::computePose()
     }
     SE3 Twc = pcurframe_->getTwc();
     const CameraCalibration &c = *pcurframe_->pcalib_leftcam_;
-    const bool success = MultiViewGeometry::ceresPnP(ctx_, vkps, vwpts, vscales, Twc, 5, pslamstate_->robust_mono_th_, true,
-                                                     pslamstate_->apply_l2_after_robust_, (float)c.fx_, (float)c.fy_,
-                                                     (float)c.cx_, (float)c.cy_, voutliersidx);   // :788-803
-    const size_t nbinliers = vwpts.size() - voutliersidx.size();
-    bool bad_t = false;
-    for (int i = 0; i < 3; ++i) bad_t = bad_t || !std::isfinite(Twc.v[i]);
-    if (!success || nbinliers < 5 || voutliersidx.size() > 0.5 * vwpts.size() || bad_t) {   // :806-826
-        bp3preq_ = true;   // "weird results, skipping here and applying p3p next"
+    const bool do_optimize = false;
+    bool success = false;
+    auto bad_translation = [&]() {
+        bool bad = false;
+        for (int i = 0; i < 3; ++i) bad = bad || !std::isfinite(Twc.v[i]);
+        return bad;
+    };
+    if (bdop3p) {                                                          // :718-782
+        const bool use_lmeds = true;                                       // :729
+        uint64_t seed = S.epi_seed_;
+        if (S.bdo_random_) {   // as the epipolar stage: a stream per frame, reproducible from (epi_seed_, frame id)
+            uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)(int64_t)pcurframe_->id_ + 1);
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+            seed = z ^ (z >> 31);
+        }
+        seed ^= OV2_P3P_SEED_MIX;   // the two stages of one frame do not draw the same indices
+        ov2_status st = OV2_OK;
+        success = MultiViewGeometry::p3pRansac(ctx_, vbvs, vwpts, S.nransac_iter_, S.fransac_err_, do_optimize, S.bdo_random_,
+                                               (float)c.fx_, (float)c.fy_, Twc, voutliersidx, use_lmeds, seed, &st);
+        if (st != OV2_OK) return st;
+        if (stats) { stats->ran = 1; stats->status = success ? 1 : 0; stats->points = (int)vwpts.size(); }
+        const size_t nbinliers = vwpts.size() - voutliersidx.size();       // :748
+        if (!success || nbinliers < 5 || bad_translation()) {              // :750-761
+            resetFrame();
+            if (stats) stats->reset = 1;
+            return OV2_OK;
+        }
+        pcurframe_->setTwc(Twc);                                           // :766
+        int k = 0;
+        for (const int idx : voutliersidx) {                               // :769-778
+            pmap_->removeObsFromCurFrameById(vkpids.at(idx - k));
+            vkps.erase(vkps.begin() + idx - k);
+            vwpts.erase(vwpts.begin() + idx - k);
+            vkpids.erase(vkpids.begin() + idx - k);
+            vscales.erase(vscales.begin() + idx - k);
+            k++;
+        }
+        if (stats) stats->removed = k;
+        voutliersidx.clear();                                              // :781
+    }
+    success = MultiViewGeometry::ceresPnP(ctx_, vkps, vwpts, vscales, Twc, 5, S.robust_mono_th_, true, S.apply_l2_after_robust_,
+                                          (float)c.fx_, (float)c.fy_, (float)c.cx_, (float)c.cy_, voutliersidx);   // :790-801
+    const size_t nbinliers = vwpts.size() - voutliersidx.size();          // :804
+    if (!success || nbinliers < 5 || voutliersidx.size() > 0.5 * vwpts.size() || bad_translation()) {   // :809-832
+        if (!bdop3p) {
+            bp3preq_ = true;   // "weird results, skipping here and applying p3p next"
+        } else if (S.mono_) {
+            resetFrame();
+            if (stats) stats->reset = 1;
+        }
         return OV2_OK;
     }
-    pcurframe_->setTwc(Twc);                                              // :831
-    bp3preq_ = false;
-    for (const int idx : voutliersidx) pmap_->removeObsFromCurFrameById(vkpids.at(idx));   // :838-841
+    pcurframe_->setTwc(Twc);                                              // :837
+    bp3preq_ = false;                                                     // :841
+    for (const int idx : voutliersidx) pmap_->removeObsFromCurFrameById(vkpids.at(idx));   // :844-847
     return OV2_OK;
 }
 

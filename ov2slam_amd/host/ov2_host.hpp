@@ -258,6 +258,23 @@ public:
     static bool compute5ptEssentialMatrix(ov2_ctx *ctx, const std::vector<Vec3> &bvs1, const std::vector<Vec3> &bvs2,
                                           int nmaxiter, float errth, bool boptimize, uint64_t seed, float fx, float fy,
                                           double Rwc[9], double twc[3], std::vector<int> &voutliersidx, ov2_status *st);
+    // src/multi_view_geometry.cpp:144-163 (-> opengvP3PLMeds :257-343 / opengvP3PRansac :168-254) through
+    // ov2_p3p_ransac_batch with B = 1, the reference's argument order; Twc is written only when the call returns true.
+    // boptimize (OpenGV's nonlinear refinement) is not built: *st = OV2_ERR_UNSUPPORTED.  bdorandom is the reference's
+    // clock seed: here the caller derives the sampler seed from it.
+    static bool p3pRansac(ov2_ctx *ctx, const std::vector<Vec3> &bvs, const std::vector<Vec3> &vwpts, int nmaxiter, float errth,
+                          bool boptimize, bool bdorandom, float fx, float fy, SE3 &Twc, std::vector<int> &voutliersidx,
+                          bool use_lmeds = false, uint64_t seed = 0, ov2_status *st = nullptr);
+};
+
+// mixed into the per-frame sampler seed of the P3P stage, so that it does not repeat the epipolar stage's draws
+#define OV2_P3P_SEED_MIX 0xD1B54A32D192ED03ull
+
+struct P3pStats {   // what the P3P branch of VisualFrontEnd::computePose did on the last frame
+    int ran = 0;             // 1: bp3preq_ || dop3p_ and >= 4 3D keypoints
+    int status = 0;          // p3pRansac's return
+    int points = 0, removed = 0;   // correspondences in, observations removed before ceresPnP
+    int reset = 0;           // 1: the frame ended in resetFrame()
 };
 
 struct EpiStats {   // what VisualFrontEnd::epipolar2d2dFiltering did on the last frame
@@ -315,9 +332,10 @@ public:
         : ctx_(ctx), pslamstate_(pstate), pcurframe_(pframe), pmap_(pmap), ptracker_(ptracker) {}
     ov2_status preprocessImage(const uint8_t *img_raw, int w, int h, int stride);   // :1143-1177
     ov2_status kltTracking();                                                        // :132-275
-    // :657-830 without the P3P-RANSAC branch (OpenGV, out of scope): when P3P is required (bp3preq_ or dop3p_) the
-    // call returns OV2_ERR_UNSUPPORTED and leaves the frame untouched.
-    ov2_status computePose();
+    // :659-851: the P3P-LMedS bootstrap (bp3preq_ or dop3p_; one ov2_p3p_ransac_batch call, correspondences in ascending
+    // lmid order) followed by ceresPnP; a failed P3P ends in resetFrame().
+    ov2_status computePose(P3pStats *stats = nullptr);
+    void resetFrame();                                                               // :1181-1203
     // :446-655, one ov2_epipolar_filter_batch call (RANSAC + the Sampson gate of the 2D keypoints in the same launch); pairs
     // in ascending lmid order.  The mono do_optimize branch (:537-544, :590-608) returns OV2_ERR_UNSUPPORTED.
     ov2_status epipolar2d2dFiltering(EpiStats *stats = nullptr);

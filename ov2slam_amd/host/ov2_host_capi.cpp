@@ -21,6 +21,8 @@ struct HostMap {
     std::shared_ptr<MapManager> map = std::make_shared<MapManager>();
     std::shared_ptr<CameraCalibration> cl = std::make_shared<CameraCalibration>(), cr = std::make_shared<CameraCalibration>();
     LocalBAProblem pb;
+    bool bp3preq = false;    // VisualFrontEnd::bp3preq_, carried from one ov2h_compute_pose call to the next
+    P3pStats last_p3p;       // the P3P branch of the last ov2h_compute_pose
 };
 }  // namespace
 
@@ -115,6 +117,25 @@ int ov2h_set_params(void *p, int klt_use_prior, int stereo_rect, int nklt_pyr_lv
     m->st->klt_use_prior_ = klt_use_prior != 0; m->st->bdo_stereo_rect_ = stereo_rect != 0;
     m->st->nklt_pyr_lvl_ = nklt_pyr_lvl; m->st->nklt_win_size_ = nklt_win_size;
     return 0;
+}
+
+// dop3p / nransac_iter / fransac_err / bdo_random of the YAML for the P3P stage of computePose + the sampler's base seed;
+// clears a pending P3P request
+int ov2h_set_p3p(void *p, int dop3p, int nransac_iter, float fransac_err, int bdo_random, unsigned long long seed)
+{
+    HostMap *m = (HostMap *)p;
+    m->st->dop3p_ = dop3p != 0; m->st->nransac_iter_ = nransac_iter; m->st->fransac_err_ = fransac_err;
+    m->st->bdo_random_ = bdo_random != 0; m->st->epi_seed_ = (uint64_t)seed;
+    m->bp3preq = false;
+    return 0;
+}
+
+// out[5]: what the P3P branch did in the last ov2h_compute_pose: ran, p3pRansac's return, correspondences in, observations
+// removed before ceresPnP, 1 if the frame ended in resetFrame()
+void ov2h_p3p_stats(void *p, double *out)
+{
+    const P3pStats &e = ((HostMap *)p)->last_p3p;
+    out[0] = e.ran; out[1] = e.status; out[2] = e.points; out[3] = e.removed; out[4] = e.reset;
 }
 
 // MapManager::stereoMatching(frame, vleftpyr, vrightpyr) on keyframe kfid; the two pyramids are built here the way
@@ -539,7 +560,9 @@ int ov2h_full_pose_graph(void *p, void *ctx, int n, double *Twc7, const double *
     return s != OV2_OK ? -2 : (ok ? 1 : 0);
 }
 
-// VisualFrontEnd::computePose on keyframe `kfid` taken as the current frame, starting from pose Twc7_init
+// VisualFrontEnd::computePose on keyframe `kfid` taken as the current frame, starting from pose Twc7_init.  The P3P request
+// (bp3preq_) is kept between calls, as the front-end keeps it between frames: a call that sets it makes the next one run
+// the P3P branch (see ov2h_p3p_stats).
 int ov2h_compute_pose(void *p, void *ctx, int kfid, const double *Twc7_init, int *p3p_req)
 {
     HostMap *m = (HostMap *)p;
@@ -550,7 +573,9 @@ int ov2h_compute_pose(void *p, void *ctx, int kfid, const double *Twc7_init, int
     f->setTwc(T0);
     m->map->pcurframe_ = f;
     VisualFrontEnd fe((ov2_ctx *)ctx, m->st, f, m->map, nullptr);
-    const ov2_status s = fe.computePose();
+    fe.bp3preq_ = m->bp3preq;
+    const ov2_status s = fe.computePose(&m->last_p3p);
+    m->bp3preq = fe.bp3preq_;
     if (p3p_req) *p3p_req = fe.bp3preq_ ? 1 : 0;
     return s;
 }
@@ -606,6 +631,29 @@ int ov2h_compute5pt(void *ctx, int n, const double *bvs1, const double *bvs2, in
     return ok ? 1 : 0;
 }
 
+// MultiViewGeometry::p3pRansac (src/multi_view_geometry.cpp:144-163) with the reference's arguments: returns its bool (0 / 1)
+// or a negative ov2_status; Twc7 is updated when it returns 1, outidx[n] the voutliersidx (count in *n_out)
+int ov2h_p3p_ransac(void *ctx, int n, const double *bvs, const double *wpts, int nmaxiter, float errth, int boptimize,
+                    int bdorandom, float fx, float fy, int use_lmeds, unsigned long long seed, double *Twc7, int *outidx, int *n_out)
+{
+    std::vector<Vec3> a((size_t)n), b((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        a[i] = Vec3{bvs[3 * i], bvs[3 * i + 1], bvs[3 * i + 2]};
+        b[i] = Vec3{wpts[3 * i], wpts[3 * i + 1], wpts[3 * i + 2]};
+    }
+    SE3 T;
+    for (int i = 0; i < 7; ++i) T.v[i] = Twc7[i];
+    std::vector<int> out;
+    ov2_status st = OV2_OK;
+    const bool ok = MultiViewGeometry::p3pRansac((ov2_ctx *)ctx, a, b, nmaxiter, errth, boptimize != 0, bdorandom != 0, fx, fy, T, out,
+                                                 use_lmeds != 0, seed, &st);
+    if (st != OV2_OK) return (int)st;
+    for (int i = 0; i < 7; ++i) Twc7[i] = T.v[i];
+    for (size_t i = 0; i < out.size(); ++i) outidx[i] = out[i];
+    *n_out = (int)out.size();
+    return ok ? 1 : 0;
+}
+
 int ov2h_get_pose(void *p, int kfid, double *Twc7)
 {
     auto f = ((HostMap *)p)->map->getKeyframe(kfid);
@@ -629,6 +677,23 @@ int ov2h_count_keypoints(void *p, int kfid, int *nbkps, int *nb3d, int *nbstereo
     if (!f) return -1;
     *nbkps = (int)f->nbkps_; *nb3d = (int)f->nb3dkps_; *nbstereo = (int)f->nb_stereo_kps_;
     return 0;
+}
+
+// out[5]: nbkps_, nb2dkps_, nb3dkps_, nb_stereo_kps_, noccupcells_ of keyframe kfid
+int ov2h_frame_counters(void *p, int kfid, int *out)
+{
+    auto f = ((HostMap *)p)->map->getKeyframe(kfid);
+    if (!f) return -1;
+    out[0] = (int)f->nbkps_; out[1] = (int)f->nb2dkps_; out[2] = (int)f->nb3dkps_; out[3] = (int)f->nb_stereo_kps_;
+    out[4] = (int)f->noccupcells_;
+    return 0;
+}
+
+// MapPoint::isobs_ of landmark lmid (1 / 0), -1 if the map does not hold it
+int ov2h_landmark_isobs(void *p, int lmid)
+{
+    auto lm = ((HostMap *)p)->map->getMapPoint(lmid);
+    return lm ? (lm->isobs_ ? 1 : 0) : -1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -723,6 +788,17 @@ void ov2h_slam_epi_stats(void *p, double *out)
 {
     const EpiStats &e = ((SlamManager *)p)->last_epi_;
     out[0] = e.status; out[1] = e.pairs; out[2] = e.removed; out[3] = e.gate_removed;
+}
+
+// dop3p of the YAML: computePose runs the P3P-LMedS bootstrap on every frame (nransac_iter, fransac_err, bdo_random and the
+// base seed are those of ov2h_slam_set_epipolar)
+void ov2h_slam_set_p3p(void *p, int dop3p) { ((SlamManager *)p)->pslamstate_->dop3p_ = dop3p != 0; }
+
+// out[5] of the last frame: the P3P branch ran, p3pRansac's return, correspondences in, observations removed, resetFrame()
+void ov2h_slam_p3p_stats(void *p, double *out)
+{
+    const P3pStats &e = ((SlamManager *)p)->last_p3p_;
+    out[0] = e.ran; out[1] = e.status; out[2] = e.points; out[3] = e.removed; out[4] = e.reset;
 }
 
 // out[3] of the last frame (keyframes only): keypoints described, local map points offered to matchToMap, merges

@@ -125,6 +125,7 @@ ov2_status SlamManager::addNewStereoImages(double time, const uint8_t *im0, cons
     pcurframe_->id_ = frame_id_; pcurframe_->img_time_ = time;   // Frame::updateFrame
     last_ = SlamStats();
     last_epi_ = EpiStats();
+    last_p3p_ = P3pStats();
     last_.frame = frame_id_;
     ov2_status st = OV2_OK;
     imraw_ = im0; imw_ = w; imh_ = h; imstride_ = stride; raw_pyr_ = Pyramid();
@@ -166,7 +167,7 @@ bool SlamManager::trackMono(const uint8_t *im, int w, int h, int stride, double 
     pcurframe_->setTwc(Twc);
     if ((*st = fe.kltTracking()) != OV2_OK) return false;
     if (pslamstate_->doepipolar_ && (*st = fe.epipolar2d2dFiltering(&last_epi_)) != OV2_OK) return false;   // :93
-    if ((*st = fe.computePose()) != OV2_OK) return false;
+    if ((*st = fe.computePose(&last_p3p_)) != OV2_OK) return false;
     if (!policy_.compose_motion) motion_model_.updateMotionModel(pcurframe_->Twc_, time);
     if (policy_.kf_every > 0) return pcurframe_->id_ % policy_.kf_every == 0;
     return checkNewKfReq();

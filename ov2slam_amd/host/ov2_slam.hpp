@@ -9,8 +9,10 @@
 //   SlamManager::run (one image)     src/ov2slam.cpp:152-205    Estimator::applyLocalBA  src/estimator.cpp:67-98
 // The reference runs front-end, mapper and estimator on three threads; here one call processes one stereo frame to the
 // end (keyframe work included), i.e. the reference with bforce_realtime = 0 and an idle back-end: deterministic.
-// VisualFrontEnd::epipolar2d2dFiltering :446-655 runs with doepipolar_ (ov2_epipolar_filter_batch).
-// Out of scope and refused loudly where reached: P3P (OpenGV), the mono branch of the epipolar filter, loop closing.
+// VisualFrontEnd::epipolar2d2dFiltering :446-655 runs with doepipolar_ (ov2_epipolar_filter_batch); computePose runs its
+// P3P-LMedS bootstrap (ov2_p3p_ransac_batch) when tracking asks for it (bp3preq_) or dop3p_ is set, and resetFrame() where
+// that fails.
+// Out of scope and refused loudly where reached: the mono branch of the epipolar filter, loop closing.
 #pragma once
 #include "ov2_host.hpp"
 
@@ -82,6 +84,7 @@ public:
     int frame_id_ = -1;
     SlamStats last_;
     EpiStats last_epi_;   // epipolar2d2dFiltering on the last frame (doepipolar_)
+    P3pStats last_p3p_;   // the P3P branch of computePose on the last frame (bp3preq_ or dop3p_)
     std::vector<SlamStats> stats_;
     std::vector<SE3> traj_;
 

@@ -72,6 +72,17 @@ def lib():
         L.ov2h_slam_set_epipolar.restype = None
         L.ov2h_slam_epi_stats.argtypes = [C.c_void_p, dp]
         L.ov2h_slam_epi_stats.restype = None
+        L.ov2h_slam_set_p3p.argtypes = [C.c_void_p, C.c_int]
+        L.ov2h_slam_set_p3p.restype = None
+        L.ov2h_slam_p3p_stats.argtypes = [C.c_void_p, dp]
+        L.ov2h_slam_p3p_stats.restype = None
+        L.ov2h_set_p3p.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_ulonglong]
+        L.ov2h_p3p_stats.argtypes = [C.c_void_p, dp]
+        L.ov2h_p3p_stats.restype = None
+        L.ov2h_p3p_ransac.argtypes = [C.c_void_p, C.c_int, dp, dp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float,
+                                      C.c_int, C.c_ulonglong, dp, ip, ip]
+        L.ov2h_frame_counters.argtypes = [C.c_void_p, C.c_int, ip]
+        L.ov2h_landmark_isobs.argtypes = [C.c_void_p, C.c_int]
         L.ov2h_slam_device_handle.argtypes = [C.c_void_p]
         L.ov2h_slam_device_handle.restype = C.c_void_p
         L.ov2h_slam_flush_device.argtypes = [C.c_void_p]
@@ -374,6 +385,18 @@ class HostMap:
         st = lib().ov2h_compute_pose(self.h, ctx.h, kfid, _dp(np.ascontiguousarray(Twc_init, np.float64)), C.byref(req))
         return st, bool(req.value)
 
+    def set_p3p(self, dop3p=True, nransac_iter=100, fransac_err=3.0, bdo_random=False, seed=0):
+        """dop3p / nransac_iter / fransac_err / bdo_random of the YAML for the P3P stage of computePose; seed = the sampler's
+        base seed.  Clears a pending P3P request."""
+        lib().ov2h_set_p3p(self.h, int(bool(dop3p)), int(nransac_iter), float(fransac_err), int(bool(bdo_random)),
+                           int(seed) & ((1 << 64) - 1))
+
+    def p3p_stats(self):
+        """what the P3P branch did in the last compute_pose: dict(ran, status, points, removed, reset)"""
+        e = np.zeros(5)
+        lib().ov2h_p3p_stats(self.h, _dp(e))
+        return dict(ran=int(e[0]), status=int(e[1]), points=int(e[2]), removed=int(e[3]), reset=int(e[4]))
+
     def structure_only_ba(self, ctx, lmids):
         """Optimizer::structureOnlyBA(vlm2optids) (src/optimizer.cpp:2594-2781). returns (status, final cost, LM iterations)"""
         ids = np.ascontiguousarray(lmids, np.int32)
@@ -473,6 +496,10 @@ class CppSlam:
             e = np.zeros(4)
             lib().ov2h_slam_epi_stats(self.h_, _dp(e))
             self.epi_stats.append(dict(status=int(e[0]), pairs=int(e[1]), removed=int(e[2]), gate_removed=int(e[3])))
+        if getattr(self, "p3p_stats", None) is not None:
+            e = np.zeros(5)
+            lib().ov2h_slam_p3p_stats(self.h_, _dp(e))
+            self.p3p_stats.append(dict(ran=int(e[0]), status=int(e[1]), points=int(e[2]), removed=int(e[3]), reset=int(e[4])))
         if getattr(self, "kf_stats", None) is not None and self.stats[-1]["kf"]:
             k = np.zeros(3)
             lib().ov2h_slam_kf_stats(self.h_, _dp(k))
@@ -493,6 +520,13 @@ class CppSlam:
         lib().ov2h_slam_set_epipolar(self.h_, int(bool(on)), int(nransac_iter), float(fransac_err), int(bool(bdo_random)),
                                      int(seed) & ((1 << 64) - 1))
         self.epi_stats = []
+
+    def set_p3p(self, dop3p=True):
+        """dop3p of the YAML: computePose runs the P3P-LMedS bootstrap (ov2_p3p_ransac_batch) on every frame, not only when
+        tracking asks for it; iterations, error bound and seed are those of set_epipolar.  Starts the per-frame p3p_stats list
+        (also useful with dop3p off: the branch runs whenever bp3preq_ is set)."""
+        lib().ov2h_slam_set_p3p(self.h_, int(bool(dop3p)))
+        self.p3p_stats = []
 
     def check_map(self):
         """(violations of the host map's invariants, total) -- see ov2h_slam_check_map"""
@@ -657,6 +691,20 @@ def compute5pt_essential(ctx, bvs1, bvs2, nmaxiter, errth, boptimize, fx, fy, se
     return bool(r), R.reshape(3, 3), t, out[:nout.value].copy()
 
 
+def p3p_ransac(ctx, bvs, vwpts, nmaxiter, errth, boptimize, bdorandom, fx, fy, Twc, use_lmeds=True, seed=0):
+    """the C++ MultiViewGeometry::p3pRansac (src/multi_view_geometry.cpp:144-163) over the C ABI.
+    returns (success, Twc (7,), voutliersidx); a negative status raises"""
+    b, x = np.ascontiguousarray(bvs, np.float64).reshape(-1, 3), np.ascontiguousarray(vwpts, np.float64).reshape(-1, 3)
+    n = len(b)
+    T, out, nout = np.array(Twc, np.float64), np.zeros(max(n, 1), np.int32), C.c_int(0)
+    r = lib().ov2h_p3p_ransac(ctx.h, n, _dp(b), _dp(x), int(nmaxiter), float(errth), int(bool(boptimize)), int(bool(bdorandom)),
+                              float(fx), float(fy), int(bool(use_lmeds)), int(seed), _dp(T), out.ctypes.data_as(C.POINTER(C.c_int)),
+                              C.byref(nout))
+    if r < 0:
+        raise RuntimeError(f"p3pRansac: status {r}")
+    return bool(r), T, out[:nout.value].copy()
+
+
 class TwoViewMap:
     """two keyframes of the C++ host mirror with chosen keypoints (pixels, 2D / 3D), to run
     VisualFrontEnd::epipolar2d2dFiltering with one as the previous keyframe and the other as the current frame"""
@@ -736,6 +784,38 @@ class FrontEndFrame:
                                      i3.ctypes.data_as(u8), ist.ctypes.data_as(u8), rp.ctypes.data_as(fpp))
         assert 0 <= n <= cap
         return {int(lm[k]): (px[k].copy(), bool(i3[k]), bool(ist[k]), rp[k].copy()) for k in range(n)}
+
+    # -- VisualFrontEnd::computePose on this frame (the P3P stage included) ---------------------------------------------
+    def set_p3p(self, dop3p=True, nransac_iter=100, fransac_err=3.0, bdo_random=False, seed=0):
+        """dop3p / nransac_iter / fransac_err / bdo_random of the YAML + the sampler's base seed; clears a pending P3P request"""
+        lib().ov2h_set_p3p(self.h, int(bool(dop3p)), int(nransac_iter), float(fransac_err), int(bool(bdo_random)),
+                           int(seed) & ((1 << 64) - 1))
+
+    def compute_pose(self, ctx, Twc_init):
+        """computePose from pose Twc_init; the P3P request is kept between calls. returns (status, p3p requested)"""
+        req = C.c_int()
+        st = lib().ov2h_compute_pose(self.h, ctx.h, 0, _dp(np.ascontiguousarray(Twc_init, np.float64)), C.byref(req))
+        return st, bool(req.value)
+
+    def p3p_stats(self):
+        """what the P3P branch did in the last compute_pose: dict(ran, status, points, removed, reset)"""
+        e = np.zeros(5)
+        lib().ov2h_p3p_stats(self.h, _dp(e))
+        return dict(ran=int(e[0]), status=int(e[1]), points=int(e[2]), removed=int(e[3]), reset=int(e[4]))
+
+    def pose(self):
+        out = np.zeros(7)
+        assert lib().ov2h_get_pose(self.h, 0, _dp(out)) == 0
+        return out
+
+    def counters(self):
+        """dict(nbkps, nb2dkps, nb3dkps, nb_stereo_kps, noccupcells) of the frame"""
+        c = np.zeros(5, np.int32)
+        assert lib().ov2h_frame_counters(self.h, 0, c.ctypes.data_as(C.POINTER(C.c_int))) == 0
+        return dict(zip(("nbkps", "nb2dkps", "nb3dkps", "nb_stereo_kps", "noccupcells"), c.tolist()))
+
+    def landmark_isobs(self, lmid):
+        return lib().ov2h_landmark_isobs(self.h, int(lmid))
 
     def frl(self):
         F = np.zeros(9)

@@ -1,6 +1,6 @@
-"""Host-side mirror of MultiViewGeometry::ceresPnP (reference include/multi_view_geometry.hpp:104,
-src/multi_view_geometry.cpp:492-586) over the C ABI.  The LM loop, the chi2 flags and the L2 re-solve run inside one
-HIP kernel (csrc/pnp.hip); this file only marshals arrays.  No arithmetic happens here."""
+"""Host-side mirror of the reference's static MultiViewGeometry helpers (ceresPnP, compute5ptEssentialMatrix, p3pRansac,
+triangulate; reference include/multi_view_geometry.hpp, src/multi_view_geometry.cpp) over the C ABI.  The solves run in HIP
+kernels (csrc/pnp.hip, epipolar.hip, p3p.hip, tri.hip); this file only marshals arrays.  No arithmetic happens here."""
 import numpy as np
 
 from .frontend import _check
@@ -149,3 +149,55 @@ class MultiViewGeometry:
         c = self.ctx
         _check(c.h, c.lib.ov2_dbg_fivept(c.h, n, _vp(bv1), _vp(bv2), _vp(E), _vp(ns)))
         return E[:n].reshape(n, 10, 3, 3), ns[:n]
+
+    # -- the P3P stage of computePose (csrc/p3p.hip) --------------------------------------------------------------------
+    def p3pRansac(self, bvs, vwpts, nmaxiter, errth, boptimize, bdorandom, fx, fy, Twc=None, use_lmeds=True, seed=0):
+        """MultiViewGeometry::p3pRansac (src/multi_view_geometry.cpp:144-163 -> opengvP3PLMeds :257-343 / opengvP3PRansac
+        :168-254) through ov2_p3p_ransac_batch with B = 1.  returns (success, Twc (7,) [t, qx qy qz qw] -- the argument
+        unchanged unless success --, voutliersidx (sorted int array)).  bdorandom only selects the seed in the C++ mirror
+        (the caller passes it here); boptimize = True (OpenGV's nonlinear refinement) is not built."""
+        if boptimize:
+            raise NotImplementedError("p3pRansac: boptimize (OpenGV optimizeModelCoefficients) is not built")
+        T0 = np.array([0, 0, 0, 0, 0, 0, 1.]) if Twc is None else np.asarray(Twc, np.float64)
+        r = self.p3pRansac_batch([bvs], [vwpts], nmaxiter, errth, np.array([[fx, fy, 0., 0.]]), [seed], use_lmeds, T0[None])
+        return bool(r["status"][0]), r["Twc"][0], np.flatnonzero(r["outlier"][0]).astype(np.int32)
+
+    def p3pRansac_batch(self, bvs_list, wpts_list, nmaxiter, errth, K, seeds, use_lmeds=True, Twc0=None):
+        """B frames in one call (ov2_p3p_ransac_batch).  returns dict(status (B,), Twc (B,7), outlier [mask per frame],
+        info (B,4): counted draws, skipped draws, chosen draw, inliers)."""
+        B = len(bvs_list)
+        n = np.array([len(np.asarray(b).reshape(-1, 3)) for b in bvs_list], np.int32)
+        if any(len(np.asarray(x).reshape(-1, 3)) != k for x, k in zip(wpts_list, n)):
+            raise ValueError("bvs.size() != vwpts.size()")       # the reference asserts (:263)
+        cat = lambda xs: (np.concatenate([np.asarray(x, np.float64).reshape(-1, 3) for x in xs]) if B and n.sum()
+                          else np.zeros((1, 3)))
+        bv, X = np.ascontiguousarray(cat(bvs_list)), np.ascontiguousarray(cat(wpts_list))
+        K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(B, 4))
+        sd = np.ascontiguousarray(np.asarray(seeds, np.uint64).reshape(B))
+        T = np.ascontiguousarray(np.tile([0, 0, 0, 0, 0, 0, 1.], (max(B, 1), 1)) if Twc0 is None
+                                 else np.array(Twc0, np.float64).reshape(B, 7))
+        outl = np.zeros(max(int(n.sum()), 1), np.uint8)
+        st, info = np.zeros(max(B, 1), np.int32), np.zeros((max(B, 1), 4), np.int32)
+        c = self.ctx
+        _check(c.h, c.lib.ov2_p3p_ransac_batch(c.h, B, _vp(n), _vp(bv), _vp(X), _vp(K), int(nmaxiter), float(errth),
+                                               int(bool(use_lmeds)), _vp(sd), _vp(T), _vp(outl), _vp(st), _vp(info)))
+        off = np.concatenate([[0], np.cumsum(n)])
+        return dict(status=st[:B], Twc=T[:B], info=info[:B], outlier=[outl[off[b]:off[b + 1]].astype(bool) for b in range(B)])
+
+    def p3pRansac_batch_dev(self, B, d_off, d_bvs, d_wpts, d_K, nmaxiter, errth, use_lmeds, d_seed, d_Twc, d_outlier,
+                            d_status, d_info=None):
+        """device-resident, asynchronous form (ov2_p3p_ransac_batch_dev): DeviceArrays in, nothing synchronised."""
+        p = lambda a: None if a is None else a.ptr
+        c = self.ctx
+        _check(c.h, c.lib.ov2_p3p_ransac_batch_dev(c.h, int(B), p(d_off), p(d_bvs), p(d_wpts), p(d_K), int(nmaxiter),
+                                                   float(errth), int(bool(use_lmeds)), p(d_seed), p(d_Twc), p(d_outlier),
+                                                   p(d_status), p(d_info)))
+
+    def dbg_p3p(self, bv, X):
+        """the device P3P solver on n samples (ov2_dbg_p3p): bv, X (n,3,3) -> R (n,4,3,3), t (n,4,3), nsol (n,)"""
+        bv, X = np.ascontiguousarray(bv, np.float64).reshape(-1, 3, 3), np.ascontiguousarray(X, np.float64).reshape(-1, 3, 3)
+        n = len(bv)
+        R, t, ns = np.zeros((max(n, 1), 4, 9)), np.zeros((max(n, 1), 4, 3)), np.zeros(max(n, 1), np.int32)
+        c = self.ctx
+        _check(c.h, c.lib.ov2_dbg_p3p(c.h, n, _vp(bv), _vp(X), _vp(R), _vp(t), _vp(ns)))
+        return R[:n].reshape(n, 4, 3, 3), t[:n], ns[:n]

@@ -16,7 +16,7 @@ this synthetic sequence with exact ground truth stands in for "results match the
 frames").  The loop itself is bookkeeping (ids, lists, the flat BA problem); no arithmetic of the path happens here.
 Simplifications against the reference, all deterministic: a keyframe every `kf_every` frames instead of the parallax /
 track-count heuristics of checkNewKfReq; the local-BA window is the last `ba_window` keyframes (oldest `ba_fixed`
-constant) instead of the covisibility walk (tested separately, tests/test_map_gpu.py); no P3P / map tracking / loop closing."""
+constant) instead of the covisibility walk (tested separately, tests/test_map_gpu.py); no P3P bootstrap (the C++ loop, ov2::SlamManager, has it) / map tracking / loop closing."""
 import numpy as np
 
 from . import synth_ba
