@@ -10,8 +10,13 @@
 // at least one cell apart while a mask disc has radius cell/4, so one launch per colour runs its cells in parallel
 // without interaction and the four launches reproduce the sequential result exactly.
 //
-// Kernels: det_mask_kernel (occupancy + discs of the existing keypoints), det_mineig_kernel / det_fast_kernel (one
-// workgroup per cell: response map in LDS, masked arg-max, disc, second arg-max), subpix_kernel (one wave per point).
+// Kernels: det_mask_kernel (occupancy + discs of the existing keypoints, eight lanes per keypoint), det_worklist_kernel
+// (one sweep per image lists the free cells of the four colours), det_mineig_kernel / det_fast_kernel (a workgroup per
+// free cell: response map in LDS, masked arg-max, disc, second arg-max), det_assemble_kernel, subpix_kernel (four points
+// per wave).  The list lengths stay on the device: the grids of the cell and cornerSubPix launches are upper bounds and
+// their workgroups compare against the device-side count (the ones beyond it retire while the others work: bounded,
+// striding grids were measured and are not faster).  One fill zeroes counters, occupancy, per-cell
+// outputs and the mask (0 = free, non-zero = masked) in front of a call.
 #include "ov2_internal.h"
 
 #include <cmath>
@@ -57,7 +62,7 @@ __device__ __forceinline__ int reflect101(int i, int n)
     return i;
 }
 
-// all threads of the workgroup zero the disc around (cx, cy) in the w x h mask
+// all threads of the workgroup mark the disc around (cx, cy) in the w x h mask
 __device__ __forceinline__ void draw_disc(unsigned char *mask, int w, int h, int cx, int cy, const disc_shape &ds)
 {
     const int side = 2 * ds.r + 1;
@@ -65,27 +70,40 @@ __device__ __forceinline__ void draw_disc(unsigned char *mask, int w, int h, int
         const int oy = i / side - ds.r, ox = i % side - ds.r;
         const int hw = ds.hw[ds.r + oy];
         const int x = cx + ox, y = cy + oy;
-        if (hw >= 0 && ox >= -hw && ox <= hw && x >= 0 && x < w && y >= 0 && y < h) mask[(size_t)y * w + x] = 0;
+        if (hw >= 0 && ox >= -hw && ox <= hw && x >= 0 && x < w && y >= 0 && y < h) mask[(size_t)y * w + x] = 1;
     }
 }
 
 // existing keypoints: occupancy of their grid cell (voccupcells, :316-320 / :466-470) + their discs in the mask.
-// One wave per keypoint; `valid` (optional) marks the keypoints that count (e.g. the tracking status).
-__global__ __launch_bounds__(64) void det_mask_kernel(const float2 *__restrict__ cur, const int *__restrict__ cur_img,
-                                                      const unsigned char *__restrict__ valid, int n_cur, int cell,
-                                                      int nwcells, int nhcells, unsigned char *__restrict__ occ_all,
-                                                      unsigned char *__restrict__ mask_all, int w, int h, disc_shape ds)
+// DET_MASK_LANES lanes per keypoint: lane j of the group walks the spans of disc rows j, j + DET_MASK_LANES, ...  All
+// stores write 1, so keypoints that overlap need no order.  `valid` (optional) marks the keypoints that count (e.g. the
+// tracking status).
+#define DET_MASK_LANES 8
+#define DET_MASK_KPS (256 / DET_MASK_LANES)   // keypoints per workgroup and trip
+__global__ __launch_bounds__(256) void det_mask_kernel(const float2 *__restrict__ cur, const int *__restrict__ cur_img,
+                                                       const unsigned char *__restrict__ valid, int n_cur, int cell,
+                                                       int nwcells, int nhcells, unsigned char *__restrict__ occ_all,
+                                                       unsigned char *__restrict__ mask_all, int w, int h, disc_shape ds)
 {
-    for (int k = blockIdx.x; k < n_cur; k += gridDim.x) {
+    const int sub = threadIdx.x % DET_MASK_LANES;
+    for (int k = blockIdx.x * DET_MASK_KPS + threadIdx.x / DET_MASK_LANES; k < n_cur; k += gridDim.x * DET_MASK_KPS) {
         if (valid && !valid[k]) continue;
         const float2 p = cur[k];
         const int bimg = cur_img[k];
-        if (threadIdx.x == 0) {
+        if (sub == 0) {
             const int cr = (int)(p.y / (float)cell), cc = (int)(p.x / (float)cell);
             if (cr >= 0 && cr <= nhcells && cc >= 0 && cc <= nwcells)
                 occ_all[(size_t)bimg * (nhcells + 1) * (nwcells + 1) + cr * (nwcells + 1) + cc] = 1;
         }
-        draw_disc(mask_all + (size_t)bimg * w * h, w, h, (int)__builtin_rintf(p.x), (int)__builtin_rintf(p.y), ds);
+        unsigned char *mask = mask_all + (size_t)bimg * w * h;
+        const int cx = (int)__builtin_rintf(p.x), cy = (int)__builtin_rintf(p.y);
+        if (cx < -ds.r || cx >= w + ds.r || cy < -ds.r || cy >= h + ds.r) continue;   // no pixel of the disc is inside
+        for (int row = sub; row <= 2 * ds.r; row += DET_MASK_LANES) {
+            const int hw = ds.hw[row], y = cy + row - ds.r;
+            if (hw < 0 || y < 0 || y >= h) continue;
+            const int xa = max(cx - hw, 0), xb = min(cx + hw, w - 1);
+            for (int x = xa; x <= xb; ++x) mask[(size_t)y * w + x] = 1;
+        }
     }
 }
 
@@ -105,48 +123,71 @@ __device__ __forceinline__ int block_rank_256(bool flag, int *sh4, int *total)
 }
 
 // one workgroup per image: the free, border-valid cells (:338-350) of each colour are appended to the four global
-// work lists (one atomic per image and colour reserves the range; the order inside a colour is irrelevant)
+// work lists (one atomic per image and colour reserves the range; the order inside a colour is irrelevant).  ONE sweep
+// over the occupancy bytes: a thread keeps the flags and colours of its cells (cell tid + 256 k = bit k) in registers
+// and its four per-colour counts in the 16-bit fields of one word, a single block scan of that word gives every
+// thread its place in the four ranges, and the placement walks the set bits.  Images of more than 64 x 256 cells take
+// the sweep in chunks.  The image's number of occupied cells (nboccup of the reference) is counted on the way.
+#define DET_WL_TRIPS 64
 __global__ __launch_bounds__(256) void det_worklist_kernel(int cell, int nwcells, int nhcells, int w, int h,
                                                            const unsigned char *__restrict__ occ_all,
                                                            int2 *__restrict__ work /* 4 lists of list_cap */, int list_cap,
-                                                           unsigned *__restrict__ wcount /* [4] */)
+                                                           unsigned *__restrict__ wcount /* [4] */,
+                                                           int *__restrict__ nocc_all /* [images] */)
 {
-    __shared__ int sh4[4];
+    __shared__ unsigned long long shw[4];
     __shared__ int base[4];
-    const int b = blockIdx.x, nb = nwcells * nhcells, tid = threadIdx.x;
+    const int b = blockIdx.x, nb = nwcells * nhcells, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const unsigned char *occ = occ_all + (size_t)b * (nhcells + 1) * (nwcells + 1);
-    for (int colour = 0; colour < 4; ++colour) {
-        int done = 0;   // cells of this colour already placed (block-uniform)
-        // pass 1: count, pass 2: place -- two passes keep the reservation to one atomic per (image, colour)
-        int cnt = 0;
-        for (int i0 = 0; i0 < nb; i0 += 256) {
-            const int i = i0 + tid;
-            bool f = false;
-            if (i < nb) {
-                const int rr = i / nwcells, cc = i - rr * nwcells;
-                f = ((rr & 1) * 2 + (cc & 1)) == colour && !occ[rr * (nwcells + 1) + cc] &&
-                    (cc * cell + cell < w - 1 && rr * cell + cell < h - 1);
+    const int step_r = 256 / nwcells, step_c = 256 % nwcells;   // (row, column) of cell i + 256 from those of cell i
+    int nocc = 0;
+    for (int c0 = 0; c0 < nb; c0 += DET_WL_TRIPS * 256) {
+        unsigned long long fl = 0, col_lo = 0, col_hi = 0, cnt = 0;
+        int i = c0 + tid, rr = i / nwcells, cc = i - rr * nwcells;
+        for (int k = 0; k < DET_WL_TRIPS && i < nb; ++k, i += 256) {
+            const bool oc = occ[rr * (nwcells + 1) + cc] != 0;
+            nocc += oc;
+            if (!oc && cc * cell + cell < w - 1 && rr * cell + cell < h - 1) {
+                fl |= 1ull << k;
+                col_lo |= (unsigned long long)(cc & 1) << k;
+                col_hi |= (unsigned long long)(rr & 1) << k;
+                cnt += 1ull << (16 * ((rr & 1) * 2 + (cc & 1)));   // a chunk has 2^14 cells: the fields cannot carry
             }
-            int tot;
-            (void)block_rank_256(f, sh4, &tot);
-            cnt += tot;
+            cc += step_c;
+            rr += step_r;
+            if (cc >= nwcells) { cc -= nwcells; ++rr; }
         }
-        if (tid == 0) base[colour] = cnt ? (int)atomicAdd(&wcount[colour], (unsigned)cnt) : 0;
+        unsigned long long inc = cnt;   // inclusive scan over the wave, all four fields at once
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long t = __shfl_up(inc, o);
+            if (lane >= o) inc += t;
+        }
+        if (lane == 63) shw[wv] = inc;
         __syncthreads();
-        for (int i0 = 0; i0 < nb; i0 += 256) {
-            const int i = i0 + tid;
-            bool f = false;
-            if (i < nb) {
-                const int rr = i / nwcells, cc = i - rr * nwcells;
-                f = ((rr & 1) * 2 + (cc & 1)) == colour && !occ[rr * (nwcells + 1) + cc] &&
-                    (cc * cell + cell < w - 1 && rr * cell + cell < h - 1);
-            }
-            int tot;
-            const int rank = block_rank_256(f, sh4, &tot);
-            if (f) work[(size_t)colour * list_cap + base[colour] + done + rank] = make_int2(b, i);
-            done += tot;
+        unsigned long long pre = inc - cnt, tot = 0;
+        for (int k = 0; k < 4; ++k) {
+            if (k < wv) pre += shw[k];
+            tot += shw[k];
         }
+        if (tid < 4) {
+            const unsigned n = (unsigned)(tot >> (16 * tid)) & 0xffffu;
+            base[tid] = n ? (int)atomicAdd(&wcount[tid], n) : 0;
+        }
+        __syncthreads();
+        while (fl) {
+            const int k = __ffsll((long long)fl) - 1;
+            fl &= fl - 1;
+            const int colour = (int)((col_hi >> k) & 1) * 2 + (int)((col_lo >> k) & 1);
+            const int pos = base[colour] + (int)((pre >> (16 * colour)) & 0xffffu);
+            pre += 1ull << (16 * colour);
+            work[(size_t)colour * list_cap + pos] = make_int2(b, c0 + k * 256 + tid);
+        }
+        __syncthreads();   // shw / base are written again by the next chunk and by the sum below
     }
+    for (int o = 32; o > 0; o >>= 1) nocc += __shfl_xor(nocc, o);
+    if (lane == 0) base[wv] = nocc;
+    __syncthreads();
+    if (tid == 0) nocc_all[b] = base[0] + base[1] + base[2] + base[3];
 }
 
 // ordered key: larger value wins, on ties the smaller index (cv::minMaxLoc returns the first maximum)
@@ -180,7 +221,7 @@ struct det_out {          // per cell
 // 1/(2n) away from every integer, far more than the fp32 error of the product
 __device__ __forceinline__ int div_small(int p, float inv_n) { return (int)(((float)p + 0.5f) * inv_n); }
 
-// zero the disc around (cx, cy) in the global mask and in the cell-local copy mk (cell origin x0,y0, side n)
+// mark the disc around (cx, cy) in the global mask and in the cell-local copy mk (cell origin x0,y0, side n)
 __device__ __forceinline__ void draw_disc_both(unsigned char *mask, int w, int h, unsigned char *mk, int x0, int y0, int n,
                                                int cx, int cy, const disc_shape &ds)
 {
@@ -192,9 +233,9 @@ __device__ __forceinline__ void draw_disc_both(unsigned char *mask, int w, int h
         const int hw = ds.hw[ds.r + oy];
         const int x = cx + ox, y = cy + oy;
         if (hw >= 0 && ox >= -hw && ox <= hw && x >= 0 && x < w && y >= 0 && y < h) {
-            mask[(size_t)y * w + x] = 0;
+            mask[(size_t)y * w + x] = 1;
             const int lx = x - x0, ly = y - y0;
-            if (lx >= 0 && lx < n && ly >= 0 && ly < n) mk[ly * n + lx] = 0;
+            if (lx >= 0 && lx < n && ly >= 0 && ly < n) mk[ly * n + lx] = 1;
         }
     }
 }
@@ -283,7 +324,7 @@ __global__ __launch_bounds__(256) void det_mineig_kernel(const unsigned char *__
     for (int pass = 0; pass < 2; ++pass) {
         unsigned long long key = argmax_key(-3.4028234663852886e38f, 0x7ffffffe);
         for (int p = tid; p < n2; p += nth) {
-            const float v = mk[p] ? hmap[p] : 0.f;
+            const float v = mk[p] ? 0.f : hmap[p];
             const unsigned long long k2 = argmax_key(v, p);
             key = k2 > key ? k2 : key;
         }
@@ -346,7 +387,7 @@ __device__ inline int fast_score(const unsigned char *p, int stride, int thresho
     return -b0 - 1;
 }
 
-// detectGridFAST: one workgroup per cell of the current colour
+// detectGridFAST: one workgroup per free cell of the current colour
 __global__ __launch_bounds__(256) void det_fast_kernel(const unsigned char *__restrict__ img0, size_t img_bstride,
                                                        int istride, int w, int h, int cell, int nwcells, int nhcells,
                                                        const int2 *__restrict__ work,
@@ -388,7 +429,7 @@ __global__ __launch_bounds__(256) void det_fast_kernel(const unsigned char *__re
                 if ((j || ii) && !(s > score[(y + j) * n + x + ii])) nms = false;
         if (!nms) continue;
         // the reference passes its CV_32F mask to FastFeatureDetector::detect, which reads it as bytes (oracle header)
-        if ((x & 3) < 2 || !mask[(size_t)(y0 + y) * w + x0 + (x >> 2)]) continue;
+        if ((x & 3) < 2 || mask[(size_t)(y0 + y) * w + x0 + (x >> 2)]) continue;
         const unsigned long long k2 = ((unsigned long long)(unsigned)s << 32) | (unsigned)(0x7fffffff - p);
         key = k2 > key ? k2 : key;
     }
@@ -404,9 +445,9 @@ __global__ __launch_bounds__(256) void det_fast_kernel(const unsigned char *__re
 
 // one workgroup per image: candidates in cell order (:393-412 / :532-538), the second candidates of detectSingleScale
 // up to the number of still empty cells, the adaptive threshold (:418-423 / :546-552), and the image's points appended
-// to the global list cornerSubPix walks (order across images irrelevant).
+// to the global list cornerSubPix walks (order across images irrelevant).  nboccup comes from det_worklist_kernel.
 __global__ __launch_bounds__(256) void det_assemble_kernel(int mode, int nwcells, int nhcells,
-                                                           const unsigned char *__restrict__ occ_all,
+                                                           const int *__restrict__ nocc_all,
                                                            const det_out *__restrict__ out_all, double *__restrict__ thresh,
                                                            int *__restrict__ n_out, float2 *__restrict__ out_xy, int out_cap,
                                                            int *__restrict__ pt_ref, int *__restrict__ pt_img,
@@ -415,20 +456,17 @@ __global__ __launch_bounds__(256) void det_assemble_kernel(int mode, int nwcells
     __shared__ int sh4[4];
     __shared__ int gbase;
     const int b = blockIdx.x, nb = nwcells * nhcells, tid = threadIdx.x;
-    const unsigned char *occ = occ_all + (size_t)b * (nhcells + 1) * (nwcells + 1);
     const det_out *ho = out_all + (size_t)b * nb;
     float2 *o = out_xy + (size_t)b * out_cap;
-    int n = 0, nboccup = 0;
+    int n = 0;
+    const int nboccup = nocc_all[b];
     for (int i0 = 0; i0 < nb; i0 += 256) {
         const int i = i0 + tid;
         const bool f = i < nb && ho[i].has_first;
-        bool oc = false;
-        if (i < nb) { const int rr = i / nwcells, cc = i - rr * nwcells; oc = occ[rr * (nwcells + 1) + cc] != 0; }
-        int tot, toc;
+        int tot;
         const int rank = block_rank_256(f, sh4, &tot);
-        (void)block_rank_256(oc, sh4, &toc);
         if (f) o[n + rank] = make_float2(ho[i].fx, ho[i].fy);
-        n += tot; nboccup += toc;
+        n += tot;
     }
     const int nbempty = nb - nboccup;
     double th = thresh[b];
@@ -487,12 +525,35 @@ __device__ __forceinline__ double row_tree_f64(double v)
 // the (2HW+3)^2 bilinear samples are formed from LDS, window term t is owned by lane t % 16 (terms t, t+16, ... added
 // in that order), the five sums are closed by the 16-leaf tree above (the oracle uses the same order => bit-equal)
 // and every lane of the row solves the 2x2 system, so the scalar work of an iteration is shared by four points.
+// The window weights travel as a kernel argument.
+template <int HW>
+struct subpix_weights {
+    float w[(2 * HW + 1) * (2 * HW + 1)];
+};
+
+// cornerSubPix's window weights exp(-y^2) exp(-x^2) over (y, x) in [-1, 1]: float products of the host's expf
+template <int HW>
+subpix_weights<HW> make_subpix_weights()
+{
+    subpix_weights<HW> wt;
+    const int win = 2 * HW + 1;
+    for (int i = 0; i < win; ++i) {
+        const float y = (float)(i - HW) / (float)HW;
+        const float vy = expf(-y * y);
+        for (int j = 0; j < win; ++j) {
+            const float x = (float)(j - HW) / (float)HW;
+            wt.w[i * win + j] = (float)(vy * expf(-x * x));
+        }
+    }
+    return wt;
+}
+
 template <int HW>
 __global__ __launch_bounds__(64) void subpix_kernel(const unsigned char *__restrict__ img0, size_t img_bstride,
                                                     const int *__restrict__ pt_img, const int *__restrict__ pt_ref,
                                                     const unsigned *__restrict__ npts, int istride, int w, int h,
                                                     float2 *__restrict__ pts, int max_iter, double eps2,
-                                                    const float *__restrict__ wmask)
+                                                    subpix_weights<HW> wmask)
 {
     const int n = (int)*npts;                       // the grid is an upper bound; the point count lives on the device
     if ((int)blockIdx.x * 4 >= n) return;
@@ -500,6 +561,9 @@ __global__ __launch_bounds__(64) void subpix_kernel(const unsigned char *__restr
     __shared__ unsigned char src[4][(SW * SW + 3) & ~3];
     __shared__ float buf[4][BW * BW];
     const int lane = threadIdx.x, sub = lane & 15, row = lane >> 4;
+    double wm[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) wm[k] = (sub + 16 * k < NT) ? (double)wmask.w[sub + 16 * k] : 0.0;
     const int p = blockIdx.x * 4 + row;
     const bool act = p < n;
     const int pp = act ? p : n - 1;
@@ -509,9 +573,6 @@ __global__ __launch_bounds__(64) void subpix_kernel(const unsigned char *__restr
     float cIx = cTx, cIy = cTy;
     int iter = 0;
     bool go = act;
-    double wm[NK];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) wm[k] = (sub + 16 * k < NT) ? (double)wmask[sub + 16 * k] : 0.0;
     while (__any(go)) {
         const float cx = cIx - (float)(BW - 1) * 0.5f, cy = cIy - (float)(BW - 1) * 0.5f;
         const int ipx = (int)floorf(cx), ipy = (int)floorf(cy);
@@ -576,9 +637,9 @@ __global__ __launch_bounds__(64) void subpix_kernel(const unsigned char *__restr
 
 }  // namespace
 
-// Everything on the device, nothing synchronous: mask + occupancy of the existing keypoints, per-colour work lists,
-// the four colour launches, assembly in cell order + threshold adaptation, cornerSubPix.  Work-list lengths and the
-// point count never visit the host: the dependent grids are upper bounds and their workgroups compare against the
+// Everything on the device, nothing synchronous: one fill, mask + occupancy of the existing keypoints, per-colour work
+// lists, the four colour launches, assembly in cell order + threshold adaptation, cornerSubPix.  Work-list lengths and
+// the point count never visit the host: the dependent grids are upper bounds and their workgroups compare against the
 // device-side counters.
 extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, int cell, int mode, double *d_thresh,
                                                 int n_cur, const float *d_cur_xy, const int32_t *d_cur_img,
@@ -602,66 +663,63 @@ extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, 
     const unsigned char *img = v.base + L.img_off + (size_t)v.pad * L.istride + OV2_LM;
     const int nh = h / cell, nw = w / cell, nb = nh * nw;
     hipStream_t st = c->stream;
-    OV2_HIP(c, hipMemsetAsync(d_n_out, 0, sizeof(int) * B, st));
-    if (nb == 0) return OV2_OK;
-    if (out_cap < 2 * nb) return ov2_set_err(c, OV2_ERR_INVALID, "out_cap %d < 2 * cells (%d)", out_cap, 2 * nb);
+    // det_assemble_kernel writes every image's count; the returns that do not reach it zero the counts themselves
+    if (nb == 0 || out_cap < 2 * nb) {
+        OV2_HIP(c, hipMemsetAsync(d_n_out, 0, sizeof(int) * B, st));
+        if (nb == 0) return OV2_OK;
+        return ov2_set_err(c, OV2_ERR_INVALID, "out_cap %d < 2 * cells (%d)", out_cap, 2 * nb);
+    }
     const int rx = roi ? roi[0] : 0, ry = roi ? roi[1] : 0, rw = roi ? roi[2] : w, rh = roi ? roi[3] : h;
-    // scratch: [counters | occupancy | det_out] zeroed per call, then masks | work lists | point refs | weights
+    // scratch: [counters | occupancy | det_out | masks] zeroed per call by ONE fill, then work lists | point refs
     auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t occ_sz = (size_t)(nh + 1) * (nw + 1);
     const int list_cap = ((nh + 1) / 2) * ((nw + 1) / 2) * B;           // cells of one colour, all images
-    const size_t off_cnt = 0, off_occ = 256, off_out = off_occ + up(occ_sz * B);
-    const size_t zero_bytes = off_out + up(sizeof(det_out) * nb * B);
-    const size_t off_mask = zero_bytes, off_work = off_mask + up((size_t)w * h * B);
+    const size_t off_cnt = 0, off_occ = up(32 + sizeof(int) * B), off_out = off_occ + up(occ_sz * B);
+    const size_t off_mask = off_out + up(sizeof(det_out) * nb * B);
+    const size_t zero_bytes = off_mask + up((size_t)w * h * B);
+    const size_t off_work = zero_bytes;
     const size_t off_ref = off_work + up(sizeof(int2) * 4 * (size_t)list_cap), off_pimg = off_ref + up(sizeof(int) * (size_t)nb * B);
-    const size_t off_wm = off_pimg + up(sizeof(int) * (size_t)nb * B), total = off_wm + 1024;
+    const size_t total = off_pimg + up(sizeof(int) * (size_t)nb * B);
     void *scr = nullptr;
     ov2_status s = ov2_scratch(c, total, &scr);
-    if (s != OV2_OK) return s;
+    if (s != OV2_OK) {
+        (void)hipMemsetAsync(d_n_out, 0, sizeof(int) * B, st);
+        return s;
+    }
     char *base = (char *)scr;
     unsigned *cnt = (unsigned *)(base + off_cnt);           // [0..3] work-list lengths, [4] number of points
+    int *nocc = (int *)(base + off_cnt + 32);               // [B] occupied cells per image
     unsigned char *occ = (unsigned char *)(base + off_occ), *mask = (unsigned char *)(base + off_mask);
     det_out *dout = (det_out *)(base + off_out);
     int2 *dwork = (int2 *)(base + off_work);
     int *pt_ref = (int *)(base + off_ref), *pt_img = (int *)(base + off_pimg);
-    float *dwm = (float *)(base + off_wm);
     OV2_HIP(c, hipMemsetAsync(base, 0, zero_bytes, st));
-    OV2_HIP(c, hipMemsetAsync(mask, 1, (size_t)w * h * B, st));
     const disc_shape ds = make_disc(cell / 4);
     if (n_cur > 0)
-        OV2_LAUNCH(c, OV2_K_DETECT + 1, det_mask_kernel, dim3(std::min(n_cur, 65536)), dim3(64), 0, st,
-                   reinterpret_cast<const float2 *>(d_cur_xy), d_cur_img, d_cur_valid, n_cur, cell, nw, nh, occ, mask, w, h, ds);
-    OV2_LAUNCH(c, OV2_K_DETECT + 5, det_worklist_kernel, dim3(B), dim3(256), 0, st, cell, nw, nh, w, h, occ, dwork, list_cap, cnt);
+        OV2_LAUNCH(c, OV2_K_DETECT + 1, det_mask_kernel, dim3(std::min((n_cur + DET_MASK_KPS - 1) / DET_MASK_KPS, 65536)), dim3(256), 0,
+                   st, reinterpret_cast<const float2 *>(d_cur_xy), d_cur_img, d_cur_valid, n_cur, cell, nw, nh, occ, mask, w, h, ds);
+    OV2_LAUNCH(c, OV2_K_DETECT + 5, det_worklist_kernel, dim3(B), dim3(256), 0, st, cell, nw, nh, w, h, occ, dwork, list_cap, cnt, nocc);
     const int nthreads = (cell * cell <= 256) ? 64 : 256;   // small cells: one wave walks the cell
     const size_t mineig_lds = (size_t)(cell + 2) * (cell + 2) * 10 + (size_t)cell * cell * 5;
     for (int colour = 0; colour < 4; ++colour) {
-        // cells of this colour per image (upper bound of the list): rows of parity colour>>1 x columns of parity colour&1
+        // cells of this colour per image (upper bound of the list, <= list_cap: a workgroup reads its own list entry
+        // only): rows of parity colour>>1 x columns of parity colour&1
         const int rows_c = (nh + 1 - (colour >> 1)) / 2, cols_c = (nw + 1 - (colour & 1)) / 2, nitems = rows_c * cols_c * B;
         if (nitems <= 0) continue;
         const int2 *wl = dwork + (size_t)colour * list_cap;
         if (mode == OV2_DETECT_MINEIG)
-            OV2_LAUNCH(c, OV2_K_DETECT, det_mineig_kernel, dim3(nitems), dim3(nthreads), mineig_lds, st, img, L.img_bstride, L.istride,
-                       w, h, cell, nw, nh, wl, cnt + colour, mask, ds, rx, ry, rw, rh, d_thresh, dout);
+            OV2_LAUNCH(c, OV2_K_DETECT, det_mineig_kernel, dim3(nitems), dim3(nthreads), mineig_lds, st, img,
+                       L.img_bstride, L.istride, w, h, cell, nw, nh, wl, cnt + colour, mask, ds, rx, ry, rw, rh, d_thresh, dout);
         else
-            OV2_LAUNCH(c, OV2_K_DETECT, det_fast_kernel, dim3(nitems), dim3(nthreads), (size_t)cell * cell * 4, st, img, L.img_bstride,
-                       L.istride, w, h, cell, nw, nh, wl, cnt + colour, mask, ds, d_thresh, dout);
+            OV2_LAUNCH(c, OV2_K_DETECT, det_fast_kernel, dim3(nitems), dim3(nthreads), (size_t)cell * cell * 4, st,
+                       img, L.img_bstride, L.istride, w, h, cell, nw, nh, wl, cnt + colour, mask, ds, d_thresh, dout);
     }
-    OV2_LAUNCH(c, OV2_K_DETECT + 5, det_assemble_kernel, dim3(B), dim3(256), 0, st, mode, nw, nh, occ, dout, d_thresh, d_n_out,
+    OV2_LAUNCH(c, OV2_K_DETECT + 5, det_assemble_kernel, dim3(B), dim3(256), 0, st, mode, nw, nh, nocc, dout, d_thresh, d_n_out,
                reinterpret_cast<float2 *>(d_out_xy), out_cap, pt_ref, pt_img, cnt + 4);
     if (do_subpix) {
-        const int hw = 3, win = 7;
-        float wm[49];
-        for (int i = 0; i < win; ++i) {
-            const float y = (float)(i - hw) / (float)hw;
-            const float vy = expf(-y * y);
-            for (int j = 0; j < win; ++j) {
-                const float x = (float)(j - hw) / (float)hw;
-                wm[i * win + j] = (float)(vy * expf(-x * x));
-            }
-        }
-        OV2_HIP(c, hipMemcpyAsync(dwm, wm, sizeof(wm), hipMemcpyHostToDevice, st));   // 196 B: copied at enqueue time
-        OV2_LAUNCH(c, OV2_K_DETECT + 2, subpix_kernel<3>, dim3(((size_t)nb * B + 3) / 4), dim3(64), 0, st, img, L.img_bstride, pt_img,
-                   pt_ref, cnt + 4, L.istride, w, h, reinterpret_cast<float2 *>(d_out_xy), 30, 0.01 * 0.01, dwm);
+        static const subpix_weights<3> wts = make_subpix_weights<3>();   // depend on the window alone: formed once
+        OV2_LAUNCH(c, OV2_K_DETECT + 2, subpix_kernel<3>, dim3(((size_t)nb * B + 3) / 4), dim3(64), 0, st, img, L.img_bstride,
+                   pt_img, pt_ref, cnt + 4, L.istride, w, h, reinterpret_cast<float2 *>(d_out_xy), 30, 0.01 * 0.01, wts);
     }
     OV2_HIP(c, hipGetLastError());
     return OV2_OK;
