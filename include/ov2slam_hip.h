@@ -51,6 +51,11 @@ void ov2_ctx_destroy(ov2_ctx *ctx);
 const char *ov2_last_error(const ov2_ctx *ctx);
 const char *ov2_status_string(ov2_status s);
 ov2_status ov2_ctx_synchronize(ov2_ctx *ctx);
+/* Keyframe overlap (on by default; OV2_KF_OVERLAP=0 in the environment starts a context with it off): the detector chain
+ * of ov2_detect_grid_batch_dev runs on a side stream of the context, beside the ov2_stereo_matching_dev call in front of
+ * it when the two provably touch different arrays (see both entry points).  Results and the ordering of the calls are the
+ * same either way; off = the chain is enqueued on the context's main stream. */
+ov2_status ov2_ctx_set_kf_overlap(ov2_ctx *ctx, int on);
 /* hipEvent pair on the ctx stream (used by bench.py: torch.cuda.Event would only see torch's stream) */
 ov2_status ov2_timer_start(ov2_ctx *ctx);
 ov2_status ov2_timer_stop(ov2_ctx *ctx, float *elapsed_ms);   /* synchronises on the stop event */
@@ -191,7 +196,9 @@ typedef struct ov2_cam_model {
  * model here).  out_rxy stays the RAW right pixel (Frame::updateKeypointStereo undistorts it itself).
  * out_status[i] = 1 where the reference reaches Frame::updateKeypointStereo(id, out_rxy[i]).
  * Host pointers; the _dev form takes device pointers (F_rl stays a host pointer), is asynchronous, d_iters as in
- * ov2_klt_tracking_frame_dev. */
+ * ov2_klt_tracking_frame_dev.  With the keyframe overlap on, the _dev form also marks the point in front of its first
+ * kernel and remembers the arrays it reads (d_kps_xy, d_prior_xy, d_has_prior, d_img_idx, d_lunpx_xy) and writes
+ * (d_out_rxy, d_out_status, d_iters) for the detector call that may follow (ov2_detect_grid_batch_dev). */
 ov2_status ov2_stereo_matching(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *right, int win, int nlevels_full,
                                int max_iter, float eps, float err_th, float fb_th, int n, const float *kps_xy,
                                const float *prior_xy, const uint8_t *has_prior, const float *lunpx_xy, int rectified,
@@ -226,7 +233,13 @@ ov2_status ov2_detect_grid_batch(ov2_ctx *ctx, const ov2_pyr *pyr, int cell, int
  *   n_cur keypoints of all images: d_cur_xy (n_cur x 2 floats), d_cur_img (image index per keypoint),
  *   d_cur_valid (optional, n_cur bytes: only keypoints with a non-zero byte count, e.g. the tracking status)
  *   d_n_out    B ints, d_out_xy  B x out_cap x 2 floats (out_cap >= 2 * cells)
- * roi is a host pointer (4 ints or NULL). */
+ * roi is a host pointer (4 ints or NULL).
+ * Ordering: the call is ordered after every earlier call on the context and before every later one.  With the keyframe
+ * overlap on its kernels run on the context's side stream, and they run BESIDE the kernels of an ov2_stereo_matching_dev
+ * call when all of this holds: that call is the last thing enqueued on the context (releasing or retaining pyramids in
+ * between does not count); `pyr` is one of its two pyramids; d_thresh, d_n_out and d_out_xy meet none of the arrays it reads
+ * or writes; d_thresh, d_cur_xy, d_cur_img and d_cur_valid meet none of the arrays it writes.  Anything else, and any
+ * case the check cannot prove, runs behind the stereo call. */
 ov2_status ov2_detect_grid_batch_dev(ov2_ctx *ctx, const ov2_pyr *pyr, int cell, int mode, double *d_thresh, int n_cur,
                                      const float *d_cur_xy, const int32_t *d_cur_img, const uint8_t *d_cur_valid,
                                      const int *roi, int do_subpix, int32_t *d_n_out, float *d_out_xy, int out_cap);

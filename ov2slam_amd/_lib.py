@@ -23,6 +23,7 @@ SIGNATURES = {
     "ov2_last_error": (C.c_char_p, [vp]),
     "ov2_status_string": (C.c_char_p, [C.c_int]),
     "ov2_ctx_synchronize": (C.c_int, [vp]),
+    "ov2_ctx_set_kf_overlap": (C.c_int, [vp, C.c_int]),
     "ov2_timer_start": (C.c_int, [vp]),
     "ov2_timer_stop": (C.c_int, [vp, fp]),
     "ov2_ktime_enable": (C.c_int, [vp, C.c_int]),

@@ -74,13 +74,24 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
         if (pk && atoi(pk) >= 0) c->klt_yield_pickup = atoi(pk);
     }
     c->stage_ev_pending = false;
+    c->stream_kf = nullptr;
+    c->kf_scratch_dev = nullptr;
+    c->kf_scratch_bytes = 0;
+    c->kf.fork = c->kf.done = nullptr;
+    c->kf.want_stereo_ev = c->kf.stereo_valid = false;
+    // OV2_KF_OVERLAP=0: the keyframe detector chain stays on the main stream (default 1, ov2_ctx_set_kf_overlap);
+    // experiment hook: 2 runs the chain on the pyramid stream instead of a stream of its own
+    const char *kf_env = getenv("OV2_KF_OVERLAP");
+    const int kf_mode = kf_env ? atoi(kf_env) : 1;
+    const bool kf_on_pyr = kf_mode == 2;
+    c->kf_overlap = kf_mode > 0 ? 1 : 0;
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     // experiment hook: OV2_CU_SPLIT=k keeps the first k compute units of the device for the high-priority contexts
     // (the local-BA worker) and the remaining ones for the others, instead of sharing all of them by priority
     const char *split_env = getenv("OV2_CU_SPLIT");
     const int split = split_env ? atoi(split_env) : 0;
-    hipError_t e1, e2;
+    hipError_t e1, e2, e3 = hipSuccess;
     if (split > 0) {
         hipDeviceProp_t prop;
         (void)hipGetDeviceProperties(&prop, device);
@@ -90,16 +101,23 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
             const bool mine = high_priority ? (i < split) : (i >= split);
             if (mine) mask[i / 32] |= 1u << (i % 32);
         }
-        e1 = hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)words, mask.data());
+        e1 = hipExtStreamCreateWithCUMask(&c->stream.h, (uint32_t)words, mask.data());
         e2 = hipExtStreamCreateWithCUMask(&c->stream_pyr, (uint32_t)words, mask.data());
+        if (!kf_on_pyr) e3 = hipExtStreamCreateWithCUMask(&c->stream_kf, (uint32_t)words, mask.data());
     } else {
-        e1 = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, high_priority ? prio_greatest : prio_least);
+        e1 = hipStreamCreateWithPriority(&c->stream.h, hipStreamNonBlocking, high_priority ? prio_greatest : prio_least);
         // experiment hook: OV2_SINGLE_STREAM=1 builds the pyramids on the main stream (no overlap with the tracking)
         const char *one = getenv("OV2_SINGLE_STREAM");
-        if (one && atoi(one) > 0) { c->stream_pyr = c->stream; e2 = hipSuccess; }
-        else e2 = hipStreamCreateWithPriority(&c->stream_pyr, hipStreamNonBlocking, high_priority ? prio_greatest : prio_least);
+        if (one && atoi(one) > 0) { c->stream_pyr = c->stream_kf = c->stream.h; e2 = hipSuccess; }
+        else {
+            e2 = hipStreamCreateWithPriority(&c->stream_pyr, hipStreamNonBlocking, high_priority ? prio_greatest : prio_least);
+            if (!kf_on_pyr) e3 = hipStreamCreateWithPriority(&c->stream_kf, hipStreamNonBlocking, high_priority ? prio_greatest : prio_least);
+        }
     }
-    if (e1 != hipSuccess || e2 != hipSuccess ||
+    if (kf_on_pyr && e2 == hipSuccess) c->stream_kf = c->stream_pyr;
+    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess ||
+        hipEventCreateWithFlags(&c->kf.fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->kf.done, hipEventDisableTiming) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreateWithFlags(&c->stage_ev, hipEventDisableTiming) != hipSuccess) {
         delete c;
@@ -115,6 +133,7 @@ extern "C" void ov2_ctx_destroy(ov2_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamSynchronize(c->stream_pyr);
+    if (c->stream_kf) (void)hipStreamSynchronize(c->stream_kf);
     for (ov2_pyr_buf *b : c->pool) {
         (void)hipEventDestroy(b->ready_ev);
         (void)hipEventDestroy(b->free_ev);
@@ -128,6 +147,7 @@ extern "C" void ov2_ctx_destroy(ov2_ctx *c)
     for (auto &r : c->ktime_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
     for (auto e : c->ktime_free) (void)hipEventDestroy(e);
     if (c->scratch_dev) (void)hipFree(c->scratch_dev);
+    if (c->kf_scratch_dev) (void)hipFree(c->kf_scratch_dev);
     if (c->ba_arena) (void)hipFree(c->ba_arena);
     if (c->ba_host) (void)hipHostFree(c->ba_host);
     for (int i = 0; i < 2; ++i) if (c->klt_counts[i]) (void)hipFree(c->klt_counts[i]);
@@ -140,8 +160,11 @@ extern "C" void ov2_ctx_destroy(ov2_ctx *c)
     (void)hipEventDestroy(c->ev0);
     (void)hipEventDestroy(c->ev1);
     if (c->stage_ev) (void)hipEventDestroy(c->stage_ev);
-    (void)hipStreamDestroy(c->stream);
-    if (c->stream_pyr != c->stream) (void)hipStreamDestroy(c->stream_pyr);
+    if (c->kf.fork) (void)hipEventDestroy(c->kf.fork);
+    if (c->kf.done) (void)hipEventDestroy(c->kf.done);
+    if (c->stream_kf && c->stream_kf != c->stream.h && c->stream_kf != c->stream_pyr) (void)hipStreamDestroy(c->stream_kf);
+    if (c->stream_pyr != c->stream.h) (void)hipStreamDestroy(c->stream_pyr);
+    (void)hipStreamDestroy(c->stream.h);
     delete c;
 }
 
@@ -150,7 +173,15 @@ extern "C" ov2_status ov2_ctx_synchronize(ov2_ctx *c)
     if (!c) return OV2_ERR_INVALID;
     OV2_HIP(c, hipSetDevice(c->device));   // HIP's current device is per thread
     OV2_HIP(c, hipStreamSynchronize(c->stream_pyr));
+    OV2_HIP(c, hipStreamSynchronize(c->stream_kf));
     OV2_HIP(c, hipStreamSynchronize(c->stream));
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_ctx_set_kf_overlap(ov2_ctx *c, int on)
+{
+    if (!c) return OV2_ERR_INVALID;
+    c->kf_overlap = on ? 1 : 0;
     return OV2_OK;
 }
 
@@ -232,6 +263,22 @@ ov2_status ov2_scratch(ov2_ctx *c, size_t bytes, void **out)
         c->scratch_bytes = want;
     }
     *out = c->scratch_dev;
+    return OV2_OK;
+}
+
+ov2_status ov2_kf_scratch(ov2_ctx *c, size_t bytes, void **out)
+{
+    if (bytes > c->kf_scratch_bytes) {
+        OV2_HIP(c, hipStreamSynchronize(c->stream_kf));   // the chain that used the old block; the main stream is left alone
+        if (c->kf_scratch_dev) OV2_HIP(c, hipFree(c->kf_scratch_dev));
+        c->kf_scratch_dev = nullptr;
+        c->kf_scratch_bytes = 0;
+        size_t want = bytes + bytes / 2 + 4096;
+        hipError_t e = hipMalloc(&c->kf_scratch_dev, want);
+        if (e != hipSuccess) return ov2_set_err(c, OV2_ERR_NOMEM, "side scratch hipMalloc(%zu)", want);
+        c->kf_scratch_bytes = want;
+    }
+    *out = c->kf_scratch_dev;
     return OV2_OK;
 }
 
@@ -347,6 +394,7 @@ extern "C" ov2_status ov2_ktime_report(ov2_ctx *c, int max_kernels, const char *
 {
     if (!c || !n_out || max_kernels < 0) return OV2_ERR_INVALID;
     OV2_HIP(c, hipStreamSynchronize(c->stream_pyr));
+    OV2_HIP(c, hipStreamSynchronize(c->stream_kf));
     OV2_HIP(c, hipStreamSynchronize(c->stream));
     double tot[OV2_K_MAX] = {0};
     long long cnt[OV2_K_MAX] = {0};

@@ -635,12 +635,46 @@ __global__ __launch_bounds__(64) void subpix_kernel(const unsigned char *__restr
     if (act && sub == 0) pts[ref] = make_float2(cIx, cIy);
 }
 
+bool ranges_meet(const ov2_byte_range &a, const ov2_byte_range &b) { return a.lo && b.lo && a.lo < b.hi && b.lo < a.hi; }
+
+// May the chain start from the event ov2_stereo_matching_dev recorded in front of its first kernel, i.e. run beside that
+// call?  Only when every point below is proven; anything else starts from the tail of the main stream.
+//   - the stereo call is the last thing enqueued on the main stream (pyramid retain / release bookkeeping aside),
+//   - this call's pyramid is one that call only reads,
+//   - nothing this call writes (thresholds, counts, corners) meets anything that call reads or writes,
+//   - nothing this call reads (thresholds, keypoints, their image indices and flags) meets anything that call writes.
+bool fork_at_stereo(const ov2_ctx *c, const ov2_pyr *pyr, int B, const double *d_thresh, int n_cur, const float *d_cur_xy,
+                    const int32_t *d_cur_img, const uint8_t *d_cur_valid, const int32_t *d_n_out, const float *d_out_xy, int out_cap)
+{
+    const ov2_kf_fork &k = c->kf;
+    if (!k.stereo_valid || k.uses != c->stream.uses.load(std::memory_order_relaxed)) return false;
+    if (pyr->buf != k.pyr[0] && pyr->buf != k.pyr[1]) return false;
+    auto range = [](const void *p, size_t bytes) { return ov2_byte_range{(const char *)p, p ? (const char *)p + bytes : nullptr}; };
+    const size_t N = (size_t)n_cur;
+    const ov2_byte_range wr[3] = {range(d_thresh, sizeof(double) * B), range(d_n_out, sizeof(int) * B),
+                                  range(d_out_xy, 8 * (size_t)B * out_cap)};
+    const ov2_byte_range rd[4] = {wr[0], range(d_cur_xy, 8 * N), range(d_cur_img, 4 * N), range(d_cur_valid, N)};
+    for (const ov2_byte_range &w : wr) {
+        for (const ov2_byte_range &r : k.rd) if (ranges_meet(w, r)) return false;
+        for (const ov2_byte_range &r : k.wr) if (ranges_meet(w, r)) return false;
+    }
+    for (const ov2_byte_range &r : rd)
+        for (const ov2_byte_range &w : k.wr) if (ranges_meet(r, w)) return false;
+    return true;
+}
+
 }  // namespace
 
 // Everything on the device, nothing synchronous: one fill, mask + occupancy of the existing keypoints, per-colour work
 // lists, the four colour launches, assembly in cell order + threshold adaptation, cornerSubPix.  Work-list lengths and
 // the point count never visit the host: the dependent grids are upper bounds and their workgroups compare against the
 // device-side counters.
+//
+// Where it runs: with the keyframe overlap on (ov2_ctx_set_kf_overlap, OV2_KF_OVERLAP; the default) the chain is enqueued on
+// the context's keyframe side stream and the main stream waits for its end, so the call is ordered like any other.  When
+// the call directly follows ov2_stereo_matching_dev on the same context and touches none of that call's arrays
+// (fork_at_stereo above states the rule), the chain starts in front of the stereo kernels and runs beside them.  With
+// the overlap off the chain is enqueued on the main stream with no events, as before.
 extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, int cell, int mode, double *d_thresh,
                                                 int n_cur, const float *d_cur_xy, const int32_t *d_cur_img,
                                                 const uint8_t *d_cur_valid, const int *roi, int do_subpix,
@@ -662,10 +696,9 @@ extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, 
     const int B = pyr->buf->batch, w = L.w, h = L.h;
     const unsigned char *img = v.base + L.img_off + (size_t)v.pad * L.istride + OV2_LM;
     const int nh = h / cell, nw = w / cell, nb = nh * nw;
-    hipStream_t st = c->stream;
     // det_assemble_kernel writes every image's count; the returns that do not reach it zero the counts themselves
     if (nb == 0 || out_cap < 2 * nb) {
-        OV2_HIP(c, hipMemsetAsync(d_n_out, 0, sizeof(int) * B, st));
+        OV2_HIP(c, hipMemsetAsync(d_n_out, 0, sizeof(int) * B, c->stream));
         if (nb == 0) return OV2_OK;
         return ov2_set_err(c, OV2_ERR_INVALID, "out_cap %d < 2 * cells (%d)", out_cap, 2 * nb);
     }
@@ -680,11 +713,24 @@ extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, 
     const size_t off_work = zero_bytes;
     const size_t off_ref = off_work + up(sizeof(int2) * 4 * (size_t)list_cap), off_pimg = off_ref + up(sizeof(int) * (size_t)nb * B);
     const size_t total = off_pimg + up(sizeof(int) * (size_t)nb * B);
+    // the chain runs on the keyframe side stream with a scratch block of its own, between two events: it starts from
+    // kf.fork and the main stream waits for kf.done before this call returns, so the call stays ordered behind every
+    // earlier call on the context and in front of every later one
+    const bool side = c->kf_overlap != 0 && c->stream_kf != c->stream.h;
+    const bool early = side && fork_at_stereo(c, pyr, B, d_thresh, n_cur, d_cur_xy, d_cur_img, d_cur_valid, d_n_out, d_out_xy, out_cap);
+    c->kf.stereo_valid = false;
     void *scr = nullptr;
-    ov2_status s = ov2_scratch(c, total, &scr);
+    ov2_status s = side ? ov2_kf_scratch(c, total, &scr) : ov2_scratch(c, total, &scr);
     if (s != OV2_OK) {
-        (void)hipMemsetAsync(d_n_out, 0, sizeof(int) * B, st);
+        (void)hipMemsetAsync(d_n_out, 0, sizeof(int) * B, c->stream);
         return s;
+    }
+    hipStream_t st = c->stream_kf;
+    if (side) {
+        if (!early) OV2_HIP(c, hipEventRecord(c->kf.fork, c->stream.h));   // the tail of the main stream: the serial order
+        OV2_HIP(c, hipStreamWaitEvent(st, c->kf.fork, 0));
+    } else {
+        st = c->stream;
     }
     char *base = (char *)scr;
     unsigned *cnt = (unsigned *)(base + off_cnt);           // [0..3] work-list lengths, [4] number of points
@@ -696,9 +742,9 @@ extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, 
     OV2_HIP(c, hipMemsetAsync(base, 0, zero_bytes, st));
     const disc_shape ds = make_disc(cell / 4);
     if (n_cur > 0)
-        OV2_LAUNCH(c, OV2_K_DETECT + 1, det_mask_kernel, dim3(std::min((n_cur + DET_MASK_KPS - 1) / DET_MASK_KPS, 65536)), dim3(256), 0,
+        OV2_LAUNCH_ON(c, OV2_K_DETECT + 1, st, det_mask_kernel, dim3(std::min((n_cur + DET_MASK_KPS - 1) / DET_MASK_KPS, 65536)), dim3(256), 0,
                    st, reinterpret_cast<const float2 *>(d_cur_xy), d_cur_img, d_cur_valid, n_cur, cell, nw, nh, occ, mask, w, h, ds);
-    OV2_LAUNCH(c, OV2_K_DETECT + 5, det_worklist_kernel, dim3(B), dim3(256), 0, st, cell, nw, nh, w, h, occ, dwork, list_cap, cnt, nocc);
+    OV2_LAUNCH_ON(c, OV2_K_DETECT + 5, st, det_worklist_kernel, dim3(B), dim3(256), 0, st, cell, nw, nh, w, h, occ, dwork, list_cap, cnt, nocc);
     const int nthreads = (cell * cell <= 256) ? 64 : 256;   // small cells: one wave walks the cell
     const size_t mineig_lds = (size_t)(cell + 2) * (cell + 2) * 10 + (size_t)cell * cell * 5;
     for (int colour = 0; colour < 4; ++colour) {
@@ -708,20 +754,25 @@ extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, 
         if (nitems <= 0) continue;
         const int2 *wl = dwork + (size_t)colour * list_cap;
         if (mode == OV2_DETECT_MINEIG)
-            OV2_LAUNCH(c, OV2_K_DETECT, det_mineig_kernel, dim3(nitems), dim3(nthreads), mineig_lds, st, img,
+            OV2_LAUNCH_ON(c, OV2_K_DETECT, st, det_mineig_kernel, dim3(nitems), dim3(nthreads), mineig_lds, st, img,
                        L.img_bstride, L.istride, w, h, cell, nw, nh, wl, cnt + colour, mask, ds, rx, ry, rw, rh, d_thresh, dout);
         else
-            OV2_LAUNCH(c, OV2_K_DETECT, det_fast_kernel, dim3(nitems), dim3(nthreads), (size_t)cell * cell * 4, st,
+            OV2_LAUNCH_ON(c, OV2_K_DETECT, st, det_fast_kernel, dim3(nitems), dim3(nthreads), (size_t)cell * cell * 4, st,
                        img, L.img_bstride, L.istride, w, h, cell, nw, nh, wl, cnt + colour, mask, ds, d_thresh, dout);
     }
-    OV2_LAUNCH(c, OV2_K_DETECT + 5, det_assemble_kernel, dim3(B), dim3(256), 0, st, mode, nw, nh, nocc, dout, d_thresh, d_n_out,
+    OV2_LAUNCH_ON(c, OV2_K_DETECT + 5, st, det_assemble_kernel, dim3(B), dim3(256), 0, st, mode, nw, nh, nocc, dout, d_thresh, d_n_out,
                reinterpret_cast<float2 *>(d_out_xy), out_cap, pt_ref, pt_img, cnt + 4);
     if (do_subpix) {
         static const subpix_weights<3> wts = make_subpix_weights<3>();   // depend on the window alone: formed once
-        OV2_LAUNCH(c, OV2_K_DETECT + 2, subpix_kernel<3>, dim3(((size_t)nb * B + 3) / 4), dim3(64), 0, st, img, L.img_bstride,
+        OV2_LAUNCH_ON(c, OV2_K_DETECT + 2, st, subpix_kernel<3>, dim3(((size_t)nb * B + 3) / 4), dim3(64), 0, st, img, L.img_bstride,
                    pt_img, pt_ref, cnt + 4, L.istride, w, h, reinterpret_cast<float2 *>(d_out_xy), 30, 0.01 * 0.01, wts);
     }
-    OV2_HIP(c, hipGetLastError());
+    const hipError_t le = hipGetLastError();
+    if (side) {   // joined even behind a failed launch: nothing may stay behind on the side stream unordered
+        OV2_HIP(c, hipEventRecord(c->kf.done, st));
+        OV2_HIP(c, hipStreamWaitEvent(c->stream.h, c->kf.done, 0));
+    }
+    if (le != hipSuccess) return ov2_set_err(c, OV2_ERR_HIP, "detector chain launch failed: %s", hipGetErrorString(le));
     return OV2_OK;
 }
 

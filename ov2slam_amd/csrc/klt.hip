@@ -1580,6 +1580,10 @@ ov2_status ov2_klt_two_stage_dev(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr 
         }
         ylist = (unsigned long long *)c->klt_ybuf;
     }
+    if (c->kf.want_stereo_ev) {   // ov2_stereo_matching_dev: the point a following detector call may fork from (detect.hip)
+        OV2_HIP(c, hipEventRecord(c->kf.fork, c->stream.h));
+        c->kf.want_stereo_ev = false;
+    }
     const dim3 cgrid((n + 255) / 256);
 #define KLT_STAGES_GL(W, G)                                                                                     \
     do {                                                                                                        \

@@ -61,6 +61,32 @@ enum ov2_kernel_id {
 };
 extern const char *ov2_kernel_names[OV2_K_MAX];
 
+// The main stream of a context.  It converts to hipStream_t wherever one is expected, and every conversion counts as a use:
+// ov2_detect_grid_batch_dev may fork its chain from the event ov2_stereo_matching_dev left in front of its kernels only
+// while NOTHING has been enqueued on this stream since (ov2_kf_fork::uses), and a count taken at the one place every
+// enqueue passes through cannot miss a call site.  Pure ordering bookkeeping (event records and waits of the pyramid
+// pool, which move no data) reads `.h` instead and does not count.
+struct ov2_main_stream {
+    hipStream_t h = nullptr;
+    mutable std::atomic<unsigned long long> uses{0};
+    operator hipStream_t() const { uses.fetch_add(1, std::memory_order_relaxed); return h; }
+};
+
+struct ov2_byte_range {
+    const char *lo, *hi;   // [lo, hi); lo == nullptr: absent
+};
+
+// keyframe side stream: the detector chain runs here beside the stereo matching of the same keyframe (detect.hip)
+struct ov2_kf_fork {
+    hipEvent_t fork, done;               // fork: point of the main stream the chain starts from (recorded by the detector call at
+                                         //   the tail, or by ov2_stereo_matching_dev in front of its first kernel); done: end of the chain
+    bool want_stereo_ev;                 // set by ov2_stereo_matching_dev for the two-stage tracking call it makes
+    bool stereo_valid;                   // `fork` is the stereo call's, and `uses` and the ranges below describe that call
+    unsigned long long uses;             // ov2_main_stream::uses right behind that call's last enqueue
+    const ov2_pyr_buf *pyr[2];           // the pyramids it reads (image planes: read only)
+    ov2_byte_range rd[5], wr[3];         // what it reads (keypoints, priors, flags, image indices, undistorted points) / writes
+};
+
 struct ov2_ktime_rec {
     int id;
     hipEvent_t e0, e1;
@@ -68,8 +94,13 @@ struct ov2_ktime_rec {
 
 struct ov2_ctx {
     int device;
-    hipStream_t stream;                  // main stream: KLT, detectors, BA
+    ov2_main_stream stream;              // main stream: KLT, detectors, BA
     hipStream_t stream_pyr;              // pyramid builds run here so that frame t+1's pyramid overlaps frame t's KLT
+    hipStream_t stream_kf;               // keyframe side stream: the detector chain (= main stream under OV2_SINGLE_STREAM)
+    int kf_overlap;                      // ov2_ctx_set_kf_overlap / OV2_KF_OVERLAP: 0 = the chain stays on the main stream
+    ov2_kf_fork kf;
+    void *kf_scratch_dev;                // scratch of the chain on the side stream (grown on demand; growth waits for
+    size_t kf_scratch_bytes;             //   the side stream alone)
     hipEvent_t ev0, ev1;
     std::mutex mu;                       // guards pool + err
     std::vector<ov2_pyr_buf *> pool;     // free pyramid buffers
@@ -121,6 +152,8 @@ struct ov2_pyr {
 
 ov2_status ov2_set_err(ov2_ctx *ctx, ov2_status s, const char *fmt, ...);
 ov2_status ov2_scratch(ov2_ctx *ctx, size_t bytes, void **out);
+// the same for the keyframe side stream's own buffer
+ov2_status ov2_kf_scratch(ov2_ctx *ctx, size_t bytes, void **out);
 // pinned host block of `bytes` and a device block of the same size (grown on demand, kept by the ctx)
 ov2_status ov2_staging(ov2_ctx *ctx, size_t bytes, void **host, void **dev);
 // ov2_ctx_destroy: free the device side of a map that outlives its ctx (the handle stays valid for ov2_map_destroy)

@@ -1189,7 +1189,7 @@ extern "C" void ov2_pyr_release(ov2_pyr *p)
         // stream-ordered reuse: later builds on the same ctx stream run after every kernel that reads this buffer
         // when those readers were enqueued on the same ctx.  Cross-ctx readers must synchronise before release.
         // every consumer of this pyramid was enqueued on the main stream before this release: mark that point
-        if (hipEventRecord(p->buf->free_ev, p->ctx->stream) == hipSuccess) p->buf->has_free_ev = true;
+        if (hipEventRecord(p->buf->free_ev, p->ctx->stream.h) == hipSuccess) p->buf->has_free_ev = true;
         std::lock_guard<std::mutex> g(p->ctx->mu);
         p->ctx->pool.push_back(p->buf);
         delete p;
@@ -1205,7 +1205,7 @@ extern "C" void ov2_pyr_release_from(ov2_ctx *user, ov2_pyr *p)
     if (user && user != p->ctx) {
         (void)hipSetDevice(user->device);
         std::lock_guard<std::mutex> g(p->ctx->mu);
-        if (hipEventRecord(p->buf->free_ev2, user->stream) == hipSuccess) p->buf->has_free_ev2 = true;
+        if (hipEventRecord(p->buf->free_ev2, user->stream.h) == hipSuccess) p->buf->has_free_ev2 = true;
     }
     ov2_pyr_release(p);
 }
@@ -1258,7 +1258,7 @@ ov2_status ov2_pyr_need_grad(ov2_ctx *c, const ov2_pyr *p)
     {
         std::lock_guard<std::mutex> g(p->ctx->mu);
         if (buf->grad_built) {
-            err = hipStreamWaitEvent(c->stream, buf->grad_ev, 0); what = "hipStreamWaitEvent(grad_ev)";
+            err = hipStreamWaitEvent(c->stream.h, buf->grad_ev, 0); what = "hipStreamWaitEvent(grad_ev)";
         } else if ((err = hipStreamWaitEvent(c->stream, buf->ready_ev, 0)) != hipSuccess) {
             what = "hipStreamWaitEvent(ready_ev)";
         } else {
@@ -1280,6 +1280,6 @@ ov2_status ov2_pyr_need_grad(ov2_ctx *c, const ov2_pyr *p)
 ov2_status ov2_pyr_wait_ready(ov2_ctx *c, const ov2_pyr *p)
 {
     if (!p) return OV2_ERR_INVALID;
-    OV2_HIP(c, hipStreamWaitEvent(c->stream, p->buf->ready_ev, 0));
+    OV2_HIP(c, hipStreamWaitEvent(c->stream.h, p->buf->ready_ev, 0));   // ordering only: not a use of the main stream (ov2_main_stream)
     return OV2_OK;
 }

@@ -263,6 +263,11 @@ extern "C" ov2_status ov2_line_min_sad(ov2_ctx *c, const ov2_pyr *left, const ov
     return OV2_OK;
 }
 
+// With the keyframe overlap on (ov2_ctx_set_kf_overlap, OV2_KF_OVERLAP; the default) the call records the context's fork
+// event in front of its first kernel and notes the byte ranges it reads (keypoints, priors, has-prior flags, image indices,
+// undistorted points) and writes (positions, statuses, work words).  An ov2_detect_grid_batch_dev call that follows
+// directly, on one of the two pyramids and on arrays that meet none of these ranges, starts its chain at that event and
+// runs beside this call (detect.hip, fork_at_stereo); every other call is ordered behind this one as always.
 extern "C" ov2_status ov2_stereo_matching_dev(ov2_ctx *c, const ov2_pyr *left, const ov2_pyr *right, int win, int nlevels_full,
                                               int max_iter, float eps, float err_th, float fb_th, int n, const float *d_kps_xy,
                                               const float *d_prior_xy, const uint8_t *d_has_prior, const int32_t *d_img_idx,
@@ -273,8 +278,12 @@ extern "C" ov2_status ov2_stereo_matching_dev(ov2_ctx *c, const ov2_pyr *left, c
     if (!c) return OV2_ERR_INVALID;
     if (n == 0) return OV2_OK;
     if (!rectified && !F_rl) return ov2_set_err(c, OV2_ERR_INVALID, "F_rl is required for the Sampson gate");
+    c->kf.stereo_valid = false;
+    c->kf.want_stereo_ev = c->kf_overlap != 0;   // the tracking call records kf.fork in front of its first kernel
     ov2_status s = ov2_klt_two_stage_dev(c, left, right, win, nlevels_full, max_iter, eps, err_th, fb_th, n, d_kps_xy, d_prior_xy,
                                          d_has_prior, d_img_idx, d_out_rxy, d_out_status, nullptr, d_iters, 0);
+    const bool forked = c->kf_overlap != 0 && !c->kf.want_stereo_ev;
+    c->kf.want_stereo_ev = false;
     if (s != OV2_OK) return s;
     gate_params G;
     for (int k = 0; k < 9; ++k) G.F[k] = F_rl ? F_rl[k] : 0.0;
@@ -285,6 +294,17 @@ extern "C" ov2_status ov2_stereo_matching_dev(ov2_ctx *c, const ov2_pyr *left, c
                reinterpret_cast<const float2 *>(d_kps_xy), reinterpret_cast<const float2 *>(d_lunpx_xy),
                reinterpret_cast<float2 *>(d_out_rxy), d_out_status);
     OV2_HIP(c, hipGetLastError());
+    if (forked) {   // what this call touches, for the detector call that may run beside it (ov2_detect_grid_batch_dev)
+        auto range = [](const void *p, size_t bytes) { return ov2_byte_range{(const char *)p, p ? (const char *)p + bytes : nullptr}; };
+        const size_t N = (size_t)n;
+        ov2_kf_fork &k = c->kf;
+        k.pyr[0] = left->buf; k.pyr[1] = right->buf;
+        k.rd[0] = range(d_kps_xy, 8 * N); k.rd[1] = range(d_prior_xy, 8 * N); k.rd[2] = range(d_has_prior, N);
+        k.rd[3] = range(d_img_idx, 4 * N); k.rd[4] = range(d_lunpx_xy, 8 * N);
+        k.wr[0] = range(d_out_rxy, 8 * N); k.wr[1] = range(d_out_status, N); k.wr[2] = range(d_iters, 8 * N);
+        k.uses = c->stream.uses.load(std::memory_order_relaxed);
+        k.stereo_valid = true;
+    }
     return OV2_OK;
 }
 
