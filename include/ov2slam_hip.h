@@ -613,7 +613,8 @@ ov2_status ov2_map_local_ba_setup_batch(ov2_ctx *ctx, int B, ov2_map *const *map
  * update takes it (:741): so does this call.  Allowed between the set-up and the update, through the hooks above:
  *  - ov2_map_add_keyframe: new keyframes, and rows appended to a keyframe already in the map (matchToMap / merges) --
  *    within the capacities,
- *  - ov2_map_remove_obs, ov2_map_set_obs_stereo, ov2_map_remove_landmarks, ov2_map_set_landmarks (isobs_ flips).
+ *  - ov2_map_remove_obs, ov2_map_set_obs_stereo, ov2_map_remove_landmarks, ov2_map_set_landmarks (isobs_ flips),
+ *  - ov2_map_triangulate_temporal_batch (below): landmarks it turns 3D, observations of its new keyframe it removes.
  * The observers of every landmark of the window, its oldest observer (MapPoint::kfid_; with inverse depth: the keyframe
  * whose solved pose and pixel turn rho into the world point, :822-838), isobs_ and liveness are read from the tables at
  * the update; only the set-up's rows are checked for flagged blocks, and a row that died since is neither removed again
@@ -637,6 +638,39 @@ typedef struct ov2_local_ba_update {
 } ov2_local_ba_update;
 ov2_status ov2_map_local_ba_update_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const uint8_t *const *d_outlier,
                                          const int32_t *cur_kfid, ov2_local_ba_update *out);
+
+/* Mapper::triangulateTemporal (src/mapper.cpp:191-344) on the tables of B map mirrors, one SLAM instance each: the 2D
+ * keypoints of keyframe newkf[b] -- live rows (newkf, l) of landmarks that are OV2_LM_ALIVE with neither OV2_LM_3D nor
+ * OV2_LM_KP3D -- are triangulated against the landmark's oldest observer (*MapPoint::getKfObsSet().begin()):
+ *  - skipped: fewer than 2 observers, oldest observer == newkf, stereo != 0 and |t(Tcicj)| < 0.01 m (:258-289);
+ *  - bearings ((u-cx)/fx, (v-cy)/fy, 1) normalised from the rows' unpx (held as float, as Frame::computeKeypoint keeps it)
+ *    and calib_l[4 b ..] = fx fy cx cy, for both views; then the arithmetic of ov2_triangulate_pairs in its order
+ *    (OV2_TRI_MIDPOINT, depth gate 0.1 in both views, float reprojection distances against max_reproj_err,
+ *    rotation-compensated parallax, Twc_oldest * X);
+ *  - OV2_TRI_OK: lm_xyz = world point, lm_state |= OV2_LM_3D | OV2_LM_KP3D (MapManager::updateMapPoint, :332-333);
+ *    failed with parallax > 20 px: the row (newkf, l) dies (MapManager::removeMapPointObs(lmid, newkf), :310-329).
+ * Deviations from the reference: an observation of a dead landmark or by a dead keyframe is not live in the mirror
+ * (obs_live), so the branches "missing map point" (:244-247), "keyframe gone" (:271-273) and "the older keyframe does not
+ * hold the keypoint" (:292-295) have nothing to do here -- such observers do not count and are not chosen; cameras
+ * without distortion.  The host replays MapPoint::invdepth_ / Frame counters from the lists below.
+ * map = blockIdx.y of every launch, sizes come from device memory, four launches whatever B.  The scratch arrays are the
+ * stage's own: the last set-up of a map and what its ov2_map_local_ba_update_batch reads stay as they are (see the list of
+ * edits allowed between set-up and update above).
+ * Refused with OV2_ERR_INVALID, tables untouched: newkf[b] not alive in map b, a map listed twice, calib_l == NULL.
+ * out == NULL: fully asynchronous.  out != NULL: one synchronisation for the B headers; the lists are DEVICE arrays of the
+ * map, valid until its next call of this function (or a growth of its tables), order arbitrary. */
+typedef struct ov2_map_temporal {
+    int32_t n_selected;              /* 2D keypoints of newkf (vkps.size() of the reference, minus those whose map point is gone
+                                        or already 3D: the reference skips both, :244-252) */
+    int32_t n_candidates, n_good, n_removed;
+    const int32_t *good_lmid;        /* n_good: MapManager::updateMapPoint(lmid, good_wpt, good_invdepth) */
+    const double *good_wpt;          /* n_good x 3 */
+    const double *good_invdepth;     /* n_good: 1 / depth in the oldest observer */
+    const int32_t *removed_lmid;     /* n_removed: MapManager::removeMapPointObs(lmid, newkf) */
+} ov2_map_temporal;
+ov2_status ov2_map_triangulate_temporal_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf,
+                                              const double *calib_l /* B x 4 */, int stereo, float max_reproj_err,
+                                              ov2_map_temporal *out /* B, or NULL */);
 
 /* Test / bench support.  ov2_map_save_state keeps a device copy of the mutable state of the tables (poses, landmark points
  * and states, observation flags); ov2_map_restore_state_batch rewinds B maps to it in one launch, asynchronously (every

@@ -10,11 +10,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "ov2_internal.h"
+#include "tri_pair.h"
 
 struct ov2_map {
     ov2_ctx *c;
@@ -48,6 +50,13 @@ struct ov2_map {
     double *snap_kf_pose, *snap_lm_xyz; unsigned char *snap_kf_state, *snap_lm_state, *snap_obs_flag;
     int snap_kf, snap_lm, snap_obs;
     int snap_floor;                                                 // rows a squeeze kept for the saved state: no new squeeze below 2x
+    // ov2_map_triangulate_temporal_batch: scratch and output lists of its own (the arrays of the last set-up stay as they are)
+    unsigned char *tt_zero; size_t tt_zero_bytes;                   // hdr (MH_N ints) | tt_nobs | tt_old | tt_nrow: one clear per call
+    int *tt_nobs, *tt_old, *tt_nrow;                                // [max_lm] observers, ANCH_TOP - oldest observer, row of the new keyframe + 1
+    int *tt_int;                                                    // [3 max_lm] row of the oldest observer | good_lmid | removed_lmid
+    double *tt_dbl;                                                 // [4 max_lm] good_wpt (x3) | good_invdepth
+    // host copy of kf_state (which keyframes live), so that a call can refuse a dead keyframe without a synchronisation
+    unsigned char *kf_alive_h, *snap_kf_alive_h;
 };
 
 namespace {
@@ -150,6 +159,9 @@ struct map_job {
     double K[4];                                 // left intrinsics (update stage, inverse depth)
     const double *snap_kf_pose, *snap_lm_xyz; const unsigned char *snap_kf_state, *snap_lm_state, *snap_obs_flag;
     int snap_kf, snap_lm, snap_obs;
+    // temporal triangulation (hdr / zero_blk point at the stage's own block in its job records)
+    int *tt_nobs, *tt_old, *tt_nrow, *tt_arow, *tt_good_lmid, *tt_rm_lmid;
+    double *tt_good_wpt, *tt_good_inv;
 };
 
 // the flat problem of one map inside its output block: the same carve on the device (emitters, update stage) and on the
@@ -752,6 +764,160 @@ __global__ __launch_bounds__(256) void mu_apply_kernel(const map_job *__restrict
     if (st != (int)M.lm_state[l]) j.lm_state_w[l] = (unsigned char)st;
 }
 
+// ---- Mapper::triangulateTemporal (src/mapper.cpp:191-344) on the tables ---------------------------------------------
+// The new keyframe's 2D keypoints are the live rows (newkf, l) of landmarks that are alive and neither OV2_LM_3D nor
+// OV2_LM_KP3D.  Header of the stage (its own block, cleared per call): what ov2_map_temporal reports.
+enum { TH_SELECTED = 0, TH_CANDIDATES, TH_GOOD, TH_REMOVED };
+
+__device__ __forceinline__ bool lm_is_2d(const map_view &M, int lm) { return !(M.lm_state[lm] & (OV2_LM_3D | OV2_LM_KP3D)); }
+
+// observer scan: MapPoint::set_kfids_.size(), its *begin() (order-independent integer atomics) and the row of the new keyframe
+__global__ __launch_bounds__(256) void mt_observers_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf, lm;
+    if (i >= M.n_obs || !obs_live(M, i, kf, lm) || !lm_is_2d(M, lm)) return;
+    atomicAdd(&j.tt_nobs[lm], 1);
+    atomicMax(&j.tt_old[lm], ANCH_TOP - kf);       // the smallest kfid wins
+    if (kf == j.newkf) j.tt_nrow[lm] = i + 1;      // one live row per (keyframe, landmark): one writer
+}
+
+// row scan: the row of the oldest observer of every landmark the new keyframe holds in 2D
+__global__ __launch_bounds__(256) void mt_rows_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf, lm;
+    if (i >= M.n_obs || !obs_live(M, i, kf, lm) || !lm_is_2d(M, lm) || !j.tt_nrow[lm]) return;
+    if (j.tt_old[lm] == ANCH_TOP - kf) j.tt_arow[lm] = i;
+}
+
+// SE3::inverse / SE3::operator* of the host mirror (ov2_host.cpp), so that Tcicj = Tciw * Twcj rounds as it does there
+__device__ __forceinline__ void unit_quat_R(const double *T, double R[9])
+{
+    double x = T[3], y = T[4], z = T[5], w = T[6];
+    const double n = __dsqrt_rn(x * x + y * y + z * z + w * w);
+    x /= n; y /= n; z /= n; w /= n;
+    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
+    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
+    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
+}
+
+__device__ __forceinline__ void se3_inverse(const double *T, double out[7])
+{
+    double R[9];
+    unit_quat_R(T, R);
+    out[0] = -(R[0] * T[0] + R[3] * T[1] + R[6] * T[2]);
+    out[1] = -(R[1] * T[0] + R[4] * T[1] + R[7] * T[2]);
+    out[2] = -(R[2] * T[0] + R[5] * T[1] + R[8] * T[2]);
+    const double n = __dsqrt_rn(T[3] * T[3] + T[4] * T[4] + T[5] * T[5] + T[6] * T[6]);
+    out[3] = -T[3] / n; out[4] = -T[4] / n; out[5] = -T[5] / n; out[6] = T[6] / n;
+}
+
+__device__ __forceinline__ void se3_mul(const double *A, const double *B, double out[7])
+{
+    double Ra[9], Rb[9], R[9];
+    unit_quat_R(A, Ra);
+    unit_quat_R(B, Rb);
+    R[0] = Ra[0] * Rb[0] + Ra[1] * Rb[3] + Ra[2] * Rb[6]; R[1] = Ra[0] * Rb[1] + Ra[1] * Rb[4] + Ra[2] * Rb[7];
+    R[2] = Ra[0] * Rb[2] + Ra[1] * Rb[5] + Ra[2] * Rb[8]; R[3] = Ra[3] * Rb[0] + Ra[4] * Rb[3] + Ra[5] * Rb[6];
+    R[4] = Ra[3] * Rb[1] + Ra[4] * Rb[4] + Ra[5] * Rb[7]; R[5] = Ra[3] * Rb[2] + Ra[4] * Rb[5] + Ra[5] * Rb[8];
+    R[6] = Ra[6] * Rb[0] + Ra[7] * Rb[3] + Ra[8] * Rb[6]; R[7] = Ra[6] * Rb[1] + Ra[7] * Rb[4] + Ra[8] * Rb[7];
+    R[8] = Ra[6] * Rb[2] + Ra[7] * Rb[5] + Ra[8] * Rb[8];
+    out[0] = Ra[0] * B[0] + Ra[1] * B[1] + Ra[2] * B[2] + A[0];
+    out[1] = Ra[3] * B[0] + Ra[4] * B[1] + Ra[5] * B[2] + A[1];
+    out[2] = Ra[6] * B[0] + Ra[7] * B[1] + Ra[8] * B[2] + A[2];
+    const double t = R[0] + R[4] + R[8];   // rot_to_quat
+    if (t > 0) {
+        const double q = __dsqrt_rn(t + 1.0) * 2;
+        out[6] = 0.25 * q; out[3] = (R[7] - R[5]) / q; out[4] = (R[2] - R[6]) / q; out[5] = (R[3] - R[1]) / q;
+    } else if (R[0] > R[4] && R[0] > R[8]) {
+        const double q = __dsqrt_rn(1.0 + R[0] - R[4] - R[8]) * 2;
+        out[6] = (R[7] - R[5]) / q; out[3] = 0.25 * q; out[4] = (R[1] + R[3]) / q; out[5] = (R[2] + R[6]) / q;
+    } else if (R[4] > R[8]) {
+        const double q = __dsqrt_rn(1.0 + R[4] - R[0] - R[8]) * 2;
+        out[6] = (R[2] - R[6]) / q; out[3] = (R[1] + R[3]) / q; out[4] = 0.25 * q; out[5] = (R[5] + R[7]) / q;
+    } else {
+        const double q = __dsqrt_rn(1.0 + R[8] - R[0] - R[4]) * 2;
+        out[6] = (R[3] - R[1]) / q; out[3] = (R[2] + R[6]) / q; out[4] = (R[5] + R[7]) / q; out[5] = 0.25 * q;
+    }
+}
+
+// Frame::computeKeypoint (src/frame.cpp:246-254) for a pinhole camera: unpx as the float the host keeps, bearing iK * [unpx, 1] normalised
+__device__ __forceinline__ void bearing_of(const double K[4], const double *uv, float &u, float &v, double bv[3])
+{
+    u = (float)uv[0]; v = (float)uv[1];
+    const double x = ((double)u - K[2]) / K[0], y = ((double)v - K[3]) / K[1];
+    const double nrm = __dsqrt_rn(x * x + y * y + 1.0 * 1.0);
+    bv[0] = x / nrm; bv[1] = y / nrm; bv[2] = 1.0 / nrm;
+}
+
+// candidates + apply, one lane per landmark: the reference's skips (:258-289), then tri_kernel's arithmetic in its order
+// (tri_pair.h) and the bookkeeping of its verdict (:310-333).  Every landmark is read and written by its own lane only.
+__global__ __launch_bounds__(256) void mt_tri_kernel(const map_job *__restrict__ J, int stereo, float max_err)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if ((int)blockIdx.x * 256 >= M.max_lm) return;   // uniform per workgroup
+    __shared__ int s_cnt[4], s_base[2];
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    const int nr = l < M.max_lm ? j.tt_nrow[l] : 0;
+    bool cand = false, good = false, rm = false;
+    double wpt[3] = {0., 0., 0.}, invdepth = 0.;
+    const int oldkf = nr ? ANCH_TOP - j.tt_old[l] : -1;
+    if (nr && j.tt_nobs[l] >= 2 && oldkf != j.newkf) {   // :258-266 (the oldest observer is alive and holds the keypoint: obs_live)
+        double Tciw[7], T[7];
+        se3_inverse(M.kf_pose + 7 * (size_t)oldkf, Tciw);
+        se3_mul(Tciw, M.kf_pose + 7 * (size_t)j.newkf, T);   // Tcicj (:278-279)
+        if (!(stereo && __dsqrt_rn(T[0] * T[0] + T[1] * T[1] + T[2] * T[2]) < 0.01)) {   // :287
+            cand = true;
+            float ua, va, ub, vb;
+            double f1[3], f2[3], f2u[3], R[9], X[3];
+            const int ar = min(max(j.tt_arow[l], 0), M.n_obs - 1);   // written by the row scan for every such landmark; clamped all the same
+            bearing_of(j.K, M.obs_uv + 2 * (size_t)ar, ua, va, f1);
+            bearing_of(j.K, M.obs_uv + 2 * (size_t)(nr - 1), ub, vb, f2);
+            ov2tri::quat_R(T, R);
+            ov2tri::rotate(R, f2, f2u);
+            const double parallax = ov2tri::parallax_px(j.K, f2u, ua, va);
+            ov2tri::midpoint(T, f1, f2u, X);
+            const int st = ov2tri::gates(T, R, X, j.K, j.K, ua, va, ub, vb, max_err);
+            if (st == OV2_TRI_OK) {
+                good = true;
+                ov2tri::to_world(M.kf_pose + 7 * (size_t)oldkf, X, wpt);
+                invdepth = 1. / X[2];
+            } else rm = parallax > 20.;
+        }
+    }
+    if (nr) atomicAdd(&s_cnt[TH_SELECTED], 1);
+    if (cand) atomicAdd(&s_cnt[TH_CANDIDATES], 1);
+    const int rg = good ? atomicAdd(&s_cnt[TH_GOOD], 1) : 0, rr = rm ? atomicAdd(&s_cnt[TH_REMOVED], 1) : 0;
+    __syncthreads();
+    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) {   // one global atomic per workgroup and counter
+        const int base = atomicAdd(&j.hdr[threadIdx.x], s_cnt[threadIdx.x]);
+        if (threadIdx.x >= TH_GOOD) s_base[threadIdx.x - TH_GOOD] = base;
+    }
+    __syncthreads();
+    if (good) {   // MapManager::updateMapPoint: the point turns 3D with its keypoints
+        j.lm_xyz_w[3 * (size_t)l] = wpt[0]; j.lm_xyz_w[3 * (size_t)l + 1] = wpt[1]; j.lm_xyz_w[3 * (size_t)l + 2] = wpt[2];
+        j.lm_state_w[l] = M.lm_state[l] | OV2_LM_3D | OV2_LM_KP3D;
+        const int o = s_base[0] + rg;
+        j.tt_good_lmid[o] = l; j.tt_good_inv[o] = invdepth;
+        j.tt_good_wpt[3 * (size_t)o] = wpt[0]; j.tt_good_wpt[3 * (size_t)o + 1] = wpt[1]; j.tt_good_wpt[3 * (size_t)o + 2] = wpt[2];
+    }
+    if (rm) {     // MapManager::removeMapPointObs(lmid, newkf)
+        j.obs_flag_w[nr - 1] = 0;
+        j.tt_rm_lmid[s_base[1] + rr] = l;
+    }
+}
+
 // gathers the headers of all maps (update counts) for one D2H
 __global__ __launch_bounds__(64) void mb_hdr_gather_kernel(const map_job *__restrict__ J)
 {
@@ -898,6 +1064,11 @@ static ov2_status alloc_tables(ov2_map *m)
         m->lm_new = reinterpret_cast<unsigned char *>(m->lm_anchor + L);
     }
     A(obs_cnt, N); A(obs_off, N); A(blk, 2 * ((std::max(N, L) + 1023) / 1024 + 1));   // block sums, up to 64-bit
+    m->tt_zero_bytes = (sizeof(int) * (MH_N + 3 * L) + 15) & ~(size_t)15;
+    A(tt_zero, m->tt_zero_bytes); A(tt_int, 3 * L); A(tt_dbl, 4 * L);
+    if (s == OV2_OK) {
+        m->tt_nobs = reinterpret_cast<int *>(m->tt_zero) + MH_N; m->tt_old = m->tt_nobs + L; m->tt_nrow = m->tt_old + L;
+    }
 #undef A
     return s;
 }
@@ -905,7 +1076,8 @@ static ov2_status alloc_tables(ov2_map *m)
 static void free_capacity_arrays(ov2_map *m)
 {
     void *dev[] = {m->kf_pose, m->kf_state, m->lm_xyz, m->lm_state, m->obs_kf, m->obs_lm, m->obs_scale, m->obs_uv, m->obs_ruv,
-                   m->obs_flag, m->zero_blk, m->kf_idx, m->lm_flag, m->lm_pack, m->lm_pidx, m->obs_cnt, m->obs_off, m->blk};
+                   m->obs_flag, m->zero_blk, m->kf_idx, m->lm_flag, m->lm_pack, m->lm_pidx, m->obs_cnt, m->obs_off, m->blk,
+                   m->tt_zero, m->tt_int, m->tt_dbl};
     for (void *p : dev) if (p) (void)hipFree(p);
 }
 
@@ -921,12 +1093,18 @@ static ov2_status ensure_capacity(ov2_map *m, int need_kf, int need_lm, int need
     m->kf_pose = nullptr; m->kf_state = nullptr; m->lm_xyz = nullptr; m->lm_state = nullptr;
     m->obs_kf = m->obs_lm = m->obs_scale = nullptr; m->obs_uv = m->obs_ruv = nullptr; m->obs_flag = nullptr;
     m->zero_blk = nullptr; m->kf_idx = m->lm_flag = m->obs_cnt = m->obs_off = m->blk = nullptr; m->lm_pack = m->lm_pidx = nullptr;
+    m->tt_zero = nullptr; m->tt_int = nullptr; m->tt_dbl = nullptr;
     ov2_status s = alloc_tables(m);
+    unsigned char *alive = s == OV2_OK ? (unsigned char *)calloc((size_t)m->max_kf, 1) : nullptr;
+    if (s == OV2_OK && !alive) s = ov2_set_err(c, OV2_ERR_NOMEM, "map keyframe list of %d entries", m->max_kf);
     if (s != OV2_OK) {
         free_capacity_arrays(m);
         *m = old;
         return s;
     }
+    memcpy(alive, old.kf_alive_h, (size_t)old.max_kf);
+    free(old.kf_alive_h);
+    m->kf_alive_h = alive;
     hipStream_t st = c->stream;
     const size_t K = old.max_kf, L = old.max_lm, N = old.n_obs;
     OV2_HIP(c, hipMemsetAsync(m->kf_state, 0, (size_t)m->max_kf, st));
@@ -944,6 +1122,7 @@ static ov2_status ensure_capacity(ov2_map *m, int need_kf, int need_lm, int need
     for (void *p : snap) if (p) (void)hipFree(p);
     m->snap_kf_pose = m->snap_lm_xyz = nullptr; m->snap_kf_state = m->snap_lm_state = m->snap_obs_flag = nullptr;
     m->snap_kf = m->snap_lm = m->snap_obs = 0; m->snap_floor = 0;
+    free(m->snap_kf_alive_h); m->snap_kf_alive_h = nullptr;
     return OV2_OK;
 }
 
@@ -1041,6 +1220,7 @@ extern "C" ov2_status ov2_map_create(ov2_ctx *c, int max_kf, int max_lm, int max
     memset(m, 0, sizeof(*m));
     m->c = c; m->max_kf = max_kf; m->max_lm = max_lm; m->max_obs = max_obs;
     ov2_status s = alloc_tables(m);
+    if (s == OV2_OK && !(m->kf_alive_h = (unsigned char *)calloc((size_t)max_kf, 1))) s = ov2_set_err(c, OV2_ERR_NOMEM, "map keyframe list");
     if (s == OV2_OK && hipHostMalloc((void **)&m->hdr_host, MH_N * sizeof(int), hipHostMallocDefault) != hipSuccess)
         s = ov2_set_err(c, OV2_ERR_NOMEM, "map header hipHostMalloc");
     if (s != OV2_OK) { ov2_map_destroy(m); return s; }
@@ -1061,6 +1241,7 @@ static void free_tables(ov2_map *m)
     if (m->out_dev) (void)hipFree(m->out_dev);
     if (m->out_host) (void)hipHostFree(m->out_host);
     if (m->hdr_host) (void)hipHostFree(m->hdr_host);
+    free(m->kf_alive_h); free(m->snap_kf_alive_h);
 }
 
 void ov2_map_orphan(ov2_map *m)
@@ -1142,6 +1323,7 @@ extern "C" ov2_status ov2_map_add_keyframe(ov2_map *m, int kfid, const double *T
         OV2_HIP(c, hipMemcpyAsync(m->obs_flag + o, df, n, hipMemcpyDeviceToDevice, st));
     }
     m->n_obs += n;
+    m->kf_alive_h[kfid] = 1;
     OV2_HIP(c, hipStreamSynchronize(st));   // the staging block is free again
     return OV2_OK;
 }
@@ -1247,6 +1429,7 @@ extern "C" ov2_status ov2_map_remove_keyframe(ov2_map *m, int kfid)
     if (kfid < 0 || kfid >= m->max_kf) return ov2_set_err(c, OV2_ERR_INVALID, "kfid %d outside the map capacity", kfid);
     OV2_HIP(c, hipSetDevice(c->device));
     OV2_HIP(c, hipMemsetAsync(m->kf_state + kfid, 0, 1, c->stream));
+    m->kf_alive_h[kfid] = 0;
     return OV2_OK;
 }
 
@@ -1492,6 +1675,58 @@ extern "C" ov2_status ov2_map_local_ba_update_batch(ov2_ctx *c, int B, ov2_map *
     return OV2_OK;
 }
 
+// ---- temporal triangulation of B maps: four launches, no synchronisation unless the lists are asked for -------------
+extern "C" ov2_status ov2_map_triangulate_temporal_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf,
+                                                         const double *calib_l, int stereo, float max_reproj_err, ov2_map_temporal *out)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps || !newkf || !calib_l) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_triangulate_temporal_batch: null argument");
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        if (!m || m->c != c) return ov2_set_err(c, OV2_ERR_INVALID, "map %d of the batch is null or belongs to another context", b);
+        if (newkf[b] < 0 || newkf[b] >= m->max_kf || !m->kf_alive_h[newkf[b]])
+            return ov2_set_err(c, OV2_ERR_INVALID, "keyframe %d is not alive in map %d", newkf[b], b);
+        for (int q = 0; q < b; ++q)
+            if (maps[q] == m) return ov2_set_err(c, OV2_ERR_INVALID, "map %d appears twice in the batch", b);
+    }
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    job_table JT;
+    ov2_status s = JT.begin(c, B);
+    if (s != OV2_OK) return s;
+    int nmax = 0, lmax = 0; unsigned zmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        map_job j = job_of(m, newkf[b], -1);
+        // the stage's own header and cleared block stand where the kernels shared with the set-up look for them
+        j.hdr = reinterpret_cast<int *>(m->tt_zero); j.zero_blk = m->tt_zero; j.zero_vec16 = (unsigned)(m->tt_zero_bytes / 16);
+        j.tt_nobs = m->tt_nobs; j.tt_old = m->tt_old; j.tt_nrow = m->tt_nrow;
+        j.tt_arow = m->tt_int; j.tt_good_lmid = m->tt_int + m->max_lm; j.tt_rm_lmid = m->tt_int + 2 * (size_t)m->max_lm;
+        j.tt_good_wpt = m->tt_dbl; j.tt_good_inv = m->tt_dbl + 3 * (size_t)m->max_lm;
+        for (int k = 0; k < 4; ++k) j.K[k] = calib_l[4 * b + k];
+        JT.set(b, j);
+        nmax = std::max(nmax, m->n_obs); lmax = std::max(lmax, m->max_lm); zmax = std::max(zmax, j.zero_vec16);
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), gL((lmax + 255) / 256, B), b256(256);
+    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::min(64u, (zmax + 255) / 256), B), b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mt_observers_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mt_rows_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mt_tri_kernel, gL, b256, 0, st, JT.dev, stereo ? 1 : 0, max_reproj_err);
+    if (!out) return OV2_OK;   // asynchronous: the caller did not ask for what to replay
+    OV2_LAUNCH(c, OV2_K_MAP, mb_hdr_gather_kernel, dim3(1, B), dim3(64), 0, st, JT.dev);
+    if ((s = JT.fetch_headers()) != OV2_OK) return s;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        const int *H = JT.hdr_host + (size_t)b * MH_N;
+        out[b].n_selected = H[TH_SELECTED]; out[b].n_candidates = H[TH_CANDIDATES]; out[b].n_good = H[TH_GOOD]; out[b].n_removed = H[TH_REMOVED];
+        out[b].good_lmid = m->tt_int + m->max_lm; out[b].removed_lmid = m->tt_int + 2 * (size_t)m->max_lm;
+        out[b].good_wpt = m->tt_dbl; out[b].good_invdepth = m->tt_dbl + 3 * (size_t)m->max_lm;
+    }
+    return OV2_OK;
+}
+
 // ---- saved state (bench / tests: every job starts from the same map) ----------------------------------------------
 extern "C" ov2_status ov2_map_save_state(ov2_map *m)
 {
@@ -1517,6 +1752,9 @@ extern "C" ov2_status ov2_map_save_state(ov2_map *m)
     if (N) OV2_HIP(c, hipMemcpyAsync(m->snap_obs_flag, m->obs_flag, N, hipMemcpyDeviceToDevice, st));
     OV2_HIP(c, hipStreamSynchronize(st));
     m->snap_kf = (int)K; m->snap_lm = (int)L; m->snap_obs = (int)N; m->snap_floor = 0;
+    free(m->snap_kf_alive_h);
+    if (!(m->snap_kf_alive_h = (unsigned char *)malloc(std::max<size_t>(K, 1)))) return ov2_set_err(c, OV2_ERR_NOMEM, "saved keyframe list");
+    memcpy(m->snap_kf_alive_h, m->kf_alive_h, K);
     return OV2_OK;
 }
 
@@ -1535,7 +1773,10 @@ extern "C" ov2_status ov2_map_restore_state_batch(ov2_ctx *c, int B, ov2_map *co
     job_table JT;
     ov2_status s = JT.begin(c, B);
     if (s != OV2_OK) return s;
-    for (int b = 0; b < B; ++b) { JT.set(b, job_of(maps[b], -1, -1)); maps[b]->last_valid = 0; }
+    for (int b = 0; b < B; ++b) {
+        JT.set(b, job_of(maps[b], -1, -1)); maps[b]->last_valid = 0;
+        memcpy(maps[b]->kf_alive_h, maps[b]->snap_kf_alive_h, (size_t)maps[b]->max_kf);
+    }
     if ((s = JT.upload()) != OV2_OK) return s;
     OV2_LAUNCH(c, OV2_K_MAP, mb_restore_kernel, dim3(64, B), dim3(256), 0, c->stream, JT.dev);
     // the job table must have been read before the staging block is reused: the next call that stages waits for this

@@ -10,8 +10,11 @@
 #include <cstring>
 
 #include "ov2_internal.h"
+#include "tri_pair.h"
 
 namespace {
+
+using namespace ov2tri;   // the per-pair arithmetic (tri_pair.h), shared with the temporal stage of the map mirror
 
 struct tri_args {
     int n, method, G;
@@ -25,30 +28,6 @@ struct tri_args {
     unsigned char *status;
 };
 
-__device__ __forceinline__ void quat_R(const double *T, double R[9])
-{
-    const double x = T[3], y = T[4], z = T[5], w = T[6];
-    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z);     R[2] = 2 * (x * z + w * y);
-    R[3] = 2 * (x * y + w * z);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
-    R[6] = 2 * (x * z - w * y);     R[7] = 2 * (y * z + w * x);     R[8] = 1 - 2 * (x * x + y * y);
-}
-
-// CameraCalibration::projectCamToImage (src/camera_calibration.cpp:243-252)
-__device__ __forceinline__ void project(const double K[4], const double p[3], float &u, float &v)
-{
-    const double invz = 1. / p[2];
-    const double x = p[0] * invz, y = p[1] * invz;
-    u = (float)(K[0] * x + K[2]);
-    v = (float)(K[1] * y + K[3]);
-}
-
-// cv::norm(Point2f - Point2f): float differences, square root in double
-__device__ __forceinline__ double norm2f(float ax, float ay, float bx, float by)
-{
-    const float dx = ax - bx, dy = ay - by;
-    return __dsqrt_rn((double)dx * dx + (double)dy * dy);
-}
-
 __global__ __launch_bounds__(256) void tri_kernel(tri_args A)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -60,14 +39,10 @@ __global__ __launch_bounds__(256) void tri_kernel(tri_args A)
     quat_R(T, R);
     const double f1[3] = {A.bv_a[3 * i], A.bv_a[3 * i + 1], A.bv_a[3 * i + 2]};
     const double f2[3] = {A.bv_b[3 * i], A.bv_b[3 * i + 1], A.bv_b[3 * i + 2]};
-    const double f2u[3] = {R[0] * f2[0] + R[1] * f2[1] + R[2] * f2[2], R[3] * f2[0] + R[4] * f2[1] + R[5] * f2[2],
-                           R[6] * f2[0] + R[7] * f2[1] + R[8] * f2[2]};
+    double f2u[3];
+    rotate(R, f2, f2u);
     const float ua = A.unpx_a[2 * i], va = A.unpx_a[2 * i + 1], ub = A.unpx_b[2 * i], vb = A.unpx_b[2 * i + 1];
-    if (A.parallax) {
-        float ru, rv;
-        project(A.Kb, f2u, ru, rv);
-        A.parallax[i] = norm2f(ua, va, ru, rv);
-    }
+    if (A.parallax) A.parallax[i] = parallax_px(A.Kb, f2u, ua, va);
     double X[3];
     if (A.method == OV2_TRI_RECTIFIED) {
         const float disp = ua - ub;
@@ -83,39 +58,17 @@ __global__ __launch_bounds__(256) void tri_kernel(tri_args A)
         X[1] = (double)z * ((double)va / A.Ka[1] - A.Ka[3] / A.Ka[1]);
         X[2] = (double)z;
     } else {
-        const double a00 = f1[0] * f1[0] + f1[1] * f1[1] + f1[2] * f1[2];
-        const double a10 = f1[0] * f2u[0] + f1[1] * f2u[1] + f1[2] * f2u[2];
-        const double a01 = -a10;
-        const double a11 = -(f2u[0] * f2u[0] + f2u[1] * f2u[1] + f2u[2] * f2u[2]);
-        const double b0 = T[0] * f1[0] + T[1] * f1[1] + T[2] * f1[2];
-        const double b1 = T[0] * f2u[0] + T[1] * f2u[1] + T[2] * f2u[2];
-        const double invdet = 1. / (a00 * a11 - a01 * a10);
-        const double l0 = (a11 * invdet) * b0 + (-a01 * invdet) * b1;
-        const double l1 = (-a10 * invdet) * b0 + (a00 * invdet) * b1;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) X[k] = (l0 * f1[k] + (T[k] + l1 * f2u[k])) / 2.;
+        midpoint(T, f1, f2u, X);
     }
-    const double d[3] = {X[0] - T[0], X[1] - T[1], X[2] - T[2]};
-    const double Xb[3] = {R[0] * d[0] + R[3] * d[1] + R[6] * d[2], R[1] * d[0] + R[4] * d[1] + R[7] * d[2],
-                          R[2] * d[0] + R[5] * d[1] + R[8] * d[2]};
-    int st = OV2_TRI_OK;
-    if (X[2] < 0.1 || Xb[2] < 0.1) st = OV2_TRI_BEHIND;
-    else {
-        float pu, pv, qu, qv;
-        project(A.Ka, X, pu, pv);
-        project(A.Kb, Xb, qu, qv);
-        const float ldist = (float)norm2f(pu, pv, ua, va), rdist = (float)norm2f(qu, qv, ub, vb);
-        if (ldist > A.max_err || rdist > A.max_err) st = OV2_TRI_REPROJ;
-    }
+    const int st = gates(T, R, X, A.Ka, A.Kb, ua, va, ub, vb, A.max_err);
     A.status[i] = (unsigned char)st;
 #pragma unroll
     for (int k = 0; k < 3; ++k) A.pt_a[3 * i + k] = X[k];
     if (A.wpt) {
-        const double *W = A.Twc_a + 7 * g;
-        double Rw[9];
-        quat_R(W, Rw);
+        double w[3];
+        to_world(A.Twc_a + 7 * g, X, w);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) A.wpt[3 * i + k] = Rw[3 * k] * X[0] + Rw[3 * k + 1] * X[1] + Rw[3 * k + 2] * X[2] + W[k];
+        for (int k = 0; k < 3; ++k) A.wpt[3 * i + k] = w[k];
     }
 }
 

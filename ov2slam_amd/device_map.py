@@ -24,6 +24,12 @@ class SetupC(C.Structure):
                 ("bad_lmid", C.c_void_p), ("res_outlier", C.c_void_p)]
 
 
+class TemporalC(C.Structure):
+    """ov2_map_temporal"""
+    _fields_ = [("n_selected", C.c_int32), ("n_candidates", C.c_int32), ("n_good", C.c_int32), ("n_removed", C.c_int32),
+                ("good_lmid", C.c_void_p), ("good_wpt", C.c_void_p), ("good_invdepth", C.c_void_p), ("removed_lmid", C.c_void_p)]
+
+
 class UpdateC(C.Structure):
     """ov2_local_ba_update"""
     _fields_ = [("n_removed_lm", C.c_int32), ("n_removed_obs", C.c_int32), ("n_stereo_off", C.c_int32),
@@ -109,6 +115,23 @@ class DeviceMap:
             m.add_keyframe(k, prob.pose[k], lm[a:b], un[a:b], run[a:b], st[a:b])
         return m
 
+    @classmethod
+    def from_temporal_map(cls, ctx, m, spare=(8, 8, 64)):
+        """a map of synth_temporal.make_map(dangling=False) as MapManager::attachDevice mirrors the host map built from it:
+        every observed landmark alive and seen by the current frame, a 3D map point's keypoints counted as 3D (lm_state_of),
+        2D points at the origin"""
+        assert not len(m["forget_lm"]) and not len(m["forget_kf"]) and not len(m["forget_kp"]), "dangling references have no mirror form"
+        dm = cls(ctx, m["n_kf"] + spare[0], m["n_lm"] + spare[1], len(m["obs_kf"]) + spare[2])
+        dm.newkf = int(m["newkf"])
+        seen = np.unique(m["obs_lm"]).astype(np.int32)
+        is3d = m["lm_3d"][seen].astype(bool)
+        st = np.where(is3d, LM_ALIVE | LM_OBS | LM_3D | LM_KP3D, LM_ALIVE | LM_OBS).astype(np.uint8)
+        dm.set_landmarks(seen, np.where(is3d[:, None], m["lm_xyz"][seen], 0.0), st)
+        for k in range(m["n_kf"]):
+            sel = m["obs_kf"] == k
+            dm.add_keyframe(k, m["poses"][k], m["obs_lm"][sel], m["obs_uv"][sel].astype(np.float64))
+        return dm
+
     def close(self):
         if getattr(self, "h", None):
             self.L.ov2_map_destroy(self.h)
@@ -167,6 +190,10 @@ class DeviceMap:
     def save_state(self):
         _check(self.ctx.h, self.L.ov2_map_save_state(self.h))
 
+    def triangulate_temporal_batch(self, others=(), newkf=None, calib_l=None, stereo=True, max_reproj_err=3.0, want_lists=True):
+        """ov2_map_triangulate_temporal_batch on this map and `others` in one call; see triangulate_temporal_batch"""
+        return triangulate_temporal_batch(self.ctx, [self] + list(others), newkf, calib_l, stereo, max_reproj_err, want_lists)
+
     def download(self):
         """dict of the tables (host copies)"""
         nk, nl, no = C.c_int(), C.c_int(), C.c_int()
@@ -190,6 +217,36 @@ def canonical_state(d):
         live &= d["kf_state"][d["obs_kf"]].astype(bool) & (d["lm_state"][d["obs_lm"]] & LM_ALIVE).astype(bool)
     obs = {(int(k), int(l)): int(f & OBS_STEREO) for k, l, f in zip(d["obs_kf"][live], d["obs_lm"][live], d["obs_flag"][live])}
     return kfs, lms, obs
+
+
+def triangulate_temporal_batch(ctx, maps, newkf=None, calib_l=None, stereo=True, max_reproj_err=3.0, want_lists=True):
+    """Mapper::triangulateTemporal on the tables of the maps (DeviceMap objects or raw ov2_map handles), keyframe newkf[b]
+    (default: each map's newkf) with the left intrinsics calib_l (4,) or (B, 4).  Returns per map dict(selected, candidates,
+    good_lmid, good_wpt, good_invdepth, removed_lmid), the lists sorted by lmid -- or None (want_lists=False: asynchronous)"""
+    B = len(maps)
+    hs = (C.c_void_p * B)(*[getattr(m, "h", m) for m in maps])
+    nk = np.ascontiguousarray([m.newkf for m in maps] if newkf is None else newkf, np.int32)
+    K = None if calib_l is None else np.ascontiguousarray(np.broadcast_to(np.asarray(calib_l, np.float64), (B, 4)))
+    out = (TemporalC * B)() if want_lists else None
+    _check(ctx.h, ctx.lib.ov2_map_triangulate_temporal_batch(ctx.h, B, hs, nk.ctypes.data_as(C.c_void_p),
+                                                             None if K is None else K.ctypes.data_as(C.c_void_p),
+                                                             int(bool(stereo)), float(max_reproj_err), out))
+    if not want_lists:
+        return None
+
+    def fetch(ptr, shape, dt):
+        a = np.zeros(shape, dt)
+        if a.nbytes:
+            _check(ctx.h, ctx.lib.ov2_memcpy_d2h(ctx.h, a.ctypes.data_as(C.c_void_p), ptr, a.nbytes))
+        return a
+    res = []
+    for t in out:
+        gl, rl = fetch(t.good_lmid, t.n_good, np.int32), fetch(t.removed_lmid, t.n_removed, np.int32)
+        gw, gi = fetch(t.good_wpt, (t.n_good, 3), np.float64), fetch(t.good_invdepth, t.n_good, np.float64)
+        o = np.argsort(gl)
+        res.append(dict(selected=t.n_selected, candidates=t.n_candidates, good_lmid=gl[o], good_wpt=gw[o], good_invdepth=gi[o],
+                        removed_lmid=np.sort(rl)))
+    return res
 
 
 def restore_state_batch(ctx, maps):

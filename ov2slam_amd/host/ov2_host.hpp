@@ -239,6 +239,10 @@ struct SlamParams {   // the subset of include/slam_params.hpp the path reads (Y
     float fransac_err_ = 3.f;
     bool bdo_random_ = true;
     uint64_t epi_seed_ = 0;
+    // Mapper::triangulateTemporal in Mapper::run (src/mapper.cpp:107-126).  The reference has no switch: it runs the stage for
+    // every keyframe with 2D keypoints.  The switch exists here, and is off by default, because loop tests recorded on loops
+    // without the stage hold exact counts; see SlamManager::triangulateTemporal (ov2_slam.hpp).
+    bool do_temporal_ = false;
 };
 
 struct Vec2 {
@@ -275,6 +279,28 @@ struct P3pStats {   // what the P3P branch of VisualFrontEnd::computePose did on
     int status = 0;          // p3pRansac's return
     int points = 0, removed = 0;   // correspondences in, observations removed before ceresPnP
     int reset = 0;           // 1: the frame ended in resetFrame()
+};
+
+// what Mapper::triangulateTemporal did with one keypoint of the new keyframe (src/mapper.cpp:238-336, in its order)
+enum TemporalBranch {
+    TT_NO_MAPPOINT = 0,   // :244-247 observation removed
+    TT_ALREADY_3D,        // :250-252
+    TT_FEW_OBSERVERS,     // :258-260
+    TT_OLDEST_IS_NEW,     // :264-266
+    TT_KF_GONE,           // :271-273
+    TT_NO_MOTION,         // :287-289 (stereo_)
+    TT_KP_MISSING,        // :292-295
+    TT_GOOD,              // :332-335
+    TT_BEHIND_REMOVED,    // :310-315, parallax > 20
+    TT_BEHIND_KEPT,
+    TT_REPROJ_REMOVED,    // :323-329, parallax > 20
+    TT_REPROJ_KEPT
+};
+
+struct TemporalStats {   // Mapper::triangulateTemporal on the last keyframe
+    int ran = 0;
+    int n_kps = 0, n_candidates = 0, n_good = 0, n_removed = 0;   // 2D keypoints offered, candidates, good, observations removed
+    std::vector<int> lmid, branch;                               // per offered keypoint, ids ascending: its TemporalBranch
 };
 
 struct EpiStats {   // what VisualFrontEnd::epipolar2d2dFiltering did on the last frame

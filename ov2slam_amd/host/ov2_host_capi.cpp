@@ -111,6 +111,67 @@ int ov2h_frame_init_grid(void *p, int kfid, int ncellsize)
 // drops a map point but leaves the keypoints that reference it (the "plm == nullptr" branch of stereoMatching, :414)
 int ov2h_map_forget_landmark(void *p, int lmid) { ((HostMap *)p)->map->map_plms_.erase(lmid); return 0; }
 
+// ---- a host map of N keyframes with chosen 2D / 3D keypoints (tests of Mapper::triangulateTemporal) ----
+// n keypoints of keyframe kfid; a map point is created on first use, 3D at xyz[3 i ..] when lm3d[i] is set, and the keypoint
+// carries Keypoint::is3d_ = kp3d[i]
+int ov2h_map_add_kps(void *p, int kfid, int n, const int *lmid, const float *uv, const uint8_t *kp3d, const uint8_t *lm3d, const double *xyz)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kfid);
+    if (!f) return -1;
+    for (int i = 0; i < n; ++i) {
+        auto lm = m->map->getMapPoint(lmid[i]);
+        if (!lm) {
+            lm = std::make_shared<MapPoint>(lmid[i], kfid, true);
+            if (lm3d[i]) lm->setPoint(Vec3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]});
+            m->map->map_plms_[lmid[i]] = lm;
+        }
+        Keypoint kp;
+        kp.lmid_ = lmid[i];
+        f->computeKeypoint(Point2f{uv[2 * i], uv[2 * i + 1]}, kp);
+        kp.is3d_ = kp3d[i] != 0;
+        f->addKeypoint(kp);
+        lm->addKfObs(kfid);
+    }
+    return 0;
+}
+
+// drops a keyframe but leaves it in the observer sets of its map points (the "pkf == nullptr" branch, src/mapper.cpp:271)
+int ov2h_map_forget_keyframe(void *p, int kfid) { ((HostMap *)p)->map->map_pkfs_.erase(kfid); return 0; }
+
+// drops a keypoint of keyframe kfid but leaves the keyframe among the observers of its map point (src/mapper.cpp:292-295)
+int ov2h_map_forget_kp(void *p, int kfid, int lmid)
+{
+    auto f = ((HostMap *)p)->map->getKeyframe(kfid);
+    if (!f) return -1;
+    f->removeKeypointById(lmid);
+    return 0;
+}
+
+// Mapper::triangulateTemporal on keyframe kfid.  lmid / branch (capacity cap): the keypoints offered, ids ascending, and the
+// ov2::TemporalBranch each one took; stats[4]: 2D keypoints offered, candidates, good, observations removed.  Returns the
+// number of keypoints offered, or -1 - status
+int ov2h_triangulate_temporal(void *p, void *ctx, int kfid, float max_reproj_err, int cap, int *lmid, int *branch, double *stats)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kfid);
+    if (!f) return -1 - (int)OV2_ERR_INVALID;
+    m->st->fmax_reproj_err_ = max_reproj_err;
+    TemporalStats ts;
+    const ov2_status s = SlamManager::triangulateTemporal((ov2_ctx *)ctx, *m->map, *m->st, *f, ts);
+    if (s != OV2_OK) return -1 - (int)s;
+    for (int i = 0; i < ts.n_kps && i < cap; ++i) { lmid[i] = ts.lmid[i]; branch[i] = ts.branch[i]; }
+    if (stats) { stats[0] = ts.n_kps; stats[1] = ts.n_candidates; stats[2] = ts.n_good; stats[3] = ts.n_removed; }
+    return ts.n_kps;
+}
+
+// MapPoint::invdepth_ of a landmark (-1: never set, or no such landmark)
+double ov2h_landmark_invdepth(void *p, int lmid)
+{
+    auto lm = ((HostMap *)p)->map->getMapPoint(lmid);
+    return lm ? lm->invdepth_ : -1.;
+}
+
 int ov2h_set_params(void *p, int klt_use_prior, int stereo_rect, int nklt_pyr_lvl, int nklt_win_size)
 {
     HostMap *m = (HostMap *)p;
@@ -799,6 +860,16 @@ void ov2h_slam_p3p_stats(void *p, double *out)
 {
     const P3pStats &e = ((SlamManager *)p)->last_p3p_;
     out[0] = e.ran; out[1] = e.status; out[2] = e.points; out[3] = e.removed; out[4] = e.reset;
+}
+
+// Mapper::triangulateTemporal in Mapper::run (src/mapper.cpp:107-126); off by default, see SlamParams::do_temporal_
+void ov2h_slam_set_temporal(void *p, int on) { ((SlamManager *)p)->pslamstate_->do_temporal_ = on != 0; }
+
+// out[5] of the last keyframe: the stage ran, 2D keypoints offered, candidates, good, observations removed
+void ov2h_slam_temporal_stats(void *p, double *out)
+{
+    const TemporalStats &t = ((SlamManager *)p)->last_temporal_;
+    out[0] = t.ran; out[1] = t.n_kps; out[2] = t.n_candidates; out[3] = t.n_good; out[4] = t.n_removed;
 }
 
 // out[3] of the last frame (keyframes only): keypoints described, local map points offered to matchToMap, merges

@@ -381,8 +381,11 @@ ov2_status SlamManager::mapperRun(const Keyframe &kf)
         last_.n_stereo = (int)pnewkf->nb_stereo_kps_;
         if (pnewkf->nb2dkps_ > 0 && pnewkf->nb_stereo_kps_ > 0 && (s = triangulateStereo(*pnewkf)) != OV2_OK) return s;
     }
-    // triangulateTemporal (:191-344) needs keypoints that stayed 2D over two keyframes with enough parallax: with a stereo rig
-    // every matched keypoint is 3D after its first keyframe; the mono-only path is not built here.
+    // :107-126: a keypoint whose stereo match or stereo triangulation failed is still 2D here; the reference turns it 3D as soon
+    // as two keyframes see it with enough parallax.  Behind do_temporal_ (off by default, see ov2_slam.hpp); mono initialisation
+    // and the mono reset rule (:128-144) are not built.
+    last_temporal_ = TemporalStats();
+    if (S.do_temporal_ && pnewkf->nb2dkps_ > 0 && pnewkf->kfid_ > 0 && (s = triangulateTemporal(*pnewkf)) != OV2_OK) return s;
     pmap_->updateFrameCovisibility(*pnewkf);                     // :160
     pcurframe_->map_covkfs_ = pnewkf->map_covkfs_;               // :163
     if (S.use_brief_ && kf.kfid_ > 0 && S.bdo_track_localmap_ && (s = matchingToLocalMap(*pnewkf)) != OV2_OK) return s;   // :153-162
@@ -546,6 +549,82 @@ ov2_status SlamManager::triangulateStereo(Frame &frame)
             continue;
         }
         pmap_->updateMapPoint(vkps[i].lmid_, Vec3{wpt[3 * i], wpt[3 * i + 1], wpt[3 * i + 2]}, 1. / pt[3 * i + 2]);
+    }
+    return OV2_OK;
+}
+
+ov2_status SlamManager::triangulateTemporal(ov2_ctx *ctx, MapManager &map, const SlamParams &st, Frame &frame, TemporalStats &ts)
+{   // src/mapper.cpp:191-344: the per-keypoint body (parallax, triangulation, depth and reprojection gates, world point) is
+    // ov2_triangulate_pairs with one pose pair per source keyframe; what stays here is the selection and the bookkeeping
+    ts = TemporalStats();
+    ts.ran = 1;
+    std::vector<Keypoint> vkps;   // Frame::getKeypoints2d, ids ascending
+    for (const auto &kv : frame.mapkps_)
+        if (!kv.second.is3d_) vkps.push_back(kv.second);
+    if (vkps.empty()) return OV2_OK;
+    std::sort(vkps.begin(), vkps.end(), [](const Keypoint &a, const Keypoint &b) { return a.lmid_ < b.lmid_; });
+    const size_t nbkps = vkps.size();
+    ts.n_kps = (int)nbkps;
+    ts.lmid.resize(nbkps); ts.branch.assign(nbkps, -1);
+    const SE3 Twcj = frame.getTwc();
+    std::map<int, int> grp_of;                 // source keyframe -> pose pair
+    std::vector<double> T_ab, Twc_a;           // Tcicj, Twc of the source keyframe, 7 each
+    std::vector<int32_t> grp;
+    std::vector<size_t> idx;                   // candidate -> keypoint
+    std::vector<double> bva, bvb;
+    std::vector<float> ua, ub;
+    for (size_t i = 0; i < nbkps; ++i) {
+        const int lmid = vkps[i].lmid_;
+        ts.lmid[i] = lmid;
+        auto plm = map.getMapPoint(lmid);
+        if (!plm) { map.removeMapPointObs(lmid, frame.kfid_); ++ts.n_removed; ts.branch[i] = TT_NO_MAPPOINT; continue; }   // :244-247
+        if (plm->is3d_) { ts.branch[i] = TT_ALREADY_3D; continue; }                                                        // :250-252
+        const std::set<int> co_kf_ids = plm->getKfObsSet();
+        if (co_kf_ids.size() < 2) { ts.branch[i] = TT_FEW_OBSERVERS; continue; }                                            // :258-260
+        const int kfid = *co_kf_ids.begin();
+        if (frame.kfid_ == kfid) { ts.branch[i] = TT_OLDEST_IS_NEW; continue; }                                             // :264-266
+        auto pkf = map.getKeyframe(kfid);
+        if (!pkf) { ts.branch[i] = TT_KF_GONE; continue; }                                                                  // :271-273
+        auto it = grp_of.find(kfid);
+        if (it == grp_of.end()) {   // :277-284
+            const SE3 Tcicj = pkf->getTcw() * Twcj, Twci = pkf->getTwc();
+            it = grp_of.emplace(kfid, (int)grp_of.size()).first;
+            T_ab.insert(T_ab.end(), Tcicj.v.begin(), Tcicj.v.end());
+            Twc_a.insert(Twc_a.end(), Twci.v.begin(), Twci.v.end());
+        }
+        const double *t = &T_ab[7 * (size_t)it->second];
+        if (st.stereo_ && std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]) < 0.01) { ts.branch[i] = TT_NO_MOTION; continue; }   // :287-289
+        const Keypoint kfkp = pkf->getKeypointById(lmid);
+        if (kfkp.lmid_ != lmid) { ts.branch[i] = TT_KP_MISSING; continue; }                                                 // :292-295
+        idx.push_back(i); grp.push_back(it->second);
+        bva.push_back(kfkp.bv_.x); bva.push_back(kfkp.bv_.y); bva.push_back(kfkp.bv_.z);
+        bvb.push_back(vkps[i].bv_.x); bvb.push_back(vkps[i].bv_.y); bvb.push_back(vkps[i].bv_.z);
+        ua.push_back(kfkp.unpx_.x); ua.push_back(kfkp.unpx_.y); ub.push_back(vkps[i].unpx_.x); ub.push_back(vkps[i].unpx_.y);
+    }
+    const size_t n = idx.size();
+    ts.n_candidates = (int)n;
+    if (n == 0) return OV2_OK;
+    std::vector<double> pt(3 * n), wpt(3 * n), parallax(n);
+    std::vector<uint8_t> status(n);
+    const CameraCalibration &cl = *frame.pcalib_leftcam_;
+    const double Kl[4] = {cl.fx_, cl.fy_, cl.cx_, cl.cy_};
+    const ov2_status s = ov2_triangulate_pairs(ctx, (int)n, OV2_TRI_MIDPOINT, (int)grp_of.size(), T_ab.data(), Twc_a.data(), grp.data(), bva.data(),
+                                               bvb.data(), ua.data(), ub.data(), Kl, Kl, st.fmax_reproj_err_, pt.data(), wpt.data(),
+                                               parallax.data(), status.data());
+    if (s != OV2_OK) return s;
+    for (size_t k = 0; k < n; ++k) {
+        const size_t i = idx[k];
+        const int lmid = vkps[i].lmid_;
+        if (status[k] == OV2_TRI_OK) {   // :332-335
+            map.updateMapPoint(lmid, Vec3{wpt[3 * k], wpt[3 * k + 1], wpt[3 * k + 2]}, 1. / pt[3 * k + 2]);
+            ++ts.n_good; ts.branch[i] = TT_GOOD;
+            continue;
+        }
+        const bool behind = status[k] == OV2_TRI_BEHIND;
+        if (parallax[k] > 20.) {         // :310-315, :323-329
+            map.removeMapPointObs(lmid, frame.kfid_);
+            ++ts.n_removed; ts.branch[i] = behind ? TT_BEHIND_REMOVED : TT_REPROJ_REMOVED;
+        } else ts.branch[i] = behind ? TT_BEHIND_KEPT : TT_REPROJ_KEPT;
     }
     return OV2_OK;
 }

@@ -5,7 +5,7 @@
 //                   computeParallax  :1069-1142
 //   MapManager::createKeyframe       src/map_manager.cpp:43-60  prepareFrame :64-115  extractKeypoints :286-340
 //               addKeypointsToFrame  :196-211   addKeyframe :621-634   addMapPoint :636-659
-//   Mapper::run (one keyframe)       src/mapper.cpp:38-189      triangulateStereo :346-461
+//   Mapper::run (one keyframe)       src/mapper.cpp:38-189      triangulateStereo :346-461   triangulateTemporal :191-344
 //   SlamManager::run (one image)     src/ov2slam.cpp:152-205    Estimator::applyLocalBA  src/estimator.cpp:67-98
 // The reference runs front-end, mapper and estimator on three threads; here one call processes one stereo frame to the
 // end (keyframe work included), i.e. the reference with bforce_realtime = 0 and an idle back-end: deterministic.
@@ -85,6 +85,14 @@ public:
     SlamStats last_;
     EpiStats last_epi_;   // epipolar2d2dFiltering on the last frame (doepipolar_)
     P3pStats last_p3p_;   // the P3P branch of computePose on the last frame (bp3preq_ or dop3p_)
+    TemporalStats last_temporal_;   // triangulateTemporal on the last keyframe (do_temporal_)
+    // Mapper::triangulateTemporal (src/mapper.cpp:191-344): the 2D keypoints of a new keyframe whose map point an older keyframe
+    // observes turn 3D once the two views triangulate them (a keypoint whose stereo match failed stays 2D for good without it).
+    // Mapper::run calls it for every keyframe with nb2dkps_ > 0 && kfid_ > 0, stereo as well as mono (:107-126); mapperRun does
+    // so only with SlamParams::do_temporal_, which the reference does not have and which is OFF by default: the existing loop
+    // tests hold exact counts recorded without the stage.  Selection and bookkeeping run here, the per-pair arithmetic is one
+    // ov2_triangulate_pairs call over all source keyframes.  Static so that a bare MapManager (tests) can run it too.
+    static ov2_status triangulateTemporal(ov2_ctx *ctx, MapManager &map, const SlamParams &st, Frame &frame, TemporalStats &stats);
     std::vector<SlamStats> stats_;
     std::vector<SE3> traj_;
 
@@ -108,6 +116,7 @@ private:
     void addKeyframe();
     ov2_status mapperRun(const Keyframe &kf);                                                          // src/mapper.cpp:38-189
     ov2_status triangulateStereo(Frame &frame);                                                        // :346-461
+    ov2_status triangulateTemporal(Frame &frame) { return triangulateTemporal(ctx_, *pmap_, *pslamstate_, frame, last_temporal_); }   // :191-344
     ov2_status fixedWindowBA();                                                                        // LoopPolicy::ba_window
     int nkfid_ = 0, nlmid_ = 0;
     SE3 Twc_prev_;           // compose_motion: the pose of the frame before the last

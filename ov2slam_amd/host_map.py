@@ -76,6 +76,16 @@ def lib():
         L.ov2h_slam_set_p3p.restype = None
         L.ov2h_slam_p3p_stats.argtypes = [C.c_void_p, dp]
         L.ov2h_slam_p3p_stats.restype = None
+        L.ov2h_slam_set_temporal.argtypes = [C.c_void_p, C.c_int]
+        L.ov2h_slam_set_temporal.restype = None
+        L.ov2h_slam_temporal_stats.argtypes = [C.c_void_p, dp]
+        L.ov2h_slam_temporal_stats.restype = None
+        L.ov2h_map_add_kps.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, fp, u8, u8, dp]
+        L.ov2h_map_forget_keyframe.argtypes = [C.c_void_p, C.c_int]
+        L.ov2h_map_forget_kp.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ov2h_triangulate_temporal.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, ip, ip, dp]
+        L.ov2h_landmark_invdepth.argtypes = [C.c_void_p, C.c_int]
+        L.ov2h_landmark_invdepth.restype = C.c_double
         L.ov2h_set_p3p.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_ulonglong]
         L.ov2h_p3p_stats.argtypes = [C.c_void_p, dp]
         L.ov2h_p3p_stats.restype = None
@@ -500,6 +510,11 @@ class CppSlam:
             e = np.zeros(5)
             lib().ov2h_slam_p3p_stats(self.h_, _dp(e))
             self.p3p_stats.append(dict(ran=int(e[0]), status=int(e[1]), points=int(e[2]), removed=int(e[3]), reset=int(e[4])))
+        if getattr(self, "temporal_stats", None) is not None and self.stats[-1]["kf"]:
+            e = np.zeros(5)
+            lib().ov2h_slam_temporal_stats(self.h_, _dp(e))
+            self.temporal_stats.append(dict(frame=int(self.stats[-1]["frame"]), ran=int(e[0]), kps2d=int(e[1]), candidates=int(e[2]),
+                                            good=int(e[3]), removed=int(e[4])))
         if getattr(self, "kf_stats", None) is not None and self.stats[-1]["kf"]:
             k = np.zeros(3)
             lib().ov2h_slam_kf_stats(self.h_, _dp(k))
@@ -527,6 +542,13 @@ class CppSlam:
         (also useful with dop3p off: the branch runs whenever bp3preq_ is set)."""
         lib().ov2h_slam_set_p3p(self.h_, int(bool(dop3p)))
         self.p3p_stats = []
+
+    def set_temporal(self, on=True):
+        """Mapper::triangulateTemporal in Mapper::run (src/mapper.cpp:107-126): the new keyframe's 2D keypoints are triangulated
+        against the oldest keyframe that observes them.  The reference always runs it; here it is off until this call, because
+        the existing loop tests hold counts recorded without it.  Starts the per-keyframe temporal_stats list."""
+        lib().ov2h_slam_set_temporal(self.h_, int(bool(on)))
+        self.temporal_stats = []
 
     def check_map(self):
         """(violations of the host map's invariants, total) -- see ov2h_slam_check_map"""
@@ -738,6 +760,55 @@ class TwoViewMap:
 
     def __del__(self):
         self.close()
+
+
+class TemporalMap(HostMap):
+    """N keyframes of the C++ host mirror with 2D / 3D keypoints, built from a map of ov2slam_amd.synth_temporal.make_map, to
+    run Mapper::triangulateTemporal (SlamManager::triangulateTemporal) on one of them.  export / attach_device / flush_device /
+    device_handle are HostMap's."""
+
+    def __init__(self, m, stereo=True):
+        L = lib()
+        K = np.ascontiguousarray(m["K4"], np.float64)
+        t_lr7 = np.ascontiguousarray([0.11, 0, 0, 0, 0, 0, 1.0])
+        self.h = L.ov2h_map_create(int(stereo), 1, _dp(K), _dp(K), _dp(t_lr7), int(m["w"]), int(m["h"]), 25)
+        self.m, self.newkf = m, int(m["newkf"])
+        ip, fp, u8 = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+        for k in range(m["n_kf"]):   # ascending: a map point is created by its oldest observer, as MapManager::addMapPoint does
+            L.ov2h_map_add_keyframe(self.h, k, _dp(np.ascontiguousarray(m["poses"][k], np.float64)))
+            sel = m["obs_kf"] == k
+            lm = np.ascontiguousarray(m["obs_lm"][sel], np.int32)
+            uv = np.ascontiguousarray(m["obs_uv"][sel], np.float32)
+            kp3d, lm3d = np.ascontiguousarray(m["lm_kp3d"][lm], np.uint8), np.ascontiguousarray(m["lm_3d"][lm], np.uint8)
+            xyz = np.ascontiguousarray(m["lm_xyz"][lm], np.float64)
+            assert L.ov2h_map_add_kps(self.h, k, len(lm), lm.ctypes.data_as(ip), uv.ctypes.data_as(fp), kp3d.ctypes.data_as(u8),
+                                      lm3d.ctypes.data_as(u8), _dp(xyz)) == 0
+        for k, l in m["forget_kp"]:
+            assert L.ov2h_map_forget_kp(self.h, int(k), int(l)) == 0
+        for l in m["forget_lm"]:
+            L.ov2h_map_forget_landmark(self.h, int(l))
+        for k in m["forget_kf"]:
+            L.ov2h_map_forget_keyframe(self.h, int(k))
+
+    def attach_device(self, ctx, max_kf=None, max_lm=None, max_obs=None):
+        rc = lib().ov2h_map_attach_device(self.h, ctx.h, max_kf or self.m["n_kf"] + 8, max_lm or self.m["n_lm"] + 8,
+                                          max_obs or len(self.m["obs_kf"]) + 64)
+        if rc != 0:
+            raise RuntimeError(f"attachDevice failed (status {rc})")
+
+    def triangulate_temporal(self, ctx, max_reproj_err=3.0):
+        """the stage on keyframe newkf: (lmid ascending, ov2::TemporalBranch per keypoint, stats dict)"""
+        cap = self.m["n_lm"]
+        lm, br, st = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(4)
+        ip = C.POINTER(C.c_int)
+        n = lib().ov2h_triangulate_temporal(self.h, ctx.h, self.newkf, float(max_reproj_err), cap, lm.ctypes.data_as(ip),
+                                            br.ctypes.data_as(ip), _dp(st))
+        if n < 0:
+            raise RuntimeError(f"triangulateTemporal: status {-1 - n}")
+        return lm[:n].copy(), br[:n].copy(), dict(kps2d=int(st[0]), candidates=int(st[1]), good=int(st[2]), removed=int(st[3]))
+
+    def invdepth(self, lmid):
+        return float(lib().ov2h_landmark_invdepth(self.h, int(lmid)))
 
 
 class FrontEndFrame:
