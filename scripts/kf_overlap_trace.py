@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from summarize_prof import short  # noqa: E402
 
 DET = {"det_mask_kernel", "det_worklist_kernel", "det_mineig_kernel", "det_fast_kernel", "det_assemble_kernel", "subpix_kernel"}
-KLT = {"klt_compact_kernel", "klt_stage1_kernel", "klt_resume_kernel", "klt_stage2_kernel", "epi_gate_kernel"}
+KLT = {"klt_compact_kernel", "klt_stage1_kernel", "klt_stage2_kernel", "epi_gate_kernel"}
 PYR = {"clahe_lut_kernel", "level0_kernel", "level_kernel", "level23_kernel", "clahe_level0_kernel"}
 
 
