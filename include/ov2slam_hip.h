@@ -664,6 +664,49 @@ ov2_status ov2_map_triangulate_temporal_batch(ov2_ctx *ctx, int B, ov2_map *cons
                                               const double *calib_l /* B x 4 */, int stereo, float max_reproj_err,
                                               ov2_map_temporal *out /* B, or NULL */);
 
+/* Estimator::mapFiltering (src/estimator.cpp:101-183) with MapManager::removeKeyframe (src/map_manager.cpp:885-919) and
+ * MapPoint::isBad (src/map_point.cpp:215-234) on the tables of B map mirrors, one SLAM instance each, as they are at the
+ * call (pipeline order: set-up -> solve -> update -> filter).  Per map:
+ *  - gates: kf_filtering_ratio >= 1 or newkf[b] < 20 -> zero header, no work (:103-109);
+ *  - candidates: the alive keyframes k, 0 < k < newkf, whose covisibility with newkf -- recounted from the live rows as
+ *    the set-up recounts it -- is >= 1, examined in DESCENDING k, one after the other.  Keyframe 0 is never a candidate
+ *    (the reference's walk breaks there, and 0 is the smallest key);
+ *  - nb3dkps_ of k = live rows of k whose landmark carries OV2_LM_KP3D; below nmin_covscore / 2 (integer division) k is
+ *    removed at once and counted in n_few3d (:139-143);
+ *  - otherwise, over the live rows of k whose landmark carries OV2_LM_KP3D (Frame::getKeypoints3d): a landmark with
+ *    fewer than 2 observers (live rows) that is not OV2_LM_OBS and is OV2_LM_3D is bad -- OV2_LM_3D is cleared, the
+ *    landmark is listed in unset3d_lmid and skipped, whether or not k ends up removed; every other one counts in tot, and
+ *    in good when its CURRENT observer count is > 4;
+ *  - decision in float exactly as the reference writes it: (float)good / (float)tot > kf_filtering_ratio, 0 / 0 = NaN
+ *    compares false;
+ *  - removal: kf_state[k] = 0, the observer count of the landmark of every live row of k drops by one -- which the
+ *    older candidates then see: the walk is sequential, its result is NOT what counts taken once would give -- and k is
+ *    appended to removed_kfid.  A landmark that loses its last observer while not OV2_LM_3D also loses OV2_LM_KP3D:
+ *    the bit is the Keypoint::is3d_ of its observations, and it has none left (what MapManager::attachDevice gives it).
+ * Deviations from the reference: a row whose landmark or keyframe is dead is not live in the mirror (obs_live), so the
+ * branches "missing map point" (:151-154) and "keyframe gone" (:135-138) have nothing to do here; the candidates come from
+ * the recount, not from a stored Frame::map_covkfs_; anchors (MapPoint::kfid_) and descriptors are not mirror state (the
+ * update stage recounts the oldest observer).
+ * map = blockIdx.y of every launch, sizes come from device memory, seven launches whatever B: zero, row scan (observers,
+ * landmarks of newkf, rows and 3D rows per keyframe), the three scan kernels over the rows per keyframe, covisibility +
+ * scatter into the per-keyframe row index (a counting sort over obs_kf: O(rows) per map), and one workgroup per map that
+ * walks the candidates (block reduction of (good, tot) over the candidate's indexed rows, uniform decision, decrements,
+ * a barrier before the next candidate reads the counts) and hands header and removed list to the gathered copy.  The
+ * scratch arrays are the stage's own: the arrays of the last set-up stay as they are -- but the call ENDS what that
+ * set-up can be updated from (ov2_map_local_ba_update_batch then refuses the map, as after a squeeze; gated maps are left
+ * alone).  A state saved by ov2_map_save_state stays restorable.
+ * Refused with OV2_ERR_INVALID, tables untouched: newkf[b] not alive in map b, a map listed twice, out == NULL.
+ * One synchronisation per call (B headers + removed lists in one D2H); after it the map's host copy of the keyframe
+ * states is updated.  removed_kfid is pinned HOST memory of the map, unset3d_lmid a DEVICE array of the map; both valid
+ * until its next call of this function (or a growth of its tables). */
+typedef struct ov2_map_filter {
+    int32_t n_candidates, n_removed, n_few3d, n_unset3d;
+    const int32_t *removed_kfid;   /* HOST (pinned, the map's), n_removed, removal order = descending kfid */
+    const int32_t *unset3d_lmid;   /* DEVICE, n_unset3d, order arbitrary: landmarks whose OV2_LM_3D isBad() cleared */
+} ov2_map_filter;
+ov2_status ov2_map_filter_keyframes_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf,
+                                          int nmin_covscore, float kf_filtering_ratio, ov2_map_filter *out /* B */);
+
 /* Test / bench support.  ov2_map_save_state keeps a device copy of the mutable state of the tables (poses, landmark points
  * and states, observation flags); ov2_map_restore_state_batch rewinds B maps to it in one launch, asynchronously (every
  * bench job starts from the same noisy map, as a new keyframe of a live sequence would bring it).  ov2_map_download copies

@@ -57,6 +57,15 @@ struct ov2_map {
     double *tt_dbl;                                                 // [4 max_lm] good_wpt (x3) | good_invdepth
     // host copy of kf_state (which keyframes live), so that a call can refuse a dead keyframe without a synchronisation
     unsigned char *kf_alive_h, *snap_kf_alive_h;
+    // ov2_map_filter_keyframes_batch: scratch of its own as well
+    unsigned char *fl_zero; size_t fl_zero_bytes;                   // hdr (MH_N ints) | fl_nobs | fl_cov | fl_n3d | fl_cnt | fl_fill | fl_new: one clear per call
+    int *fl_nobs;                                                   // [max_lm] observers; the walk decrements them
+    int *fl_cov, *fl_n3d, *fl_cnt, *fl_fill;                        // [max_kf] covisibility with newkf, 3D rows, live rows, rows scattered so far
+    unsigned char *fl_new;                                          // [max_lm] observed by the new keyframe
+    int *fl_start;                                                  // [max_kf] exclusive scan of fl_cnt: where the keyframe's rows start in fl_rows
+    int *fl_rows;                                                   // [max_obs] live rows grouped by keyframe
+    int *fl_unset;                                                  // [max_lm] landmarks whose OV2_LM_3D the walk cleared
+    int *fl_removed_h; int fl_removed_cap;                          // pinned: the removed keyframes of the last call
 };
 
 namespace {
@@ -66,6 +75,8 @@ enum { MH_NBKPS = 0, MH_NB3D, MH_ABORT, MH_NMAXKF, MH_NPOSE, MH_NRES, MH_NLM, MH
        MH_OVER,                         // ... and 1 when that exceeds the map's output block: nothing was emitted, the host grows it and re-runs
        MH_NRM_LM, MH_NRM_OBS, MH_NST_OFF,   // update stage: landmarks removed, observations removed, stereo observations demoted
        MH_N = 16 };
+// header of the keyframe filter (its own block, cleared per call): what ov2_map_filter reports, and the scan total of the rows
+enum { FH_CANDIDATES = 0, FH_REMOVED, FH_FEW3D, FH_UNSET3D, FH_ROWS };
 #define ANCH_TOP 0x40000000   // anchor keyframe stored as ANCH_TOP - kfid under atomicMax: 0 = none, so the array lives in the zeroed block
 enum { OBS_ALIVE = 1, OBS_STEREO = 2 };
 enum { MAP_COMPACT_MIN_ROWS = 4096 };   // below this the scans cost nothing worth a reallocation
@@ -162,6 +173,10 @@ struct map_job {
     // temporal triangulation (hdr / zero_blk point at the stage's own block in its job records)
     int *tt_nobs, *tt_old, *tt_nrow, *tt_arow, *tt_good_lmid, *tt_rm_lmid;
     double *tt_good_wpt, *tt_good_inv;
+    // keyframe filter (hdr / zero_blk point at the stage's own block in its job records; hdr_out is followed by the removed list)
+    int fl_active;                               // 0: gated map (ratio >= 1 or newkf < 20), zero header and no work
+    int *fl_nobs, *fl_cov, *fl_n3d, *fl_cnt, *fl_fill, *fl_start, *fl_rows, *fl_unset;
+    unsigned char *fl_new;
 };
 
 // the flat problem of one map inside its output block: the same carve on the device (emitters, update stage) and on the
@@ -426,8 +441,9 @@ __global__ __launch_bounds__(256) void ms_res_count_kernel(const map_job *__rest
 
 // ---- exclusive scan of an array (int, or two counters packed in 64 bits) in three launches:
 // block sums -> their scan -> block offsets.  `which` selects the array of the map: SC_LM the landmark flags (64-bit,
-// total -> NLM | NBAD), SC_RES the residual counts (total -> NRES), SC_LIVE the keep flags of a compaction (total -> NLIVE)
-enum { SC_LM = 0, SC_RES, SC_LIVE };
+// total -> NLM | NBAD), SC_RES the residual counts (total -> NRES), SC_LIVE the keep flags of a compaction (total -> NLIVE),
+// SC_KF the live rows per keyframe of the keyframe filter (total -> FH_ROWS of its header)
+enum { SC_LM = 0, SC_RES, SC_LIVE, SC_KF };
 
 template <typename T>
 __device__ __forceinline__ T shfl_up_t(T v, int o)
@@ -447,6 +463,9 @@ __device__ __forceinline__ void scan_args(const map_job &j, int which, const T *
     if (which == SC_LM) {
         in = reinterpret_cast<const T *>(j.lm_pack); out = reinterpret_cast<T *>(j.lm_pidx); n = j.M.max_lm;
         total = reinterpret_cast<T *>(j.hdr + MH_NLM);
+    } else if (which == SC_KF) {
+        in = reinterpret_cast<const T *>(j.fl_cnt); out = reinterpret_cast<T *>(j.fl_start); n = j.fl_active ? j.M.max_kf : 0;
+        total = reinterpret_cast<T *>(j.hdr + FH_ROWS);
     } else {
         in = reinterpret_cast<const T *>(j.obs_cnt); out = reinterpret_cast<T *>(j.obs_off); n = j.M.n_obs;
         total = reinterpret_cast<T *>(j.hdr + (which == SC_RES ? MH_NRES : MH_NLIVE));
@@ -918,6 +937,148 @@ __global__ __launch_bounds__(256) void mt_tri_kernel(const map_job *__restrict__
     }
 }
 
+// ---- Estimator::mapFiltering (src/estimator.cpp:101-183) on the tables -----------------------------------------------
+// Rank of a lane among the lanes of its wave that hold the same key, and their number: one atomic per wave and key where
+// one per row would serialise on the keyframe's counter (rows of a keyframe are mostly adjacent).  All lanes of the wave
+// must call it; `first` is the lowest lane of the key (the lane's own when it is off), the one to issue the atomic.
+__device__ __forceinline__ int wave_rank_by_key(bool on, int key, int &count, int &first_lane)
+{
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(on);
+    int rank = 0;
+    count = 0; first_lane = lane;
+    while (todo) {
+        const int first = __ffsll((long long)todo) - 1;
+        const int k0 = __shfl(key, first);
+        const unsigned long long same = __ballot(on && key == k0);
+        if (on && key == k0) {
+            rank = __popcll(same & ((1ull << lane) - 1ull));
+            count = __popcll(same);
+            first_lane = first;
+        }
+        todo &= ~same;
+    }
+    return rank;
+}
+
+// row scan: MapPoint::set_kfids_.size() per landmark, the landmarks of the new keyframe, live rows and 3D rows
+// (Frame::nb3dkps_) per keyframe
+__global__ __launch_bounds__(256) void mf_count_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (!j.fl_active || (int)blockIdx.x * 256 >= M.n_obs) return;   // uniform per workgroup
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf = 0, lm = 0;
+    const bool live = i < M.n_obs && obs_live(M, i, kf, lm);
+    const bool is3d = live && (M.lm_state[lm] & OV2_LM_KP3D);
+    const int lane = threadIdx.x & 63;
+    int n, n3, first, first3;
+    wave_rank_by_key(live, kf, n, first);
+    wave_rank_by_key(is3d, kf, n3, first3);
+    if (live && lane == first) atomicAdd(&j.fl_cnt[kf], n);
+    if (is3d && lane == first3) atomicAdd(&j.fl_n3d[kf], n3);
+    if (!live) return;
+    atomicAdd(&j.fl_nobs[lm], 1);
+    if (kf == j.newkf) j.fl_new[lm] = 1;
+}
+
+// covisibility with the new keyframe (MapManager::updateFrameCovisibility, as ms_cov_kernel recounts it) and the scatter of
+// the counting sort: row i joins the rows of its keyframe, in any order (only integer sums are taken over them)
+__global__ __launch_bounds__(256) void mf_index_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (!j.fl_active || (int)blockIdx.x * 256 >= M.n_obs) return;   // uniform per workgroup
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf = 0, lm = 0;
+    const bool live = i < M.n_obs && obs_live(M, i, kf, lm);
+    const bool cov = live && kf != j.newkf && j.fl_new[lm];
+    const int lane = threadIdx.x & 63;
+    int n, nc, first, firstc;
+    const int rank = wave_rank_by_key(live, kf, n, first);
+    wave_rank_by_key(cov, kf, nc, firstc);
+    if (cov && lane == firstc) atomicAdd(&j.fl_cov[kf], nc);
+    int base = (live && lane == first) ? atomicAdd(&j.fl_fill[kf], n) : 0;
+    base = __shfl(base, first);
+    // fl_start[kf] + fl_cnt[kf] <= FH_ROWS <= n_obs <= max_obs: the slot lies inside fl_rows
+    if (live) j.fl_rows[j.fl_start[kf] + base + rank] = i;
+}
+
+// One workgroup per map walks the candidates newest -> oldest (:119-179); its tail hands the header and the removed list to
+// the gathered copy.  The observer counts and landmark states the walk edits live in global memory and are read again by
+// other lanes for the next candidate: they go through device-scope atomics, and a barrier separates a candidate's edits
+// from the next candidate's reads.  Everything that decides the control flow is uniform over the workgroup.
+#define MF_THREADS 256
+__device__ __forceinline__ int ld_int(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int ld_u8(const unsigned char *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_u8(unsigned char *p, int v) { __hip_atomic_store(p, (unsigned char)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ __launch_bounds__(MF_THREADS) void mf_walk_kernel(const map_job *__restrict__ J, int nmin_cov, float ratio_th, int list_cap)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ int s_good[MF_THREADS / 64], s_tot[MF_THREADS / 64], s_unset;
+    int ncand = 0, nrem = 0, nfew = 0;   // the same in every lane
+    if (tid == 0) s_unset = 0;
+    __syncthreads();
+    if (j.fl_active) {
+        for (int k = min(M.max_kf, j.newkf) - 1; k > 0; --k) {
+            if (!M.kf_state[k] || j.fl_cov[k] < 1) continue;   // not in the map / not in newkf's covisibility map
+            ++ncand;
+            const int cnt = j.fl_cnt[k];
+            const int *rows = j.fl_rows + j.fl_start[k];
+            bool remove = j.fl_n3d[k] < nmin_cov / 2;           // :139-143
+            if (remove) ++nfew;
+            else {
+                int good = 0, tot = 0;
+                for (int t = tid; t < cnt; t += MF_THREADS) {   // Frame::getKeypoints3d of k (:147-170)
+                    const int lm = M.obs_lm[rows[t]];
+                    const int st = ld_u8(j.lm_state_w + lm);
+                    if (!(st & OV2_LM_KP3D)) continue;
+                    const int nobs = ld_int(j.fl_nobs + lm);
+                    if (nobs < 2 && !(st & OV2_LM_OBS) && (st & OV2_LM_3D)) {   // MapPoint::isBad: is3d_ goes, the point is not counted
+                        st_u8(j.lm_state_w + lm, st & ~OV2_LM_3D);
+                        j.fl_unset[atomicAdd(&s_unset, 1)] = lm;                  // a landmark turns bad once: at most max_lm entries
+                        continue;
+                    }
+                    ++tot;
+                    good += nobs > 4;
+                }
+                for (int o = 32; o; o >>= 1) { good += __shfl_xor(good, o); tot += __shfl_xor(tot, o); }
+                if (lane == 0) { s_good[wv] = good; s_tot[wv] = tot; }
+                __syncthreads();
+                good = tot = 0;
+                for (int w = 0; w < MF_THREADS / 64; ++w) { good += s_good[w]; tot += s_tot[w]; }
+                // float ratio = (float)nbgoodobs / nbtot; if (ratio > fkf_filtering_ratio_): 0 / 0 is NaN and compares false (:171-172)
+                const float ratio = (float)good / (float)tot;
+                remove = ratio > ratio_th;
+            }
+            if (remove) {   // MapManager::removeKeyframe: every keypoint's map point loses the observer, 2D ones included
+                for (int t = tid; t < cnt; t += MF_THREADS) {
+                    const int lm = M.obs_lm[rows[t]];
+                    if (atomicSub(&j.fl_nobs[lm], 1) == 1) {   // no observer left: no keypoint left to carry Keypoint::is3d_
+                        const int st = ld_u8(j.lm_state_w + lm);
+                        if (!(st & OV2_LM_3D) && (st & OV2_LM_KP3D)) st_u8(j.lm_state_w + lm, st & ~OV2_LM_KP3D);
+                    }
+                }
+                if (tid == 0) {
+                    j.kf_state_w[k] = 0;
+                    if (nrem < list_cap) j.hdr_out[MH_N + nrem] = k;
+                }
+                ++nrem;
+            }
+            __syncthreads();   // the decrements and state edits before the next candidate's reads; s_good / s_tot free again
+        }
+    }
+    if (tid == 0) {
+        int *H = j.hdr_out;
+        for (int t = 0; t < MH_N; ++t) H[t] = 0;
+        H[FH_CANDIDATES] = ncand; H[FH_REMOVED] = nrem; H[FH_FEW3D] = nfew; H[FH_UNSET3D] = s_unset;
+    }
+}
+
 // gathers the headers of all maps (update counts) for one D2H
 __global__ __launch_bounds__(64) void mb_hdr_gather_kernel(const map_job *__restrict__ J)
 {
@@ -973,18 +1134,19 @@ struct job_table {
     ov2_ctx *c = nullptr; int B = 0;
     map_job *host = nullptr; const map_job *dev = nullptr;
     int *hdr_host = nullptr, *hdr_dev = nullptr;
-    ov2_status begin(ov2_ctx *ctx, int nb)
+    size_t stride = MH_N;                        // ints per map in the gathered copy: the header, then what the stage appends
+    ov2_status begin(ov2_ctx *ctx, int nb, int extra_ints = 0)
     {
-        c = ctx; B = nb;
+        c = ctx; B = nb; stride = MH_N + (size_t)extra_ints;
         void *h, *d;
         const size_t tab = ((size_t)B * sizeof(map_job) + 255) & ~(size_t)255;
-        const ov2_status s = ov2_staging(c, tab + (size_t)B * MH_N * sizeof(int) + 256, &h, &d);
+        const ov2_status s = ov2_staging(c, tab + (size_t)B * stride * sizeof(int) + 256, &h, &d);
         if (s != OV2_OK) return s;
         host = (map_job *)h; dev = (const map_job *)d;
         hdr_host = (int *)((unsigned char *)h + tab); hdr_dev = (int *)((unsigned char *)d + tab);
         return OV2_OK;
     }
-    void set(int b, const map_job &j) { host[b] = j; host[b].hdr_out = hdr_dev + (size_t)b * MH_N; }
+    void set(int b, const map_job &j) { host[b] = j; host[b].hdr_out = hdr_dev + (size_t)b * stride; }
     ov2_status upload()
     {
         OV2_HIP(c, hipMemcpyAsync((void *)dev, host, (size_t)B * sizeof(map_job), hipMemcpyHostToDevice, c->stream));
@@ -995,7 +1157,7 @@ struct job_table {
     }
     ov2_status fetch_headers()   // D2H of the gathered headers + the call's one synchronisation
     {
-        OV2_HIP(c, hipMemcpyAsync(hdr_host, hdr_dev, (size_t)B * MH_N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        OV2_HIP(c, hipMemcpyAsync(hdr_host, hdr_dev, (size_t)B * stride * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         OV2_HIP(c, hipStreamSynchronize(c->stream));
         return OV2_OK;
     }
@@ -1063,11 +1225,18 @@ static ov2_status alloc_tables(ov2_map *m)
         m->lm_anchor = m->lm_sel + L;
         m->lm_new = reinterpret_cast<unsigned char *>(m->lm_anchor + L);
     }
-    A(obs_cnt, N); A(obs_off, N); A(blk, 2 * ((std::max(N, L) + 1023) / 1024 + 1));   // block sums, up to 64-bit
+    A(obs_cnt, N); A(obs_off, N); A(blk, 2 * ((std::max(std::max(N, L), K) + 1023) / 1024 + 1));   // block sums, up to 64-bit
     m->tt_zero_bytes = (sizeof(int) * (MH_N + 3 * L) + 15) & ~(size_t)15;
     A(tt_zero, m->tt_zero_bytes); A(tt_int, 3 * L); A(tt_dbl, 4 * L);
     if (s == OV2_OK) {
         m->tt_nobs = reinterpret_cast<int *>(m->tt_zero) + MH_N; m->tt_old = m->tt_nobs + L; m->tt_nrow = m->tt_old + L;
+    }
+    m->fl_zero_bytes = (sizeof(int) * (MH_N + L + 4 * K) + L + 15) & ~(size_t)15;
+    A(fl_zero, m->fl_zero_bytes); A(fl_start, K); A(fl_rows, N); A(fl_unset, L);
+    if (s == OV2_OK) {
+        m->fl_nobs = reinterpret_cast<int *>(m->fl_zero) + MH_N; m->fl_cov = m->fl_nobs + L; m->fl_n3d = m->fl_cov + K;
+        m->fl_cnt = m->fl_n3d + K; m->fl_fill = m->fl_cnt + K;
+        m->fl_new = reinterpret_cast<unsigned char *>(m->fl_fill + K);
     }
 #undef A
     return s;
@@ -1077,7 +1246,7 @@ static void free_capacity_arrays(ov2_map *m)
 {
     void *dev[] = {m->kf_pose, m->kf_state, m->lm_xyz, m->lm_state, m->obs_kf, m->obs_lm, m->obs_scale, m->obs_uv, m->obs_ruv,
                    m->obs_flag, m->zero_blk, m->kf_idx, m->lm_flag, m->lm_pack, m->lm_pidx, m->obs_cnt, m->obs_off, m->blk,
-                   m->tt_zero, m->tt_int, m->tt_dbl};
+                   m->tt_zero, m->tt_int, m->tt_dbl, m->fl_zero, m->fl_start, m->fl_rows, m->fl_unset};
     for (void *p : dev) if (p) (void)hipFree(p);
 }
 
@@ -1094,6 +1263,7 @@ static ov2_status ensure_capacity(ov2_map *m, int need_kf, int need_lm, int need
     m->obs_kf = m->obs_lm = m->obs_scale = nullptr; m->obs_uv = m->obs_ruv = nullptr; m->obs_flag = nullptr;
     m->zero_blk = nullptr; m->kf_idx = m->lm_flag = m->obs_cnt = m->obs_off = m->blk = nullptr; m->lm_pack = m->lm_pidx = nullptr;
     m->tt_zero = nullptr; m->tt_int = nullptr; m->tt_dbl = nullptr;
+    m->fl_zero = nullptr; m->fl_start = m->fl_rows = m->fl_unset = nullptr;
     ov2_status s = alloc_tables(m);
     unsigned char *alive = s == OV2_OK ? (unsigned char *)calloc((size_t)m->max_kf, 1) : nullptr;
     if (s == OV2_OK && !alive) s = ov2_set_err(c, OV2_ERR_NOMEM, "map keyframe list of %d entries", m->max_kf);
@@ -1241,6 +1411,7 @@ static void free_tables(ov2_map *m)
     if (m->out_dev) (void)hipFree(m->out_dev);
     if (m->out_host) (void)hipHostFree(m->out_host);
     if (m->hdr_host) (void)hipHostFree(m->hdr_host);
+    if (m->fl_removed_h) (void)hipHostFree(m->fl_removed_h);
     free(m->kf_alive_h); free(m->snap_kf_alive_h);
 }
 
@@ -1723,6 +1894,77 @@ extern "C" ov2_status ov2_map_triangulate_temporal_batch(ov2_ctx *c, int B, ov2_
         out[b].n_selected = H[TH_SELECTED]; out[b].n_candidates = H[TH_CANDIDATES]; out[b].n_good = H[TH_GOOD]; out[b].n_removed = H[TH_REMOVED];
         out[b].good_lmid = m->tt_int + m->max_lm; out[b].removed_lmid = m->tt_int + 2 * (size_t)m->max_lm;
         out[b].good_wpt = m->tt_dbl; out[b].good_invdepth = m->tt_dbl + 3 * (size_t)m->max_lm;
+    }
+    return OV2_OK;
+}
+
+// ---- keyframe culling of B maps: seven launches whatever B, one synchronisation for the headers and removed lists ---
+extern "C" ov2_status ov2_map_filter_keyframes_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf, int nmin_covscore,
+                                                     float kf_filtering_ratio, ov2_map_filter *out)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps || !newkf || !out) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_filter_keyframes_batch: null argument");
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        if (!m || m->c != c) return ov2_set_err(c, OV2_ERR_INVALID, "map %d of the batch is null or belongs to another context", b);
+        if (newkf[b] < 0 || newkf[b] >= m->max_kf || !m->kf_alive_h[newkf[b]])
+            return ov2_set_err(c, OV2_ERR_INVALID, "keyframe %d is not alive in map %d", newkf[b], b);
+        for (int q = 0; q < b; ++q)
+            if (maps[q] == m) return ov2_set_err(c, OV2_ERR_INVALID, "map %d appears twice in the batch", b);
+    }
+    memset(out, 0, (size_t)B * sizeof(*out));
+    // src/estimator.cpp:103-109: the reference's "off" value of the ratio, and no culling before keyframe 20
+    int n_active = 0, nmax = 0, kmax = 0; unsigned zmax = 0;
+    for (int b = 0; b < B; ++b)
+        if (!(kf_filtering_ratio >= 1.f) && newkf[b] >= 20) { ++n_active; kmax = std::max(kmax, maps[b]->max_kf); }
+    if (!n_active) return OV2_OK;
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    for (int b = 0; b < B; ++b) {   // the pinned list of the map follows its keyframe capacity
+        ov2_map *m = maps[b];
+        if (m->fl_removed_cap >= m->max_kf) continue;
+        if (m->fl_removed_h) OV2_HIP(c, hipHostFree(m->fl_removed_h));
+        m->fl_removed_h = nullptr; m->fl_removed_cap = 0;
+        if (hipHostMalloc((void **)&m->fl_removed_h, (size_t)m->max_kf * sizeof(int), hipHostMallocDefault) != hipSuccess)
+            return ov2_set_err(c, OV2_ERR_NOMEM, "pinned keyframe list of %d entries", m->max_kf);
+        m->fl_removed_cap = m->max_kf;
+    }
+    job_table JT;
+    ov2_status s = JT.begin(c, B, kmax);
+    if (s != OV2_OK) return s;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        map_job j = job_of(m, newkf[b], -1);
+        // the stage's own header and cleared block stand where the kernels shared with the set-up look for them
+        j.hdr = reinterpret_cast<int *>(m->fl_zero); j.zero_blk = m->fl_zero;
+        j.fl_active = newkf[b] >= 20;
+        j.zero_vec16 = j.fl_active ? (unsigned)(m->fl_zero_bytes / 16) : 0u;
+        j.fl_nobs = m->fl_nobs; j.fl_cov = m->fl_cov; j.fl_n3d = m->fl_n3d; j.fl_cnt = m->fl_cnt; j.fl_fill = m->fl_fill;
+        j.fl_new = m->fl_new; j.fl_start = m->fl_start; j.fl_rows = m->fl_rows; j.fl_unset = m->fl_unset;
+        JT.set(b, j);
+        if (j.fl_active) { nmax = std::max(nmax, m->n_obs); zmax = std::max(zmax, j.zero_vec16); }
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), b256(256);
+    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::min(64u, (zmax + 255) / 256), B), b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mf_count_kernel, gN, b256, 0, st, JT.dev);
+    if ((s = exclusive_scan<int>(c, JT, SC_KF, kmax)) != OV2_OK) return s;
+    OV2_LAUNCH(c, OV2_K_MAP, mf_index_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mf_walk_kernel, dim3(1, B), dim3(MF_THREADS), 0, st, JT.dev, nmin_covscore, kf_filtering_ratio, kmax);
+    if ((s = JT.fetch_headers()) != OV2_OK) return s;
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = maps[b];
+        if (newkf[b] < 20) continue;
+        const int *H = JT.hdr_host + (size_t)b * JT.stride;
+        out[b].n_candidates = H[FH_CANDIDATES]; out[b].n_removed = H[FH_REMOVED]; out[b].n_few3d = H[FH_FEW3D]; out[b].n_unset3d = H[FH_UNSET3D];
+        out[b].removed_kfid = m->fl_removed_h; out[b].unset3d_lmid = m->fl_unset;
+        for (int i = 0; i < H[FH_REMOVED]; ++i) {
+            const int k = H[MH_N + i];
+            m->fl_removed_h[i] = k;
+            m->kf_alive_h[k] = 0;
+        }
+        m->last_valid = 0;   // its tables changed under the last set-up: no update stage from it any more
     }
     return OV2_OK;
 }

@@ -30,6 +30,12 @@ class TemporalC(C.Structure):
                 ("good_lmid", C.c_void_p), ("good_wpt", C.c_void_p), ("good_invdepth", C.c_void_p), ("removed_lmid", C.c_void_p)]
 
 
+class FilterC(C.Structure):
+    """ov2_map_filter"""
+    _fields_ = [("n_candidates", C.c_int32), ("n_removed", C.c_int32), ("n_few3d", C.c_int32), ("n_unset3d", C.c_int32),
+                ("removed_kfid", C.c_void_p), ("unset3d_lmid", C.c_void_p)]
+
+
 class UpdateC(C.Structure):
     """ov2_local_ba_update"""
     _fields_ = [("n_removed_lm", C.c_int32), ("n_removed_obs", C.c_int32), ("n_stereo_off", C.c_int32),
@@ -131,6 +137,31 @@ class DeviceMap:
             sel = m["obs_kf"] == k
             dm.add_keyframe(k, m["poses"][k], m["obs_lm"][sel], m["obs_uv"][sel].astype(np.float64))
         return dm
+
+    @classmethod
+    def from_filter_map(cls, ctx, m, spare=(8, 8, 64), capacity=None, late=0.1):
+        """a map of synth_filter.make_map as MapManager::attachDevice mirrors the host map built from it (lm_state_of: 2D points
+        at the origin).  A fraction `late` of the rows is appended after all keyframes stand, as merges append them, so that
+        the rows of a keyframe are not contiguous.  capacity: (max_kf, max_lm, max_obs) to start from instead of a fit"""
+        cap = capacity or (m["n_kf"] + spare[0], m["n_lm"] + spare[1], len(m["obs_kf"]) + spare[2])
+        dm = cls(ctx, *cap)
+        dm.newkf = int(m["newkf"])
+        seen = np.unique(m["obs_lm"]).astype(np.int32)
+        st = (LM_ALIVE | np.where(m["lm_3d"][seen] != 0, LM_3D, 0) | np.where(m["lm_isobs"][seen] != 0, LM_OBS, 0)
+              | np.where(m["lm_kp3d"][seen] != 0, LM_KP3D, 0)).astype(np.uint8)
+        hold = (np.arange(len(m["obs_kf"])) * 7919) % 100 < int(100 * late)
+        for k in range(m["n_kf"]):   # (a landmark id beyond the capacity grows the tables here, before its state is set)
+            sel = (m["obs_kf"] == k) & ~hold
+            dm.add_keyframe(k, m["poses"][k], m["obs_lm"][sel], m["obs_uv"][sel].astype(np.float64))
+        for k in np.unique(m["obs_kf"][hold]):
+            sel = (m["obs_kf"] == k) & hold
+            dm.add_keyframe(int(k), m["poses"][k], m["obs_lm"][sel], m["obs_uv"][sel].astype(np.float64))
+        dm.set_landmarks(seen, np.where((m["lm_3d"][seen] != 0)[:, None], m["lm_xyz"][seen], 0.0), st)
+        return dm
+
+    def filter_keyframes_batch(self, others=(), newkf=None, nmin_covscore=25, ratio=0.9):
+        """ov2_map_filter_keyframes_batch on this map and `others` in one call; see filter_keyframes_batch"""
+        return filter_keyframes_batch(self.ctx, [self] + list(others), newkf, nmin_covscore, ratio)
 
     def close(self):
         if getattr(self, "h", None):
@@ -246,6 +277,25 @@ def triangulate_temporal_batch(ctx, maps, newkf=None, calib_l=None, stereo=True,
         o = np.argsort(gl)
         res.append(dict(selected=t.n_selected, candidates=t.n_candidates, good_lmid=gl[o], good_wpt=gw[o], good_invdepth=gi[o],
                         removed_lmid=np.sort(rl)))
+    return res
+
+
+def filter_keyframes_batch(ctx, maps, newkf=None, nmin_covscore=25, ratio=0.9):
+    """Estimator::mapFiltering on the tables of the maps (DeviceMap objects or raw ov2_map handles), keyframe newkf[b] (default:
+    each map's newkf) as the new keyframe.  Returns per map dict(candidates, few3d, removed: kfids in removal order,
+    unset3d: sorted lmids whose OV2_LM_3D the stage cleared)"""
+    B = len(maps)
+    hs = (C.c_void_p * B)(*[getattr(m, "h", m) for m in maps])
+    nk = np.ascontiguousarray([m.newkf for m in maps] if newkf is None else newkf, np.int32)
+    out = (FilterC * B)()
+    _check(ctx.h, ctx.lib.ov2_map_filter_keyframes_batch(ctx.h, B, hs, nk.ctypes.data_as(C.c_void_p), int(nmin_covscore), float(ratio), out))
+    res = []
+    for f in out:
+        rm = np.ctypeslib.as_array(C.cast(f.removed_kfid, i32p), (f.n_removed,)).copy() if f.n_removed else np.zeros(0, np.int32)
+        un = np.zeros(f.n_unset3d, np.int32)
+        if f.n_unset3d:
+            _check(ctx.h, ctx.lib.ov2_memcpy_d2h(ctx.h, un.ctypes.data_as(C.c_void_p), f.unset3d_lmid, un.nbytes))
+        res.append(dict(candidates=f.n_candidates, few3d=f.n_few3d, removed=rm.tolist(), unset3d=np.sort(un).tolist()))
     return res
 
 

@@ -487,6 +487,25 @@ void MapManager::removeMapPoint(int lmid)
     touchMapPoint(lmid);
 }
 
+ov2_status MapManager::removeKeyframe(int kfid)
+{   // src/map_manager.cpp:885-919
+    auto pkfit = map_pkfs_.find(kfid);
+    if (pkfit == map_pkfs_.end()) return OV2_OK;
+    for (const auto &kp : pkfit->second->getKeypoints()) {   // 2D keypoints included
+        auto plmit = map_plms_.find(kp.lmid_);
+        if (plmit == map_plms_.end()) continue;
+        plmit->second->removeKfObs(kfid);
+        touchMapPoint(kp.lmid_);   // the mirror reads Keypoint::is3d_ off the first observer, which may just have gone
+    }
+    for (const auto &kfid_cov : pkfit->second->getCovisibleKfMap()) {
+        auto pcokfit = map_pkfs_.find(kfid_cov.first);
+        if (pcokfit != map_pkfs_.end()) pcokfit->second->removeCovisibleKf(kfid);
+    }
+    map_pkfs_.erase(pkfit);
+    if (dev_ && dev_kfs_.erase(kfid)) return ov2_map_remove_keyframe(dev_, kfid);
+    return OV2_OK;
+}
+
 void MapManager::removeObsFromCurFrameById(int lmid)
 {
     if (pcurframe_) pcurframe_->removeKeypointById(lmid);
@@ -1885,6 +1904,56 @@ ov2_status Estimator::applyLocalBA()
     const ov2_status s = poptimizer_->localBA(*pnewkf_, true);
     pslamstate_->blocalba_is_on_ = false;
     return s;
+}
+
+ov2_status Estimator::mapFiltering()
+{   // src/estimator.cpp:101-183
+    last_filter_ = FilterStats();
+    if (pslamstate_->fkf_filtering_ratio_ >= 1.) return OV2_OK;
+    if (!pnewkf_ || pnewkf_->kfid_ < 20) return OV2_OK;
+    last_filter_.ran = 1;
+    ov2_status s;
+    auto covkf_map = pnewkf_->getCovisibleKfMap();
+    for (auto it = covkf_map.rbegin(); it != covkf_map.rend(); it++) {
+        int kfid = it->first;
+        if (kfid == 0) break;
+        if (kfid >= pnewkf_->kfid_) continue;
+        auto pkf = pmap_->getKeyframe(kfid);
+        if (pkf == nullptr) {
+            pnewkf_->removeCovisibleKf(kfid);
+            continue;
+        }
+        last_filter_.n_candidates++;
+        if ((int)pkf->nb3dkps_ < pslamstate_->nmin_covscore_ / 2) {
+            if ((s = pmap_->removeKeyframe(kfid)) != OV2_OK) return s;
+            last_filter_.n_few3d++;
+            last_filter_.removed.push_back(kfid);
+            continue;
+        }
+        size_t nbgoodobs = 0;
+        size_t nbtot = 0;
+        for (const auto &kp : pkf->getKeypoints3d()) {
+            auto plm = pmap_->getMapPoint(kp.lmid_);
+            if (plm == nullptr) {
+                pmap_->removeMapPointObs(kp.lmid_, kfid);
+                continue;
+            }
+            const bool was3d = plm->is3d_;
+            if (plm->isBad()) {
+                if (was3d && !plm->is3d_) { last_filter_.unset3d.push_back(kp.lmid_); pmap_->touchMapPoint(kp.lmid_); }
+                continue;
+            }
+            size_t nbcokfs = plm->getKfObsSet().size();
+            if (nbcokfs > 4) nbgoodobs++;
+            nbtot++;
+        }
+        float ratio = (float)nbgoodobs / nbtot;   // 0 / 0: NaN, compares false
+        if (ratio > pslamstate_->fkf_filtering_ratio_) {
+            if ((s = pmap_->removeKeyframe(kfid)) != OV2_OK) return s;
+            last_filter_.removed.push_back(kfid);
+        }
+    }
+    return OV2_OK;
 }
 
 }  // namespace ov2

@@ -177,6 +177,9 @@ public:
     void updateMapPoint(int lmid, const Vec3 &wpt, double kfanch_invdepth = -1.);   // src/map_manager.cpp
     void removeMapPointObs(int lmid, int kfid);
     void removeMapPoint(int lmid);
+    // src/map_manager.cpp:885-919: every keypoint's map point loses the observer (MapPoint::removeKfObs), every covisible
+    // keyframe forgets it, the keyframe leaves map_pkfs_; with a device mirror attached, ov2_map_remove_keyframe
+    ov2_status removeKeyframe(int kfid);
     void removeObsFromCurFrameById(int lmid);
     void updateFrameCovisibility(Frame &frame);   // src/map_manager.cpp:117-192: co-observation counts + the frame's local map
     void mergeMapPoints(int prevlmid, int newlmid);   // :801-882
@@ -243,6 +246,10 @@ struct SlamParams {   // the subset of include/slam_params.hpp the path reads (Y
     // every keyframe with 2D keypoints.  The switch exists here, and is off by default, because loop tests recorded on loops
     // without the stage hold exact counts; see SlamManager::triangulateTemporal (ov2_slam.hpp).
     bool do_temporal_ = false;
+    // Estimator::mapFiltering (src/estimator.cpp:101-183, YAML key kf_filtering_ratio): keyframes whose 3D keypoints are, above
+    // this ratio, landmarks with more than 4 observers are culled.  1 = off (the reference's own gate, :103); every parameter
+    // file of the reference sets 0.9 or 0.95.
+    float fkf_filtering_ratio_ = 1.f;
 };
 
 struct Vec2 {
@@ -434,11 +441,22 @@ public:
     bool bstop_localba_ = false;
 };
 
-class Estimator {   // src/estimator.cpp:67-98
+struct FilterStats {   // Estimator::mapFiltering on the last keyframe
+    int ran = 0;                 // 0: one of the gates returned (ratio >= 1, kfid < 20)
+    int n_candidates = 0;        // covisible keyframes examined (existing, 0 < kfid < newkf)
+    int n_few3d = 0;             // ... removed by the nb3dkps_ < nmin_covscore / 2 rule
+    std::vector<int> removed;    // removed kfids in removal order (descending)
+    std::vector<int> unset3d;    // landmarks whose is3d_ MapPoint::isBad() cleared, in the order met
+};
+
+class Estimator {   // src/estimator.cpp:67-183
 public:
     Estimator(std::shared_ptr<SlamParams> pstate, std::shared_ptr<MapManager> pmap, std::shared_ptr<Optimizer> popt)
         : pslamstate_(pstate), pmap_(pmap), poptimizer_(popt) {}
     ov2_status applyLocalBA();
+    // :101-183 for the single-threaded loop (bnewkfavailable_ false, no loop closer: blc_is_on_ false, lckfid_ -1)
+    ov2_status mapFiltering();
+    FilterStats last_filter_;
     std::shared_ptr<Frame> pnewkf_;
     std::shared_ptr<SlamParams> pslamstate_;
     std::shared_ptr<MapManager> pmap_;

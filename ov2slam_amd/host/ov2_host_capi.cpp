@@ -165,6 +165,48 @@ int ov2h_triangulate_temporal(void *p, void *ctx, int kfid, float max_reproj_err
     return ts.n_kps;
 }
 
+// Estimator::mapFiltering on a host map with keyframe newkf as the new keyframe (no GPU context needed; with a device mirror
+// attached the removals reach it through MapManager::removeKeyframe).  removed_kfid (capacity cap): removed ids in order;
+// stats[4]: ran, candidates examined, removed by the nb3dkps_ rule, landmarks whose is3d_ isBad() cleared.  Returns the number
+// of keyframes removed, or -1 - status
+int ov2h_map_filtering(void *p, int newkf, int nmin_covscore, float ratio, int cap, int *removed_kfid, double *stats)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(newkf);
+    if (!f) return -1 - (int)OV2_ERR_INVALID;
+    m->st->nmin_covscore_ = nmin_covscore; m->st->fkf_filtering_ratio_ = ratio;
+    Estimator est(m->st, m->map, nullptr);
+    est.pnewkf_ = f;
+    const ov2_status s = est.mapFiltering();
+    if (s != OV2_OK) return -1 - (int)s;
+    const FilterStats &fs = est.last_filter_;
+    for (size_t i = 0; i < fs.removed.size() && (int)i < cap; ++i) removed_kfid[i] = fs.removed[i];
+    if (stats) { stats[0] = fs.ran; stats[1] = fs.n_candidates; stats[2] = fs.n_few3d; stats[3] = (double)fs.unset3d.size(); }
+    return (int)fs.removed.size();
+}
+
+// The bookkeeping of a host map that ov2h_map_export does not show, as flat lists (call with zero capacities for the sizes
+// n[3]): per landmark (lmid, MapPoint::kfid_, is3d_, isobs_), the observer sets as (lmid, kfid) pairs, and Frame::map_covkfs_
+// of every keyframe as (kfid, covisible kfid, count) triples
+int ov2h_map_export_graph(void *p, int cap_lm, int cap_obs, int cap_cov, int *n, int *lm, int *observers, int *cov)
+{
+    const MapManager &M = *((HostMap *)p)->map;
+    int nl = 0, no = 0, nc = 0;
+    for (const auto &kv : M.map_plms_) {
+        const MapPoint &q = *kv.second;
+        if (nl < cap_lm) { lm[4 * nl] = kv.first; lm[4 * nl + 1] = q.kfid_; lm[4 * nl + 2] = q.is3d_; lm[4 * nl + 3] = q.isobs_; }
+        ++nl;
+        for (int k : q.set_kfids_) { if (no < cap_obs) { observers[2 * no] = kv.first; observers[2 * no + 1] = k; } ++no; }
+    }
+    for (const auto &kv : M.map_pkfs_)
+        for (const auto &c : kv.second->map_covkfs_) {
+            if (nc < cap_cov) { cov[3 * nc] = kv.first; cov[3 * nc + 1] = c.first; cov[3 * nc + 2] = c.second; }
+            ++nc;
+        }
+    n[0] = nl; n[1] = no; n[2] = nc;
+    return 0;
+}
+
 // MapPoint::invdepth_ of a landmark (-1: never set, or no such landmark)
 double ov2h_landmark_invdepth(void *p, int lmid)
 {
@@ -873,6 +915,18 @@ void ov2h_slam_temporal_stats(void *p, double *out)
 }
 
 // out[3] of the last frame (keyframes only): keypoints described, local map points offered to matchToMap, merges
+// kf_filtering_ratio of the YAML (Estimator::mapFiltering after every local BA); 1 = off, the default
+void ov2h_slam_set_kf_filtering(void *p, float ratio) { ((SlamManager *)p)->pslamstate_->fkf_filtering_ratio_ = ratio; }
+
+// what Estimator::mapFiltering did on the last keyframe: ran, candidates, removed, removed by the nb3dkps_ rule, is3d_ cleared,
+// then up to 11 removed kfids in order (-1 beyond)
+void ov2h_slam_filter_stats(void *p, double *out)
+{
+    const FilterStats &f = ((SlamManager *)p)->pestimator_->last_filter_;
+    out[0] = f.ran; out[1] = f.n_candidates; out[2] = (double)f.removed.size(); out[3] = f.n_few3d; out[4] = (double)f.unset3d.size();
+    for (int i = 0; i < 11; ++i) out[5 + i] = i < (int)f.removed.size() ? f.removed[i] : -1;
+}
+
 void ov2h_slam_kf_stats(void *p, double *out)
 {
     const SlamStats &s = ((SlamManager *)p)->last_;

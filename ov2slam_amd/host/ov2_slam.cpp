@@ -391,11 +391,17 @@ ov2_status SlamManager::mapperRun(const Keyframe &kf)
     if (S.use_brief_ && kf.kfid_ > 0 && S.bdo_track_localmap_ && (s = matchingToLocalMap(*pnewkf)) != OV2_OK) return s;   // :153-162
     last_.n_lm3d = 0;
     for (const auto &kv : pmap_->map_plms_) last_.n_lm3d += kv.second->is3d_;
-    // Estimator::addNewKf -> applyLocalBA (src/estimator.cpp:67-98)
-    if (policy_.ba_window > 0) return fixedWindowBA();
+    // Estimator::addNewKf -> applyLocalBA(); mapFiltering(); (src/estimator.cpp:45-47, 67-183)
+    pestimator_->last_filter_ = FilterStats();
+    if (policy_.ba_window > 0) {
+        if ((s = fixedWindowBA()) != OV2_OK) return s;
+        pestimator_->pnewkf_ = pnewkf;
+        return pestimator_->mapFiltering();
+    }
     if (pmap_->dev_ && (s = pmap_->addKeyframeToDevice(*pnewkf)) != OV2_OK) return s;   // the mirror learns the keyframe with its stereo observations
     pestimator_->pnewkf_ = pnewkf;
     s = pestimator_->applyLocalBA();
+    if (s == OV2_OK) s = pestimator_->mapFiltering();
     const ov2_ba_result &r = poptimizer_->last_result_;
     if (s == OV2_OK && r.n_log > 0) {
         last_.ba_done = 1; last_.ba_it_robust = r.n_log_robust - 1; last_.ba_it_l2 = r.l2_done ? r.n_log - r.n_log_robust - 1 : 0;

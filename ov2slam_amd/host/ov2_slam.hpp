@@ -62,6 +62,7 @@ public:
     SlamManager(ov2_ctx *ctx, std::shared_ptr<SlamParams> pstate, std::shared_ptr<CameraCalibration> cl,
                 std::shared_ptr<CameraCalibration> cr, const LoopPolicy &policy);
     // one stereo frame through visualTracking and, when it asks for a keyframe, Mapper::run + Estimator::applyLocalBA
+    // followed by Estimator::mapFiltering (src/estimator.cpp:45-47; off while SlamParams::fkf_filtering_ratio_ is 1)
     ov2_status addNewStereoImages(double time, const uint8_t *im0, const uint8_t *im1, int w, int h, int stride);
     SE3 pose() const { return pcurframe_->getTwc(); }
     // the 256 test pairs of BRIEF-32 (y1, x1, y2, x2 per test, int8: opencv_contrib's generated_32.i, absent from the reference

@@ -84,6 +84,12 @@ def lib():
         L.ov2h_map_forget_keyframe.argtypes = [C.c_void_p, C.c_int]
         L.ov2h_map_forget_kp.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ov2h_triangulate_temporal.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, ip, ip, dp]
+        L.ov2h_map_filtering.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, ip, dp]
+        L.ov2h_map_export_graph.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]
+        L.ov2h_slam_set_kf_filtering.argtypes = [C.c_void_p, C.c_float]
+        L.ov2h_slam_set_kf_filtering.restype = None
+        L.ov2h_slam_filter_stats.argtypes = [C.c_void_p, dp]
+        L.ov2h_slam_filter_stats.restype = None
         L.ov2h_landmark_invdepth.argtypes = [C.c_void_p, C.c_int]
         L.ov2h_landmark_invdepth.restype = C.c_double
         L.ov2h_set_p3p.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_ulonglong]
@@ -383,6 +389,36 @@ class HostMap:
         obs = {(int(k), int(l)): 2 * int(s) for k, l, s in zip(ok, ol, os_)}
         return kfs, lms, obs
 
+    def map_filtering(self, newkf=None, nmin_covscore=25, ratio=0.9, cap=4096):
+        """Estimator::mapFiltering (src/estimator.cpp:101-183) with keyframe newkf as the new keyframe, on the host objects (no
+        GPU context; an attached device mirror follows through MapManager::removeKeyframe).  Returns (removed kfids in removal
+        order, dict(ran, candidates, few3d, unset3d))"""
+        rm, st = np.zeros(cap, np.int32), np.zeros(4)
+        n = lib().ov2h_map_filtering(self.h, int(self.newkf if newkf is None else newkf), int(nmin_covscore), float(ratio), cap,
+                                     rm.ctypes.data_as(C.POINTER(C.c_int)), _dp(st))
+        if n < 0:
+            raise RuntimeError(f"mapFiltering: status {-1 - n}")
+        return rm[:n].tolist(), dict(ran=int(st[0]), candidates=int(st[1]), few3d=int(st[2]), unset3d=int(st[3]))
+
+    def export_graph(self):
+        """the bookkeeping export() does not show: ({lmid: dict(kfid (anchor), is3d, isobs, observers: frozenset)},
+        {kfid: {covisible kfid: count}} = Frame::map_covkfs_ of every keyframe)"""
+        L, ip = lib(), C.POINTER(C.c_int)
+        n = np.zeros(3, np.int32)
+        L.ov2h_map_export_graph(self.h, 0, 0, 0, n.ctypes.data_as(ip), None, None, None)
+        nl, no, nc = (int(v) for v in n)
+        lm, ob, cv = np.zeros((nl, 4), np.int32), np.zeros((no, 2), np.int32), np.zeros((nc, 3), np.int32)
+        L.ov2h_map_export_graph(self.h, nl, no, nc, n.ctypes.data_as(ip), lm.ctypes.data_as(ip), ob.ctypes.data_as(ip), cv.ctypes.data_as(ip))
+        sets = {}
+        for l, k in ob.tolist():
+            sets.setdefault(l, set()).add(k)
+        lms = {int(l): dict(kfid=int(a), is3d=bool(t), isobs=bool(o), observers=frozenset(sets.get(int(l), ()))) for l, a, t, o in lm.tolist()}
+        kfs, _, _ = self.export()
+        cov = {k: {} for k in kfs}
+        for k, c, v in cv.tolist():
+            cov[k][c] = v
+        return lms, cov
+
     def apply_local_ba(self, ctx):
         """Estimator::applyLocalBA on the GPU. returns (status, outliers pass1, pass2, final cost)."""
         n1, n2, fc = C.c_int(), C.c_int(), C.c_double()
@@ -515,6 +551,11 @@ class CppSlam:
             lib().ov2h_slam_temporal_stats(self.h_, _dp(e))
             self.temporal_stats.append(dict(frame=int(self.stats[-1]["frame"]), ran=int(e[0]), kps2d=int(e[1]), candidates=int(e[2]),
                                             good=int(e[3]), removed=int(e[4])))
+        if getattr(self, "filter_stats", None) is not None and self.stats[-1]["kf"]:
+            e = np.zeros(16)
+            lib().ov2h_slam_filter_stats(self.h_, _dp(e))
+            self.filter_stats.append(dict(frame=int(self.stats[-1]["frame"]), ran=int(e[0]), candidates=int(e[1]), n_removed=int(e[2]),
+                                          few3d=int(e[3]), unset3d=int(e[4]), removed=[int(k) for k in e[5:16] if k >= 0]))
         if getattr(self, "kf_stats", None) is not None and self.stats[-1]["kf"]:
             k = np.zeros(3)
             lib().ov2h_slam_kf_stats(self.h_, _dp(k))
@@ -542,6 +583,13 @@ class CppSlam:
         (also useful with dop3p off: the branch runs whenever bp3preq_ is set)."""
         lib().ov2h_slam_set_p3p(self.h_, int(bool(dop3p)))
         self.p3p_stats = []
+
+    def set_kf_filtering(self, ratio=0.9):
+        """kf_filtering_ratio of the YAML: Estimator::mapFiltering (src/estimator.cpp:101-183) culls redundant keyframes after
+        every local BA.  1 is the reference's own 'off' and the default here; its parameter files set 0.9 or 0.95.  Starts the
+        per-keyframe filter_stats list."""
+        lib().ov2h_slam_set_kf_filtering(self.h_, float(ratio))
+        self.filter_stats = []
 
     def set_temporal(self, on=True):
         """Mapper::triangulateTemporal in Mapper::run (src/mapper.cpp:107-126): the new keyframe's 2D keypoints are triangulated
@@ -809,6 +857,19 @@ class TemporalMap(HostMap):
 
     def invdepth(self, lmid):
         return float(lib().ov2h_landmark_invdepth(self.h, int(lmid)))
+
+
+class FilterMap(TemporalMap):
+    """the C++ host map of a synth_filter.make_map dict -- keyframes, 2D / 3D keypoints, map points with their is3d_ / isobs_
+    flags, covisibility counted by MapManager::updateFrameCovisibility -- to run Estimator::mapFiltering (map_filtering) on.
+    Needs no GPU context unless a device mirror is attached."""
+
+    def __init__(self, m):
+        TemporalMap.__init__(self, dict(m, forget_kp=(), forget_lm=(), forget_kf=()))
+        L = lib()
+        for l in np.intersect1d(np.flatnonzero(m["lm_isobs"] == 0), m["obs_lm"]):   # map points are created observed
+            assert L.ov2h_map_set_isobs(self.h, int(l), 0) == 0
+        assert L.ov2h_map_finalize(self.h, self.newkf) == 0
 
 
 class FrontEndFrame:
