@@ -330,9 +330,7 @@ __device__ inline double block_sum_256(double v, double *sh)
 // The solver's kernels are few, short waves that share their CUs with the front-end's long
 // KLT waves: raising the wave priority lets them win the SIMD issue arbitration instead of taking turns
 // (s_setprio is per wave and costs one scalar instruction; measured: 467 -> 475 LM it/s concurrent, front-end unchanged).
-#ifndef BA_WAVE_PRIO
 #define BA_WAVE_PRIO() __builtin_amdgcn_s_setprio(3)
-#endif
 
 // window that owns virtual block b: the last w with vb_start[w] <= b (windows without rows own no block)
 __device__ __forceinline__ int win_of_vblock(const int *__restrict__ vb_start, int B, int b)
@@ -826,11 +824,9 @@ __device__ __forceinline__ double grp_sum(double v)
     return v;
 }
 
-#ifndef BS_LM_GW
 #define BS_LM_GW 8   // lanes per landmark in the landmark-major kernels (column norms, elimination, back-substitution): 12 rows / 7
                      // cells per landmark are typical (six stereo observers + the anchor); with 16 lanes a wave carried four landmarks
                      // and ~6 KB of traffic through its ~10 us of dependent loads (bs_landmark 311 -> 248 us with 8)
-#endif
 #define BS_LM_PER_WG (256 / BS_LM_GW)
 
 // column norms + gradient of the landmark (E) columns: GW lanes per landmark, no atomics
@@ -994,194 +990,18 @@ __global__ __launch_bounds__(256) void ba_backsub16_kernel(ba_dev d, double *__r
 }
 
 // ------------------------------------------------------------------------------------------------------
-// K_CHOL: dense Cholesky of the reduced camera system by one workgroup (schur_complement_solver.cc:217-229 does an
-// Eigen LLT; :319-355 a sparse one -- same factor).  Column-major, lower triangle.  Left-looking, panels of NB
-// columns held in LDS; the right-hand side rides along as row m, so the forward substitution is free; the backward
-// substitution is done panel by panel afterwards.  z (solution) overwrites rhs.
-
-// 512 threads: 256 VGPRs per lane, so the register-blocked phases need no scratch (with 1024 threads / 128 VGPRs the
-// kernel spilled ~100 registers, and every dispatch that needs scratch stalled for milliseconds in the runtime's
-// queue-scratch management -- measured: 12-30 ms per minimize() instead of 3)
-#define CHOL_THREADS 512
-template <int NB>
-__global__ __launch_bounds__(CHOL_THREADS) void ba_chol_kernel(ba_dev d)
-{
-    BA_WAVE_PRIO();
-    extern __shared__ __attribute__((aligned(16))) double lds[];   // the only LDS object of this kernel
-    ba_win &W = d.W[blockIdx.x];                                   // one workgroup per window
-    if (!W.active || W.m == 0) return;
-    double *__restrict__ A = d.Spool + W.S_off;
-    double *__restrict__ rhs = d.rhs + (size_t)W.f0 * 6;
-    const int m = W.m;
-    const int tid = threadIdx.x, nth = blockDim.x;
-    const int M1 = m + 1;               // augmented row count (row m = right-hand side)
-    constexpr int PS = NB + 1;          // panel row stride (bank spread)
-    constexpr int KC = 64, HALF = NB / 2;
-    double *P = lds;                    // panel: rows x NB
-    double *Lj = lds + (((size_t)M1 * PS + 1) & ~(size_t)1); // 16-B aligned; KC x NB chunk of the previous columns of rows j0..j0+nb  ([kk][c])
-    volatile int *failp = reinterpret_cast<volatile int *>(Lj + NB * KC);
-    if (tid == 0) *failp = 0;
-    __syncthreads();
-    for (int j0 = 0; j0 < m; j0 += NB) {
-        const int nb = min(NB, m - j0);
-        const int rows = M1 - j0;       // panel rows j0 .. m
-        for (int idx = tid; idx < rows * nb; idx += nth) {
-            const int c = idx / rows, i = idx - c * rows;
-            const int gi = j0 + i;
-            P[i * PS + c] = (gi < m) ? A[(size_t)(j0 + c) * m + gi] : rhs[j0 + c];
-        }
-        __syncthreads();
-        // P -= L[j0.., 0..j0) * L[j0..j0+nb, 0..j0)^T ; thread = (row, half of the panel columns)
-        const int groups = (rows * 2 <= nth) ? 2 : 1;
-        for (int k0 = 0; k0 < j0; k0 += KC) {
-            const int kc = min(KC, j0 - k0);
-            for (int idx = tid; idx < NB * KC; idx += nth) {
-                const int kk = idx / NB, c = idx - kk * NB;
-                Lj[idx] = (kk < kc && c < nb) ? A[(size_t)(k0 + kk) * m + j0 + c] : 0.0;
-            }
-            __syncthreads();
-            for (int w = tid; w < rows * groups; w += nth) {
-                const int i = w % rows, g = w / rows;
-                const int gi = j0 + i;
-                for (int h = g; h < 2; h += groups) {
-                    const int c0 = h * HALF;
-                    double acc[HALF];
-#pragma unroll
-                    for (int c = 0; c < HALF; ++c) acc[c] = 0.0;
-                    // row m (rhs) of previous columns lives in rhs[] after their panel was written back
-                    const double *src = (gi < m) ? (A + (size_t)k0 * m + gi) : (rhs + k0);
-                    const size_t sstep = (gi < m) ? (size_t)m : 1;
-                    // register double buffer of UB L[i][k] values: the next batch is in flight while this one is used
-                    // (sized for the 256-VGPR budget of a 512-thread workgroup: a dispatch that needs
-                    // scratch costs milliseconds of queue-scratch management on this runtime, see CHOL_THREADS)
-                    constexpr int UB = 16;
-                    double cur[UB], nxt[UB];
-#pragma unroll
-                    for (int u = 0; u < UB; ++u) cur[u] = (u < kc) ? src[(size_t)u * sstep] : 0.0;
-                    for (int kk0 = 0; kk0 < kc; kk0 += UB) {
-#pragma unroll
-                        for (int u = 0; u < UB; ++u) nxt[u] = (kk0 + UB + u < kc) ? src[(size_t)(kk0 + UB + u) * sstep] : 0.0;
-#pragma unroll
-                        for (int u = 0; u < UB; ++u) {
-#pragma unroll
-                            for (int c = 0; c < HALF; ++c) acc[c] += cur[u] * Lj[(kk0 + u) * NB + c0 + c];
-                        }
-#pragma unroll
-                        for (int u = 0; u < UB; ++u) cur[u] = nxt[u];
-                    }
-#pragma unroll
-                    for (int c = 0; c < HALF; ++c)
-                        if (c0 + c < nb) P[i * PS + c0 + c] -= acc[c];
-                }
-            }
-            __syncthreads();
-        }
-        // (a) the nb x nb diagonal block: ONE wave, lane i keeps row i in registers, pivots travel by v_readlane
-        if (tid < 64) {
-            double row[NB];
-#pragma unroll
-            for (int c = 0; c < NB; ++c) row[c] = (tid < nb && c < nb) ? P[tid * PS + c] : ((tid == c) ? 1.0 : 0.0);
-            int bad = 0;
-#pragma unroll
-            for (int c = 0; c < NB; ++c) {
-                const double dcc = readlane_f64(row[c], c);
-                if (c < nb && !(dcc > 0.0)) bad = 1;
-                const double dsq = sqrt(dcc > 0.0 ? dcc : 1.0);
-                row[c] = (tid == c) ? dsq : row[c] / dsq;
-#pragma unroll
-                for (int c2 = c + 1; c2 < NB; ++c2) {
-                    const double l = readlane_f64(row[c], c2);
-                    row[c2] -= row[c] * l;      // rows above the diagonal collect garbage that is never read
-                }
-            }
-            if (tid < nb) {
-#pragma unroll
-                for (int c = 0; c < NB; ++c)
-                    if (c <= tid && c < nb) P[tid * PS + c] = row[c];
-            }
-            if (bad && tid == 0) *failp = 1;
-        }
-        __syncthreads();
-        if (*failp) break;
-        // (b) rows below the block (and the rhs row): x L_D^T = P[i,:], forward substitution, one thread per row
-        for (int i = nb + tid; i < rows; i += nth) {
-            double x[NB];
-#pragma unroll
-            for (int c = 0; c < NB; ++c) x[c] = (c < nb) ? P[i * PS + c] : 0.0;
-#pragma unroll
-            for (int c = 0; c < NB; ++c) {
-                if (c < nb) {
-                    double v = x[c];
-#pragma unroll
-                    for (int k = 0; k < c; ++k) v -= x[k] * P[c * PS + k];
-                    x[c] = v / P[c * PS + c];
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < NB; ++c)
-                if (c < nb) P[i * PS + c] = x[c];
-        }
-        __syncthreads();
-        for (int idx = tid; idx < rows * nb; idx += nth) {
-            const int c = idx / rows, i = idx - c * rows;
-            const int gi = j0 + i;
-            if (gi < m) { if (i >= c) A[(size_t)(j0 + c) * m + gi] = P[i * PS + c]; }
-            else rhs[j0 + c] = P[i * PS + c];   // y = L^-1 b rides along as row m
-        }
-        __syncthreads();
-    }
-    if (*failp) {
-        if (tid == 0) W.chol_fail = 1;
-        return;
-    }
-    __threadfence_block();
-    __syncthreads();
-    // backward substitution L^T z = y, panel by panel from the bottom: (1) every wave takes panel columns and forms
-    // t_c = sum_{i below the panel} L[i][c] z[i] with coalesced column reads, (2) wave 0 solves the nb x nb triangle
-    // with the block's columns in registers (pivots by v_readlane).  z lives in LDS.
-    {
-        double *zb = lds, *tpart = lds + m;
-        const int lane = tid & 63, wave = tid >> 6, nwaves = nth >> 6;
-        for (int i = tid; i < m; i += nth) zb[i] = rhs[i];
-        __syncthreads();
-        for (int j0 = ((m - 1) / NB) * NB; j0 >= 0; j0 -= NB) {
-            const int nb = min(NB, m - j0);
-            for (int c = wave; c < nb; c += nwaves) {
-                double sacc = 0.0;
-                for (int i = j0 + nb + lane; i < m; i += 64) sacc += A[(size_t)(j0 + c) * m + i] * zb[i];
-                for (int o = 32; o > 0; o >>= 1) sacc += __shfl_xor(sacc, o);
-                if (lane == 0) tpart[c] = sacc;
-            }
-            __syncthreads();
-            if (tid < 64) {
-                double y = (lane < nb) ? zb[j0 + lane] - tpart[lane] : 0.0;
-                double colD[NB];   // lane i: colD[j] = L[j0+j][j0+i], j >= i
-#pragma unroll
-                for (int j = 0; j < NB; ++j)
-                    colD[j] = (lane < nb && j < nb && j >= lane) ? A[(size_t)(j0 + lane) * m + j0 + j] : ((j == lane) ? 1.0 : 0.0);
-#pragma unroll
-                for (int j = NB - 1; j >= 0; --j) {
-                    const double zj = readlane_f64(y, j) / readlane_f64(colD[j], j);
-                    if (lane == j) y = zj;
-                    else if (lane < j) y -= colD[j] * zj;
-                }
-                if (lane < nb) zb[j0 + lane] = y;
-            }
-            __syncthreads();
-        }
-        for (int i = tid; i < m; i += nth) rhs[i] = zb[i];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// K_CHOL, one workgroup per window with the panel update on the matrix cores.  Same left-looking blocked factorisation
-// as ba_chol_kernel (32-column panel in LDS, right-hand side as row m, diagonal block by one wave, rows below by
-// forward substitution, blocked backward substitution) -- what changes is the O(m^3) part: the update of a panel with
-// the columns before it, P -= L[j0.., 0..j0) L[j0..j0+32, 0..j0)^T, is a GEMM, and ba_chol_kernel spent it one LDS read
-// per fused multiply-add (every thread a row, 16 columns each).  Here every wave takes 16-row tiles of the panel (both
-// 16-column halves at once, sharing the row operand) and walks k in steps of four with v_mfma_f64_16x16x4_f64, both
-// operands straight from the factor in L2 (for a fixed k, 16 consecutive rows are 128 contiguous bytes): no LDS traffic
-// and no barrier inside the update.
+// K_CHOL for m < CHOL_MULTI_MIN: dense Cholesky of the reduced camera system, one workgroup per window
+// (schur_complement_solver.cc:217-229 does an Eigen LLT; :319-355 a sparse one -- same factor).  Column-major, lower
+// triangle.  Left-looking, panels of 32 columns held in LDS (row stride 33: bank spread); the right-hand side rides along
+// as row m, so the forward substitution is free.  Per panel: the update with the columns before it, then the 32 x 32
+// diagonal block by one wave, then the rows below it by forward substitution, one thread per row, then the write-back.
+// The backward substitution L^T z = y is done panel by panel afterwards; z (solution) overwrites rhs.
+// The O(m^3) part runs on the matrix cores: the update of a panel with the columns before it,
+// P -= L[j0.., 0..j0) L[j0..j0+32, 0..j0)^T, is a GEMM.  Every wave takes 16-row tiles of the panel (both 16-column
+// halves at once, sharing the row operand) and walks k in steps of four with v_mfma_f64_16x16x4_f64, both operands
+// straight from the factor in L2 (for a fixed k, 16 consecutive rows are 128 contiguous bytes): no LDS traffic and no
+// barrier inside the update.  (A form without the matrix cores, every thread a row and 16 columns of the panel, spent
+// one LDS read per fused multiply-add there: 690 us per LM round at m = 354 against 422.)
 typedef double ov2_v4f64 __attribute__((ext_vector_type(4)));
 // 1 / d by v_rcp_f64 + two Newton steps (within an ulp of the correctly rounded quotient): an IEEE f64 division is a ~35
 // instruction sequence here, and the substitution loops of the factorisation made one per row and column
@@ -1192,13 +1012,6 @@ __device__ __forceinline__ double chol_rcp(double d)
     x = __builtin_fma(__builtin_fma(-d, x, 1.0), x, x);
     return x;
 }
-
-#ifdef OV2_CHOL_PROF
-__device__ unsigned long long g_chol_prof[8];   // phase clocks (100 MHz ticks) of workgroup 0: update, diagonal, substitution, write-back, backward
-#define CHOL_TICK(slot) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long t_ = wall_clock64(); g_chol_prof[slot] += t_ - t_prev; t_prev = t_; } } while (0)
-#else
-#define CHOL_TICK(slot) do { } while (0)
-#endif
 
 // sqrt(d) and 1 / sqrt(d) for a pivot (d > 0, far from the ends of the exponent range: a sum of squared jacobian entries plus
 // the LM diagonal): v_rsq_f64 + two Newton steps for the reciprocal root, the root as d * that with one correction.  The
@@ -1216,15 +1029,14 @@ __device__ __forceinline__ void chol_sqrt_rcp(double d, double &root, double &in
     inv = __builtin_fma(__builtin_fma(-r, y, 1.0), y, y);   // 1 / root (y is 1 / sqrt(d); one step onto the rounded root)
 }
 
-#ifndef CHOL_TRIP
 #define CHOL_TRIP 8   // k-steps per trip of the panel update (4 columns each): 32 = the panel width divides every j0
-#endif
+// 512 threads: 256 VGPRs per lane, so the register-blocked phases need no scratch (with 1024 threads / 128 VGPRs the
+// kernel spilled ~100 registers, and every dispatch that needs scratch stalled for milliseconds in the runtime's
+// queue-scratch management -- measured: 12-30 ms per minimize() instead of 3)
+#define CHOL_THREADS 512
 __global__ __launch_bounds__(CHOL_THREADS) void ba_chol_mfma_kernel(ba_dev d)
 {
     BA_WAVE_PRIO();
-#ifdef OV2_CHOL_PROF
-    unsigned long long t_prev = wall_clock64();
-#endif
     constexpr int NB = 32, PS = NB + 1;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     ba_win &W = d.W[blockIdx.x];
@@ -1287,7 +1099,6 @@ __global__ __launch_bounds__(CHOL_THREADS) void ba_chol_mfma_kernel(ba_dev d)
             }
         }
         __syncthreads();
-        CHOL_TICK(0);
         // (a) the nb x nb diagonal block: ONE wave, lane i keeps row i in registers, pivots travel by v_readlane
         if (tid < 64) {
             double row[NB];
@@ -1318,7 +1129,6 @@ __global__ __launch_bounds__(CHOL_THREADS) void ba_chol_mfma_kernel(ba_dev d)
             if (bad && tid == 0) *failp = 1;
         }
         __syncthreads();
-        CHOL_TICK(1);
         if (*failp) break;
         // (b) rows below the block (and the rhs row): x L_D^T = P[i,:], forward substitution, one thread per row
         for (int i = nb + tid; i < rows; i += nth) {
@@ -1345,7 +1155,6 @@ __global__ __launch_bounds__(CHOL_THREADS) void ba_chol_mfma_kernel(ba_dev d)
                 if (c < nb) P[i * PS + c] = x[c];
         }
         __syncthreads();
-        CHOL_TICK(2);
         for (int c = wave; c < nb; c += nwaves) {   // a column per wave: consecutive lanes, consecutive rows
             double *__restrict__ colA = A + (size_t)(j0 + c) * m + j0;
             for (int i = c + lane; i < rows; i += 64) {
@@ -1355,7 +1164,6 @@ __global__ __launch_bounds__(CHOL_THREADS) void ba_chol_mfma_kernel(ba_dev d)
         }
         __threadfence_block();
         __syncthreads();
-        CHOL_TICK(3);
     }
     if (*failp) {
         if (tid == 0) W.chol_fail = 1;
@@ -1363,7 +1171,9 @@ __global__ __launch_bounds__(CHOL_THREADS) void ba_chol_mfma_kernel(ba_dev d)
     }
     __threadfence_block();
     __syncthreads();
-    // backward substitution L^T z = y, as in ba_chol_kernel
+    // backward substitution L^T z = y, panel by panel from the bottom: (1) every wave takes panel columns and forms
+    // t_c = sum_{i below the panel} L[i][c] z[i] with coalesced column reads, (2) wave 0 solves the nb x nb triangle
+    // with the block's columns in registers (pivots by v_readlane).  z lives in LDS.
     {
         double *zb = lds, *tpart = lds + m;
         for (int i = tid; i < m; i += nth) zb[i] = rhs[i];
@@ -1396,7 +1206,6 @@ __global__ __launch_bounds__(CHOL_THREADS) void ba_chol_mfma_kernel(ba_dev d)
         }
         for (int i = tid; i < m; i += nth) rhs[i] = zb[i];
     }
-    CHOL_TICK(4);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1413,8 +1222,12 @@ __global__ __launch_bounds__(CHOL_THREADS) void ba_chol_mfma_kernel(ba_dev d)
                              // m = 250 the 16 launches win 6 % on an idle GPU (3.28 -> 3.08 ms) but lose 9 % beside a busy
                              // front-end (332 vs 363 LM iterations/s: every dispatch queues), so the single launch stays there.
                              // Round 3, batches of 64 distinct windows with the one-workgroup kernel's panel update on the
-                             // matrix cores (ba_chol_mfma_kernel): m <= 354: 24.4 ms per batch against 25.5 (this path) and 26.2
-                             // (ba_chol_kernel); m ~ 440 (75 keyframes): 17.1 against 16.0 -- the crossover sits near 400
+                             // matrix cores (ba_chol_mfma_kernel): m <= 354: 24.4 ms per batch against 25.5 (this path);
+                             // m ~ 440 (75 keyframes): 17.1 against 16.0 -- the crossover sits near 400
+// dynamic LDS of ba_chol_mfma_kernel: the panel (m + 1 rows of 33 doubles), the panel's 32 reciprocal pivots, the failure flag
+constexpr size_t chol_mfma_lds(int m) { return ((size_t)(m + 1) * 33 + 32 + 8) * 8; }
+static_assert(chol_mfma_lds(CHOL_MULTI_MIN - 1) <= 158 * 1024,
+              "every m below CHOL_MULTI_MIN must fit the one-workgroup kernel's panel into the 160 KiB of LDS (105 920 B at 399)");
 
 __global__ __launch_bounds__(64) void ba_chol_panel_kernel(ba_dev d, double *__restrict__ Dpool, size_t dstride, int k0)
 {
@@ -2387,7 +2200,7 @@ __device__ __forceinline__ void bs_diag_block(const ba_dev &d, const ba_cells &C
 template <int E>
 __device__ __forceinline__ void bs_pair_block(const ba_dev &d, const ba_cells &C, int n_pairs,
                                               const u64 *__restrict__ pair_key, const int *__restrict__ seg_start,
-                                              const int2 *__restrict__ pent, int fb, int pidx, int dbg = 0)
+                                              const int2 *__restrict__ pent, int fb, int pidx)
 {
     const int lane = threadIdx.x & 63;
     if (pidx >= n_pairs) return;
@@ -2430,7 +2243,7 @@ __device__ __forceinline__ void bs_pair_block(const ba_dev &d, const ba_cells &C
             // observes, element (i of hi, j of lo) is -((U s_hi)_i (U s_lo)_j) summed over the two residual components.
             // Formed here from the one or two 48-byte rows of the run, lane-parallel like the rest of the entry (nothing
             // materialised per cell: the 288-byte F'Fa records were the largest store of the whole Schur complement).
-            if (!(dbg & 4) && (eh < 0 || el < 0)) {
+            if (eh < 0 || el < 0) {
                 const int4 rr = C.qrow[el < 0 ? qh : ql];
                 double wp[3];   // the rows of a cell belong to one landmark
                 load_wpt(d, (size_t)rr.z, wp);
@@ -2454,15 +2267,13 @@ __device__ __forceinline__ void bs_pair_block(const ba_dev &d, const ba_cells &C
     // off-diagonal block has this wave as its only writer and was zeroed by ba_sinit: plain stores (a serial
     // read-modify-write of 36 elements by one lane made these short waves latency-bound)
     double mine = 0.0;
-    if (dbg & 8) {
-#pragma unroll
-        for (int t = 0; t < 36; ++t) mine += acc[t];
-    } else {
 #pragma unroll
     for (int t = 0; t < 36; ++t) {
-        const double v = wave_total(acc[t]);
+        double v = wave_total(acc[t]);
+        // every total lands in a VGPR before the next one is read: left free, the scheduler issues the lane reads of many
+        // totals ahead of their sums (8 SGPRs each), 202 SGPRs spill into VGPR lanes and E = 1 drops from 3 to 2 waves per SIMD
+        asm volatile("" : "+v"(v));
         if (lane == t) mine = v;
-    }
     }
     if (lane < 36) {
         const int i = lane % 6, j = lane / 6;
@@ -2478,12 +2289,10 @@ __device__ __forceinline__ void bs_pair_block(const ba_dev &d, const ba_cells &C
 template <int E>
 __global__ __launch_bounds__(256) void bs_gather_kernel(ba_dev d, ba_cells C, const int *__restrict__ pcell_ptr,
                                                         const int *__restrict__ n_pairs, const u64 *__restrict__ pair_key,
-                                                        const int *__restrict__ seg_start, const int2 *__restrict__ pent, int fb,
-                                                        int dbg_only)
+                                                        const int *__restrict__ seg_start, const int2 *__restrict__ pent, int fb)
 {
     BA_WAVE_PRIO();
     __shared__ double red[4][27];
-    if ((dbg_only & 3) && (((dbg_only & 3) == 1) != ((int)blockIdx.x < d.n_f))) return;   // timing experiments: 1 = diagonal part only, 2 = pairs only
     if ((int)blockIdx.x < d.n_f) bs_diag_block<E>(d, C, pcell_ptr, blockIdx.x, red);
     else {
         // Consecutive pairs share their `hi` pose, i.e. they re-read the same run of cell records; workgroups are dealt
@@ -2493,22 +2302,12 @@ __global__ __launch_bounds__(256) void bs_gather_kernel(ba_dev d, ba_cells C, co
         const int npb = (((np + 3) >> 2) + 7) & ~7;   // pair blocks that have work (the grid is sized for an upper bound), a multiple of 8
         if (pb >= npb) return;
         const int blk = (pb & 7) * (npb >> 3) + (pb >> 3);
-        bs_pair_block<E>(d, C, np, pair_key, seg_start, pent, fb, blk * 4 + (int)(threadIdx.x >> 6), dbg_only);
+        bs_pair_block<E>(d, C, np, pair_key, seg_start, pent, fb, blk * 4 + (int)(threadIdx.x >> 6));
     }
 }
 
 // ------------------------------------------------------------------------------------------------------
 // host side
-
-struct dev_buf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
-struct ba_workspace {
-    std::vector<dev_buf> bufs;
-    size_t next = 0;
-};
 
 // device memory of a solve is carved from one arena owned by the ctx and kept across solves (no hipMalloc/hipFree on
 // the keyframe path); ov2_ba_solve sizes it from an upper bound before the first carve.
@@ -2531,17 +2330,6 @@ ov2_status dalloc2(ov2_ctx *c, size_t &off, T **out, size_t n)
         return ov2_set_err(c, OV2_ERR_NOMEM, "BA structure arena exhausted (%zu + %zu > %zu)", off, bytes, c->ba_arena2_cap);
     *out = (T *)((char *)c->ba_arena2 + off);
     off += bytes;
-    return OV2_OK;
-}
-
-template <typename T>
-ov2_status dupload(ov2_ctx *c, size_t &off, const T **out, const std::vector<T> &v)
-{
-    T *p = nullptr;
-    ov2_status s = dalloc(c, off, &p, v.size());
-    if (s != OV2_OK) return s;
-    if (!v.empty()) OV2_HIP(c, hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    *out = p;
     return OV2_OK;
 }
 
@@ -2576,11 +2364,11 @@ struct ba_solver {
     const int *rows = nullptr;   // device: sorted row -> batch-wide residual index
     // atomic-free Schur complement: cells, pose -> cells, pose pairs -> (cell, cell) entries (see the bs_* kernels)
     ba_cells cells;
-    const int *pcell_ptr = nullptr, *pcell_ent = nullptr;
+    const int *pcell_ptr = nullptr;
     const int *n_pairs = nullptr, *seg_start = nullptr;
-    const u64 *pair_key = nullptr, *pair_val = nullptr;   // pair_val: the sorted (pose pair | entry) keys
+    const u64 *pair_key = nullptr;
     const int2 *pair_ent = nullptr;                       // sorted entry -> its two cells (pose-major positions, bit 31 = anchor cell)
-    int fb = 1, pb = 1;                                   // bit widths of a pose block id / of a pair entry index in the packed keys
+    int fb = 1;                                           // bit width of a pose block id in the packed pair keys
     long long pair_cap = 0;
     double *xp = nullptr, *xl = nullptr, *cp = nullptr, *cl = nullptr;  // device states (batch-wide)
     double *chold = nullptr;      // diagonal blocks of the Cholesky factors (multi-workgroup path), one slab per window
@@ -2893,7 +2681,7 @@ ov2_status build_program(ba_solver &S)
         ba_cells &Cc = S.cells;
         const long long pair_cap = std::min<long long>((long long)P_tot, pair_cap_bound);
         const int fb = bits_for((size_t)d.n_f), pb = bits_for((size_t)P_tot);   // pair keys: [pose hi : fb] [pose lo : fb] [entry : pb]
-        S.fb = fb; S.pb = pb;
+        S.fb = fb;
         if (2 * fb + pb > 64)
             return ov2_set_err(c, OV2_ERR_UNSUPPORTED, "batch too large for the packed pair keys (%d free poses, %d cell pairs): split it",
                                d.n_f, P_tot);
@@ -2946,8 +2734,8 @@ ov2_status build_program(ba_solver &S)
             OV2_HIP(c, hipcub::DeviceScan::ExclusiveSum(tsort, tbytes, head, rank, P_tot + 1, st));
             BA_LAUNCH(S, K_MISC, bs_segs_kernel, dim3((P_tot + 255) / 256), dim3(256), 0, st, pkey2, P_tot, head, rank, seg_start, ukey, pb);
         }
-        S.pcell_ptr = pcell_ptr; S.pcell_ent = pcell_ent; S.n_pairs = rank + P_tot;   // exclusive rank behind the last entry = number of pose pairs
-        S.seg_start = seg_start; S.pair_key = ukey; S.pair_val = pkey2; S.pair_ent = pent_sorted; S.pair_cap = P_tot > 0 ? pair_cap : 0;
+        S.pcell_ptr = pcell_ptr; S.n_pairs = rank + P_tot;   // exclusive rank behind the last entry = number of pose pairs
+        S.seg_start = seg_start; S.pair_key = ukey; S.pair_ent = pent_sorted; S.pair_cap = P_tot > 0 ? pair_cap : 0;
     }
     return OV2_OK;
 }
@@ -3031,8 +2819,6 @@ ov2_status enqueue_minimize(ba_solver &S, int max_rounds)
     }
     BA_LAUNCH(S, K_REDUCE, ba_winreduce_kernel<WR_JAC>, g_win, dim3(256), 0, st, d, lo, S.xp, part_cost, part_step, part_norm, part_model,
               1, o->initial_radius, 0);
-    static const int dbg_gather = getenv("OV2_BA_GATHER_ONLY") ? atoi(getenv("OV2_BA_GATHER_ONLY")) : 0;
-    static const int chol_multi_min = getenv("OV2_CHOL_MULTI_MIN") ? atoi(getenv("OV2_CHOL_MULTI_MIN")) : CHOL_MULTI_MIN;
     for (int round = 0; round < max_rounds; ++round) {
         // ---- ComputeTrustRegionStep
         BA_LAUNCH(S, K_LMDIAG, ba_lmdiag_sinit_kernel, dim3((unsigned)((S.cover_max + 255) / 256), B), dim3(256), 0, st, d, lo.min_d, lo.max_d);
@@ -3042,17 +2828,17 @@ ov2_status enqueue_minimize(ba_solver &S, int max_rounds)
                 BA_LAUNCH(S, K_SCHUR, (bs_landmark_kernel<1, BS_LM_GW>), g_lm, dim3(256), 0, st, d, S.cells);
                 if (gblocks > 0)
                     BA_LAUNCH(S, K_SCHUR, bs_gather_kernel<1>, dim3((unsigned)gblocks), dim3(256), 0, st, d, S.cells, S.pcell_ptr,
-                              S.n_pairs, S.pair_key, S.seg_start, S.pair_ent, S.fb, dbg_gather);
+                              S.n_pairs, S.pair_key, S.seg_start, S.pair_ent, S.fb);
             } else {
                 BA_LAUNCH(S, K_SCHUR, (bs_landmark_kernel<3, BS_LM_GW>), g_lm, dim3(256), 0, st, d, S.cells);
                 if (gblocks > 0)
                     BA_LAUNCH(S, K_SCHUR, bs_gather_kernel<3>, dim3((unsigned)gblocks), dim3(256), 0, st, d, S.cells, S.pcell_ptr,
-                              S.n_pairs, S.pair_key, S.seg_start, S.pair_ent, S.fb, dbg_gather);
+                              S.n_pairs, S.pair_key, S.seg_start, S.pair_ent, S.fb);
             }
         }
         if (S.mmax > 0) {
             const int m = S.mmax;
-            if (m >= chol_multi_min) {
+            if (m >= CHOL_MULTI_MIN) {
                 // right-looking, two launches per panel (trailing update on the matrix cores), then the backward pass;
                 // window = blockIdx.y, grids sized for the largest window
                 for (int k0 = 0; k0 < m; k0 += CHOL_NB) {
@@ -3065,19 +2851,7 @@ ov2_status enqueue_minimize(ba_solver &S, int max_rounds)
                 }
                 BA_LAUNCH(S, K_CHOL, ba_chol_backward_kernel, dim3(B), dim3(256), (size_t)(m + CHOL_NB + 2) * 8, st, d, S.chold, S.chold_stride);
             } else {
-                static const int chol_mfma = getenv("OV2_CHOL_MFMA") ? atoi(getenv("OV2_CHOL_MFMA")) : 1;
-                const size_t ldsm = ((size_t)(m + 1) * 33 + 32 + 8) * 8;
-                if (chol_mfma && ldsm <= 158 * 1024) {
-                    BA_LAUNCH(S, K_CHOL, ba_chol_mfma_kernel, g_win, dim3(CHOL_THREADS), ldsm, st, d);
-                } else {
-                // one workgroup per window; panel width by LDS budget: (m+1) x (NB+1) + NB x 64 doubles <= 158 KiB
-                const size_t lds32 = ((size_t)(m + 1) * 33 + 32 * 64 + 4) * 8, lds16 = ((size_t)(m + 1) * 17 + 16 * 64 + 4) * 8,
-                             lds8 = ((size_t)(m + 1) * 9 + 8 * 64 + 4) * 8;
-                if (lds32 <= 158 * 1024) BA_LAUNCH(S, K_CHOL, ba_chol_kernel<32>, g_win, dim3(CHOL_THREADS), lds32, st, d);
-                else if (lds16 <= 158 * 1024) BA_LAUNCH(S, K_CHOL, ba_chol_kernel<16>, g_win, dim3(CHOL_THREADS), lds16, st, d);
-                else if (lds8 <= 158 * 1024) BA_LAUNCH(S, K_CHOL, ba_chol_kernel<8>, g_win, dim3(CHOL_THREADS), lds8, st, d);
-                else return ov2_set_err(c, OV2_ERR_UNSUPPORTED, "reduced camera system of %d unknowns exceeds the one-workgroup Cholesky", m);
-                }
+                BA_LAUNCH(S, K_CHOL, ba_chol_mfma_kernel, g_win, dim3(CHOL_THREADS), chol_mfma_lds(m), st, d);   // one workgroup per window
             }
         }
         {
@@ -3137,16 +2911,6 @@ ov2_status fetch_windows(ba_solver &S)
 }
 
 }  // namespace
-
-#ifdef OV2_CHOL_PROF
-extern "C" int ov2_debug_chol_prof(unsigned long long *out, int reset)
-{
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chol_prof), sizeof(z)) != hipSuccess) return 1;
-    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_chol_prof), z, sizeof(z)) != hipSuccess) return 1;
-    return 0;
-}
-#endif
 
 extern "C" void ov2_ba_default_options(ov2_ba_options *o, float robust_mono_th)
 {

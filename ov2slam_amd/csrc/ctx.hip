@@ -70,42 +70,16 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     c->kf_scratch_bytes = 0;
     c->kf.fork = c->kf.done = nullptr;
     c->kf.want_stereo_ev = c->kf.stereo_valid = false;
-    // OV2_KF_OVERLAP=0: the keyframe detector chain stays on the main stream (default 1, ov2_ctx_set_kf_overlap);
-    // experiment hook: 2 runs the chain on the pyramid stream instead of a stream of its own
+    // OV2_KF_OVERLAP=0: the keyframe detector chain stays on the main stream (default 1, ov2_ctx_set_kf_overlap)
     const char *kf_env = getenv("OV2_KF_OVERLAP");
-    const int kf_mode = kf_env ? atoi(kf_env) : 1;
-    const bool kf_on_pyr = kf_mode == 2;
-    c->kf_overlap = kf_mode > 0 ? 1 : 0;
+    c->kf_overlap = (kf_env ? atoi(kf_env) : 1) > 0 ? 1 : 0;
+    // three streams of one priority: tracking / BA, pyramid builds, keyframe detector chain
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    // experiment hook: OV2_CU_SPLIT=k keeps the first k compute units of the device for the high-priority contexts
-    // (the local-BA worker) and the remaining ones for the others, instead of sharing all of them by priority
-    const char *split_env = getenv("OV2_CU_SPLIT");
-    const int split = split_env ? atoi(split_env) : 0;
-    hipError_t e1, e2, e3 = hipSuccess;
-    if (split > 0) {
-        hipDeviceProp_t prop;
-        (void)hipGetDeviceProperties(&prop, device);
-        const int ncu = prop.multiProcessorCount, words = (ncu + 31) / 32;
-        std::vector<uint32_t> mask(words, 0u);
-        for (int i = 0; i < ncu; ++i) {
-            const bool mine = high_priority ? (i < split) : (i >= split);
-            if (mine) mask[i / 32] |= 1u << (i % 32);
-        }
-        e1 = hipExtStreamCreateWithCUMask(&c->stream.h, (uint32_t)words, mask.data());
-        e2 = hipExtStreamCreateWithCUMask(&c->stream_pyr, (uint32_t)words, mask.data());
-        if (!kf_on_pyr) e3 = hipExtStreamCreateWithCUMask(&c->stream_kf, (uint32_t)words, mask.data());
-    } else {
-        e1 = hipStreamCreateWithPriority(&c->stream.h, hipStreamNonBlocking, high_priority ? prio_greatest : prio_least);
-        // experiment hook: OV2_SINGLE_STREAM=1 builds the pyramids on the main stream (no overlap with the tracking)
-        const char *one = getenv("OV2_SINGLE_STREAM");
-        if (one && atoi(one) > 0) { c->stream_pyr = c->stream_kf = c->stream.h; e2 = hipSuccess; }
-        else {
-            e2 = hipStreamCreateWithPriority(&c->stream_pyr, hipStreamNonBlocking, high_priority ? prio_greatest : prio_least);
-            if (!kf_on_pyr) e3 = hipStreamCreateWithPriority(&c->stream_kf, hipStreamNonBlocking, high_priority ? prio_greatest : prio_least);
-        }
-    }
-    if (kf_on_pyr && e2 == hipSuccess) c->stream_kf = c->stream_pyr;
+    const int prio = high_priority ? prio_greatest : prio_least;
+    const hipError_t e1 = hipStreamCreateWithPriority(&c->stream.h, hipStreamNonBlocking, prio);
+    const hipError_t e2 = hipStreamCreateWithPriority(&c->stream_pyr, hipStreamNonBlocking, prio);
+    const hipError_t e3 = hipStreamCreateWithPriority(&c->stream_kf, hipStreamNonBlocking, prio);
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess ||
         hipEventCreateWithFlags(&c->kf.fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->kf.done, hipEventDisableTiming) != hipSuccess ||
@@ -124,7 +98,7 @@ extern "C" void ov2_ctx_destroy(ov2_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamSynchronize(c->stream_pyr);
-    if (c->stream_kf) (void)hipStreamSynchronize(c->stream_kf);
+    (void)hipStreamSynchronize(c->stream_kf);
     for (ov2_pyr_buf *b : c->pool) {
         (void)hipEventDestroy(b->ready_ev);
         (void)hipEventDestroy(b->free_ev);
@@ -152,8 +126,8 @@ extern "C" void ov2_ctx_destroy(ov2_ctx *c)
     if (c->stage_ev) (void)hipEventDestroy(c->stage_ev);
     if (c->kf.fork) (void)hipEventDestroy(c->kf.fork);
     if (c->kf.done) (void)hipEventDestroy(c->kf.done);
-    if (c->stream_kf && c->stream_kf != c->stream.h && c->stream_kf != c->stream_pyr) (void)hipStreamDestroy(c->stream_kf);
-    if (c->stream_pyr != c->stream.h) (void)hipStreamDestroy(c->stream_pyr);
+    (void)hipStreamDestroy(c->stream_kf);
+    (void)hipStreamDestroy(c->stream_pyr);
     (void)hipStreamDestroy(c->stream.h);
     delete c;
 }

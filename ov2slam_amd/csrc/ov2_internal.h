@@ -96,7 +96,7 @@ struct ov2_ctx {
     int device;
     ov2_main_stream stream;              // main stream: KLT, detectors, BA
     hipStream_t stream_pyr;              // pyramid builds run here so that frame t+1's pyramid overlaps frame t's KLT
-    hipStream_t stream_kf;               // keyframe side stream: the detector chain (= main stream under OV2_SINGLE_STREAM)
+    hipStream_t stream_kf;               // keyframe side stream: the detector chain while kf_overlap is on (always a stream of its own)
     int kf_overlap;                      // ov2_ctx_set_kf_overlap / OV2_KF_OVERLAP: 0 = the chain stays on the main stream
     ov2_kf_fork kf;
     void *kf_scratch_dev;                // scratch of the chain on the side stream (grown on demand; growth waits for

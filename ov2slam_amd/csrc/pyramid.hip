@@ -59,9 +59,7 @@ __device__ __forceinline__ void store_reflections(unsigned char *plane, int istr
 // 4l .. 4l+3 for the clip / redistribute / scan steps (wave shuffles), and writes its four LUT bytes as one dword.
 // A workgroup per tile (the first version) is a chain of barrier-separated phases with eight workgroups resident per CU
 // (4.2 rounds for 64 images x 135 tiles); here every tile of the batch is resident at once.
-#ifndef CLW_COPIES
 #define CLW_COPIES 4
-#endif
 __global__ __launch_bounds__(256) void clahe_lut_wave_kernel(const unsigned char *__restrict__ src, int w, int h,
                                                              int sstride, size_t sbstride, int tiles_x, int tiles_y,
                                                              int tw, int th, int clip_limit, float lut_scale,
@@ -545,12 +543,8 @@ __global__ __launch_bounds__(256) void pyrdown_kernel(ov2_pyr_view pv, int l)
 //   LDS level l+1: rows 2Y-2 .. 2Y+2 P2_TH+1, groups of four columns from 2X-4 (group g = columns 2X-4+4g .. +3)
 // grid (ceil(w_{l+2}/P2_TW), ceil(h_{l+2}/P2_TH), batch), 256 threads.
 static_assert(OV2_LM % 16 == 0, "pyrdown2_kernel stages 16-byte chunks from column -16 of the tile");
-#ifndef P2_TW
 #define P2_TW 32
-#endif
-#ifndef P2_TH
 #define P2_TH 16
-#endif
 #define P2_R1 (2 * P2_TH + 4)                  // level-(l+1) rows in LDS
 #define P2_G1 (P2_TW / 2 + 2)                  // level-(l+1) dword groups per LDS row (the first and last feed the ring)
 #define P2_DW1 ((P2_G1 + 3) & ~3)              // level-(l+1) LDS row stride, dwords (16-byte rows)
@@ -1111,8 +1105,7 @@ extern "C" ov2_status ov2_pyramid_build_images(ov2_ctx *c, const ov2_images *im,
         const int cells = ((int)((float)(L0_TW + 16) / tw) + 2) * ((int)((float)(L0_TH + 4) / th) + 2);
         fused_lds = ((size_t)L0_ROWS * L0_DW + 4 * L0_RT_DW + (size_t)cells * 256) * 4;
     }
-    static const bool no_fused = getenv("OV2_PYR_NO_FUSED") != nullptr;   // experiments: the two-kernel path
-    if (use_clahe && v.nlevels >= 2 && fused_lds <= 64 * 1024 && im->w >= 8 && im->h >= 8 && !no_fused) {
+    if (use_clahe && v.nlevels >= 2 && fused_lds <= 64 * 1024 && im->w >= 8 && im->h >= 8) {
         OV2_LAUNCH_ON(c, OV2_K_LEVEL0, sp, level0_clahe_pyrdown_kernel, dim3((im->w + L0_TW - 1) / L0_TW, (im->h + L0_TH - 1) / L0_TH, B),
                       dim3(256), fused_lds, sp, im->base, im->w, im->h, im->stride, im->bstride, buf->lut, tiles_x, tiles_y, inv_tw,
                       inv_th, v);
@@ -1127,10 +1120,9 @@ extern "C" ov2_status ov2_pyramid_build_images(ov2_ctx *c, const ov2_images *im,
     }
     // pyrDown chain only: the gradient planes are written when a consumer asks for them (ov2_pyr_need_grad)
     { std::lock_guard<std::mutex> g(c->mu); buf->grad_built = false; }
-    // two levels per launch while two are left, then one; OV2_PYR_ONE_LEVEL (experiments): one level per launch throughout
-    static const bool one_level = getenv("OV2_PYR_ONE_LEVEL") != nullptr;
+    // two levels per launch while two are left, then one
     int l = first_down;
-    for (; !one_level && l + 2 < v.nlevels; l += 2) {
+    for (; l + 2 < v.nlevels; l += 2) {
         const ov2_level_desc &M = v.lv[l + 2];
         OV2_LAUNCH_ON(c, OV2_K_LEVEL, sp, pyrdown2_kernel, dim3((M.w + P2_TW - 1) / P2_TW, (M.h + P2_TH - 1) / P2_TH, B), dim3(256), 0,
                       sp, v, l);

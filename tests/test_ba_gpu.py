@@ -87,16 +87,49 @@ def test_local_ba_edge_cases(ctx, oracle):
         local_ba.Optimizer(ctx).localBA(B)
 
 
-def test_local_ba_multi_workgroup_cholesky_ragged(ctx, oracle):
-    """68 keyframes: the reduced camera system (m = 6 x free poses >= 320) takes the right-looking multi-workgroup
-    Cholesky (MFMA trailing updates) with a ragged last panel and ragged 16 x 16 tiles."""
-    P = synth_ba.make_window(68, 5000, inv_depth=True, seed=61, max_obs=7)
+CHOL_MULTI_MIN = 400   # ov2slam_amd/csrc/ba.hip: from this m on the Cholesky is the multi-workgroup form
+
+
+@pytest.fixture(scope="module")
+def multi_wg_windows(oracle):
+    """two windows on the multi-workgroup side of CHOL_MULTI_MIN (m = 414 and 438, 19 k residual blocks each) with their
+    oracle solves: (initial problem, problem solved by the oracle, oracle result); shared, so the tests work on copies."""
+    out = []
+    for n_kf in (86, 91):
+        P = synth_ba.make_window(n_kf, 1500, inv_depth=True, seed=61, max_obs=7)
+        Pc = P.copy()
+        out.append((P, Pc, oracle.ba_solve(Pc)))
+    return out
+
+
+def test_local_ba_multi_workgroup_cholesky_ragged(ctx, multi_wg_windows):
+    """86 keyframes: the reduced camera system (m = 6 x free poses = 414 >= CHOL_MULTI_MIN) takes the right-looking
+    multi-workgroup Cholesky (MFMA trailing updates) with a ragged last panel and ragged 16 x 16 tiles."""
+    P0, Pc, Rc = multi_wg_windows[0]
+    P = P0.copy()
     m = 6 * int((P.pose_const == 0).sum())
-    assert m >= 320 and m % 32 != 0 and m % 16 != 0
-    Pc = P.copy()
+    assert m >= CHOL_MULTI_MIN and m % 32 != 0 and m % 16 != 0
     Rg = local_ba.Optimizer(ctx).localBA(P)
-    Rc = oracle.ba_solve(Pc)
     _compare(P, Rg, Pc, Rc, flags_exact=False)
+
+
+def test_local_ba_batch_multi_workgroup_cholesky(ctx, multi_wg_windows):
+    """two windows of different m >= CHOL_MULTI_MIN (414 and 438, both ragged) in one batch: the panel / trailing-update grids
+    are sized for the larger window and window = blockIdx.y.  Each window matches the oracle like a lone solve does and is
+    BITWISE what the same window gives when it is solved alone."""
+    Ps = [w[0].copy() for w in multi_wg_windows]
+    singles = [w[0].copy() for w in multi_wg_windows]
+    ms = [6 * int((P.pose_const == 0).sum()) for P in Ps]
+    assert ms[0] != ms[1] and all(m >= CHOL_MULTI_MIN and m % 32 != 0 and m % 16 != 0 for m in ms)
+    opt = local_ba.Optimizer(ctx)
+    Rb = opt.localBA_batch(Ps)
+    for k, (P, R) in enumerate(zip(Ps, Rb)):
+        Rs = opt.localBA(singles[k])
+        assert np.array_equal(P.pose.view(np.uint64), singles[k].pose.view(np.uint64)), k
+        assert np.array_equal(P.lm.view(np.uint64), singles[k].lm.view(np.uint64)), k
+        assert R.c.n_log == Rs.c.n_log and R.c.final_cost == Rs.c.final_cost and R.c.l2_final_cost == Rs.c.l2_final_cost
+        assert np.array_equal(R.outlier, Rs.outlier) and np.array_equal(R.chi2.view(np.uint64), Rs.chi2.view(np.uint64))
+        _compare(P, R, multi_wg_windows[k][1], multi_wg_windows[k][2])
 
 
 @pytest.mark.parametrize("inv_depth", [True, False])
