@@ -33,6 +33,8 @@
 // MFMA only in the multi-workgroup Cholesky's SYRK (v_mfma_f64_16x16x4_f64): the other contractions are 6x6 / 6x1 / 6x3
 // blocks and every kernel of an LM round waits on memory (SQ counters: 52-82 % of the wave cycles, scripts/profile_ba_sq.sh).
 #include "ov2_internal.h"
+#include "ov2_se3.h"
+#include "ov2_wave.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -43,6 +45,9 @@
 #include <algorithm>
 #include <cmath>
 #include <numeric>
+
+using namespace ov2se3;    // pose / quaternion arithmetic in the oracle's order (ov2_se3.h)
+using namespace ov2wave;   // fixed-order wave and workgroup sums (ov2_wave.h)
 
 namespace {
 
@@ -119,81 +124,6 @@ struct ba_lmopt {   // the solver options the device-side state machine needs
     double min_d, max_d, max_radius, min_radius, min_rel, ptol, gtol, ftol;
     int max_invalid, jacobi;
 };
-
-// ------------------------------------------------------------------------------------------------------
-// SE3 helpers (same formulas as the oracle / Sophus / Eigen)
-
-__host__ __device__ inline void quat_to_R(const double q[4], double R[9])
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
-__host__ __device__ inline void pose_Rt(const double *p, double R[9], double t[3])
-{
-    double q[4] = {p[3], p[4], p[5], p[6]};
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
-    quat_to_R(q, R);
-    t[0] = p[0]; t[1] = p[1]; t[2] = p[2];
-}
-
-__device__ inline void se3_plus(const double *x, const double *d, double *out)
-{
-    // Sophus::SE3::exp(d) * SE3(q,t)   (se3left_parametrization.hpp:41-60)
-    const double *u = d, *w = d + 3;
-    const double eps = 1e-10;
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    double theta, imag, real;
-    if (th2 < eps * eps) {
-        theta = 0.0;
-        const double th4 = th2 * th2;
-        imag = 0.5 - (1.0 / 48.0) * th2 + (1.0 / 3840.0) * th4;
-        real = 1.0 - (1.0 / 8.0) * th2 + (1.0 / 384.0) * th4;
-    } else {
-        theta = sqrt(th2);
-        const double half = 0.5 * theta;
-        imag = sin(half) / theta;
-        real = cos(half);
-    }
-    const double a[4] = {imag * w[0], imag * w[1], imag * w[2], real};
-    double Ra[9], V[9];
-    quat_to_R(a, Ra);
-    if (theta < eps) {
-        for (int i = 0; i < 9; ++i) V[i] = Ra[i];
-    } else {
-        const double O[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-        double O2[9];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double s = 0;
-                for (int k = 0; k < 3; ++k) s += O[3 * i + k] * O[3 * k + j];
-                O2[3 * i + j] = s;
-            }
-        const double t2 = theta * theta;
-        const double c1 = (1.0 - cos(theta)) / t2, c2 = (theta - sin(theta)) / (t2 * theta);
-        for (int i = 0; i < 9; ++i) V[i] = ((i % 4 == 0) ? 1.0 : 0.0) + c1 * O[i] + c2 * O2[i];
-    }
-    double b[4] = {x[3], x[4], x[5], x[6]};
-    const double nb = sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2] + b[3] * b[3]);
-    b[0] /= nb; b[1] /= nb; b[2] /= nb; b[3] /= nb;
-    double q[4];
-    q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-    const double nq = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int r = 0; r < 3; ++r)
-        out[r] = (V[3 * r] * u[0] + V[3 * r + 1] * u[1] + V[3 * r + 2] * u[2]) +
-                 (Ra[3 * r] * x[0] + Ra[3 * r + 1] * x[1] + Ra[3 * r + 2] * x[2]);
-    out[3] = q[0] / nq; out[4] = q[1] / nq; out[5] = q[2] / nq; out[6] = q[3] / nq;
-}
 
 // ------------------------------------------------------------------------------------------------------
 // one residual block: r, local jacobians, chi2, depth sign  (src/ceres_parametrization.cpp, 5 functors)
@@ -309,19 +239,6 @@ __device__ inline void huber(double a, double s, double rho[3])
     } else {
         rho[0] = s; rho[1] = 1.0; rho[2] = 0.0;
     }
-}
-
-// block-wide ordered sum of one double per thread (blockDim = 256) -> lane 0 of the block returns the total
-__device__ inline double block_sum_256(double v, double *sh)
-{
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) sh[t] += sh[t + s];
-        __syncthreads();
-    }
-    return sh[0];
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -742,23 +659,6 @@ __global__ void ba_lmdiag_sinit_kernel(ba_dev d, double min_d, double max_d)
 
 // Packed 64-bit sort keys with runtime field widths (every sort is a hipcub SortKeys over the bit range that matters; the
 // radix sort is stable, so whatever sits in the bits below the range rides along in its original order).
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int lane)   // lane must be wave-uniform
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | lo);
-}
-
 // n doubles (n even) from a 16-byte aligned address as 16-byte loads
 template <int N>
 __device__ __forceinline__ void load_d2(const double *__restrict__ p, double *out)
@@ -789,15 +689,6 @@ __device__ __forceinline__ void load_U(const ba_dev &d, size_t r, const double *
     }
 }
 
-__device__ __forceinline__ double row_sum(double v)
-{
-    v += dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_f64<0x141>(v);   // row_half_mirror
-    v += dpp_f64<0x140>(v);   // row_mirror
-    return v;
-}
-
 template <int E>
 __device__ __forceinline__ void invert_ete(const double *ete, double *ie)
 {
@@ -811,17 +702,6 @@ __device__ __forceinline__ void invert_ete(const double *ete, double *ie)
         ie[3] = B * id; ie[4] = (a * f - c * c) * id; ie[5] = (b * c - a * ee) * id;
         ie[6] = C * id; ie[7] = ie[5]; ie[8] = (a * dd - b * b) * id;
     }
-}
-
-// sum over the GW (8 | 16) lanes of a landmark group, result in all of them
-template <int GW>
-__device__ __forceinline__ double grp_sum(double v)
-{
-    v += dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_f64<0x141>(v);   // row_half_mirror
-    if (GW == 16) v += dpp_f64<0x140>(v);   // row_mirror
-    return v;
 }
 
 #define BS_LM_GW 8   // lanes per landmark in the landmark-major kernels (column norms, elimination, back-substitution): 12 rows / 7
@@ -851,7 +731,7 @@ __global__ __launch_bounds__(256) void ba_colnorm16_kernel(ba_dev d, int mode)
             }
         }
     }
-    for (int c = 0; c < e; ++c) { se[c] = grp_sum<GW>(se[c]); ge[c] = grp_sum<GW>(ge[c]); }
+    for (int c = 0; c < e; ++c) { se[c] = row_sum_f64<GW>(se[c]); ge[c] = row_sum_f64<GW>(ge[c]); }
     if (live && sub == 0)
         for (int c = 0; c < e; ++c) { d.sqn[l * e + c] = se[c]; d.grad[l * e + c] = ge[c]; }
 }
@@ -899,8 +779,7 @@ __global__ __launch_bounds__(256) void ba_pose_normal_kernel(ba_dev d, const int
     }
 #pragma unroll
     for (int c = 0; c < 27; ++c) {
-        const double v = row_sum(acc[c]);
-        const double w = (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+        const double w = wave_sum_f64(acc[c]);
         if ((tid & 63) == 0) sh[tid >> 6][c] = w;
     }
     __syncthreads();
@@ -963,7 +842,7 @@ __global__ __launch_bounds__(256) void ba_backsub16_kernel(ba_dev d, double *__r
         if (r < r1) { rowv v; load_row(r, v); sweep1(v); }
     }
     double y[E];
-    for (int i = 0; i < E; ++i) acc[i] = grp_sum<GW>(acc[i]);
+    for (int i = 0; i < E; ++i) acc[i] = row_sum_f64<GW>(acc[i]);
     for (int i = 0; i < E; ++i) {
         double s = 0;
         for (int j = 0; j < E; ++j) s += (live ? d.iete[(size_t)l * E * E + i * E + j] : 0.0) * acc[j];
@@ -982,7 +861,7 @@ __global__ __launch_bounds__(256) void ba_backsub16_kernel(ba_dev d, double *__r
         const int r = base + sub;
         if (r < r1) { rowv v; load_row(r, v); sweep2(v); }
     }
-    mc = grp_sum<GW>(mc);
+    mc = row_sum_f64<GW>(mc);
     if (live && sub == 0) {
         for (int i = 0; i < E; ++i) d.step[l * E + i] = -y[i];
         part[l] = mc;
@@ -2068,8 +1947,8 @@ __global__ __launch_bounds__(256) void bs_landmark_kernel(ba_dev d, ba_cells C)
             }
         }
     }
-    for (int i = 0; i < E * E; ++i) ete[i] = grp_sum<GW>(ete[i]);
-    for (int i = 0; i < E; ++i) g[i] = grp_sum<GW>(g[i]);
+    for (int i = 0; i < E * E; ++i) ete[i] = row_sum_f64<GW>(ete[i]);
+    for (int i = 0; i < E; ++i) g[i] = row_sum_f64<GW>(g[i]);
     if (live) for (int i = 0; i < E; ++i) { const double dv = d.lmd[l * E + i]; ete[i * E + i] += dv * dv; }
     else for (int i = 0; i < E; ++i) ete[i * E + i] = 1.0;
     double ie[E * E], ieg[E];
@@ -2130,15 +2009,9 @@ __global__ __launch_bounds__(256) void bs_landmark_kernel(ba_dev d, ba_cells C)
         store_cell(C.cell_rank[c0 + c], Wk);
     }
     if (has_anchor) {   // W of the anchor cell: summed over all rows by the group (anchor block of a row = -U)
-        for (int i = 0; i < 6 * E; ++i) Wa[i] = grp_sum<GW>(Wa[i]);
+        for (int i = 0; i < 6 * E; ++i) Wa[i] = row_sum_f64<GW>(Wa[i]);
         if (sub == 0) store_cell(C.cell_rank[c0 + nc - 1], Wa);
     }
-}
-
-__device__ __forceinline__ double wave_total(double v)
-{
-    v = row_sum(v);
-    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
 }
 
 // (2a) one workgroup per pose block: diagonal block of S (lower triangle) = D_f^2 + F'F - sum_cells W (E'E + D)^-1 W' and
@@ -2176,7 +2049,7 @@ __device__ __forceinline__ void bs_diag_block(const ba_dev &d, const ba_cells &C
     }
 #pragma unroll
     for (int t = 0; t < 27; ++t) {
-        const double w = wave_total(acc[t]);
+        const double w = wave_sum_f64(acc[t]);
         if ((tid & 63) == 0) red[tid >> 6][t] = w;
     }
     __syncthreads();
@@ -2269,7 +2142,7 @@ __device__ __forceinline__ void bs_pair_block(const ba_dev &d, const ba_cells &C
     double mine = 0.0;
 #pragma unroll
     for (int t = 0; t < 36; ++t) {
-        double v = wave_total(acc[t]);
+        double v = wave_sum_f64(acc[t]);
         // every total lands in a VGPR before the next one is read: left free, the scheduler issues the lane reads of many
         // totals ahead of their sums (8 SGPRs each), 202 SGPRs spill into VGPR lanes and E = 1 drops from 3 to 2 waves per SIMD
         asm volatile("" : "+v"(v));

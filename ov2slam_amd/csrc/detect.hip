@@ -18,8 +18,11 @@
 // striding grids were measured and are not faster).  One fill zeroes counters, occupancy, per-cell
 // outputs and the mask (0 = free, non-zero = masked) in front of a call.
 #include "ov2_internal.h"
+#include "ov2_wave.h"
 
 #include <cmath>
+
+using namespace ov2wave;   // fixed-order wave and workgroup sums (ov2_wave.h)
 
 namespace {
 
@@ -53,13 +56,6 @@ disc_shape make_disc(int radius)
         minus -= m & 2;
     }
     return s;
-}
-
-__device__ __forceinline__ int reflect101(int i, int n)
-{
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-    return i;
 }
 
 // all threads of the workgroup mark the disc around (cx, cy) in the w x h mask
@@ -500,26 +496,6 @@ __global__ __launch_bounds__(256) void det_assemble_kernel(int mode, int nwcells
     for (int k = tid; k < n; k += 256) { pt_ref[gbase + k] = b * out_cap + k; pt_img[gbase + k] = b; }
 }
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | lo);
-}
-
-// 16-leaf pairwise tree ((l0+l1)+(l2+l3))+... over a DPP row, total in every lane of the row.  After the two quad steps
-// all lanes of a quad agree, so the mirror steps pair equal partial sums exactly like xor 4 / xor 8 would.
-__device__ __forceinline__ double row_tree_f64(double v)
-{
-    v += dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_f64<0x141>(v);   // row_half_mirror
-    v += dpp_f64<0x140>(v);   // row_mirror
-    return v;
-}
-
 // cv::cornerSubPix (win = (HW,HW), zeroZone none): FOUR points per wave, one per DPP row of 16 lanes.
 // Per iteration: the (2HW+4)^2 source pixels are fetched once (clamped = getRectSubPix's BORDER_REPLICATE) into LDS,
 // the (2HW+3)^2 bilinear samples are formed from LDS, window term t is owned by lane t % 16 (terms t, t+16, ... added
@@ -615,8 +591,8 @@ __global__ __launch_bounds__(64) void subpix_kernel(const unsigned char *__restr
                 }
             }
         }
-        A = row_tree_f64(A); Bm = row_tree_f64(Bm); C = row_tree_f64(C);
-        bb1 = row_tree_f64(bb1); bb2 = row_tree_f64(bb2);
+        A = row_sum_f64<16>(A); Bm = row_sum_f64<16>(Bm); C = row_sum_f64<16>(C);
+        bb1 = row_sum_f64<16>(bb1); bb2 = row_sum_f64<16>(bb2);
         if (go) {
             const double det = A * C - Bm * Bm;
             if (fabs(det) <= 2.220446049250313e-16 * 2.220446049250313e-16) go = false;

@@ -21,6 +21,9 @@
 #include <cstdlib>
 
 #include "ov2_internal.h"
+#include "ov2_wave.h"
+
+using namespace ov2wave;   // fixed-order wave and workgroup sums (ov2_wave.h)
 
 namespace {
 
@@ -35,43 +38,6 @@ struct klt_params {
 };
 
 #define W_BITS 14
-
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v)
-{
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
-}
-
-// sum over the GL (8 or 16) lanes of a keypoint's lane group, result in every lane of the group
-template <int GL>
-__device__ __forceinline__ int row_sum_i32(int v)
-{
-    v += dpp_i32<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_i32<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_i32<0x141>(v);   // row_half_mirror: lane l <-> 7 - l of its half row
-    if (GL == 16) v += dpp_i32<0x140>(v);   // row_mirror
-    return v;
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64k(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | lo);
-}
-
-// exact: the addends are integers below 2^32, every partial sum is an integer below 2^53
-template <int GL>
-__device__ __forceinline__ double row_sum_f64(double v)
-{
-    v += dpp_f64k<0xB1>(v);
-    v += dpp_f64k<0x4E>(v);
-    v += dpp_f64k<0x141>(v);
-    if (GL == 16) v += dpp_f64k<0x140>(v);
-    return v;
-}
 
 __device__ __forceinline__ void lk_weights(float a, float b, int &w00, int &w01, int &w10, int &w11)
 {
@@ -435,7 +401,7 @@ __device__ __forceinline__ int lk_level(const level_ptrs &I, const level_ptrs &J
         if (__all((unsigned)(pb1 + (1 << 27)) < (1u << 28) && (unsigned)(pb2 + (1 << 27)) < (1u << 28))) {
             b1 = (float)row_sum_i32<GL>(pb1) * FLT_SCALE;
             b2 = (float)row_sum_i32<GL>(pb2) * FLT_SCALE;
-        } else {
+        } else {   // exact: the addends are integers below 2^32, every partial sum is an integer below 2^53
             b1 = (float)row_sum_f64<GL>((double)pb1) * FLT_SCALE;
             b2 = (float)row_sum_f64<GL>((double)pb2) * FLT_SCALE;
         }
@@ -524,9 +490,9 @@ __device__ __forceinline__ int sum3_i32(int v, int c)
 }
 __device__ __forceinline__ double sum3_f64(double v, int c)
 {
-    double t = v + dpp_f64k<0x111>(v);
-    t += dpp_f64k<0x112>(v);
-    const double u1 = dpp_f64k<0x101>(t), u2 = dpp_f64k<0x102>(t);
+    double t = v + dpp_f64<0x111>(v);
+    t += dpp_f64<0x112>(v);
+    const double u1 = dpp_f64<0x101>(t), u2 = dpp_f64<0x102>(t);
     return c == 2 ? t : (c == 1 ? u1 : u2);
 }
 

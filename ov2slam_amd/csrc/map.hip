@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ov2_internal.h"
+#include "ov2_se3.h"
 #include "tri_pair.h"
 
 struct ov2_map {
@@ -561,11 +562,10 @@ __device__ __forceinline__ void me_lms(const map_job &j, int l, int inv, const f
 // z of (Twc^-1 * p): third row of R' times (p - t); Twc = [t, qx qy qz qw] (Sophus, include/frame.hpp getTcw)
 __device__ __forceinline__ double depth_in_kf(const double *T, const double *p)
 {
-    const double x = T[3], y = T[4], z = T[5], w = T[6];
     const double dx = p[0] - T[0], dy = p[1] - T[1], dz = p[2] - T[2];
-    // third column of R(q) = third row of R'
-    const double r02 = 2.0 * (x * z + w * y), r12 = 2.0 * (y * z - w * x), r22 = 1.0 - 2.0 * (x * x + y * y);
-    return r02 * dx + r12 * dy + r22 * dz;
+    double R[9];
+    ov2se3::tri_quat_R(T, R);
+    return R[2] * dx + R[5] * dy + R[8] * dz;   // third column of R(q) = third row of R'
 }
 
 __device__ __forceinline__ void me_res(const map_job &j, int i, int inv, const flat_out &O)
@@ -705,18 +705,6 @@ __global__ __launch_bounds__(256) void mu_recount_kernel(const map_job *__restri
     atomicMax(&j.lm_pack[lm], ((unsigned long long)(ANCH_TOP - kf) << 32) | (unsigned)i);
 }
 
-// rotation of the unit quaternion (x, y, z, w) applied to v, plus t: Twc * v
-__device__ __forceinline__ void se3_apply(const double *T, const double *v, double *out)
-{
-    const double x = T[3], y = T[4], z = T[5], w = T[6];
-    const double r00 = 1.0 - 2.0 * (y * y + z * z), r01 = 2.0 * (x * y - z * w), r02 = 2.0 * (x * z + y * w);
-    const double r10 = 2.0 * (x * y + z * w), r11 = 1.0 - 2.0 * (x * x + z * z), r12 = 2.0 * (y * z - x * w);
-    const double r20 = 2.0 * (x * z - y * w), r21 = 2.0 * (y * z + x * w), r22 = 1.0 - 2.0 * (x * x + y * y);
-    out[0] = r00 * v[0] + r01 * v[1] + r02 * v[2] + T[0];
-    out[1] = r10 * v[0] + r11 * v[1] + r12 * v[2] + T[1];
-    out[2] = r20 * v[0] + r21 * v[1] + r22 * v[2] + T[2];
-}
-
 // pass 2: blocks [0, gP) write the solved poses of the non-constant keyframes (:767-786); the others take one landmark
 // each: the local landmarks (:789-853: isBad / culling / positive depth / new world point) and then, for the members of
 // set_badlmids -- the isBad() landmarks of the set-up and every landmark that had a flagged block -- the second
@@ -769,7 +757,7 @@ __global__ __launch_bounds__(256) void mu_apply_kernel(const map_job *__restrict
             else {
                 const double u = M.obs_uv[2 * r], v = M.obs_uv[2 * r + 1];
                 const double cam[3] = {zanch * (u - j.K[2]) / j.K[0], zanch * (v - j.K[3]) / j.K[1], zanch};
-                se3_apply(O.pose + 7 * a, cam, wpt);
+                ov2se3::tri_apply(O.pose + 7 * a, cam, wpt);   // Twc * cam
             }
         } else {
             wpt[0] = O.lm[3 * idx]; wpt[1] = O.lm[3 * idx + 1]; wpt[2] = O.lm[3 * idx + 2];
@@ -815,23 +803,10 @@ __global__ __launch_bounds__(256) void mt_rows_kernel(const map_job *__restrict_
 }
 
 // SE3::inverse / SE3::operator* of the host mirror (ov2_host.cpp), so that Tcicj = Tciw * Twcj rounds as it does there
-__device__ __forceinline__ void unit_quat_R(const double *T, double R[9])
-{
-    double x = T[3], y = T[4], z = T[5], w = T[6];
-    const double n = __dsqrt_rn(x * x + y * y + z * z + w * w);
-    x /= n; y /= n; z /= n; w /= n;
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
 __device__ __forceinline__ void se3_inverse(const double *T, double out[7])
 {
     double R[9];
-    unit_quat_R(T, R);
+    ov2se3::pose_R(T, R);
     out[0] = -(R[0] * T[0] + R[3] * T[1] + R[6] * T[2]);
     out[1] = -(R[1] * T[0] + R[4] * T[1] + R[7] * T[2]);
     out[2] = -(R[2] * T[0] + R[5] * T[1] + R[8] * T[2]);
@@ -842,8 +817,8 @@ __device__ __forceinline__ void se3_inverse(const double *T, double out[7])
 __device__ __forceinline__ void se3_mul(const double *A, const double *B, double out[7])
 {
     double Ra[9], Rb[9], R[9];
-    unit_quat_R(A, Ra);
-    unit_quat_R(B, Rb);
+    ov2se3::pose_R(A, Ra);
+    ov2se3::pose_R(B, Rb);
     R[0] = Ra[0] * Rb[0] + Ra[1] * Rb[3] + Ra[2] * Rb[6]; R[1] = Ra[0] * Rb[1] + Ra[1] * Rb[4] + Ra[2] * Rb[7];
     R[2] = Ra[0] * Rb[2] + Ra[1] * Rb[5] + Ra[2] * Rb[8]; R[3] = Ra[3] * Rb[0] + Ra[4] * Rb[3] + Ra[5] * Rb[6];
     R[4] = Ra[3] * Rb[1] + Ra[4] * Rb[4] + Ra[5] * Rb[7]; R[5] = Ra[3] * Rb[2] + Ra[4] * Rb[5] + Ra[5] * Rb[8];
@@ -852,20 +827,7 @@ __device__ __forceinline__ void se3_mul(const double *A, const double *B, double
     out[0] = Ra[0] * B[0] + Ra[1] * B[1] + Ra[2] * B[2] + A[0];
     out[1] = Ra[3] * B[0] + Ra[4] * B[1] + Ra[5] * B[2] + A[1];
     out[2] = Ra[6] * B[0] + Ra[7] * B[1] + Ra[8] * B[2] + A[2];
-    const double t = R[0] + R[4] + R[8];   // rot_to_quat
-    if (t > 0) {
-        const double q = __dsqrt_rn(t + 1.0) * 2;
-        out[6] = 0.25 * q; out[3] = (R[7] - R[5]) / q; out[4] = (R[2] - R[6]) / q; out[5] = (R[3] - R[1]) / q;
-    } else if (R[0] > R[4] && R[0] > R[8]) {
-        const double q = __dsqrt_rn(1.0 + R[0] - R[4] - R[8]) * 2;
-        out[6] = (R[7] - R[5]) / q; out[3] = 0.25 * q; out[4] = (R[1] + R[3]) / q; out[5] = (R[2] + R[6]) / q;
-    } else if (R[4] > R[8]) {
-        const double q = __dsqrt_rn(1.0 + R[4] - R[0] - R[8]) * 2;
-        out[6] = (R[2] - R[6]) / q; out[3] = (R[1] + R[3]) / q; out[4] = 0.25 * q; out[5] = (R[5] + R[7]) / q;
-    } else {
-        const double q = __dsqrt_rn(1.0 + R[8] - R[0] - R[4]) * 2;
-        out[6] = (R[3] - R[1]) / q; out[3] = (R[2] + R[6]) / q; out[4] = (R[5] + R[7]) / q; out[5] = 0.25 * q;
-    }
+    ov2se3::rot_to_quat(R, out + 3);
 }
 
 // Frame::computeKeypoint (src/frame.cpp:246-254) for a pinhole camera: unpx as the float the host keeps, bearing iK * [unpx, 1] normalised
@@ -903,14 +865,14 @@ __global__ __launch_bounds__(256) void mt_tri_kernel(const map_job *__restrict__
             const int ar = min(max(j.tt_arow[l], 0), M.n_obs - 1);   // written by the row scan for every such landmark; clamped all the same
             bearing_of(j.K, M.obs_uv + 2 * (size_t)ar, ua, va, f1);
             bearing_of(j.K, M.obs_uv + 2 * (size_t)(nr - 1), ub, vb, f2);
-            ov2tri::quat_R(T, R);
+            ov2se3::tri_quat_R(T, R);
             ov2tri::rotate(R, f2, f2u);
             const double parallax = ov2tri::parallax_px(j.K, f2u, ua, va);
             ov2tri::midpoint(T, f1, f2u, X);
             const int st = ov2tri::gates(T, R, X, j.K, j.K, ua, va, ub, vb, max_err);
             if (st == OV2_TRI_OK) {
                 good = true;
-                ov2tri::to_world(M.kf_pose + 7 * (size_t)oldkf, X, wpt);
+                ov2se3::tri_apply(M.kf_pose + 7 * (size_t)oldkf, X, wpt);
                 invdepth = 1. / X[2];
             } else rm = parallax > 20.;
         }
@@ -1681,15 +1643,42 @@ ov2_status setup_pass(ov2_ctx *c, const std::vector<int> &sel, ov2_map *const *m
     return OV2_OK;
 }
 
+// the refusals the batch entry points share, one per call so that every entry point keeps its own order of checks
+ov2_status batch_map_ok(ov2_ctx *c, const ov2_map *m, int b)
+{
+    if (!m || m->c != c) return ov2_set_err(c, OV2_ERR_INVALID, "map %d of the batch is null or belongs to another context", b);
+    return OV2_OK;
+}
+
+ov2_status batch_map_once(ov2_ctx *c, ov2_map *const *maps, int b)
+{
+    for (int q = 0; q < b; ++q)
+        if (maps[q] == maps[b]) return ov2_set_err(c, OV2_ERR_INVALID, "map %d appears twice in the batch", b);
+    return OV2_OK;
+}
+
+ov2_status batch_kf_alive(ov2_ctx *c, const ov2_map *m, int kfid, int b)
+{
+    if (kfid < 0 || kfid >= m->max_kf || !m->kf_alive_h[kfid])
+        return ov2_set_err(c, OV2_ERR_INVALID, "keyframe %d is not alive in map %d", kfid, b);
+    return OV2_OK;
+}
+
+// a stage's own header and cleared block stand where the kernels shared with the set-up look for them
+void stage_block(map_job &j, unsigned char *blk, size_t bytes)
+{
+    j.hdr = reinterpret_cast<int *>(blk); j.zero_blk = blk; j.zero_vec16 = (unsigned)(bytes / 16);
+}
+
 ov2_status setup_batch_impl(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf, int nmin_cov, int nmin_cst, int inv,
                             const double *calib_l, bool squeeze_first)
 {
+    ov2_status s;
     for (int b = 0; b < B; ++b) {
         ov2_map *m = maps[b];
-        if (!m || m->c != c) return ov2_set_err(c, OV2_ERR_INVALID, "map %d of the batch is null or belongs to another context", b);
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
         if (newkf[b] < 0 || newkf[b] >= m->max_kf) return ov2_set_err(c, OV2_ERR_INVALID, "kfid %d outside the capacity of map %d", newkf[b], b);
-        for (int q = 0; q < b; ++q)
-            if (maps[q] == m) return ov2_set_err(c, OV2_ERR_INVALID, "map %d appears twice in the batch", b);
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
         m->have_K = calib_l != nullptr;
         for (int k = 0; k < 4; ++k) m->last_K[k] = calib_l ? calib_l[4 * b + k] : 0.0;
     }
@@ -1705,8 +1694,7 @@ ov2_status setup_batch_impl(ov2_ctx *c, int B, ov2_map *const *maps, const int32
     std::vector<int> sel((size_t)B);
     for (int b = 0; b < B; ++b) sel[b] = b;
     for (int pass = 0; pass < 3 && !sel.empty(); ++pass) {
-        ov2_status s = setup_pass(c, sel, maps, newkf, nmin_cov, nmin_cst, inv);
-        if (s != OV2_OK) return s;
+        if ((s = setup_pass(c, sel, maps, newkf, nmin_cov, nmin_cst, inv)) != OV2_OK) return s;
         // a flat problem that did not fit its block: grow the block, run that map again (first calls / growing windows only)
         std::vector<int> again;
         for (int b : sel) {
@@ -1788,16 +1776,16 @@ extern "C" ov2_status ov2_map_local_ba_update_batch(ov2_ctx *c, int B, ov2_map *
     if (B == 0) return OV2_OK;
     if (B < 0 || !maps) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_local_ba_update_batch: null argument");
     int inv = -1;
+    ov2_status s;
     for (int b = 0; b < B; ++b) {
         ov2_map *m = maps[b];
-        if (!m || m->c != c) return ov2_set_err(c, OV2_ERR_INVALID, "map %d of the batch is null or belongs to another context", b);
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
         if (!m->last_valid)
             return ov2_set_err(c, OV2_ERR_INVALID, "map %d: no set-up to update from (none ran, or the tables grew / were squeezed "
                                "/ restored since)", b);
         if (m->last_updated)
             return ov2_set_err(c, OV2_ERR_INVALID, "map %d: the update stage of its last set-up has already run", b);
-        for (int q = 0; q < b; ++q)
-            if (maps[q] == m) return ov2_set_err(c, OV2_ERR_INVALID, "map %d appears twice in the batch", b);
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
         if (inv < 0) inv = m->last_inv;
         if (m->last_inv != inv) return ov2_set_err(c, OV2_ERR_INVALID, "the maps of a batch must share one landmark parametrisation (map %d)", b);
         if (inv && !m->have_K && !m->last_hdr[MH_ABORT])
@@ -1806,8 +1794,7 @@ extern "C" ov2_status ov2_map_local_ba_update_batch(ov2_ctx *c, int B, ov2_map *
     OV2_HIP(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     job_table JT;
-    ov2_status s = JT.begin(c, B);
-    if (s != OV2_OK) return s;
+    if ((s = JT.begin(c, B)) != OV2_OK) return s;
     int nset = 0, nnow = 0, pmax = 0, lmax = 0;
     for (int b = 0; b < B; ++b) {
         ov2_map *m = maps[b];
@@ -1853,25 +1840,22 @@ extern "C" ov2_status ov2_map_triangulate_temporal_batch(ov2_ctx *c, int B, ov2_
     if (!c) return OV2_ERR_INVALID;
     if (B == 0) return OV2_OK;
     if (B < 0 || !maps || !newkf || !calib_l) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_triangulate_temporal_batch: null argument");
+    ov2_status s;
     for (int b = 0; b < B; ++b) {
         const ov2_map *m = maps[b];
-        if (!m || m->c != c) return ov2_set_err(c, OV2_ERR_INVALID, "map %d of the batch is null or belongs to another context", b);
-        if (newkf[b] < 0 || newkf[b] >= m->max_kf || !m->kf_alive_h[newkf[b]])
-            return ov2_set_err(c, OV2_ERR_INVALID, "keyframe %d is not alive in map %d", newkf[b], b);
-        for (int q = 0; q < b; ++q)
-            if (maps[q] == m) return ov2_set_err(c, OV2_ERR_INVALID, "map %d appears twice in the batch", b);
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
+        if ((s = batch_kf_alive(c, m, newkf[b], b)) != OV2_OK) return s;
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
     }
     OV2_HIP(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     job_table JT;
-    ov2_status s = JT.begin(c, B);
-    if (s != OV2_OK) return s;
+    if ((s = JT.begin(c, B)) != OV2_OK) return s;
     int nmax = 0, lmax = 0; unsigned zmax = 0;
     for (int b = 0; b < B; ++b) {
         const ov2_map *m = maps[b];
         map_job j = job_of(m, newkf[b], -1);
-        // the stage's own header and cleared block stand where the kernels shared with the set-up look for them
-        j.hdr = reinterpret_cast<int *>(m->tt_zero); j.zero_blk = m->tt_zero; j.zero_vec16 = (unsigned)(m->tt_zero_bytes / 16);
+        stage_block(j, m->tt_zero, m->tt_zero_bytes);
         j.tt_nobs = m->tt_nobs; j.tt_old = m->tt_old; j.tt_nrow = m->tt_nrow;
         j.tt_arow = m->tt_int; j.tt_good_lmid = m->tt_int + m->max_lm; j.tt_rm_lmid = m->tt_int + 2 * (size_t)m->max_lm;
         j.tt_good_wpt = m->tt_dbl; j.tt_good_inv = m->tt_dbl + 3 * (size_t)m->max_lm;
@@ -1905,13 +1889,12 @@ extern "C" ov2_status ov2_map_filter_keyframes_batch(ov2_ctx *c, int B, ov2_map 
     if (!c) return OV2_ERR_INVALID;
     if (B == 0) return OV2_OK;
     if (B < 0 || !maps || !newkf || !out) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_filter_keyframes_batch: null argument");
+    ov2_status s;
     for (int b = 0; b < B; ++b) {
         const ov2_map *m = maps[b];
-        if (!m || m->c != c) return ov2_set_err(c, OV2_ERR_INVALID, "map %d of the batch is null or belongs to another context", b);
-        if (newkf[b] < 0 || newkf[b] >= m->max_kf || !m->kf_alive_h[newkf[b]])
-            return ov2_set_err(c, OV2_ERR_INVALID, "keyframe %d is not alive in map %d", newkf[b], b);
-        for (int q = 0; q < b; ++q)
-            if (maps[q] == m) return ov2_set_err(c, OV2_ERR_INVALID, "map %d appears twice in the batch", b);
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
+        if ((s = batch_kf_alive(c, m, newkf[b], b)) != OV2_OK) return s;
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
     }
     memset(out, 0, (size_t)B * sizeof(*out));
     // src/estimator.cpp:103-109: the reference's "off" value of the ratio, and no culling before keyframe 20
@@ -1931,15 +1914,12 @@ extern "C" ov2_status ov2_map_filter_keyframes_batch(ov2_ctx *c, int B, ov2_map 
         m->fl_removed_cap = m->max_kf;
     }
     job_table JT;
-    ov2_status s = JT.begin(c, B, kmax);
-    if (s != OV2_OK) return s;
+    if ((s = JT.begin(c, B, kmax)) != OV2_OK) return s;
     for (int b = 0; b < B; ++b) {
         const ov2_map *m = maps[b];
         map_job j = job_of(m, newkf[b], -1);
-        // the stage's own header and cleared block stand where the kernels shared with the set-up look for them
-        j.hdr = reinterpret_cast<int *>(m->fl_zero); j.zero_blk = m->fl_zero;
         j.fl_active = newkf[b] >= 20;
-        j.zero_vec16 = j.fl_active ? (unsigned)(m->fl_zero_bytes / 16) : 0u;
+        stage_block(j, m->fl_zero, j.fl_active ? m->fl_zero_bytes : 0);
         j.fl_nobs = m->fl_nobs; j.fl_cov = m->fl_cov; j.fl_n3d = m->fl_n3d; j.fl_cnt = m->fl_cnt; j.fl_fill = m->fl_fill;
         j.fl_new = m->fl_new; j.fl_start = m->fl_start; j.fl_rows = m->fl_rows; j.fl_unset = m->fl_unset;
         JT.set(b, j);
@@ -2005,16 +1985,16 @@ extern "C" ov2_status ov2_map_restore_state_batch(ov2_ctx *c, int B, ov2_map *co
     if (!c) return OV2_ERR_INVALID;
     if (B == 0) return OV2_OK;
     if (B < 0 || !maps) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_restore_state_batch: null argument");
+    ov2_status s;
     for (int b = 0; b < B; ++b) {
         ov2_map *m = maps[b];
-        if (!m || m->c != c) return ov2_set_err(c, OV2_ERR_INVALID, "map %d of the batch is null or belongs to another context", b);
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
         if (!m->snap_kf_pose || m->snap_kf != m->max_kf || m->snap_lm != m->max_lm || m->snap_obs != m->n_obs)
             return ov2_set_err(c, OV2_ERR_INVALID, "map %d: no saved state, or the tables changed shape since it was saved", b);
     }
     OV2_HIP(c, hipSetDevice(c->device));
     job_table JT;
-    ov2_status s = JT.begin(c, B);
-    if (s != OV2_OK) return s;
+    if ((s = JT.begin(c, B)) != OV2_OK) return s;
     for (int b = 0; b < B; ++b) {
         JT.set(b, job_of(maps[b], -1, -1)); maps[b]->last_valid = 0;
         memcpy(maps[b]->kf_alive_h, maps[b]->snap_kf_alive_h, (size_t)maps[b]->max_kf);

@@ -5,6 +5,7 @@
 // Integer box sums and Hamming distances => bit-exact against the oracle; the float gates are evaluated in its order.
 #include "ov2_internal.h"
 #include "ov2_cam.h"
+#include "ov2_se3.h"
 
 namespace {
 
@@ -71,13 +72,8 @@ struct match_dev {   // device twin of ov2_match_input
 
 __device__ inline void world_to_cam(const double *Twc, const double *p, double c[3])
 {
-    double x = Twc[3], y = Twc[4], z = Twc[5], w = Twc[6];
-    const double n = sqrt(x * x + y * y + z * z + w * w);
-    x /= n; y /= n; z /= n; w /= n;
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    const double R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+    double R[9];
+    ov2se3::pose_R(Twc, R);
     const double d[3] = {p[0] - Twc[0], p[1] - Twc[1], p[2] - Twc[2]};
     for (int r = 0; r < 3; ++r) c[r] = R[r] * d[0] + R[3 + r] * d[1] + R[6 + r] * d[2];
 }

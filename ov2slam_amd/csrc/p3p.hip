@@ -41,6 +41,7 @@
 #include <cstring>
 
 #include "ov2_internal.h"
+#include "ov2_se3.h"
 
 #define HD __host__ __device__
 #include "p3p_model.h"
@@ -246,24 +247,6 @@ __global__ __launch_bounds__(P3P_THREADS) void p3p_score_kernel(p3p_args A)
         A.pen[(size_t)b * A.L + kk] = (n & 1) ? p3p_sqrt(dmid) : (p3p_sqrt(dlow) + p3p_sqrt(dmid)) / 2.;
 }
 
-__device__ inline void p3p_rot_to_quat(const double R[9], double q[4])
-{   // the C++ mirror's SE3::fromRt
-    const double t = R[0] + R[4] + R[8];
-    if (t > 0) {
-        const double s = p3p_sqrt(t + 1.0) * 2;
-        q[3] = 0.25 * s; q[0] = (R[7] - R[5]) / s; q[1] = (R[2] - R[6]) / s; q[2] = (R[3] - R[1]) / s;
-    } else if (R[0] > R[4] && R[0] > R[8]) {
-        const double s = p3p_sqrt(1.0 + R[0] - R[4] - R[8]) * 2;
-        q[3] = (R[7] - R[5]) / s; q[0] = 0.25 * s; q[1] = (R[1] + R[3]) / s; q[2] = (R[2] + R[6]) / s;
-    } else if (R[4] > R[8]) {
-        const double s = p3p_sqrt(1.0 + R[4] - R[0] - R[8]) * 2;
-        q[3] = (R[2] - R[6]) / s; q[0] = (R[1] + R[3]) / s; q[1] = 0.25 * s; q[2] = (R[5] + R[7]) / s;
-    } else {
-        const double s = p3p_sqrt(1.0 + R[8] - R[0] - R[4]) * 2;
-        q[3] = (R[3] - R[1]) / s; q[0] = (R[2] + R[6]) / s; q[1] = (R[5] + R[7]) / s; q[2] = 0.25 * s;
-    }
-}
-
 __global__ __launch_bounds__(P3P_THREADS) void p3p_final_kernel(p3p_args A)
 {
     __shared__ int sh[P3P_THREADS];
@@ -357,7 +340,7 @@ __global__ __launch_bounds__(P3P_THREADS) void p3p_final_kernel(p3p_args A)
         A.status[b] = status;
         if (status) {
             double q[4];
-            p3p_rot_to_quat(m, q);
+            ov2se3::rot_to_quat(m, q);
             for (int e = 0; e < 3; ++e) A.Twc[7 * b + e] = m[9 + e];
             for (int e = 0; e < 4; ++e) A.Twc[7 * b + 3 + e] = q[e];
         }

@@ -11,6 +11,11 @@
 // reduced in a fixed order (DPP row sums -> readlane -> LDS across the 4 waves), and the scalar LM logic is executed
 // redundantly by all threads, so there is no host round trip and no divergence.  The jacobian is never stored.
 #include "ov2_internal.h"
+#include "ov2_se3.h"
+#include "ov2_wave.h"
+
+using namespace ov2se3;    // pose / quaternion arithmetic in the oracle's order (ov2_se3.h)
+using namespace ov2wave;   // fixed-order wave and workgroup sums (ov2_wave.h)
 
 namespace {
 
@@ -19,32 +24,6 @@ struct pnp_params {
     double huber_a, chi2_th, ftol, initial_radius, max_radius, min_radius, min_diag, max_diag, min_rel, ptol;
 };
 
-__device__ __forceinline__ double readlane_d(double v, int lane)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | lo);
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-    v += dpp_d<0xB1>(v);
-    v += dpp_d<0x4E>(v);
-    v += dpp_d<0x141>(v);
-    v += dpp_d<0x140>(v);
-    return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
-}
-
 // acc[K] of every thread -> block totals in every thread
 template <int K>
 __device__ __forceinline__ void block_sum(double *acc, double (*sh)[28])
@@ -52,86 +31,13 @@ __device__ __forceinline__ void block_sum(double *acc, double (*sh)[28])
     const int tid = threadIdx.x;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const double w = wave_sum_d(acc[k]);
+        const double w = wave_sum_f64(acc[k]);
         if ((tid & 63) == 0) sh[tid >> 6][k] = w;
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < K; ++k) acc[k] = (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
     __syncthreads();
-}
-
-__device__ __forceinline__ void quat_R(const double *p, double R[9])
-{
-    double x = p[3], y = p[4], z = p[5], w = p[6];
-    const double n = sqrt(x * x + y * y + z * z + w * w);
-    x /= n; y /= n; z /= n; w /= n;
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
-__device__ inline void se3_plus_d(const double *x, const double *d, double *out)
-{
-    const double *u = d, *w = d + 3;
-    const double eps = 1e-10;
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    double theta, imag, real;
-    if (th2 < eps * eps) {
-        theta = 0.0;
-        const double th4 = th2 * th2;
-        imag = 0.5 - (1.0 / 48.0) * th2 + (1.0 / 3840.0) * th4;
-        real = 1.0 - (1.0 / 8.0) * th2 + (1.0 / 384.0) * th4;
-    } else {
-        theta = sqrt(th2);
-        const double half = 0.5 * theta;
-        imag = sin(half) / theta;
-        real = cos(half);
-    }
-    const double a[7] = {0, 0, 0, imag * w[0], imag * w[1], imag * w[2], real};
-    double Ra[9], V[9];
-    {
-        const double q[7] = {0, 0, 0, a[3], a[4], a[5], a[6]};
-        // exp's quaternion is unit up to rounding; quat_R normalises, the oracle's quat_to_R does not: build it raw
-        const double X = q[3], Y = q[4], Z = q[5], W = q[6];
-        const double tx = 2 * X, ty = 2 * Y, tz = 2 * Z;
-        const double twx = tx * W, twy = ty * W, twz = tz * W, txx = tx * X, txy = ty * X, txz = tz * X;
-        const double tyy = ty * Y, tyz = tz * Y, tzz = tz * Z;
-        Ra[0] = 1 - (tyy + tzz); Ra[1] = txy - twz;       Ra[2] = txz + twy;
-        Ra[3] = txy + twz;       Ra[4] = 1 - (txx + tzz); Ra[5] = tyz - twx;
-        Ra[6] = txz - twy;       Ra[7] = tyz + twx;       Ra[8] = 1 - (txx + tyy);
-    }
-    if (theta < eps) {
-        for (int i = 0; i < 9; ++i) V[i] = Ra[i];
-    } else {
-        const double O[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-        double O2[9];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double s = 0;
-                for (int k = 0; k < 3; ++k) s += O[3 * i + k] * O[3 * k + j];
-                O2[3 * i + j] = s;
-            }
-        const double t2 = theta * theta;
-        const double c1 = (1.0 - cos(theta)) / t2, c2 = (theta - sin(theta)) / (t2 * theta);
-        for (int i = 0; i < 9; ++i) V[i] = ((i % 4 == 0) ? 1.0 : 0.0) + c1 * O[i] + c2 * O2[i];
-    }
-    double b[4] = {x[3], x[4], x[5], x[6]};
-    const double nb = sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2] + b[3] * b[3]);
-    b[0] /= nb; b[1] /= nb; b[2] /= nb; b[3] /= nb;
-    double q[4];
-    q[3] = a[6] * b[3] - a[3] * b[0] - a[4] * b[1] - a[5] * b[2];
-    q[0] = a[6] * b[0] + a[3] * b[3] + a[4] * b[2] - a[5] * b[1];
-    q[1] = a[6] * b[1] + a[4] * b[3] + a[5] * b[0] - a[3] * b[2];
-    q[2] = a[6] * b[2] + a[5] * b[3] + a[3] * b[1] - a[4] * b[0];
-    const double nq = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int r = 0; r < 3; ++r)
-        out[r] = (V[3 * r] * u[0] + V[3 * r + 1] * u[1] + V[3 * r + 2] * u[2]) +
-                 (Ra[3 * r] * x[0] + Ra[3 * r + 1] * x[1] + Ra[3 * r + 2] * x[2]);
-    out[3] = q[0] / nq; out[4] = q[1] / nq; out[5] = q[2] / nq; out[6] = q[3] / nq;
 }
 
 struct pnp_frame {
@@ -148,7 +54,7 @@ __device__ inline void pnp_accumulate(const pnp_frame &F, const double *x, bool 
                                       double *acc)
 {
     double R[9];
-    quat_R(x, R);
+    pose_R(x, R);
 #pragma unroll
     for (int k = 0; k < (JAC ? 28 : 1); ++k) acc[k] = 0.0;
     for (int i = F.i0 + (int)threadIdx.x; i < F.i1; i += 256) {
@@ -290,7 +196,7 @@ __device__ inline int pnp_minimize(const pnp_frame &F, double *T, const pnp_para
         invalid = 0;
         double delta[6], cand[7];
         for (int c = 0; c < 6; ++c) delta[c] = step[c] * scale[c];
-        se3_plus_d(x, delta, cand);
+        se3_plus(x, delta, cand);
         double cacc[1];
         pnp_accumulate<false>(F, cand, use_removed, use_loss, P.huber_a, cacc);
         block_sum<1>(cacc, sh);
@@ -342,7 +248,7 @@ __global__ __launch_bounds__(256) void pnp_kernel(int B, const int *__restrict__
     int term = pnp_minimize(F, T, P, false, P.use_robust, sh, &it1, Te);
     // chi2 / depth flags as the functors cached them at their last evaluation (:551-565)
     double R[9];
-    quat_R(Te, R);
+    pose_R(Te, R);
     int nbad = 0;
     for (int i = F.i0 + tid; i < F.i1; i += 256) {
         const double inv_sigma = 1.0 / (scales ? exp2((double)scales[i]) : 1.0);

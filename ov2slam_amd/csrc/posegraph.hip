@@ -19,6 +19,11 @@
 #include <vector>
 
 #include "ov2_internal.h"
+#include "ov2_se3.h"
+#include "ov2_wave.h"
+
+using namespace ov2se3;    // pose / quaternion arithmetic in the oracle's order (ov2_se3.h)
+using namespace ov2wave;   // fixed-order wave and workgroup sums (ov2_wave.h)
 
 namespace {
 
@@ -39,20 +44,6 @@ struct pg_opt {
 };
 
 struct se3m { double R[9], t[3]; };
-
-__device__ inline void pg_from7(const double *p, se3m &T)
-{
-    double x = p[3], y = p[4], z = p[5], w = p[6];
-    const double n = sqrt(x * x + y * y + z * z + w * w);
-    x /= n; y /= n; z /= n; w /= n;
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    T.R[0] = 1 - (tyy + tzz); T.R[1] = txy - twz;       T.R[2] = txz + twy;
-    T.R[3] = txy + twz;       T.R[4] = 1 - (txx + tzz); T.R[5] = tyz - twx;
-    T.R[6] = txz - twy;       T.R[7] = tyz + twx;       T.R[8] = 1 - (txx + tyy);
-    T.t[0] = p[0]; T.t[1] = p[1]; T.t[2] = p[2];
-}
 
 __device__ inline void pg_mul(const se3m &A, const se3m &B, se3m &C)
 {
@@ -170,9 +161,9 @@ __device__ inline void pg_eval_edge(const pg_dev &d, const double *poses, int e,
 {
     const int i = d.edge_i[e], j = d.edge_j[e];
     se3m T0, T1, T01, T1i, A, E;
-    pg_from7(poses + 7 * i, T0);
-    pg_from7(poses + 7 * j, T1);
-    pg_from7(d.T_ij + 7 * (size_t)e, T01);
+    pose_Rt(poses + 7 * i, T0.R, T0.t);
+    pose_Rt(poses + 7 * j, T1.R, T1.t);
+    pose_Rt(d.T_ij + 7 * (size_t)e, T01.R, T01.t);
     pg_inv(T1, T1i);
     pg_mul(T1i, T0, A);
     pg_mul(A, T01, E);
@@ -189,17 +180,10 @@ __device__ inline void pg_eval_edge(const pg_dev &d, const double *poses, int e,
     pg_jac(r, Pi, 1.0, -1.0, (scaled && fj >= 0) ? d.scale + 6 * fj : nullptr, d.Jj + 36 * (size_t)e);
 }
 
-// fixed-order sum of one value per thread (256 threads), result to every thread
+// fixed-order sum of one value per thread (256 threads), result to every thread; sh is free again on return
 __device__ inline double pg_block_sum(double v, double *sh)
 {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) sh[t] += sh[t + s];
-        __syncthreads();
-    }
-    const double tot = sh[0];
+    const double tot = block_sum_256(v, sh);
     __syncthreads();
     return tot;
 }
@@ -367,66 +351,6 @@ __device__ inline bool pg_solve(const pg_dev &d, int *flag)
     return *flag != 0;
 }
 
-// SE3LeftParameterization::Plus (exp(delta) * x), as pnp.hip / the oracle
-__device__ inline void pg_se3_plus(const double *x, const double *dl, double *out)
-{
-    const double *u = dl, *w = dl + 3;
-    const double eps = 1e-10;
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    double theta, imag, real;
-    if (th2 < eps * eps) {
-        theta = 0.0;
-        const double th4 = th2 * th2;
-        imag = 0.5 - (1.0 / 48.0) * th2 + (1.0 / 3840.0) * th4;
-        real = 1.0 - (1.0 / 8.0) * th2 + (1.0 / 384.0) * th4;
-    } else {
-        theta = sqrt(th2);
-        const double half = 0.5 * theta;
-        imag = sin(half) / theta;
-        real = cos(half);
-    }
-    const double ax = imag * w[0], ay = imag * w[1], az = imag * w[2], aw = real;
-    double Ra[9], V[9];
-    {
-        const double tx = 2 * ax, ty = 2 * ay, tz = 2 * az;
-        const double twx = tx * aw, twy = ty * aw, twz = tz * aw, txx = tx * ax, txy = ty * ax, txz = tz * ax;
-        const double tyy = ty * ay, tyz = tz * ay, tzz = tz * az;
-        Ra[0] = 1 - (tyy + tzz); Ra[1] = txy - twz;       Ra[2] = txz + twy;
-        Ra[3] = txy + twz;       Ra[4] = 1 - (txx + tzz); Ra[5] = tyz - twx;
-        Ra[6] = txz - twy;       Ra[7] = tyz + twx;       Ra[8] = 1 - (txx + tyy);
-    }
-    if (theta < eps) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) V[i] = Ra[i];
-    } else {
-        const double O[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-        const double t2 = theta * theta;
-        const double c1 = (1.0 - cos(theta)) / t2, c2 = (theta - sin(theta)) / (t2 * theta);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                double s = 0;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) s += O[3 * i + k] * O[3 * k + j];
-                V[3 * i + j] = ((i == j) ? 1.0 : 0.0) + c1 * O[3 * i + j] + c2 * s;
-            }
-    }
-    double b0 = x[3], b1 = x[4], b2 = x[5], b3 = x[6];
-    const double nb = sqrt(b0 * b0 + b1 * b1 + b2 * b2 + b3 * b3);
-    b0 /= nb; b1 /= nb; b2 /= nb; b3 /= nb;
-    double q3 = aw * b3 - ax * b0 - ay * b1 - az * b2;
-    double q0 = aw * b0 + ax * b3 + ay * b2 - az * b1;
-    double q1 = aw * b1 + ay * b3 + az * b0 - ax * b2;
-    double q2 = aw * b2 + az * b3 + ax * b1 - ay * b0;
-    const double nq = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-    q0 /= nq; q1 /= nq; q2 /= nq; q3 /= nq;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        out[i] = (V[3 * i] * u[0] + V[3 * i + 1] * u[1] + V[3 * i + 2] * u[2]) + (Ra[3 * i] * x[0] + Ra[3 * i + 1] * x[1] + Ra[3 * i + 2] * x[2]);
-    out[3] = q0; out[4] = q1; out[5] = q2; out[6] = q3;
-}
-
 // out = Plus(x, delta) on the free poses (the other poses are copied); delta = -v (PG_NEG), v * scale (PG_STEP: the step
 // of the scaled problem) or -v / scale (PG_NEG_UNSCALE: the gradient of the unscaled problem from the scaled one)
 enum { PG_NEG = 0, PG_STEP = 1, PG_NEG_UNSCALE = 2 };
@@ -444,7 +368,7 @@ __device__ inline void pg_plus(const pg_dev &d, const double *x, const double *v
                 const double vv = v[6 * f + k], sc = d.scale[6 * f + k];
                 dl[k] = mode == PG_STEP ? vv * sc : (mode == PG_NEG_UNSCALE ? -vv / sc : -vv);
             }
-            pg_se3_plus(x + 7 * i, dl, out + 7 * i);
+            se3_plus(x + 7 * i, dl, out + 7 * i);
         }
     }
     __threadfence_block();

@@ -16,18 +16,13 @@
 //   level_kernel          one pass over level l staged in LDS (64x16 tile + 2-px halo):
 //                         writes Scharr(l) as 16-byte stores and pyrDown(l) -> level l+1 (+ its reflect border)
 #include "ov2_internal.h"
+#include "ov2_wave.h"
+
+using ov2wave::reflect101;
 
 namespace {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int reflect101(int i, int n)
-{
-    // one reflection is enough for |overshoot| < n (callers guarantee it)
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-    return i;
-}
 
 __device__ __forceinline__ unsigned char sat_u8_rn(float v)
 {

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void tri_kernel(tri_args A)
     g = min(max(g, 0), A.G - 1);   // validated on the host for host arrays; clamped for device-resident ones
     const double *T = A.T_ab + 7 * g;
     double R[9];
-    quat_R(T, R);
+    ov2se3::tri_quat_R(T, R);
     const double f1[3] = {A.bv_a[3 * i], A.bv_a[3 * i + 1], A.bv_a[3 * i + 2]};
     const double f2[3] = {A.bv_b[3 * i], A.bv_b[3 * i + 1], A.bv_b[3 * i + 2]};
     double f2u[3];
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void tri_kernel(tri_args A)
     for (int k = 0; k < 3; ++k) A.pt_a[3 * i + k] = X[k];
     if (A.wpt) {
         double w[3];
-        to_world(A.Twc_a + 7 * g, X, w);
+        ov2se3::tri_apply(A.Twc_a + 7 * g, X, w);   // Frame::projCamToWorld: Twc_a * X
 #pragma unroll
         for (int k = 0; k < 3; ++k) A.wpt[3 * i + k] = w[k];
     }

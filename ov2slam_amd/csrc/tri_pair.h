@@ -1,21 +1,15 @@
 // tri_pair.h -- the per-pair arithmetic of the mapper's two triangulation stages as device functions, shared by
 // tri_kernel (tri.hip: pairs handed in as flat arrays) and the temporal stage on the map mirror (map.hip: pairs read off
 // the observation table).  Arithmetic and operation order are those of oracle/ov2_oracle_tri.c (f64, contraction off);
-// every R[9] / X[3] is indexed statically so that nothing spills to private memory.
+// every R[9] / X[3] is indexed statically so that nothing spills to private memory.  The pose arithmetic (tri_quat_R,
+// tri_apply) is in ov2_se3.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/ov2slam_hip.h"
+#include "ov2_se3.h"
 
 namespace ov2tri {
-
-__device__ __forceinline__ void quat_R(const double *T, double R[9])
-{
-    const double x = T[3], y = T[4], z = T[5], w = T[6];
-    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z);     R[2] = 2 * (x * z + w * y);
-    R[3] = 2 * (x * y + w * z);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
-    R[6] = 2 * (x * z - w * y);     R[7] = 2 * (y * z + w * x);     R[8] = 1 - 2 * (x * x + y * y);
-}
 
 // CameraCalibration::projectCamToImage (src/camera_calibration.cpp:243-252)
 __device__ __forceinline__ void project(const double K[4], const double p[3], float &u, float &v)
@@ -80,16 +74,6 @@ __device__ __forceinline__ int gates(const double *T, const double R[9], const d
     project(Kb, Xb, qu, qv);
     const float ldist = (float)norm2f(pu, pv, ua, va), rdist = (float)norm2f(qu, qv, ub, vb);
     return (ldist > max_err || rdist > max_err) ? OV2_TRI_REPROJ : OV2_TRI_OK;
-}
-
-// Frame::projCamToWorld: Twc_a * X
-__device__ __forceinline__ void to_world(const double *W, const double X[3], double out[3])
-{
-    double Rw[9];
-    quat_R(W, Rw);
-    out[0] = Rw[0] * X[0] + Rw[1] * X[1] + Rw[2] * X[2] + W[0];
-    out[1] = Rw[3] * X[0] + Rw[4] * X[1] + Rw[5] * X[2] + W[1];
-    out[2] = Rw[6] * X[0] + Rw[7] * X[1] + Rw[8] * X[2] + W[2];
 }
 
 }  // namespace ov2tri
