@@ -459,6 +459,44 @@ ov2_status ov2_p3p_ransac_batch_dev(ov2_ctx *ctx, int B, const int32_t *d_off, c
                                     double *d_Twc, uint8_t *d_outlier, int32_t *d_status, int32_t *d_info);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Loop-candidate matching: the two nearest neighbours of every query descriptor among the train descriptors of its pair, by
+ * Hamming distance over 32 bytes, all against all.
+ * Replaces cv::BFMatcher(cv::NORM_HAMMING).knnMatch(query, train, vmatches, 2) of LoopCloser::knnMatching
+ * (src/loop_closer.cpp:426-428; query = descriptors of the new keyframe's map points, train = those of the candidate's).
+ * B independent pairs per call; pair b owns n_query[b] consecutive rows of `query` and n_train[b] consecutive rows of
+ * `train`.  All pointers are HOST pointers; one synchronisation.
+ *   query   sum(n_query) x 32   train   sum(n_train) x 32   one BRIEF-32 descriptor per row
+ *   idx     sum(n_query) x 2    train row of neighbour 0 / 1, counted from the first train row of the query's OWN pair
+ *   dist    sum(n_query) x 2    their Hamming distances (0 .. 256)
+ * Neighbours 0 and 1 of a query are the two train rows of its pair with the smallest (distance, row) in lexicographic order:
+ * of two rows at the same distance the lower row comes first.  That is what cv::batchDistance keeps for K = 2 (a candidate
+ * displaces a kept one only on a strictly smaller distance, so the earlier row wins a tie).  OpenCV is not vendored by the
+ * reference, so the rule is restated from its published source, and its parity with a built OpenCV is not pinned by a test.
+ * A neighbour that does not exist (n_train[b] of 0 or 1) is idx = -1, dist = -1.  A pair with n_query[b] = 0 writes nothing;
+ * B = 0 is OV2_OK.  Only integers are involved: the results are bit-identical whatever the composition of the batch, the
+ * lane mapping (ov2_knn_set_lanes) and the form (host or _dev).
+ * Limits, refused with OV2_ERR_INVALID beyond them (as are negative counts and null arrays that a non-empty call needs):
+ * n_train[b] <= OV2_KNN_MAX_TRAIN (the row index shares a 32-bit key with the distance), sum(n_query) and sum(n_train)
+ * <= OV2_KNN_MAX_ROWS, B <= OV2_KNN_MAX_BATCH.  OV2_KNN_TILE is the number of train rows that pass through LDS at a time
+ * (no limit; tests place their sizes around it). */
+#define OV2_KNN_MAX_TRAIN 65536
+#define OV2_KNN_MAX_ROWS (1 << 24)
+#define OV2_KNN_MAX_BATCH 65535
+#define OV2_KNN_TILE 1024
+ov2_status ov2_knn2_hamming_batch(ov2_ctx *ctx, int B, const int *n_query, const int *n_train, const uint8_t *query,
+                                  const uint8_t *train, int32_t *idx, int32_t *dist);
+/* device-resident, asynchronous form: d_q_off / d_t_off = B + 1 prefix offsets (rows) of the pairs' query / train blocks, every
+ * other array as above but in HBM, d_query and d_train 16-byte aligned (else OV2_ERR_INVALID).  total_query = d_q_off[B],
+ * given by the host because it sizes the grid: rows at or beyond min(total_query, d_q_off[B]) are not written.  Nothing is
+ * synchronised or read back, so the per-pair limit cannot be refused here: train rows of a pair beyond OV2_KNN_MAX_TRAIN are
+ * not looked at. */
+ov2_status ov2_knn2_hamming_batch_dev(ov2_ctx *ctx, int B, int total_query, const int32_t *d_q_off, const int32_t *d_t_off,
+                                      const uint8_t *d_query, const uint8_t *d_train, int32_t *d_idx, int32_t *d_dist);
+/* Lanes that share one query and split its train rows between them: 1, 4, 16 or 64 forces that mapping (tests, tuning; all
+ * give the same bits), 0 (default) picks by the number of query rows of the call.  Anything else is OV2_ERR_INVALID. */
+ov2_status ov2_knn_set_lanes(ov2_ctx *ctx, int lanes);
+
+/* ---------------------------------------------------------------------------------------------------
  * Pose graphs: Optimizer::localPoseGraph (src/optimizer.cpp:2346-2592, the loop closer's chain of
  * keyframes loop .. new + the loop edge) and Optimizer::fullPoseGraph (:2783-2870, the chain of all frames between
  * constant keyframes at the end of a run) = LeftSE3RelativePoseError (src/ceres_parametrization.cpp:30-102,

@@ -108,6 +108,9 @@ SIGNATURES = {
     "ov2_p3p_ransac_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
     "ov2_p3p_ransac_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
     "ov2_dbg_p3p": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+    "ov2_knn2_hamming_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "ov2_knn2_hamming_batch_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "ov2_knn_set_lanes": (C.c_int, [vp, C.c_int]),
 }
 
 _lib = None

@@ -49,6 +49,8 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     c->tmp_img = nullptr;
     c->ktime_on = false;
     c->klt_lanes = 0;
+    c->knn_lanes = 0;
+    c->knn_cus = 0;
     c->ba_arena = nullptr;
     c->ba_arena_cap = 0;
     c->ba_host = nullptr;
@@ -320,7 +322,7 @@ const char *ov2_kernel_names[OV2_K_MAX] = {"clahe_lut_kernel", "level0_kernel", 
                                            "detect_list_kernels", "map_setup_kernels", "tri_kernel", "stereo_sad_kernel",
                                            "stereo_gate_kernel", "brief_kernel", "match_kernels", "pose_graph_kernel",
                                            "epipolar_kernel", "fivept_dbg_kernel", "p3p_solve_kernel", "p3p_select_kernel",
-                                           "p3p_score_kernel", "p3p_final_kernel", "p3p_dbg_kernel"};
+                                           "p3p_score_kernel", "p3p_final_kernel", "p3p_dbg_kernel", "knn2_kernel"};
 
 static hipEvent_t ktime_event(ov2_ctx *c)
 {

@@ -127,6 +127,8 @@ struct ov2_ctx {
     hipStream_t ba_copy_stream;          // second half of a batch upload (measurements) travels here while the program build sorts
     hipEvent_t ba_copy_ev[2];            // [0] head uploaded (main stream), [1] measurements uploaded (copy stream)
     int klt_lanes;                       // ov2_klt_set_lanes: 0 = by call size, 3 / 8 / 16 = forced lanes per keypoint
+    int knn_lanes;                       // ov2_knn_set_lanes: 0 = by call size, 1 / 4 / 16 / 64 = forced lanes per query
+    int knn_cus;                         // compute units of the device (read on first use by the matcher's automatic choice)
     // optional per-kernel hipEvent timing (bench.py roofline leg); off by default
     bool ktime_on;
     std::vector<ov2_ktime_rec> ktime_recs;   // recorded (kernel id, event pair) since the last report

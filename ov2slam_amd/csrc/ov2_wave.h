@@ -1,7 +1,7 @@
 // ov2_wave.h -- the fixed-order wave / workgroup reductions of the kernels, written once.  Every sum that has to round
 // like the oracle's is a tree of a fixed shape, so the shape lives here: DPP moves inside a row of 16 lanes, readlane
-// across the four rows of a wave, LDS across the waves of a 256-thread workgroup.  The border index that the image kernels
-// share stands at the end.
+// across the four rows of a wave, LDS across the waves of a 256-thread workgroup.  The two-smallest-keys reduction of the
+// descriptor matcher uses the same moves.  The border index that the image kernels share stands at the end.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,6 +60,40 @@ __device__ __forceinline__ double wave_sum_f64(double v)
 {
     v = row_sum_f64<16>(v);
     return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+}
+
+// The two smallest of the keys that the GW (4 | 16) lanes of a lane group inside a DPP row hold, two per lane (lo <= hi), to
+// every lane of the group.  Exact and order-free as long as the keys of a group are distinct (a filler above every key, such
+// as INT_MAX, may repeat): the smallest of a union is the smaller of the two lows, the second the smaller of the larger
+// low and the two highs.  Each step pairs disjoint sets of lanes (after the quad steps a quad agrees).
+__device__ __forceinline__ void min2_merge_i32(int &lo, int &hi, int olo, int ohi)
+{
+    hi = min(max(lo, olo), min(hi, ohi));
+    lo = min(lo, olo);
+}
+
+template <int GW>
+__device__ __forceinline__ void row_min2_i32(int &lo, int &hi)
+{
+    static_assert(GW == 4 || GW == 16, "a lane group is a quad or a whole DPP row");
+    min2_merge_i32(lo, hi, dpp_i32<0xB1>(lo), dpp_i32<0xB1>(hi));
+    min2_merge_i32(lo, hi, dpp_i32<0x4E>(lo), dpp_i32<0x4E>(hi));
+    if (GW == 16) {
+        min2_merge_i32(lo, hi, dpp_i32<0x141>(lo), dpp_i32<0x141>(hi));
+        min2_merge_i32(lo, hi, dpp_i32<0x140>(lo), dpp_i32<0x140>(hi));
+    }
+}
+
+// the same over the 64 lanes of a wave, wave-uniform: the four rows merged as (l0, l16), (l32, l48)
+__device__ __forceinline__ void wave_min2_i32(int &lo, int &hi)
+{
+    row_min2_i32<16>(lo, hi);
+    int alo = __builtin_amdgcn_readlane(lo, 0), ahi = __builtin_amdgcn_readlane(hi, 0);
+    min2_merge_i32(alo, ahi, __builtin_amdgcn_readlane(lo, 16), __builtin_amdgcn_readlane(hi, 16));
+    int blo = __builtin_amdgcn_readlane(lo, 32), bhi = __builtin_amdgcn_readlane(hi, 32);
+    min2_merge_i32(blo, bhi, __builtin_amdgcn_readlane(lo, 48), __builtin_amdgcn_readlane(hi, 48));
+    min2_merge_i32(alo, ahi, blo, bhi);
+    lo = alo; hi = ahi;
 }
 
 // Ordered sum of one double per thread of a 256-thread workgroup through sh[256], total to every thread.  No barrier

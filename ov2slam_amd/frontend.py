@@ -44,6 +44,10 @@ class Context:
         """ov2_klt_set_lanes: 0 = by call size, 3 / 8 / 16 = lanes per keypoint in the tracking kernels"""
         _check(self.h, self.lib.ov2_klt_set_lanes(self.h, int(lanes)))
 
+    def set_knn_lanes(self, lanes):
+        """ov2_knn_set_lanes: 0 = by call size, 1 / 4 / 16 / 64 = lanes per query in the loop-candidate matcher"""
+        _check(self.h, self.lib.ov2_knn_set_lanes(self.h, int(lanes)))
+
     def set_kf_overlap(self, on):
         """ov2_ctx_set_kf_overlap: the keyframe detector chain on the side stream, beside stereo matching (default on)"""
         _check(self.h, self.lib.ov2_ctx_set_kf_overlap(self.h, int(bool(on))))

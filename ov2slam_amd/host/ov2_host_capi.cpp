@@ -185,6 +185,121 @@ int ov2h_map_filtering(void *p, int newkf, int nmin_covscore, float ratio, int c
     return (int)fs.removed.size();
 }
 
+// ---- loop-candidate matching (ov2::LoopCloser, the 2D-2D half of processLoopCandidate) ----
+// MapPoint::addDesc(kfid, desc) on landmark lmid: the descriptor keyframe kfid holds of it (the first one becomes desc_)
+int ov2h_map_add_desc(void *p, int lmid, int kfid, const uint8_t *desc32)
+{
+    auto lm = ((HostMap *)p)->map->getMapPoint(lmid);
+    if (!lm) return -1;
+    Desc d;
+    std::copy(desc32, desc32 + 32, d.begin());
+    lm->addDesc(kfid, d);
+    return 0;
+}
+
+// Frame::map_covkfs_[other] = score on keyframe kfid (the covisibility gate of processLoopCandidate reads it)
+int ov2h_map_set_covscore(void *p, int kfid, int other, int score)
+{
+    auto f = ((HostMap *)p)->map->getKeyframe(kfid);
+    if (!f) return -1;
+    f->map_covkfs_[other] = score;
+    return 0;
+}
+
+// what LoopCloser::knnMatching assembles for the pair (newkf, lckf) in front of the matcher, no GPU context needed: query
+// lmids, train lmids and identity pairs (one lmid each) in the mirror's own iteration order, capacity cap each; n[3] = their
+// counts.  query_desc / train_desc (cap x 32, may be NULL): the rows the matcher would receive
+int ov2h_loop_assemble(void *p, int newkf, int lckf, int cap, int *n, int *query_lmid, int *train_lmid, int *identity_lmid,
+                       uint8_t *query_desc, uint8_t *train_desc)
+{
+    HostMap *m = (HostMap *)p;
+    auto a = m->map->getKeyframe(newkf), b = m->map->getKeyframe(lckf);
+    if (!a || !b) return (int)OV2_ERR_INVALID;
+    LoopCloser lc(nullptr, m->st, m->map);
+    LoopKnnInputs in;
+    lc.assembleKnn(*a, *b, in);
+    n[0] = (int)in.vkpids.size(); n[1] = (int)in.vlmids.size(); n[2] = (int)in.vkplmids.size();
+    if (n[0] > cap || n[1] > cap || n[2] > cap) return (int)OV2_ERR_INVALID;
+    std::copy(in.vkpids.begin(), in.vkpids.end(), query_lmid);
+    std::copy(in.vlmids.begin(), in.vlmids.end(), train_lmid);
+    for (int i = 0; i < n[2]; ++i) identity_lmid[i] = in.vkplmids[i].first;
+    if (query_desc) std::copy(in.query.begin(), in.query.end(), query_desc);
+    if (train_desc) std::copy(in.train.begin(), in.train.end(), train_desc);
+    return 0;
+}
+
+// LoopCloser::acceptMatch (the ratio test of knnMatching, :434-442); d1 < 0 = fewer than two neighbours
+int ov2h_loop_accept(int d0, int d1) { return LoopCloser::acceptMatch(d0, d1) ? 1 : 0; }
+
+// LoopCloser::removeOutliers (:899-928) on n pairs with n_out outlier indices; pairs (n x 2) is rewritten in place; returns
+// the number of pairs left
+int ov2h_loop_remove_outliers(int n, int *pairs, int n_out, const int *outliers)
+{
+    std::vector<std::pair<int, int>> v((size_t)n);
+    for (int i = 0; i < n; ++i) v[i] = {pairs[2 * i], pairs[2 * i + 1]};
+    std::vector<int> o(outliers, outliers + n_out);
+    LoopCloser::removeOutliers(v, o);
+    for (size_t i = 0; i < v.size(); ++i) { pairs[2 * i] = v[i].first; pairs[2 * i + 1] = v[i].second; }
+    return (int)v.size();
+}
+
+// LoopCloser::processLoopCandidate (:184-236 as written, one pair, a launch and a synchronisation per stage).  out[5]: branch,
+// candidate used, pairs before the filter, outliers, pairs after it; success: the filter's bool (-1 = not reached);
+// pairs_knn / pairs_out (cap x 2): the two lists.  Returns 0 or a negative ov2_status
+int ov2h_loop_candidate(void *p, void *ctx, int newkf, int lckf, unsigned long long seed, int nransac_iter, float fransac_err, int cap,
+                        int *out, int *success, int *pairs_knn, int *pairs_out)
+{
+    HostMap *m = (HostMap *)p;
+    m->st->nransac_iter_ = nransac_iter; m->st->fransac_err_ = fransac_err;
+    LoopCloser lc((ov2_ctx *)ctx, m->st, m->map);
+    LoopPairResult r;
+    const ov2_status s = lc.processLoopCandidate(newkf, lckf, (uint64_t)seed, r);
+    if (s != OV2_OK) return (int)s;
+    if (r.vkplmids_knn.size() > (size_t)cap) return (int)OV2_ERR_INVALID;
+    out[0] = r.branch; out[1] = r.lckfid; out[2] = (int)r.vkplmids_knn.size(); out[3] = r.n_outliers; out[4] = (int)r.vkplmids.size();
+    *success = r.epi_status;
+    for (size_t i = 0; i < r.vkplmids_knn.size(); ++i) { pairs_knn[2 * i] = r.vkplmids_knn[i].first; pairs_knn[2 * i + 1] = r.vkplmids_knn[i].second; }
+    for (size_t i = 0; i < r.vkplmids.size(); ++i) { pairs_out[2 * i] = r.vkplmids[i].first; pairs_out[2 * i + 1] = r.vkplmids[i].second; }
+    return 0;
+}
+
+// LoopCloser::matchLoopCandidates on B pairs (newkf[b], lckf[b]) with one sampler seed each; nransac_iter / fransac_err as the
+// YAML keys.  Per pair: branch (ov2::LoopBranch); counts (B x 8): candidate used, identity pairs, query rows, train rows, pairs
+// before the filter, outliers, pairs after the filter, epipolar status (-1 = not offered); info (B x 4): the filter's info; Rt
+// (B x 12): R then t where the status is >= 1.  pairs_knn / pairs_out (cap x 2 each): the lists before / after the filter,
+// pair after pair.  stats[5]: pairs, offered to the matcher, offered to the filter, matcher launches, filter launches.
+// Returns 0 or a negative ov2_status (OV2_ERR_INVALID also when cap is too small)
+int ov2h_loop_match(void *p, void *ctx, int B, const int *newkf, const int *lckf, const unsigned long long *seeds, int nransac_iter,
+                    float fransac_err, int cap, int *branch, int *counts, int *info, double *Rt, int *pairs_knn, int *pairs_out,
+                    int *stats)
+{
+    HostMap *m = (HostMap *)p;
+    m->st->nransac_iter_ = nransac_iter; m->st->fransac_err_ = fransac_err;
+    LoopCloser lc((ov2_ctx *)ctx, m->st, m->map);
+    std::vector<std::pair<int, int>> pairs((size_t)B);
+    std::vector<uint64_t> sd((size_t)B);
+    for (int b = 0; b < B; ++b) { pairs[b] = {newkf[b], lckf[b]}; sd[b] = (uint64_t)seeds[b]; }
+    std::vector<LoopPairResult> out;
+    const ov2_status s = lc.matchLoopCandidates(pairs, sd, out);
+    if (s != OV2_OK) return (int)s;
+    size_t ok = 0, oo = 0;
+    for (int b = 0; b < B; ++b) {
+        const LoopPairResult &r = out[b];
+        if (ok + r.vkplmids_knn.size() > (size_t)cap || oo + r.vkplmids.size() > (size_t)cap) return (int)OV2_ERR_INVALID;
+        branch[b] = r.branch;
+        int *c = counts + 8 * b;
+        c[0] = r.lckfid; c[1] = r.n_identity; c[2] = r.n_query; c[3] = r.n_train; c[4] = (int)r.vkplmids_knn.size();
+        c[5] = r.n_outliers; c[6] = (int)r.vkplmids.size(); c[7] = r.epi_status;
+        std::copy(r.epi_info, r.epi_info + 4, info + 4 * b);
+        std::copy(r.R, r.R + 9, Rt + 12 * b); std::copy(r.t, r.t + 3, Rt + 12 * b + 9);
+        for (const auto &q : r.vkplmids_knn) { pairs_knn[2 * ok] = q.first; pairs_knn[2 * ok + 1] = q.second; ++ok; }
+        for (const auto &q : r.vkplmids) { pairs_out[2 * oo] = q.first; pairs_out[2 * oo + 1] = q.second; ++oo; }
+    }
+    stats[0] = lc.last_.pairs; stats[1] = lc.last_.knn_pairs; stats[2] = lc.last_.epi_pairs; stats[3] = lc.last_.knn_calls;
+    stats[4] = lc.last_.epi_calls;
+    return 0;
+}
+
 // The bookkeeping of a host map that ov2h_map_export does not show, as flat lists (call with zero capacities for the sizes
 // n[3]): per landmark (lmid, MapPoint::kfid_, is3d_, isobs_), the observer sets as (lmid, kfid) pairs, and Frame::map_covkfs_
 // of every keyframe as (kfid, covisible kfid, count) triples

@@ -731,4 +731,242 @@ ov2_status SlamManager::fixedWindowBA()
     return OV2_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- LoopCloser (2D-2D half)
+void LoopCloser::assembleKnn(const Frame &newkf, const Frame &lckf, LoopKnnInputs &in) const
+{   // src/loop_closer.cpp:380-420
+    in.vkpids.reserve(newkf.nb3dkps_); in.vlmids.reserve(newkf.nb3dkps_);
+    for (const auto &kp : newkf.getKeypoints()) {                                       // :391
+        if (lckf.isObservingKp(kp.lmid_) && kp.is3d_) {                                 // :393
+            in.vkplmids.push_back(std::pair<int, int>(kp.lmid_, kp.lmid_));
+        } else {
+            auto plm = pmap_->getMapPoint(kp.lmid_);                                    // :397
+            if (plm == nullptr) continue;
+            else if (plm->has_desc_) {                                                  // :400 !plm->desc_.empty()
+                in.query.insert(in.query.end(), plm->desc_.begin(), plm->desc_.end());
+                in.vkpids.push_back(kp.lmid_);
+            }
+        }
+    }
+    for (const auto &kp : lckf.getKeypoints3d()) {                                      // :407
+        if (newkf.isObservingKp(kp.lmid_)) continue;
+        auto plm = pmap_->getMapPoint(kp.lmid_);                                        // :412
+        if (plm == nullptr) continue;
+        else if (plm->has_desc_) {
+            in.train.insert(in.train.end(), plm->desc_.begin(), plm->desc_.end());
+            in.vlmids.push_back(kp.lmid_);
+        }
+    }
+}
+
+bool LoopCloser::acceptMatch(int d0, int d1)
+{   // :430-442.  DMatch::distance is a float; `distance * 0.85` is float * double, evaluated and compared in double
+    const int maxdist = (int)(32 * 0.5 * 8.);   // query.cols * 0.5 * 8.
+    if (d1 < 0) return true;                    // m.size() < 2
+    const float f0 = (float)d0, f1 = (float)d1;
+    return f0 <= maxdist && (double)f0 <= (double)f1 * 0.85;
+}
+
+void LoopCloser::acceptMatches(const LoopKnnInputs &in, const int32_t *idx, const int32_t *dist, std::vector<std::pair<int, int>> &vkplmids)
+{   // :432-449 (a query without any neighbour cannot occur: the train set is not empty)
+    for (size_t q = 0; q < in.vkpids.size(); ++q) {
+        if (idx[2 * q] < 0) continue;
+        if (acceptMatch(dist[2 * q], idx[2 * q + 1] < 0 ? -1 : dist[2 * q + 1]))
+            vkplmids.push_back(std::pair<int, int>(in.vkpids.at(q), in.vlmids.at((size_t)idx[2 * q])));
+    }
+}
+
+ov2_status LoopCloser::knnMatching(const Frame &newkf, const Frame &lckf, std::vector<std::pair<int, int>> &vkplmids)
+{   // :378-459
+    LoopKnnInputs in;
+    assembleKnn(newkf, lckf, in);
+    vkplmids.insert(vkplmids.end(), in.vkplmids.begin(), in.vkplmids.end());
+    if (in.vkpids.empty() || in.vlmids.empty()) return OV2_OK;                          // :422
+    const int nq = (int)in.vkpids.size(), nt = (int)in.vlmids.size();
+    std::vector<int32_t> idx(2 * (size_t)nq), dist(2 * (size_t)nq);
+    const ov2_status s = ov2_knn2_hamming_batch(ctx_, 1, &nq, &nt, in.query.data(), in.train.data(), idx.data(), dist.data());   // :426-428
+    if (s != OV2_OK) return s;
+    acceptMatches(in, idx.data(), dist.data(), vkplmids);
+    return OV2_OK;
+}
+
+bool LoopCloser::epipolarFiltering(const Frame &newkf, const Frame &lckf, std::vector<std::pair<int, int>> &vkplmids,
+                                   std::vector<int> &voutliers_idx, uint64_t seed, ov2_status *st)
+{   // :462-499
+    double R[9], t[3];
+    std::vector<Vec3> vlcbvs, vcurbvs;
+    vlcbvs.reserve(vkplmids.size()); vcurbvs.reserve(vkplmids.size());
+    for (const auto &kplmid : vkplmids) {                                               // :474-480
+        vcurbvs.push_back(newkf.getKeypointById(kplmid.first).bv_);
+        vlcbvs.push_back(lckf.getKeypointById(kplmid.second).bv_);
+    }
+    return MultiViewGeometry::compute5ptEssentialMatrix(ctx_, vlcbvs, vcurbvs, 10 * pslamstate_->nransac_iter_, pslamstate_->fransac_err_,
+                                                        false, seed, (float)newkf.pcalib_leftcam_->fx_, (float)newkf.pcalib_leftcam_->fy_,
+                                                        R, t, voutliers_idx, st);       // :482-491
+}
+
+void LoopCloser::removeOutliers(std::vector<std::pair<int, int>> &vkplmids, std::vector<int> &voutliers_idx)
+{   // :899-928
+    if (voutliers_idx.empty()) return;
+    const size_t nbkps = vkplmids.size();
+    std::vector<std::pair<int, int>> vkplmidstmp;
+    vkplmidstmp.reserve(nbkps);
+    size_t j = 0;
+    for (size_t i = 0; i < nbkps; i++) {
+        if ((int)i != voutliers_idx.at(j)) {
+            vkplmidstmp.push_back(vkplmids.at(i));
+        } else {
+            j++;
+            if (j == voutliers_idx.size()) {
+                j = 0;
+                voutliers_idx.at(0) = -1;
+            }
+        }
+    }
+    vkplmids.swap(vkplmidstmp);
+    voutliers_idx.clear();
+}
+
+ov2_status LoopCloser::processLoopCandidate(int newkfid, int lckfid, uint64_t seed, LoopPairResult &r)
+{   // :184-236
+    r = LoopPairResult();
+    auto pnewkf = pmap_->getKeyframe(newkfid);
+    if (!pnewkf) return OV2_ERR_INVALID;
+    int kfid = lckfid;
+    auto plckf = pmap_->getKeyframe(kfid);
+    while (plckf == nullptr) {                                                          // :192-195
+        if (--kfid < 0) return OV2_ERR_INVALID;
+        plckf = pmap_->getKeyframe(kfid);
+    }
+    r.lckfid = kfid;
+    auto cov_map = pnewkf->getCovisibleKfMap();                                         // :201-209
+    auto it = cov_map.find(kfid);
+    if (it != cov_map.end()) {
+        if (it->second > 30) { r.branch = LC_COVISIBLE; return OV2_OK; }
+    }
+    std::vector<std::pair<int, int>> vkplmids;
+    ov2_status s = knnMatching(*pnewkf, *plckf, vkplmids);                              // :215
+    if (s != OV2_OK) return s;
+    r.vkplmids_knn = vkplmids;
+    r.branch = LC_FEW_MATCHES;
+    if (vkplmids.size() < 15) return OV2_OK;                                            // :217
+    std::vector<int> voutliers_idx;
+    bool success = epipolarFiltering(*pnewkf, *plckf, vkplmids, voutliers_idx, seed, &s);   // :223
+    if (s != OV2_OK) return s;
+    r.epi_status = success ? 1 : 0;
+    r.n_outliers = (int)voutliers_idx.size();
+    size_t nbinliers = vkplmids.size() - voutliers_idx.size();                          // :225
+    r.branch = LC_FILTER_FAILED;
+    if (!success || nbinliers < 10) return OV2_OK;                                      // :227
+    if (!voutliers_idx.empty()) removeOutliers(vkplmids, voutliers_idx);                // :233-236
+    r.vkplmids = vkplmids;
+    r.branch = LC_PASSED;
+    return OV2_OK;
+}
+
+ov2_status LoopCloser::matchLoopCandidates(const std::vector<std::pair<int, int>> &pairs, const std::vector<uint64_t> &seeds,
+                                           std::vector<LoopPairResult> &out)
+{   // :184-236, B pairs at a time
+    const size_t B = pairs.size();
+    if (seeds.size() != B) return OV2_ERR_INVALID;
+    out.assign(B, LoopPairResult());
+    last_ = LoopStats();
+    last_.pairs = (int)B;
+    std::vector<std::shared_ptr<Frame>> vnew(B), vlc(B);
+    std::vector<LoopKnnInputs> vin(B);
+    std::vector<int> knn_of;                      // pairs that reach the matcher
+    std::vector<int> nq, nt;
+    std::vector<uint8_t> query, train;
+    for (size_t b = 0; b < B; ++b) {
+        LoopPairResult &r = out[b];
+        vnew[b] = pmap_->getKeyframe(pairs[b].first);
+        if (!vnew[b]) return OV2_ERR_INVALID;
+        int kfid = pairs[b].second;
+        auto plckf = pmap_->getKeyframe(kfid);
+        while (plckf == nullptr) {                                                      // :192-195
+            if (--kfid < 0) return OV2_ERR_INVALID;
+            plckf = pmap_->getKeyframe(kfid);
+        }
+        vlc[b] = plckf; r.lckfid = kfid;
+        const auto cov_map = vnew[b]->getCovisibleKfMap();                              // :201-209
+        const auto it = cov_map.find(kfid);
+        if (it != cov_map.end() && it->second > 30) { r.branch = LC_COVISIBLE; continue; }
+        r.branch = LC_FEW_MATCHES;
+        LoopKnnInputs &in = vin[b];
+        assembleKnn(*vnew[b], *plckf, in);                                              // :215 -> :380-420
+        r.n_identity = (int)in.vkplmids.size();
+        r.vkplmids_knn = in.vkplmids;
+        if (in.vkpids.empty() || in.vlmids.empty()) continue;                           // :422
+        r.n_query = (int)in.vkpids.size(); r.n_train = (int)in.vlmids.size();
+        knn_of.push_back((int)b);
+        nq.push_back(r.n_query); nt.push_back(r.n_train);
+        query.insert(query.end(), in.query.begin(), in.query.end());
+        train.insert(train.end(), in.train.begin(), in.train.end());
+    }
+    last_.knn_pairs = (int)knn_of.size();
+    if (!knn_of.empty()) {                                                              // :426-428, all pairs in one call
+        std::vector<int32_t> idx(query.size() / 16), dist(query.size() / 16);
+        const ov2_status s = ov2_knn2_hamming_batch(ctx_, (int)knn_of.size(), nq.data(), nt.data(), query.data(), train.data(),
+                                                    idx.data(), dist.data());
+        if (s != OV2_OK) return s;
+        last_.knn_calls = 1;
+        size_t o = 0;
+        for (size_t k = 0; k < knn_of.size(); ++k) {
+            acceptMatches(vin[knn_of[k]], idx.data() + 2 * o, dist.data() + 2 * o, out[knn_of[k]].vkplmids_knn);   // :430-449
+            o += (size_t)nq[k];
+        }
+    }
+    std::vector<int> epi_of, npairs;              // pairs that reach the filter
+    std::vector<double> bvkf, bvcur, K;
+    std::vector<uint64_t> eseed;
+    for (size_t b = 0; b < B; ++b) {
+        LoopPairResult &r = out[b];
+        if (r.branch == LC_COVISIBLE || r.vkplmids_knn.size() < 15) continue;           // :217
+        r.branch = LC_FILTER_FAILED;
+        epi_of.push_back((int)b);
+        npairs.push_back((int)r.vkplmids_knn.size());
+        for (const auto &kplmid : r.vkplmids_knn) {                                     // :474-480
+            const Vec3 c = vnew[b]->getKeypointById(kplmid.first).bv_, l = vlc[b]->getKeypointById(kplmid.second).bv_;
+            bvcur.insert(bvcur.end(), {c.x, c.y, c.z});
+            bvkf.insert(bvkf.end(), {l.x, l.y, l.z});
+        }
+        // compute5ptEssentialMatrix takes fx, fy as floats and passes no principal point (ov2_host.cpp)
+        K.insert(K.end(), {(double)(float)vnew[b]->pcalib_leftcam_->fx_, (double)(float)vnew[b]->pcalib_leftcam_->fy_, 0., 0.});
+        eseed.push_back(seeds[b]);
+    }
+    last_.epi_pairs = (int)epi_of.size();
+    if (epi_of.empty()) return OV2_OK;
+    const int E = (int)epi_of.size();
+    std::vector<double> R(9 * (size_t)E), t(3 * (size_t)E);
+    std::vector<uint8_t> outlier(bvkf.size() / 3 + 1);
+    std::vector<int> status((size_t)E), info(4 * (size_t)E);
+    const ov2_status s = ov2_epipolar_filter_batch(ctx_, E, npairs.data(), bvkf.data(), bvcur.data(), nullptr, nullptr, nullptr, K.data(),
+                                                   10 * pslamstate_->nransac_iter_, pslamstate_->fransac_err_, eseed.data(), R.data(),
+                                                   t.data(), outlier.data(), nullptr, status.data(), info.data());   // :482-491
+    if (s != OV2_OK) return s;
+    last_.epi_calls = 1;
+    size_t o = 0;
+    for (int e = 0; e < E; ++e) {
+        LoopPairResult &r = out[epi_of[e]];
+        const size_t n = (size_t)npairs[e];
+        r.epi_status = status[e];
+        std::copy(info.begin() + 4 * e, info.begin() + 4 * e + 4, r.epi_info);
+        const bool success = status[e] >= 1;      // MultiViewGeometry::compute5ptEssentialMatrix: < 8 pairs, no model, < 10 inliers
+        std::vector<int> voutliers_idx;
+        if (success) {
+            std::copy(R.begin() + 9 * e, R.begin() + 9 * e + 9, r.R);
+            std::copy(t.begin() + 3 * e, t.begin() + 3 * e + 3, r.t);
+            for (size_t i = 0; i < n; ++i)
+                if (outlier[o + i]) voutliers_idx.push_back((int)i);
+        }
+        o += n;
+        r.n_outliers = (int)voutliers_idx.size();
+        const size_t nbinliers = n - voutliers_idx.size();                              // :225
+        if (!success || nbinliers < 10) continue;                                       // :227
+        r.vkplmids = r.vkplmids_knn;
+        if (!voutliers_idx.empty()) removeOutliers(r.vkplmids, voutliers_idx);          // :233-236
+        r.branch = LC_PASSED;
+    }
+    return OV2_OK;
+}
+
 }  // namespace ov2

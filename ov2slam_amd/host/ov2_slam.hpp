@@ -12,7 +12,11 @@
 // VisualFrontEnd::epipolar2d2dFiltering :446-655 runs with doepipolar_ (ov2_epipolar_filter_batch); computePose runs its
 // P3P-LMedS bootstrap (ov2_p3p_ransac_batch) when tracking asks for it (bp3preq_) or dop3p_ is set, and resetFrame() where
 // that fails.
-// Out of scope and refused loudly where reached: the mono branch of the epipolar filter, loop closing.
+//   LoopCloser (2D-2D half)         src/loop_closer.cpp:184-236  knnMatching :378-459  epipolarFiltering :462-499
+//                                   removeOutliers :899-928
+// Out of scope and refused loudly where reached: the mono branch of the epipolar filter.  Of loop closing, what decides
+// whether a candidate keyframe is a loop is built up to the pair list that p3pRansac would receive (LoopCloser below); the
+// frame loop calls none of it, because nothing proposes candidates yet.
 #pragma once
 #include "ov2_host.hpp"
 
@@ -122,6 +126,72 @@ private:
     int nkfid_ = 0, nlmid_ = 0;
     SE3 Twc_prev_;           // compose_motion: the pose of the frame before the last
     bool have_prev_ = false;
+};
+
+// what LoopCloser::processLoopCandidate did with one candidate pair, up to the call of p3pRansac (src/loop_closer.cpp:201-236)
+enum LoopBranch {
+    LC_COVISIBLE = 0,     // :201-209 covisibility score > 30
+    LC_FEW_MATCHES,       // :217 fewer than 15 pairs after knnMatching
+    LC_FILTER_FAILED,     // :227 the 5-point RANSAC failed or left fewer than 10 inliers
+    LC_PASSED             // :233-236 the pair list p3pRansac would receive
+};
+
+struct LoopKnnInputs {   // what knnMatching assembles for one pair (:380-424), in the mirror's iteration order
+    std::vector<std::pair<int, int>> vkplmids;   // identity pairs (:393-395)
+    std::vector<int> vkpids, vlmids;             // lmid of every query / train row
+    std::vector<uint8_t> query, train;           // rows x 32
+};
+
+struct LoopPairResult {
+    int lckfid = -1;                                  // the candidate used (:192-195 walk down to a keyframe still in the map)
+    int branch = LC_COVISIBLE;
+    int n_identity = 0, n_query = 0, n_train = 0;     // rows of n_query / n_train are 0 when the pair did not reach the matcher
+    std::vector<std::pair<int, int>> vkplmids_knn;    // after knnMatching (empty for LC_COVISIBLE)
+    std::vector<std::pair<int, int>> vkplmids;        // after removeOutliers (LC_PASSED only)
+    int epi_status = -1;                              // -1: not offered to the filter; else the ov2_epipolar_filter_batch status
+    int epi_info[4] = {0, 0, -1, 0};                  // its info: iterations, skipped draws, chosen draw, inlier count
+    int n_outliers = 0;                               // voutliers_idx.size() (0 unless the filter returned true)
+    double R[9] = {0}, t[3] = {0};                    // [R12 | t12] of the filter where epi_status >= 1
+};
+
+struct LoopStats {   // one matchLoopCandidates call
+    int pairs = 0, knn_pairs = 0, epi_pairs = 0;   // pairs given, offered to the matcher, offered to the 5-point filter
+    int knn_calls = 0, epi_calls = 0;              // launches of each (0 or 1)
+};
+
+// The 2D-2D half of LoopCloser::processLoopCandidate (src/loop_closer.cpp:184-236): does the new keyframe see the same place
+// as a candidate keyframe?  The second half (:238-300: p3pRansac with refinement, trackLoopLocalMap, computePnP) is not built;
+// neither is a detector that proposes candidates (:89-181, iBoW-LCD).
+class LoopCloser {
+public:
+    LoopCloser(ov2_ctx *ctx, std::shared_ptr<SlamParams> pstate, std::shared_ptr<MapManager> pmap)
+        : ctx_(ctx), pslamstate_(pstate), pmap_(pmap) {}
+    // :380-424, the part of knnMatching in front of the matcher: identity pairs, query and train sets (no GPU)
+    void assembleKnn(const Frame &newkf, const Frame &lckf, LoopKnnInputs &in) const;
+    // :430-449: maxdist, the ratio test in double, (kpid, lmid) of the accepted matches appended to vkplmids; idx / dist:
+    // n_query x 2 as ov2_knn2_hamming_batch writes them
+    static void acceptMatches(const LoopKnnInputs &in, const int32_t *idx, const int32_t *dist, std::vector<std::pair<int, int>> &vkplmids);
+    static bool acceptMatch(int d0, int d1);   // :434-442, d1 < 0: fewer than 2 neighbours
+    // :378-459, ov2_knn2_hamming_batch with B = 1
+    ov2_status knnMatching(const Frame &newkf, const Frame &lckf, std::vector<std::pair<int, int>> &vkplmids);
+    // :462-499 -> MultiViewGeometry::compute5ptEssentialMatrix (10 nransac_iter_ iterations, fransac_err_, no optimisation);
+    // seed replaces the reference's bdo_random clock seed
+    bool epipolarFiltering(const Frame &newkf, const Frame &lckf, std::vector<std::pair<int, int>> &vkplmids,
+                           std::vector<int> &voutliers_idx, uint64_t seed, ov2_status *st = nullptr);
+    // :899-928, as written: voutliers_idx must ascend, and once its last entry is met j wraps to 0 with entry 0 set to -1
+    static void removeOutliers(std::vector<std::pair<int, int>> &vkplmids, std::vector<int> &voutliers_idx);
+    // :184-236 as written, one candidate: knnMatching, epipolarFiltering, removeOutliers one after the other (a synchronisation
+    // each).  Fills the same fields as matchLoopCandidates except epi_info, R and t, which the reference's call does not return.
+    ov2_status processLoopCandidate(int newkfid, int lckfid, uint64_t seed, LoopPairResult &r);
+    // :184-236 for B pairs (newkfid, candidate kfid) of this map: one ov2_knn2_hamming_batch call for all pairs that reach the
+    // matcher, one ov2_epipolar_filter_batch call for all that reach the filter (two synchronisations whatever B is); B = 1
+    // is the reference's call.  seeds: one sampler seed per pair.  A new keyframe that is not in the map is OV2_ERR_INVALID.
+    ov2_status matchLoopCandidates(const std::vector<std::pair<int, int>> &pairs, const std::vector<uint64_t> &seeds,
+                                   std::vector<LoopPairResult> &out);
+    LoopStats last_;
+    ov2_ctx *ctx_;
+    std::shared_ptr<SlamParams> pslamstate_;
+    std::shared_ptr<MapManager> pmap_;
 };
 
 }  // namespace ov2

@@ -151,6 +151,14 @@ def lib():
         L.ov2h_klt_tracking.argtypes = [C.c_void_p, C.c_void_p, C.c_int, u8, u8, C.c_int, C.c_int, ip]
         L.ov2h_get_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, fpp, u8, u8, fpp]
         L.ov2h_get_frl.argtypes = [C.c_void_p, C.c_int, dp]
+        L.ov2h_map_add_desc.argtypes = [C.c_void_p, C.c_int, C.c_int, u8]
+        L.ov2h_map_set_covscore.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.ov2h_loop_assemble.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, u8, u8]
+        L.ov2h_loop_accept.argtypes = [C.c_int, C.c_int]
+        L.ov2h_loop_remove_outliers.argtypes = [C.c_int, ip, C.c_int, ip]
+        L.ov2h_loop_candidate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, C.c_int, C.c_float, C.c_int, ip, ip, ip, ip]
+        L.ov2h_loop_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, C.POINTER(C.c_ulonglong), C.c_int, C.c_float, C.c_int,
+                                      ip, ip, ip, dp, ip, ip, ip]
         _lib = L
     return _lib
 
@@ -870,6 +878,105 @@ class FilterMap(TemporalMap):
         for l in np.intersect1d(np.flatnonzero(m["lm_isobs"] == 0), m["obs_lm"]):   # map points are created observed
             assert L.ov2h_map_set_isobs(self.h, int(l), 0) == 0
         assert L.ov2h_map_finalize(self.h, self.newkf) == 0
+
+
+class LoopMap:
+    """the C++ host map of a synth_loop.make_scene dict -- keyframes with 2D / 3D keypoints, map points with one descriptor
+    each (MapPoint::addDesc), chosen covisibility scores -- to run ov2::LoopCloser on: assemble (no GPU context), loop_match."""
+
+    def __init__(self, s):
+        L = lib()
+        K = np.ascontiguousarray(s["K4"], np.float64)
+        t_lr7 = np.ascontiguousarray([0.11, 0, 0, 0, 0, 0, 1.0])
+        self.h = L.ov2h_map_create(1, 1, _dp(K), _dp(K), _dp(t_lr7), int(s["w"]), int(s["h"]), 25)
+        self.s = s
+        ip, fp, u8 = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+        for k in s["kfids"]:
+            L.ov2h_map_add_keyframe(self.h, int(k), _dp(np.ascontiguousarray(s["poses"][k], np.float64)))
+            v = s["kps"][k]
+            lm, uv = np.ascontiguousarray(v["lmid"], np.int32), np.ascontiguousarray(v["uv"], np.float32)
+            kp3d = np.ascontiguousarray(v["kp3d"], np.uint8)
+            xyz = np.zeros((len(lm), 3))
+            assert L.ov2h_map_add_kps(self.h, int(k), len(lm), lm.ctypes.data_as(ip), uv.ctypes.data_as(fp), kp3d.ctypes.data_as(u8),
+                                      kp3d.ctypes.data_as(u8), _dp(xyz)) == 0
+        for l, d in s["desc"].items():
+            d = np.ascontiguousarray(d, np.uint8)
+            kfid = min(k for k in s["kfids"] if l in s["kps"][k]["lmid"])
+            assert L.ov2h_map_add_desc(self.h, int(l), int(kfid), d.ctypes.data_as(u8)) == 0
+        for l in s["forget_lm"]:
+            L.ov2h_map_forget_landmark(self.h, int(l))
+        for a, b, score in s["cov"]:
+            assert L.ov2h_map_set_covscore(self.h, int(a), int(b), int(score)) == 0
+
+    def keypoint_order(self, kfid, cap=1 << 16):
+        """lmids of keyframe kfid in the mirror's iteration order (Frame::getKeypoints)"""
+        lm, px, a, b, rpx = np.zeros(cap, np.int32), np.zeros((cap, 2), np.float32), np.zeros(cap, np.uint8), np.zeros(cap, np.uint8), \
+            np.zeros((cap, 2), np.float32)
+        u8, fp = C.POINTER(C.c_uint8), C.POINTER(C.c_float)
+        n = lib().ov2h_get_keypoints(self.h, int(kfid), cap, lm.ctypes.data_as(C.POINTER(C.c_int)), px.ctypes.data_as(fp),
+                                     a.ctypes.data_as(u8), b.ctypes.data_as(u8), rpx.ctypes.data_as(fp))
+        assert 0 <= n <= cap
+        return lm[:n].tolist()
+
+    def order(self):
+        return {k: self.keypoint_order(k) for k in self.s["kfids"]}
+
+    def assemble(self, newkf, lckf, cap=1 << 14):
+        """what knnMatching hands to the matcher: (identity lmids, query lmids, train lmids, query rows, train rows)"""
+        ip, u8 = C.POINTER(C.c_int), C.POINTER(C.c_uint8)
+        n, q, t, i = np.zeros(3, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        qd, td = np.zeros((cap, 32), np.uint8), np.zeros((cap, 32), np.uint8)
+        rc = lib().ov2h_loop_assemble(self.h, int(newkf), int(lckf), cap, n.ctypes.data_as(ip), q.ctypes.data_as(ip), t.ctypes.data_as(ip),
+                                      i.ctypes.data_as(ip), qd.ctypes.data_as(u8), td.ctypes.data_as(u8))
+        if rc != 0:
+            raise RuntimeError(f"ov2h_loop_assemble: status {rc}")
+        return i[:n[2]].tolist(), q[:n[0]].tolist(), t[:n[1]].tolist(), qd[:n[0]].copy(), td[:n[1]].copy()
+
+    def loop_candidate(self, ctx, newkf, lckf, seed, nransac_iter=100, fransac_err=3.0, cap=1 << 14):
+        """LoopCloser::processLoopCandidate as the reference writes it, one pair: dict(branch, lckfid, knn, n_outliers, out,
+        success: the filter's bool, -1 = not reached); a negative status raises"""
+        ip = C.POINTER(C.c_int)
+        o, ok, pk, po = np.zeros(5, np.int32), C.c_int(-1), np.zeros((cap, 2), np.int32), np.zeros((cap, 2), np.int32)
+        rc = lib().ov2h_loop_candidate(self.h, ctx.h, int(newkf), int(lckf), int(seed), int(nransac_iter), float(fransac_err), cap,
+                                       o.ctypes.data_as(ip), C.byref(ok), pk.ctypes.data_as(ip), po.ctypes.data_as(ip))
+        if rc != 0:
+            raise RuntimeError(f"processLoopCandidate: status {rc}")
+        return dict(branch=int(o[0]), lckfid=int(o[1]), knn=[tuple(r) for r in pk[:o[2]].tolist()], n_outliers=int(o[3]),
+                    out=[tuple(r) for r in po[:o[4]].tolist()], success=ok.value)
+
+    def loop_match(self, ctx, pairs, seeds, nransac_iter=100, fransac_err=3.0, cap=1 << 16):
+        """LoopCloser::matchLoopCandidates: (list of per-pair dicts, stats dict); a negative status raises"""
+        B = len(pairs)
+        ip = C.POINTER(C.c_int)
+        nk = np.ascontiguousarray([p[0] for p in pairs], np.int32)
+        lc = np.ascontiguousarray([p[1] for p in pairs], np.int32)
+        sd = np.ascontiguousarray(seeds, np.uint64)
+        branch, counts, info, Rt = np.zeros(B, np.int32), np.zeros((B, 8), np.int32), np.zeros((B, 4), np.int32), np.zeros((B, 12))
+        pk, po, stats = np.zeros((cap, 2), np.int32), np.zeros((cap, 2), np.int32), np.zeros(5, np.int32)
+        rc = lib().ov2h_loop_match(self.h, ctx.h, B, nk.ctypes.data_as(ip), lc.ctypes.data_as(ip), sd.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                   int(nransac_iter), float(fransac_err), cap, branch.ctypes.data_as(ip), counts.ctypes.data_as(ip),
+                                   info.ctypes.data_as(ip), _dp(Rt), pk.ctypes.data_as(ip), po.ctypes.data_as(ip), stats.ctypes.data_as(ip))
+        if rc != 0:
+            raise RuntimeError(f"matchLoopCandidates: status {rc}")
+        out, ok, oo = [], 0, 0
+        for b in range(B):
+            c = counts[b]
+            out.append(dict(branch=int(branch[b]), lckfid=int(c[0]), n_identity=int(c[1]), n_query=int(c[2]), n_train=int(c[3]),
+                            knn=[tuple(r) for r in pk[ok:ok + c[4]].tolist()], n_outliers=int(c[5]),
+                            out=[tuple(r) for r in po[oo:oo + c[6]].tolist()], status=int(c[7]), info=info[b].tolist(),
+                            R=Rt[b, :9].copy(), t=Rt[b, 9:].copy()))
+            ok += c[4]
+            oo += c[6]
+        return out, dict(pairs=int(stats[0]), knn_pairs=int(stats[1]), epi_pairs=int(stats[2]), knn_calls=int(stats[3]),
+                         epi_calls=int(stats[4]))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ov2h_map_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
 
 
 class FrontEndFrame:
