@@ -143,7 +143,7 @@ ov2_status ov2_klt_tracking_frame_dev(ov2_ctx *ctx, const ov2_pyr *prev, const o
 
 /* Tuning / test knob: lanes of a wavefront that share one keypoint in the tracking kernels.  0 (default) picks by call
  * size: 9 x 9 windows (nklt_win_size of every parameter file of the reference) take THREE lanes per keypoint at every
- * call size (20 keypoints per wave, Scharr derivatives formed in the kernel, no gradient planes read);
+ * call size (21 keypoints per wave, Scharr derivatives formed in the kernel, no gradient planes read);
  * other windows 8 lanes from 65 536 keypoints on, 16 below.  All mappings give bit-identical results. */
 ov2_status ov2_klt_set_lanes(ov2_ctx *ctx, int lanes);
 

@@ -1,4 +1,4 @@
-// klt.hip -- forward-backward pyramidal Lucas-Kanade, EIGHT keypoints per 64-lane wavefront (gfx950).
+// klt.hip -- forward-backward pyramidal Lucas-Kanade, 21, eight or four keypoints per 64-lane wavefront (gfx950).
 //
 // Replaces (reference, /root/reference): FeatureTracker::fbKltTracking src/feature_tracker.cpp:35-137
 // (= 2x cv::calcOpticalFlowPyrLK + the status / err / inBorder / forward-backward gates) and the two-stage
@@ -8,8 +8,9 @@
 // fp32 once (order independent, so the lane reduction is bit-identical to the oracle's scalar loop), fp32
 // 2x2 solve with contraction off, fp64 for the two comparisons OpenCV does in double.
 //
-// Mapping: one keypoint per group of 8 or 16 lanes (8 or 4 keypoints per wave), lane = window column walking the win
-// rows of its column.
+// Mapping: 9 x 9 windows take three lanes per keypoint (21 keypoints per wave on lanes 0 .. 62, lane = three window columns:
+// lk_level3 below); the other windows one keypoint per group of 8 or 16 lanes (8 or 4 keypoints per wave), lane = window
+// column walking the win rows of its column.
 //   - every "scalar" of the LK update is per-group vector math, so the keypoints of a wave share each instruction;
 //   - the windows (template I + its Scharr gradients, search window J) are fetched row-wise with 16-byte loads into LDS
 //     and read from there as pixel pairs: the kernel was bound by the texture addresser when every lane gathered two
@@ -427,15 +428,16 @@ __device__ __forceinline__ int lk_level(const level_ptrs &I, const level_ptrs &J
 // The 8-lane mapping above spends most of a level pass on per-keypoint arithmetic that every lane of the group repeats
 // (positions, weights, 2 x 2 solve, convergence tests: ~70 of the ~190 vector instructions of an LK iteration, and
 // more around the template).  Here a keypoint takes THREE lanes, each owning three adjacent columns of the 9 x 9 window,
-// so a wave carries 20 keypoints (five groups per 16-lane DPP row, lane 15 of every row idles) and that overhead is
-// shared by 2.5 x as many keypoints:
-//   - one aligned dword pair + v_alignbyte give the four pixels (x .. x+3) a lane's three columns touch in a row;
+// so a wave carries 21 keypoints (group g on lanes 3g .. 3g + 2, only lane 63 idles) and that overhead is shared by 2.6 x
+// as many keypoints:
+//   - one aligned dword pair holds the four pixels (x .. x+3) a lane's three columns touch in a row; its pixel pairs are
+//     cut out by v_perm_b32 with per-lane selectors (the byte shift is a constant of the lane for the whole window);
 //   - the template rows (I: 8 B, gradient: 16 B per lane and row) go from global memory straight to registers -- no
 //     LDS for them;
 //   - the SEARCH image is staged once per level pass as a 14-row x 48-byte region around the start position
 //     (margin 2 rows / >= 11 columns): the later iterations of the pass read it from LDS without another trip to
 //     memory, and a window that leaves the region re-stages it (rare);
-//   - sums over the three lanes: two DPP row shifts + two selects.
+//   - sums over the three lanes: whole-wave DPP shifts by one lane (groups 5 and 10 straddle a DPP row) + two selects.
 // Arithmetic per window pixel is the one of lk_level (same taps, exact integer sums), so results are bit-identical.
 #ifndef KLT3_RROWS
 #define KLT3_RROWS 14
@@ -465,10 +467,10 @@ struct klt_map {
 };
 template <>
 struct klt_map<3> {
-    static constexpr int KPW = 20;
-    static __device__ __forceinline__ int slot(int tid) { return (tid >> 4) * 5 + min(((tid & 15) * 11) >> 5, 4); }   // (t * 11) >> 5 == t / 3 for t < 16
-    static __device__ __forceinline__ int sub(int tid) { const int t = tid & 15; return t - 3 * ((t * 11) >> 5); }
-    static __device__ __forceinline__ bool lane_ok(int tid) { return (tid & 15) != 15; }
+    static constexpr int KPW = 21;   // groups on lanes 3g .. 3g + 2, g = 0 .. 20; lane 63 idles and shadows lane 60
+    static __device__ __forceinline__ int slot(int tid) { return min((tid * 171) >> 9, KPW - 1); }   // (t * 171) >> 9 == t / 3 for t < 64
+    static __device__ __forceinline__ int sub(int tid) { return tid == 63 ? 0 : tid - 3 * ((tid * 171) >> 9); }
+    static __device__ __forceinline__ bool lane_ok(int tid) { return tid != 63; }
 };
 
 template <int WIN, int GL>
@@ -480,28 +482,27 @@ struct klt_smem<WIN, 3> {
     static constexpr int BYTES = klt_map<3>::KPW * klt3::RSZ;
 };
 
-// sum over the three lanes of a group, result in all three (c = lane of the group)
+// sum over the three lanes of a group, result in all three (c = lane of the group).  Groups 5 and 10 of a wave straddle a
+// 16-lane DPP row, so the moves are the whole-wave single-lane shifts (wave_shr:1 / wave_shl:1), which cross the rows
 __device__ __forceinline__ int sum3_i32(int v, int c)
 {
-    int t = v + dpp_i32<0x111>(v);   // row_shr:1  lane l reads l - 1
-    t += dpp_i32<0x112>(v);          // row_shr:2  complete in lane c == 2
-    const int u1 = dpp_i32<0x101>(t), u2 = dpp_i32<0x102>(t);   // row_shl:1 / 2: lane l reads l + 1 / l + 2
+    const int t1 = v + dpp_i32<0x138>(v);   // wave_shr:1  lane l reads l - 1
+    const int t = v + dpp_i32<0x138>(t1);   // v[l] + v[l - 1] + v[l - 2]: complete in lane c == 2
+    const int u1 = dpp_mov_i32<0x130>(t), u2 = dpp_mov_i32<0x130>(u1);   // wave_shl:1: lane l reads l + 1; twice: l + 2
     return c == 2 ? t : (c == 1 ? u1 : u2);
 }
 __device__ __forceinline__ double sum3_f64(double v, int c)
 {
-    double t = v + dpp_f64<0x111>(v);
-    t += dpp_f64<0x112>(v);
-    const double u1 = dpp_f64<0x101>(t), u2 = dpp_f64<0x102>(t);
+    const double s1 = dpp_f64<0x138>(v), s2 = dpp_f64<0x138>(s1);
+    const double t = (v + s1) + s2;   // (v[l] + v[l - 1]) + v[l - 2]
+    const double u1 = dpp_f64<0x130>(t), u2 = dpp_f64<0x130>(u1);
     return c == 2 ? t : (c == 1 ? u1 : u2);
 }
 
-// (byte k, byte k + 1) of a dword as two zero-extended 16-bit halves
-template <int K>
-__device__ __forceinline__ unsigned spread_pair(unsigned t)
-{
-    return __builtin_amdgcn_perm(0u, t, 0x0c000c00u + (unsigned)K * 0x00010001u + 0x00010000u);
-}
+// v_perm_b32 selector for (byte k, byte k + 1) of a dword PAIR (k = 0 .. 6) as two zero-extended 16-bit halves; the byte shift
+// of a lane's columns is the same for every row of a window, so a lane forms its selectors once and every row is cut
+// straight out of the two loaded dwords: __builtin_amdgcn_perm(hi dword, lo dword, klt3_pair_sel(k))
+__device__ __forceinline__ unsigned klt3_pair_sel(unsigned k) { return 0x0c010c00u + k * 0x00010001u; }
 
 // origin of the staged search region (padded row, byte column) for a window at (inx, iny)
 __device__ __forceinline__ void klt3_region_origin(const level_ptrs &J, int pad, int inx, int iny, int &rr0, int &cc0)
@@ -539,7 +540,7 @@ __device__ __forceinline__ void klt3_store_region(const klt3_segs &S, int c, boo
 }
 
 // One LKTrackerInvoker pass for the keypoint of this three-lane group; lane c owns window columns 3c .. 3c + 2.
-// `lane_ok` is false for the idle sixteenth lane of a DPP row (it computes along on zeros and never stores).
+// `lane_ok` is false for the idle last lane of the wave (it computes along on zeros and never stores).
 template <int WIN>
 __device__ __forceinline__ int lk_level3(const level_ptrs &I, const level_ptrs &J, int pad, int level, int max_level,
                                          bool run, float kx, float ky, float &nx_io, float &ny_io, int &status,
@@ -611,29 +612,38 @@ __device__ __forceinline__ int lk_level3(const level_ptrs &I, const level_ptrs &
 
         const unsigned W01 = pack_lo16((unsigned)w00, (unsigned)w01), W23 = pack_lo16((unsigned)w10, (unsigned)w11);
         // derivative positions outside the image are zero: masks per column pair and per row (always applied: a
-        // wave-uniform branch around them costs 60 more registers than it saves time); idle lanes / groups get all-zero
-        // masks, so their gradients -- and with them everything they add to the sums below -- vanish
+        // wave-uniform branch around them costs 60 more registers than it saves time).  The column masks are constants of
+        // the lane for the whole pass, so they go into the tap weights of the gradient interpolation once (dot2(G & m, W) ==
+        // dot2(G, W & m) for a mask of 0 / 0xffff per half) and only the row mask is applied per derivative row; idle lanes /
+        // groups get all-zero masks: their interpolated gradients are (0 + 2^13) >> 14 = 0 -- and with them everything they add
+        // to the sums below vanishes
         const int x0 = ipx + 3 * c;
         const unsigned wlim = (run && lane_ok) ? (unsigned)I.w : 0u, hlim = (run && lane_ok) ? (unsigned)I.h : 0u;
         unsigned cm[2];   // columns (0, 1) and (2, 3) of the lane
 #pragma unroll
         for (int j = 0; j < 2; ++j)
             cm[j] = ((unsigned)(x0 + 2 * j) < wlim ? 0xffffu : 0u) | ((unsigned)(x0 + 2 * j + 1) < wlim ? 0xffff0000u : 0u);
+        // gradient tap weights of the lane's derivative pairs (0, 1), (1, 2), (2, 3)
+        const unsigned cmi[3] = {cm[0], __builtin_amdgcn_perm(cm[1], cm[0], 0x05040302u), cm[1]};
+        unsigned W01g[3], W23g[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { W01g[i] = W01 & cmi[i]; W23g[i] = W23 & cmi[i]; }
         // per loaded row: pixel pairs P_k = (q_k, q_k+1), k = 0..4, of the lane's six pixels q_0..q_5 (window columns
         // 3c - 1 .. 3c + 4); horizontal terms for the column pairs (0, 1) and (2, 3): Hd = P_k+2 - P_k, Sm = 3 (P_k + P_k+2)
         // + 10 P_k+1 with k = 0 / 2 (packed 16-bit); the middle pair (1, 2) of a derivative row is cut out of the two
+        unsigned selI[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) selI[k] = klt3_pair_sel(shI + (unsigned)k);
         unsigned Pm[2][3] = {};              // P_1..P_3 (the window's own pixel pairs) of the two previous loaded rows
         unsigned Hd[3][2] = {}, Sm[3][2] = {};   // [age][pair]: ages 0 / 1 / 2 = loaded rows p - 2 / p - 1 / p
         unsigned GXp[3] = {0, 0, 0}, GYp[3] = {0, 0, 0};   // derivative pairs of the previous window row
         unsigned piv = 0, pix = 0, piy = 0;
 #pragma unroll
         for (int p = 0; p < WIN + 3; ++p) {
-            const unsigned e0 = __builtin_amdgcn_alignbyte(irow[p].y, irow[p].x, shI);
-            const unsigned e1 = __builtin_amdgcn_alignbyte(irow[p].z, irow[p].y, shI);
-            unsigned P[5];
-            P[0] = spread_pair<0>(e0); P[1] = spread_pair<1>(e0); P[2] = spread_pair<2>(e0);
-            P[3] = __builtin_amdgcn_perm(e1, e0, 0x0c040c03u);   // (e0 byte 3, e1 byte 0)
-            P[4] = spread_pair<0>(e1);
+            unsigned P[5];   // bytes shI + k, shI + k + 1: k <= 3 inside the first two dwords, k = 4 is pair 0 of the next two
+#pragma unroll
+            for (int k = 0; k < 4; ++k) P[k] = __builtin_amdgcn_perm(irow[p].y, irow[p].x, selI[k]);
+            P[4] = __builtin_amdgcn_perm(irow[p].z, irow[p].y, selI[0]);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 Hd[0][j] = Hd[1][j]; Hd[1][j] = Hd[2][j]; Sm[0][j] = Sm[1][j]; Sm[1][j] = Sm[2][j];
@@ -646,9 +656,8 @@ __device__ __forceinline__ int lk_level3(const level_ptrs &I, const level_ptrs &
                 unsigned GX[3], GY[3];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const unsigned m = cm[j] & rm;
-                    GX[2 * j] = pk_mad16(Hd[1][j], 10u, pk_mul16(pk_add16(Hd[0][j], Hd[2][j]), 3u)) & m;
-                    GY[2 * j] = pk_sub16(Sm[2][j], Sm[0][j]) & m;
+                    GX[2 * j] = pk_mad16(Hd[1][j], 10u, pk_mul16(pk_add16(Hd[0][j], Hd[2][j]), 3u)) & rm;
+                    GY[2 * j] = pk_sub16(Sm[2][j], Sm[0][j]) & rm;
                 }
                 // (column 1, column 2) = (high half of pair 0, low half of pair 2)
                 GX[1] = __builtin_amdgcn_perm(GX[2], GX[0], 0x05040302u); GY[1] = __builtin_amdgcn_perm(GY[2], GY[0], 0x05040302u);
@@ -659,8 +668,8 @@ __device__ __forceinline__ int lk_level3(const level_ptrs &I, const level_ptrs &
                     for (int i = 0; i < 3; ++i) {
                         const int e = 3 * y + i;
                         const unsigned av = (unsigned)dot2(Pm[1][i], W23, dot2k(Pm[0][i], W01, 1 << (W_BITS - 5 - 1)));
-                        const int ax_ = dot2(GX[i], W23, dot2k(GXp[i], W01, 1 << (W_BITS - 1)));
-                        const int ay_ = dot2(GY[i], W23, dot2k(GYp[i], W01, 1 << (W_BITS - 1)));
+                        const int ax_ = dot2(GX[i], W23g[i], dot2k(GXp[i], W01g[i], 1 << (W_BITS - 1)));
+                        const int ay_ = dot2(GY[i], W23g[i], dot2k(GYp[i], W01g[i], 1 << (W_BITS - 1)));
                         if (e & 1) {
                             Iv2[e >> 1] = shr_pack_hi<W_BITS - 5>(piv, av);
                             Ix2[e >> 1] = ashr_pack_hi<W_BITS>(pix, ax_);
@@ -728,20 +737,20 @@ __device__ __forceinline__ int lk_level3(const level_ptrs &I, const level_ptrs &
         const unsigned W01 = pack_lo16((unsigned)w00j, (unsigned)w01j), W23 = pack_lo16((unsigned)w10j, (unsigned)w11j);
         const int cq = cb + 3 * c;
         const unsigned *q = reinterpret_cast<const unsigned *>(lj + rb * klt3::RBYTES + (cq & ~3));
-        const unsigned sh = (unsigned)cq & 3u;
+        unsigned selJ[3];   // the lane's pixel pairs (x, x + 1), (x + 1, x + 2), (x + 2, x + 3) of a row's dword pair
+#pragma unroll
+        for (int i = 0; i < 3; ++i) selJ[i] = klt3_pair_sel(((unsigned)cq & 3u) + (unsigned)i);
         int pb1 = 0, pb2 = 0;
         unsigned T[3];
-        {
-            const unsigned p4 = __builtin_amdgcn_alignbyte(q[1], q[0], sh);
-            T[0] = spread_pair<0>(p4); T[1] = spread_pair<1>(p4); T[2] = spread_pair<2>(p4);
-        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) T[i] = __builtin_amdgcn_perm(q[1], q[0], selJ[i]);
         unsigned pj = 0;
 #pragma unroll
         for (int y = 0; y < WIN; ++y) {
             const unsigned *qr = q + (klt3::RBYTES / 4) * (y + 1);
-            const unsigned p4 = __builtin_amdgcn_alignbyte(qr[1], qr[0], sh);
             unsigned B[3];
-            B[0] = spread_pair<0>(p4); B[1] = spread_pair<1>(p4); B[2] = spread_pair<2>(p4);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) B[i] = __builtin_amdgcn_perm(qr[1], qr[0], selJ[i]);
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const int e = 3 * y + i;
@@ -1065,7 +1074,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
 }
 
 // Lanes per keypoint for a call of n keypoints.  9 x 9 windows (the reference's nklt_win_size) take the three-lane
-// mapping (20 keypoints per wave, Scharr derivatives formed in the kernel) at EVERY call size: measured per frame-batch of
+// mapping (21 keypoints per wave, Scharr derivatives formed in the kernel) at EVERY call size: measured per frame-batch of
 // 308 keypoints (EuRoC size, scripts/klt_small_time.py), pyramid build + two-stage tracking back to back: 1 sequence 64.1 us
 // against 71.4 us with the 16-lane kernels (which first need the four gradient-plane launches), 8 sequences 77.9 / 90.5,
 // 64 sequences 109.8 / 182.5; synchronised latency of one frame 103 / 121 us.  ov2_klt_set_lanes (or OV2_KLT_LANES = 3 / 8 /

@@ -13,6 +13,13 @@ __device__ __forceinline__ int dpp_i32(int v)
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
 }
 
+// the bare move: lanes whose source lane does not exist read 0 (bound_ctrl), so no register has to be zeroed for them first
+template <int CTRL>
+__device__ __forceinline__ int dpp_mov_i32(int v)
+{
+    return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, true);
+}
+
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v)
 {
