@@ -56,6 +56,24 @@ ov2_status ov2_ctx_synchronize(ov2_ctx *ctx);
  * it when the two provably touch different arrays (see both entry points).  Results and the ordering of the calls are the
  * same either way; off = the chain is enqueued on the context's main stream. */
 ov2_status ov2_ctx_set_kf_overlap(ov2_ctx *ctx, int on);
+/* Depth of the pyramid pool's ring, n = 1 .. 8 (anything else: OV2_ERR_INVALID, the depth stays; default 3; OV2_PYR_RING=n
+ * in the environment starts a context with depth n).  Released pyramid buffers go back to a pool per context.  A build
+ * takes a pooled buffer of its geometry whose readers have finished if there is one; otherwise it allocates a new buffer
+ * while fewer than n such buffers are pooled with readers still pending; otherwise it takes the one released longest ago
+ * and waits (on the pyramid stream) for its readers.  With a host that enqueues ahead of the device no buffer ever tests
+ * as finished, and n then decides how far the builds run ahead: in a loop build(t), track(t - 1 -> t), release(t - 1)
+ * the build of frame t waits for the tracking call of frame t - n.  At n = 2 every tracking call of that loop waits for
+ * its pyramid, from n = 3 on none does.  Results do not depend on n.
+ * Cost: a frame loop that holds p pyramids keeps up to p + n buffers alive.  One buffer of 64 images of 752 x 480, window
+ * 9, 4 levels is 174 739 456 bytes (78.9 % of it gradient planes, allocated whether or not a consumer asks for them) plus
+ * 67 108 864 bytes of CLAHE tables.
+ * Lowering n synchronises the context's streams and frees, per geometry, the pooled buffers beyond the n released last;
+ * raising n frees nothing. */
+ov2_status ov2_ctx_set_pyr_ring(ov2_ctx *ctx, int n);
+/* Counters of the pyramid pool (no device work): out[0] buffers alive (pooled + handed out), out[1] buffers pooled now,
+ * out[2] / out[3] / out[4] builds since the context was created that took a finished pooled buffer / a pooled buffer with
+ * readers pending / a new allocation. */
+ov2_status ov2_ctx_pyr_pool_stats(ov2_ctx *ctx, int32_t out[5]);
 /* hipEvent pair on the ctx stream (used by bench.py: torch.cuda.Event would only see torch's stream) */
 ov2_status ov2_timer_start(ov2_ctx *ctx);
 ov2_status ov2_timer_stop(ov2_ctx *ctx, float *elapsed_ms);   /* synchronises on the stop event */

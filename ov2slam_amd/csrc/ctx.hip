@@ -75,7 +75,14 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     // OV2_KF_OVERLAP=0: the keyframe detector chain stays on the main stream (default 1, ov2_ctx_set_kf_overlap)
     const char *kf_env = getenv("OV2_KF_OVERLAP");
     c->kf_overlap = (kf_env ? atoi(kf_env) : 1) > 0 ? 1 : 0;
-    // three streams of one priority: tracking / BA, pyramid builds, keyframe detector chain
+    // OV2_PYR_RING=1..8: depth of the pyramid pool's ring (ov2_ctx_set_pyr_ring); any other value is ignored
+    const char *ring_env = getenv("OV2_PYR_RING");
+    const int ring = ring_env ? atoi(ring_env) : 0;
+    c->pyr_ring = (ring >= 1 && ring <= OV2_PYR_RING_MAX) ? ring : OV2_PYR_RING_DEFAULT;
+    c->pyr_alive = 0;
+    c->pyr_acquires[0] = c->pyr_acquires[1] = c->pyr_acquires[2] = 0;
+    // three streams of one priority: tracking / BA, pyramid builds, keyframe detector chain (a pyramid stream one level
+    // more urgent than the other two was measured and changes nothing, DESIGN.md section 7 "A ring for the pyramid pool")
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     const int prio = high_priority ? prio_greatest : prio_least;
@@ -101,14 +108,7 @@ extern "C" void ov2_ctx_destroy(ov2_ctx *c)
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamSynchronize(c->stream_pyr);
     (void)hipStreamSynchronize(c->stream_kf);
-    for (ov2_pyr_buf *b : c->pool) {
-        (void)hipEventDestroy(b->ready_ev);
-        (void)hipEventDestroy(b->free_ev);
-        (void)hipEventDestroy(b->free_ev2);
-        (void)hipFree(b->base);
-        if (b->lut) (void)hipFree(b->lut);
-        delete b;
-    }
+    for (ov2_pyr_buf *b : c->pool) ov2_pyr_buf_free(b);
     for (ov2_map *m : c->maps) ov2_map_orphan(m);
     if (c->tmp_img) ov2_images_destroy(c->tmp_img);
     for (auto &r : c->ktime_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
@@ -148,6 +148,68 @@ extern "C" ov2_status ov2_ctx_set_kf_overlap(ov2_ctx *c, int on)
 {
     if (!c) return OV2_ERR_INVALID;
     c->kf_overlap = on ? 1 : 0;
+    return OV2_OK;
+}
+
+void ov2_pyr_buf_free(ov2_pyr_buf *b)
+{
+    (void)hipEventDestroy(b->ready_ev);
+    (void)hipEventDestroy(b->grad_ev);
+    (void)hipEventDestroy(b->free_ev);
+    (void)hipEventDestroy(b->free_ev2);
+    (void)hipFree(b->base);
+    if (b->lut) (void)hipFree(b->lut);
+    delete b;
+}
+
+// Depth of the pyramid pool's ring: how many released buffers of one geometry whose readers have not finished the pool
+// holds before a build takes the oldest of them (and waits for its readers) instead of allocating another one.
+extern "C" ov2_status ov2_ctx_set_pyr_ring(ov2_ctx *c, int n)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (n < 1 || n > OV2_PYR_RING_MAX) return ov2_set_err(c, OV2_ERR_INVALID, "pyramid ring depth %d (1..%d)", n, OV2_PYR_RING_MAX);
+    int old;
+    { std::lock_guard<std::mutex> g(c->mu); old = c->pyr_ring; c->pyr_ring = n; }
+    if (n >= old) return OV2_OK;   // raising frees nothing
+    // lowering: every kernel this context enqueued has run once its streams are idle; of each geometry the n buffers
+    // released last stay pooled, the older ones are freed
+    OV2_HIP(c, hipSetDevice(c->device));
+    OV2_HIP(c, hipStreamSynchronize(c->stream_pyr));
+    OV2_HIP(c, hipStreamSynchronize(c->stream_kf));
+    OV2_HIP(c, hipStreamSynchronize(c->stream.h));
+    std::vector<ov2_pyr_buf *> drop;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        for (size_t i = c->pool.size(); i-- > 0;) {
+            const ov2_pyr_buf *b = c->pool[i];
+            int newer = 0;
+            for (size_t j = i + 1; j < c->pool.size(); ++j) {
+                const ov2_pyr_buf *o = c->pool[j];
+                if (o->w == b->w && o->h == b->h && o->pad == b->pad && o->max_level == b->max_level && o->batch == b->batch) ++newer;
+            }
+            if (newer >= n) {
+                drop.push_back(c->pool[i]);
+                c->pool.erase(c->pool.begin() + i);
+                --c->pyr_alive;
+            }
+        }
+    }
+    for (ov2_pyr_buf *b : drop) {
+        if (b->has_free_ev2) (void)hipEventSynchronize(b->free_ev2);   // readers another context enqueued on its own stream
+        ov2_pyr_buf_free(b);
+    }
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_ctx_pyr_pool_stats(ov2_ctx *c, int32_t out[5])
+{
+    if (!c || !out) return OV2_ERR_INVALID;
+    std::lock_guard<std::mutex> g(c->mu);
+    out[0] = c->pyr_alive;
+    out[1] = (int32_t)c->pool.size();
+    out[2] = c->pyr_acquires[0];
+    out[3] = c->pyr_acquires[1];
+    out[4] = c->pyr_acquires[2];
     return OV2_OK;
 }
 

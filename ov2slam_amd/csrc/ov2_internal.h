@@ -103,7 +103,11 @@ struct ov2_ctx {
     size_t kf_scratch_bytes;             //   the side stream alone)
     hipEvent_t ev0, ev1;
     std::mutex mu;                       // guards pool + err
-    std::vector<ov2_pyr_buf *> pool;     // free pyramid buffers
+    std::vector<ov2_pyr_buf *> pool;     // free pyramid buffers, in release order (oldest first)
+    int pyr_ring;                        // ov2_ctx_set_pyr_ring / OV2_PYR_RING: released-but-unfinished buffers of one geometry the
+                                         //   pool holds before a build reuses the oldest of them
+    int pyr_alive;                       // pyramid buffers allocated and not freed (pooled + handed out); under mu
+    int pyr_acquires[3];                 // builds served by a finished / a pending / a newly allocated buffer; under mu
     std::vector<struct ov2_map *> maps;  // live map mirrors (their device memory is released with the ctx)
     std::string err;
     // scratch for host-pointer entry points (grown on demand)
@@ -149,7 +153,12 @@ struct ov2_pyr {
     ov2_pyr_buf *buf;
 };
 
+#define OV2_PYR_RING_DEFAULT 3   // the smallest depth at which the frame loop no longer waits for its pyramids
+#define OV2_PYR_RING_MAX 8
+
 ov2_status ov2_set_err(ov2_ctx *ctx, ov2_status s, const char *fmt, ...);
+// frees a pyramid buffer that no kernel reads or writes any more (device memory, LUT, events)
+void ov2_pyr_buf_free(ov2_pyr_buf *b);
 ov2_status ov2_scratch(ov2_ctx *ctx, size_t bytes, void **out);
 // the same for the keyframe side stream's own buffer
 ov2_status ov2_kf_scratch(ov2_ctx *ctx, size_t bytes, void **out);

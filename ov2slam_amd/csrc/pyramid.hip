@@ -953,25 +953,30 @@ ov2_status acquire_buf(ov2_ctx *c, int w, int h, int pad, int max_level, int bat
 {
     {
         // prefer a pooled buffer whose last consumers have already finished: taking the one released a moment ago
-        // would chain the new build behind the KLT that still reads it and defeat the two-stream overlap.  Up to
-        // OV2_PYR_RING buffers per geometry are kept so that a finished one is normally available.
+        // would chain the new build behind the KLT that still reads it and defeat the two-stream overlap.  A host that
+        // runs ahead of the device never finds one, so the pool is a ring: while fewer than pyr_ring buffers of this
+        // geometry are pooled with their readers still pending another one is allocated, after that the build takes the
+        // one released longest ago (the pool is in release order) and waits for its readers.  A ring of n lets a build
+        // start as soon as the tracking call n frames back has ended (ov2_ctx_set_pyr_ring, OV2_PYR_RING).
         std::lock_guard<std::mutex> g(c->mu);
-        int pending = -1, same = 0;
+        int pending = -1, npending = 0;
         for (size_t i = 0; i < c->pool.size(); ++i) {
             ov2_pyr_buf *b = c->pool[i];
             if (!(b->w == w && b->h == h && b->pad == pad && b->max_level == max_level && b->batch == batch)) continue;
-            ++same;
             if ((!b->has_free_ev || hipEventQuery(b->free_ev) == hipSuccess) &&
                 (!b->has_free_ev2 || hipEventQuery(b->free_ev2) == hipSuccess)) {
                 c->pool.erase(c->pool.begin() + i);
+                ++c->pyr_acquires[0];
                 *out = b;
                 return OV2_OK;
             }
+            ++npending;
             if (pending < 0) pending = (int)i;
         }
-        if (pending >= 0 && same >= 2) {   // two idle-but-pending buffers already exist: reuse rather than grow
+        if (npending >= c->pyr_ring) {   // the ring is full: reuse rather than grow
             ov2_pyr_buf *b = c->pool[pending];
             c->pool.erase(c->pool.begin() + pending);
+            ++c->pyr_acquires[1];
             *out = b;
             return OV2_OK;
         }
@@ -1024,6 +1029,11 @@ ov2_status acquire_buf(ov2_ctx *c, int w, int h, int pad, int max_level, int bat
     b->has_free_ev2 = false;
     b->grad_built = false;
     v.base = b->base;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        ++c->pyr_alive;
+        ++c->pyr_acquires[2];
+    }
     *out = b;
     return OV2_OK;
 }

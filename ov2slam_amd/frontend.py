@@ -52,6 +52,18 @@ class Context:
         """ov2_ctx_set_kf_overlap: the keyframe detector chain on the side stream, beside stereo matching (default on)"""
         _check(self.h, self.lib.ov2_ctx_set_kf_overlap(self.h, int(bool(on))))
 
+    def set_pyr_ring(self, n):
+        """ov2_ctx_set_pyr_ring: released pyramid buffers of one geometry, readers still pending, that the pool holds before
+        a build reuses the oldest (1 .. 8, default 3); lowering it synchronises and frees the buffers beyond n"""
+        _check(self.h, self.lib.ov2_ctx_set_pyr_ring(self.h, int(n)))
+
+    def pyr_pool_stats(self):
+        """ov2_ctx_pyr_pool_stats: dict(alive, pooled, finished, pending, allocated) -- buffers now, and builds served by a
+        finished pooled buffer / a pending one / a new allocation since the context was created"""
+        out = (C.c_int32 * 5)()
+        _check(self.h, self.lib.ov2_ctx_pyr_pool_stats(self.h, out))
+        return dict(zip(("alive", "pooled", "finished", "pending", "allocated"), (int(v) for v in out)))
+
     def synchronize(self):
         _check(self.h, self.lib.ov2_ctx_synchronize(self.h))
 
