@@ -4,19 +4,25 @@ costs to 1e-9 relative, poses to 1e-8."""
 import numpy as np
 import pytest
 
+import pg_cases
 from ov2slam_amd import ba_types as T, pose_graph
 from test_oracle_pg import chain, expm, hat6, mat, pose7
 
 pytestmark = pytest.mark.gpu
 
 
+def _same_cost(a, b):
+    """1e-9 relative; a NaN cost (a NaN measurement) must be NaN on both sides"""
+    return bool(np.isnan(a)) and bool(np.isnan(b)) if np.isnan(a) or np.isnan(b) else a == pytest.approx(b, rel=1e-9, abs=1e-18)
+
+
 def _compare(Pg, Rg, Pc, Rc):
     assert Rg.termination == Rc.termination and Rg.n_log == Rc.n_log
     for a, b in zip(Rg.log[:Rg.n_log], Rc.log[:Rc.n_log]):
         assert (a.step_is_valid, a.step_is_successful) == (b.step_is_valid, b.step_is_successful)
-        assert a.cost == pytest.approx(b.cost, rel=1e-9, abs=1e-18)
+        assert _same_cost(a.cost, b.cost), (a.cost, b.cost)
         assert a.radius == pytest.approx(b.radius, rel=1e-6)
-    assert Rg.final_cost == pytest.approx(Rc.final_cost, rel=1e-9, abs=1e-18)
+    assert _same_cost(Rg.final_cost, Rc.final_cost), (Rg.final_cost, Rc.final_cost)
     assert np.abs(Pg.pose - Pc.pose).max() < 1e-8
     const = Pc.pose_const != 0
     assert np.array_equal(Pg.pose[const], Pc.pose[const])
@@ -79,3 +85,24 @@ def test_pose_graph_edge_cases(ctx, oracle):
     S.pose_const[10] = 1
     Sc = S.copy()
     _compare(S, pose_graph.solve(ctx, S), Sc, oracle.pose_graph_solve(Sc))
+
+
+@pytest.mark.parametrize("case", pg_cases.cases(), ids=pg_cases.ids())
+def test_case_matches_oracle(ctx, oracle, case):
+    """every case of pg_cases.py (rejected and invalid steps, each termination, the log cap, no Jacobi scaling, the
+    quaternion branches of the SE(3) log, the graph shapes, 255 / 256 / 257 runs): one launch each, the bar of this file.
+    tests/test_pg_cases_cpu.py holds each case to its branch and to tameness on the oracle."""
+    Pc, Rc = pg_cases.reference(oracle, case)
+    P = case.problem.copy()
+    Rg = pose_graph.solve(ctx, P, pg_cases.apply_options(pose_graph.default_options(), case.options))
+    assert pg_cases.flags(Rg) == pg_cases.flags(Rc)
+    assert _same_cost(Rg.initial_cost, Rc.initial_cost), (Rg.initial_cost, Rc.initial_cost)
+    _compare(P, Rg, Pc, Rc)
+    # the model's predicted decrease, from the residuals, jacobians and step of that round: after a rejected step it is
+    # only right if the residuals at x were put back.  1e-6 as the radius, which follows from it.
+    for k, (a, b) in enumerate(zip(Rg.log[:Rg.n_log], Rc.log[:Rc.n_log])):
+        assert a.model_cost_change == pytest.approx(b.model_cost_change, rel=1e-6, abs=0), k
+    for k in np.flatnonzero(case.problem.pose_const == 0):       # every run, pose by pose
+        assert np.abs(P.pose[k] - Pc.pose[k]).max() < 1e-8, k
+    if case.expect.get("unchanged"):        # MIN_RADIUS, no iteration, a rejected only step, FAILURE
+        assert np.array_equal(P.pose, case.problem.pose)

@@ -5,6 +5,7 @@ Bar: same LM iteration counts (robust + L2), identical outlier flags, identical 
 import numpy as np
 import pytest
 
+import pnp_cases
 from ov2slam_amd import synth_ba
 from ov2slam_amd.multi_view_geometry import MultiViewGeometry
 
@@ -64,6 +65,22 @@ def test_many_iterations_and_tight_threshold(ctx, oracle):
         eok, eT, eout, _ = oracle.pnp_solve(p["unpx"], p["wpts"], p["K"], p["Twc0"], None, max_iters=iters, chi2th=th)
         assert ok == eok and np.array_equal(idx, np.flatnonzero(eout))
         assert np.abs(T - eT).max() < TOL
+
+
+def test_far_off_initial_pose_rejects_steps(ctx, oracle):
+    """frames that start 0.8 rad / 2 m off: the loop rejects steps and cuts the radius (shown on the oracle in
+    tests/test_pnp_cases_cpu.py); 10 iterations, one launch"""
+    frames = pnp_cases.cases()
+    mvg = MultiViewGeometry(ctx)
+    ok, T, outs, it = mvg.ceresPnP_batch([p["unpx"] for p in frames], [p["wpts"] for p in frames],
+                                         np.stack([p["Twc0"] for p in frames]), pnp_cases.MAX_ITERS, 5.9915, True, True,
+                                         np.stack([p["K"] for p in frames]))
+    for b, p in enumerate(frames):
+        eok, eT, eout, eit = pnp_cases.solve_oracle(oracle, p)
+        assert ok[b] == eok, b
+        assert np.array_equal(outs[b], eout), b
+        assert tuple(it[b]) == eit, b
+        assert np.abs(T[b] - eT).max() < TOL, b
 
 
 def test_invalid_arguments(ctx):
