@@ -462,7 +462,15 @@ ov2_status ov2_epipolar_filter_batch_dev(ov2_ctx *ctx, int B, const int32_t *d_o
  * of a draw it scores 1 under every candidate, an exact tie that falls to the first candidate in root order (ascending
  * cos(theta)).  Only real roots of Kneip's
  * quartic give candidates (OpenGV takes the real parts of complex ones), and each candidate is polished on the three
- * distance constraints.  OpenGV's nonlinear refinement (boptimize) is not built: the callers refuse it.
+ * distance constraints.
+ * DEVIATION, do_optimize / boptimize: OpenGV's optimizeModelCoefficients is not restated (its source is not in the reference
+ * tree, and its cost -- the sum of SQUARED 1 - f.p -- is quartic in the angular error and flat at the minimum).  What takes its
+ * place after a successful RANSAC or LMedS is a pixel-space motion-only solve on the inliers: ov2_pnp_solve_batch with
+ * unpx = (fx bx / bz, fy by / bz) formed from the bearings, K = (fx, fy, 0, 0) (no principal point is known here and it
+ * cancels), scales = NULL, 10 iterations, chi2th = 5.9915, robust, no L2 re-solve; inliers with bz <= 0 stay out, its outlier
+ * flags are ignored (the outlier mask stays this call's), and the pose stays this call's when the solve returns success = 0.
+ * That is a second call, made by the caller: ov2::LoopCloser::refineP3P of the host mirror (LoopCloser::p3pRansac,
+ * verifyLoopCandidates).  The static MultiViewGeometry::p3pRansac wrappers still refuse boptimize (OV2_ERR_UNSUPPORTED).
  * nmaxiter outside [0, OV2_P3P_MAX_ITER] and B above OV2_P3P_MAX_BATCH are OV2_ERR_INVALID (a call looks at at most
  * 11 nmaxiter + 1 draws per frame). */
 #define OV2_P3P_MAX_ITER (1 << 20)
@@ -867,6 +875,69 @@ typedef struct ov2_match_input {
  * candidate with the smallest distance, the later one on ties (:754-771).  Host pointers, synchronous. */
 ov2_status ov2_match_to_map(ov2_ctx *ctx, const ov2_match_input *in, float fmaxprojerr, float fdistratio,
                             int32_t *match_cand /* n_kp */, float *match_dist /* n_kp */);
+
+/* LoopCloser::matchToMap(frame, Tcw, fmaxprojerr, fdistratio, vmatchedkpids, set_local_lmids) (include/loop_closer.hpp,
+ * src/loop_closer.cpp:586-763) for B candidate pairs in one call.  It is NOT Mapper::matchToMap: the projection pose is an
+ * argument (Twc, one per pair: the P3P result, not the frame's stored pose), dmaxpxdist = fmaxprojerr is never doubled,
+ * there is no mean-reprojection gate (so no kp_kf_px / kf_Twc arrays), and keypoints already matched are masked out.
+ *
+ * Layout: pair b owns keypoints kp_off[b] .. kp_off[b + 1] and candidates cand_off[b] .. cand_off[b + 1] of the flat arrays
+ * (n_kp = kp_off[B], n_cand = cand_off[B]); the *_ptr arrays are prefix offsets over the WHOLE flat arrays (n + 1 entries).
+ * Keypoints = the new keyframe's keypoints (kp.lmid_ >= 0); kp_matched[k] != 0 where the keypoint's lmid is in
+ * vmatchedkpids (:672-675); an EMPTY descriptor range = the keypoint's map point is gone or has no descriptor (:690-695).
+ * Candidates = set_local_lmids in the order the caller walks it (the order decides ties), WITHOUT those the frame observes,
+ * that are gone, not 3-D or isBad() (:614-624); an empty descriptor range = desc_.empty() (:629).  Keyframe lists =
+ * MapPoint::set_kfids_, ascending.  grid: one CSR grid per pair, pair b's cells at grid_ptr[b * ncells .. (b + 1) * ncells]
+ * (ncells = ceil(img_w / cell) * ceil(img_h / cell), row-major, B * ncells + 1 entries over the flat grid_kp); grid_kp holds
+ * keypoint indices WITHIN the pair, in Frame::vgridkps_ order (it decides ties).  One camera per call.
+ *
+ * Per candidate, in the reference's order: descriptors present (:629), z < 0.1 (:636), the view angle (:640-644),
+ * Frame::projCamToImageDist with the lens model (:646), isInImage (:648), the 2 x 2 cells of
+ * Frame::getSurroundingKeypoints(cv::Point2f) (src/frame.cpp:624-650; cells with r < 0, c < 0 or index >= ncells are
+ * skipped, as ov2_match_to_map does).  Per keypoint: the matched mask BEFORE the pixel gate, pxdist > dmaxpxdist (:683),
+ * map point present with descriptors, never co-observed (a merge of the two ascending keyframe lists, :697-707),
+ * MapPoint::computeMinDescDist (minimum over both descriptor sets).  Best / second best are replayed in keypoint order with
+ * `<=` and the 0.9 ratio (:711-728); per keypoint the smallest distance wins, the LATER candidate on ties (:743-760).
+ * Thresholds: view_th is formed AS WRITTEN at :595-605 -- vfov / hfov are PRODUCTS 0.5 * img_h * fy and 0.5 * img_w * fx
+ * (double, stored to float), atan(hfov) is taken in both branches, cos in float -- which leaves a threshold of ~1e-5 that
+ * hardly gates anything: restated, not fixed.  mindist = (float)((double)(32.f * fdistratio) * 8.) (:656).
+ *
+ * match_cand[k] = the candidate's index WITHIN ITS OWN PAIR, or -1; match_dist[k] = its Hamming distance (0 with -1).
+ * Only integers and gate decisions come out: the results are bit-identical whatever the batch composition (a pair alone =
+ * its slot in any batch), the workgroup shape and the form (host / _dev).
+ * Host form: host pointers (cam included), one staging block, one synchronisation.  B = 0, a pair without keypoints and a
+ * pair without candidates are OV2_OK (and write -1); negative counts, decreasing offsets, a grid entry outside its pair and
+ * null arrays that a non-empty call needs are OV2_ERR_INVALID.
+ * _dev form: every array pointer of `in` is a DEVICE pointer (cam stays a host pointer) and n_kp / n_cand must be given;
+ * d_work = n_kp 64-bit words of scratch; descriptor arrays 8-byte aligned; nothing is synchronised and the arrays are not
+ * read on the host, so the _dev form trusts the offsets (a grid entry outside its pair is still skipped). */
+typedef struct ov2_loop_match_input {
+    int32_t B;
+    int32_t n_kp, n_cand;          /* totals (host form: checked against kp_off[B] / cand_off[B]) */
+    double K[4];
+    int32_t img_w, img_h, cell;
+    const ov2_cam_model *cam;      /* HOST pointer in both forms, NULL = pinhole K */
+    const double *Twc;             /* B x 7 [t, qx qy qz qw] */
+    const int32_t *kp_off;         /* B + 1 */
+    const int32_t *cand_off;       /* B + 1 */
+    const float *kp_px;            /* n_kp x 2 */
+    const uint8_t *kp_matched;     /* n_kp */
+    const int32_t *kp_desc_ptr;    /* n_kp + 1 */
+    const uint8_t *kp_descs;
+    const int32_t *kp_kf_ptr;      /* n_kp + 1 */
+    const int32_t *kp_kfids;
+    const int32_t *grid_ptr;       /* B * ncells + 1 */
+    const int32_t *grid_kp;        /* keypoint indices within the pair */
+    const double *cand_wpt;        /* n_cand x 3 */
+    const int32_t *cand_desc_ptr;  /* n_cand + 1 */
+    const uint8_t *cand_descs;
+    const int32_t *cand_kf_ptr;    /* n_cand + 1 */
+    const int32_t *cand_kfids;
+} ov2_loop_match_input;
+ov2_status ov2_loop_match_to_map_batch(ov2_ctx *ctx, const ov2_loop_match_input *in, float fmaxprojerr, float fdistratio,
+                                       int32_t *match_cand /* n_kp */, float *match_dist /* n_kp */);
+ov2_status ov2_loop_match_to_map_batch_dev(ov2_ctx *ctx, const ov2_loop_match_input *in, float fmaxprojerr, float fdistratio,
+                                           uint64_t *d_work /* n_kp */, int32_t *d_match_cand, float *d_match_dist);
 
 /* ---- diagnostics -----------------------------------------------------------------------------------
  * Reads a device buffer of nrows x stride_bytes exactly once with the access pattern of the KLT window staging (each lane of

@@ -384,7 +384,8 @@ const char *ov2_kernel_names[OV2_K_MAX] = {"clahe_lut_kernel", "level0_kernel", 
                                            "detect_list_kernels", "map_setup_kernels", "tri_kernel", "stereo_sad_kernel",
                                            "stereo_gate_kernel", "brief_kernel", "match_kernels", "pose_graph_kernel",
                                            "epipolar_kernel", "fivept_dbg_kernel", "p3p_solve_kernel", "p3p_select_kernel",
-                                           "p3p_score_kernel", "p3p_final_kernel", "p3p_dbg_kernel", "knn2_kernel"};
+                                           "p3p_score_kernel", "p3p_final_kernel", "p3p_dbg_kernel", "knn2_kernel",
+                                           "loop_match_kernels"};
 
 static hipEvent_t ktime_event(ov2_ctx *c)
 {

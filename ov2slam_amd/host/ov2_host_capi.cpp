@@ -228,6 +228,186 @@ int ov2h_loop_assemble(void *p, int newkf, int lckf, int cap, int *n, int *query
     return 0;
 }
 
+// what LoopCloser::trackLoopLocalMap assembles for the pair (newkf, lckf) in front of its matcher (assembleLoopLocalMap), no
+// GPU context needed.  pairs_in (n_in x 2): the incoming vkplmids.  pairs_out (cap x 2): vkplmids with the identity pairs
+// appended; matched / local / cands (cap each): vmatchedkpids, the local set and the candidates offered to the matcher, the
+// last two in the mirror's order of first encounter.  n[4] = their counts; OV2_ERR_INVALID when one exceeds cap
+int ov2h_loop_local_map(void *p, int newkf, int lckf, int n_in, const int *pairs_in, int cap, int *n, int *pairs_out, int *matched,
+                        int *local, int *cands)
+{
+    HostMap *m = (HostMap *)p;
+    auto a = m->map->getKeyframe(newkf), b = m->map->getKeyframe(lckf);
+    if (!a || !b || n_in < 0) return (int)OV2_ERR_INVALID;
+    LoopCloser lc(nullptr, m->st, m->map);
+    std::vector<std::pair<int, int>> v((size_t)n_in);
+    for (int i = 0; i < n_in; ++i) v[i] = {pairs_in[2 * i], pairs_in[2 * i + 1]};
+    LoopLocalMap in;
+    lc.assembleLoopLocalMap(*a, *b, v, in);
+    n[0] = (int)v.size(); n[1] = (int)in.vmatchedkpids.size(); n[2] = (int)in.vlocal.size(); n[3] = (int)in.vcands.size();
+    if (n[0] > cap || n[1] > cap || n[2] > cap || n[3] > cap) return (int)OV2_ERR_INVALID;
+    for (size_t i = 0; i < v.size(); ++i) { pairs_out[2 * i] = v[i].first; pairs_out[2 * i + 1] = v[i].second; }
+    std::copy(in.vmatchedkpids.begin(), in.vmatchedkpids.end(), matched);
+    std::copy(in.vlocal.begin(), in.vlocal.end(), local);
+    std::copy(in.vcands.begin(), in.vcands.end(), cands);
+    return in.n_identity;
+}
+
+// LoopCloser::trackLoopLocalMaps on B jobs (newkf[b], lckf[b], Twc (B x 7), the incoming pair lists one after the other:
+// n_in[b] pairs each in pairs_in).  pairs_out (cap x 2): the lists after tracking, job after job, n_out[b] pairs each; counts
+// (B x 3): identity pairs appended, candidates offered, matches appended; stats[3]: jobs, offered to the matcher, launches.
+// Returns 0 or a negative ov2_status (OV2_ERR_INVALID also when cap is too small)
+int ov2h_loop_track(void *p, void *ctx, int B, const int *newkf, const int *lckf, const double *Twc7, float maxdist, float ratio,
+                    const int *n_in, const int *pairs_in, int cap, int *n_out, int *pairs_out, int *counts, int *stats)
+{
+    HostMap *m = (HostMap *)p;
+    if (B < 0) return (int)OV2_ERR_INVALID;
+    LoopCloser lc((ov2_ctx *)ctx, m->st, m->map);
+    std::vector<LoopTrackJob> jobs((size_t)B);
+    size_t o = 0;
+    for (int b = 0; b < B; ++b) {
+        jobs[b].newkfid = newkf[b]; jobs[b].lckfid = lckf[b];
+        for (int i = 0; i < 7; ++i) jobs[b].Twc.v[i] = Twc7[7 * b + i];
+        if (n_in[b] < 0) return (int)OV2_ERR_INVALID;
+        for (int i = 0; i < n_in[b]; ++i, ++o) jobs[b].vkplmids.push_back({pairs_in[2 * o], pairs_in[2 * o + 1]});
+    }
+    const ov2_status s = lc.trackLoopLocalMaps(jobs, maxdist, ratio);
+    if (s != OV2_OK) return (int)s;
+    o = 0;
+    for (int b = 0; b < B; ++b) {
+        const LoopTrackJob &j = jobs[b];
+        if (o + j.vkplmids.size() > (size_t)cap) return (int)OV2_ERR_INVALID;
+        n_out[b] = (int)j.vkplmids.size();
+        counts[3 * b] = j.n_identity; counts[3 * b + 1] = j.n_offered; counts[3 * b + 2] = j.n_matched;
+        for (const auto &q : j.vkplmids) { pairs_out[2 * o] = q.first; pairs_out[2 * o + 1] = q.second; ++o; }
+    }
+    stats[0] = lc.last_track_.pairs; stats[1] = lc.last_track_.match_pairs; stats[2] = lc.last_track_.match_calls;
+    return 0;
+}
+
+// LoopCloser::computePnP (:834-897) on keyframe kfid with n pairs (kpid, lmid) and the start pose Twc7 (updated in place);
+// outidx (cap): the n_out_in indices it is given followed by those it appends, *n_out their count.  Returns its bool (0 / 1)
+// or a negative ov2_status
+int ov2h_loop_compute_pnp(void *p, void *ctx, int kfid, int n, const int *pairs, double *Twc7, int n_out_in, int cap, int *outidx, int *n_out)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kfid);
+    if (!f || n < 0 || n_out_in < 0 || n_out_in > cap) return (int)OV2_ERR_INVALID;
+    LoopCloser lc((ov2_ctx *)ctx, m->st, m->map);
+    std::vector<std::pair<int, int>> v((size_t)n);
+    for (int i = 0; i < n; ++i) v[i] = {pairs[2 * i], pairs[2 * i + 1]};
+    std::vector<int> out(outidx, outidx + n_out_in);
+    SE3 T;
+    for (int i = 0; i < 7; ++i) T.v[i] = Twc7[i];
+    const bool ok = lc.computePnP(*f, v, T, out);
+    if (out.size() > (size_t)cap) return (int)OV2_ERR_INVALID;
+    for (int i = 0; i < 7; ++i) Twc7[i] = T.v[i];
+    std::copy(out.begin(), out.end(), outidx);
+    *n_out = (int)out.size();
+    return ok ? 1 : 0;
+}
+
+// One LoopVerifyResult as flat arrays.  ints[13]: branch (ov2::LoopVerifyBranch), P3P status (-1 = not run), its info[4], pairs after
+// P3P, after tracking, at the end, identity pairs appended, candidates offered, matches found, computePnP outliers; dbl[15]: Twc after
+// P3P + refinement, final Twc, lc_pose_err; lists: the three pair lists (2 ints per pair) and the outlier indices, one after the
+// other, appended at *used (capacity cap ints).  false = cap too small
+static bool pack_verify(const LoopVerifyResult &r, int *ints, double *dbl, int cap, int *lists, size_t *used)
+{
+    ints[0] = r.branch; ints[1] = r.p3p_status; std::copy(r.p3p_info, r.p3p_info + 4, ints + 2);
+    ints[6] = (int)r.vkplmids_p3p.size(); ints[7] = (int)r.vkplmids_track.size(); ints[8] = (int)r.vkplmids.size();
+    ints[9] = r.n_identity; ints[10] = r.n_offered; ints[11] = r.n_matched; ints[12] = (int)r.pnp_outliers.size();
+    std::copy(r.Twc_p3p.v.begin(), r.Twc_p3p.v.end(), dbl); std::copy(r.Twc.v.begin(), r.Twc.v.end(), dbl + 7); dbl[14] = r.lc_pose_err;
+    const size_t need = 2 * (r.vkplmids_p3p.size() + r.vkplmids_track.size() + r.vkplmids.size()) + r.pnp_outliers.size();
+    if (*used + need > (size_t)cap) return false;
+    int *o = lists + *used;
+    for (const auto *v : {&r.vkplmids_p3p, &r.vkplmids_track, &r.vkplmids})
+        for (const auto &q : *v) { *o++ = q.first; *o++ = q.second; }
+    for (int i : r.pnp_outliers) *o++ = i;
+    *used += need;
+    return true;
+}
+
+static void loop_params(HostMap *m, int nransac_iter, float fransac_err) { m->st->nransac_iter_ = nransac_iter; m->st->fransac_err_ = fransac_err; }
+
+// LoopCloser::verifyLoopCandidates on B pairs (newkf[b], lckf[b]) with their incoming lists one after the other (n_in[b] pairs
+// each in pairs_in) and one sampler seed each.  ints (B x 13), dbl (B x 15), lists (cap ints): pack_verify, pair after pair.
+// stats[8]: pairs that reached P3P, the refinement, the matcher, computePnP, and the library calls of each stage.
+// Returns 0 or a negative ov2_status (OV2_ERR_INVALID also when cap is too small)
+int ov2h_loop_verify(void *p, void *ctx, int B, const int *newkf, const int *lckf, const int *n_in, const int *pairs_in,
+                     const unsigned long long *seeds, int nransac_iter, float fransac_err, int cap, int *ints, double *dbl, int *lists,
+                     int *stats)
+{
+    HostMap *m = (HostMap *)p;
+    if (B < 0) return (int)OV2_ERR_INVALID;
+    loop_params(m, nransac_iter, fransac_err);
+    LoopCloser lc((ov2_ctx *)ctx, m->st, m->map);
+    std::vector<std::pair<int, int>> pairs((size_t)B);
+    std::vector<std::vector<std::pair<int, int>>> vl((size_t)B);
+    std::vector<uint64_t> sd((size_t)B);
+    size_t o = 0;
+    for (int b = 0; b < B; ++b) {
+        pairs[b] = {newkf[b], lckf[b]}; sd[b] = (uint64_t)seeds[b];
+        if (n_in[b] < 0) return (int)OV2_ERR_INVALID;
+        for (int i = 0; i < n_in[b]; ++i, ++o) vl[b].push_back({pairs_in[2 * o], pairs_in[2 * o + 1]});
+    }
+    std::vector<LoopVerifyResult> out;
+    const ov2_status s = lc.verifyLoopCandidates(pairs, vl, sd, out);
+    if (s != OV2_OK) return (int)s;
+    size_t used = 0;
+    for (int b = 0; b < B; ++b)
+        if (!pack_verify(out[b], ints + 13 * b, dbl + 15 * b, cap, lists, &used)) return (int)OV2_ERR_INVALID;
+    const LoopStats &L = lc.last_;
+    const int st[8] = {L.p3p_pairs, L.refine_pairs, L.track_pairs, L.pnp_pairs, L.p3p_calls, L.refine_calls, L.track_calls, L.pnp_calls};
+    std::copy(st, st + 8, stats);
+    return 0;
+}
+
+// LoopCloser::verifyLoopCandidate, the reference-shaped call on one pair (a call and a synchronisation per stage); outputs as
+// one row of ov2h_loop_verify
+int ov2h_loop_verify_candidate(void *p, void *ctx, int newkf, int lckf, int n_in, const int *pairs_in, unsigned long long seed,
+                               int nransac_iter, float fransac_err, int cap, int *ints, double *dbl, int *lists)
+{
+    HostMap *m = (HostMap *)p;
+    if (n_in < 0) return (int)OV2_ERR_INVALID;
+    loop_params(m, nransac_iter, fransac_err);
+    LoopCloser lc((ov2_ctx *)ctx, m->st, m->map);
+    std::vector<std::pair<int, int>> v((size_t)n_in);
+    for (int i = 0; i < n_in; ++i) v[i] = {pairs_in[2 * i], pairs_in[2 * i + 1]};
+    LoopVerifyResult r;
+    const ov2_status s = lc.verifyLoopCandidate(newkf, lckf, v, (uint64_t)seed, r);
+    if (s != OV2_OK) return (int)s;
+    size_t used = 0;
+    return pack_verify(r, ints, dbl, cap, lists, &used) ? 0 : (int)OV2_ERR_INVALID;
+}
+
+// LoopCloser::processLoopCandidates on B pairs: branch (B, ov2::LoopBranch of the 2D-2D half), n_passed (B: pairs it passed on),
+// then the rows of ov2h_loop_verify (a pair that did not pass keeps the row of an untouched LoopVerifyResult); stats[13]: the five
+// of ov2h_loop_match followed by the eight of ov2h_loop_verify
+int ov2h_loop_process(void *p, void *ctx, int B, const int *newkf, const int *lckf, const unsigned long long *seeds, int nransac_iter,
+                      float fransac_err, int cap, int *branch, int *n_passed, int *ints, double *dbl, int *lists, int *stats)
+{
+    HostMap *m = (HostMap *)p;
+    if (B < 0) return (int)OV2_ERR_INVALID;
+    loop_params(m, nransac_iter, fransac_err);
+    LoopCloser lc((ov2_ctx *)ctx, m->st, m->map);
+    std::vector<std::pair<int, int>> pairs((size_t)B);
+    std::vector<uint64_t> sd((size_t)B);
+    for (int b = 0; b < B; ++b) { pairs[b] = {newkf[b], lckf[b]}; sd[b] = (uint64_t)seeds[b]; }
+    std::vector<LoopPairResult> matched;
+    std::vector<LoopVerifyResult> out;
+    const ov2_status s = lc.processLoopCandidates(pairs, sd, matched, out);
+    if (s != OV2_OK) return (int)s;
+    size_t used = 0;
+    for (int b = 0; b < B; ++b) {
+        branch[b] = matched[b].branch; n_passed[b] = (int)matched[b].vkplmids.size();
+        if (!pack_verify(out[b], ints + 13 * b, dbl + 15 * b, cap, lists, &used)) return (int)OV2_ERR_INVALID;
+    }
+    const LoopStats &L = lc.last_;
+    const int st[13] = {L.pairs, L.knn_pairs, L.epi_pairs, L.knn_calls, L.epi_calls, L.p3p_pairs, L.refine_pairs, L.track_pairs, L.pnp_pairs,
+                        L.p3p_calls, L.refine_calls, L.track_calls, L.pnp_calls};
+    std::copy(st, st + 13, stats);
+    return 0;
+}
+
 // LoopCloser::acceptMatch (the ratio test of knnMatching, :434-442); d1 < 0 = fewer than two neighbours
 int ov2h_loop_accept(int d0, int d1) { return LoopCloser::acceptMatch(d0, d1) ? 1 : 0; }
 

@@ -826,6 +826,472 @@ void LoopCloser::removeOutliers(std::vector<std::pair<int, int>> &vkplmids, std:
     voutliers_idx.clear();
 }
 
+void LoopCloser::assembleLoopLocalMap(const Frame &newkf, const Frame &lckf, std::vector<std::pair<int, int>> &vkplmids, LoopLocalMap &in) const
+{   // src/loop_closer.cpp:502-568, then :612-631
+    in = LoopLocalMap();
+    std::unordered_set<int> set_checked_kpids, set_local;
+    std::vector<int> vlocal;                                                            // set_local_lmids, order of first encounter
+    auto lccov_map = lckf.getCovisibleKfMap();                                          // :507
+    lccov_map[lckf.kfid_] = 100;                                                        // :509
+    for (const auto &cokf : lccov_map) {                                                // :514, ascending kfid
+        const int kfid = cokf.first;
+        if (kfid < lckf.kfid_ - 15) continue;                                           // :518-522
+        else if (kfid > lckf.kfid_ + 15) break;
+        auto pcokf = pmap_->getKeyframe(kfid);                                          // :524-527
+        if (pcokf == nullptr) continue;
+        for (const auto &kp : pcokf->getKeypoints3d()) {                                // :533
+            if (!set_checked_kpids.insert(kp.lmid_).second) continue;                   // :535-539
+            if (newkf.isObservingKp(kp.lmid_)) {                                        // :543-548
+                const std::pair<int, int> kplmid(kp.lmid_, kp.lmid_);
+                if (std::find(vkplmids.begin(), vkplmids.end(), kplmid) == vkplmids.end()) { vkplmids.push_back(kplmid); ++in.n_identity; }
+            } else if (set_local.insert(kp.lmid_).second) {                             // :550
+                vlocal.push_back(kp.lmid_);
+            }
+        }
+    }
+    in.vmatchedkpids.reserve(vkplmids.size());
+    for (const auto &kplmid : vkplmids) {                                               // :559-562
+        in.vmatchedkpids.push_back(kplmid.first);
+        set_local.erase(kplmid.second);
+    }
+    for (const int lmid : vlocal)
+        if (set_local.count(lmid)) in.vlocal.push_back(lmid);
+    for (const int lmid : in.vlocal) {                                                  // :612-631
+        if (newkf.isObservingKp(lmid)) continue;
+        auto plm = pmap_->getMapPoint(lmid);
+        if (plm == nullptr) continue;
+        else if (!plm->is3d_ || plm->isBad()) continue;
+        if (!plm->has_desc_) continue;
+        in.vcands.push_back(lmid);
+    }
+}
+
+ov2_status LoopCloser::trackLoopLocalMaps(std::vector<LoopTrackJob> &jobs, float maxdist, float ratio)
+{   // src/loop_closer.cpp:502-583 for B pairs; the matcher (:586-763) is one ov2_loop_match_to_map_batch call
+    last_track_ = LoopTrackStats();
+    last_track_.pairs = (int)jobs.size();
+    struct Slot { int job; std::vector<int> kp_lmid, cand_lmid; };
+    std::vector<Slot> slots;                      // the jobs that reach the matcher, in job order
+    std::vector<double> Twc, cand_wpt;
+    std::vector<int32_t> kp_off(1, 0), cand_off(1, 0), kp_desc_ptr(1, 0), kp_kf_ptr(1, 0), kp_kfids, grid_ptr(1, 0), grid_kp;
+    std::vector<int32_t> cand_desc_ptr(1, 0), cand_kf_ptr(1, 0), cand_kfids;
+    std::vector<float> kp_px;
+    std::vector<uint8_t> kp_matched, kp_descs, cand_descs;
+    const CameraCalibration *cam0 = nullptr;
+    size_t cell = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        LoopTrackJob &job = jobs[j];
+        job.n_identity = job.n_offered = job.n_matched = 0;
+        auto pnewkf = pmap_->getKeyframe(job.newkfid), plckf = pmap_->getKeyframe(job.lckfid);
+        if (!pnewkf || !plckf) return OV2_ERR_INVALID;
+        const Frame &newkf = *pnewkf;
+        LoopLocalMap in;
+        assembleLoopLocalMap(newkf, *plckf, job.vkplmids, in);                          // :502-568, :612-631
+        job.n_identity = in.n_identity; job.n_offered = (int)in.vcands.size();
+        if (in.vcands.empty()) continue;                                                // :591-593 (nothing to offer)
+        if (!newkf.ncellsize_ || !newkf.pcalib_leftcam_) return OV2_ERR_INVALID;
+        if (!cam0) { cam0 = newkf.pcalib_leftcam_.get(); cell = newkf.ncellsize_; }
+        else if (cam0 != newkf.pcalib_leftcam_.get() || cell != newkf.ncellsize_) return OV2_ERR_INVALID;
+        Slot s;
+        s.job = (int)j;
+        // keypoints: every keypoint of the new keyframe in grid order, so that the cells list them contiguously
+        const std::unordered_set<int> matched(in.vmatchedkpids.begin(), in.vmatchedkpids.end());
+        for (const auto &gcell : newkf.vgridkps_) {
+            for (int lmid : gcell) {
+                auto it = newkf.mapkps_.find(lmid);
+                if (it == newkf.mapkps_.end()) continue;
+                const Keypoint &kp = it->second;
+                grid_kp.push_back((int32_t)s.kp_lmid.size());
+                s.kp_lmid.push_back(lmid);
+                kp_px.push_back(kp.px_.x); kp_px.push_back(kp.px_.y);
+                kp_matched.push_back(matched.count(lmid) ? 1 : 0);                      // :672-675
+                auto pkplm = pmap_->getMapPoint(lmid);
+                if (pkplm && pkplm->has_desc_) {                                        // :690-695: else an empty range
+                    for (const auto &kd : pkplm->map_kf_desc_) kp_descs.insert(kp_descs.end(), kd.second.begin(), kd.second.end());
+                    for (int kfid : pkplm->getKfObsSet()) kp_kfids.push_back(kfid);
+                }
+                kp_desc_ptr.push_back((int32_t)(kp_descs.size() / 32));
+                kp_kf_ptr.push_back((int32_t)kp_kfids.size());
+            }
+            grid_ptr.push_back((int32_t)grid_kp.size());
+        }
+        for (const int lmid : in.vcands) {                                              // already filtered (:614-631)
+            auto plm = pmap_->getMapPoint(lmid);
+            const Vec3 w = plm->getPoint();
+            s.cand_lmid.push_back(lmid);
+            cand_wpt.push_back(w.x); cand_wpt.push_back(w.y); cand_wpt.push_back(w.z);
+            for (const auto &kd : plm->map_kf_desc_) cand_descs.insert(cand_descs.end(), kd.second.begin(), kd.second.end());
+            for (int kfid : plm->getKfObsSet()) cand_kfids.push_back(kfid);
+            cand_desc_ptr.push_back((int32_t)(cand_descs.size() / 32));
+            cand_kf_ptr.push_back((int32_t)cand_kfids.size());
+        }
+        kp_off.push_back(kp_off.back() + (int32_t)s.kp_lmid.size());
+        cand_off.push_back(cand_off.back() + (int32_t)s.cand_lmid.size());
+        Twc.insert(Twc.end(), job.Twc.v.begin(), job.Twc.v.end());
+        slots.push_back(std::move(s));
+    }
+    last_track_.match_pairs = (int)slots.size();
+    if (slots.empty() || kp_off.back() == 0) return OV2_OK;
+    ov2_loop_match_input in;
+    memset(&in, 0, sizeof(in));
+    in.B = (int32_t)slots.size(); in.n_kp = kp_off.back(); in.n_cand = cand_off.back();
+    in.K[0] = cam0->fx_; in.K[1] = cam0->fy_; in.K[2] = cam0->cx_; in.K[3] = cam0->cy_;
+    in.img_w = (int32_t)cam0->img_w_; in.img_h = (int32_t)cam0->img_h_; in.cell = (int32_t)cell;
+    ov2_cam_model cam;
+    in.cam = cam0->fillCamModel(&cam) ? &cam : nullptr;
+    in.Twc = Twc.data(); in.kp_off = kp_off.data(); in.cand_off = cand_off.data();
+    in.kp_px = kp_px.data(); in.kp_matched = kp_matched.data(); in.kp_desc_ptr = kp_desc_ptr.data(); in.kp_descs = kp_descs.data();
+    in.kp_kf_ptr = kp_kf_ptr.data(); in.kp_kfids = kp_kfids.data(); in.grid_ptr = grid_ptr.data(); in.grid_kp = grid_kp.data();
+    in.cand_wpt = cand_wpt.data(); in.cand_desc_ptr = cand_desc_ptr.data(); in.cand_descs = cand_descs.data();
+    in.cand_kf_ptr = cand_kf_ptr.data(); in.cand_kfids = cand_kfids.data();
+    std::vector<int32_t> match_cand((size_t)in.n_kp, -1);
+    std::vector<float> match_dist((size_t)in.n_kp, 0.f);
+    const ov2_status st = ov2_loop_match_to_map_batch(ctx_, &in, maxdist, ratio, match_cand.data(), match_dist.data());   // :570
+    if (st != OV2_OK) return st;
+    last_track_.match_calls = 1;
+    for (size_t b = 0; b < slots.size(); ++b) {                                         // :576-582
+        const Slot &s = slots[b];
+        std::map<int, int> map_previd_newid;
+        for (size_t k = 0; k < s.kp_lmid.size(); ++k) {
+            const int c = match_cand[(size_t)kp_off[b] + k];
+            if (c >= 0) map_previd_newid.emplace(s.kp_lmid[k], s.cand_lmid[(size_t)c]);
+        }
+        LoopTrackJob &job = jobs[(size_t)s.job];
+        for (const auto &kpid_lmid : map_previd_newid) job.vkplmids.push_back(std::pair<int, int>(kpid_lmid.first, kpid_lmid.second));
+        job.n_matched = (int)map_previd_newid.size();
+    }
+    return OV2_OK;
+}
+
+ov2_status LoopCloser::trackLoopLocalMap(const Frame &newkf, const Frame &lckf, const SE3 &Twc, float maxdist, float ratio,
+                                         std::vector<std::pair<int, int>> &vkplmids)
+{   // :502-583
+    std::vector<LoopTrackJob> jobs(1);
+    jobs[0].newkfid = newkf.kfid_; jobs[0].lckfid = lckf.kfid_; jobs[0].Twc = Twc; jobs[0].vkplmids = vkplmids;
+    const ov2_status s = trackLoopLocalMaps(jobs, maxdist, ratio);
+    if (s == OV2_OK) vkplmids = jobs[0].vkplmids;
+    last_track_job_ = jobs[0];
+    last_track_job_.vkplmids.clear();
+    return s;
+}
+
+bool LoopCloser::computePnP(const Frame &frame, const std::vector<std::pair<int, int>> &vkplmids, SE3 &Twc, std::vector<int> &voutlier_idx)
+{   // src/loop_closer.cpp:834-897
+    std::vector<Vec3> vwpts;
+    std::vector<Vec2> vkps;
+    std::vector<int> vgoodkpidx, vscales, voutidx;
+    const size_t nbkps = vkplmids.size();
+    for (size_t i = 0; i < nbkps; i++) {                                                // :851-871
+        auto plm = pmap_->getMapPoint(vkplmids.at(i).second);
+        if (plm == nullptr) continue;
+        const Keypoint kp = frame.getKeypointById(vkplmids.at(i).first);
+        if (kp.lmid_ < 0) continue;
+        vgoodkpidx.push_back((int)i);
+        vscales.push_back(kp.scale_);
+        vwpts.push_back(plm->getPoint());
+        vkps.push_back(Vec2{kp.unpx_.x, kp.unpx_.y});
+    }
+    if (vkps.size() < 3) return false;                                                  // :874, :896
+    const CameraCalibration &c = *frame.pcalib_leftcam_;
+    const bool success = MultiViewGeometry::ceresPnP(ctx_, vkps, vwpts, vscales, Twc, 10, pslamstate_->robust_mono_th_, true, false,
+                                                     (float)c.fx_, (float)c.fy_, (float)c.cx_, (float)c.cy_, voutidx);   // :881-887
+    for (const int idx : voutidx) voutlier_idx.push_back(vgoodkpidx.at((size_t)idx));   // :889-891: appended, as written
+    return success;
+}
+
+ov2_status LoopCloser::refineP3P(ov2_ctx *ctx, int B, const int *n, const double *bvs, const double *wpts, const uint8_t *outlier,
+                                 const double *K, double *Twc)
+{   // stands for opengv's sac_problems::...::optimizeModelCoefficients (do_optimize): see the header
+    if (B <= 0) return OV2_OK;
+    std::vector<int> m((size_t)B, 0);
+    std::vector<double> unpx, X, Kp(4 * (size_t)B, 0.);
+    size_t o = 0;
+    for (int b = 0; b < B; ++b) {
+        Kp[4 * (size_t)b] = K[0]; Kp[4 * (size_t)b + 1] = K[1];
+        for (int i = 0; i < n[b]; ++i, ++o) {
+            const double *bv = bvs + 3 * o;
+            if (outlier[o] || !(bv[2] > 0.)) continue;
+            unpx.push_back(K[0] * bv[0] / bv[2]); unpx.push_back(K[1] * bv[1] / bv[2]);
+            X.insert(X.end(), wpts + 3 * o, wpts + 3 * o + 3);
+            ++m[b];
+        }
+    }
+    std::vector<double> T(Twc, Twc + 7 * (size_t)B);
+    std::vector<uint8_t> flags(unpx.size() / 2 + 1);
+    std::vector<int> ok((size_t)B, 0);
+    const ov2_status s = ov2_pnp_solve_batch(ctx, B, m.data(), unpx.empty() ? nullptr : unpx.data(), X.empty() ? nullptr : X.data(), nullptr,
+                                             Kp.data(), T.data(), 10, 5.9915f, 1, 0, flags.data(), ok.data(), nullptr);
+    if (s != OV2_OK) return s;
+    for (int b = 0; b < B; ++b)
+        if (ok[b]) std::copy(T.begin() + 7 * b, T.begin() + 7 * b + 7, Twc + 7 * (size_t)b);
+    return OV2_OK;
+}
+
+// :773-812 of p3pRansac: bearings and world points of the pairs whose map point exists; the others are ERASED from vkplmids
+static bool loop_p3p_inputs(const MapManager &map, const Frame &newkf, std::vector<std::pair<int, int>> &vkplmids, std::vector<double> &bvs,
+                            std::vector<double> &wpts)
+{
+    if (vkplmids.size() < 4) return false;                                              // :767
+    const size_t nbkps = vkplmids.size();
+    std::vector<int> vbadidx;
+    for (size_t i = 0; i < nbkps; i++) {                                                // :785-800
+        auto plm = map.getMapPoint(vkplmids.at(i).second);
+        if (plm == nullptr) { vbadidx.push_back((int)i); continue; }
+        const Keypoint kp = newkf.getKeypointById(vkplmids.at(i).first);
+        const Vec3 w = plm->getPoint();
+        wpts.insert(wpts.end(), {w.x, w.y, w.z});
+        bvs.insert(bvs.end(), {kp.bv_.x, kp.bv_.y, kp.bv_.z});
+    }
+    int k = 0;
+    for (const auto &badidx : vbadidx) { vkplmids.erase(vkplmids.begin() + badidx - k); k++; }   // :802-806
+    return bvs.size() / 3 >= 4;                                                         // :808
+}
+
+bool LoopCloser::p3pRansac(const Frame &newkf, std::vector<std::pair<int, int>> &vkplmids, std::vector<int> &voutliers_idx, SE3 &Twc,
+                           uint64_t seed, ov2_status *st, int *status, int *info)
+{   // src/loop_closer.cpp:765-831
+    if (st) *st = OV2_OK;
+    std::vector<double> bvs, wpts;
+    if (!loop_p3p_inputs(*pmap_, newkf, vkplmids, bvs, wpts)) return false;
+    const int n = (int)(bvs.size() / 3);
+    const double K[4] = {(double)(float)newkf.pcalib_leftcam_->fx_, (double)(float)newkf.pcalib_leftcam_->fy_, 0., 0.};   // float fx, fy (:821)
+    std::vector<uint8_t> out((size_t)n + 1);
+    int stt = 0, inf[4] = {0, 0, -1, 0};
+    SE3 T = Twc;
+    ov2_status s = ov2_p3p_ransac_batch(ctx_, 1, &n, bvs.data(), wpts.data(), K, 10 * pslamstate_->nransac_iter_, pslamstate_->fransac_err_, 0,
+                                        &seed, T.v.data(), out.data(), &stt, inf);       // :816-824
+    if (status) *status = stt;
+    if (info) std::copy(inf, inf + 4, info);
+    if (s != OV2_OK) { if (st) *st = s; return false; }
+    if (stt != 1) return false;
+    s = refineP3P(ctx_, 1, &n, bvs.data(), wpts.data(), out.data(), K, T.v.data());     // do_optimize = true (:814)
+    if (s != OV2_OK) { if (st) *st = s; return false; }
+    Twc = T;
+    for (int i = 0; i < n; ++i)
+        if (out[i]) voutliers_idx.push_back(i);
+    return true;
+}
+
+static double loop_pose_err(const Frame &newkf, const SE3 &Twc)
+{   // :318 (pnewkf_->getTcw() * Twc).log().norm()
+    double l[6];
+    se3_log(newkf.getTcw() * Twc, l);
+    double a = 0.;
+    for (double v : l) a += v * v;
+    return std::sqrt(a);
+}
+
+ov2_status LoopCloser::verifyLoopCandidate(int newkfid, int lckfid, const std::vector<std::pair<int, int>> &vkplmids_in, uint64_t seed,
+                                           LoopVerifyResult &r)
+{   // :238-300
+    r = LoopVerifyResult();
+    auto pnewkf = pmap_->getKeyframe(newkfid), plckf = pmap_->getKeyframe(lckfid);
+    if (!pnewkf || !plckf) return OV2_ERR_INVALID;
+    std::vector<std::pair<int, int>> vkplmids = vkplmids_in;
+    std::vector<int> voutliers_idx;
+    SE3 Twc = pnewkf->getTwc();                                                         // :239
+    ov2_status s = OV2_OK;
+    bool success = p3pRansac(*pnewkf, vkplmids, voutliers_idx, Twc, seed, &s, &r.p3p_status, r.p3p_info);   // :244
+    if (s != OV2_OK) return s;
+    size_t nbinliers = vkplmids.size() - voutliers_idx.size();                          // :249
+    if (!success || nbinliers < 5) return OV2_OK;                                       // :251
+    if (!voutliers_idx.empty()) removeOutliers(vkplmids, voutliers_idx);                // :260-263
+    r.vkplmids_p3p = vkplmids; r.Twc_p3p = Twc;
+    const size_t before = vkplmids.size();
+    s = trackLoopLocalMap(*pnewkf, *plckf, Twc, 10.f, pslamstate_->fmax_desc_dist_ * 1.5f, vkplmids);   // :269
+    if (s != OV2_OK) return s;
+    r.vkplmids_track = vkplmids;
+    r.n_identity = last_track_job_.n_identity; r.n_offered = last_track_job_.n_offered; r.n_matched = last_track_job_.n_matched;
+    (void)before;
+    r.branch = LV_NO_NEW_MATCHES;
+    if (!(vkplmids.size() > nbinliers)) return OV2_OK;                                  // :275, :298-300
+    success = computePnP(*pnewkf, vkplmids, Twc, voutliers_idx);                        // :277
+    r.pnp_outliers = voutliers_idx; r.Twc = Twc;
+    nbinliers = vkplmids.size() - voutliers_idx.size();                                 // :283
+    r.branch = LV_PNP_FAILED;
+    if (!success || nbinliers < 30) return OV2_OK;                                      // :288
+    if (!voutliers_idx.empty()) removeOutliers(vkplmids, voutliers_idx);                // :294-297
+    r.vkplmids = vkplmids;
+    r.branch = vkplmids.size() >= 30 ? LV_ACCEPTED : LV_FEW_GOOD;                       // :302-305
+    r.lc_pose_err = loop_pose_err(*pnewkf, Twc);
+    return OV2_OK;
+}
+
+ov2_status LoopCloser::verifyLoopCandidates(const std::vector<std::pair<int, int>> &pairs,
+                                            const std::vector<std::vector<std::pair<int, int>>> &lists, const std::vector<uint64_t> &seeds,
+                                            std::vector<LoopVerifyResult> &out)
+{   // :238-300 for B pairs, one library call per stage
+    const size_t B = pairs.size();
+    if (lists.size() != B || seeds.size() != B) return OV2_ERR_INVALID;
+    out.assign(B, LoopVerifyResult());
+    last_.p3p_pairs = last_.refine_pairs = last_.track_pairs = last_.pnp_pairs = 0;
+    last_.p3p_calls = last_.refine_calls = last_.track_calls = last_.pnp_calls = 0;
+    if (last_.pairs == 0) last_.pairs = (int)B;
+    std::vector<std::shared_ptr<Frame>> vnew(B), vlc(B);
+    std::vector<std::vector<std::pair<int, int>>> work(lists);
+    std::vector<size_t> nbinliers(B, 0);
+    // stage 1: P3P RANSAC (:244, :765-831)
+    std::vector<int> of1, n1;
+    std::vector<double> bvs, wpts, T1;
+    std::vector<uint64_t> sd;
+    const CameraCalibration *cam = nullptr;
+    for (size_t b = 0; b < B; ++b) {
+        vnew[b] = pmap_->getKeyframe(pairs[b].first); vlc[b] = pmap_->getKeyframe(pairs[b].second);
+        if (!vnew[b] || !vlc[b]) return OV2_ERR_INVALID;
+        if (!cam) cam = vnew[b]->pcalib_leftcam_.get();
+        else if (cam != vnew[b]->pcalib_leftcam_.get()) return OV2_ERR_INVALID;
+        const size_t o = bvs.size();
+        if (!loop_p3p_inputs(*pmap_, *vnew[b], work[b], bvs, wpts)) { bvs.resize(o); wpts.resize(o); continue; }
+        of1.push_back((int)b); n1.push_back((int)((bvs.size() - o) / 3)); sd.push_back(seeds[b]);
+        const SE3 T = vnew[b]->getTwc();                                                // :239
+        T1.insert(T1.end(), T.v.begin(), T.v.end());
+    }
+    last_.p3p_pairs = (int)of1.size();
+    if (of1.empty()) return OV2_OK;
+    const double K[4] = {(double)(float)cam->fx_, (double)(float)cam->fy_, 0., 0.};
+    const int P = (int)of1.size();
+    std::vector<double> Kp(4 * (size_t)P, 0.);
+    for (int e = 0; e < P; ++e) { Kp[4 * (size_t)e] = K[0]; Kp[4 * (size_t)e + 1] = K[1]; }
+    std::vector<uint8_t> outl(bvs.size() / 3 + 1);
+    std::vector<int> status((size_t)P), info(4 * (size_t)P);
+    ov2_status s = ov2_p3p_ransac_batch(ctx_, P, n1.data(), bvs.data(), wpts.data(), Kp.data(), 10 * pslamstate_->nransac_iter_,
+                                        pslamstate_->fransac_err_, 0, sd.data(), T1.data(), outl.data(), status.data(), info.data());
+    if (s != OV2_OK) return s;
+    last_.p3p_calls = 1;
+    // stage 2: the refinement on the inliers of the pairs whose RANSAC succeeded
+    std::vector<int> of2, n2;
+    std::vector<double> bv2, X2, T2;
+    std::vector<uint8_t> outl2;
+    {
+        size_t o = 0;
+        for (int e = 0; e < P; ++e) {
+            LoopVerifyResult &r = out[(size_t)of1[e]];
+            r.p3p_status = status[e];
+            std::copy(info.begin() + 4 * e, info.begin() + 4 * e + 4, r.p3p_info);
+            if (status[e] == 1) {
+                of2.push_back(e); n2.push_back(n1[e]);
+                bv2.insert(bv2.end(), bvs.begin() + 3 * o, bvs.begin() + 3 * (o + n1[e]));
+                X2.insert(X2.end(), wpts.begin() + 3 * o, wpts.begin() + 3 * (o + n1[e]));
+                outl2.insert(outl2.end(), outl.begin() + o, outl.begin() + o + n1[e]);
+                T2.insert(T2.end(), T1.begin() + 7 * e, T1.begin() + 7 * e + 7);
+            }
+            o += (size_t)n1[e];
+        }
+    }
+    last_.refine_pairs = (int)of2.size();
+    if (of2.empty()) return OV2_OK;
+    s = refineP3P(ctx_, (int)of2.size(), n2.data(), bv2.data(), X2.data(), outl2.data(), K, T2.data());
+    if (s != OV2_OK) return s;
+    last_.refine_calls = 1;
+    // :249-263, then stage 3: trackLoopLocalMap for the survivors (:269)
+    std::vector<LoopTrackJob> jobs;
+    std::vector<int> of3;
+    {
+        size_t o = 0;
+        for (size_t q = 0; q < of2.size(); ++q) {
+            const size_t b = (size_t)of1[(size_t)of2[q]];
+            LoopVerifyResult &r = out[b];
+            std::vector<int> voutliers_idx;
+            for (int i = 0; i < n2[q]; ++i)
+                if (outl2[o + i]) voutliers_idx.push_back(i);
+            o += (size_t)n2[q];
+            nbinliers[b] = work[b].size() - voutliers_idx.size();                       // :249
+            if (nbinliers[b] < 5) continue;                                             // :251
+            if (!voutliers_idx.empty()) removeOutliers(work[b], voutliers_idx);         // :260-263
+            r.vkplmids_p3p = work[b];
+            std::copy(T2.begin() + 7 * q, T2.begin() + 7 * q + 7, r.Twc_p3p.v.begin());
+            LoopTrackJob j;
+            j.newkfid = pairs[b].first; j.lckfid = pairs[b].second; j.Twc = r.Twc_p3p; j.vkplmids = work[b];
+            jobs.push_back(j); of3.push_back((int)b);
+        }
+    }
+    last_.track_pairs = (int)jobs.size();
+    if (jobs.empty()) return OV2_OK;
+    s = trackLoopLocalMaps(jobs, 10.f, pslamstate_->fmax_desc_dist_ * 1.5f);
+    if (s != OV2_OK) return s;
+    last_.track_calls = last_track_.match_calls;
+    // :275, then stage 4: computePnP for the pairs that gained matches (:277, :834-897)
+    std::vector<int> of4, n4;
+    std::vector<std::vector<int>> vgood;
+    std::vector<double> unpx, X4, T4, K4;
+    std::vector<int> scales;
+    for (size_t q = 0; q < jobs.size(); ++q) {
+        const size_t b = (size_t)of3[q];
+        LoopVerifyResult &r = out[b];
+        work[b] = jobs[q].vkplmids;
+        r.vkplmids_track = work[b];
+        r.n_identity = jobs[q].n_identity; r.n_offered = jobs[q].n_offered; r.n_matched = jobs[q].n_matched;
+        r.branch = LV_NO_NEW_MATCHES;
+        if (!(work[b].size() > nbinliers[b])) continue;                                 // :275
+        r.branch = LV_PNP_FAILED;
+        r.Twc = r.Twc_p3p;
+        std::vector<int> good;
+        const size_t o = unpx.size() / 2;
+        for (size_t i = 0; i < work[b].size(); i++) {                                   // :851-871
+            auto plm = pmap_->getMapPoint(work[b][i].second);
+            if (plm == nullptr) continue;
+            const Keypoint kp = vnew[b]->getKeypointById(work[b][i].first);
+            if (kp.lmid_ < 0) continue;
+            good.push_back((int)i);
+            scales.push_back(kp.scale_);
+            const Vec3 w = plm->getPoint();
+            X4.insert(X4.end(), {w.x, w.y, w.z});
+            unpx.push_back(kp.unpx_.x); unpx.push_back(kp.unpx_.y);
+        }
+        if (good.size() < 3) { unpx.resize(2 * o); X4.resize(3 * o); scales.resize(o); continue; }   // :874, :896: false
+        of4.push_back((int)b); n4.push_back((int)good.size()); vgood.push_back(good);
+        T4.insert(T4.end(), r.Twc_p3p.v.begin(), r.Twc_p3p.v.end());
+        K4.insert(K4.end(), {(double)(float)cam->fx_, (double)(float)cam->fy_, (double)(float)cam->cx_, (double)(float)cam->cy_});
+    }
+    last_.pnp_pairs = (int)of4.size();
+    if (of4.empty()) return OV2_OK;
+    std::vector<uint8_t> flags(unpx.size() / 2 + 1);
+    std::vector<int> ok(of4.size(), 0);
+    s = ov2_pnp_solve_batch(ctx_, (int)of4.size(), n4.data(), unpx.data(), X4.data(), scales.data(), K4.data(), T4.data(), 10,
+                            pslamstate_->robust_mono_th_, 1, 0, flags.data(), ok.data(), nullptr);   // :881-887
+    if (s != OV2_OK) return s;
+    last_.pnp_calls = 1;
+    size_t o = 0;
+    for (size_t q = 0; q < of4.size(); ++q) {
+        const size_t b = (size_t)of4[q];
+        LoopVerifyResult &r = out[b];
+        std::vector<int> voutliers_idx;
+        for (int i = 0; i < n4[q]; ++i)
+            if (flags[o + i]) voutliers_idx.push_back(vgood[q][(size_t)i]);             // :889-891
+        o += (size_t)n4[q];
+        std::copy(T4.begin() + 7 * q, T4.begin() + 7 * q + 7, r.Twc.v.begin());
+        r.pnp_outliers = voutliers_idx;
+        const size_t nbin = work[b].size() - voutliers_idx.size();                      // :283
+        if (!ok[q] || nbin < 30) continue;                                              // :288
+        if (!voutliers_idx.empty()) removeOutliers(work[b], voutliers_idx);             // :294-297
+        r.vkplmids = work[b];
+        r.branch = work[b].size() >= 30 ? LV_ACCEPTED : LV_FEW_GOOD;                    // :302-305
+        r.lc_pose_err = loop_pose_err(*vnew[b], r.Twc);
+    }
+    return OV2_OK;
+}
+
+ov2_status LoopCloser::processLoopCandidates(const std::vector<std::pair<int, int>> &pairs, const std::vector<uint64_t> &seeds,
+                                             std::vector<LoopPairResult> &matched, std::vector<LoopVerifyResult> &verified)
+{   // :184-300 for B pairs: the 2D-2D half, then the 2D-3D half for the pairs that passed it
+    ov2_status s = matchLoopCandidates(pairs, seeds, matched);
+    if (s != OV2_OK) return s;
+    verified.assign(pairs.size(), LoopVerifyResult());
+    std::vector<std::pair<int, int>> vp;
+    std::vector<std::vector<std::pair<int, int>>> vl;
+    std::vector<uint64_t> vs;
+    std::vector<size_t> of;
+    for (size_t b = 0; b < pairs.size(); ++b)
+        if (matched[b].branch == LC_PASSED) {
+            vp.push_back({pairs[b].first, matched[b].lckfid}); vl.push_back(matched[b].vkplmids); vs.push_back(seeds[b]); of.push_back(b);
+        }
+    std::vector<LoopVerifyResult> r;
+    s = verifyLoopCandidates(vp, vl, vs, r);
+    if (s != OV2_OK) return s;
+    for (size_t k = 0; k < of.size(); ++k) verified[of[k]] = r[k];
+    return OV2_OK;
+}
+
 ov2_status LoopCloser::processLoopCandidate(int newkfid, int lckfid, uint64_t seed, LoopPairResult &r)
 {   // :184-236
     r = LoopPairResult();

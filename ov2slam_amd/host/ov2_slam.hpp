@@ -14,9 +14,12 @@
 // that fails.
 //   LoopCloser (2D-2D half)         src/loop_closer.cpp:184-236  knnMatching :378-459  epipolarFiltering :462-499
 //                                   removeOutliers :899-928
+//   LoopCloser::trackLoopLocalMap   src/loop_closer.cpp:502-583  matchToMap :586-763 (ov2_loop_match_to_map_batch)
+//               computePnP          :834-897
 // Out of scope and refused loudly where reached: the mono branch of the epipolar filter.  Of loop closing, what decides
-// whether a candidate keyframe is a loop is built up to the pair list that p3pRansac would receive (LoopCloser below); the
-// frame loop calls none of it, because nothing proposes candidates yet.
+// whether a candidate keyframe is a loop is built up to the pair list that p3pRansac would receive, and from the pose it
+// returns through trackLoopLocalMap and computePnP to the accepted pose and pair list (LoopCloser below); the frame loop calls
+// none of it, because nothing proposes candidates yet.
 #pragma once
 #include "ov2_host.hpp"
 
@@ -157,15 +160,106 @@ struct LoopPairResult {
 struct LoopStats {   // one matchLoopCandidates call
     int pairs = 0, knn_pairs = 0, epi_pairs = 0;   // pairs given, offered to the matcher, offered to the 5-point filter
     int knn_calls = 0, epi_calls = 0;              // launches of each (0 or 1)
+    // verifyLoopCandidates (zero after matchLoopCandidates alone): pairs that reached P3P, the refinement, the local-map matcher
+    // and computePnP, and the library calls made for each stage (0 or 1 whatever B is)
+    int p3p_pairs = 0, refine_pairs = 0, track_pairs = 0, pnp_pairs = 0;
+    int p3p_calls = 0, refine_calls = 0, track_calls = 0, pnp_calls = 0;
+};
+
+// what the 2D-3D half of LoopCloser::processLoopCandidate did with one pair (src/loop_closer.cpp:238-300); an enum of its own,
+// LoopBranch and LoopPairResult keep their meaning
+enum LoopVerifyBranch {
+    LV_P3P_FAILED = 0,    // :251 p3pRansac false (fewer than 4 pairs, no model) or fewer than 5 inliers
+    LV_NO_NEW_MATCHES,    // :275, :298-300 trackLoopLocalMap added nothing
+    LV_PNP_FAILED,        // :288 computePnP false or fewer than 30 inliers
+    LV_FEW_GOOD,          // :305 fewer than 30 pairs left
+    LV_ACCEPTED           // the loop would be closed: Twc and vkplmids are what localPoseGraph / mergeMapPoints receive
+};
+
+struct LoopVerifyResult {
+    int branch = LV_P3P_FAILED;
+    int p3p_status = -1;                          // -1: P3P not run (fewer than 4 pairs); else the ov2_p3p_ransac_batch status
+    int p3p_info[4] = {0, 0, -1, 0};              // its info: counted draws, skipped draws, chosen draw, inliers
+    std::vector<std::pair<int, int>> vkplmids_p3p, vkplmids_track, vkplmids;   // after P3P + removeOutliers, after tracking, at the end
+    std::vector<int> pnp_outliers;                // computePnP's voutliers_idx (indices into vkplmids_track)
+    int n_identity = 0, n_offered = 0, n_matched = 0;
+    SE3 Twc_p3p, Twc;                             // after P3P + refinement; after computePnP
+    double lc_pose_err = 0.;                      // :318 |log(Tcw_new * Twc)|
+};
+
+struct LoopLocalMap {   // what trackLoopLocalMap assembles in front of its matcher (:502-568 and the candidate filter of :612-631)
+    int n_identity = 0;                 // identity pairs appended to vkplmids (:543-548)
+    std::vector<int> vmatchedkpids;     // first elements of vkplmids after those additions (:559-561)
+    std::vector<int> vlocal;            // set_local_lmids without the second elements of vkplmids (:562), ORDER OF FIRST ENCOUNTER
+    std::vector<int> vcands;            // vlocal after the candidate filter (:614-631), same order: what the matcher is offered
+};
+
+struct LoopTrackJob {   // one trackLoopLocalMap call (:269): in: the pair, the projection pose (the P3P result), vkplmids
+    int newkfid = -1, lckfid = -1;
+    SE3 Twc;
+    std::vector<std::pair<int, int>> vkplmids;   // in / out
+    int n_identity = 0, n_offered = 0, n_matched = 0;   // out: identity pairs appended, candidates offered, matches appended
+};
+
+struct LoopTrackStats {   // one trackLoopLocalMaps call
+    int pairs = 0, match_pairs = 0, match_calls = 0;   // jobs given, offered to the matcher, launches of it (0 or 1)
 };
 
 // The 2D-2D half of LoopCloser::processLoopCandidate (src/loop_closer.cpp:184-236): does the new keyframe see the same place
-// as a candidate keyframe?  The second half (:238-300: p3pRansac with refinement, trackLoopLocalMap, computePnP) is not built;
-// neither is a detector that proposes candidates (:89-181, iBoW-LCD).
+// as a candidate keyframe?  The second half (:238-300) decides it: p3pRansac with a refinement, trackLoopLocalMap, computePnP,
+// for one pair as the reference writes it (verifyLoopCandidate) and for B pairs with one library call per stage
+// (verifyLoopCandidates).  A detector that proposes candidates (:89-181, iBoW-LCD) and the calls after an accepted loop
+// (:302-372) are not chained here.
 class LoopCloser {
 public:
     LoopCloser(ov2_ctx *ctx, std::shared_ptr<SlamParams> pstate, std::shared_ptr<MapManager> pmap)
         : ctx_(ctx), pslamstate_(pstate), pmap_(pmap) {}
+    // :502-568 + :612-631, the part of trackLoopLocalMap in front of the matcher (no GPU): the candidate's covisible keyframes in
+    // ascending id with the candidate forced in, the window lckf.kfid_ +- 15 (`continue` below it, `break` above it), keyframes
+    // no longer in the map skipped, every lmid looked at once; an lmid the new keyframe observes becomes an identity pair
+    // (appended to vkplmids unless that pair is already there), the others form the local set, minus the second elements of
+    // vkplmids; then the filter the matcher applies before it projects: observed by the frame, gone, not 3D, isBad() (called
+    // as the reference calls it: it may clear is3d_), no descriptor.  The reference keeps the local set in an unordered_set,
+    // so the order in which it offers the candidates is implementation-defined; here it is a vector in ORDER OF FIRST
+    // ENCOUNTER (keyframes ascending, each keyframe's getKeypoints3d() order), and that order decides the matcher's ties.
+    void assembleLoopLocalMap(const Frame &newkf, const Frame &lckf, std::vector<std::pair<int, int>> &vkplmids, LoopLocalMap &in) const;
+    // :502-583 for B pairs: assembleLoopLocalMap on each, then ONE ov2_loop_match_to_map_batch call (one synchronisation) for
+    // the pairs that have keypoints and candidates, whatever B is; the new pairs of each job are appended to its vkplmids in
+    // ascending keypoint-lmid order (the reference's std::map).  The keypoints go to the kernel in the order of the new
+    // keyframe's grid, the candidates in vcands' order.  Every new keyframe needs a grid of one cell size and the map's one left
+    // camera (else OV2_ERR_INVALID); a keyframe that is not in the map is OV2_ERR_INVALID.
+    ov2_status trackLoopLocalMaps(std::vector<LoopTrackJob> &jobs, float maxdist, float ratio);
+    // :502-583 as written, one pair: trackLoopLocalMaps with B = 1
+    ov2_status trackLoopLocalMap(const Frame &newkf, const Frame &lckf, const SE3 &Twc, float maxdist, float ratio,
+                                 std::vector<std::pair<int, int>> &vkplmids);
+    LoopTrackStats last_track_;
+    LoopTrackJob last_track_job_;   // the counts of the last trackLoopLocalMap call (its list is not kept)
+    // :834-897 as written -> MultiViewGeometry::ceresPnP (10 iterations, robust_mono_th_, robust, no L2 re-solve): pairs whose
+    // map point is gone or whose keypoint the frame does not hold stay out, the solver's outliers are mapped back through
+    // vgoodkpidx and APPENDED to voutlier_idx; fewer than 3 correspondences: false
+    bool computePnP(const Frame &frame, const std::vector<std::pair<int, int>> &vkplmids, SE3 &Twc, std::vector<int> &voutlier_idx);
+    // :765-831 as written: pairs whose map point is gone are ERASED from vkplmids (vbadidx), fewer than 4 -> false, RANSAC with
+    // 10 * nransac_iter_ draws (ov2_p3p_ransac_batch, use_lmeds = 0), and do_optimize = true through refineP3P
+    bool p3pRansac(const Frame &newkf, std::vector<std::pair<int, int>> &vkplmids, std::vector<int> &voutliers_idx, SE3 &Twc,
+                   uint64_t seed, ov2_status *st = nullptr, int *status = nullptr, int *info = nullptr);
+    // What stands for OpenGV's optimizeModelCoefficients (do_optimize) after a successful RANSAC, for B poses in one
+    // ov2_pnp_solve_batch call: a motion-only solve on each pair's RANSAC inliers with bz > 0, pixels (fx bx / bz, fy by / bz),
+    // K = (fx, fy, 0, 0) (no principal point is known here and it cancels), no scales, 10 iterations, chi2 5.9915, robust, no
+    // L2 re-solve (computePnP's settings).  Its outlier flags are ignored; a pose whose solve returns success = 0 stays RANSAC's.
+    // n / bvs / wpts / outlier: the pairs' correspondences one after the other; Twc: B x 7, in / out
+    static ov2_status refineP3P(ov2_ctx *ctx, int B, const int *n, const double *bvs, const double *wpts, const uint8_t *outlier,
+                                const double *K, double *Twc);
+    // :238-300 as written, one pair: p3pRansac, removeOutliers, trackLoopLocalMap, computePnP, one call and one synchronisation
+    // per stage.  vkplmids: the list the 2D-2D half passed on
+    ov2_status verifyLoopCandidate(int newkfid, int lckfid, const std::vector<std::pair<int, int>> &vkplmids, uint64_t seed,
+                                   LoopVerifyResult &r);
+    // the same for B pairs: ONE ov2_p3p_ransac_batch call, ONE refinement call, ONE ov2_loop_match_to_map_batch call and ONE
+    // ov2_pnp_solve_batch call whatever B is, each for the pairs that reach that stage; the counts are kept in last_
+    ov2_status verifyLoopCandidates(const std::vector<std::pair<int, int>> &pairs, const std::vector<std::vector<std::pair<int, int>>> &lists,
+                                    const std::vector<uint64_t> &seeds, std::vector<LoopVerifyResult> &out);
+    // matchLoopCandidates, then verifyLoopCandidates for the pairs that ended LC_PASSED (against the candidate it used)
+    ov2_status processLoopCandidates(const std::vector<std::pair<int, int>> &pairs, const std::vector<uint64_t> &seeds,
+                                     std::vector<LoopPairResult> &matched, std::vector<LoopVerifyResult> &verified);
     // :380-424, the part of knnMatching in front of the matcher: identity pairs, query and train sets (no GPU)
     void assembleKnn(const Frame &newkf, const Frame &lckf, LoopKnnInputs &in) const;
     // :430-449: maxdist, the ratio test in double, (kpid, lmid) of the accepted matches appended to vkplmids; idx / dist:

@@ -154,6 +154,14 @@ def lib():
         L.ov2h_map_add_desc.argtypes = [C.c_void_p, C.c_int, C.c_int, u8]
         L.ov2h_map_set_covscore.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.ov2h_loop_assemble.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, u8, u8]
+        L.ov2h_loop_local_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip, ip, ip]
+        L.ov2h_loop_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, dp, C.c_float, C.c_float, ip, ip, C.c_int, ip, ip, ip, ip]
+        L.ov2h_loop_compute_pnp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, C.c_int, ip, ip]
+        ull = C.POINTER(C.c_ulonglong)
+        L.ov2h_loop_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, ip, ip, ull, C.c_int, C.c_float, C.c_int, ip, dp, ip, ip]
+        L.ov2h_loop_verify_candidate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, ip, C.c_ulonglong, C.c_int, C.c_float,
+                                                 C.c_int, ip, dp, ip]
+        L.ov2h_loop_process.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, ull, C.c_int, C.c_float, C.c_int, ip, ip, ip, dp, ip, ip]
         L.ov2h_loop_accept.argtypes = [C.c_int, C.c_int]
         L.ov2h_loop_remove_outliers.argtypes = [C.c_int, ip, C.c_int, ip]
         L.ov2h_loop_candidate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, C.c_int, C.c_float, C.c_int, ip, ip, ip, ip]
@@ -882,7 +890,9 @@ class FilterMap(TemporalMap):
 
 class LoopMap:
     """the C++ host map of a synth_loop.make_scene dict -- keyframes with 2D / 3D keypoints, map points with one descriptor
-    each (MapPoint::addDesc), chosen covisibility scores -- to run ov2::LoopCloser on: assemble (no GPU context), loop_match."""
+    each (MapPoint::addDesc), chosen covisibility scores -- to run ov2::LoopCloser on: assemble (no GPU context), loop_match.
+    A synth_revisit.make_local_map_scene dict adds world points, further descriptors per map point and the keypoint grid of
+    the new keyframe: local_map (no GPU context), loop_track, compute_pnp."""
 
     def __init__(self, s):
         L = lib()
@@ -896,13 +906,19 @@ class LoopMap:
             v = s["kps"][k]
             lm, uv = np.ascontiguousarray(v["lmid"], np.int32), np.ascontiguousarray(v["uv"], np.float32)
             kp3d = np.ascontiguousarray(v["kp3d"], np.uint8)
-            xyz = np.zeros((len(lm), 3))
+            xyz = np.ascontiguousarray(v["xyz"], np.float64) if "xyz" in v else np.zeros((len(lm), 3))   # world points, where the scene has them
             assert L.ov2h_map_add_kps(self.h, int(k), len(lm), lm.ctypes.data_as(ip), uv.ctypes.data_as(fp), kp3d.ctypes.data_as(u8),
                                       kp3d.ctypes.data_as(u8), _dp(xyz)) == 0
         for l, d in s["desc"].items():
             d = np.ascontiguousarray(d, np.uint8)
             kfid = min(k for k in s["kfids"] if l in s["kps"][k]["lmid"])
             assert L.ov2h_map_add_desc(self.h, int(l), int(kfid), d.ctypes.data_as(u8)) == 0
+        for l, kd in s.get("descs", {}).items():      # further descriptors of a map point, one per observing keyframe, in this order
+            for kfid, d in kd:
+                d = np.ascontiguousarray(d, np.uint8)
+                assert L.ov2h_map_add_desc(self.h, int(l), int(kfid), d.ctypes.data_as(u8)) == 0
+        for k in s.get("grid_kfs", []):               # keyframes that need their keypoint grid (Frame::vgridkps_)
+            assert L.ov2h_frame_init_grid(self.h, int(k), int(s["cell"])) == 0
         for l in s["forget_lm"]:
             L.ov2h_map_forget_landmark(self.h, int(l))
         for a, b, score in s["cov"]:
@@ -931,6 +947,120 @@ class LoopMap:
         if rc != 0:
             raise RuntimeError(f"ov2h_loop_assemble: status {rc}")
         return i[:n[2]].tolist(), q[:n[0]].tolist(), t[:n[1]].tolist(), qd[:n[0]].copy(), td[:n[1]].copy()
+
+    def local_map(self, newkf, lckf, vkplmids, cap=1 << 14):
+        """what trackLoopLocalMap hands to its matcher (LoopCloser::assembleLoopLocalMap, no GPU context): dict(vkplmids: the
+        list with the identity pairs appended, n_identity, matched: vmatchedkpids, local / cands: the local set and the
+        candidates offered, in the mirror's order of first encounter)"""
+        ip = C.POINTER(C.c_int)
+        pin = np.ascontiguousarray(vkplmids, np.int32).reshape(-1, 2)
+        n, po = np.zeros(4, np.int32), np.zeros((cap, 2), np.int32)
+        m, lo, ca = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        rc = lib().ov2h_loop_local_map(self.h, int(newkf), int(lckf), len(pin), pin.ctypes.data_as(ip), cap, n.ctypes.data_as(ip),
+                                       po.ctypes.data_as(ip), m.ctypes.data_as(ip), lo.ctypes.data_as(ip), ca.ctypes.data_as(ip))
+        if rc < 0:
+            raise RuntimeError(f"ov2h_loop_local_map: status {rc}")
+        return dict(vkplmids=[tuple(r) for r in po[:n[0]].tolist()], n_identity=int(rc), matched=m[:n[1]].tolist(),
+                    local=lo[:n[2]].tolist(), cands=ca[:n[3]].tolist())
+
+    def loop_track(self, ctx, jobs, maxdist=10.0, ratio=0.3, cap=1 << 16):
+        """LoopCloser::trackLoopLocalMaps: jobs = [(newkf, lckf, Twc (7,), vkplmids)]; returns (list of dict(vkplmids,
+        n_identity, n_offered, n_matched), stats dict); a negative status raises"""
+        B = len(jobs)
+        ip = C.POINTER(C.c_int)
+        nk = np.ascontiguousarray([j[0] for j in jobs], np.int32)
+        lc = np.ascontiguousarray([j[1] for j in jobs], np.int32)
+        T = np.ascontiguousarray([j[2] for j in jobs], np.float64).reshape(-1, 7)
+        n_in = np.ascontiguousarray([len(j[3]) for j in jobs], np.int32)
+        pin = np.ascontiguousarray([p for j in jobs for p in j[3]], np.int32).reshape(-1, 2)
+        n_out, po, cnt, st = np.zeros(max(B, 1), np.int32), np.zeros((cap, 2), np.int32), np.zeros((max(B, 1), 3), np.int32), np.zeros(3, np.int32)
+        rc = lib().ov2h_loop_track(self.h, ctx.h, B, nk.ctypes.data_as(ip), lc.ctypes.data_as(ip), _dp(T), float(maxdist), float(ratio),
+                                   n_in.ctypes.data_as(ip), pin.ctypes.data_as(ip), cap, n_out.ctypes.data_as(ip), po.ctypes.data_as(ip),
+                                   cnt.ctypes.data_as(ip), st.ctypes.data_as(ip))
+        if rc != 0:
+            raise RuntimeError(f"trackLoopLocalMaps: status {rc}")
+        out, o = [], 0
+        for b in range(B):
+            out.append(dict(vkplmids=[tuple(r) for r in po[o:o + n_out[b]].tolist()], n_identity=int(cnt[b, 0]), n_offered=int(cnt[b, 1]),
+                            n_matched=int(cnt[b, 2])))
+            o += n_out[b]
+        return out, dict(pairs=int(st[0]), match_pairs=int(st[1]), match_calls=int(st[2]))
+
+    def compute_pnp(self, ctx, kfid, vkplmids, Twc, voutlier_idx=(), cap=1 << 14):
+        """LoopCloser::computePnP: returns (success, Twc (7,), voutlier_idx: the given indices followed by the appended ones);
+        a negative status raises"""
+        ip = C.POINTER(C.c_int)
+        pin = np.ascontiguousarray(vkplmids, np.int32).reshape(-1, 2)
+        T, out, nout = np.array(Twc, np.float64), np.zeros(cap, np.int32), C.c_int(0)
+        out[:len(voutlier_idx)] = list(voutlier_idx)
+        rc = lib().ov2h_loop_compute_pnp(self.h, ctx.h, int(kfid), len(pin), pin.ctypes.data_as(ip), _dp(T), len(voutlier_idx), cap,
+                                         out.ctypes.data_as(ip), C.byref(nout))
+        if rc < 0:
+            raise RuntimeError(f"computePnP: status {rc}")
+        return bool(rc), T, out[:nout.value].tolist()
+
+    VERIFY_STATS = ("p3p_pairs", "refine_pairs", "track_pairs", "pnp_pairs", "p3p_calls", "refine_calls", "track_calls", "pnp_calls")
+
+    @staticmethod
+    def _unpack_verify(B, ints, dbl, lists):
+        """the rows ov2h_loop_verify writes -> list of dicts (no arithmetic: slicing only)"""
+        out, o = [], 0
+        for b in range(B):
+            i, d = ints[b].tolist(), dbl[b]
+            take = []
+            for n, w in ((i[6], 2), (i[7], 2), (i[8], 2), (i[12], 1)):
+                take.append(lists[o:o + n * w].reshape(-1, w).tolist())
+                o += n * w
+            out.append(dict(branch=i[0], p3p_status=i[1], p3p_info=i[2:6], after_p3p=[tuple(r) for r in take[0]],
+                            after_track=[tuple(r) for r in take[1]], final=[tuple(r) for r in take[2]], pnp_outliers=[r[0] for r in take[3]],
+                            n_identity=i[9], n_offered=i[10], n_matched=i[11], Twc_p3p=d[:7].copy(), Twc=d[7:14].copy(),
+                            lc_pose_err=float(d[14])))
+        return out
+
+    def loop_verify(self, ctx, pairs, lists, seeds, nransac_iter=100, fransac_err=3.0, cap=1 << 18):
+        """LoopCloser::verifyLoopCandidates: pairs [(newkf, lckf)], lists: the incoming vkplmids of each, seeds; returns (list of
+        per-pair dicts, stats dict); a negative status raises"""
+        B = len(pairs)
+        ip = C.POINTER(C.c_int)
+        nk, lc = np.ascontiguousarray([p[0] for p in pairs], np.int32), np.ascontiguousarray([p[1] for p in pairs], np.int32)
+        n_in = np.ascontiguousarray([len(v) for v in lists], np.int32)
+        pin = np.ascontiguousarray([q for v in lists for q in v], np.int32).reshape(-1, 2)
+        sd = np.ascontiguousarray(seeds, np.uint64)
+        ints, dbl, li, st = np.zeros((max(B, 1), 13), np.int32), np.zeros((max(B, 1), 15)), np.zeros(cap, np.int32), np.zeros(8, np.int32)
+        rc = lib().ov2h_loop_verify(self.h, ctx.h, B, nk.ctypes.data_as(ip), lc.ctypes.data_as(ip), n_in.ctypes.data_as(ip),
+                                    pin.ctypes.data_as(ip), sd.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(nransac_iter),
+                                    float(fransac_err), cap, ints.ctypes.data_as(ip), _dp(dbl), li.ctypes.data_as(ip), st.ctypes.data_as(ip))
+        if rc != 0:
+            raise RuntimeError(f"verifyLoopCandidates: status {rc}")
+        return self._unpack_verify(B, ints, dbl, li), dict(zip(self.VERIFY_STATS, st.tolist()))
+
+    def loop_verify_candidate(self, ctx, newkf, lckf, vkplmids, seed, nransac_iter=100, fransac_err=3.0, cap=1 << 16):
+        """LoopCloser::verifyLoopCandidate, the reference-shaped call on one pair: one dict as loop_verify returns them"""
+        ip = C.POINTER(C.c_int)
+        pin = np.ascontiguousarray(vkplmids, np.int32).reshape(-1, 2)
+        ints, dbl, li = np.zeros((1, 13), np.int32), np.zeros((1, 15)), np.zeros(cap, np.int32)
+        rc = lib().ov2h_loop_verify_candidate(self.h, ctx.h, int(newkf), int(lckf), len(pin), pin.ctypes.data_as(ip), int(seed),
+                                              int(nransac_iter), float(fransac_err), cap, ints.ctypes.data_as(ip), _dp(dbl),
+                                              li.ctypes.data_as(ip))
+        if rc != 0:
+            raise RuntimeError(f"verifyLoopCandidate: status {rc}")
+        return self._unpack_verify(1, ints, dbl, li)[0]
+
+    def loop_process(self, ctx, pairs, seeds, nransac_iter=100, fransac_err=3.0, cap=1 << 18):
+        """LoopCloser::processLoopCandidates: (branches of the 2D-2D half, pairs each passed on, per-pair verify dicts, stats)"""
+        B = len(pairs)
+        ip = C.POINTER(C.c_int)
+        nk, lc = np.ascontiguousarray([p[0] for p in pairs], np.int32), np.ascontiguousarray([p[1] for p in pairs], np.int32)
+        sd = np.ascontiguousarray(seeds, np.uint64)
+        br, npass = np.zeros(max(B, 1), np.int32), np.zeros(max(B, 1), np.int32)
+        ints, dbl, li, st = np.zeros((max(B, 1), 13), np.int32), np.zeros((max(B, 1), 15)), np.zeros(cap, np.int32), np.zeros(13, np.int32)
+        rc = lib().ov2h_loop_process(self.h, ctx.h, B, nk.ctypes.data_as(ip), lc.ctypes.data_as(ip), sd.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                     int(nransac_iter), float(fransac_err), cap, br.ctypes.data_as(ip), npass.ctypes.data_as(ip),
+                                     ints.ctypes.data_as(ip), _dp(dbl), li.ctypes.data_as(ip), st.ctypes.data_as(ip))
+        if rc != 0:
+            raise RuntimeError(f"processLoopCandidates: status {rc}")
+        keys = ("pairs", "knn_pairs", "epi_pairs", "knn_calls", "epi_calls") + self.VERIFY_STATS
+        return br[:B].tolist(), npass[:B].tolist(), self._unpack_verify(B, ints, dbl, li), dict(zip(keys, st.tolist()))
 
     def loop_candidate(self, ctx, newkf, lckf, seed, nransac_iter=100, fransac_err=3.0, cap=1 << 14):
         """LoopCloser::processLoopCandidate as the reference writes it, one pair: dict(branch, lckfid, knn, n_outliers, out,

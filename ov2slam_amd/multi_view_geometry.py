@@ -193,6 +193,18 @@ class MultiViewGeometry:
                                                    float(errth), int(bool(use_lmeds)), p(d_seed), p(d_Twc), p(d_outlier),
                                                    p(d_status), p(d_info)))
 
+    # -- the loop closer's local-map matcher (csrc/match.hip) ----------------------------------------------------------
+    def loopMatchToMap_batch(self, inp, fmaxprojerr=10.0, fdistratio=0.3):
+        """LoopCloser::matchToMap (src/loop_closer.cpp:586-763) for the B pairs of a loop_match.LoopMatchInput through
+        ov2_loop_match_to_map_batch.  returns (match_cand (n_kp,) int32: candidate index within the pair or -1, match_dist)"""
+        from . import loop_match
+        return loop_match.loopMatchToMap_batch(self.ctx, inp, fmaxprojerr, fdistratio)
+
+    def loopMatchToMap_batch_dev(self, dev_inp, fmaxprojerr=10.0, fdistratio=0.3):
+        """device-resident, asynchronous form (ov2_loop_match_to_map_batch_dev) on a loop_match.LoopMatchInputDev: nothing is
+        synchronised; dev_inp.get() synchronises and downloads"""
+        dev_inp.enqueue(fmaxprojerr, fdistratio)
+
     def dbg_p3p(self, bv, X):
         """the device P3P solver on n samples (ov2_dbg_p3p): bv, X (n,3,3) -> R (n,4,3,3), t (n,4,3), nsol (n,)"""
         bv, X = np.ascontiguousarray(bv, np.float64).reshape(-1, 3, 3), np.ascontiguousarray(X, np.float64).reshape(-1, 3, 3)
