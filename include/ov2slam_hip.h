@@ -523,6 +523,68 @@ ov2_status ov2_knn2_hamming_batch_dev(ov2_ctx *ctx, int B, int total_query, cons
 ov2_status ov2_knn_set_lanes(ov2_ctx *ctx, int lanes);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Loop detection: the visual-word table of one incremental index, resident in HBM, and the exact search in it.
+ * A table holds the live descriptors (words) of one obindex2::ImageIndex (Thirdparty/obindex2/lib/src/binary_index.cc), 32
+ * bytes per slot, in ascending word-id order; it replaces the descriptor storage behind BinaryTree / BinaryDescriptor.
+ * The word id of a row is the number of rows appended before it (0, 1, 2, ...; never reused, as ImageIndex::addDescriptor's
+ * counter, binary_index.cc:349-363).  All calls on a table are ordered on its context's main stream; none is thread-safe
+ * against another call on the same context.  Pointers are HOST pointers unless named d_*. */
+typedef struct ov2_lcd_table ov2_lcd_table;
+#define OV2_LCD_MAX_WORDS (1 << 22)   /* live words of a table: the slot shares a 31-bit key with 9 bits of distance */
+#define OV2_LCD_MAX_BATCH 4096        /* pairs of a search call */
+#define OV2_LCD_MAX_QUERY (1 << 20)   /* query rows of a search call */
+#define OV2_LCD_MAX_SPLITS 1024       /* train-axis splits of a table */
+#define OV2_LCD_TILE 512              /* table rows that pass through LDS at a time (no limit; tests place sizes around it) */
+/* An empty table with room for max(capacity_hint, 1024) slots; capacity_hint < 0 or > OV2_LCD_MAX_WORDS is OV2_ERR_INVALID
+ * (checked on the count alone).  Destroying the context releases the device side of its tables; the handle stays valid for
+ * ov2_lcd_table_destroy. */
+ov2_status ov2_lcd_table_create(ov2_ctx *ctx, int capacity_hint, ov2_lcd_table **table);
+void ov2_lcd_table_destroy(ov2_lcd_table *table);
+/* ImageIndex::addDescriptor (binary_index.cc:349-363), n at a time: appends n rows behind the last slot, *first_slot = the slot
+ * of the first.  The buffer grows geometrically (device-to-device copy on the context's stream).  More than
+ * OV2_LCD_MAX_WORDS live words is OV2_ERR_INVALID; dead slots in the way of that limit are compacted away first. */
+ov2_status ov2_lcd_table_append(ov2_ctx *ctx, ov2_lcd_table *table, int n, const uint8_t *descs, int *first_slot);
+/* ImageIndex::deleteDescriptor (binary_index.cc:365-379), n at a time: marks the slots dead.  A dead slot is never returned by
+ * a search; killing it again changes nothing.  A slot outside the table is OV2_ERR_INVALID and nothing is marked.  The call
+ * compacts the table itself when it leaves more dead slots than live ones, which keeps
+ *     slots <= 2 x live + rows appended since the last compaction
+ * (slots <= 2 x live right after a kill), so the caller compares the compaction count of ov2_lcd_table_count before and after. */
+ov2_status ov2_lcd_table_kill(ov2_ctx *ctx, ov2_lcd_table *table, int n, const int32_t *slots);
+/* Removes the dead slots; live rows keep their relative order (rows in front of the first dead slot do not move).  Counted
+ * only when a slot changed its meaning, i.e. when there was a dead slot. */
+ov2_status ov2_lcd_table_compact(ov2_ctx *ctx, ov2_lcd_table *table);
+/* slots (live + dead), live words and compactions so far; any pointer may be NULL */
+ov2_status ov2_lcd_table_count(const ov2_lcd_table *table, int *slots, int *live, int *compactions);
+/* the slot-to-word-id map: ids[s] = word id of slot s for s < min(cap, slots), ascending; dead (may be NULL) = 1 where the
+ * slot is dead.  Read it after every compaction. */
+ov2_status ov2_lcd_table_ids(const ov2_lcd_table *table, int cap, int32_t *ids, uint8_t *dead);
+/* ImageIndex::searchDescriptors (binary_index.cc:217-245, :253-347) with knn = 2, for B (query set, table) pairs per call: pair b owns
+ * n_query[b] consecutive rows of `query` and searches tables[b] (one table may serve several pairs).
+ *   query   sum(n_query) x 32
+ *   idx     sum(n_query) x 2    slot of neighbour 0 / 1 in the pair's table
+ *   dist    sum(n_query) x 2    their Hamming distances (0 .. 256)
+ * DEPARTURE from the reference: the search is exact, over every live word, not a walk of randomised trees with 64 checks.
+ * Neighbours 0 and 1 are the two live slots with the smallest (distance, slot): of two words at one distance the lower slot
+ * (= the lower word id) comes first.  A neighbour that does not exist is idx = -1, dist = -1.  A pair with n_query[b] = 0
+ * writes nothing, B = 0 is OV2_OK, and nothing is written beyond row sum(n_query).  Two launches whatever B is; only
+ * integers are involved: the results are bit-identical whatever the split count (ov2_lcd_set_splits), the composition of the
+ * batch and the form.  Refused with OV2_ERR_INVALID: negative counts, null arguments that a non-empty call needs, a table
+ * of another context, B > OV2_LCD_MAX_BATCH, sum(n_query) > OV2_LCD_MAX_QUERY, and a forced split count that needs more
+ * than 1 << 26 (query row, split) scratch entries.  One synchronisation. */
+ov2_status ov2_lcd_search2_batch(ov2_ctx *ctx, int B, ov2_lcd_table *const *tables, const int *n_query, const uint8_t *query,
+                                 int32_t *idx, int32_t *dist);
+/* device-resident, asynchronous form: tables and n_query stay host arrays (they size the grid), d_query / d_idx / d_dist are in
+ * HBM, d_query 16-byte aligned (else OV2_ERR_INVALID).  Nothing is synchronised or read back. */
+ov2_status ov2_lcd_search2_batch_dev(ov2_ctx *ctx, int B, ov2_lcd_table *const *tables, const int *n_query,
+                                     const uint8_t *d_query, int32_t *d_idx, int32_t *d_dist);
+/* Train-axis splits of every table of a call: 0 (default) picks by the size of the call (four workgroups per compute unit,
+ * whole tiles per split), 1 .. OV2_LCD_MAX_SPLITS forces that number (tests, tuning; all give the same bits).  Anything else
+ * is OV2_ERR_INVALID. */
+ov2_status ov2_lcd_set_splits(ov2_ctx *ctx, int splits);
+/* search calls of this context that reached the device so far (tests count the calls of a detector step with it) */
+ov2_status ov2_lcd_search_calls(ov2_ctx *ctx, long long *calls);
+
+/* ---------------------------------------------------------------------------------------------------
  * Pose graphs: Optimizer::localPoseGraph (src/optimizer.cpp:2346-2592, the loop closer's chain of
  * keyframes loop .. new + the loop edge) and Optimizer::fullPoseGraph (:2783-2870, the chain of all frames between
  * constant keyframes at the end of a run) = LeftSE3RelativePoseError (src/ceres_parametrization.cpp:30-102,

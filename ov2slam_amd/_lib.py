@@ -115,6 +115,17 @@ SIGNATURES = {
     "ov2_knn2_hamming_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     "ov2_knn2_hamming_batch_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "ov2_knn_set_lanes": (C.c_int, [vp, C.c_int]),
+    "ov2_lcd_table_create": (C.c_int, [vp, C.c_int, vpp]),
+    "ov2_lcd_table_destroy": (None, [vp]),
+    "ov2_lcd_table_append": (C.c_int, [vp, vp, C.c_int, vp, ip]),
+    "ov2_lcd_table_kill": (C.c_int, [vp, vp, C.c_int, vp]),
+    "ov2_lcd_table_compact": (C.c_int, [vp, vp]),
+    "ov2_lcd_table_count": (C.c_int, [vp, ip, ip, ip]),
+    "ov2_lcd_table_ids": (C.c_int, [vp, C.c_int, vp, vp]),
+    "ov2_lcd_search2_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+    "ov2_lcd_search2_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+    "ov2_lcd_set_splits": (C.c_int, [vp, C.c_int]),
+    "ov2_lcd_search_calls": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
 }
 
 _lib = None

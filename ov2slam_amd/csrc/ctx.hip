@@ -51,6 +51,8 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     c->klt_lanes = 0;
     c->knn_lanes = 0;
     c->knn_cus = 0;
+    c->lcd_splits = 0;
+    c->lcd_calls = 0;
     c->ba_arena = nullptr;
     c->ba_arena_cap = 0;
     c->ba_host = nullptr;
@@ -110,6 +112,7 @@ extern "C" void ov2_ctx_destroy(ov2_ctx *c)
     (void)hipStreamSynchronize(c->stream_kf);
     for (ov2_pyr_buf *b : c->pool) ov2_pyr_buf_free(b);
     for (ov2_map *m : c->maps) ov2_map_orphan(m);
+    for (ov2_lcd_table *t : c->lcd_tables) ov2_lcd_table_orphan(t);
     if (c->tmp_img) ov2_images_destroy(c->tmp_img);
     for (auto &r : c->ktime_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
     for (auto e : c->ktime_free) (void)hipEventDestroy(e);
@@ -385,7 +388,7 @@ const char *ov2_kernel_names[OV2_K_MAX] = {"clahe_lut_kernel", "level0_kernel", 
                                            "stereo_gate_kernel", "brief_kernel", "match_kernels", "pose_graph_kernel",
                                            "epipolar_kernel", "fivept_dbg_kernel", "p3p_solve_kernel", "p3p_select_kernel",
                                            "p3p_score_kernel", "p3p_final_kernel", "p3p_dbg_kernel", "knn2_kernel",
-                                           "loop_match_kernels"};
+                                           "loop_match_kernels", "lcd_search_kernel", "lcd_merge_kernel", "lcd_table_kernels"};
 
 static hipEvent_t ktime_event(ov2_ctx *c)
 {

@@ -133,6 +133,9 @@ struct ov2_ctx {
     int klt_lanes;                       // ov2_klt_set_lanes: 0 = by call size, 3 / 8 / 16 = forced lanes per keypoint
     int knn_lanes;                       // ov2_knn_set_lanes: 0 = by call size, 1 / 4 / 16 / 64 = forced lanes per query
     int knn_cus;                         // compute units of the device (read on first use by the matcher's automatic choice)
+    int lcd_splits;                      // ov2_lcd_set_splits: 0 = by call size, otherwise the forced number of train-axis splits
+    long long lcd_calls;                 // ov2_lcd_search2_batch(_dev) calls that launched (ov2_lcd_search_calls)
+    std::vector<struct ov2_lcd_table *> lcd_tables;   // live word tables (their device memory is released with the ctx)
     // optional per-kernel hipEvent timing (bench.py roofline leg); off by default
     bool ktime_on;
     std::vector<ov2_ktime_rec> ktime_recs;   // recorded (kernel id, event pair) since the last report
@@ -166,6 +169,8 @@ ov2_status ov2_kf_scratch(ov2_ctx *ctx, size_t bytes, void **out);
 ov2_status ov2_staging(ov2_ctx *ctx, size_t bytes, void **host, void **dev);
 // ov2_ctx_destroy: free the device side of a map that outlives its ctx (the handle stays valid for ov2_map_destroy)
 void ov2_map_orphan(struct ov2_map *m);
+// the same for a word table of the loop detector (lcd.hip)
+void ov2_lcd_table_orphan(struct ov2_lcd_table *t);
 
 #define OV2_HIP(ctx, call)                                                                          \
     do {                                                                                            \

@@ -11,6 +11,7 @@
 #include <thread>
 
 #include "ov2_host.hpp"
+#include "ov2_lcd.hpp"
 #include "ov2_slam.hpp"
 
 using namespace ov2;
@@ -1829,6 +1830,110 @@ void ov2h_feloop_destroy(void *h)
     if (!f) return;
     if (f->prev) ov2_pyr_release(f->prev);
     delete f;
+}
+
+}  // extern "C"
+
+// ---- LoopCloser::newKeyframe: a loop closer that lives across keyframes (its detector and vkfids_) ---------------------------------
+
+extern "C" {
+
+void *ov2h_loop_closer_create(void *p, void *ctx, int lcd_p, float nndr, double min_score, int island_size, int nframes_after_lc,
+                              int purge, int min_feat_apps, int nransac_iter, float fransac_err)
+{
+    HostMap *m = (HostMap *)p;
+    loop_params(m, nransac_iter, fransac_err);
+    LoopCloser *lc = new LoopCloser((ov2_ctx *)ctx, m->st, m->map);
+    LCDetectorParams &P = lc->lcd_params_;
+    P.p = (unsigned)lcd_p; P.nndr = nndr; P.min_score = min_score; P.island_size = (unsigned)island_size;
+    P.nframes_after_lc = (unsigned)nframes_after_lc; P.purge_descriptors = purge != 0; P.min_feat_apps = (unsigned)min_feat_apps;
+    return lc;
+}
+
+void ov2h_loop_closer_destroy(void *h) { delete (LoopCloser *)h; }
+
+// out[10]: skipped, image id, detector status, train image id, candidate kfid, candidate used by the 2D-2D half, its branch,
+// pairs it passed on, branch of the 2D-3D half, pairs at its end; stats[13] as ov2h_loop_process (zeros without a candidate).
+// Returns 0 or a negative ov2_status
+int ov2h_loop_new_keyframe(void *h, int kfid, unsigned long long seed, int *out, int *stats)
+{
+    LoopCloser *lc = (LoopCloser *)h;
+    LoopNewKeyframeResult r;
+    lc->last_ = LoopStats();
+    const ov2_status s = lc->newKeyframe(kfid, (uint64_t)seed, r);
+    if (s != OV2_OK) return (int)s;
+    out[0] = r.skipped ? 1 : 0; out[1] = r.image_id; out[2] = (int)r.det.status; out[3] = (int)r.det.train_id; out[4] = r.cand_kfid;
+    out[5] = r.matched.lckfid; out[6] = r.matched.branch; out[7] = (int)r.matched.vkplmids.size(); out[8] = r.verified.branch;
+    out[9] = (int)r.verified.vkplmids.size();
+    const LoopStats &L = lc->last_;
+    const int st[13] = {L.pairs, L.knn_pairs, L.epi_pairs, L.knn_calls, L.epi_calls, L.p3p_pairs, L.refine_pairs, L.track_pairs, L.pnp_pairs,
+                        L.p3p_calls, L.refine_calls, L.track_calls, L.pnp_calls};
+    std::copy(st, st + 13, stats);
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- loop detector (ov2_lcd.hpp): create with parameters, process / process_batch, and what the last call did -------------
+
+extern "C" {
+
+// ctx may be null: the host brute-force back end
+void *ov2h_lcd_create(void *ctx, int p, float nndr, double min_score, int island_size, int nframes_after_lc, int purge, int min_feat_apps)
+{
+    LCDetectorParams P;
+    P.p = (unsigned)p; P.nndr = nndr; P.min_score = min_score; P.island_size = (unsigned)island_size;
+    P.nframes_after_lc = (unsigned)nframes_after_lc; P.purge_descriptors = purge != 0; P.min_feat_apps = (unsigned)min_feat_apps;
+    return new LCDetector((ov2_ctx *)ctx, P);
+}
+
+void ov2h_lcd_destroy(void *h) { delete (LCDetector *)h; }
+
+// status / train_id: B each.  Returns 0 or a negative ov2_status
+int ov2h_lcd_process_batch(int B, void *const *h, const unsigned *image_id, const uint8_t *const *descs, const int *n, int *status,
+                           int *train_id)
+{
+    std::vector<LCDetectorResult> r((size_t)std::max(B, 0));
+    const ov2_status s = LCDetector::processBatch(B, (LCDetector *const *)h, image_id, descs, n, r.data());
+    if (s != OV2_OK) return (int)s;
+    for (int b = 0; b < B; ++b) { status[b] = (int)r[b].status; train_id[b] = (int)r[b].train_id; }
+    return 0;
+}
+
+int ov2h_lcd_process(void *h, unsigned image_id, const uint8_t *descs, int n, int *status, int *train_id)
+{
+    return ov2h_lcd_process_batch(1, &h, &image_id, &descs, &n, status, train_id);
+}
+
+// out[10]: images, live words of the host index, device slots / live words / compactions, and of the last process call the
+// number of add matches, query matches, words added, words purged, islands (scores: one per image)
+void ov2h_lcd_counts(void *h, int *out)
+{
+    const LCDetector *d = (const LCDetector *)h;
+    const LCDetectorTrace &t = d->trace();
+    out[0] = (int)d->index().numImages(); out[1] = (int)d->index().numDescriptors();
+    d->index().deviceCounts(&out[2], &out[3], &out[4]);
+    out[5] = (int)t.add_matches.size(); out[6] = (int)t.matches.size(); out[7] = (int)t.added.size(); out[8] = (int)t.purged.size();
+    out[9] = (int)t.islands.size();
+}
+
+// the trace of the last process call into arrays sized from ov2h_lcd_counts: matches as (query row, word id, distance) int
+// triples, islands as (img_id, min, max) + score; returns the number of scores written (<= cap_scores)
+int ov2h_lcd_trace(void *h, int *add_matches, int *matches, int *added, int *purged, double *scores, int cap_scores, int *islands,
+                   double *island_scores)
+{
+    const LCDetectorTrace &t = ((const LCDetector *)h)->trace();
+    for (size_t i = 0; i < t.add_matches.size(); ++i) { add_matches[3 * i] = t.add_matches[i].queryIdx; add_matches[3 * i + 1] = t.add_matches[i].trainIdx; add_matches[3 * i + 2] = (int)t.add_matches[i].distance; }
+    for (size_t i = 0; i < t.matches.size(); ++i) { matches[3 * i] = t.matches[i].queryIdx; matches[3 * i + 1] = t.matches[i].trainIdx; matches[3 * i + 2] = (int)t.matches[i].distance; }
+    for (size_t i = 0; i < t.added.size(); ++i) added[i] = (int)t.added[i];
+    for (size_t i = 0; i < t.purged.size(); ++i) purged[i] = (int)t.purged[i];
+    const int ns = (int)std::min(t.scores.size(), (size_t)std::max(cap_scores, 0));
+    for (int i = 0; i < ns; ++i) scores[i] = t.scores[i];
+    for (size_t i = 0; i < t.islands.size(); ++i) {
+        islands[3 * i] = (int)t.islands[i].img_id; islands[3 * i + 1] = (int)t.islands[i].min_img_id; islands[3 * i + 2] = (int)t.islands[i].max_img_id;
+        island_scores[i] = t.islands[i].score;
+    }
+    return ns;
 }
 
 }  // extern "C"

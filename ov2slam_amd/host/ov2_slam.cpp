@@ -1292,6 +1292,38 @@ ov2_status LoopCloser::processLoopCandidates(const std::vector<std::pair<int, in
     return OV2_OK;
 }
 
+ov2_status LoopCloser::newKeyframe(int kfid, uint64_t seed, LoopNewKeyframeResult &r)
+{   // the body of LoopCloser::run for one keyframe, :86-169
+    r = LoopNewKeyframeResult();
+    const auto pnewkf = pmap_->getKeyframe(kfid);
+    if (!pnewkf) return OV2_ERR_INVALID;
+    if (!plcdetector_) plcdetector_.reset(new LCDetector(ctx_, lcd_params_));
+    std::vector<uint8_t> descs;
+    for (const auto &kp : pnewkf->getKeypoints()) {                         // :97-109
+        const auto plm = pmap_->getMapPoint(kp.lmid_);
+        if (plm == nullptr) continue;
+        if (plm->has_desc_) descs.insert(descs.end(), plm->desc_.begin(), plm->desc_.end());
+    }
+    if (descs.empty()) { r.skipped = true; return OV2_OK; }                // :111-113
+    kf_idx_++;                                                              // :147-148
+    vkfids_.push_back(kfid);
+    r.image_id = kf_idx_;
+    ov2_status s = plcdetector_->process((unsigned)kf_idx_, descs.data(), (int)(descs.size() / 32), &r.det);   // :150-151
+    if (s != OV2_OK) return s;
+    if (r.det.status != LC_DETECTED) return OV2_OK;                         // :156-164
+    int cand = vkfids_.at(r.det.train_id);                                  // :187
+    while (cand >= 0 && pmap_->getKeyframe(cand) == nullptr) cand--;        // :192-195
+    if (cand < 0) return OV2_OK;
+    r.cand_kfid = cand;
+    std::vector<LoopPairResult> matched;
+    std::vector<LoopVerifyResult> verified;
+    s = processLoopCandidates({{kfid, cand}}, {seed}, matched, verified);   // :167
+    if (s != OV2_OK) return s;
+    r.matched = matched[0];
+    r.verified = verified[0];
+    return OV2_OK;
+}
+
 ov2_status LoopCloser::processLoopCandidate(int newkfid, int lckfid, uint64_t seed, LoopPairResult &r)
 {   // :184-236
     r = LoopPairResult();

@@ -22,6 +22,7 @@
 // none of it, because nothing proposes candidates yet.
 #pragma once
 #include "ov2_host.hpp"
+#include "ov2_lcd.hpp"
 
 namespace ov2 {
 
@@ -208,12 +209,33 @@ struct LoopTrackStats {   // one trackLoopLocalMaps call
 // The 2D-2D half of LoopCloser::processLoopCandidate (src/loop_closer.cpp:184-236): does the new keyframe see the same place
 // as a candidate keyframe?  The second half (:238-300) decides it: p3pRansac with a refinement, trackLoopLocalMap, computePnP,
 // for one pair as the reference writes it (verifyLoopCandidate) and for B pairs with one library call per stage
-// (verifyLoopCandidates).  A detector that proposes candidates (:89-181, iBoW-LCD) and the calls after an accepted loop
-// (:302-372) are not chained here.
+// (verifyLoopCandidates).  newKeyframe is the body of LoopCloser::run for one keyframe (:86-169): the detector that proposes the
+// candidate (ov2::LCDetector, ov2_lcd.hpp) in front of processLoopCandidates.  Not built: the 300 extra FAST + BRIEF keypoints
+// of :115-140 (the detector sees the map points' descriptors only), the calls after an accepted loop (:302-372), and any
+// call from SlamManager's frame loop.
+struct LoopNewKeyframeResult {
+    bool skipped = false;        // :111-113 no map point of the keyframe has a descriptor: the detector is not called
+    int image_id = -1;           // kf_idx_ of this keyframe (index into vkfids_); -1 when skipped
+    LCDetectorResult det;        // the detector's result (status LC_NOT_DETECTED when skipped)
+    int cand_kfid = -1;          // on LC_DETECTED: vkfids_[train_id], walked down to the closest keyframe still in the map (:187-195)
+    LoopPairResult matched;      // processLoopCandidates on (kfid, cand_kfid); untouched without a candidate
+    LoopVerifyResult verified;
+};
+
 class LoopCloser {
 public:
     LoopCloser(ov2_ctx *ctx, std::shared_ptr<SlamParams> pstate, std::shared_ptr<MapManager> pmap)
         : ctx_(ctx), pslamstate_(pstate), pmap_(pmap) {}
+    // :86-169 for one keyframe of the map: the descriptors (plm->desc_) of the keyframe's keypoints whose map point exists and
+    // has one, in getKeypoints() order; none: skipped, the image id does not advance.  Otherwise kfid goes to vkfids_ and the
+    // detector processes image kf_idx_; on LC_DETECTED train_id is mapped through vkfids_ (walking down while the keyframe is no
+    // longer in the map; below keyframe 0 there is no candidate, where the reference would not end) and the pair goes to
+    // processLoopCandidates.  The detector is created on first use with lcd_params_ on this closer's context.
+    ov2_status newKeyframe(int kfid, uint64_t seed, LoopNewKeyframeResult &r);
+    LCDetectorParams lcd_params_;
+    std::unique_ptr<LCDetector> plcdetector_;
+    std::vector<int> vkfids_;
+    int kf_idx_ = -1;
     // :502-568 + :612-631, the part of trackLoopLocalMap in front of the matcher (no GPU): the candidate's covisible keyframes in
     // ascending id with the candidate forced in, the window lckf.kfid_ +- 15 (`continue` below it, `break` above it), keyframes
     // no longer in the map skipped, every lmid looked at once; an lmid the new keyframe observes becomes an identity pair
