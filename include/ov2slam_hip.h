@@ -254,6 +254,33 @@ ov2_status ov2_detect_grid_batch_dev(ov2_ctx *ctx, const ov2_pyr *pyr, int cell,
                                      const float *d_cur_xy, const int32_t *d_cur_img, const uint8_t *d_cur_valid,
                                      const int *roi, int do_subpix, int32_t *d_n_out, float *d_out_xy, int out_cap);
 
+/* Whole-image FAST-9/16 with non-maximum suppression, a pixel mask and retainBest, on level 0 of each of the B images of
+ * `pyr`: the detector half of the 300 extra loop-closing keypoints, LoopCloser::run src/loop_closer.cpp:95-126.  Per image:
+ *   score   s(x, y) = cornerScore<16> at `threshold` (clamped to 0..255) where 3 <= x < w-3, 3 <= y < h-3 and the pixel passes
+ *           the 9-contiguous segment test, else 0 (cv::FastFeatureDetector::create(20)->detect, :123 = FAST_t<16>)
+ *   nms     a keypoint iff s > 0 and s is strictly greater than its eight neighbours' s (nonmaxSuppression = true)
+ *   mask    applied AFTER the suppression (KeyPointsFilter::runByPixelsMask): the union of cv::circle(mask, px, mask_radius, 0,
+ *           FILLED) over the mask points (:95-109), centre = (cvRound(x), cvRound(y)), half to even; a masked pixel still
+ *           suppresses its neighbours.  mask_radius < 0 or no mask point: no mask; mask_radius <= OV2_FAST_MAX_MASK_RADIUS
+ *   best    cv::KeyPointsFilter::retainBest(n_best) (:126): at most n_best left: all kept; otherwise every keypoint whose
+ *           response is >= the n_best-th largest one (ties at the bound are all kept, so the count may exceed n_best);
+ *           n_best == 0 keeps none, n_best < 0 keeps all
+ *   order   row-major, y ascending then x ascending (OpenCV's order after nth_element is unspecified),
+ *           bit-identical from run to run and for every batch composition
+ * n_total[b] = keypoints kept, n_out[b] = min(n_total[b], out_cap); the first n_out[b] of them in that order are written to
+ * out_xy[b] (integer-valued floats) and out_resp[b] (the score); an image that does not fit is no error.  n_mask[B] mask points
+ * per image, mask_xy = those of image 0, then image 1, ... (n_mask may be NULL: no mask).  One synchronisation. */
+#define OV2_FAST_MAX_MASK_RADIUS 16
+ov2_status ov2_fast_detect_batch(ov2_ctx *ctx, const ov2_pyr *pyr, int threshold, int mask_radius, const int *n_mask,
+                                 const float *mask_xy, int n_best, int out_cap, int *n_total, int *n_out,
+                                 float *out_xy /* B x out_cap x 2 */, uint8_t *out_resp /* B x out_cap */);
+/* Device-resident, asynchronous form (no host synchronisation): the n_mask mask points of all images as d_mask_xy
+ * (n_mask x 2 floats) and d_mask_img (image index per point; a point with an index outside the batch is ignored), like the
+ * keypoints of ov2_detect_grid_batch_dev; d_n_total / d_n_out B ints, d_out_xy B x out_cap x 2 floats, d_out_resp B x out_cap. */
+ov2_status ov2_fast_detect_batch_dev(ov2_ctx *ctx, const ov2_pyr *pyr, int threshold, int mask_radius, int n_mask,
+                                     const float *d_mask_xy, const int32_t *d_mask_img, int n_best, int out_cap,
+                                     int32_t *d_n_total, int32_t *d_n_out, float *d_out_xy, uint8_t *d_out_resp);
+
 /* ---- local bundle adjustment ------------------------------------------------------------------- */
 /* Flat, POD restatement of the ceres::Problem that Optimizer::localBA assembles (src/optimizer.cpp:76-392).
  * The host adapter (ov2slam_amd/host/local_ba_adapter.*) fills it from Frame/MapPoint graphs and applies the
@@ -891,9 +918,15 @@ ov2_status ov2_triangulate_pairs_dev(ov2_ctx *ctx, int n, int method, int G, con
  * most significant bit of byte 0; keypoints closer than 28 px to the border get no descriptor: valid[i] = 0, the reference
  * returns an empty cv::Mat for them).  im = level 0 of pyramid `b` of `pyr` (the CLAHE'd frame).  The 256 test pairs of
  * opencv_contrib (generated_32.i) are not in the reference tree: `pattern` (256 x {y1, x1, y2, x2}, int8, |v| <= 24) is
- * supplied by the caller.  Host pointers; the _dev form takes device pointers (pattern too) + an image index per point. */
+ * supplied by the caller.  Host pointers; the _dev form takes device pointers (pattern too) + an image index per point.
+ * The kernel reads whatever level 0 of the pyramid holds: the CLAHE'd frame where the pyramid was built with CLAHE, the raw
+ * image where it was built without (describeBRIEF on imraw, src/map_manager.cpp:300, 325; pbriefd_->compute on newkfimg_,
+ * src/loop_closer.cpp:129).  ov2_describe_brief_batch is the host-pointer form for points of several images of the batch
+ * (img_idx[n]), one synchronisation. */
 ov2_status ov2_describe_brief(ov2_ctx *ctx, const ov2_pyr *pyr, int b, int n, const float *pts_xy, const int8_t *pattern,
                               uint8_t *desc /* n x 32 */, uint8_t *valid /* n */);
+ov2_status ov2_describe_brief_batch(ov2_ctx *ctx, const ov2_pyr *pyr, int n, const float *pts_xy, const int32_t *img_idx,
+                                    const int8_t *pattern, uint8_t *desc /* n x 32 */, uint8_t *valid /* n */);
 ov2_status ov2_describe_brief_dev(ov2_ctx *ctx, const ov2_pyr *pyr, int n, const float *d_pts_xy, const int32_t *d_img_idx,
                                   const int8_t *d_pattern, uint8_t *d_desc, uint8_t *d_valid);
 

@@ -65,6 +65,8 @@ SIGNATURES = {
     "ov2_detect_grid": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, C.c_int, ip, vp]),
     "ov2_detect_grid_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_double), ip, vp, vp, C.c_int, ip, vp, C.c_int]),
     "ov2_detect_grid_batch_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]),
+    "ov2_fast_detect_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "ov2_fast_detect_batch_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "ov2_ba_default_options": (None, [vp, C.c_float]),
     "ov2_ba_solve": (C.c_int, [vp, vp, vp, vp]),
     "ov2_ba_solve_batch": (C.c_int, [vp, C.c_int, vp, vp, vp]),
@@ -98,6 +100,7 @@ SIGNATURES = {
                                             vp, vp, vp, vp]),
     "ov2_dbg_rowload16": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, vp]),
     "ov2_describe_brief": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "ov2_describe_brief_batch": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
     "ov2_describe_brief_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
     "ov2_match_to_map": (C.c_int, [vp, vp, C.c_float, C.c_float, vp, vp]),
     "ov2_loop_match_to_map_batch": (C.c_int, [vp, vp, C.c_float, C.c_float, vp, vp]),

@@ -388,7 +388,8 @@ const char *ov2_kernel_names[OV2_K_MAX] = {"clahe_lut_kernel", "level0_kernel", 
                                            "stereo_gate_kernel", "brief_kernel", "match_kernels", "pose_graph_kernel",
                                            "epipolar_kernel", "fivept_dbg_kernel", "p3p_solve_kernel", "p3p_select_kernel",
                                            "p3p_score_kernel", "p3p_final_kernel", "p3p_dbg_kernel", "knn2_kernel",
-                                           "loop_match_kernels", "lcd_search_kernel", "lcd_merge_kernel", "lcd_table_kernels"};
+                                           "loop_match_kernels", "lcd_search_kernel", "lcd_merge_kernel", "lcd_table_kernels",
+                                           "fast_score_kernel", "fast_nms_kernel", "fast_select_kernels"};
 
 static hipEvent_t ktime_event(ov2_ctx *c)
 {

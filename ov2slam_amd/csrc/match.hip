@@ -223,33 +223,52 @@ extern "C" ov2_status ov2_describe_brief_dev(ov2_ctx *c, const ov2_pyr *pyr, int
     return OV2_OK;
 }
 
-extern "C" ov2_status ov2_describe_brief(ov2_ctx *c, const ov2_pyr *pyr, int b, int n, const float *pts_xy, const int8_t *pattern,
-                                         uint8_t *desc, uint8_t *valid)
+// host-pointer form; img_idx == nullptr: every point lies in image b
+static ov2_status describe_brief_host(ov2_ctx *c, const ov2_pyr *pyr, int b, int n, const float *pts_xy, const int32_t *img_idx,
+                                      const int8_t *pattern, uint8_t *desc, uint8_t *valid)
 {
     if (!c) return OV2_ERR_INVALID;
     if (n == 0) return OV2_OK;
     if (n < 0 || !pyr || !pts_xy || !pattern || !desc || !valid) return ov2_set_err(c, OV2_ERR_INVALID, "null/negative argument");
     if (b < 0 || b >= pyr->buf->batch) return ov2_set_err(c, OV2_ERR_INVALID, "image %d outside the pyramid batch", b);
+    if (img_idx)
+        for (int k = 0; k < n; ++k)
+            if (img_idx[k] < 0 || img_idx[k] >= pyr->buf->batch)
+                return ov2_set_err(c, OV2_ERR_INVALID, "image %d outside the pyramid batch", (int)img_idx[k]);
     for (int k = 0; k < 1024; ++k)
         if (pattern[k] < -24 || pattern[k] > 24) return ov2_set_err(c, OV2_ERR_INVALID, "BRIEF test offset %d outside [-24, 24]", (int)pattern[k]);
     void *hs = nullptr, *ds = nullptr;
-    const size_t nb = (size_t)n * 8, need = nb + 1024 + (size_t)n * 33 + 64;
+    const size_t npts = (size_t)n * 8, nb = npts + (img_idx ? (size_t)n * 4 : 0), need = nb + 1024 + (size_t)n * 33 + 64;
     ov2_status s = ov2_staging(c, need, &hs, &ds);
     if (s != OV2_OK) return s;
     char *h = (char *)hs, *d = (char *)ds;
-    memcpy(h, pts_xy, nb);
+    memcpy(h, pts_xy, npts);
+    if (img_idx) memcpy(h + npts, img_idx, (size_t)n * 4);
     memcpy(h + nb, pattern, 1024);
     OV2_HIP(c, hipSetDevice(c->device));
     OV2_HIP(c, hipMemcpyAsync(d, h, nb + 1024, hipMemcpyHostToDevice, c->stream));
     if ((s = ov2_pyr_wait_ready(c, pyr)) != OV2_OK) return s;
     uint8_t *d_desc = (uint8_t *)(d + nb + 1024), *d_valid = d_desc + (size_t)n * 32;
-    OV2_LAUNCH(c, K_BRIEF, brief_kernel, dim3(n), dim3(64), 0, c->stream, pyr->buf->view, n, reinterpret_cast<const float2 *>(d), nullptr,
-               reinterpret_cast<const signed char *>(d + nb), d_desc, d_valid, b);
+    OV2_LAUNCH(c, K_BRIEF, brief_kernel, dim3(n), dim3(64), 0, c->stream, pyr->buf->view, n, reinterpret_cast<const float2 *>(d),
+               img_idx ? reinterpret_cast<const int32_t *>(d + npts) : nullptr, reinterpret_cast<const signed char *>(d + nb), d_desc, d_valid, b);
     OV2_HIP(c, hipMemcpyAsync(h + nb + 1024, d_desc, (size_t)n * 33, hipMemcpyDeviceToHost, c->stream));
     OV2_HIP(c, hipStreamSynchronize(c->stream));
     memcpy(desc, h + nb + 1024, (size_t)n * 32);
     memcpy(valid, h + nb + 1024 + (size_t)n * 32, (size_t)n);
     return OV2_OK;
+}
+
+extern "C" ov2_status ov2_describe_brief(ov2_ctx *c, const ov2_pyr *pyr, int b, int n, const float *pts_xy, const int8_t *pattern,
+                                         uint8_t *desc, uint8_t *valid)
+{
+    return describe_brief_host(c, pyr, b, n, pts_xy, nullptr, pattern, desc, valid);
+}
+
+extern "C" ov2_status ov2_describe_brief_batch(ov2_ctx *c, const ov2_pyr *pyr, int n, const float *pts_xy, const int32_t *img_idx,
+                                               const int8_t *pattern, uint8_t *desc, uint8_t *valid)
+{
+    if (c && n > 0 && !img_idx) return ov2_set_err(c, OV2_ERR_INVALID, "null image indices");
+    return describe_brief_host(c, pyr, 0, n, pts_xy, img_idx, pattern, desc, valid);
 }
 
 extern "C" ov2_status ov2_match_to_map(ov2_ctx *c, const ov2_match_input *in, float fmaxprojerr, float fdistratio,

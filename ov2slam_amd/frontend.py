@@ -401,3 +401,34 @@ def detect_grid_batch(ctx, pyr, cell, mode, thresh, cur_list, roi=None, subpix=T
                                                 None if r is None else r.ctypes.data_as(C.c_void_p), int(subpix),
                                                 n_out.ctypes.data_as(C.POINTER(C.c_int)), out.ctypes.data_as(C.c_void_p), cap))
     return [out[b, :n_out[b]].copy() for b in range(B)]
+
+
+def fast_detect_batch(ctx, pyr, threshold, mask_radius, mask_list, n_best, out_cap):
+    """whole-image FAST + NMS + mask + retainBest on level 0 of every image of `pyr` (ov2_fast_detect_batch,
+    src/loop_closer.cpp:95-126).  mask_list: one (n_b, 2) array of mask points per image, or None.  Returns (n_total [B],
+    n_out [B], out_xy [B, out_cap, 2] f32, out_resp [B, out_cap] u8) as the call wrote them."""
+    B = pyr.batch
+    vp = C.c_void_p
+    n_mask = xy = None
+    if mask_list is not None:
+        assert len(mask_list) == B
+        pts = [np.asarray(m, np.float32).reshape(-1, 2) for m in mask_list]
+        n_mask = np.ascontiguousarray([len(m) for m in pts], np.int32)
+        xy = np.ascontiguousarray(np.concatenate(pts) if B else np.zeros((0, 2)), np.float32)
+    n_total, n_out = np.full(B, -1, np.int32), np.full(B, -1, np.int32)
+    out_xy, out_resp = np.zeros((B, max(out_cap, 0), 2), np.float32), np.zeros((B, max(out_cap, 0)), np.uint8)
+    _check(ctx.h, ctx.lib.ov2_fast_detect_batch(ctx.h, pyr.h, int(threshold), int(mask_radius),
+                                                None if n_mask is None else n_mask.ctypes.data_as(vp),
+                                                None if xy is None else xy.ctypes.data_as(vp), int(n_best), int(out_cap),
+                                                n_total.ctypes.data_as(vp), n_out.ctypes.data_as(vp), out_xy.ctypes.data_as(vp),
+                                                out_resp.ctypes.data_as(vp)))
+    return n_total, n_out, out_xy, out_resp
+
+
+def fast_detect_batch_dev(ctx, pyr, threshold, mask_radius, n_mask, d_mask_xy, d_mask_img, n_best, out_cap, d_n_total, d_n_out,
+                          d_out_xy, d_out_resp):
+    """device-resident, asynchronous form (ov2_fast_detect_batch_dev): nothing is synchronised."""
+    ptr = lambda a: None if a is None else (a.ptr if isinstance(a, DeviceArray) else a)
+    _check(ctx.h, ctx.lib.ov2_fast_detect_batch_dev(ctx.h, pyr.h, int(threshold), int(mask_radius), int(n_mask), ptr(d_mask_xy),
+                                                    ptr(d_mask_img), int(n_best), int(out_cap), ptr(d_n_total), ptr(d_n_out),
+                                                    ptr(d_out_xy), ptr(d_out_resp)))

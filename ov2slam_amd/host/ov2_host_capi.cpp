@@ -1872,6 +1872,73 @@ int ov2h_loop_new_keyframe(void *h, int kfid, unsigned long long seed, int *out,
     return 0;
 }
 
+void ov2h_loop_set_brief_pattern(void *h, const int8_t *pattern256x4) { ((LoopCloser *)h)->setBriefPattern(pattern256x4); }
+
+// room per image of the first detect call of extraKeypoints (2048 by default)
+void ov2h_loop_set_extra_cap(void *h, int cap) { ((LoopCloser *)h)->extra_out_cap_ = cap; }
+
+// the closer's detector (null before its first keyframe) for ov2h_lcd_counts / ov2h_lcd_trace; the closer keeps owning it
+void *ov2h_loop_closer_detector(void *h) { return ((LoopCloser *)h)->plcdetector_.get(); }
+
+// LoopCloser::extraKeypoints for B closers (h[k], kfid[k], image b[k] of pyr).  counts: B x 5 = skipped, nbkps, mask points,
+// keypoints after retainBest, keypoints described; mask_xy / add_xy: B x cap x 2, add_resp: B x cap, add_desc: B x cap x 32 (a
+// job with more than cap mask points or keypoints: OV2_ERR_INVALID, counts still written); stats[2]: detect and describe calls
+int ov2h_loop_extra_keypoints(int B, void *const *h, const int *kfid, void *pyr, const int *b, int cap, int *counts, float *mask_xy,
+                              float *add_xy, uint8_t *add_resp, uint8_t *add_desc, int *stats)
+{
+    if (B <= 0 || !h || !h[0]) return (int)OV2_ERR_INVALID;
+    std::vector<LoopExtraJob> jobs((size_t)B);
+    for (int k = 0; k < B; ++k) { jobs[k].closer = (LoopCloser *)h[k]; jobs[k].kfid = kfid[k]; jobs[k].b = b[k]; }
+    LoopExtraStats es;
+    const ov2_status s = LoopCloser::extraKeypoints(jobs[0].closer->ctx_, (const ov2_pyr *)pyr, jobs, es);
+    stats[0] = es.detect_calls; stats[1] = es.describe_calls;
+    if (s != OV2_OK) return (int)s;
+    bool fits = true;
+    for (int k = 0; k < B; ++k) {
+        const LoopExtraJob &J = jobs[k];
+        const int c[5] = {J.skipped ? 1 : 0, J.nbkps, (int)J.mask_px.size(), J.n_detected, (int)J.add_px.size()};
+        std::copy(c, c + 5, counts + 5 * k);
+        if ((int)J.mask_px.size() > cap || (int)J.add_px.size() > cap) { fits = false; continue; }
+        for (size_t i = 0; i < J.mask_px.size(); ++i) { mask_xy[((size_t)k * cap + i) * 2] = J.mask_px[i].x; mask_xy[((size_t)k * cap + i) * 2 + 1] = J.mask_px[i].y; }
+        for (size_t i = 0; i < J.add_px.size(); ++i) { add_xy[((size_t)k * cap + i) * 2] = J.add_px[i].x; add_xy[((size_t)k * cap + i) * 2 + 1] = J.add_px[i].y; }
+        std::copy(J.add_resp.begin(), J.add_resp.end(), add_resp + (size_t)k * cap);
+        std::copy(J.add_descs.begin(), J.add_descs.end(), add_desc + (size_t)k * cap * 32);
+    }
+    return fits ? 0 : (int)OV2_ERR_INVALID;
+}
+
+// LoopCloser::newKeyframes: out B x 13 = the ten of ov2h_loop_new_keyframe, then nbkps, extra keypoints described, descriptor
+// rows the detector received; stats B x 13 as there; extra_stats[2]: detect and describe calls of the step
+int ov2h_loop_new_keyframes_img(int B, void *const *h, const int *kfid, const unsigned long long *seeds, void *pyr, const int *b, int *out,
+                                int *stats, int *extra_stats)
+{
+    if (B <= 0 || !h) return (int)OV2_ERR_INVALID;
+    std::vector<LoopCloser *> lcs((LoopCloser *const *)h, (LoopCloser *const *)h + B);
+    std::vector<LoopNewKeyframeResult> res;
+    LoopExtraStats es;
+    const ov2_status s = LoopCloser::newKeyframes(lcs, std::vector<int>(kfid, kfid + B), std::vector<uint64_t>(seeds, seeds + B),
+                                                  (const ov2_pyr *)pyr, std::vector<int>(b, b + B), res, &es);
+    extra_stats[0] = es.detect_calls; extra_stats[1] = es.describe_calls;
+    if (s != OV2_OK) return (int)s;
+    for (int k = 0; k < B; ++k) {
+        const LoopNewKeyframeResult &r = res[k];
+        const int o[13] = {r.skipped ? 1 : 0, r.image_id, (int)r.det.status, (int)r.det.train_id, r.cand_kfid, r.matched.lckfid, r.matched.branch,
+                           (int)r.matched.vkplmids.size(), r.verified.branch, (int)r.verified.vkplmids.size(), r.nbkps, r.n_extra, r.n_descs};
+        std::copy(o, o + 13, out + 13 * k);
+        const LoopStats &L = lcs[k]->last_;
+        const int st[13] = {L.pairs, L.knn_pairs, L.epi_pairs, L.knn_calls, L.epi_calls, L.p3p_pairs, L.refine_pairs, L.track_pairs, L.pnp_pairs,
+                            L.p3p_calls, L.refine_calls, L.track_calls, L.pnp_calls};
+        std::copy(st, st + 13, stats + 13 * k);
+    }
+    return 0;
+}
+
+// LoopCloser::newKeyframe with the keyframe's raw image: one row of ov2h_loop_new_keyframes_img
+int ov2h_loop_new_keyframe_img(void *h, int kfid, unsigned long long seed, void *pyr, int b, int *out, int *stats, int *extra_stats)
+{
+    return ov2h_loop_new_keyframes_img(1, &h, &kfid, &seed, pyr, &b, out, stats, extra_stats);
+}
+
 }  // extern "C"
 
 // ---- loop detector (ov2_lcd.hpp): create with parameters, process / process_batch, and what the last call did -------------

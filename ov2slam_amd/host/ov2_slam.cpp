@@ -1295,21 +1295,38 @@ ov2_status LoopCloser::processLoopCandidates(const std::vector<std::pair<int, in
 ov2_status LoopCloser::newKeyframe(int kfid, uint64_t seed, LoopNewKeyframeResult &r)
 {   // the body of LoopCloser::run for one keyframe, :86-169
     r = LoopNewKeyframeResult();
-    const auto pnewkf = pmap_->getKeyframe(kfid);
-    if (!pnewkf) return OV2_ERR_INVALID;
-    if (!plcdetector_) plcdetector_.reset(new LCDetector(ctx_, lcd_params_));
     std::vector<uint8_t> descs;
-    for (const auto &kp : pnewkf->getKeypoints()) {                         // :97-109
-        const auto plm = pmap_->getMapPoint(kp.lmid_);
-        if (plm == nullptr) continue;
-        if (plm->has_desc_) descs.insert(descs.end(), plm->desc_.begin(), plm->desc_.end());
-    }
+    if (!mapPointDescs(kfid, descs, nullptr, nullptr)) return OV2_ERR_INVALID;
+    if (!plcdetector_) plcdetector_.reset(new LCDetector(ctx_, lcd_params_));
     if (descs.empty()) { r.skipped = true; return OV2_OK; }                // :111-113
     kf_idx_++;                                                              // :147-148
     vkfids_.push_back(kfid);
     r.image_id = kf_idx_;
+    r.n_descs = (int)(descs.size() / 32);
     ov2_status s = plcdetector_->process((unsigned)kf_idx_, descs.data(), (int)(descs.size() / 32), &r.det);   // :150-151
     if (s != OV2_OK) return s;
+    return afterDetector(kfid, seed, r);
+}
+
+bool LoopCloser::mapPointDescs(int kfid, std::vector<uint8_t> &descs, std::vector<Point2f> *px, int *nbkps) const
+{   // :89-109
+    const auto pnewkf = pmap_->getKeyframe(kfid);
+    if (!pnewkf) return false;
+    const auto vkps = pnewkf->getKeypoints();
+    if (nbkps) *nbkps = (int)vkps.size();
+    for (const auto &kp : vkps) {
+        const auto plm = pmap_->getMapPoint(kp.lmid_);
+        if (plm == nullptr) continue;
+        if (plm->has_desc_) {
+            descs.insert(descs.end(), plm->desc_.begin(), plm->desc_.end());
+            if (px) px->push_back(kp.px_);                                  // :107 the centre of a mask disc
+        }
+    }
+    return true;
+}
+
+ov2_status LoopCloser::afterDetector(int kfid, uint64_t seed, LoopNewKeyframeResult &r)
+{
     if (r.det.status != LC_DETECTED) return OV2_OK;                         // :156-164
     int cand = vkfids_.at(r.det.train_id);                                  // :187
     while (cand >= 0 && pmap_->getKeyframe(cand) == nullptr) cand--;        // :192-195
@@ -1317,11 +1334,148 @@ ov2_status LoopCloser::newKeyframe(int kfid, uint64_t seed, LoopNewKeyframeResul
     r.cand_kfid = cand;
     std::vector<LoopPairResult> matched;
     std::vector<LoopVerifyResult> verified;
-    s = processLoopCandidates({{kfid, cand}}, {seed}, matched, verified);   // :167
+    const ov2_status s = processLoopCandidates({{kfid, cand}}, {seed}, matched, verified);   // :167
     if (s != OV2_OK) return s;
     r.matched = matched[0];
     r.verified = verified[0];
     return OV2_OK;
+}
+
+ov2_status LoopCloser::extraKeypoints(ov2_ctx *ctx, const ov2_pyr *pyr, std::vector<LoopExtraJob> &jobs, LoopExtraStats &stats)
+{   // :95-134
+    stats = LoopExtraStats();
+    if (!ctx || !pyr) return OV2_ERR_INVALID;
+    const int B = ov2_pyr_batch(pyr);
+    std::vector<int> job_of((size_t)std::max(B, 0), -1);
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        LoopExtraJob &J = jobs[j];
+        if (!J.closer || J.b < 0 || J.b >= B || job_of[J.b] >= 0) return OV2_ERR_INVALID;
+        job_of[J.b] = (int)j;
+        J.skipped = false; J.nbkps = 0; J.n_detected = 0;
+        J.map_descs.clear(); J.mask_px.clear(); J.add_px.clear(); J.add_resp.clear(); J.add_descs.clear();
+        if (!J.closer->mapPointDescs(J.kfid, J.map_descs, &J.mask_px, &J.nbkps)) return OV2_ERR_INVALID;
+        J.skipped = J.map_descs.empty();                                    // :111-113, in front of the detection
+    }
+    const LoopCloser *first = nullptr;
+    for (const LoopExtraJob &J : jobs)
+        if (!J.skipped && !first) first = J.closer;
+    if (!first) return OV2_OK;
+    if (first->brief_pattern_.size() != 1024) return OV2_ERR_INVALID;
+    std::vector<int> n_mask((size_t)B, 0);
+    std::vector<float> mask_xy;
+    for (int b = 0; b < B; ++b) {                                           // image order: the layout of the call
+        if (job_of[b] < 0 || jobs[job_of[b]].skipped) continue;
+        const LoopExtraJob &J = jobs[job_of[b]];
+        n_mask[b] = (int)J.mask_px.size();
+        for (const Point2f &p : J.mask_px) { mask_xy.push_back(p.x); mask_xy.push_back(p.y); }
+    }
+    int cap = std::max(first->extra_out_cap_, 0);
+    std::vector<int> n_total((size_t)B), n_out((size_t)B);
+    std::vector<float> out_xy;
+    std::vector<uint8_t> out_resp;
+    for (int pass = 0; pass < 2; ++pass) {
+        out_xy.assign((size_t)B * cap * 2 + 2, 0.f);
+        out_resp.assign((size_t)B * cap + 1, 0);
+        const ov2_status s = ov2_fast_detect_batch(ctx, pyr, first->extra_fast_th_, first->extra_mask_radius_, n_mask.data(), mask_xy.data(),
+                                                   first->extra_nbest_, cap, n_total.data(), n_out.data(), out_xy.data(), out_resp.data());
+        if (s != OV2_OK) return s;
+        stats.detect_calls++;
+        int most = 0;
+        for (const LoopExtraJob &J : jobs)
+            if (!J.skipped) most = std::max(most, n_total[J.b]);
+        if (most <= cap) break;
+        if (pass == 1) return OV2_ERR_UNSUPPORTED;   // cannot happen: the repeat had room for every count of the first pass
+        cap = most;
+    }
+    std::vector<float> pts;
+    std::vector<int32_t> img;
+    for (LoopExtraJob &J : jobs) {
+        if (J.skipped) continue;
+        J.n_detected = n_total[J.b];
+        pts.insert(pts.end(), out_xy.begin() + (size_t)J.b * cap * 2, out_xy.begin() + ((size_t)J.b * cap + J.n_detected) * 2);
+        img.insert(img.end(), (size_t)J.n_detected, (int32_t)J.b);
+    }
+    const int n = (int)img.size();
+    if (n == 0) return OV2_OK;                                              // :125
+    std::vector<uint8_t> desc((size_t)n * 32), valid((size_t)n);
+    const ov2_status s = ov2_describe_brief_batch(ctx, pyr, n, pts.data(), img.data(), first->brief_pattern_.data(), desc.data(), valid.data());
+    if (s != OV2_OK) return s;
+    stats.describe_calls++;
+    size_t k = 0;
+    for (LoopExtraJob &J : jobs) {
+        if (J.skipped) continue;
+        for (int i = 0; i < J.n_detected; ++i, ++k) {
+            if (!valid[k]) continue;                                        // compute() removes the keypoints it cannot describe
+            J.add_px.push_back(Point2f{pts[2 * k], pts[2 * k + 1]});
+            J.add_resp.push_back(out_resp[(size_t)J.b * cap + i]);
+            J.add_descs.insert(J.add_descs.end(), desc.begin() + k * 32, desc.begin() + (k + 1) * 32);
+        }
+    }
+    return OV2_OK;
+}
+
+ov2_status LoopCloser::newKeyframes(const std::vector<LoopCloser *> &closers, const std::vector<int> &kfids, const std::vector<uint64_t> &seeds,
+                                    const ov2_pyr *pyr, const std::vector<int> &bs, std::vector<LoopNewKeyframeResult> &out, LoopExtraStats *stats)
+{
+    const size_t B = closers.size();
+    if (kfids.size() != B || seeds.size() != B || bs.size() != B) return OV2_ERR_INVALID;
+    out.assign(B, LoopNewKeyframeResult());
+    if (B == 0) return OV2_OK;
+    std::vector<LoopExtraJob> jobs(B);
+    for (size_t k = 0; k < B; ++k) {
+        if (!closers[k] || closers[k]->ctx_ != closers[0]->ctx_) return OV2_ERR_INVALID;
+        for (size_t j = 0; j < k; ++j)
+            if (closers[j] == closers[k]) return OV2_ERR_INVALID;
+        jobs[k].closer = closers[k]; jobs[k].kfid = kfids[k]; jobs[k].b = bs[k];
+        closers[k]->last_ = LoopStats();
+    }
+    LoopExtraStats es;
+    ov2_status s = extraKeypoints(closers[0]->ctx_, pyr, jobs, es);
+    if (stats) *stats = es;
+    if (s != OV2_OK) return s;
+    std::vector<LCDetector *> dets;
+    std::vector<unsigned> ids;
+    std::vector<std::vector<uint8_t>> descs;
+    std::vector<size_t> of;
+    for (size_t k = 0; k < B; ++k) {
+        LoopCloser &lc = *closers[k];
+        LoopNewKeyframeResult &r = out[k];
+        lc.last_extra_ = es;
+        r.nbkps = jobs[k].nbkps;
+        if (jobs[k].skipped) { r.skipped = true; continue; }                // :111-113
+        if (!lc.plcdetector_) lc.plcdetector_.reset(new LCDetector(lc.ctx_, lc.lcd_params_));
+        r.n_extra = (int)jobs[k].add_px.size();
+        descs.push_back(jobs[k].map_descs);                                 // :131-134 the extra ones behind the map points'
+        descs.back().insert(descs.back().end(), jobs[k].add_descs.begin(), jobs[k].add_descs.end());
+        r.n_descs = (int)(descs.back().size() / 32);
+        lc.kf_idx_++;                                                       // :147-148
+        lc.vkfids_.push_back(kfids[k]);
+        r.image_id = lc.kf_idx_;
+        dets.push_back(lc.plcdetector_.get());
+        ids.push_back((unsigned)lc.kf_idx_);
+        of.push_back(k);
+    }
+    if (dets.empty()) return OV2_OK;
+    std::vector<const uint8_t *> ptrs;
+    std::vector<int> n;
+    for (const auto &d : descs) { ptrs.push_back(d.data()); n.push_back((int)(d.size() / 32)); }
+    std::vector<LCDetectorResult> res(dets.size());
+    s = LCDetector::processBatch((int)dets.size(), dets.data(), ids.data(), ptrs.data(), n.data(), res.data());   // :150-151
+    if (s != OV2_OK) return s;
+    for (size_t i = 0; i < of.size(); ++i) {
+        out[of[i]].det = res[i];
+        closers[of[i]]->last_ = LoopStats();
+        if ((s = closers[of[i]]->afterDetector(kfids[of[i]], seeds[of[i]], out[of[i]])) != OV2_OK) return s;
+    }
+    return OV2_OK;
+}
+
+ov2_status LoopCloser::newKeyframe(int kfid, uint64_t seed, const ov2_pyr *pyr, int b, LoopNewKeyframeResult &r)
+{
+    std::vector<LoopNewKeyframeResult> out;
+    const ov2_status s = newKeyframes({this}, {kfid}, {seed}, pyr, {b}, out);
+    if (!out.empty()) r = out[0];
+    return s;
 }
 
 ov2_status LoopCloser::processLoopCandidate(int newkfid, int lckfid, uint64_t seed, LoopPairResult &r)

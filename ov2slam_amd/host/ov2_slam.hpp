@@ -210,9 +210,9 @@ struct LoopTrackStats {   // one trackLoopLocalMaps call
 // as a candidate keyframe?  The second half (:238-300) decides it: p3pRansac with a refinement, trackLoopLocalMap, computePnP,
 // for one pair as the reference writes it (verifyLoopCandidate) and for B pairs with one library call per stage
 // (verifyLoopCandidates).  newKeyframe is the body of LoopCloser::run for one keyframe (:86-169): the detector that proposes the
-// candidate (ov2::LCDetector, ov2_lcd.hpp) in front of processLoopCandidates.  Not built: the 300 extra FAST + BRIEF keypoints
-// of :115-140 (the detector sees the map points' descriptors only), the calls after an accepted loop (:302-372), and any
-// call from SlamManager's frame loop.
+// candidate (ov2::LCDetector, ov2_lcd.hpp) in front of processLoopCandidates; with the keyframe's raw image it also detects and
+// describes the 300 extra FAST + BRIEF keypoints of :115-140 (extraKeypoints) and hands the detector both sets.  Not built: the
+// calls after an accepted loop (:302-372), and any call from SlamManager's frame loop.
 struct LoopNewKeyframeResult {
     bool skipped = false;        // :111-113 no map point of the keyframe has a descriptor: the detector is not called
     int image_id = -1;           // kf_idx_ of this keyframe (index into vkfids_); -1 when skipped
@@ -220,6 +220,29 @@ struct LoopNewKeyframeResult {
     int cand_kfid = -1;          // on LC_DETECTED: vkfids_[train_id], walked down to the closest keyframe still in the map (:187-195)
     LoopPairResult matched;      // processLoopCandidates on (kfid, cand_kfid); untouched without a candidate
     LoopVerifyResult verified;
+    int nbkps = 0, n_extra = 0;  // the two counts the reference logs (:138): vkps.size() and vaddkps.size(); image forms only
+    int n_descs = 0;             // descriptor rows the detector received
+};
+
+class LoopCloser;
+
+struct LoopExtraJob {   // one (keyframe, raw image) pair of LoopCloser::extraKeypoints
+    LoopCloser *closer = nullptr;
+    int kfid = -1;
+    int b = 0;                           // image of the pyramid batch
+    // out
+    bool skipped = false;                // :111-113 no map point of the keyframe has a descriptor: nothing detected for it
+    int nbkps = 0;                       // vkps.size() (:90)
+    std::vector<uint8_t> map_descs;      // plm->desc_ of the keypoints whose map point exists and has one (:97-109), rows of 32
+    std::vector<Point2f> mask_px;        // kp.px_ of exactly those keypoints: the centres of the mask discs (:107)
+    int n_detected = 0;                  // keypoints after retainBest (:126)
+    std::vector<Point2f> add_px;         // the ones BRIEF describes (28 px or more from the border, :129), row-major
+    std::vector<uint8_t> add_resp;
+    std::vector<uint8_t> add_descs;      // rows of 32
+};
+
+struct LoopExtraStats {   // library calls of one extraKeypoints
+    int detect_calls = 0, describe_calls = 0;
 };
 
 class LoopCloser {
@@ -232,6 +255,27 @@ public:
     // longer in the map; below keyframe 0 there is no candidate, where the reference would not end) and the pair goes to
     // processLoopCandidates.  The detector is created on first use with lcd_params_ on this closer's context.
     ov2_status newKeyframe(int kfid, uint64_t seed, LoopNewKeyframeResult &r);
+    // :95-134 for B (keyframe, image b of `pyr`) pairs, `pyr` = level 0 of the RAW left images (built without CLAHE): the mask
+    // discs of radius 2 around the described keypoints, whole-image FAST(20) with non-maximum suppression, retainBest(300) and
+    // BRIEF on the raw image with the pattern of the first job's closer -- ONE ov2_fast_detect_batch call and ONE
+    // ov2_describe_brief_batch call whatever B is (none for the jobs that are skipped, which comes before detection, :111-113).
+    // The detect call has room for extra_out_cap_ keypoints per image; if an image has more, it is repeated once with room for
+    // the largest.  Keypoints without a descriptor (border) are dropped after retainBest, as compute does.  Images of the batch
+    // that no job names are detected on without a mask and ignored; two jobs on one image are OV2_ERR_INVALID.
+    static ov2_status extraKeypoints(ov2_ctx *ctx, const ov2_pyr *pyr, std::vector<LoopExtraJob> &jobs, LoopExtraStats &stats);
+    // newKeyframe with the keyframe's raw image: the same, with the extra descriptors appended behind the map points' (:131-134)
+    ov2_status newKeyframe(int kfid, uint64_t seed, const ov2_pyr *pyr, int b, LoopNewKeyframeResult &r);
+    // the step for B closers (distinct, on one context) and one keyframe each: one extraKeypoints, then LCDetector::processBatch
+    // over the closers that were not skipped, then processLoopCandidates for each closer whose detector proposed a candidate
+    static ov2_status newKeyframes(const std::vector<LoopCloser *> &closers, const std::vector<int> &kfids, const std::vector<uint64_t> &seeds,
+                                   const ov2_pyr *pyr, const std::vector<int> &bs, std::vector<LoopNewKeyframeResult> &out,
+                                   LoopExtraStats *stats = nullptr);
+    // the 256 test pairs of BRIEF-32, as SlamManager::setBriefPattern
+    void setBriefPattern(const int8_t *pattern256x4) { brief_pattern_.assign(pattern256x4, pattern256x4 + 1024); }
+    std::vector<int8_t> brief_pattern_;
+    int extra_fast_th_ = 20, extra_mask_radius_ = 2, extra_nbest_ = 300;   // :107, :123 (pfastd_ = FastFeatureDetector::create(20)), :126
+    int extra_out_cap_ = 2048;
+    LoopExtraStats last_extra_;   // of the last image-form newKeyframe(s) this closer took part in
     LCDetectorParams lcd_params_;
     std::unique_ptr<LCDetector> plcdetector_;
     std::vector<int> vkfids_;
@@ -308,6 +352,12 @@ public:
     ov2_ctx *ctx_;
     std::shared_ptr<SlamParams> pslamstate_;
     std::shared_ptr<MapManager> pmap_;
+
+private:
+    // :97-109: the descriptors of the keyframe's map points (and, with px, the pixels of those keypoints); false: no such keyframe
+    bool mapPointDescs(int kfid, std::vector<uint8_t> &descs, std::vector<Point2f> *px, int *nbkps) const;
+    // :187-195 and :167 behind a detector result
+    ov2_status afterDetector(int kfid, uint64_t seed, LoopNewKeyframeResult &r);
 };
 
 }  // namespace ov2

@@ -207,6 +207,81 @@ class LoopCloser:
             raise RuntimeError(f"newKeyframe: status {rc}")
         r = dict(zip(("skipped", "image_id", "status", "train_id", "cand_kfid", "lckfid", "branch", "n_passed", "verify_branch", "n_final"),
                      out.tolist()))
-        r["stats"] = dict(zip(("pairs", "knn_pairs", "epi_pairs", "knn_calls", "epi_calls", "p3p_pairs", "refine_pairs", "track_pairs",
-                               "pnp_pairs", "p3p_calls", "refine_calls", "track_calls", "pnp_calls"), st.tolist()))
+        r["stats"] = dict(zip(_LOOP_STATS, st.tolist()))
         return r
+
+    def set_brief_pattern(self, pattern):
+        """the 256 BRIEF-32 test pairs (256 x {y1, x1, y2, x2}, int8) the extra keypoints are described with"""
+        pat = np.ascontiguousarray(pattern, np.int8).reshape(256, 4)
+        self.L.ov2h_loop_set_brief_pattern.argtypes = [vp, vp]
+        self.L.ov2h_loop_set_brief_pattern(self.h, pat.ctypes.data_as(vp))
+
+    def set_extra_cap(self, cap):
+        """room per image of the first detect call of extraKeypoints"""
+        self.L.ov2h_loop_set_extra_cap.argtypes = [vp, C.c_int]
+        self.L.ov2h_loop_set_extra_cap(self.h, int(cap))
+
+    def detector_counts(self):
+        """Detector.counts() of the closer's own detector (None before its first keyframe)"""
+        self.L.ov2h_loop_closer_detector.restype = vp
+        self.L.ov2h_loop_closer_detector.argtypes = [vp]
+        h = self.L.ov2h_loop_closer_detector(self.h)
+        if not h:
+            return None
+        out = np.zeros(10, np.int32)
+        self.L.ov2h_lcd_counts(vp(h), out.ctypes.data_as(vp))
+        return dict(zip(("images", "words", "dev_slots", "dev_live", "dev_compactions", "n_add_matches", "n_matches", "n_added",
+                         "n_purged", "n_islands"), out.tolist()))
+
+    def new_keyframe_img(self, kfid, seed, pyr, b=0):
+        """newKeyframe with the keyframe's raw image (image b of `pyr`): the extra FAST + BRIEF keypoints go to the detector too"""
+        return new_keyframes([self], [kfid], [seed], pyr, [b])[0]
+
+
+_LOOP_STATS = ("pairs", "knn_pairs", "epi_pairs", "knn_calls", "epi_calls", "p3p_pairs", "refine_pairs", "track_pairs", "pnp_pairs",
+               "p3p_calls", "refine_calls", "track_calls", "pnp_calls")
+
+
+def _closer_args(closers, kfids, bs):
+    B = len(closers)
+    return (B, (vp * B)(*[c.h for c in closers]), np.ascontiguousarray(kfids, np.int32), np.ascontiguousarray(bs, np.int32))
+
+
+def extra_keypoints(closers, kfids, pyr, bs, cap=4096):
+    """LoopCloser::extraKeypoints for B closers: one dict per job (skipped, nbkps, mask_xy, n_detected, add_xy, add_resp, add_desc)
+    and the (detect, describe) call counts"""
+    L = closers[0].L
+    B, hs, kf, b = _closer_args(closers, kfids, bs)
+    counts, stats = np.zeros((B, 5), np.int32), np.zeros(2, np.int32)
+    mxy, axy = np.zeros((B, cap, 2), np.float32), np.zeros((B, cap, 2), np.float32)
+    ar, ad = np.zeros((B, cap), np.uint8), np.zeros((B, cap, 32), np.uint8)
+    P = lambda a: a.ctypes.data_as(vp)
+    L.ov2h_loop_extra_keypoints.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    rc = L.ov2h_loop_extra_keypoints(B, hs, P(kf), pyr.h, P(b), cap, P(counts), P(mxy), P(axy), P(ar), P(ad), P(stats))
+    if rc != 0:
+        raise RuntimeError(f"extraKeypoints: status {rc}")
+    jobs = [dict(skipped=int(c[0]), nbkps=int(c[1]), mask_xy=mxy[k, :c[2]].copy(), n_detected=int(c[3]), add_xy=axy[k, :c[4]].copy(),
+                 add_resp=ar[k, :c[4]].copy(), add_desc=ad[k, :c[4]].copy()) for k, c in enumerate(counts)]
+    return jobs, dict(detect_calls=int(stats[0]), describe_calls=int(stats[1]))
+
+
+def new_keyframes(closers, kfids, seeds, pyr, bs):
+    """LoopCloser::newKeyframes: B closers stepped together on the images bs of `pyr`; one dict per closer as new_keyframe returns
+    it, plus nbkps, n_extra, n_descs and `extra` = the (detect, describe) call counts of the step"""
+    L = closers[0].L
+    B, hs, kf, b = _closer_args(closers, kfids, bs)
+    sd = np.ascontiguousarray(seeds, np.uint64)
+    out, st, es = np.zeros((B, 13), np.int32), np.zeros((B, 13), np.int32), np.zeros(2, np.int32)
+    P = lambda a: a.ctypes.data_as(vp)
+    L.ov2h_loop_new_keyframes_img.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    rc = L.ov2h_loop_new_keyframes_img(B, hs, P(kf), P(sd), pyr.h, P(b), P(out), P(st), P(es))
+    if rc != 0:
+        raise RuntimeError(f"newKeyframes: status {rc}")
+    res = []
+    for k in range(B):
+        r = dict(zip(("skipped", "image_id", "status", "train_id", "cand_kfid", "lckfid", "branch", "n_passed", "verify_branch", "n_final",
+                      "nbkps", "n_extra", "n_descs"), out[k].tolist()))
+        r["stats"] = dict(zip(_LOOP_STATS, st[k].tolist()))
+        r["extra"] = dict(detect_calls=int(es[0]), describe_calls=int(es[1]))
+        res.append(r)
+    return res
