@@ -898,8 +898,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
 // full, there is no intra-workgroup imbalance, and the grid needs no host-side knowledge of the live count.
 
 // pass 1 lists the keypoints with a prior (list A, 2 pyramid levels) and those without (list B, full pyramid: they do
-// not depend on the outcome of the first group, so both groups run in ONE launch); pass 2 lists the failures of
-// list A, which are re-tracked on the full pyramid once the per-image tally of list A is complete (the 33 % rule).
+// not depend on the outcome of the first group, so for kltTracking both groups run in ONE launch); the failures of
+// list A (list C) are re-tracked on the full pyramid once the per-image tally of list A is complete (the 33 % rule).
+// stereoMatching has no such rule and long list-B waves: there list B runs in the second launch, in front of list C.
 __global__ __launch_bounds__(256) void klt_compact_kernel(int n, int pass, const unsigned char *__restrict__ has_prior,
                                                           const unsigned char *__restrict__ out_status,
                                                           unsigned *__restrict__ iters, int *__restrict__ list_a,
@@ -979,12 +980,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
                                                         unsigned *__restrict__ counts /* [batch][64] slots: low 16 bits n3d, high 16 good */,
                                                         unsigned *__restrict__ iters, const int *__restrict__ list_a,
                                                         const int *__restrict__ list_b, unsigned *__restrict__ cnt,
-                                                        int *__restrict__ list_c)
+                                                        int *__restrict__ list_c,
+                                                        int b_word /* cnt[b_word] = length of list B for THIS launch: 1, or the zero word 3 when the second launch takes the list */)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[klt_smem<WIN, KLT_GL>::BYTES];
     using M = klt_map<KLT_GL>;
     constexpr int KLT_KPW = M::KPW;
-    const int total_a = (int)cnt[0], total_b = (int)cnt[1];
+    const int total_a = (int)cnt[0], total_b = (int)cnt[b_word];
     // list B first: its waves run the full pyramid (about twice the work of a list-A wave), so the short list-A waves
     // fill the tail of the launch instead of the long ones forming it
     const int groups_b = (total_b + KLT_KPW - 1) / KLT_KPW;
@@ -999,7 +1001,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
     const float2 kp = kps[i];
     const int b = img_idx ? img_idx[i] : 0;
     // kltTracking: keypoints without a prior start from their own position (vpriors = vkps, :181-183); stereoMatching's
-    // full-pyramid list carries priors of its own (kp.px_ or the SAD prior, src/map_manager.cpp:419-436,486-488)
+    // full-pyramid list carries priors of its own (kp.px_ or the SAD prior, src/map_manager.cpp:419-436,486-488).
+    // Invariant of ov2_klt_two_stage_dev's b_word1 / b_word2: the B segment of THIS launch is kltTracking's and that of the
+    // second launch stereoMatching's, so no caller reaches the !P.rule33 arm for list B today; it stays so that a host that
+    // hands B here without the rule still tracks it as klt_stage2_kernel's B segment would
     float2 pr = (is_a || !P.rule33) ? prior[i] : kp;
     unsigned work = 0;
     const int nl = is_a ? min(1, pv.nlevels - 1) : P.nlevels;
@@ -1008,7 +1013,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
 }
 
 // second launch: the failures of list A, full pyramid, from the failed forward result -- or from the keypoint itself
-// when less than 33 % of the image's list-A keypoints were tracked (:228-233, which also raises bp3preq_)
+// when less than 33 % of the image's list-A keypoints were tracked (:228-233, which also raises bp3preq_).
+// For stereoMatching a leading segment of workgroups tracks list B here instead of in the first launch: list B's waves
+// and the re-tracked ones are equally long (full pyramid, far from the answer), and run one behind the other they made two
+// tails -- the first launch lasted as long as its B waves, then a few lone re-tracking waves of the same length ran on an
+// idle device.  Nothing orders the two lists (no 33 % rule, list B reads no result of list A), so the first launch
+// tracks list A alone and B shares this launch with the re-tracking.
 template <int WIN, int KLT_GL>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WIN, KLT_GL)))) void klt_stage2_kernel(ov2_pyr_view pv, ov2_pyr_view cv, klt_params P, int n,
                                                         const float2 *__restrict__ kps,
@@ -1017,7 +1027,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
                                                         const unsigned *__restrict__ counts, int *__restrict__ p3p_req,
                                                         unsigned *__restrict__ iters, const int *__restrict__ list_c,
                                                         const unsigned *__restrict__ cnt, int batch,
-                                                        unsigned *__restrict__ next_counts, int next_words)
+                                                        unsigned *__restrict__ next_counts, int next_words,
+                                                        const int *__restrict__ list_b, int b_word,
+                                                        const float2 *__restrict__ prior)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[klt_smem<WIN, KLT_GL>::BYTES];
     using M = klt_map<KLT_GL>;
@@ -1053,17 +1065,31 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
             if (b < batch && lane_ok && sub == 0 && n3 > 0 && (double)good < 0.33 * (double)n3) p3p_req[b] = 1;
         }
     }
-    const int total = (int)cnt[2];
-    if ((int)blockIdx.x * KLT_KPW >= total) return;
-    const int idx = blockIdx.x * KLT_KPW + slot;
+    // list B first (workgroups [0, groups_b)), then the re-tracking list: both run the full pyramid, so the launch has ONE
+    // tail.  The host hands list B to exactly one of the two launches (cnt[b_word] is the list's length here and a zero
+    // word there); B and the failures of A are disjoint, so groups_b + groups_c <= ceil(n / KPW) + 2, the grid
+    const int total_b = (int)cnt[b_word];
+    const int groups_b = (total_b + KLT_KPW - 1) / KLT_KPW;
+    const bool is_b = (int)blockIdx.x < groups_b;
+    const int g = is_b ? (int)blockIdx.x : (int)blockIdx.x - groups_b;
+    const int total = is_b ? total_b : (int)cnt[2];
+    if (g * KLT_KPW >= total) return;
+    const int idx = g * KLT_KPW + slot;
     const bool act = idx < total && lane_ok;
-    const int i = list_c[idx < total ? idx : total - 1];
+    const int i = (is_b ? list_b : list_c)[idx < total ? idx : total - 1];
     const int b = img_idx ? img_idx[i] : 0;
-    int n3, good;
-    tally(b, n3, good);
-    const bool drop = P.rule33 && n3 > 0 && (double)good < 0.33 * (double)n3;  // :228
     const float2 kp = kps[i];
-    float2 pr = drop ? kp : out_xy[i];
+    float2 pr;
+    if (is_b) {   // as the first launch tracks the list for stereoMatching: from the caller's prior, no tally, no append
+        // the B segment of this launch is stereoMatching's alone (rule33 = 0; the host's b_word1 / b_word2 choice in
+        // ov2_klt_two_stage_dev): kltTracking's list B starts from kp and belongs to the first launch, never here
+        pr = prior[i];
+    } else {
+        int n3, good;
+        tally(b, n3, good);
+        const bool drop = P.rule33 && n3 > 0 && (double)good < 0.33 * (double)n3;  // :228
+        pr = drop ? kp : out_xy[i];
+    }
     unsigned work = 0;
     const int ok = fb_track<WIN, KLT_GL>(pv, cv, b, act, kp.x, kp.y, pr.x, pr.y, P, P.nlevels, sub, lane_ok, work, smem, slot);
     if (act && sub == 0) {
@@ -1220,7 +1246,7 @@ ov2_status ov2_klt_two_stage_dev(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr 
     const int lanes = klt_lanes_for(c, n, win, prev, cur);
     if (lanes != 3 && ((s = ov2_pyr_need_grad(c, prev)) != OV2_OK || (s = ov2_pyr_need_grad(c, cur)) != OV2_OK)) return s;
     const int B = prev->buf->batch;
-    // counters: [tallies B x 64 | list lengths (3), words 3 and 4 unused, padded to 16] in the ctx's double buffer (zeroed by
+    // counters: [tallies B x 64 | list lengths (3), word 3 never written: the zero length of an empty list B, padded to 16] in the ctx's double buffer (zeroed by
     // the previous call's last kernel); scratch: the three keypoint lists
     const size_t cnt_words = (size_t)B * 64 + 16;
     if (cnt_words > c->klt_counts_words) {
@@ -1250,19 +1276,25 @@ ov2_status ov2_klt_two_stage_dev(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr 
         c->kf.want_stereo_ev = false;
     }
     const dim3 cgrid((n + 255) / 256);
+    // which launch tracks list B: the first for kltTracking (the 33 % rule orders the re-tracking behind list A's tally, and
+    // B fills the first launch), the second for stereoMatching (see klt_stage2_kernel).  The other launch reads B's length
+    // from word 3 of the list-length block, which nothing writes: zero, so its B segment is empty
+    const int b_word1 = P.rule33 ? 1 : 3, b_word2 = P.rule33 ? 3 : 1;
 #define KLT_STAGES_GL(W, G)                                                                                     \
     do {                                                                                                        \
-        const dim3 tgrid((n + klt_map<G>::KPW - 1) / klt_map<G>::KPW + 1);   /* groups of list A + groups of list B <= n/KPW + 2 */ \
+        /* two disjoint lists of the n keypoints: groups of the one + groups of the other <= ceil(n / KPW) + 2 */ \
+        const dim3 tgrid((n + klt_map<G>::KPW - 1) / klt_map<G>::KPW + 2);                                      \
         OV2_LAUNCH(c, OV2_K_DETECT + 4, klt_compact_kernel, cgrid, dim3(256), 0, c->stream, n, 1, d_has_prior,  \
                    d_out_status, d_iters, list_a, list_b, live_cnt, d_p3p_req, B);                              \
-        OV2_LAUNCH(c, OV2_K_KLT_STAGE1, (klt_stage1_kernel<W, G>), dim3(tgrid.x + 1), dim3(64), 0, c->stream,   \
+        OV2_LAUNCH(c, OV2_K_KLT_STAGE1, (klt_stage1_kernel<W, G>), tgrid, dim3(64), 0, c->stream,               \
                    prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps),              \
                    reinterpret_cast<const float2 *>(d_prior), d_img_idx, reinterpret_cast<float2 *>(d_out_xy),  \
-                   d_out_status, counts, d_iters, list_a, list_b, live_cnt, list_c);                           \
+                   d_out_status, counts, d_iters, list_a, list_b, live_cnt, list_c, b_word1);                  \
         OV2_LAUNCH(c, OV2_K_KLT_STAGE2, (klt_stage2_kernel<W, G>), tgrid, dim3(64), 0, c->stream,               \
                    prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps), d_img_idx,   \
                    reinterpret_cast<float2 *>(d_out_xy), d_out_status, counts, d_p3p_req, d_iters, list_c,      \
-                   live_cnt, B, next_counts, next_words);                                                       \
+                   live_cnt, B, next_counts, next_words, list_b, b_word2,                                       \
+                   reinterpret_cast<const float2 *>(d_prior));                                                  \
     } while (0)
 #define KLT_STAGES(W)                                                                                           \
     do {                                                                                                        \

@@ -6,6 +6,10 @@
   their overlap, the length of the period (stereo start to the next stereo start), and the summed kernel durations of
   the period by group (tracking + stereo, detector chain, pyramid builds, everything else) with the hardware queues
   each group ran on -- two groups that share a queue cannot overlap.
+A second table splits the stereo interval kernel by kernel (klt_compact_kernel, the first and the second tracking launch,
+epi_gate_kernel and the gaps between them) with the detector chain's interval, the period, the idle time of the tracking
+kernels' queue and that of the pyramid builds' queue (over the period, and the part of it inside the stereo interval) beside
+it, and closes with the mean and the lower quartile / median / upper quartile of every column.
 usage: kf_overlap_trace.py <kernel_trace.csv or a directory holding one> [more traces ...]"""
 import csv
 import glob
@@ -88,6 +92,75 @@ def report(path):
         n += 1
     if n:
         print("mean " + "  ".join(f"{k} {v / n:.1f}" for k, v in tot.items()) + f"  (us, {n} periods)")
+    split(rows, kfs)
+
+
+SPLIT = ("klt_compact_kernel", "klt_stage1_kernel", "klt_stage2_kernel", "epi_gate_kernel")
+
+
+def idle(rows, q, t0, t1):
+    """[t0, t1) minus the union of the kernel intervals of queue q (rows are sorted by start)"""
+    busy, end = 0, t0
+    for r in rows:
+        if r[3] == q and r[1] > t0 and r[0] < t1:
+            a, b = max(r[0], end), min(r[1], t1)
+            if b > a:
+                busy += b - a
+                end = b
+    return t1 - t0 - busy
+
+
+def quartiles(v):
+    """lower quartile, median, upper quartile (linear interpolation between the order statistics)"""
+    v = sorted(v)
+    def at(p):
+        x = p * (len(v) - 1)
+        lo = int(x)
+        return v[lo] + (v[min(lo + 1, len(v) - 1)] - v[lo]) * (x - lo)
+    return at(0.25), at(0.5), at(0.75)
+
+
+def split(rows, kfs):
+    """the stereo interval kernel by kernel (the call's four launches in stream order and the gaps between them) with the
+    detector chain's interval beside it, the idle time of the tracking kernels' queue over the period, and the idle time
+    of the pyramid builds' queue over the period and inside the stereo interval; then mean and quartiles of every column"""
+    us = lambda ns: ns / 1000.0
+    cols = ("compact", "gap", "stage1", "gap", "stage2", "gap", "epi_gate")
+    print("kf  " + "  ".join(f"{c:>8s}" for c in cols) + "  | stereo_us  det_us  period_us  tracking_queue_idle_us  "
+          "pyramid_queue_idle_us  of_it_in_stereo_us")
+    names = ("compact", "gap1", "stage1", "gap2", "stage2", "gap3", "epi_gate", "stereo", "det", "period", "tracking_queue_idle",
+             "pyramid_queue_idle", "pyramid_queue_idle_in_stereo")
+    table = []
+    for k, (i0, i1) in enumerate(kfs):
+        if k + 1 >= len(kfs):
+            continue
+        call = [r for r in rows[i0:i1 + 1] if r[2] in SPLIT]
+        if [r[2] for r in call] != list(SPLIT):
+            continue      # not the plain four-launch call (another call's kernels of the same names in between)
+        s0, s1, nxt = call[0][0], call[-1][1], rows[kfs[k + 1][0]][0]
+        det = [r for r in rows if r[2] in DET and s0 <= r[0] < nxt]
+        if not det:
+            continue
+        vals = []
+        for j, r in enumerate(call):
+            vals.append(us(r[1] - r[0]))
+            if j + 1 < len(call):
+                vals.append(us(call[j + 1][0] - r[1]))
+        # the queue the pyramid builds of this period run on (the one that holds most of their kernel time)
+        pq = defaultdict(int)
+        for r in rows:
+            if s0 <= r[0] < nxt and group(r[2]) == "pyramid":
+                pq[r[3]] += r[1] - r[0]
+        pyr = max(pq, key=pq.get) if pq else None
+        vals += [us(s1 - s0), us(max(r[1] for r in det) - min(r[0] for r in det)), us(nxt - s0), us(idle(rows, call[0][3], s0, nxt)),
+                 us(idle(rows, pyr, s0, nxt)) if pq else float("nan"), us(idle(rows, pyr, s0, s1)) if pq else float("nan")]
+        print(f"{k:2d}  " + "  ".join(f"{v:8.1f}" for v in vals[:len(cols)]) + "  | " + "  ".join(f"{v:9.1f}" for v in vals[len(cols):]))
+        table.append(vals)
+    if table:
+        n = len(table)
+        print("mean split " + "  ".join(f"{k} {sum(c) / n:.1f}" for k, c in zip(names, zip(*table))) + f"  (us, {n} periods)")
+        print("lower quartile / median / upper quartile  " +
+              "  ".join(f"{k} {'/'.join(f'{q:.1f}' for q in quartiles(c))}" for k, c in zip(names, zip(*table))))
 
 
 if __name__ == "__main__":
