@@ -178,6 +178,10 @@ struct map_job {
     int fl_active;                               // 0: gated map (ratio >= 1 or newkf < 20), zero header and no work
     int *fl_nobs, *fl_cov, *fl_n3d, *fl_cnt, *fl_fill, *fl_start, *fl_rows, *fl_unset;
     unsigned char *fl_new;
+    // pose-graph update (hdr / zero_blk point at the temporal stage's block; the anchor scan lands in tt_old)
+    int pg_n;                                    // free keyframes of the graph, 0: nothing to do for this map
+    const int *pg_kfid; const double *pg_Twc;    // their ids (ascending, last = newkf) and optimised poses, in the staging block
+    double *pg_tmp;                              // 14 doubles behind hdr_out: inverse(old(newkf)) | T_corr
 };
 
 // the flat problem of one map inside its output block: the same carve on the device (emitters, update stage) and on the
@@ -1041,6 +1045,125 @@ __global__ __launch_bounds__(MF_THREADS) void mf_walk_kernel(const map_job *__re
     }
 }
 
+// ---- update stage of Optimizer::localPoseGraph (src/optimizer.cpp:2476-2577) on the tables ------------------------------
+// The free keyframes of the graph (listed, ascending, last = newkf) take their optimised poses, every younger keyframe k
+// moves rigidly with the new one (opt * (ini * old(k)), ini = inverse(old(newkf))), and a landmark moves with the keyframe
+// that anchors it (MapPoint::kfid_ = its oldest live observer) when that keyframe moved and the landmark's keypoints are
+// 3D: xyz' = new(a) * (inverse(old(a)) * xyz).  Three scans: anchors (rows), landmarks -- which read the OLD poses and
+// work out new(a) themselves --, then the poses.  ini and T_corr = opt * ini are written once, by the first scan, into
+// the map's slot behind its gathered header, so that no scan reads the pose of newkf while another lane replaces it.
+enum { PH_KF_CHAIN = 0, PH_KF_YOUNGER, PH_LM_MOVED };
+
+// SE3::operator*(Vec3) of the host mirror
+__device__ __forceinline__ void se3_apply(const double *T, const double *p, double out[3])
+{
+    double R[9];
+    ov2se3::pose_R(T, R);
+    out[0] = R[0] * p[0] + R[1] * p[1] + R[2] * p[2] + T[0];
+    out[1] = R[3] * p[0] + R[4] * p[1] + R[5] * p[2] + T[1];
+    out[2] = R[6] * p[0] + R[7] * p[1] + R[8] * p[2] + T[2];
+}
+
+// place of keyframe kf in the ascending list, -1 when it is not listed
+__device__ __forceinline__ int pg_listed(const map_job &j, int kf)
+{
+    int lo = 0, hi = j.pg_n - 1;
+    while (lo <= hi) {
+        const int mid = (lo + hi) >> 1, v = j.pg_kfid[mid];
+        if (v == kf) return mid;
+        if (v < kf) lo = mid + 1; else hi = mid - 1;
+    }
+    return -1;
+}
+
+// the pose keyframe k ends with: its listed pose, opt * (ini * old(k)) when it is younger than newkf, else none (false).
+// For a keyframe that moves both candidates are formed and one is selected element by element: nothing is indexed
+// dynamically, nothing spills.
+__device__ __forceinline__ bool pg_new_pose(const map_job &j, int k, double out[7], bool &listed)
+{
+    const int idx = pg_listed(j, k);
+    listed = idx >= 0;
+    if (!listed && k <= j.newkf) return false;      // neither listed nor younger: nothing to work out
+    double rel[7], y[7];
+    se3_mul(j.pg_tmp, j.M.kf_pose + 7 * (size_t)k, rel);
+    se3_mul(j.pg_Twc + 7 * (size_t)(j.pg_n - 1), rel, y);
+    const double *L = j.pg_Twc + 7 * (size_t)(listed ? idx : 0);
+#pragma unroll
+    for (int q = 0; q < 7; ++q) out[q] = listed ? L[q] : y[q];
+    return true;
+}
+
+__global__ __launch_bounds__(256) void mp_anchor_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (!j.pg_n) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        double ini[7], corr[7];
+        se3_inverse(M.kf_pose + 7 * (size_t)j.newkf, ini);
+        se3_mul(j.pg_Twc + 7 * (size_t)(j.pg_n - 1), ini, corr);
+#pragma unroll
+        for (int q = 0; q < 7; ++q) { j.pg_tmp[q] = ini[q]; j.pg_tmp[7 + q] = corr[q]; }
+    }
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf, lm;
+    if (i >= M.n_obs || !obs_live(M, i, kf, lm)) return;
+    atomicMax(&j.tt_old[lm], ANCH_TOP - kf);       // the smallest kfid wins
+}
+
+// one lane per landmark; the poses are still the old ones
+__global__ __launch_bounds__(256) void mp_landmarks_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (!j.pg_n || (int)blockIdx.x * 256 >= M.max_lm) return;   // uniform per workgroup
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    bool moved = false;
+    if (l < M.max_lm) {
+        const unsigned char st = M.lm_state[l];
+        const int o = j.tt_old[l];
+        if ((st & OV2_LM_ALIVE) && (st & OV2_LM_KP3D) && o) {
+            const int a = ANCH_TOP - o;
+            double Tnew[7];
+            bool listed;
+            if (pg_new_pose(j, a, Tnew, listed)) {
+                double Tcw[7], cam[3], w[3];
+                se3_inverse(M.kf_pose + 7 * (size_t)a, Tcw);
+                se3_apply(Tcw, M.lm_xyz + 3 * (size_t)l, cam);      // Frame::projWorldToCam
+                se3_apply(Tnew, cam, w);
+                j.lm_xyz_w[3 * (size_t)l] = w[0]; j.lm_xyz_w[3 * (size_t)l + 1] = w[1]; j.lm_xyz_w[3 * (size_t)l + 2] = w[2];
+                j.lm_state_w[l] = st | OV2_LM_3D;                   // MapManager::updateMapPoint -> MapPoint::setPoint
+                moved = true;
+            }
+        }
+    }
+    const unsigned long long bal = __ballot(moved);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&j.hdr[PH_LM_MOVED], __popcll(bal));
+}
+
+// one lane per keyframe: a lane reads its own old pose only (and ini from the map's slot)
+__global__ __launch_bounds__(256) void mp_poses_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (!j.pg_n || (int)blockIdx.x * 256 >= M.max_kf) return;   // uniform per workgroup
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    bool listed = false, moved = false;
+    if (k < M.max_kf && M.kf_state[k]) {
+        double T[7];
+        moved = pg_new_pose(j, k, T, listed);
+        if (moved) {
+#pragma unroll
+            for (int q = 0; q < 7; ++q) j.kf_pose_w[7 * (size_t)k + q] = T[q];
+        }
+    }
+    const unsigned long long bl = __ballot(moved && listed), by = __ballot(moved && !listed);
+    if ((threadIdx.x & 63) == 0) {
+        if (bl) atomicAdd(&j.hdr[PH_KF_CHAIN], __popcll(bl));
+        if (by) atomicAdd(&j.hdr[PH_KF_YOUNGER], __popcll(by));
+    }
+}
+
 // gathers the headers of all maps (update counts) for one D2H
 __global__ __launch_bounds__(64) void mb_hdr_gather_kernel(const map_job *__restrict__ J)
 {
@@ -1097,21 +1220,27 @@ struct job_table {
     map_job *host = nullptr; const map_job *dev = nullptr;
     int *hdr_host = nullptr, *hdr_dev = nullptr;
     size_t stride = MH_N;                        // ints per map in the gathered copy: the header, then what the stage appends
-    ov2_status begin(ov2_ctx *ctx, int nb, int extra_ints = 0)
+    unsigned char *tail_host = nullptr, *tail_dev = nullptr;   // tail_bytes of call arguments behind the headers (256-aligned)
+    size_t tail_off = 0, tail_bytes = 0;
+    ov2_status begin(ov2_ctx *ctx, int nb, int extra_ints = 0, size_t tail = 0)
     {
-        c = ctx; B = nb; stride = MH_N + (size_t)extra_ints;
+        c = ctx; B = nb; stride = MH_N + (size_t)extra_ints; tail_bytes = tail;
         void *h, *d;
         const size_t tab = ((size_t)B * sizeof(map_job) + 255) & ~(size_t)255;
-        const ov2_status s = ov2_staging(c, tab + (size_t)B * stride * sizeof(int) + 256, &h, &d);
+        tail_off = (tab + (size_t)B * stride * sizeof(int) + 255) & ~(size_t)255;
+        const ov2_status s = ov2_staging(c, tail_off + tail + 256, &h, &d);
         if (s != OV2_OK) return s;
         host = (map_job *)h; dev = (const map_job *)d;
         hdr_host = (int *)((unsigned char *)h + tab); hdr_dev = (int *)((unsigned char *)d + tab);
+        tail_host = (unsigned char *)h + tail_off; tail_dev = (unsigned char *)d + tail_off;
         return OV2_OK;
     }
     void set(int b, const map_job &j) { host[b] = j; host[b].hdr_out = hdr_dev + (size_t)b * stride; }
     ov2_status upload()
     {
-        OV2_HIP(c, hipMemcpyAsync((void *)dev, host, (size_t)B * sizeof(map_job), hipMemcpyHostToDevice, c->stream));
+        // one copy: the records alone, or everything up to the end of the tail when the call has one
+        const size_t bytes = tail_bytes ? tail_off + tail_bytes : (size_t)B * sizeof(map_job);
+        OV2_HIP(c, hipMemcpyAsync((void *)dev, host, bytes, hipMemcpyHostToDevice, c->stream));
         // calls that return without synchronising leave this copy in flight: the next user of the staging block waits for it
         OV2_HIP(c, hipEventRecord(c->stage_ev, c->stream));
         c->stage_ev_pending = true;
@@ -1945,6 +2074,78 @@ extern "C" ov2_status ov2_map_filter_keyframes_batch(ov2_ctx *c, int B, ov2_map 
             m->kf_alive_h[k] = 0;
         }
         m->last_valid = 0;   // its tables changed under the last set-up: no update stage from it any more
+    }
+    return OV2_OK;
+}
+
+// ---- pose-graph update of B maps: four launches whatever B, no synchronisation unless the headers are asked for -------
+extern "C" ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf,
+                                                      const int32_t *chain_off, const int32_t *chain_kfid, const double *chain_Twc,
+                                                      ov2_map_pg_update *out)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps || !newkf || !chain_off) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_pose_graph_update_batch: null argument");
+    ov2_status s;
+    int n_active = 0;
+    if (chain_off[0] != 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_pose_graph_update_batch: chain_off[0] must be 0");
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
+        const int n = chain_off[b + 1] - chain_off[b];
+        if (n < 0) return ov2_set_err(c, OV2_ERR_INVALID, "map %d: chain_off descends", b);
+        if (!n) continue;
+        if (!chain_kfid || !chain_Twc) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_pose_graph_update_batch: null argument");
+        if ((s = batch_kf_alive(c, m, newkf[b], b)) != OV2_OK) return s;
+        const int32_t *ids = chain_kfid + chain_off[b];
+        for (int i = 0; i < n; ++i) {
+            if ((s = batch_kf_alive(c, m, ids[i], b)) != OV2_OK) return s;
+            if (i && ids[i] <= ids[i - 1]) return ov2_set_err(c, OV2_ERR_INVALID, "map %d: the listed keyframes do not ascend (%d after %d)", b, ids[i], ids[i - 1]);
+        }
+        if (ids[n - 1] != newkf[b])
+            return ov2_set_err(c, OV2_ERR_INVALID, "map %d: the list ends in keyframe %d, not in the new keyframe %d", b, ids[n - 1], newkf[b]);
+        ++n_active;
+    }
+    if (out) memset(out, 0, (size_t)B * sizeof(*out));
+    if (!n_active) return OV2_OK;
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t total = (size_t)chain_off[B];
+    const size_t ids_bytes = (total * sizeof(int32_t) + 15) & ~(size_t)15;
+    job_table JT;
+    if ((s = JT.begin(c, B, 28, ids_bytes + total * 7 * sizeof(double))) != OV2_OK) return s;   // 28 ints = 14 doubles per map
+    memcpy(JT.tail_host, chain_kfid, total * sizeof(int32_t));
+    memcpy(JT.tail_host + ids_bytes, chain_Twc, total * 7 * sizeof(double));
+    int nmax = 0, lmax = 0, kmax = 0; unsigned zmax = 0;
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = maps[b];
+        map_job j = job_of(m, newkf[b], -1);
+        j.pg_n = chain_off[b + 1] - chain_off[b];
+        stage_block(j, m->tt_zero, j.pg_n ? m->tt_zero_bytes : 0);
+        j.tt_old = m->tt_old;
+        j.pg_kfid = (const int *)JT.tail_dev + chain_off[b];
+        j.pg_Twc = (const double *)(JT.tail_dev + ids_bytes) + 7 * (size_t)chain_off[b];
+        JT.set(b, j);
+        JT.host[b].pg_tmp = (double *)(JT.host[b].hdr_out + MH_N);
+        if (!j.pg_n) continue;
+        nmax = std::max(nmax, m->n_obs); lmax = std::max(lmax, m->max_lm); kmax = std::max(kmax, m->max_kf); zmax = std::max(zmax, j.zero_vec16);
+        m->last_valid = 0;   // its tables change under the last set-up: no update stage from it any more
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), gL((lmax + 255) / 256, B), gK((kmax + 255) / 256, B), b256(256);
+    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::min(64u, (zmax + 255) / 256), B), b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mp_anchor_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mp_landmarks_kernel, gL, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mp_poses_kernel, gK, b256, 0, st, JT.dev);
+    if (!out) return OV2_OK;   // fully asynchronous
+    OV2_LAUNCH(c, OV2_K_MAP, mb_hdr_gather_kernel, dim3(1, B), dim3(64), 0, st, JT.dev);
+    if ((s = JT.fetch_headers()) != OV2_OK) return s;
+    for (int b = 0; b < B; ++b) {
+        if (chain_off[b + 1] == chain_off[b]) continue;
+        const int *H = JT.hdr_host + (size_t)b * JT.stride;
+        out[b].n_kf_chain = H[PH_KF_CHAIN]; out[b].n_kf_younger = H[PH_KF_YOUNGER]; out[b].n_lm_moved = H[PH_LM_MOVED];
+        memcpy(out[b].T_corr, (const double *)(H + MH_N) + 7, 7 * sizeof(double));
     }
     return OV2_OK;
 }

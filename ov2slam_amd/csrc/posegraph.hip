@@ -14,7 +14,8 @@
 // hundred dependent 6 x 6 operations) are strided over the threads; sums over edges close with a fixed-order tree; the
 // trust-region bookkeeping is done by thread 0 in LDS.  A loop closure of 200 keyframes is 10 x ~0.5 ms of mostly
 // serial latency -- this is glue on the loop closer's path, not a throughput kernel; it exists so that the solver's
-// results do not depend on a host Ceres.
+// results do not depend on a host Ceres.  ov2_pose_graph_solve_batch gives every graph of a batch such a workgroup in one
+// launch (blockIdx.x = graph, its descriptor read from a table): the latency is paid once for B loops, not B times.
 #include <algorithm>
 #include <vector>
 
@@ -422,11 +423,14 @@ __device__ inline void pg_logit(ov2_pg_result *R, double cost, double change, do
 }
 
 // the whole minimisation (trust_region_minimizer.cc as restated in oracle/ov2_oracle_pg.c); every thread carries the
-// scalar state redundantly (all sums are broadcast), so the control flow is uniform
-__global__ __launch_bounds__(256) void pg_minimize_kernel(pg_dev d, pg_opt o)
+// scalar state redundantly (all sums are broadcast), so the control flow is uniform.  One workgroup per graph of the
+// batch (blockIdx.x): its descriptor names its own inputs, workspace and result record, nothing is shared between
+// workgroups, so a graph's arithmetic does not depend on the batch around it.
+__global__ __launch_bounds__(256) void pg_minimize_kernel(const pg_dev *__restrict__ dv, pg_opt o)
 {
     __shared__ double sh[256];
     __shared__ int flag;
+    const pg_dev d = dv[blockIdx.x];
     ov2_pg_result *R = d.res;
     if (threadIdx.x == 0) { R->n_log = 0; R->termination = OV2_BA_TERM_MAX_ITER; }
     const int m = 6 * d.nf;
@@ -536,97 +540,167 @@ __global__ __launch_bounds__(256) void pg_minimize_kernel(pg_dev d, pg_opt o)
     if (threadIdx.x == 0) { R->final_cost = minimum_cost; R->termination = term; }
 }
 
+// what the host derives from one graph before anything is enqueued: free-pose numbering, incidence lists, runs
+struct pg_plan {
+    int n = 0, E = 0, nf = 0, n_seg = 0;
+    std::vector<int> fidx, pose_of_f, inc_ptr, inc_flat, seg0, seg1;
+    // byte offsets inside the staging block
+    size_t o_ei, o_ej, o_fi, o_pf, o_ip, o_in, o_s0, o_s1, o_T, o_x, o_res;
+    size_t o_cand, o_best, o_r, o_Ji, o_Jj, o_D, o_O, o_Ld, o_Lo, o_v, o_part;
+};
+
+// validates graph P and fills its plan; `who` opens the error text (the batch call names the graph there).
+// nf == 0 or E == 0 on return: the graph is skipped.
+ov2_status pg_plan_build(ov2_ctx *c, const char *who, const ov2_pg_problem *P, pg_plan &pl)
+{
+    const int n = P->n_pose, E = P->n_edge;
+    if (n < 0 || E < 0 || (n && (!P->pose || !P->pose_const)) || (E && (!P->edge_i || !P->edge_j || !P->T_ij)))
+        return ov2_set_err(c, OV2_ERR_INVALID, "%snull / negative field", who);
+    pl.n = n; pl.E = E;
+    pl.fidx.assign((size_t)n, -1);
+    for (int i = 0; i < n; ++i) {
+        pl.fidx[i] = P->pose_const[i] ? -1 : (int)pl.pose_of_f.size();
+        if (!P->pose_const[i]) pl.pose_of_f.push_back(i);
+    }
+    const int nf = pl.nf = (int)pl.pose_of_f.size();
+    if (nf == 0 || E == 0) return OV2_OK;
+    // chain structure, incidence lists, runs of coupled free poses
+    std::vector<std::vector<int>> inc((size_t)nf);
+    std::vector<char> couple((size_t)nf, 0);
+    for (int e = 0; e < E; ++e) {
+        const int i = P->edge_i[e], j = P->edge_j[e];
+        if (i < 0 || i >= n || j < 0 || j >= n || i == j) return ov2_set_err(c, OV2_ERR_INVALID, "%sedge %d joins poses %d and %d", who, e, i, j);
+        const int fi = pl.fidx[i], fj = pl.fidx[j];
+        if (fi >= 0) inc[fi].push_back(2 * e);
+        if (fj >= 0) inc[fj].push_back(2 * e + 1);
+        if (fi >= 0 && fj >= 0) {
+            if (std::abs(fi - fj) != 1)
+                return ov2_set_err(c, OV2_ERR_UNSUPPORTED, "%sedge %d joins free poses %d and %d that are not neighbours: only chains "
+                                   "(localPoseGraph / fullPoseGraph) are solved", who, e, i, j);
+            couple[std::min(fi, fj)] = 1;
+        }
+    }
+    pl.inc_ptr.assign((size_t)nf + 1, 0);
+    for (int f = 0; f < nf; ++f) { pl.inc_ptr[f + 1] = pl.inc_ptr[f] + (int)inc[f].size(); pl.inc_flat.insert(pl.inc_flat.end(), inc[f].begin(), inc[f].end()); }
+    for (int f = 0; f < nf;) {
+        int g = f;
+        while (g + 1 < nf && couple[g]) ++g;
+        pl.seg0.push_back(f); pl.seg1.push_back(g);
+        f = g + 1;
+    }
+    pl.n_seg = (int)pl.seg0.size();
+    return OV2_OK;
+}
+
+// B graphs, one launch: `who` as above (nullptr: the batch form, which names the graph itself)
+ov2_status pg_solve_graphs(ov2_ctx *c, const char *who, int B, const ov2_pg_problem *P, const ov2_ba_options *o, ov2_pg_result *R)
+{
+    memset(R, 0, sizeof(*R) * (size_t)B);
+    std::vector<pg_plan> plans((size_t)B);
+    std::vector<int> act;          // graphs that take a workgroup, in batch order
+    for (int b = 0; b < B; ++b) {
+        char name[64];
+        if (!who) snprintf(name, sizeof(name), "ov2_pose_graph_solve_batch: graph %d: ", b);
+        const ov2_status s = pg_plan_build(c, who ? who : name, P + b, plans[b]);
+        if (s != OV2_OK) return s;
+        if (plans[b].nf == 0 || plans[b].E == 0) R[b].termination = OV2_BA_TERM_SKIPPED;
+        else act.push_back(b);
+    }
+    const int na = (int)act.size();
+    if (na == 0) return OV2_OK;
+    OV2_HIP(c, hipSetDevice(c->device));
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    // staging block: [descriptors | inputs of every graph | poses of every graph | results] mirrored on the device,
+    // followed by the device-only workspaces
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o_ = off; off += up(bytes); return o_; };
+    const size_t o_dev = carve(sizeof(pg_dev) * (size_t)na);
+    for (int b : act) {
+        pg_plan &q = plans[b];
+        const size_t E = (size_t)q.E, n = (size_t)q.n, nf = (size_t)q.nf, ns = (size_t)q.n_seg;
+        q.o_ei = carve(sizeof(int) * E); q.o_ej = carve(sizeof(int) * E); q.o_fi = carve(sizeof(int) * n); q.o_pf = carve(sizeof(int) * nf);
+        q.o_ip = carve(sizeof(int) * (nf + 1)); q.o_in = carve(sizeof(int) * (q.inc_flat.size() + 1));
+        q.o_s0 = carve(sizeof(int) * ns); q.o_s1 = carve(sizeof(int) * ns); q.o_T = carve(sizeof(double) * 7 * E);
+    }
+    const size_t x_begin = off;
+    for (int b : act) plans[b].o_x = carve(sizeof(double) * 7 * (size_t)plans[b].n);
+    const size_t in_end = off;
+    for (int b : act) plans[b].o_res = carve(sizeof(ov2_pg_result));
+    const size_t io_end = off;
+    for (int b : act) {
+        pg_plan &q = plans[b];
+        const size_t E = (size_t)q.E, n = (size_t)q.n, nf = (size_t)q.nf;
+        q.o_cand = carve(sizeof(double) * 7 * n); q.o_best = carve(sizeof(double) * 7 * n);
+        q.o_r = carve(sizeof(double) * 6 * E); q.o_Ji = carve(sizeof(double) * 36 * E); q.o_Jj = carve(sizeof(double) * 36 * E);
+        q.o_D = carve(sizeof(double) * 36 * nf); q.o_O = carve(sizeof(double) * 36 * nf); q.o_Ld = carve(sizeof(double) * 36 * nf);
+        q.o_Lo = carve(sizeof(double) * 36 * nf); q.o_v = carve(sizeof(double) * 6 * nf * 8); q.o_part = carve(sizeof(double) * 256);
+    }
+    char *hp = nullptr, *dp = nullptr;
+    ov2_status s = ov2_staging(c, off, (void **)&hp, (void **)&dp);
+    if (s != OV2_OK) return s;
+    pg_dev *hd = (pg_dev *)(hp + o_dev);
+    for (int a = 0; a < na; ++a) {
+        const ov2_pg_problem *G = P + act[a];
+        const pg_plan &q = plans[act[a]];
+        const int E = q.E, n = q.n, nf = q.nf, n_seg = q.n_seg;
+        memcpy(hp + q.o_ei, G->edge_i, sizeof(int) * E); memcpy(hp + q.o_ej, G->edge_j, sizeof(int) * E);
+        memcpy(hp + q.o_fi, q.fidx.data(), sizeof(int) * n); memcpy(hp + q.o_pf, q.pose_of_f.data(), sizeof(int) * nf);
+        memcpy(hp + q.o_ip, q.inc_ptr.data(), sizeof(int) * (nf + 1));
+        if (!q.inc_flat.empty()) memcpy(hp + q.o_in, q.inc_flat.data(), sizeof(int) * q.inc_flat.size());
+        memcpy(hp + q.o_s0, q.seg0.data(), sizeof(int) * n_seg); memcpy(hp + q.o_s1, q.seg1.data(), sizeof(int) * n_seg);
+        memcpy(hp + q.o_T, G->T_ij, sizeof(double) * 7 * E);
+        memcpy(hp + q.o_x, G->pose, sizeof(double) * 7 * n);
+        pg_dev d;
+        d.n_pose = n; d.n_edge = E; d.nf = nf; d.n_seg = n_seg;
+        d.edge_i = (const int *)(dp + q.o_ei); d.edge_j = (const int *)(dp + q.o_ej); d.fidx = (const int *)(dp + q.o_fi);
+        d.pose_of_f = (const int *)(dp + q.o_pf); d.inc_ptr = (const int *)(dp + q.o_ip); d.inc = (const int *)(dp + q.o_in);
+        d.seg0 = (const int *)(dp + q.o_s0); d.seg1 = (const int *)(dp + q.o_s1); d.T_ij = (const double *)(dp + q.o_T);
+        d.x = (double *)(dp + q.o_x); d.cand = (double *)(dp + q.o_cand); d.best = (double *)(dp + q.o_best);
+        d.r = (double *)(dp + q.o_r); d.Ji = (double *)(dp + q.o_Ji); d.Jj = (double *)(dp + q.o_Jj);
+        d.D = (double *)(dp + q.o_D); d.O = (double *)(dp + q.o_O); d.Ld = (double *)(dp + q.o_Ld); d.Lo = (double *)(dp + q.o_Lo);
+        double *v = (double *)(dp + q.o_v);
+        const size_t m = 6 * (size_t)nf;
+        d.g = v; d.sqn = v + m; d.scale = v + 2 * m; d.diag = v + 3 * m; d.lmd = v + 4 * m; d.step = v + 5 * m; d.y = v + 6 * m;
+        d.part = (double *)(dp + q.o_part);
+        d.res = (ov2_pg_result *)(dp + q.o_res);
+        hd[a] = d;
+    }
+    // the result records go up zeroed: the kernel writes n_log entries of the log, the rest comes back as zeros
+    memset(hp + in_end, 0, io_end - in_end);
+    hipStream_t st = c->stream;
+    OV2_HIP(c, hipMemcpyAsync(dp, hp, io_end, hipMemcpyHostToDevice, st));
+    pg_opt po;
+    po.max_iters = o->max_iters; po.jacobi = o->jacobi_scaling; po.max_invalid = o->max_consecutive_invalid_steps;
+    po.ftol = o->function_tolerance; po.initial_radius = o->initial_radius; po.max_radius = o->max_radius; po.min_radius = o->min_radius;
+    po.min_d = o->min_lm_diagonal; po.max_d = o->max_lm_diagonal; po.min_rel = o->min_relative_decrease;
+    po.ptol = o->parameter_tolerance; po.gtol = o->gradient_tolerance;
+    OV2_LAUNCH(c, OV2_K_MAP + 6, pg_minimize_kernel, dim3(na), dim3(256), 0, st, (const pg_dev *)(dp + o_dev), po);
+    OV2_HIP(c, hipGetLastError());
+    OV2_HIP(c, hipMemcpyAsync(hp + x_begin, dp + x_begin, io_end - x_begin, hipMemcpyDeviceToHost, st));
+    OV2_HIP(c, hipStreamSynchronize(st));
+    for (int b : act) {
+        memcpy(P[b].pose, hp + plans[b].o_x, sizeof(double) * 7 * (size_t)plans[b].n);
+        memcpy(R + b, hp + plans[b].o_res, sizeof(*R));
+    }
+    return OV2_OK;
+}
+
 }  // namespace
 
 extern "C" ov2_status ov2_pose_graph_solve(ov2_ctx *c, const ov2_pg_problem *P, const ov2_ba_options *o, ov2_pg_result *R)
 {
     if (!c) return OV2_ERR_INVALID;
     if (!P || !o || !R) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_pose_graph_solve: null argument");
-    memset(R, 0, sizeof(*R));
-    const int n = P->n_pose, E = P->n_edge;
-    if (n < 0 || E < 0 || (n && (!P->pose || !P->pose_const)) || (E && (!P->edge_i || !P->edge_j || !P->T_ij)))
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_pose_graph_solve: null / negative field");
-    std::vector<int> fidx((size_t)n), pose_of_f;
-    for (int i = 0; i < n; ++i) {
-        fidx[i] = P->pose_const[i] ? -1 : (int)pose_of_f.size();
-        if (!P->pose_const[i]) pose_of_f.push_back(i);
-    }
-    const int nf = (int)pose_of_f.size();
-    if (nf == 0 || E == 0) { R->termination = OV2_BA_TERM_SKIPPED; return OV2_OK; }
-    // chain structure, incidence lists, runs of coupled free poses
-    std::vector<std::vector<int>> inc((size_t)nf);
-    std::vector<char> couple((size_t)nf, 0);
-    for (int e = 0; e < E; ++e) {
-        const int i = P->edge_i[e], j = P->edge_j[e];
-        if (i < 0 || i >= n || j < 0 || j >= n || i == j) return ov2_set_err(c, OV2_ERR_INVALID, "edge %d joins poses %d and %d", e, i, j);
-        const int fi = fidx[i], fj = fidx[j];
-        if (fi >= 0) inc[fi].push_back(2 * e);
-        if (fj >= 0) inc[fj].push_back(2 * e + 1);
-        if (fi >= 0 && fj >= 0) {
-            if (std::abs(fi - fj) != 1)
-                return ov2_set_err(c, OV2_ERR_UNSUPPORTED, "edge %d joins free poses %d and %d that are not neighbours: only chains "
-                                   "(localPoseGraph / fullPoseGraph) are solved", e, i, j);
-            couple[std::min(fi, fj)] = 1;
-        }
-    }
-    std::vector<int> inc_ptr((size_t)nf + 1, 0), inc_flat, seg0, seg1;
-    for (int f = 0; f < nf; ++f) { inc_ptr[f + 1] = inc_ptr[f] + (int)inc[f].size(); inc_flat.insert(inc_flat.end(), inc[f].begin(), inc[f].end()); }
-    for (int f = 0; f < nf;) {
-        int g = f;
-        while (g + 1 < nf && couple[g]) ++g;
-        seg0.push_back(f); seg1.push_back(g);
-        f = g + 1;
-    }
-    const int n_seg = (int)seg0.size();
-    OV2_HIP(c, hipSetDevice(c->device));
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    // staging block: [inputs | poses || result] mirrored on the device, followed by the device-only workspace
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o_ = off; off += up(bytes); return o_; };
-    const size_t o_ei = carve(sizeof(int) * E), o_ej = carve(sizeof(int) * E), o_fi = carve(sizeof(int) * n), o_pf = carve(sizeof(int) * nf);
-    const size_t o_ip = carve(sizeof(int) * (nf + 1)), o_in = carve(sizeof(int) * (inc_flat.size() + 1));
-    const size_t o_s0 = carve(sizeof(int) * n_seg), o_s1 = carve(sizeof(int) * n_seg), o_T = carve(sizeof(double) * 7 * E);
-    const size_t o_x = carve(sizeof(double) * 7 * n), in_end = off;
-    const size_t o_res = carve(sizeof(ov2_pg_result)), io_end = off;
-    const size_t o_cand = carve(sizeof(double) * 7 * n), o_best = carve(sizeof(double) * 7 * n);
-    const size_t o_r = carve(sizeof(double) * 6 * E), o_Ji = carve(sizeof(double) * 36 * E), o_Jj = carve(sizeof(double) * 36 * E);
-    const size_t o_D = carve(sizeof(double) * 36 * nf), o_O = carve(sizeof(double) * 36 * nf), o_Ld = carve(sizeof(double) * 36 * nf);
-    const size_t o_Lo = carve(sizeof(double) * 36 * nf), o_v = carve(sizeof(double) * 6 * nf * 8), o_part = carve(sizeof(double) * 256);
-    char *hp = nullptr, *dp = nullptr;
-    ov2_status s = ov2_staging(c, off, (void **)&hp, (void **)&dp);
-    if (s != OV2_OK) return s;
-    memcpy(hp + o_ei, P->edge_i, sizeof(int) * E); memcpy(hp + o_ej, P->edge_j, sizeof(int) * E);
-    memcpy(hp + o_fi, fidx.data(), sizeof(int) * n); memcpy(hp + o_pf, pose_of_f.data(), sizeof(int) * nf);
-    memcpy(hp + o_ip, inc_ptr.data(), sizeof(int) * (nf + 1));
-    if (!inc_flat.empty()) memcpy(hp + o_in, inc_flat.data(), sizeof(int) * inc_flat.size());
-    memcpy(hp + o_s0, seg0.data(), sizeof(int) * n_seg); memcpy(hp + o_s1, seg1.data(), sizeof(int) * n_seg);
-    memcpy(hp + o_T, P->T_ij, sizeof(double) * 7 * E);
-    memcpy(hp + o_x, P->pose, sizeof(double) * 7 * n);
-    hipStream_t st = c->stream;
-    OV2_HIP(c, hipMemcpyAsync(dp, hp, in_end, hipMemcpyHostToDevice, st));
-    pg_dev d;
-    d.n_pose = n; d.n_edge = E; d.nf = nf; d.n_seg = n_seg;
-    d.edge_i = (const int *)(dp + o_ei); d.edge_j = (const int *)(dp + o_ej); d.fidx = (const int *)(dp + o_fi);
-    d.pose_of_f = (const int *)(dp + o_pf); d.inc_ptr = (const int *)(dp + o_ip); d.inc = (const int *)(dp + o_in);
-    d.seg0 = (const int *)(dp + o_s0); d.seg1 = (const int *)(dp + o_s1); d.T_ij = (const double *)(dp + o_T);
-    d.x = (double *)(dp + o_x); d.cand = (double *)(dp + o_cand); d.best = (double *)(dp + o_best);
-    d.r = (double *)(dp + o_r); d.Ji = (double *)(dp + o_Ji); d.Jj = (double *)(dp + o_Jj);
-    d.D = (double *)(dp + o_D); d.O = (double *)(dp + o_O); d.Ld = (double *)(dp + o_Ld); d.Lo = (double *)(dp + o_Lo);
-    double *v = (double *)(dp + o_v);
-    const size_t m = 6 * (size_t)nf;
-    d.g = v; d.sqn = v + m; d.scale = v + 2 * m; d.diag = v + 3 * m; d.lmd = v + 4 * m; d.step = v + 5 * m; d.y = v + 6 * m;
-    d.part = (double *)(dp + o_part);
-    d.res = (ov2_pg_result *)(dp + o_res);
-    pg_opt po;
-    po.max_iters = o->max_iters; po.jacobi = o->jacobi_scaling; po.max_invalid = o->max_consecutive_invalid_steps;
-    po.ftol = o->function_tolerance; po.initial_radius = o->initial_radius; po.max_radius = o->max_radius; po.min_radius = o->min_radius;
-    po.min_d = o->min_lm_diagonal; po.max_d = o->max_lm_diagonal; po.min_rel = o->min_relative_decrease;
-    po.ptol = o->parameter_tolerance; po.gtol = o->gradient_tolerance;
-    OV2_LAUNCH(c, OV2_K_MAP + 6, pg_minimize_kernel, dim3(1), dim3(256), 0, st, d, po);
-    OV2_HIP(c, hipGetLastError());
-    OV2_HIP(c, hipMemcpyAsync(hp + o_x, dp + o_x, io_end - o_x, hipMemcpyDeviceToHost, st));
-    OV2_HIP(c, hipStreamSynchronize(st));
-    memcpy(P->pose, hp + o_x, sizeof(double) * 7 * n);
-    memcpy(R, hp + o_res, sizeof(*R));
-    return OV2_OK;
+    return pg_solve_graphs(c, "ov2_pose_graph_solve: ", 1, P, o, R);     // the B = 1 case of the batch
 }
+
+extern "C" ov2_status ov2_pose_graph_solve_batch(ov2_ctx *c, int B, const ov2_pg_problem *P, const ov2_ba_options *o, ov2_pg_result *R)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B < 0 || B > OV2_PG_MAX_BATCH)
+        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_pose_graph_solve_batch: B %d outside [0, %d]", B, OV2_PG_MAX_BATCH);
+    if (B == 0) return OV2_OK;
+    if (!P || !o || !R) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_pose_graph_solve_batch: null argument");
+    return pg_solve_graphs(c, nullptr, B, P, o, R);
+}
+

@@ -36,6 +36,11 @@ class FilterC(C.Structure):
                 ("removed_kfid", C.c_void_p), ("unset3d_lmid", C.c_void_p)]
 
 
+class PgUpdateC(C.Structure):
+    """ov2_map_pg_update"""
+    _fields_ = [("n_kf_chain", C.c_int32), ("n_kf_younger", C.c_int32), ("n_lm_moved", C.c_int32), ("T_corr", C.c_double * 7)]
+
+
 class UpdateC(C.Structure):
     """ov2_local_ba_update"""
     _fields_ = [("n_removed_lm", C.c_int32), ("n_removed_obs", C.c_int32), ("n_stereo_off", C.c_int32),
@@ -162,6 +167,10 @@ class DeviceMap:
     def filter_keyframes_batch(self, others=(), newkf=None, nmin_covscore=25, ratio=0.9):
         """ov2_map_filter_keyframes_batch on this map and `others` in one call; see filter_keyframes_batch"""
         return filter_keyframes_batch(self.ctx, [self] + list(others), newkf, nmin_covscore, ratio)
+
+    def pose_graph_update_batch(self, others=(), newkf=None, chain_kfid=(), chain_Twc=(), want_header=True):
+        """ov2_map_pose_graph_update_batch on this map and `others` in one call; see pose_graph_update_batch"""
+        return pose_graph_update_batch(self.ctx, [self] + list(others), newkf, chain_kfid, chain_Twc, want_header)
 
     def close(self):
         if getattr(self, "h", None):
@@ -297,6 +306,29 @@ def filter_keyframes_batch(ctx, maps, newkf=None, nmin_covscore=25, ratio=0.9):
             _check(ctx.h, ctx.lib.ov2_memcpy_d2h(ctx.h, un.ctypes.data_as(C.c_void_p), f.unset3d_lmid, un.nbytes))
         res.append(dict(candidates=f.n_candidates, few3d=f.n_few3d, removed=rm.tolist(), unset3d=np.sort(un).tolist()))
     return res
+
+
+def pose_graph_update_batch(ctx, maps, newkf=None, chain_kfid=(), chain_Twc=(), want_header=True):
+    """the update stage of Optimizer::localPoseGraph on the tables of the maps (DeviceMap objects or raw ov2_map handles):
+    chain_kfid[b] / chain_Twc[b] list the free keyframes of map b's graph (ascending, last = newkf[b]; default: each map's
+    newkf) with their optimised poses (n x 7); an empty list leaves the map alone.  Returns per map dict(n_kf_chain,
+    n_kf_younger, n_lm_moved, T_corr) -- or None (want_header=False: fully asynchronous)"""
+    B = len(maps)
+    hs = (C.c_void_p * B)(*[getattr(m, "h", m) for m in maps])
+    nk = np.ascontiguousarray([m.newkf for m in maps] if newkf is None else newkf, np.int32)
+    ids = [np.ascontiguousarray(k, np.int32).reshape(-1) for k in chain_kfid]
+    Ts = [np.ascontiguousarray(t, np.float64).reshape(-1, 7) for t in chain_Twc]
+    assert len(ids) == len(Ts) == B and all(len(k) == len(t) for k, t in zip(ids, Ts))
+    off = np.concatenate([[0], np.cumsum([len(k) for k in ids])]).astype(np.int32)
+    kid = np.ascontiguousarray(np.concatenate(ids + [np.zeros(0, np.int32)]), np.int32)
+    Twc = np.ascontiguousarray(np.concatenate(Ts + [np.zeros((0, 7))]), np.float64)
+    out = (PgUpdateC * B)() if want_header else None
+    _check(ctx.h, ctx.lib.ov2_map_pose_graph_update_batch(ctx.h, B, hs, nk.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p),
+                                                          kid.ctypes.data_as(C.c_void_p), Twc.ctypes.data_as(C.c_void_p), out))
+    if not want_header:
+        return None
+    return [dict(n_kf_chain=u.n_kf_chain, n_kf_younger=u.n_kf_younger, n_lm_moved=u.n_lm_moved, T_corr=np.array(u.T_corr[:]))
+            for u in out]
 
 
 def restore_state_batch(ctx, maps):

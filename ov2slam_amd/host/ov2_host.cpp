@@ -1712,27 +1712,26 @@ ov2_status Optimizer::looseBA(int inikfid, const int nkfid, const bool buse_robu
 }
 
 // ---- pose graphs ------------------------------------------------------------------------------------------------
-bool Optimizer::localPoseGraph(Frame &newframe, int kfloop_id, const SE3 &newTwc, ov2_status *status)
+// the three stages of Optimizer::localPoseGraph (src/optimizer.cpp:2346-2592), split so that a batch of loop closures can
+// share one solve (LoopCloser::closeLoops, ov2_slam.cpp) and a test can drive the update alone
+bool Optimizer::assembleLocalPoseGraph(Frame &newframe, int kfloop_id, const SE3 &newTwc, LocalPoseGraph &g)
 {
-    if (status) *status = OV2_OK;
-    const SE3 iniTcw = newframe.getTcw();
+    g = LocalPoseGraph();
+    g.iniTcw = newframe.getTcw();
+    g.newTwc = newTwc;
+    g.newkfid = newframe.kfid_;
     int nkfid_max = -1;
     for (const auto &kv : pmap_->map_pkfs_) nkfid_max = std::max(nkfid_max, kv.first);
     auto ploopkf = pmap_->getKeyframe(kfloop_id);
     while (!ploopkf && kfloop_id < nkfid_max) ploopkf = pmap_->getKeyframe(++kfloop_id);   // :2368-2371
     if (!ploopkf) return false;
-    std::vector<double> pose, Tij;
-    std::vector<uint8_t> cst;
-    std::vector<int32_t> ei, ej;
-    std::vector<int> kfids;
-    std::map<int, std::shared_ptr<Frame>> map_pkfs;
     auto push_pose = [&](int kfid, const SE3 &T, bool c) {
-        kfids.push_back(kfid);
-        pose.insert(pose.end(), T.v.begin(), T.v.end());
-        cst.push_back(c ? 1 : 0);
-        return (int)kfids.size() - 1;
+        g.kfids.push_back(kfid);
+        g.pose.insert(g.pose.end(), T.v.begin(), T.v.end());
+        g.cst.push_back(c ? 1 : 0);
+        return (int)g.kfids.size() - 1;
     };
-    auto push_edge = [&](int a, int b, const SE3 &T) { ei.push_back(a); ej.push_back(b); Tij.insert(Tij.end(), T.v.begin(), T.v.end()); };
+    auto push_edge = [&](int a, int b, const SE3 &T) { g.ei.push_back(a); g.ej.push_back(b); g.Tij.insert(g.Tij.end(), T.v.begin(), T.v.end()); };
     push_pose(kfloop_id, ploopkf->getTwc(), true);
     SE3 Tciw = ploopkf->getTcw();
     int ci = 0;
@@ -1740,25 +1739,40 @@ bool Optimizer::localPoseGraph(Frame &newframe, int kfloop_id, const SE3 &newTwc
     for (int kfid = kfloop_id + 1; kfid <= newframe.kfid_; ++kfid) {   // :2389-2420
         auto pkf = pmap_->getKeyframe(kfid);
         if (!pkf) { if (kfid == newframe.kfid_) return false; continue; }
-        map_pkfs.emplace(kfid, pkf);
         const SE3 Twcj = pkf->getTwc();
         const int j = push_pose(kfid, Twcj, false);
         push_edge(ci, j, Tciw * Twcj);
         Tciw = Twcj.inverse();
         ci = j;
     }
-    if (kfids.size() < 2 || kfids.back() != newframe.kfid_) return false;
-    push_edge(0, (int)kfids.size() - 1, Tloop_new);              // :2422-2425
+    if (g.kfids.size() < 2 || g.kfids.back() != newframe.kfid_) return false;
+    push_edge(0, (int)g.kfids.size() - 1, Tloop_new);            // :2422-2425
+    return true;
+}
+
+ov2_pg_problem LocalPoseGraph::view()
+{
     ov2_pg_problem P;
     P.n_pose = (int)kfids.size(); P.pose = pose.data(); P.pose_const = cst.data();
     P.n_edge = (int)ei.size(); P.edge_i = ei.data(); P.edge_j = ej.data(); P.T_ij = Tij.data();
+    return P;
+}
+
+ov2_ba_options Optimizer::localPoseGraphOptions() const
+{
     ov2_ba_options o;
     ov2_ba_default_options(&o, pslamstate_->robust_mono_th_);
     o.max_iters = 10; o.function_tolerance = 1e-4;               // :2445-2446
-    const ov2_status s = ov2_pose_graph_solve(ctx_, &P, &o, &last_pg_);
-    if (status) *status = s;
-    if (s != OV2_OK) return false;
-    auto pose_of = [&](int idx) { SE3 T; for (int k = 0; k < 7; ++k) T.v[k] = pose[7 * (size_t)idx + k]; return T; };
+    return o;
+}
+
+bool Optimizer::applyLocalPoseGraph(LocalPoseGraph &g)
+{
+    const std::vector<int> &kfids = g.kfids;
+    const SE3 &iniTcw = g.iniTcw, &newTwc = g.newTwc;
+    int nkfid_max = -1;
+    for (const auto &kv : pmap_->map_pkfs_) nkfid_max = std::max(nkfid_max, kv.first);
+    auto pose_of = [&](int idx) { SE3 T; for (int k = 0; k < 7; ++k) T.v[k] = g.pose[7 * (size_t)idx + k]; return T; };
     const SE3 newoptTwc = pose_of((int)kfids.size() - 1);
     {
         const double dx = newTwc.v[0] - newoptTwc.v[0], dy = newTwc.v[1] - newoptTwc.v[1], dz = newTwc.v[2] - newoptTwc.v[2];
@@ -1770,7 +1784,8 @@ bool Optimizer::localPoseGraph(Frame &newframe, int kfloop_id, const SE3 &newTwc
     std::vector<std::pair<int, SE3>> vkf;
     for (size_t i = 1; i < kfids.size(); ++i) {
         const int kfid = kfids[i];
-        auto pkf = map_pkfs.at(kfid);
+        auto pkf = pmap_->getKeyframe(kfid);
+        if (!pkf) continue;
         const SE3 T = pose_of((int)i);
         vkf.emplace_back(kfid, T);
         for (const auto &kp : pkf->getKeypoints3d()) {
@@ -1785,7 +1800,7 @@ bool Optimizer::localPoseGraph(Frame &newframe, int kfloop_id, const SE3 &newTwc
         }
     }
     // the correction of the new keyframe carried to the younger keyframes and their landmarks (:2527-2560)
-    for (int kfid = newframe.kfid_ + 1; kfid <= nkfid_max; ++kfid) {
+    for (int kfid = g.newkfid + 1; kfid <= nkfid_max; ++kfid) {
         auto pkf = pmap_->getKeyframe(kfid);
         if (!pkf) continue;
         const SE3 updTwkf = newoptTwc * (iniTcw * pkf->getTwc());
@@ -1812,6 +1827,19 @@ bool Optimizer::localPoseGraph(Frame &newframe, int kfloop_id, const SE3 &newTwc
         pc->setTwc(newoptTwc * (iniTcw * pc->getTwc()));
     }
     return true;
+}
+
+bool Optimizer::localPoseGraph(Frame &newframe, int kfloop_id, const SE3 &newTwc, ov2_status *status)
+{
+    if (status) *status = OV2_OK;
+    LocalPoseGraph g;
+    if (!assembleLocalPoseGraph(newframe, kfloop_id, newTwc, g)) return false;
+    ov2_pg_problem P = g.view();
+    const ov2_ba_options o = localPoseGraphOptions();
+    const ov2_status s = ov2_pose_graph_solve(ctx_, &P, &o, &last_pg_);
+    if (status) *status = s;
+    if (s != OV2_OK) return false;
+    return applyLocalPoseGraph(g);
 }
 
 bool Optimizer::fullPoseGraph(std::vector<SE3> &vTwc, const std::vector<SE3> &vTpc, const std::vector<bool> &viskf, ov2_status *status)

@@ -398,6 +398,18 @@ struct LocalBAProblem {
     ov2_ba_problem view(const SlamParams &st, const Frame &newframe);
 };
 
+// the chain graph of Optimizer::localPoseGraph between its stages: pose 0 = the constant loop keyframe, then the free
+// keyframes in ascending kfid (last = the new keyframe); `pose` is solved in place
+struct LocalPoseGraph {
+    std::vector<double> pose, Tij;
+    std::vector<uint8_t> cst;
+    std::vector<int32_t> ei, ej;
+    std::vector<int> kfids;
+    SE3 iniTcw, newTwc;              // Tcw of the new keyframe at assembly, the loop pose the graph was built for
+    int newkfid = -1;
+    ov2_pg_problem view();           // over the vectors above
+};
+
 class Optimizer {   // include/optimizer.hpp:42, src/optimizer.cpp:34-897
 public:
     Optimizer(ov2_ctx *ctx, std::shared_ptr<SlamParams> pstate, std::shared_ptr<MapManager> pmap)
@@ -417,6 +429,12 @@ public:
     // ov2_pose_graph_solve (10 iterations, 1e-4); rejected when the optimised new pose lands > 0.3 m from newTwc (stereo);
     // then keyframes, the landmarks they anchor, the younger keyframes and the current frame are moved
     bool localPoseGraph(Frame &newframe, int kfloop_id, const SE3 &newTwc, ov2_status *status = nullptr);
+    // its three stages (localPoseGraph is these in sequence): the graph (:2361-2425; false: no loop keyframe / no chain),
+    // the options of the solve (:2442-2446), and -- on the solved g.pose -- the degenerate test (:2467-2474; false:
+    // rejected, nothing moved) with the update of keyframes, anchored landmarks, younger keyframes and current frame (:2476-2585)
+    bool assembleLocalPoseGraph(Frame &newframe, int kfloop_id, const SE3 &newTwc, LocalPoseGraph &g);
+    ov2_ba_options localPoseGraphOptions() const;
+    bool applyLocalPoseGraph(LocalPoseGraph &g);
     // :2783-2870 (SlamManager::writeFullTrajectoryLC, src/ov2slam.cpp:702): every frame a pose (keyframes constant),
     // consecutive frames joined by vTpc; vTwc receives the optimised trajectory (the reference writes it to a file)
     bool fullPoseGraph(std::vector<SE3> &vTwc, const std::vector<SE3> &vTpc, const std::vector<bool> &viskf, ov2_status *status = nullptr);

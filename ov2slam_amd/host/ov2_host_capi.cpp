@@ -380,6 +380,73 @@ int ov2h_loop_verify_candidate(void *p, void *ctx, int newkf, int lckf, int n_in
     return pack_verify(r, ints, dbl, cap, lists, &used) ? 0 : (int)OV2_ERR_INVALID;
 }
 
+// one LoopCloseResult as flat rows: ints[9] = branch, inikfid, looseBA's start id, status of the pose-graph solve, of
+// structureOnlyBA, of looseBA (ov2::LCL_NOT_CALLED = 1 where the call was not made), merged lmids, termination and log
+// entries of the pose graph; dbl[3] = lc_pose_err, initial and final cost of the pose graph; merged: the lmids (room for cap)
+static bool pack_close(const LoopCloseResult &r, int *ints, double *dbl, int cap, int *merged)
+{
+    const int v[9] = {r.branch, r.inikfid, r.loose_start, r.pg_status, r.sba_status, r.loose_status, (int)r.vmergedlmids.size(),
+                      r.pg.termination, r.pg.n_log};
+    std::copy(v, v + 9, ints);
+    dbl[0] = r.lc_pose_err; dbl[1] = r.pg.initial_cost; dbl[2] = r.pg.final_cost;
+    if ((int)r.vmergedlmids.size() > cap) return false;
+    std::copy(r.vmergedlmids.begin(), r.vmergedlmids.end(), merged);
+    return true;
+}
+
+// LoopCloser::closeLoop on one accepted loop; stats[3] = last_close_ (jobs, graphs offered, solve calls).  0 or a negative ov2_status
+int ov2h_loop_close(void *p, void *ctx, int newkf, int lckf, const double *Twc7, int n, const int *pairs, int cap, int *ints, double *dbl,
+                    int *merged, int *stats)
+{
+    HostMap *m = (HostMap *)p;
+    if (n < 0) return (int)OV2_ERR_INVALID;
+    LoopCloser lc((ov2_ctx *)ctx, m->st, m->map);
+    std::vector<std::pair<int, int>> v((size_t)n);
+    for (int i = 0; i < n; ++i) v[i] = {pairs[2 * i], pairs[2 * i + 1]};
+    SE3 T;
+    for (int k = 0; k < 7; ++k) T.v[k] = Twc7[k];
+    LoopCloseResult r;
+    const ov2_status s = lc.closeLoop(newkf, lckf, T, v, r);
+    stats[0] = lc.last_close_.jobs; stats[1] = lc.last_close_.graphs; stats[2] = lc.last_close_.solve_calls;
+    if (s != OV2_OK) return (int)s;
+    return pack_close(r, ints, dbl, cap, merged) ? 0 : (int)OV2_ERR_INVALID;
+}
+
+// LoopCloser::closeLoops on B maps (one accepted loop each): rows of ov2h_loop_close per map (ints B x 9, dbl B x 3, merged
+// B x cap), n_pairs[b] pairs of map b one after the other in `pairs`
+int ov2h_loop_close_batch(int B, void *const *maps, void *ctx, const int *newkf, const int *lckf, const double *Twc7, const int *n_pairs,
+                          const int *pairs, int cap, int *ints, double *dbl, int *merged, int *stats)
+{
+    if (B < 0) return (int)OV2_ERR_INVALID;
+    std::vector<std::unique_ptr<LoopCloser>> closers;
+    std::vector<LoopCloseJob> jobs((size_t)B);
+    size_t o = 0;
+    for (int b = 0; b < B; ++b) {
+        HostMap *m = (HostMap *)maps[b];
+        if (!m || n_pairs[b] < 0) return (int)OV2_ERR_INVALID;
+        closers.emplace_back(new LoopCloser((ov2_ctx *)ctx, m->st, m->map));
+        LoopCloseJob &J = jobs[b];
+        J.closer = closers.back().get(); J.newkfid = newkf[b]; J.lckfid = lckf[b];
+        for (int k = 0; k < 7; ++k) J.Twc.v[k] = Twc7[7 * (size_t)b + k];
+        for (int i = 0; i < n_pairs[b]; ++i, ++o) J.vkplmids.push_back({pairs[2 * o], pairs[2 * o + 1]});
+    }
+    const ov2_status s = LoopCloser::closeLoops(jobs);
+    stats[0] = stats[1] = stats[2] = 0;
+    if (B) { const LoopCloseStats &L = closers[0]->last_close_; stats[0] = L.jobs; stats[1] = L.graphs; stats[2] = L.solve_calls; }
+    if (s != OV2_OK) return (int)s;
+    for (int b = 0; b < B; ++b)
+        if (!pack_close(jobs[b].r, ints + 9 * (size_t)b, dbl + 3 * (size_t)b, cap, merged + (size_t)cap * b)) return (int)OV2_ERR_INVALID;
+    return 0;
+}
+
+// MapManager::mergeMapPoints(prevlmid, newlmid), so that a test can walk the chain step by step
+int ov2h_map_merge_points(void *p, int prevlmid, int newlmid)
+{
+    HostMap *m = (HostMap *)p;
+    m->map->mergeMapPoints(prevlmid, newlmid);
+    return 0;
+}
+
 // LoopCloser::processLoopCandidates on B pairs: branch (B, ov2::LoopBranch of the 2D-2D half), n_passed (B: pairs it passed on),
 // then the rows of ov2h_loop_verify (a pair that did not pass keeps the row of an untouched LoopVerifyResult); stats[13]: the five
 // of ov2h_loop_match followed by the eight of ov2h_loop_verify
@@ -937,6 +1004,35 @@ int ov2h_local_pose_graph(void *p, void *ctx, int newkf, int kfloop_id, const do
     if (final_cost) *final_cost = opt.last_pg_.final_cost;
     if (n_log) *n_log = opt.last_pg_.n_log;
     return s != OV2_OK ? -2 : (ok ? 1 : 0);
+}
+
+// Optimizer::applyLocalPoseGraph alone (test hook): the n free keyframes kfids (ascending, last = newkf) take the poses
+// Twc7 as if a solve had produced them; the loop pose is taken equal to the new keyframe's pose, so the degenerate test
+// passes.  returns 1 applied, 0 rejected, -1 a keyframe is missing
+int ov2h_apply_local_pose_graph(void *p, int newkf, int n, const int *kfids, const double *Twc7)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(newkf);
+    if (!f || n < 1 || kfids[n - 1] != newkf) return -1;
+    LocalPoseGraph g;
+    g.iniTcw = f->getTcw();
+    g.newkfid = newkf;
+    g.kfids.push_back(-1);                      // the constant loop keyframe: the update never looks at it
+    g.pose.assign(7, 0.0);
+    for (int i = 0; i < n; ++i) {
+        if (!m->map->getKeyframe(kfids[i])) return -1;
+        g.kfids.push_back(kfids[i]);
+        g.pose.insert(g.pose.end(), Twc7 + 7 * (size_t)i, Twc7 + 7 * (size_t)i + 7);
+    }
+    for (int k = 0; k < 7; ++k) g.newTwc.v[k] = Twc7[7 * (size_t)(n - 1) + k];
+    // the test maps stand one of their keyframes in as the current frame (ov2h_map_finalize); a live current frame is an
+    // object of its own, so set the alias aside: it would be moved once as a keyframe and once more as the current frame
+    auto cur = m->map->pcurframe_;
+    if (cur && m->map->getKeyframe(cur->kfid_) == cur) m->map->pcurframe_ = nullptr;
+    Optimizer opt(nullptr, m->st, m->map);
+    const bool ok = opt.applyLocalPoseGraph(g);
+    m->map->pcurframe_ = cur;
+    return ok ? 1 : 0;
 }
 
 // Optimizer::fullPoseGraph(vTwc, vTpc, viskf) on flat arrays (n x 7, n x 7, n); vTwc is overwritten
@@ -1861,6 +1957,7 @@ int ov2h_loop_new_keyframe(void *h, int kfid, unsigned long long seed, int *out,
     LoopNewKeyframeResult r;
     lc->last_ = LoopStats();
     const ov2_status s = lc->newKeyframe(kfid, (uint64_t)seed, r);
+    lc->last_closed_ = r.closed;
     if (s != OV2_OK) return (int)s;
     out[0] = r.skipped ? 1 : 0; out[1] = r.image_id; out[2] = (int)r.det.status; out[3] = (int)r.det.train_id; out[4] = r.cand_kfid;
     out[5] = r.matched.lckfid; out[6] = r.matched.branch; out[7] = (int)r.matched.vkplmids.size(); out[8] = r.verified.branch;
@@ -1878,6 +1975,18 @@ void ov2h_loop_set_brief_pattern(void *h, const int8_t *pattern256x4) { ((LoopCl
 void ov2h_loop_set_extra_cap(void *h, int cap) { ((LoopCloser *)h)->extra_out_cap_ = cap; }
 
 // the closer's detector (null before its first keyframe) for ov2h_lcd_counts / ov2h_lcd_trace; the closer keeps owning it
+// LoopCloser::close_loops_: newKeyframe(s) go on to closeLoop(s) on an LV_ACCEPTED result
+void ov2h_loop_closer_set_close(void *h, int on) { ((LoopCloser *)h)->close_loops_ = on != 0; }
+
+// `closed` of the closer's last ov2h_loop_new_keyframe result, as a row of ov2h_loop_close (an untouched LoopCloseResult when
+// nothing was closed); stats[3] = last_close_
+int ov2h_loop_closer_closed(void *h, int cap, int *ints, double *dbl, int *merged, int *stats)
+{
+    LoopCloser *lc = (LoopCloser *)h;
+    stats[0] = lc->last_close_.jobs; stats[1] = lc->last_close_.graphs; stats[2] = lc->last_close_.solve_calls;
+    return pack_close(lc->last_closed_, ints, dbl, cap, merged) ? 0 : (int)OV2_ERR_INVALID;
+}
+
 void *ov2h_loop_closer_detector(void *h) { return ((LoopCloser *)h)->plcdetector_.get(); }
 
 // LoopCloser::extraKeypoints for B closers (h[k], kfid[k], image b[k] of pyr).  counts: B x 5 = skipped, nbkps, mask points,

@@ -1325,7 +1325,96 @@ bool LoopCloser::mapPointDescs(int kfid, std::vector<uint8_t> &descs, std::vecto
     return true;
 }
 
-ov2_status LoopCloser::afterDetector(int kfid, uint64_t seed, LoopNewKeyframeResult &r)
+// ---- after an accepted loop (src/loop_closer.cpp:302-372) ----------------------------------------------------------------------
+ov2_status LoopCloser::closeLoops(std::vector<LoopCloseJob> &jobs)
+{
+    const size_t B = jobs.size();
+    if (B == 0) return OV2_OK;
+    LoopCloseStats stats;
+    stats.jobs = (int)B;
+    for (size_t k = 0; k < B; ++k) {
+        if (!jobs[k].closer || jobs[k].closer->ctx_ != jobs[0].closer->ctx_) return OV2_ERR_INVALID;
+        for (size_t j = 0; j < k; ++j)
+            if (jobs[j].closer == jobs[k].closer || jobs[j].closer->pmap_ == jobs[k].closer->pmap_) return OV2_ERR_INVALID;
+        jobs[k].r = LoopCloseResult();
+    }
+    ov2_ctx *ctx = jobs[0].closer->ctx_;
+    struct Pending { size_t job; LocalPoseGraph g; };
+    std::vector<Pending> pend;
+    pend.reserve(B);
+    std::vector<std::shared_ptr<Frame>> vnew(B);
+    for (size_t k = 0; k < B; ++k) {
+        LoopCloseJob &J = jobs[k];
+        LoopCloser &lc = *J.closer;
+        LoopCloseResult &r = J.r;
+        if (J.vkplmids.size() < 30) continue;                                            // :305
+        auto pnewkf = lc.pmap_->getKeyframe(J.newkfid), plckf = lc.pmap_->getKeyframe(J.lckfid);
+        if (!pnewkf || !plckf) return OV2_ERR_INVALID;
+        vnew[k] = pnewkf;
+        const auto cov = plckf->getCovisibleKfMap();
+        r.inikfid = cov.empty() ? plckf->kfid_ : cov.begin()->first;                     // :314 (empty map: the keyframe's own id)
+        r.lc_pose_err = loop_pose_err(*pnewkf, J.Twc);                                   // :318
+        r.branch = LCL_PG_REFUSED;
+        Optimizer opt(ctx, lc.pslamstate_, lc.pmap_);
+        Pending P;
+        P.job = k;
+        if (!opt.assembleLocalPoseGraph(*pnewkf, r.inikfid, J.Twc, P.g)) continue;       // :320, first stage
+        pend.push_back(std::move(P));
+    }
+    if (!pend.empty()) {                                                                 // :320, the solve: one call for all
+        std::vector<ov2_pg_problem> Ps;
+        std::vector<ov2_pg_result> Rs(pend.size());
+        for (auto &P : pend) Ps.push_back(P.g.view());
+        Optimizer o0(ctx, jobs[pend[0].job].closer->pslamstate_, jobs[pend[0].job].closer->pmap_);
+        const ov2_ba_options o = o0.localPoseGraphOptions();
+        const ov2_status s = ov2_pose_graph_solve_batch(ctx, (int)Ps.size(), Ps.data(), &o, Rs.data());
+        stats.graphs = (int)Ps.size();
+        stats.solve_calls = 1;
+        for (size_t i = 0; i < pend.size(); ++i) { jobs[pend[i].job].r.pg_status = (int)s; jobs[pend[i].job].r.pg = Rs[i]; }
+        if (s != OV2_OK) {
+            for (auto &J : jobs) J.closer->last_close_ = stats;
+            return s;
+        }
+    }
+    for (auto &P : pend) {
+        LoopCloseJob &J = jobs[P.job];
+        LoopCloser &lc = *J.closer;
+        LoopCloseResult &r = J.r;
+        Optimizer opt(ctx, lc.pslamstate_, lc.pmap_);
+        if (!opt.applyLocalPoseGraph(P.g)) continue;                                     // :320, last stage; :325
+        r.branch = LCL_CLOSED;
+        for (const auto &kplmid : J.vkplmids) {                                          // :336-348
+            const int prevlmid = kplmid.first, newlmid = kplmid.second;
+            if (prevlmid == newlmid) continue;
+            lc.pmap_->mergeMapPoints(prevlmid, newlmid);
+            r.vmergedlmids.push_back(newlmid);
+        }
+        r.sba_status = (int)opt.structureOnlyBA(r.vmergedlmids);                         // :353
+        if (r.lc_pose_err >= 0.02) {                                                     // :358-371
+            auto pinikf = lc.pmap_->getKeyframe(r.inikfid);
+            r.loose_start = r.inikfid;
+            if (pinikf) {
+                const auto cov = pinikf->getCovisibleKfMap();
+                if (!cov.empty()) r.loose_start = cov.begin()->first;
+            }
+            r.loose_status = (int)opt.looseBA(r.loose_start, J.newkfid, true);
+            r.branch = LCL_CLOSED_LOOSE_BA;
+        }
+    }
+    for (auto &J : jobs) J.closer->last_close_ = stats;
+    return OV2_OK;
+}
+
+ov2_status LoopCloser::closeLoop(int newkfid, int lckfid, const SE3 &Twc, const std::vector<std::pair<int, int>> &vkplmids, LoopCloseResult &r)
+{
+    std::vector<LoopCloseJob> jobs(1);
+    jobs[0].closer = this; jobs[0].newkfid = newkfid; jobs[0].lckfid = lckfid; jobs[0].Twc = Twc; jobs[0].vkplmids = vkplmids;
+    const ov2_status s = closeLoops(jobs);
+    r = jobs[0].r;
+    return s;
+}
+
+ov2_status LoopCloser::afterDetector(int kfid, uint64_t seed, LoopNewKeyframeResult &r, bool close_now)
 {
     if (r.det.status != LC_DETECTED) return OV2_OK;                         // :156-164
     int cand = vkfids_.at(r.det.train_id);                                  // :187
@@ -1338,6 +1427,8 @@ ov2_status LoopCloser::afterDetector(int kfid, uint64_t seed, LoopNewKeyframeRes
     if (s != OV2_OK) return s;
     r.matched = matched[0];
     r.verified = verified[0];
+    if (close_loops_ && close_now && r.verified.branch == LV_ACCEPTED)                   // :302-372
+        return closeLoop(kfid, r.matched.lckfid, r.verified.Twc, r.verified.vkplmids, r.closed);
     return OV2_OK;
 }
 
@@ -1465,7 +1556,22 @@ ov2_status LoopCloser::newKeyframes(const std::vector<LoopCloser *> &closers, co
     for (size_t i = 0; i < of.size(); ++i) {
         out[of[i]].det = res[i];
         closers[of[i]]->last_ = LoopStats();
-        if ((s = closers[of[i]]->afterDetector(kfids[of[i]], seeds[of[i]], out[of[i]])) != OV2_OK) return s;
+        if ((s = closers[of[i]]->afterDetector(kfids[of[i]], seeds[of[i]], out[of[i]], false)) != OV2_OK) return s;
+    }
+    // the accepted loops of the closers that close them: one closeLoops call (one pose-graph solve)
+    std::vector<LoopCloseJob> cj;
+    std::vector<size_t> cof;
+    for (size_t i = 0; i < of.size(); ++i) {
+        const LoopNewKeyframeResult &r = out[of[i]];
+        if (!closers[of[i]]->close_loops_ || r.verified.branch != LV_ACCEPTED) continue;
+        LoopCloseJob J;
+        J.closer = closers[of[i]]; J.newkfid = kfids[of[i]]; J.lckfid = r.matched.lckfid; J.Twc = r.verified.Twc; J.vkplmids = r.verified.vkplmids;
+        cj.push_back(J); cof.push_back(of[i]);
+    }
+    if (!cj.empty()) {
+        s = closeLoops(cj);
+        for (size_t i = 0; i < cj.size(); ++i) out[cof[i]].closed = cj[i].r;
+        if (s != OV2_OK) return s;
     }
     return OV2_OK;
 }

@@ -211,8 +211,44 @@ struct LoopTrackStats {   // one trackLoopLocalMaps call
 // for one pair as the reference writes it (verifyLoopCandidate) and for B pairs with one library call per stage
 // (verifyLoopCandidates).  newKeyframe is the body of LoopCloser::run for one keyframe (:86-169): the detector that proposes the
 // candidate (ov2::LCDetector, ov2_lcd.hpp) in front of processLoopCandidates; with the keyframe's raw image it also detects and
-// describes the 300 extra FAST + BRIEF keypoints of :115-140 (extraKeypoints) and hands the detector both sets.  Not built: the
-// calls after an accepted loop (:302-372), and any call from SlamManager's frame loop.
+// describes the 300 extra FAST + BRIEF keypoints of :115-140 (extraKeypoints) and hands the detector both sets.  closeLoop is
+// what follows an accepted loop (:302-372): localPoseGraph, mergeMapPoints, structureOnlyBA, looseBA; closeLoops does it for
+// the loops of B maps with one pose-graph solve call.  With close_loops_ set, newKeyframe(s) go on to it; it is off by default.
+// Not built: any call from SlamManager's frame loop.
+// what LoopCloser::closeLoop did with an accepted loop (src/loop_closer.cpp:302-372)
+enum LoopCloseBranch {
+    LCL_FEW_PAIRS = 0,     // :305 fewer than 30 pairs: nothing is called
+    LCL_PG_REFUSED,        // :320 localPoseGraph returned false (no chain, or the degenerate test of src/optimizer.cpp:2467-2474): the map is untouched
+    LCL_CLOSED,            // pose graph applied, pairs merged, structureOnlyBA run; lc_pose_err < 0.02: no looseBA
+    LCL_CLOSED_LOOSE_BA    // ... and looseBA run (:358-371)
+};
+enum { LCL_NOT_CALLED = 1 };   // value of a status field whose call was not made (an ov2_status is <= 0)
+
+struct LoopCloseResult {
+    int branch = LCL_FEW_PAIRS;
+    int inikfid = -1;                 // :314 the smallest key of the loop keyframe's covisibility map
+    int loose_start = -1;             // :363 the smallest key of inikf's covisibility map (looseBA's first keyframe)
+    double lc_pose_err = 0.;          // :318
+    int pg_status = LCL_NOT_CALLED;   // status of the pose-graph solve
+    ov2_pg_result pg{};
+    std::vector<int> vmergedlmids;    // :347 the new lmid of every pair with prev != new, in list order
+    int sba_status = LCL_NOT_CALLED, loose_status = LCL_NOT_CALLED;   // structureOnlyBA (:353), looseBA (:368)
+};
+
+class LoopCloser;
+
+struct LoopCloseJob {   // one accepted loop for LoopCloser::closeLoops
+    LoopCloser *closer = nullptr;
+    int newkfid = -1, lckfid = -1;
+    SE3 Twc;
+    std::vector<std::pair<int, int>> vkplmids;
+    LoopCloseResult r;   // out
+};
+
+struct LoopCloseStats {   // one closeLoop(s) call
+    int jobs = 0, graphs = 0, solve_calls = 0;   // jobs given, graphs offered to ov2_pose_graph_solve_batch, calls of it (0 or 1)
+};
+
 struct LoopNewKeyframeResult {
     bool skipped = false;        // :111-113 no map point of the keyframe has a descriptor: the detector is not called
     int image_id = -1;           // kf_idx_ of this keyframe (index into vkfids_); -1 when skipped
@@ -220,6 +256,7 @@ struct LoopNewKeyframeResult {
     int cand_kfid = -1;          // on LC_DETECTED: vkfids_[train_id], walked down to the closest keyframe still in the map (:187-195)
     LoopPairResult matched;      // processLoopCandidates on (kfid, cand_kfid); untouched without a candidate
     LoopVerifyResult verified;
+    LoopCloseResult closed;      // closeLoop on an LV_ACCEPTED result while close_loops_ is set; untouched otherwise
     int nbkps = 0, n_extra = 0;  // the two counts the reference logs (:138): vkps.size() and vaddkps.size(); image forms only
     int n_descs = 0;             // descriptor rows the detector received
 };
@@ -349,6 +386,20 @@ public:
     ov2_status matchLoopCandidates(const std::vector<std::pair<int, int>> &pairs, const std::vector<uint64_t> &seeds,
                                    std::vector<LoopPairResult> &out);
     LoopStats last_;
+    // :302-372, statement by statement: the >= 30 gate; inikfid = the smallest key of the loop keyframe's covisibility map
+    // (DEPARTURE: an empty map is undefined behaviour in the reference, here it stands for the keyframe's own id);
+    // lc_pose_err; localPoseGraph; on success mergeMapPoints for every pair with prev != new in list order,
+    // structureOnlyBA(vmergedlmids) and, if lc_pose_err >= 0.02, looseBA(smallest key of inikf's covisibility map, newkfid,
+    // true).  A keyframe that is not in the map is OV2_ERR_INVALID.  closeLoop is closeLoops with one job.
+    ov2_status closeLoop(int newkfid, int lckfid, const SE3 &Twc, const std::vector<std::pair<int, int>> &vkplmids, LoopCloseResult &r);
+    // the same for B closers with distinct maps on one context: every job's graph is assembled, ONE
+    // ov2_pose_graph_solve_batch call solves the graphs of the jobs that pass the gate and have a chain (a graph that the
+    // degenerate test then refuses has been solved: it counts as offered), then apply / merge / structureOnlyBA / looseBA
+    // per job -- the two BA calls stay one library call per job.  A job's outcome equals closeLoop on it.
+    static ov2_status closeLoops(std::vector<LoopCloseJob> &jobs);
+    LoopCloseStats last_close_;
+    LoopCloseResult last_closed_;   // `closed` of the last newKeyframe result handed out through the C hooks
+    bool close_loops_ = false;
     ov2_ctx *ctx_;
     std::shared_ptr<SlamParams> pslamstate_;
     std::shared_ptr<MapManager> pmap_;
@@ -357,7 +408,7 @@ private:
     // :97-109: the descriptors of the keyframe's map points (and, with px, the pixels of those keypoints); false: no such keyframe
     bool mapPointDescs(int kfid, std::vector<uint8_t> &descs, std::vector<Point2f> *px, int *nbkps) const;
     // :187-195 and :167 behind a detector result
-    ov2_status afterDetector(int kfid, uint64_t seed, LoopNewKeyframeResult &r);
+    ov2_status afterDetector(int kfid, uint64_t seed, LoopNewKeyframeResult &r, bool close_now = true);
 };
 
 }  // namespace ov2

@@ -37,6 +37,7 @@ def lib():
         L.ov2h_range_ba_setup.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip]
         L.ov2h_full_ba.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, C.POINTER(C.c_double), ip]
         L.ov2h_local_pose_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, dp, C.POINTER(C.c_double), ip]
+        L.ov2h_apply_local_pose_graph.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp]
         L.ov2h_full_pose_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, dp, C.POINTER(C.c_uint8), C.POINTER(C.c_double)]
         L.ov2h_loose_ba.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_double)]
         L.ov2h_map_remove_obs.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -321,6 +322,18 @@ class HostMap:
         if rc < 0:
             raise RuntimeError(f"localPoseGraph failed ({rc})")
         return rc, fc.value, nl.value
+
+    def apply_local_pose_graph(self, newkf, kfids, Twc):
+        """Optimizer::applyLocalPoseGraph alone: the free keyframes `kfids` (ascending, last = newkf) take the poses Twc
+        (n x 7) as a solve would have left them, and keyframes / anchored landmarks / younger keyframes follow.  Needs no
+        GPU context; with a device mirror attached the edits wait in its dirty lists for flush_device()."""
+        k = np.ascontiguousarray(kfids, np.int32)
+        T = np.ascontiguousarray(Twc, np.float64).reshape(-1, 7)
+        assert len(k) == len(T)
+        rc = lib().ov2h_apply_local_pose_graph(self.h, int(newkf), len(k), k.ctypes.data_as(C.POINTER(C.c_int)), _dp(T))
+        if rc < 0:
+            raise RuntimeError(f"applyLocalPoseGraph failed ({rc})")
+        return rc
 
     def full_pose_graph(self, ctx, Twc, Tpc, iskf):
         """Optimizer::fullPoseGraph on (n x 7) poses, (n x 7) relative poses prev -> cur, keyframe flags. returns (ok, Twc, cost)"""
@@ -1100,6 +1113,24 @@ class LoopMap:
         return out, dict(pairs=int(stats[0]), knn_pairs=int(stats[1]), epi_pairs=int(stats[2]), knn_calls=int(stats[3]),
                          epi_calls=int(stats[4]))
 
+    # the steps of the chain one by one, and what a test reads back: HostMap's methods work on any ov2h map handle
+    local_pose_graph = HostMap.local_pose_graph
+    structure_only_ba = HostMap.structure_only_ba
+    loose_ba = HostMap.loose_ba
+    pose = HostMap.pose
+    landmark = HostMap.landmark
+
+    def merge_points(self, prevlmid, newlmid):
+        """MapManager::mergeMapPoints"""
+        L = lib()
+        L.ov2h_map_merge_points.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        assert L.ov2h_map_merge_points(self.h, int(prevlmid), int(newlmid)) == 0
+
+    def loop_close(self, ctx, newkf, lckf, Twc, vkplmids, cap=1 << 14):
+        """LoopCloser::closeLoop on an accepted loop (src/loop_closer.cpp:302-372): dict as unpack_close gives it; a negative
+        status raises"""
+        return loop_close_batch(ctx, [self], [newkf], [lckf], [Twc], [vkplmids], cap, single=True)[0]
+
     def close(self):
         if getattr(self, "h", None):
             lib().ov2h_map_destroy(self.h)
@@ -1107,6 +1138,47 @@ class LoopMap:
 
     def __del__(self):
         self.close()
+
+
+LCL_FEW_PAIRS, LCL_PG_REFUSED, LCL_CLOSED, LCL_CLOSED_LOOSE_BA = range(4)   # ov2::LoopCloseBranch
+LCL_NOT_CALLED = 1                                                          # a status field whose call was not made
+
+
+def unpack_close(ints, dbl, merged, stats):
+    """one row of ov2h_loop_close -> dict (slicing only)"""
+    i = [int(v) for v in ints]
+    return dict(branch=i[0], inikfid=i[1], loose_start=i[2], pg_status=i[3], sba_status=i[4], loose_status=i[5],
+                merged=[int(v) for v in merged[:i[6]]], pg_termination=i[7], pg_n_log=i[8], lc_pose_err=float(dbl[0]),
+                pg_initial_cost=float(dbl[1]), pg_final_cost=float(dbl[2]),
+                last_close=dict(jobs=int(stats[0]), graphs=int(stats[1]), solve_calls=int(stats[2])))
+
+
+def loop_close_batch(ctx, maps, newkf, lckf, Twc, lists, cap=1 << 14, single=False):
+    """LoopCloser::closeLoops on B LoopMaps of one context, one accepted loop each (Twc[b], lists[b] = its vkplmids): ONE
+    pose-graph solve call for all, then apply / merge / structureOnlyBA / looseBA per map.  Returns the list of per-map dicts
+    (each carries the call's last_close counts).  single: LoopCloser::closeLoop through its own hook (B must be 1)"""
+    L, B = lib(), len(maps)
+    vp, ip, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)
+    nk, lc = np.ascontiguousarray(newkf, np.int32), np.ascontiguousarray(lckf, np.int32)
+    T = np.ascontiguousarray(Twc, np.float64).reshape(-1, 7)
+    n_in = np.ascontiguousarray([len(v) for v in lists], np.int32)
+    pin = np.ascontiguousarray([q for v in lists for q in v], np.int32).reshape(-1, 2)
+    ints, dbl = np.zeros((max(B, 1), 9), np.int32), np.zeros((max(B, 1), 3))
+    merged, st = np.zeros((max(B, 1), cap), np.int32), np.zeros(3, np.int32)
+    if single:
+        assert B == 1
+        L.ov2h_loop_close.argtypes = [vp, vp, C.c_int, C.c_int, dp, C.c_int, ip, C.c_int, ip, dp, ip, ip]
+        rc = L.ov2h_loop_close(maps[0].h, ctx.h, int(nk[0]), int(lc[0]), _dp(T), int(n_in[0]), pin.ctypes.data_as(ip), cap,
+                               ints.ctypes.data_as(ip), _dp(dbl), merged.ctypes.data_as(ip), st.ctypes.data_as(ip))
+    else:
+        L.ov2h_loop_close_batch.argtypes = [C.c_int, vp, vp, ip, ip, dp, ip, ip, C.c_int, ip, dp, ip, ip]
+        hs = (vp * max(B, 1))(*[m.h for m in maps])
+        rc = L.ov2h_loop_close_batch(B, hs, ctx.h, nk.ctypes.data_as(ip), lc.ctypes.data_as(ip), _dp(T), n_in.ctypes.data_as(ip),
+                                     pin.ctypes.data_as(ip), cap, ints.ctypes.data_as(ip), _dp(dbl), merged.ctypes.data_as(ip),
+                                     st.ctypes.data_as(ip))
+    if rc != 0:
+        raise RuntimeError(f"closeLoops: status {rc}")
+    return [unpack_close(ints[b], dbl[b], merged[b], st) for b in range(B)]
 
 
 class FrontEndFrame:

@@ -210,6 +210,22 @@ class LoopCloser:
         r["stats"] = dict(zip(_LOOP_STATS, st.tolist()))
         return r
 
+    def set_close(self, on):
+        """LoopCloser::close_loops_: new_keyframe goes on to closeLoop on an accepted loop (off by default)"""
+        self.L.ov2h_loop_closer_set_close.argtypes = [vp, C.c_int]
+        self.L.ov2h_loop_closer_set_close(self.h, int(bool(on)))
+
+    def closed(self, cap=1 << 14):
+        """`closed` of the last new_keyframe result (host_map.unpack_close layout; an untouched result when nothing was closed)"""
+        from .host_map import unpack_close
+        ints, dbl, merged, st = np.zeros(9, np.int32), np.zeros(3), np.zeros(cap, np.int32), np.zeros(3, np.int32)
+        self.L.ov2h_loop_closer_closed.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        rc = self.L.ov2h_loop_closer_closed(self.h, cap, ints.ctypes.data_as(vp), dbl.ctypes.data_as(vp), merged.ctypes.data_as(vp),
+                                            st.ctypes.data_as(vp))
+        if rc != 0:
+            raise RuntimeError(f"ov2h_loop_closer_closed: status {rc}")
+        return unpack_close(ints, dbl, merged, st)
+
     def set_brief_pattern(self, pattern):
         """the 256 BRIEF-32 test pairs (256 x {y1, x1, y2, x2}, int8) the extra keypoints are described with"""
         pat = np.ascontiguousarray(pattern, np.int8).reshape(256, 4)

@@ -4,7 +4,7 @@ the whole LM loop on the MI355X.  Plumbing only."""
 import ctypes as C
 
 from . import _lib
-from .ba_types import BaOptionsC, PgResultC
+from .ba_types import BaOptionsC, PgProblemC, PgResultC
 from .frontend import _check
 
 
@@ -24,3 +24,15 @@ def solve(ctx, problem, options=None):
     pc = problem.as_c()
     _check(ctx.h, ctx.lib.ov2_pose_graph_solve(ctx.h, C.byref(pc), C.byref(o), C.byref(res)))
     return res
+
+
+def solve_batch(ctx, problems, options=None):
+    """ov2_pose_graph_solve_batch: every PgProblem of `problems` solved in place by one launch (one workgroup per graph),
+    each bit-identical to solve() on it; returns the list of PgResultC.  A graph the single call would refuse refuses the
+    whole call and leaves every pose array as it was."""
+    o = options if options is not None else default_options()
+    B = len(problems)
+    pcs = (PgProblemC * max(B, 1))(*[p.as_c() for p in problems])
+    rcs = (PgResultC * max(B, 1))()
+    _check(ctx.h, ctx.lib.ov2_pose_graph_solve_batch(ctx.h, B, pcs, C.byref(o), rcs))
+    return [PgResultC.from_buffer_copy(rcs[k]) for k in range(B)]
