@@ -74,6 +74,17 @@ ov2_status ov2_ctx_set_pyr_ring(ov2_ctx *ctx, int n);
  * out[2] / out[3] / out[4] builds since the context was created that took a finished pooled buffer / a pooled buffer with
  * readers pending / a new allocation. */
 ov2_status ov2_ctx_pyr_pool_stats(ov2_ctx *ctx, int32_t out[5]);
+/* Counters of the waits for pyramids (no device work).  Every call that reads a pyramid puts ctx's main stream behind the
+ * build (and, for the 8 / 16-lane tracking kernels, behind the gradient planes) before it enqueues its kernels.  For a
+ * pyramid built on ctx itself the stream needs that only once per build: *issued counts the event waits enqueued on ctx's
+ * main stream since the context was created, *elided the ones left out because the stream had waited for that build
+ * before or the build had already completed.  A pyramid built on another context is always waited for, so a context that
+ * only consumes foreign pyramids reports *elided == 0. */
+ov2_status ov2_ctx_pyr_wait_stats(ov2_ctx *ctx, int64_t *issued, int64_t *elided);
+/* The part of *elided above that was left out because the build (or the gradient planes) had already completed when
+ * asked for, as opposed to waited for before.  For the pyramids a context builds and consumes itself,
+ * issued + found_complete = the number of builds consumed: each is waited for, or found complete, exactly once. */
+ov2_status ov2_ctx_pyr_wait_found_complete(ov2_ctx *ctx, int64_t *found_complete);
 /* hipEvent pair on the ctx stream (used by bench.py: torch.cuda.Event would only see torch's stream) */
 ov2_status ov2_timer_start(ov2_ctx *ctx);
 ov2_status ov2_timer_stop(ov2_ctx *ctx, float *elapsed_ms);   /* synchronises on the stop event */
@@ -118,7 +129,9 @@ void ov2_pyr_retain(ov2_pyr *p);
 void ov2_pyr_release(ov2_pyr *p);
 /* release a reference whose readers were enqueued on ANOTHER context's stream (the mapper thread's context: Keyframe
  * holds the pyramids for Mapper::run, include/mapper.hpp:39-85, src/mapper.cpp:76-97): the buffer is not reused before
- * those readers have run.  One foreign consumer context per pyramid. */
+ * those readers have run.  One foreign consumer context per pyramid, and it must be a context of the SAME device as the
+ * one that built the pyramid: the kernels read the buffer in place and the pool's events order streams of one device only
+ * (no system-scope fence).  A call that is handed a pyramid of another device returns OV2_ERR_INVALID. */
 void ov2_pyr_release_from(ov2_ctx *user, ov2_pyr *p);
 int ov2_pyr_batch(const ov2_pyr *p);
 int ov2_pyr_nlevels(const ov2_pyr *p);

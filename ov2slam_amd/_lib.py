@@ -26,6 +26,8 @@ SIGNATURES = {
     "ov2_ctx_set_kf_overlap": (C.c_int, [vp, C.c_int]),
     "ov2_ctx_set_pyr_ring": (C.c_int, [vp, C.c_int]),
     "ov2_ctx_pyr_pool_stats": (C.c_int, [vp, C.POINTER(C.c_int32)]),
+    "ov2_ctx_pyr_wait_stats": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ov2_ctx_pyr_wait_found_complete": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "ov2_timer_start": (C.c_int, [vp]),
     "ov2_timer_stop": (C.c_int, [vp, fp]),
     "ov2_ktime_enable": (C.c_int, [vp, C.c_int]),

@@ -83,6 +83,9 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     c->pyr_ring = (ring >= 1 && ring <= OV2_PYR_RING_MAX) ? ring : OV2_PYR_RING_DEFAULT;
     c->pyr_alive = 0;
     c->pyr_acquires[0] = c->pyr_acquires[1] = c->pyr_acquires[2] = 0;
+    c->pyr_waits[0].store(0);
+    c->pyr_waits[1].store(0);
+    c->pyr_waits[2].store(0);
     // three streams of one priority: tracking / BA, pyramid builds, keyframe detector chain (a pyramid stream one level
     // more urgent than the other two was measured and changes nothing, DESIGN.md section 7 "A ring for the pyramid pool")
     int prio_least = 0, prio_greatest = 0;
@@ -92,8 +95,8 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     const hipError_t e2 = hipStreamCreateWithPriority(&c->stream_pyr, hipStreamNonBlocking, prio);
     const hipError_t e3 = hipStreamCreateWithPriority(&c->stream_kf, hipStreamNonBlocking, prio);
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess ||
-        hipEventCreateWithFlags(&c->kf.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->kf.done, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->kf.fork, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
+        hipEventCreateWithFlags(&c->kf.done, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreateWithFlags(&c->stage_ev, hipEventDisableTiming) != hipSuccess) {
         delete c;
@@ -213,6 +216,21 @@ extern "C" ov2_status ov2_ctx_pyr_pool_stats(ov2_ctx *c, int32_t out[5])
     out[2] = c->pyr_acquires[0];
     out[3] = c->pyr_acquires[1];
     out[4] = c->pyr_acquires[2];
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_ctx_pyr_wait_stats(ov2_ctx *c, int64_t *issued, int64_t *elided)
+{
+    if (!c || !issued || !elided) return OV2_ERR_INVALID;
+    *issued = c->pyr_waits[0].load(std::memory_order_relaxed);
+    *elided = c->pyr_waits[1].load(std::memory_order_relaxed);
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_ctx_pyr_wait_found_complete(ov2_ctx *c, int64_t *found_complete)
+{
+    if (!c || !found_complete) return OV2_ERR_INVALID;
+    *found_complete = c->pyr_waits[2].load(std::memory_order_relaxed);
     return OV2_OK;
 }
 

@@ -41,6 +41,12 @@ struct ov2_pyr_buf {  // pooled allocation; geometry key = (w,h,pad,max_level,ba
     unsigned char *base;
     unsigned char *lut;  // CLAHE LUTs: batch * tiles * 256 (allocated lazily, max tiles 64x64)
     hipEvent_t ready_ev; // recorded on the ctx pyramid stream when the build is enqueued; consumers wait on it
+    // Which build the buffer holds, and the builds the owning ctx's main stream already waits behind: a stream that waited for
+    // a build once stays behind it, so a second wait for the same build is an event packet that orders nothing
+    // (ov2_pyr_wait_ready).  All three are guarded by the owning ctx's mutex.
+    unsigned long long build_seq;         // bumped by every ov2_pyramid_build_images into this buffer
+    unsigned long long ready_waited_seq;  // build whose ready_ev the owner's main stream has waited for (or found complete)
+    unsigned long long grad_waited_seq;   // build whose gradient planes the owner's main stream is ordered behind
     hipEvent_t free_ev;  // recorded on the ctx main stream when the last handle is released; the next build waits on it
     bool has_free_ev;
     hipEvent_t free_ev2; // recorded on ANOTHER context's main stream by ov2_pyr_release_from (the mapper's readers); the next build waits on it too
@@ -102,12 +108,16 @@ struct ov2_ctx {
     void *kf_scratch_dev;                // scratch of the chain on the side stream (grown on demand; growth waits for
     size_t kf_scratch_bytes;             //   the side stream alone)
     hipEvent_t ev0, ev1;
-    std::mutex mu;                       // guards pool + err
+    std::mutex mu;                       // guards pool + err, and of every pyramid buffer this ctx built: grad_built and the
+                                         //   build / waited sequence numbers (held around the event query and wait of ov2_pyr_wait_ready)
     std::vector<ov2_pyr_buf *> pool;     // free pyramid buffers, in release order (oldest first)
     int pyr_ring;                        // ov2_ctx_set_pyr_ring / OV2_PYR_RING: released-but-unfinished buffers of one geometry the
                                          //   pool holds before a build reuses the oldest of them
     int pyr_alive;                       // pyramid buffers allocated and not freed (pooled + handed out); under mu
     int pyr_acquires[3];                 // builds served by a finished / a pending / a newly allocated buffer; under mu
+    std::atomic<long long> pyr_waits[3]; // pyramid waits THIS ctx's main stream was asked for: event packets issued / elided /
+                                         //   of the elided, those left out because the event had completed (ov2_ctx_pyr_wait_stats,
+                                         //   ov2_ctx_pyr_wait_found_complete; atomics, the guard held is the pyramid owner's, not ours)
     std::vector<struct ov2_map *> maps;  // live map mirrors (their device memory is released with the ctx)
     std::string err;
     // scratch for host-pointer entry points (grown on demand)
@@ -155,6 +165,12 @@ struct ov2_pyr {
     ov2_ctx *ctx;
     ov2_pyr_buf *buf;
 };
+
+// Events that only order streams of one device against each other (the pyramid pool's ready / grad / free marks, the fork
+// and join of the keyframe side stream): no timing, and no system-scope fence with the record -- that fence makes the
+// writes in front of the event visible to the host and to other devices, and nothing on either reads behind these events.
+// stage_ev (the host rewrites the pinned staging block behind it), ba_copy_ev and the timing events keep their flags.
+#define OV2_ORDER_EVENT_FLAGS (hipEventDisableTiming | hipEventDisableSystemFence)
 
 #define OV2_PYR_RING_DEFAULT 3   // the smallest depth at which the frame loop no longer waits for its pyramids
 #define OV2_PYR_RING_MAX 8

@@ -1017,10 +1017,10 @@ ov2_status acquire_buf(ov2_ctx *c, int w, int h, int pad, int max_level, int bat
         delete b;
         return ov2_set_err(c, OV2_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     }
-    if (hipEventCreateWithFlags(&b->ready_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&b->grad_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&b->free_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&b->free_ev2, hipEventDisableTiming) != hipSuccess) {
+    if (hipEventCreateWithFlags(&b->ready_ev, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
+        hipEventCreateWithFlags(&b->grad_ev, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
+        hipEventCreateWithFlags(&b->free_ev, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
+        hipEventCreateWithFlags(&b->free_ev2, OV2_ORDER_EVENT_FLAGS) != hipSuccess) {
         (void)hipFree(b->base);
         delete b;
         return ov2_set_err(c, OV2_ERR_HIP, "hipEventCreate failed");
@@ -1028,6 +1028,7 @@ ov2_status acquire_buf(ov2_ctx *c, int w, int h, int pad, int max_level, int bat
     b->has_free_ev = false;
     b->has_free_ev2 = false;
     b->grad_built = false;
+    b->build_seq = b->ready_waited_seq = b->grad_waited_seq = 0;
     v.base = b->base;
     {
         std::lock_guard<std::mutex> g(c->mu);
@@ -1124,7 +1125,8 @@ extern "C" ov2_status ov2_pyramid_build_images(ov2_ctx *c, const ov2_images *im,
                       im->h, im->stride, im->bstride, use_clahe, buf->lut, tiles_x, tiles_y, inv_tw, inv_th, v);
     }
     // pyrDown chain only: the gradient planes are written when a consumer asks for them (ov2_pyr_need_grad)
-    { std::lock_guard<std::mutex> g(c->mu); buf->grad_built = false; }
+    // a new build: whatever the main stream waited for in this buffer was an earlier one
+    { std::lock_guard<std::mutex> g(c->mu); buf->grad_built = false; ++buf->build_seq; }
     // two levels per launch while two are left, then one
     int l = first_down;
     for (; l + 2 < v.nlevels; l += 2) {
@@ -1242,11 +1244,45 @@ extern "C" ov2_status ov2_pyr_download_level(ov2_ctx *c, const ov2_pyr *p, int b
     return OV2_OK;
 }
 
+namespace {
+
+// Puts c's main stream behind `ev` (ready_ev or grad_ev of p's buffer) unless it provably is already.  Call with the OWNING
+// context's mutex held.  The owner's main stream needs one wait per build: `*waited_seq` names the build it has waited
+// for, and every later call finds the stream behind that point already (the second call of a frame loop that tracks
+// t - 1 -> t, then t -> t + 1; the detector behind the stereo call of a keyframe).  An event that has completed orders
+// nothing either, so a host that does not run ahead of the device issues no packet at all.  A consumer on another
+// context has a stream of its own and no record here: it always waits.  The keyframe side stream needs no wait of its
+// own, its chain starts from an event recorded on the main stream behind this point (detect.hip).
+hipError_t wait_once(ov2_ctx *c, const ov2_pyr *p, hipEvent_t ev, unsigned long long *waited_seq)
+{
+    const ov2_pyr_buf *buf = p->buf;
+    const bool own = c == p->ctx;
+    if (own && *waited_seq == buf->build_seq) {
+        c->pyr_waits[1].fetch_add(1, std::memory_order_relaxed);
+        return hipSuccess;
+    }
+    if (own && hipEventQuery(ev) == hipSuccess) {
+        *waited_seq = buf->build_seq;
+        c->pyr_waits[1].fetch_add(1, std::memory_order_relaxed);
+        c->pyr_waits[2].fetch_add(1, std::memory_order_relaxed);
+        return hipSuccess;
+    }
+    const hipError_t err = hipStreamWaitEvent(c->stream.h, ev, 0);   // ordering only: not a use of the main stream (ov2_main_stream)
+    if (err == hipSuccess) {
+        if (own) *waited_seq = buf->build_seq;
+        c->pyr_waits[0].fetch_add(1, std::memory_order_relaxed);
+    }
+    return err;
+}
+
+}  // namespace
+
 // Scharr planes of every level, written once per pyramid by the first consumer that needs them (the 8 / 16-lane KLT
 // kernels, ov2_pyr_download_level) on ITS main stream, behind the build; later consumers wait for that point.
 ov2_status ov2_pyr_need_grad(ov2_ctx *c, const ov2_pyr *p)
 {
     if (!c || !p) return OV2_ERR_INVALID;
+    if (c->device != p->ctx->device) return ov2_set_err(c, OV2_ERR_INVALID, "pyramid of device %d used on device %d", p->ctx->device, c->device);
     ov2_pyr_buf *buf = p->buf;
     // The HIP calls run under the owning context's mutex (two consumer contexts must not both write the planes), so their
     // failures are collected and reported AFTER the guard is gone: ov2_set_err locks the same mutex when c == p->ctx.
@@ -1255,8 +1291,10 @@ ov2_status ov2_pyr_need_grad(ov2_ctx *c, const ov2_pyr *p)
     {
         std::lock_guard<std::mutex> g(p->ctx->mu);
         if (buf->grad_built) {
-            err = hipStreamWaitEvent(c->stream.h, buf->grad_ev, 0); what = "hipStreamWaitEvent(grad_ev)";
-        } else if ((err = hipStreamWaitEvent(c->stream, buf->ready_ev, 0)) != hipSuccess) {
+            err = wait_once(c, p, buf->grad_ev, &buf->grad_waited_seq); what = "hipStreamWaitEvent(grad_ev)";
+            // the planes were written behind the build: a stream behind them is behind the build as well
+            if (err == hipSuccess && c == p->ctx) buf->ready_waited_seq = buf->build_seq;
+        } else if ((err = wait_once(c, p, buf->ready_ev, &buf->ready_waited_seq)) != hipSuccess) {
             what = "hipStreamWaitEvent(ready_ev)";
         } else {
             const ov2_pyr_view &v = buf->view;
@@ -1267,7 +1305,10 @@ ov2_status ov2_pyr_need_grad(ov2_ctx *c, const ov2_pyr *p)
             }
             if ((err = hipGetLastError()) != hipSuccess) what = "level_kernel launch";
             else if ((err = hipEventRecord(buf->grad_ev, c->stream)) != hipSuccess) what = "hipEventRecord(grad_ev)";
-            else buf->grad_built = true;
+            else {
+                buf->grad_built = true;
+                if (c == p->ctx) buf->grad_waited_seq = buf->build_seq;   // written on this very stream: ordered without an event
+            }
         }
     }
     if (err != hipSuccess) return ov2_set_err(c, OV2_ERR_HIP, "%s failed: %s", what, hipGetErrorString(err));
@@ -1276,7 +1317,15 @@ ov2_status ov2_pyr_need_grad(ov2_ctx *c, const ov2_pyr *p)
 
 ov2_status ov2_pyr_wait_ready(ov2_ctx *c, const ov2_pyr *p)
 {
-    if (!p) return OV2_ERR_INVALID;
-    OV2_HIP(c, hipStreamWaitEvent(c->stream.h, p->buf->ready_ev, 0));   // ordering only: not a use of the main stream (ov2_main_stream)
+    if (!c || !p) return OV2_ERR_INVALID;
+    // the pool's events carry no system-scope fence (OV2_ORDER_EVENT_FLAGS) and the kernels read the buffer directly: a
+    // consumer context must sit on the device the pyramid was built on
+    if (c->device != p->ctx->device) return ov2_set_err(c, OV2_ERR_INVALID, "pyramid of device %d used on device %d", p->ctx->device, c->device);
+    hipError_t err;
+    {
+        std::lock_guard<std::mutex> g(p->ctx->mu);
+        err = wait_once(c, p, p->buf->ready_ev, &p->buf->ready_waited_seq);
+    }
+    if (err != hipSuccess) return ov2_set_err(c, OV2_ERR_HIP, "hipStreamWaitEvent(ready_ev) failed: %s", hipGetErrorString(err));
     return OV2_OK;
 }

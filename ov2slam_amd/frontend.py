@@ -64,6 +64,15 @@ class Context:
         _check(self.h, self.lib.ov2_ctx_pyr_pool_stats(self.h, out))
         return dict(zip(("alive", "pooled", "finished", "pending", "allocated"), (int(v) for v in out)))
 
+    def pyr_wait_stats(self):
+        """ov2_ctx_pyr_wait_stats / ov2_ctx_pyr_wait_found_complete: dict(issued, elided, found_complete) -- event waits for
+        pyramids enqueued on this context's main stream / left out because the stream was behind that build already or the
+        build had completed / the second kind alone, since the context was created"""
+        issued, elided, done = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.h, self.lib.ov2_ctx_pyr_wait_stats(self.h, C.byref(issued), C.byref(elided)))
+        _check(self.h, self.lib.ov2_ctx_pyr_wait_found_complete(self.h, C.byref(done)))
+        return dict(issued=int(issued.value), elided=int(elided.value), found_complete=int(done.value))
+
     def synchronize(self):
         _check(self.h, self.lib.ov2_ctx_synchronize(self.h))
 

@@ -3,16 +3,20 @@
 `bench.py --no-ba --steps 6 --warmup 2 --no-cpu-baseline --no-euroc-like --no-hard-stream` (a run of its own, no
 counters; the input of kf_overlap_trace.py) and prints
   per tracking or stereo call (a klt_compact_kernel and the tracking kernels that follow it): its start, the idle time of
-  its hardware queue in front of it, the end stamp of the last kernel of the pyramid build it consumes, and the
-  difference between that end and the call's start -- a call that starts a few us behind its build's end was waiting
-  for it;
+  its hardware queue in front of it, the number of wait packets the call put in front of its kernels, the end stamp of
+  the last kernel of the pyramid build it consumes, and the difference between that end and the call's start -- a call
+  that starts a few us behind its build's end was waiting for it;
   per keyframe period (stereo start to the next stereo start): the idle time of the tracking queue and of the pyramid
   queue, how much of the pyramid queue's idle time lies inside the stereo interval, the number of calls that start
   within 10 us of their build's end, the summed kernel durations by group and the hardware queues of each group.
 Builds and calls are paired by count, the order bench.py's Workload.step enqueues them in: every call consumes the next
 build (a tracking call the left pyramid of its frame, the stereo call of a keyframe the right one); a stereo call with
 no tracking call in front of it (the first frame) skips one build, its own left pyramid.
-usage: pyr_wait_trace.py <kernel_trace.csv or a directory holding one> [more traces ...]"""
+Wait packets are no kernels and leave no row in a kernel trace: the column follows from the same pairing and the pool's
+rule (ov2_pyr_wait_ready: the main stream waits once per build), so a call issues one packet per build it is the first
+to consume, the host running ahead of the device as it does in this bench.  ov2_ctx_pyr_wait_stats has the measured
+totals.  --every-wait gives the column for a library from before that rule: one packet per pyramid a call reads, two per call.
+usage: pyr_wait_trace.py [--every-wait] <kernel_trace.csv or a directory holding one> [more traces ...]"""
 import os
 import sys
 from collections import defaultdict
@@ -44,9 +48,10 @@ def busy_ns(spans, lo, hi):
     return total
 
 
-def analyse(rows):
+def analyse(rows, every_wait=False):
     """rows = load()'s (start ns, end ns, kernel, queue), sorted by start.  Returns (calls, periods, notes): a dict per
-    tracking / stereo call and per complete keyframe period, times in ns."""
+    tracking / stereo call and per complete keyframe period, times in ns.  every_wait: the library waits for every
+    pyramid a call reads (two packets per call) instead of once per build."""
     notes = []
     # ---- builds: runs of pyramid kernels, a new one at every CLAHE table kernel
     builds = []
@@ -73,8 +78,14 @@ def analyse(rows):
         if k < len(calls) and calls[k]["first"] == i:
             c = calls[k]
             c["idle_before"] = max(0, s - last_end[q]) if q in last_end else None
+            c["waits"] = 1                                           # the build paired with the call: first consumed here
             if c["stereo"] and not prev_was_tracking:
                 nb += 1                                              # its own left pyramid, consumed by no call before it
+                c["waits"] += 1
+            elif k == 0:
+                c["waits"] += 1                                      # a trace that opens with a tracking call: prev as well
+            if every_wait:
+                c["waits"] = 2
             c["build"] = nb if nb < len(builds) else None
             c["build_end"] = builds[nb]["end"] if nb < len(builds) else None
             c["gap"] = s - builds[nb]["end"] if nb < len(builds) else None
@@ -111,9 +122,9 @@ def analyse(rows):
     return calls, periods, notes
 
 
-def report(path, per_periods=3):
+def report(path, per_periods=3, every_wait=False):
     path, rows = load(path)
-    calls, periods, notes = analyse(rows)
+    calls, periods, notes = analyse(rows, every_wait)
     us = lambda ns: float("nan") if ns is None else ns / 1000.0
     t0 = rows[0][0] if rows else 0
     print(f"# {path}: {len(rows)} kernel launches, {len(calls)} tracking / stereo calls, {len(periods)} complete keyframe periods")
@@ -122,12 +133,12 @@ def report(path, per_periods=3):
     # the calls of the last complete periods: the steady state, past the warm-up
     shown = periods[-per_periods:]
     lo, hi = (shown[0]["start"], shown[-1]["start"] + shown[-1]["period"]) if shown else (0, 0)
-    print("call  kind      start_us  queue  idle_before_us  build  build_end_us  start_minus_build_end_us")
+    print("call  kind      start_us  queue  idle_before_us  wait_packets  build  build_end_us  start_minus_build_end_us")
     for n, c in enumerate(calls):
         if not lo <= c["start"] < hi:
             continue
         print(f"{n:4d}  {'stereo  ' if c['stereo'] else 'tracking'}  {us(c['start'] - t0):10.1f}  {c['queue']:>5}  "
-              f"{us(c['idle_before']):14.1f}  {str(c['build']):>5}  {us(None if c['build_end'] is None else c['build_end'] - t0):12.1f}  "
+              f"{us(c['idle_before']):14.1f}  {c['waits']:12d}  {str(c['build']):>5}  {us(None if c['build_end'] is None else c['build_end'] - t0):12.1f}  "
               f"{us(c['gap']):10.1f}")
     print("kf  period_us  stereo_us  track_idle_us  pyr_idle_us  pyr_idle_in_stereo_us  calls  within_10us | kernel us: "
           "tracking  detector  pyramid  other | queues: tracking / detector / pyramid")
@@ -153,11 +164,17 @@ def report(path, per_periods=3):
             print(f"plain tracking calls: {len(plain)}, start minus build end: lower quartile {gaps[len(gaps) // 4]:.1f} us, median "
                   f"{gaps[len(gaps) // 2]:.1f} us, upper quartile {gaps[3 * len(gaps) // 4]:.1f} us, within 10 us: "
                   f"{sum(1 for g in gaps if 0 <= g <= 10.0)}, within 20 us: {sum(1 for g in gaps if 0 <= g <= 20.0)}, idle in front: mean "
-                  f"{sum(us(c['idle_before']) for c in plain) / len(plain):.1f} us")
+                  f"{sum(us(c['idle_before']) for c in plain) / len(plain):.1f} us, wait packets per call: "
+                  f"{sum(c['waits'] for c in plain) / len(plain):.2f}")
+        st = [c for c in calls if c["stereo"] and c["start"] >= periods[0]["start"] and c["idle_before"] is not None]
+        if st:
+            print(f"stereo calls: {len(st)}, idle in front: mean {sum(us(c['idle_before']) for c in st) / len(st):.1f} us, wait packets "
+                  f"per call: {sum(c['waits'] for c in st) / len(st):.2f}")
 
 
 if __name__ == "__main__":
-    if len(sys.argv) < 2:
+    args = [a for a in sys.argv[1:] if a != "--every-wait"]
+    if not args:
         sys.exit(__doc__)
-    for p in sys.argv[1:]:
-        report(p)
+    for p in args:
+        report(p, every_wait="--every-wait" in sys.argv[1:])
