@@ -44,8 +44,9 @@ typedef struct ov2_pyr ov2_pyr;        /* ref-counted device pyramid(s): B x lev
 
 /* ---- context --------------------------------------------------------------------------------- */
 ov2_status ov2_ctx_create(int device, ov2_ctx **out);
-/* high_priority != 0 creates the ctx stream at the highest HIP stream priority: for the latency-critical, small-grid
- * caller (the Estimator / localBA thread) that shares the GPU with the front-end's large grids. */
+/* high_priority != 0 creates the ctx streams at the highest HIP stream priority and starts the context at wave priority
+ * OV2_WAVE_PRIO_HIGH (ov2_ctx_set_wave_prio): for the caller whose latency counts (the tracking thread) beside the
+ * contexts it shares the GPU with. */
 ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx **out);
 void ov2_ctx_destroy(ov2_ctx *ctx);
 const char *ov2_last_error(const ov2_ctx *ctx);
@@ -56,6 +57,14 @@ ov2_status ov2_ctx_synchronize(ov2_ctx *ctx);
  * it when the two provably touch different arrays (see both entry points).  Results and the ordering of the calls are the
  * same either way; off = the chain is enqueued on the context's main stream. */
 ov2_status ov2_ctx_set_kf_overlap(ov2_ctx *ctx, int on);
+/* Wave priority of the context's kernels, level = 0 .. 3 (anything else: OV2_ERR_INVALID, the level stays).  A SIMD
+ * arbitrates instruction issue between its resident waves by this priority, then by age, so where the waves of two
+ * contexts share a SIMD the higher level wins every conflict; the stream priority of ov2_ctx_create_ex only orders the
+ * dispatch of workgroups.  A context created with high_priority != 0 starts at OV2_WAVE_PRIO_HIGH, every other at 0.
+ * The level is read when a call enqueues its kernels and changes no result. */
+#define OV2_WAVE_PRIO_HIGH 2
+ov2_status ov2_ctx_set_wave_prio(ov2_ctx *ctx, int level);
+int ov2_ctx_get_wave_prio(const ov2_ctx *ctx);   /* -1 for a null context */
 /* Depth of the pyramid pool's ring, n = 1 .. 8 (anything else: OV2_ERR_INVALID, the depth stays; default 3; OV2_PYR_RING=n
  * in the environment starts a context with depth n).  Released pyramid buffers go back to a pool per context.  A build
  * takes a pooled buffer of its geometry whose readers have finished if there is one; otherwise it allocates a new buffer

@@ -24,6 +24,8 @@ SIGNATURES = {
     "ov2_status_string": (C.c_char_p, [C.c_int]),
     "ov2_ctx_synchronize": (C.c_int, [vp]),
     "ov2_ctx_set_kf_overlap": (C.c_int, [vp, C.c_int]),
+    "ov2_ctx_set_wave_prio": (C.c_int, [vp, C.c_int]),
+    "ov2_ctx_get_wave_prio": (C.c_int, [vp]),
     "ov2_ctx_set_pyr_ring": (C.c_int, [vp, C.c_int]),
     "ov2_ctx_pyr_pool_stats": (C.c_int, [vp, C.POINTER(C.c_int32)]),
     "ov2_ctx_pyr_wait_stats": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

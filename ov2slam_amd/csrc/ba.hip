@@ -115,6 +115,7 @@ struct ba_dev {
     // L2 re-solve on the SAME program: rows flagged by the robust pass are dead (zero residual and jacobian), blocks whose
     // rows all died stay out of the parameter norms (Ceres' reduced program would not contain them)
     int masked;
+    int wave_prio;             // wave priority of the solver's kernels: the launching context's level (ov2_ctx_set_wave_prio)
     unsigned char *dead;       // per sorted row
     unsigned char *e_dead;     // per landmark block: no live row left
     unsigned char *f_live;     // per pose block: some live row refers to it
@@ -244,10 +245,10 @@ __device__ inline void huber(double a, double s, double rho[3])
 // ------------------------------------------------------------------------------------------------------
 // K_EVAL: residual (+ jacobian), loss, corrector, Jacobi scaling; cost partial per workgroup
 
-// The solver's kernels are few, short waves that share their CUs with the front-end's long
-// KLT waves: raising the wave priority lets them win the SIMD issue arbitration instead of taking turns
-// (s_setprio is per wave and costs one scalar instruction; measured: 467 -> 475 LM it/s concurrent, front-end unchanged).
-#define BA_WAVE_PRIO() __builtin_amdgcn_s_setprio(3)
+// The solver's kernels run at the wave priority of the context that launches them (ov2_ctx::wave_prio, carried in
+// ba_dev): 0 for a normal-priority worker, so that on a SIMD it shares with a front-end wave the issue arbitration falls
+// back to age instead of going to the solver every time; the level of a high-priority front end for a high-priority
+// worker.  One scalar compare and at most one s_setprio per wave (ov2wave::set_wave_prio).
 
 // window that owns virtual block b: the last w with vb_start[w] <= b (windows without rows own no block)
 __device__ __forceinline__ int win_of_vblock(const int *__restrict__ vb_start, int B, int b)
@@ -277,7 +278,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
                                                       const double *__restrict__ lms, int mode, double huber_a,
                                                       double *__restrict__ part, const int *__restrict__ pose_off)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     __shared__ double sh[256];
     __shared__ double sRt_buf[EV_RT_MAX * EV_RT_STRIDE];
     __shared__ int sw;
@@ -451,7 +452,7 @@ __global__ __launch_bounds__(256) void ba_winreduce_kernel(ba_dev d, ba_lmopt o,
                                                            const double *__restrict__ part_model, int first,
                                                            double initial_radius, int next_round)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     __shared__ double sh[256];
     const int w = blockIdx.x;
     ba_win &W = d.W[w];
@@ -627,7 +628,7 @@ __global__ void ba_make_scale_kernel(ba_dev d)
 // this launch write.
 __global__ void ba_lmdiag_sinit_kernel(ba_dev d, double min_d, double max_d)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     const ba_win &W = d.W[blockIdx.y];
     if (!W.active) return;
     const int e = d.e, refresh_diag = W.refresh_diag;
@@ -713,7 +714,7 @@ __device__ __forceinline__ void invert_ete(const double *ete, double *ie)
 template <int GW>
 __global__ __launch_bounds__(256) void ba_colnorm16_kernel(ba_dev d, int mode)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     const int l = blockIdx.x * (256 / GW) + (int)(threadIdx.x / GW), sub = threadIdx.x % GW;
     const bool live = l < d.n_e && win_runs(d.W[d.win_of_e[l]], mode);
     const int e = d.e;
@@ -750,7 +751,7 @@ __global__ __launch_bounds__(256) void ba_colnorm16_kernel(ba_dev d, int mode)
 __global__ __launch_bounds__(256) void ba_pose_normal_kernel(ba_dev d, const int *__restrict__ pose_ptr,
                                                              const int *__restrict__ pose_ent, int mode)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     __shared__ double sh[4][27];
     const int f = blockIdx.x, tid = threadIdx.x;
     if (!win_runs(d.W[d.win_of_f[f]], mode)) return;
@@ -798,7 +799,7 @@ __global__ __launch_bounds__(256) void ba_pose_normal_kernel(ba_dev d, const int
 template <int E, int GW>
 __global__ __launch_bounds__(256) void ba_backsub16_kernel(ba_dev d, double *__restrict__ part)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     {   // the pose part of the step is -z (z = the reduced solve's result in rhs); written here to save a launch
         const int gi = blockIdx.x * 256 + threadIdx.x;
         if (gi < d.m) d.step[d.n_e * d.e + gi] = -d.rhs[gi];
@@ -915,7 +916,7 @@ __device__ __forceinline__ void chol_sqrt_rcp(double d, double &root, double &in
 #define CHOL_THREADS 512
 __global__ __launch_bounds__(CHOL_THREADS) void ba_chol_mfma_kernel(ba_dev d)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     constexpr int NB = 32, PS = NB + 1;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     ba_win &W = d.W[blockIdx.x];
@@ -1110,7 +1111,7 @@ static_assert(chol_mfma_lds(CHOL_MULTI_MIN - 1) <= 158 * 1024,
 
 __global__ __launch_bounds__(64) void ba_chol_panel_kernel(ba_dev d, double *__restrict__ Dpool, size_t dstride, int k0)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     constexpr int NB = CHOL_NB;
     __shared__ double LD[NB][NB + 1];
     ba_win &W = d.W[blockIdx.y];   // window = blockIdx.y; the x grid is sized for the largest window
@@ -1182,7 +1183,7 @@ __global__ __launch_bounds__(64) void ba_chol_panel_kernel(ba_dev d, double *__r
 
 __global__ __launch_bounds__(64) void ba_chol_syrk_kernel(ba_dev d, int k0)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     constexpr int NB = CHOL_NB;
     const ba_win &W = d.W[blockIdx.y];
     const int m = W.m;
@@ -1232,7 +1233,7 @@ __global__ __launch_bounds__(64) void ba_chol_syrk_kernel(ba_dev d, int k0)
 // nb x nb triangle with the block's columns (from the side buffer) in registers, pivots by v_readlane.  z in LDS.
 __global__ __launch_bounds__(256) void ba_chol_backward_kernel(ba_dev d, const double *__restrict__ Dpool, size_t dstride)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     constexpr int NB = CHOL_NB;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const ba_win &W = d.W[blockIdx.x];
@@ -1331,7 +1332,7 @@ __global__ __launch_bounds__(256) void ba_flag_kernel(ba_dev d, const double *__
                                                       double *__restrict__ chi2, unsigned char *__restrict__ depth,
                                                       unsigned char *__restrict__ active, unsigned char *__restrict__ outlier)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     const int row = blockIdx.x * 256 + threadIdx.x;
     const bool in = row < d.n_rows;
     const int w = d.row_win[in ? row : d.n_rows - 1];
@@ -1877,7 +1878,7 @@ __global__ __launch_bounds__(256) void bs_pent_sorted_kernel(const u64 *__restri
 template <int E, int GW>
 __global__ __launch_bounds__(256) void bs_landmark_kernel(ba_dev d, ba_cells C)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     const int grp = threadIdx.x / GW, sub = threadIdx.x % GW;
     const int l = blockIdx.x * (256 / GW) + grp;
     const bool live = l < d.n_e && d.W[d.win_of_e[l]].active;
@@ -2164,7 +2165,7 @@ __global__ __launch_bounds__(256) void bs_gather_kernel(ba_dev d, ba_cells C, co
                                                         const int *__restrict__ n_pairs, const u64 *__restrict__ pair_key,
                                                         const int *__restrict__ seg_start, const int2 *__restrict__ pent, int fb)
 {
-    BA_WAVE_PRIO();
+    ov2wave::set_wave_prio(d.wave_prio);
     __shared__ double red[4][27];
     if ((int)blockIdx.x < d.n_f) bs_diag_block<E>(d, C, pcell_ptr, blockIdx.x, red);
     else {
@@ -2416,6 +2417,7 @@ ov2_status build_program(ba_solver &S)
     memset(&d, 0, sizeof(d));
     const int e = S.e, B = S.B;
     d.e = e; d.B = B;
+    d.wave_prio = c->wave_prio;
     d.n_pose = S.n_pose; d.n_lm = S.n_lm;
     d.W = S.W; d.wc = S.wc;
     hipStream_t st = c->stream;

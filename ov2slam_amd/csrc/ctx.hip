@@ -48,6 +48,7 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     c->scratch_bytes = 0;
     c->tmp_img = nullptr;
     c->ktime_on = false;
+    c->wave_prio = high_priority ? OV2_WAVE_PRIO_HIGH : 0;
     c->klt_lanes = 0;
     c->knn_lanes = 0;
     c->knn_cus = 0;
@@ -156,6 +157,16 @@ extern "C" ov2_status ov2_ctx_set_kf_overlap(ov2_ctx *c, int on)
     c->kf_overlap = on ? 1 : 0;
     return OV2_OK;
 }
+
+extern "C" ov2_status ov2_ctx_set_wave_prio(ov2_ctx *c, int level)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (level < 0 || level > 3) return ov2_set_err(c, OV2_ERR_INVALID, "wave priority %d (0..3)", level);
+    c->wave_prio = level;
+    return OV2_OK;
+}
+
+extern "C" int ov2_ctx_get_wave_prio(const ov2_ctx *c) { return c ? c->wave_prio : -1; }
 
 void ov2_pyr_buf_free(ov2_pyr_buf *b)
 {

@@ -49,8 +49,9 @@ __device__ __forceinline__ void draw_disc(unsigned char *mask, int w, int h, int
 __global__ __launch_bounds__(256) void det_mask_kernel(const float2 *__restrict__ cur, const int *__restrict__ cur_img,
                                                        const unsigned char *__restrict__ valid, int n_cur, int cell,
                                                        int nwcells, int nhcells, unsigned char *__restrict__ occ_all,
-                                                       unsigned char *__restrict__ mask_all, int w, int h, disc_shape ds)
+                                                       unsigned char *__restrict__ mask_all, int w, int h, disc_shape ds, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     const int sub = threadIdx.x % DET_MASK_LANES;
     for (int k = blockIdx.x * DET_MASK_KPS + threadIdx.x / DET_MASK_LANES; k < n_cur; k += gridDim.x * DET_MASK_KPS) {
         if (valid && !valid[k]) continue;
@@ -99,8 +100,9 @@ __global__ __launch_bounds__(256) void det_worklist_kernel(int cell, int nwcells
                                                            const unsigned char *__restrict__ occ_all,
                                                            int2 *__restrict__ work /* 4 lists of list_cap */, int list_cap,
                                                            unsigned *__restrict__ wcount /* [4] */,
-                                                           int *__restrict__ nocc_all /* [images] */)
+                                                           int *__restrict__ nocc_all /* [images] */, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     __shared__ unsigned long long shw[4];
     __shared__ int base[4];
     const int b = blockIdx.x, nb = nwcells * nhcells, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -216,8 +218,9 @@ __global__ __launch_bounds__(256) void det_mineig_kernel(const unsigned char *__
                                                          const unsigned *__restrict__ work_count,
                                                          unsigned char *__restrict__ mask_all, disc_shape ds, int rx,
                                                          int ry, int rw, int rh, const double *__restrict__ quality_all,
-                                                         det_out *__restrict__ out_all)
+                                                         det_out *__restrict__ out_all, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     __shared__ unsigned long long shk[4];
     if (blockIdx.x >= *work_count) return;   // the grid is an upper bound; the list length lives on the device
@@ -320,8 +323,9 @@ __global__ __launch_bounds__(256) void det_fast_kernel(const unsigned char *__re
                                                        const unsigned *__restrict__ work_count,
                                                        unsigned char *__restrict__ mask_all, disc_shape ds,
                                                        const double *__restrict__ thresh_all,
-                                                       det_out *__restrict__ out_all)
+                                                       det_out *__restrict__ out_all, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     __shared__ unsigned long long shk[4];
     if (blockIdx.x >= *work_count) return;
@@ -377,8 +381,9 @@ __global__ __launch_bounds__(256) void det_assemble_kernel(int mode, int nwcells
                                                            const det_out *__restrict__ out_all, double *__restrict__ thresh,
                                                            int *__restrict__ n_out, float2 *__restrict__ out_xy, int out_cap,
                                                            int *__restrict__ pt_ref, int *__restrict__ pt_img,
-                                                           unsigned *__restrict__ npts)
+                                                           unsigned *__restrict__ npts, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     __shared__ int sh4[4];
     __shared__ int gbase;
     const int b = blockIdx.x, nb = nwcells * nhcells, tid = threadIdx.x;
@@ -459,8 +464,9 @@ __global__ __launch_bounds__(64) void subpix_kernel(const unsigned char *__restr
                                                     const int *__restrict__ pt_img, const int *__restrict__ pt_ref,
                                                     const unsigned *__restrict__ npts, int istride, int w, int h,
                                                     float2 *__restrict__ pts, int max_iter, double eps2,
-                                                    subpix_weights<HW> wmask)
+                                                    subpix_weights<HW> wmask, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     const int n = (int)*npts;                       // the grid is an upper bound; the point count lives on the device
     if ((int)blockIdx.x * 4 >= n) return;
     constexpr int WIN = 2 * HW + 1, BW = WIN + 2, SW = BW + 1, NT = WIN * WIN, NK = (NT + 15) / 16;
@@ -649,8 +655,8 @@ extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, 
     const disc_shape ds = make_disc(cell / 4);
     if (n_cur > 0)
         OV2_LAUNCH_ON(c, OV2_K_DETECT + 1, st, det_mask_kernel, dim3(std::min((n_cur + DET_MASK_KPS - 1) / DET_MASK_KPS, 65536)), dim3(256), 0,
-                   st, reinterpret_cast<const float2 *>(d_cur_xy), d_cur_img, d_cur_valid, n_cur, cell, nw, nh, occ, mask, w, h, ds);
-    OV2_LAUNCH_ON(c, OV2_K_DETECT + 5, st, det_worklist_kernel, dim3(B), dim3(256), 0, st, cell, nw, nh, w, h, occ, dwork, list_cap, cnt, nocc);
+                   st, reinterpret_cast<const float2 *>(d_cur_xy), d_cur_img, d_cur_valid, n_cur, cell, nw, nh, occ, mask, w, h, ds, c->wave_prio);
+    OV2_LAUNCH_ON(c, OV2_K_DETECT + 5, st, det_worklist_kernel, dim3(B), dim3(256), 0, st, cell, nw, nh, w, h, occ, dwork, list_cap, cnt, nocc, c->wave_prio);
     const int nthreads = (cell * cell <= 256) ? 64 : 256;   // small cells: one wave walks the cell
     const size_t mineig_lds = (size_t)(cell + 2) * (cell + 2) * 10 + (size_t)cell * cell * 5;
     for (int colour = 0; colour < 4; ++colour) {
@@ -661,17 +667,17 @@ extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, 
         const int2 *wl = dwork + (size_t)colour * list_cap;
         if (mode == OV2_DETECT_MINEIG)
             OV2_LAUNCH_ON(c, OV2_K_DETECT, st, det_mineig_kernel, dim3(nitems), dim3(nthreads), mineig_lds, st, img,
-                       L.img_bstride, L.istride, w, h, cell, nw, nh, wl, cnt + colour, mask, ds, rx, ry, rw, rh, d_thresh, dout);
+                       L.img_bstride, L.istride, w, h, cell, nw, nh, wl, cnt + colour, mask, ds, rx, ry, rw, rh, d_thresh, dout, c->wave_prio);
         else
             OV2_LAUNCH_ON(c, OV2_K_DETECT, st, det_fast_kernel, dim3(nitems), dim3(nthreads), (size_t)cell * cell * 4, st,
-                       img, L.img_bstride, L.istride, w, h, cell, nw, nh, wl, cnt + colour, mask, ds, d_thresh, dout);
+                       img, L.img_bstride, L.istride, w, h, cell, nw, nh, wl, cnt + colour, mask, ds, d_thresh, dout, c->wave_prio);
     }
     OV2_LAUNCH_ON(c, OV2_K_DETECT + 5, st, det_assemble_kernel, dim3(B), dim3(256), 0, st, mode, nw, nh, nocc, dout, d_thresh, d_n_out,
-               reinterpret_cast<float2 *>(d_out_xy), out_cap, pt_ref, pt_img, cnt + 4);
+               reinterpret_cast<float2 *>(d_out_xy), out_cap, pt_ref, pt_img, cnt + 4, c->wave_prio);
     if (do_subpix) {
         static const subpix_weights<3> wts = make_subpix_weights<3>();   // depend on the window alone: formed once
         OV2_LAUNCH_ON(c, OV2_K_DETECT + 2, st, subpix_kernel<3>, dim3(((size_t)nb * B + 3) / 4), dim3(64), 0, st, img, L.img_bstride,
-                   pt_img, pt_ref, cnt + 4, L.istride, w, h, reinterpret_cast<float2 *>(d_out_xy), 30, 0.01 * 0.01, wts);
+                   pt_img, pt_ref, cnt + 4, L.istride, w, h, reinterpret_cast<float2 *>(d_out_xy), 30, 0.01 * 0.01, wts, c->wave_prio);
     }
     const hipError_t le = hipGetLastError();
     if (side) {   // joined even behind a failed launch: nothing may stay behind on the side stream unordered

@@ -30,6 +30,7 @@ namespace {
 
 struct klt_params {
     int win, nlevels, max_iter;
+    int wave_prio;   // the launching context's wave priority (ov2_ctx_set_wave_prio)
     double eps2;     // criteria.epsilon^2 (double, as in calcOpticalFlowPyrLK)
     float err_th;    // nklt_err
     double fb_th;    // fmax_fbklt_dist promoted to double for the cv::norm comparison
@@ -872,6 +873,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
                                                     const int *__restrict__ img_idx, unsigned *__restrict__ iters)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[klt_smem<WIN, KLT_GL>::BYTES];
+    ov2wave::set_wave_prio(P.wave_prio);
     using M = klt_map<KLT_GL>;
     constexpr int KLT_KPW = M::KPW;
     const int slot = M::slot((int)threadIdx.x), sub = M::sub((int)threadIdx.x), i = blockIdx.x * KLT_KPW + slot;
@@ -905,8 +907,9 @@ __global__ __launch_bounds__(256) void klt_compact_kernel(int n, int pass, const
                                                           const unsigned char *__restrict__ out_status,
                                                           unsigned *__restrict__ iters, int *__restrict__ list_a,
                                                           int *__restrict__ list_b, unsigned *__restrict__ cnt,
-                                                          int *__restrict__ p3p_req, int batch)
+                                                          int *__restrict__ p3p_req, int batch, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     __shared__ int wsum[2][4];
     __shared__ int wbase[2];
     const int f = blockIdx.x * 256 + threadIdx.x;
@@ -994,6 +997,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
     const int g = is_a ? (int)blockIdx.x - groups_b : (int)blockIdx.x;
     const int total = is_a ? total_a : total_b;
     if (g * KLT_KPW >= total) return;
+    ov2wave::set_wave_prio(P.wave_prio);   // behind the return: an empty workgroup retires without it
     const int slot = M::slot((int)threadIdx.x), sub = M::sub((int)threadIdx.x), idx = g * KLT_KPW + slot;
     const bool lane_ok = M::lane_ok((int)threadIdx.x);
     const bool act = idx < total && lane_ok;
@@ -1074,6 +1078,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
     const int g = is_b ? (int)blockIdx.x : (int)blockIdx.x - groups_b;
     const int total = is_b ? total_b : (int)cnt[2];
     if (g * KLT_KPW >= total) return;
+    ov2wave::set_wave_prio(P.wave_prio);   // behind the return: an empty workgroup retires without it
     const int idx = g * KLT_KPW + slot;
     const bool act = idx < total && lane_ok;
     const int i = (is_b ? list_b : list_c)[idx < total ? idx : total - 1];
@@ -1130,6 +1135,7 @@ ov2_status make_params(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr *cur, int 
     if (nlevels < 0) return ov2_set_err(c, OV2_ERR_INVALID, "nlevels < 0");
     if (a.nlevels < nlevels + 1) nlevels = a.nlevels - 1;  // :50-52
     P->win = win;
+    P->wave_prio = c->wave_prio;
     P->nlevels = nlevels;
     P->max_iter = max_iter < 0 ? 0 : (max_iter > 100 ? 100 : max_iter);  // TermCriteria clamps
     double e = (double)eps;
@@ -1285,7 +1291,7 @@ ov2_status ov2_klt_two_stage_dev(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr 
         /* two disjoint lists of the n keypoints: groups of the one + groups of the other <= ceil(n / KPW) + 2 */ \
         const dim3 tgrid((n + klt_map<G>::KPW - 1) / klt_map<G>::KPW + 2);                                      \
         OV2_LAUNCH(c, OV2_K_DETECT + 4, klt_compact_kernel, cgrid, dim3(256), 0, c->stream, n, 1, d_has_prior,  \
-                   d_out_status, d_iters, list_a, list_b, live_cnt, d_p3p_req, B);                              \
+                   d_out_status, d_iters, list_a, list_b, live_cnt, d_p3p_req, B, P.wave_prio);                 \
         OV2_LAUNCH(c, OV2_K_KLT_STAGE1, (klt_stage1_kernel<W, G>), tgrid, dim3(64), 0, c->stream,               \
                    prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps),              \
                    reinterpret_cast<const float2 *>(d_prior), d_img_idx, reinterpret_cast<float2 *>(d_out_xy),  \

@@ -140,6 +140,7 @@ struct ov2_ctx {
     bool klt_counts_dirty;               // a call did not run to its end: both buffers are zeroed again
     hipStream_t ba_copy_stream;          // second half of a batch upload (measurements) travels here while the program build sorts
     hipEvent_t ba_copy_ev[2];            // [0] head uploaded (main stream), [1] measurements uploaded (copy stream)
+    int wave_prio;                       // ov2_ctx_set_wave_prio: 0..3, the s_setprio level of every kernel this ctx launches that takes one
     int klt_lanes;                       // ov2_klt_set_lanes: 0 = by call size, 3 / 8 / 16 = forced lanes per keypoint
     int knn_lanes;                       // ov2_knn_set_lanes: 0 = by call size, 1 / 4 / 16 / 64 = forced lanes per query
     int knn_cus;                         // compute units of the device (read on first use by the matcher's automatic choice)

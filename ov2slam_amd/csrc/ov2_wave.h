@@ -117,6 +117,17 @@ __device__ inline double block_sum_256(double v, double *sh)
     return sh[0];
 }
 
+// Raises the calling wave to priority `level` (0..3; 0 issues nothing) for the rest of its life.  s_setprio takes an
+// immediate and ignores EXEC, so the level is forced wave-uniform first and the choice among the three instructions is
+// made by scalar compares and branches: a guard lowered through EXEC would run every s_setprio it guards.
+__device__ __forceinline__ void set_wave_prio(int level)
+{
+    const int l = __builtin_amdgcn_readfirstlane(level);
+    if (l == 1) __builtin_amdgcn_s_setprio(1);
+    else if (l == 2) __builtin_amdgcn_s_setprio(2);
+    else if (l == 3) __builtin_amdgcn_s_setprio(3);
+}
+
 // cv::BORDER_REFLECT_101 index; one reflection is enough for |overshoot| < n (callers guarantee it)
 __device__ __forceinline__ int reflect101(int i, int n)
 {

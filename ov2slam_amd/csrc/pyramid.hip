@@ -58,8 +58,9 @@ __device__ __forceinline__ void store_reflections(unsigned char *plane, int istr
 __global__ __launch_bounds__(256) void clahe_lut_wave_kernel(const unsigned char *__restrict__ src, int w, int h,
                                                              int sstride, size_t sbstride, int tiles_x, int tiles_y,
                                                              int tw, int th, int clip_limit, float lut_scale,
-                                                             unsigned char *__restrict__ lut)
+                                                             unsigned char *__restrict__ lut, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     __shared__ int hist_all[4][256 * CLW_COPIES];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int tile = blockIdx.x * 4 + wv, b = blockIdx.y;
@@ -198,8 +199,9 @@ __global__ __launch_bounds__(256) void clahe_lut_wave_kernel(const unsigned char
 __global__ __launch_bounds__(64) void level0_kernel(const unsigned char *__restrict__ src, int w, int h, int sstride,
                                                     size_t sbstride, int use_clahe,
                                                     const unsigned char *__restrict__ lut, int tiles_x, int tiles_y,
-                                                    float inv_tw, float inv_th, ov2_pyr_view pv)
+                                                    float inv_tw, float inv_th, ov2_pyr_view pv, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     const int x0 = (blockIdx.x * 64 + threadIdx.x) * 4;
     const int y = blockIdx.y, b = blockIdx.z;
     if (x0 >= w) return;
@@ -263,8 +265,9 @@ __global__ __launch_bounds__(256) void level0_clahe_tiled_kernel(const unsigned 
                                                                  int sstride, size_t sbstride,
                                                                  const unsigned char *__restrict__ lut, int tiles_x,
                                                                  int tiles_y, float inv_tw, float inv_th, int ncx_max,
-                                                                 ov2_pyr_view pv)
+                                                                 ov2_pyr_view pv, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     // tile = 64 x 64 px; a thread owns 4 px in each of 4 rows (y0+ty, +16, +32, +48) and issues its 4 source loads
     // back to back: the kernel is bound by the number of memory round trips per resident wave, not by bandwidth.
     extern __shared__ __attribute__((aligned(16))) unsigned char llds[];
@@ -361,8 +364,9 @@ __global__ __launch_bounds__(256) void level0_clahe_tiled_kernel(const unsigned 
 #define LDS_ROWS (TILE_H + 4)  // rows y0-2 .. y0+TILE_H+1
 #define LDS_DW 18              // dwords per row: cols x0-4 .. x0+67
 
-__global__ __launch_bounds__(256) void level_kernel(ov2_pyr_view pv, int l, int has_next, int do_scharr)
+__global__ __launch_bounds__(256) void level_kernel(ov2_pyr_view pv, int l, int has_next, int do_scharr, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     __shared__ unsigned int tile[LDS_ROWS][LDS_DW];
     const int tid = threadIdx.x;
     const int b = blockIdx.z;
@@ -477,8 +481,9 @@ __global__ __launch_bounds__(256) void level_kernel(ov2_pyr_view pv, int l, int 
 #define PD_ROWS (PD_TH + 4)       // rows y0-2 .. y0+PD_TH+1
 #define PD_DW (PD_TW / 4 + 4)     // dwords per row: cols x0-4 .. x0+PD_TW+11
 
-__global__ __launch_bounds__(256) void pyrdown_kernel(ov2_pyr_view pv, int l)
+__global__ __launch_bounds__(256) void pyrdown_kernel(ov2_pyr_view pv, int l, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     __shared__ __attribute__((aligned(16))) unsigned int tile[PD_ROWS][PD_DW];
     const int tid = threadIdx.x, b = blockIdx.z;
     const int x0 = blockIdx.x * PD_TW, y0 = blockIdx.y * PD_TH;
@@ -613,8 +618,9 @@ __device__ __forceinline__ void lds_border(const unsigned char *src, int sstride
     }
 }
 
-__global__ __launch_bounds__(256) void pyrdown2_kernel(ov2_pyr_view pv, int l)
+__global__ __launch_bounds__(256) void pyrdown2_kernel(ov2_pyr_view pv, int l, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     __shared__ __attribute__((aligned(16))) unsigned int t0[P2_R0][P2_DW0];
     __shared__ __attribute__((aligned(16))) unsigned int t1[P2_R1][P2_DW1];
     __shared__ __attribute__((aligned(16))) unsigned int t2[P2_TH][P2_TW / 4];   // the level-(l+2) tile, for its border
@@ -851,8 +857,9 @@ __device__ __forceinline__ void l0_border(int w, int h, unsigned char *__restric
 __global__ __launch_bounds__(256) void level0_clahe_pyrdown_kernel(const unsigned char *__restrict__ src, int w, int h,
                                                                    int sstride, size_t sbstride,
                                                                    const unsigned char *__restrict__ lut, int tiles_x,
-                                                                   int tiles_y, float inv_tw, float inv_th, ov2_pyr_view pv)
+                                                                   int tiles_y, float inv_tw, float inv_th, ov2_pyr_view pv, int wave_prio)
 {
+    ov2wave::set_wave_prio(wave_prio);
     extern __shared__ __attribute__((aligned(16))) unsigned int fl[];
     unsigned int (*tile)[L0_DW] = reinterpret_cast<unsigned int (*)[L0_DW]>(fl);   // L0_ROWS x L0_DW
     uint4 *rt_all = reinterpret_cast<uint4 *>(fl + L0_ROWS * L0_DW);              // 4 waves x L0_ROWS row records
@@ -1092,7 +1099,7 @@ extern "C" ov2_status ov2_pyramid_build_images(ov2_ctx *c, const ov2_images *im,
         inv_tw = 1.0f / (float)tw;
         inv_th = 1.0f / (float)th;
         OV2_LAUNCH_ON(c, OV2_K_CLAHE_LUT, sp, clahe_lut_wave_kernel, dim3((tiles_x * tiles_y + 3) / 4, B), dim3(256), 0, sp, im->base, im->w,
-                           im->h, im->stride, im->bstride, tiles_x, tiles_y, tw, th, clip_limit, lut_scale, buf->lut);
+                           im->h, im->stride, im->bstride, tiles_x, tiles_y, tw, th, clip_limit, lut_scale, buf->lut, c->wave_prio);
     }
     int ncx_max = 0, ncy_max = 0;
     size_t l0_lds = 0;
@@ -1114,15 +1121,15 @@ extern "C" ov2_status ov2_pyramid_build_images(ov2_ctx *c, const ov2_images *im,
     if (use_clahe && v.nlevels >= 2 && fused_lds <= 64 * 1024 && im->w >= 8 && im->h >= 8) {
         OV2_LAUNCH_ON(c, OV2_K_LEVEL0, sp, level0_clahe_pyrdown_kernel, dim3((im->w + L0_TW - 1) / L0_TW, (im->h + L0_TH - 1) / L0_TH, B),
                       dim3(256), fused_lds, sp, im->base, im->w, im->h, im->stride, im->bstride, buf->lut, tiles_x, tiles_y, inv_tw,
-                      inv_th, v);
+                      inv_th, v, c->wave_prio);
         first_down = 1;
     } else if (use_clahe && l0_lds <= 48 * 1024)
         OV2_LAUNCH_ON(c, OV2_K_LEVEL0, sp, level0_clahe_tiled_kernel, dim3((im->w + 63) / 64, (im->h + 63) / 64, B), dim3(256), l0_lds,
                    sp, im->base, im->w, im->h, im->stride, im->bstride, buf->lut, tiles_x, tiles_y, inv_tw, inv_th,
-                   ncx_max, v);
+                   ncx_max, v, c->wave_prio);
     else {
         OV2_LAUNCH_ON(c, OV2_K_LEVEL0, sp, level0_kernel, dim3((im->w + 255) / 256, im->h, B), dim3(64), 0, sp, im->base, im->w,
-                      im->h, im->stride, im->bstride, use_clahe, buf->lut, tiles_x, tiles_y, inv_tw, inv_th, v);
+                      im->h, im->stride, im->bstride, use_clahe, buf->lut, tiles_x, tiles_y, inv_tw, inv_th, v, c->wave_prio);
     }
     // pyrDown chain only: the gradient planes are written when a consumer asks for them (ov2_pyr_need_grad)
     // a new build: whatever the main stream waited for in this buffer was an earlier one
@@ -1132,12 +1139,12 @@ extern "C" ov2_status ov2_pyramid_build_images(ov2_ctx *c, const ov2_images *im,
     for (; l + 2 < v.nlevels; l += 2) {
         const ov2_level_desc &M = v.lv[l + 2];
         OV2_LAUNCH_ON(c, OV2_K_LEVEL, sp, pyrdown2_kernel, dim3((M.w + P2_TW - 1) / P2_TW, (M.h + P2_TH - 1) / P2_TH, B), dim3(256), 0,
-                      sp, v, l);
+                      sp, v, l, c->wave_prio);
     }
     for (; l + 1 < v.nlevels; ++l) {
         const ov2_level_desc &L = v.lv[l];
         OV2_LAUNCH_ON(c, OV2_K_LEVEL, sp, pyrdown_kernel, dim3((L.w + PD_TW - 1) / PD_TW, (L.h + PD_TH - 1) / PD_TH, B), dim3(256), 0, sp,
-                      v, l);
+                      v, l, c->wave_prio);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -1301,7 +1308,7 @@ ov2_status ov2_pyr_need_grad(ov2_ctx *c, const ov2_pyr *p)
             for (int l = 0; l < v.nlevels; ++l) {
                 const ov2_level_desc &L = v.lv[l];
                 OV2_LAUNCH(c, OV2_K_LEVEL, level_kernel, dim3((L.w + TILE_W - 1) / TILE_W, (L.h + TILE_H - 1) / TILE_H, buf->batch), dim3(256), 0,
-                           c->stream, v, l, 0, 1);
+                           c->stream, v, l, 0, 1, c->wave_prio);
             }
             if ((err = hipGetLastError()) != hipSuccess) what = "level_kernel launch";
             else if ((err = hipEventRecord(buf->grad_ev, c->stream)) != hipSuccess) what = "hipEventRecord(grad_ev)";

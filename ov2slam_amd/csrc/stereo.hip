@@ -7,6 +7,7 @@
 // the gate's float expressions are evaluated in the oracle's order (-ffp-contract=off).
 #include "ov2_internal.h"
 #include "ov2_cam.h"
+#include "ov2_wave.h"
 
 namespace {
 
@@ -175,6 +176,7 @@ __global__ __launch_bounds__(64) void sad_kernel(ov2_pyr_view lv, ov2_pyr_view r
 struct gate_params {
     double F[9];
     int rectified;
+    int wave_prio;        // the launching context's wave priority (ov2_ctx_set_wave_prio)
     ov2_cam_model rcam;   // the right camera's lens model (model 0: undistortImagePoint is the identity)
 };
 
@@ -184,6 +186,7 @@ __global__ __launch_bounds__(256) void epi_gate_kernel(int n, gate_params G, con
                                                        const float2 *__restrict__ lunpx, float2 *__restrict__ rxy,
                                                        unsigned char *__restrict__ status)
 {
+    ov2wave::set_wave_prio(G.wave_prio);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n || !status[i]) return;
     const float2 l = lunpx ? lunpx[i] : kps[i];
@@ -288,6 +291,7 @@ extern "C" ov2_status ov2_stereo_matching_dev(ov2_ctx *c, const ov2_pyr *left, c
     gate_params G;
     for (int k = 0; k < 9; ++k) G.F[k] = F_rl ? F_rl[k] : 0.0;
     G.rectified = rectified ? 1 : 0;
+    G.wave_prio = c->wave_prio;
     G.rcam = ov2_cam_normalised(right_cam);
     if (G.rcam.model < 0 || G.rcam.model > 2) return ov2_set_err(c, OV2_ERR_INVALID, "unknown lens model %d", G.rcam.model);
     OV2_LAUNCH(c, K_GATE, epi_gate_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, G,

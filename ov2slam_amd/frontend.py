@@ -13,6 +13,9 @@ import numpy as np
 from . import _lib
 
 
+WAVE_PRIO_HIGH = 2   # OV2_WAVE_PRIO_HIGH of include/ov2slam_hip.h: the wave priority a high-priority context starts at
+
+
 def _check(ctx_handle, status):
     if status != 0:
         lib = _lib.load()
@@ -51,6 +54,14 @@ class Context:
     def set_kf_overlap(self, on):
         """ov2_ctx_set_kf_overlap: the keyframe detector chain on the side stream, beside stereo matching (default on)"""
         _check(self.h, self.lib.ov2_ctx_set_kf_overlap(self.h, int(bool(on))))
+
+    def set_wave_prio(self, level):
+        """ov2_ctx_set_wave_prio: s_setprio level (0 .. 3) of the kernels this context launches from now on"""
+        _check(self.h, self.lib.ov2_ctx_set_wave_prio(self.h, int(level)))
+
+    def get_wave_prio(self):
+        """ov2_ctx_get_wave_prio: OV2_WAVE_PRIO_HIGH on a fresh high-priority context, 0 on any other"""
+        return int(self.lib.ov2_ctx_get_wave_prio(self.h))
 
     def set_pyr_ring(self, n):
         """ov2_ctx_set_pyr_ring: released pyramid buffers of one geometry, readers still pending, that the pool holds before
