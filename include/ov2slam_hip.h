@@ -186,6 +186,12 @@ ov2_status ov2_klt_tracking_frame_dev(ov2_ctx *ctx, const ov2_pyr *prev, const o
  * call size (21 keypoints per wave, Scharr derivatives formed in the kernel, no gradient planes read);
  * other windows 8 lanes from 65 536 keypoints on, 16 below.  All mappings give bit-identical results. */
 ov2_status ov2_klt_set_lanes(ov2_ctx *ctx, int lanes);
+/* Tuning / test knob of ov2_stereo_matching(_dev): the keypoints without a prior descend the whole pyramid, and that
+ * descent is cut in two at level k -- the first tracking launch runs their levels nlevels .. k + 1 beside the keypoints
+ * with a prior, the second launch levels k .. 0, the gates and the backward pass beside the re-tracked failures.  k >=
+ * the call's level count (after the clamp to the pyramid's levels) runs the whole descent in the second launch; k < 0
+ * (default) leaves the choice to the library.  Every k gives bit-identical results. */
+ov2_status ov2_klt_set_stereo_split(ov2_ctx *ctx, int k);
 
 /* ---- stereo matching (keyframe rate) -------------------------------------------------------------- */
 /* Replaces FeatureTracker::getLineMinSAD(iml, imr, pt, nwinsize, xprior, l1err, bgoleft) (include/feature_tracker.hpp:50,

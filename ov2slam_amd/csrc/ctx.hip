@@ -50,6 +50,7 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     c->ktime_on = false;
     c->wave_prio = high_priority ? OV2_WAVE_PRIO_HIGH : 0;
     c->klt_lanes = 0;
+    c->klt_stereo_split = -1;
     c->knn_lanes = 0;
     c->knn_cus = 0;
     c->lcd_splits = 0;

@@ -814,17 +814,33 @@ __device__ __forceinline__ int lk_pass(const level_ptrs &I, const level_ptrs &J,
     }
 }
 
+//
+// The level loop can be cut in two at a pyramid level (stereoMatching's list B, klt_stage1_kernel / klt_stage2_kernel): the
+// "upper" form runs levels nlevels .. l_lo > 0 and hands back what the loop carries between passes (forward position in
+// fx / fy, err_out, work = iterations | passes << 16: the 16 bytes of a klt_handover record; status is only ever cleared on
+// level 0, which the upper form never reaches), the "resume" form starts at l_hi < nlevels from such a record and finishes as the whole descent does.  Every
+// pass restarts with run = act and the first resumed pass takes the `nx_io * 2` arm (max_level stays nlevels), so the two
+// halves execute the passes of the unsplit loop one for one.  The whole descent is l_hi = nlevels, l_lo = 0 from an empty
+// record.
+struct __attribute__((aligned(16))) klt_handover { float fx, fy, err; unsigned work; };
+
 template <int WIN, int GL>
 __device__ __forceinline__ int fb_track(const ov2_pyr_view &pv, const ov2_pyr_view &cv, int b, bool act, float kx,
                                           float ky, float &fx, float &fy, const klt_params &P, int nlevels, int sub,
-                                          bool lane_ok, unsigned &work, unsigned char *smem, int slot)
+                                          bool lane_ok, unsigned &work, unsigned char *smem, int slot,
+                                          int l_hi, int l_lo, float err0, unsigned work0, float &err_out)
 {
     int status = 1;
-    float err = 0.f;
-    unsigned it = 0, passes = 0;
-    for (int l = nlevels; l >= 0; --l) {
+    float err = err0;
+    unsigned it = work0 & 0xffffu, passes = work0 >> 16;
+    for (int l = l_hi; l >= l_lo; --l) {
         const level_ptrs I = level_of(pv, l, b), J = level_of(cv, l, b);
         it += lk_pass<WIN, GL>(I, J, pv.pad, l, nlevels, act, kx, ky, fx, fy, status, err, P, sub, lane_ok, passes, smem, slot);
+    }
+    if (l_lo > 0) {   // upper form (uniform over the workgroup): the caller stores the record
+        work = it | (passes << 16);
+        err_out = err;
+        return 0;
     }
     // gates of src/feature_tracker.cpp:79-101
     const int W0 = cv.lv[0].w, H0 = cv.lv[0].h;
@@ -849,11 +865,31 @@ __device__ __forceinline__ int fb_track(const ov2_pyr_view &pv, const ov2_pyr_vi
     return ok;
 }
 
+// the whole descent
+template <int WIN, int GL>
+__device__ __forceinline__ int fb_track(const ov2_pyr_view &pv, const ov2_pyr_view &cv, int b, bool act, float kx,
+                                          float ky, float &fx, float &fy, const klt_params &P, int nlevels, int sub,
+                                          bool lane_ok, unsigned &work, unsigned char *smem, int slot)
+{
+    float err;
+    return fb_track<WIN, GL>(pv, cv, b, act, kx, ky, fx, fy, P, nlevels, sub, lane_ok, work, smem, slot, nlevels, 0, 0.f, 0u, err);
+}
+
 // Lanes per keypoint, chosen per call: 8 lanes (eight keypoints per wave) halve the wave-instructions per keypoint and
 // win once the launch holds several rounds of waves (measured: 106k vs 103k frames/s at 64 x 2048 keypoints per call);
 // 16 lanes (four per wave) give twice as many, shorter waves and win while the launch is latency-bound (68k vs 60k
 // frames/s at 16 x 2048).
 #define KLT_GL8_MIN_KPS 65536
+// stereoMatching's split descent: the level list B resumes at in the second launch when ov2_klt_set_stereo_split leaves the
+// choice here (DESIGN.md section 7 "Stereo matching: split the no-prior descent across both launches")
+#ifndef KLT_STEREO_SPLIT_DEFAULT
+#define KLT_STEREO_SPLIT_DEFAULT 0
+#endif
+// order of the second launch's two segments when the descent is split: 1 = list C (whole descent) in front of the resumed
+// list B, 0 = B in front as in the unsplit launch (measured against each other, same section)
+#ifndef KLT_SPLIT_C_FIRST
+#define KLT_SPLIT_C_FIRST 1
+#endif
 // occupancy bounds handed to the register allocator (min, max waves per SIMD).  Measured on 64 x 2048 keypoints,
 // first launch: register-squeezed to 6-7 waves 228 us, unconstrained (5 waves) 209 us, capped at 3 / 4 / 5 waves
 // 204 / 203.5 / 205 us -- the kernel is issue-bound, extra waves only add pressure, so the allocator gets room.
@@ -902,7 +938,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
 // pass 1 lists the keypoints with a prior (list A, 2 pyramid levels) and those without (list B, full pyramid: they do
 // not depend on the outcome of the first group, so for kltTracking both groups run in ONE launch); the failures of
 // list A (list C) are re-tracked on the full pyramid once the per-image tally of list A is complete (the 33 % rule).
-// stereoMatching has no such rule and long list-B waves: there list B runs in the second launch, in front of list C.
+// stereoMatching has no such rule and long list-B waves: there list B's descent is cut in two at a pyramid level, its upper
+// levels run in the first launch beside list A and the rest in the second launch behind list C (unsplit: all of it in the
+// second launch, in front of list C).
 __global__ __launch_bounds__(256) void klt_compact_kernel(int n, int pass, const unsigned char *__restrict__ has_prior,
                                                           const unsigned char *__restrict__ out_status,
                                                           unsigned *__restrict__ iters, int *__restrict__ list_a,
@@ -973,8 +1011,10 @@ __device__ __forceinline__ void klt_stage1_finish(bool mine, bool is_a, int i, i
 }
 
 // first launch: list A = keypoints with a prior on 2 pyramid levels (nbpyrlvl = 1, src/visual_front_end.cpp:190),
-// list B = keypoints without prior on the full pyramid from their own position (:237-270, vpriors = vkps)
-template <int WIN, int KLT_GL>
+// list B = keypoints without prior on the full pyramid from their own position (:237-270, vpriors = vkps).
+// SPLIT = stereoMatching's call with the split descent: an instantiation of its own, so that the plain call's kernel (the
+// dominant kernel of every frame) carries none of it
+template <int WIN, int KLT_GL, bool SPLIT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WIN, KLT_GL)))) void klt_stage1_kernel(ov2_pyr_view pv, ov2_pyr_view cv, klt_params P, int n,
                                                         const float2 *__restrict__ kps,
                                                         const float2 *__restrict__ prior,
@@ -984,7 +1024,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
                                                         unsigned *__restrict__ iters, const int *__restrict__ list_a,
                                                         const int *__restrict__ list_b, unsigned *__restrict__ cnt,
                                                         int *__restrict__ list_c,
-                                                        int b_word /* cnt[b_word] = length of list B for THIS launch: 1, or the zero word 3 when the second launch takes the list */)
+                                                        int b_word /* cnt[b_word] = length of list B for THIS launch: 1, or the zero word 3 when the second launch takes the list */,
+                                                        int split_k /* SPLIT: the B segment runs levels nlevels .. split_k + 1 only and leaves a record */,
+                                                        klt_handover *__restrict__ hand /* [n], by keypoint */)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[klt_smem<WIN, KLT_GL>::BYTES];
     using M = klt_map<KLT_GL>;
@@ -1006,13 +1048,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
     const int b = img_idx ? img_idx[i] : 0;
     // kltTracking: keypoints without a prior start from their own position (vpriors = vkps, :181-183); stereoMatching's
     // full-pyramid list carries priors of its own (kp.px_ or the SAD prior, src/map_manager.cpp:419-436,486-488).
-    // Invariant of ov2_klt_two_stage_dev's b_word1 / b_word2: the B segment of THIS launch is kltTracking's and that of the
-    // second launch stereoMatching's, so no caller reaches the !P.rule33 arm for list B today; it stays so that a host that
-    // hands B here without the rule still tracks it as klt_stage2_kernel's B segment would
+    // ov2_klt_two_stage_dev's b_word1 / b_word2: the B segment of THIS launch is kltTracking's (whole descent from kp), or
+    // stereoMatching's upper levels when the descent is split (from the caller's prior, the !P.rule33 arm)
     float2 pr = (is_a || !P.rule33) ? prior[i] : kp;
     unsigned work = 0;
     const int nl = is_a ? min(1, pv.nlevels - 1) : P.nlevels;
-    const int ok = fb_track<WIN, KLT_GL>(pv, cv, b, act, kp.x, kp.y, pr.x, pr.y, P, nl, sub, lane_ok, work, smem, slot);
+    // split descent (stereoMatching, split_k < P.nlevels by the host's choice): list B's upper levels run here beside list
+    // A, and the second launch resumes at level split_k from the record -- the B waves of neither launch outlast its other list
+    const bool upper = SPLIT && !is_a;
+    float err;
+    const int ok = fb_track<WIN, KLT_GL>(pv, cv, b, act, kp.x, kp.y, pr.x, pr.y, P, nl, sub, lane_ok, work, smem, slot, nl,
+                                         upper ? split_k + 1 : 0, 0.f, 0u, err);
+    if (upper) {   // uniform over the workgroup: no result, status, work word or tally yet
+        if (act && sub == 0) hand[i] = klt_handover{pr.x, pr.y, err, work};
+        return;
+    }
     klt_stage1_finish(act && sub == 0, is_a, i, b, n, ok, pr, work, out_xy, out_status, counts, iters, cnt, list_c);
 }
 
@@ -1022,7 +1072,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
 // and the re-tracked ones are equally long (full pyramid, far from the answer), and run one behind the other they made two
 // tails -- the first launch lasted as long as its B waves, then a few lone re-tracking waves of the same length ran on an
 // idle device.  Nothing orders the two lists (no 33 % rule, list B reads no result of list A), so the first launch
-// tracks list A alone and B shares this launch with the re-tracking.
+// tracks list A alone and B shares this launch with the re-tracking.  Both launches were still as long as their longest
+// waves with the device partly idle, so B's descent is split (ov2_klt_set_stereo_split): its levels above split_k ran in the
+// first launch beside A, and this launch resumes them at level split_k from the hand-over records.
 template <int WIN, int KLT_GL>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WIN, KLT_GL)))) void klt_stage2_kernel(ov2_pyr_view pv, ov2_pyr_view cv, klt_params P, int n,
                                                         const float2 *__restrict__ kps,
@@ -1033,7 +1085,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
                                                         const unsigned *__restrict__ cnt, int batch,
                                                         unsigned *__restrict__ next_counts, int next_words,
                                                         const int *__restrict__ list_b, int b_word,
-                                                        const float2 *__restrict__ prior)
+                                                        const float2 *__restrict__ prior,
+                                                        int split_k /* >= 0: the B segment resumes at level split_k from `hand`; < 0: whole descent */,
+                                                        const klt_handover *__restrict__ hand)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[klt_smem<WIN, KLT_GL>::BYTES];
     using M = klt_map<KLT_GL>;
@@ -1072,11 +1126,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
     // list B first (workgroups [0, groups_b)), then the re-tracking list: both run the full pyramid, so the launch has ONE
     // tail.  The host hands list B to exactly one of the two launches (cnt[b_word] is the list's length here and a zero
     // word there); B and the failures of A are disjoint, so groups_b + groups_c <= ceil(n / KPW) + 2, the grid
-    const int total_b = (int)cnt[b_word];
-    const int groups_b = (total_b + KLT_KPW - 1) / KLT_KPW;
-    const bool is_b = (int)blockIdx.x < groups_b;
-    const int g = is_b ? (int)blockIdx.x : (int)blockIdx.x - groups_b;
-    const int total = is_b ? total_b : (int)cnt[2];
+    // With the split descent list B's waves have split_k + 2 passes left and the re-tracked ones all of theirs: the longest
+    // go first, so list C leads and B follows
+    const int total_b = (int)cnt[b_word], total_c = (int)cnt[2];
+    const bool b_first = split_k < 0 || !KLT_SPLIT_C_FIRST;
+    const int groups_1 = ((b_first ? total_b : total_c) + KLT_KPW - 1) / KLT_KPW;
+    const bool first = (int)blockIdx.x < groups_1;
+    const bool is_b = first == b_first;
+    const int g = first ? (int)blockIdx.x : (int)blockIdx.x - groups_1;
+    const int total = is_b ? total_b : total_c;
     if (g * KLT_KPW >= total) return;
     ov2wave::set_wave_prio(P.wave_prio);   // behind the return: an empty workgroup retires without it
     const int idx = g * KLT_KPW + slot;
@@ -1085,10 +1143,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
     const int b = img_idx ? img_idx[i] : 0;
     const float2 kp = kps[i];
     float2 pr;
+    int l_hi = P.nlevels;
+    float err0 = 0.f;
+    unsigned work0 = 0;
     if (is_b) {   // as the first launch tracks the list for stereoMatching: from the caller's prior, no tally, no append
         // the B segment of this launch is stereoMatching's alone (rule33 = 0; the host's b_word1 / b_word2 choice in
         // ov2_klt_two_stage_dev): kltTracking's list B starts from kp and belongs to the first launch, never here
-        pr = prior[i];
+        if (split_k >= 0) {   // the first launch ran levels nlevels .. split_k + 1: resume from its record
+            const klt_handover hr = hand[i];
+            pr = make_float2(hr.fx, hr.fy);
+            err0 = hr.err; work0 = hr.work; l_hi = split_k;
+        } else {
+            pr = prior[i];
+        }
     } else {
         int n3, good;
         tally(b, n3, good);
@@ -1096,7 +1163,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
         pr = drop ? kp : out_xy[i];
     }
     unsigned work = 0;
-    const int ok = fb_track<WIN, KLT_GL>(pv, cv, b, act, kp.x, kp.y, pr.x, pr.y, P, P.nlevels, sub, lane_ok, work, smem, slot);
+    float err;
+    const int ok = fb_track<WIN, KLT_GL>(pv, cv, b, act, kp.x, kp.y, pr.x, pr.y, P, P.nlevels, sub, lane_ok, work, smem, slot,
+                                         l_hi, 0, err0, work0, err);
     if (act && sub == 0) {
         out_xy[i] = pr;
         out_status[i] = (unsigned char)ok;
@@ -1156,6 +1225,13 @@ extern "C" ov2_status ov2_klt_set_lanes(ov2_ctx *c, int lanes)
     if (!c) return OV2_ERR_INVALID;
     if (lanes != 0 && lanes != 3 && lanes != 8 && lanes != 16) return ov2_set_err(c, OV2_ERR_INVALID, "lanes per keypoint: 0 (auto), 3, 8 or 16");
     c->klt_lanes = lanes;
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_klt_set_stereo_split(ov2_ctx *c, int k)
+{
+    if (!c) return OV2_ERR_INVALID;
+    c->klt_stereo_split = k < 0 ? -1 : k;
     return OV2_OK;
 }
 
@@ -1271,7 +1347,9 @@ ov2_status ov2_klt_two_stage_dev(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr 
         for (int i = 0; i < 2; ++i) OV2_HIP(c, hipMemsetAsync(c->klt_counts[i], 0, c->klt_counts_words * sizeof(unsigned), c->stream));
     c->klt_counts_dirty = true;   // until this call's last kernel is enqueued
     void *scr = nullptr;
-    s = ov2_scratch(c, 3 * (size_t)n * sizeof(int) + 256, &scr);
+    // the three keypoint lists and, behind them, list B's hand-over records of the split descent (16 bytes per keypoint)
+    const size_t lists_bytes = (3 * (size_t)n * sizeof(int) + 255) / 256 * 256;
+    s = ov2_scratch(c, lists_bytes + (size_t)n * sizeof(klt_handover) + 256, &scr);
     if (s != OV2_OK) return s;
     unsigned *counts = c->klt_counts[c->klt_counts_cur], *live_cnt = counts + (size_t)B * 64;
     unsigned *next_counts = c->klt_counts[c->klt_counts_cur ^ 1];
@@ -1285,22 +1363,34 @@ ov2_status ov2_klt_two_stage_dev(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr 
     // which launch tracks list B: the first for kltTracking (the 33 % rule orders the re-tracking behind list A's tally, and
     // B fills the first launch), the second for stereoMatching (see klt_stage2_kernel).  The other launch reads B's length
     // from word 3 of the list-length block, which nothing writes: zero, so its B segment is empty
-    const int b_word1 = P.rule33 ? 1 : 3, b_word2 = P.rule33 ? 3 : 1;
+    // stereoMatching's split descent (ov2_klt_set_stereo_split): both launches read list B's real length, the first runs its
+    // levels above split_k and the second the rest.  split_k >= P.nlevels (the clamped level count: also a pyramid with
+    // fewer levels than the split needs) is no split, and so is every kltTracking call
+    const int want_k = c->klt_stereo_split < 0 ? KLT_STEREO_SPLIT_DEFAULT : c->klt_stereo_split;
+    const int split_k = (!P.rule33 && want_k < P.nlevels) ? want_k : -1;
+    const int b_word1 = (P.rule33 || split_k >= 0) ? 1 : 3, b_word2 = P.rule33 ? 3 : 1;
+    klt_handover *hand = reinterpret_cast<klt_handover *>((char *)scr + lists_bytes);
 #define KLT_STAGES_GL(W, G)                                                                                     \
     do {                                                                                                        \
         /* two disjoint lists of the n keypoints: groups of the one + groups of the other <= ceil(n / KPW) + 2 */ \
         const dim3 tgrid((n + klt_map<G>::KPW - 1) / klt_map<G>::KPW + 2);                                      \
         OV2_LAUNCH(c, OV2_K_DETECT + 4, klt_compact_kernel, cgrid, dim3(256), 0, c->stream, n, 1, d_has_prior,  \
                    d_out_status, d_iters, list_a, list_b, live_cnt, d_p3p_req, B, P.wave_prio);                 \
-        OV2_LAUNCH(c, OV2_K_KLT_STAGE1, (klt_stage1_kernel<W, G>), tgrid, dim3(64), 0, c->stream,               \
-                   prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps),              \
-                   reinterpret_cast<const float2 *>(d_prior), d_img_idx, reinterpret_cast<float2 *>(d_out_xy),  \
-                   d_out_status, counts, d_iters, list_a, list_b, live_cnt, list_c, b_word1);                  \
+        if (split_k >= 0)                                                                                       \
+            OV2_LAUNCH(c, OV2_K_KLT_STAGE1, (klt_stage1_kernel<W, G, true>), tgrid, dim3(64), 0, c->stream,     \
+                       prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps),          \
+                       reinterpret_cast<const float2 *>(d_prior), d_img_idx, reinterpret_cast<float2 *>(d_out_xy), \
+                       d_out_status, counts, d_iters, list_a, list_b, live_cnt, list_c, b_word1, split_k, hand); \
+        else                                                                                                    \
+            OV2_LAUNCH(c, OV2_K_KLT_STAGE1, (klt_stage1_kernel<W, G, false>), tgrid, dim3(64), 0, c->stream,    \
+                       prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps),          \
+                       reinterpret_cast<const float2 *>(d_prior), d_img_idx, reinterpret_cast<float2 *>(d_out_xy), \
+                       d_out_status, counts, d_iters, list_a, list_b, live_cnt, list_c, b_word1, split_k, hand); \
         OV2_LAUNCH(c, OV2_K_KLT_STAGE2, (klt_stage2_kernel<W, G>), tgrid, dim3(64), 0, c->stream,               \
                    prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps), d_img_idx,   \
                    reinterpret_cast<float2 *>(d_out_xy), d_out_status, counts, d_p3p_req, d_iters, list_c,      \
                    live_cnt, B, next_counts, next_words, list_b, b_word2,                                       \
-                   reinterpret_cast<const float2 *>(d_prior));                                                  \
+                   reinterpret_cast<const float2 *>(d_prior), split_k, hand);                                   \
     } while (0)
 #define KLT_STAGES(W)                                                                                           \
     do {                                                                                                        \

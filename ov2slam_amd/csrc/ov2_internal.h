@@ -142,6 +142,7 @@ struct ov2_ctx {
     hipEvent_t ba_copy_ev[2];            // [0] head uploaded (main stream), [1] measurements uploaded (copy stream)
     int wave_prio;                       // ov2_ctx_set_wave_prio: 0..3, the s_setprio level of every kernel this ctx launches that takes one
     int klt_lanes;                       // ov2_klt_set_lanes: 0 = by call size, 3 / 8 / 16 = forced lanes per keypoint
+    int klt_stereo_split;                // ov2_klt_set_stereo_split: the level stereoMatching's list B resumes at in the second launch, -1 = built-in
     int knn_lanes;                       // ov2_knn_set_lanes: 0 = by call size, 1 / 4 / 16 / 64 = forced lanes per query
     int knn_cus;                         // compute units of the device (read on first use by the matcher's automatic choice)
     int lcd_splits;                      // ov2_lcd_set_splits: 0 = by call size, otherwise the forced number of train-axis splits

@@ -47,6 +47,11 @@ class Context:
         """ov2_klt_set_lanes: 0 = by call size, 3 / 8 / 16 = lanes per keypoint in the tracking kernels"""
         _check(self.h, self.lib.ov2_klt_set_lanes(self.h, int(lanes)))
 
+    def set_stereo_split(self, k):
+        """ov2_klt_set_stereo_split: the level stereoMatching's no-prior list resumes at in the second tracking launch
+        (k >= the call's levels: whole descent in the second launch; k < 0: the library's default)"""
+        _check(self.h, self.lib.ov2_klt_set_stereo_split(self.h, int(k)))
+
     def set_knn_lanes(self, lanes):
         """ov2_knn_set_lanes: 0 = by call size, 1 / 4 / 16 / 64 = lanes per query in the loop-candidate matcher"""
         _check(self.h, self.lib.ov2_knn_set_lanes(self.h, int(lanes)))
