@@ -470,7 +470,8 @@ ov2_status ov2_pnp_solve_batch_dev(ov2_ctx *ctx, int B, const int32_t *d_off, co
  *   mix(z) = SplitMix64 finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31)
  *   a = mix(seed + G (d + 1)), x = mix(a + G (j + 1)), G = 0x9E3779B97F4A7C15, index = ((x >> 32) * n) >> 32
  * (64-bit wrapping arithmetic).  Candidates of one sample whose summed scores are within 1e-9 of the lowest are broken
- * by the larger trace of R; t is returned of unit length.  Mono do_optimize (OpenGV's nonlinear refinement) is not built.
+ * by the larger trace of R; t is returned of unit length.  Mono do_optimize (OpenGV's nonlinear refinement) is a second call
+ * on the same arrays, ov2_relpose_refine_batch below.
  * nmaxiter outside [0, OV2_EPI_MAX_ITER] is OV2_ERR_INVALID (a launch evaluates at most 11 nmaxiter + 1 draws). */
 #define OV2_EPI_MAX_ITER (1 << 24)
 ov2_status ov2_epipolar_filter_batch(ov2_ctx *ctx, int B, const int *n_pairs, const double *bv_kf, const double *bv_cur,
@@ -484,6 +485,56 @@ ov2_status ov2_epipolar_filter_batch_dev(ov2_ctx *ctx, int B, const int32_t *d_o
                                          const float *d_gate_unpx_cur, const double *d_K, int nmaxiter, float errth,
                                          const uint64_t *d_seed, double *d_R_kfc, double *d_t_kfc, uint8_t *d_outlier,
                                          uint8_t *d_gate_bad, int32_t *d_status, int32_t *d_info);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Mono do_optimize: refinement of the 5-point model [R | t] on the RANSAC inliers, the whole Levenberg-Marquardt loop in one
+ * launch.  Stands for the do_optimize = true branch of opengv5ptEssentialMatrix (src/multi_view_geometry.cpp:672-681:
+ * ransac.sac_model_->optimizeModelCoefficients on the inliers, then twc.normalize()), which the reference takes in
+ * VisualFrontEnd::checkReadyForInit (src/visual_front_end.cpp:855-984) and in the poor-tracking mono branch of
+ * epipolar2d2dFiltering (:537-544, :590-608).
+ * B independent frames per call, one workgroup each; frame b owns n_pairs[b] consecutive pairs.  All pointers are HOST
+ * pointers; one synchronisation.
+ *   bv_kf, bv_cur  sum(n) x 3   bearing vectors f1 / f2 as in ov2_epipolar_filter_batch (any bearing, z <= 0 included)
+ *   skip    sum(n)  1 = the pair is left out (the RANSAC outlier mask as it is); NULL = every pair is admitted
+ *   K       B x 4   fx fy cx cy; only focal = (fx + fy) / 2 (double) is used, as the unit of the residual
+ *   R_kfc   B x 9, t_kfc B x 3   in: the model to start from (X_kf = R X_cur + t; t is normalised first); out: the refined
+ *                   model, R orthogonal (from a unit quaternion), |t| = 1.  Written when status == 1, BIT-UNTOUCHED otherwise
+ *   status  B       1: at least one LM step was accepted; 0: fewer than 6 admitted pairs, a non-finite value in an admitted
+ *                   bearing / R / t or t = 0, no accepted step, or a frame skipped through d_in_status
+ *   info    B x 2   (may be NULL) LM iterations, termination (OV2_BA_TERM_*; OV2_BA_TERM_SKIPPED where nothing was run)
+ *   cost    B x 2   (may be NULL) initial and final cost (0, 0 where nothing was run)
+ * Cost of a frame: 1/2 sum r_i^2 over the admitted pairs, no loss function (the input is the inlier set), with
+ *   g = R f2,  c = f1 . (t x g),  u = R^T (f1 x t),  r_i = focal c / sqrt(|t x g|^2 - c^2 + |u|^2 - (u . f2)^2)
+ * the Sampson distance on the sphere: the denominator is the squared length of the gradients of c in the tangent planes at f1
+ * and f2.  For pinhole bearings near the axis it is the pixel Sampson distance of the gate above; it is defined for any
+ * bearing.  A pair whose denominator is not a finite positive number contributes nothing to that evaluation.
+ * Parametrisation (5 degrees of freedom, step (w, a, b)): the rotation is a unit quaternion updated on the left,
+ * q <- exp(w) q, renormalised; t <- (t + a b1 + b b2) / |...| with b1 = normalise(e_k x t), k the index of the smallest |t_k|
+ * (the lowest on a tie), b2 = t x b1, the basis taken anew at every accepted point.  The jacobian is analytic and includes
+ * the derivative of the denominator.
+ * Solver: the trust-region loop of ov2_pnp_solve_batch with its constants (ov2_ba_default_options: Jacobi scaling, diagonal
+ * clamp, radius rules, min_relative_decrease, parameter tolerance, 5 invalid steps), a 5x5 system, 21 sums per evaluation
+ * reduced in a fixed order: a frame's result is bit-identical whatever else the batch holds.  One constant differs: the
+ * function tolerance is OV2_RELPOSE_FUNCTION_TOLERANCE = 1e-6, Ceres' default, not the 1e-3 that the reference sets for its
+ * BA problems (src/optimizer.cpp:463) and ov2_ba_default_options carries.  The tolerances are tested before a step is
+ * accepted, and from a RANSAC model the first, nearly undamped step can overshoot to a cost within 1e-3 of the start: with
+ * 1e-3 such a frame ended with no accepted step.
+ * DEVIATION: OpenGV's optimizeModelCoefficients is not restated (its source is not in the reference tree); as for the P3P
+ * stage below, a refinement of this project's own takes its place, on the RANSAC inliers, and the RANSAC outlier mask stays.
+ * B < 0, max_iters < 0, a negative pair count and null arrays that a non-empty call needs are OV2_ERR_INVALID before any
+ * launch. */
+#define OV2_RELPOSE_FUNCTION_TOLERANCE 1e-6
+ov2_status ov2_relpose_refine_batch(ov2_ctx *ctx, int B, const int *n_pairs, const double *bv_kf, const double *bv_cur,
+                                    const uint8_t *skip, const double *K, int max_iters, double *R_kfc, double *t_kfc,
+                                    int *status, int *info, double *cost);
+/* device-resident, asynchronous form: d_off = B + 1 prefix offsets, every other array as above but in HBM; d_in_status (B,
+ * may be NULL): frame b is refined only if d_in_status[b] >= 1.  d_skip, d_R_kfc, d_t_kfc and d_in_status are the d_outlier,
+ * d_R_kfc, d_t_kfc and d_status of ov2_epipolar_filter_batch_dev as they are: RANSAC and refinement of B frames are two
+ * enqueues on one stream.  Nothing is synchronised. */
+ov2_status ov2_relpose_refine_batch_dev(ov2_ctx *ctx, int B, const int32_t *d_off, const double *d_bv_kf,
+                                        const double *d_bv_cur, const uint8_t *d_skip, const double *d_K, int max_iters,
+                                        const int32_t *d_in_status, double *d_R_kfc, double *d_t_kfc, int32_t *d_status,
+                                        int32_t *d_info, double *d_cost);
 
 /* ---------------------------------------------------------------------------------------------------
  * The P3P stage of computePose: P3P LMedS / RANSAC on 2D-3D correspondences.

@@ -118,7 +118,9 @@ SIGNATURES = {
                                             vp, vp, vp, vp]),
     "ov2_epipolar_filter_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp, vp,
                                                 vp, vp, vp, vp]),
-    "ov2_dbg_fivept": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+    "ov2_relpose_refine_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+    "ov2_relpose_refine_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "ov2_dbg_fivept":(C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
     "ov2_p3p_ransac_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
     "ov2_p3p_ransac_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
     "ov2_dbg_p3p": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),

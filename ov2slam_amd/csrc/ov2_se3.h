@@ -88,6 +88,32 @@ __device__ inline void se3_plus(const double *x, const double *d, double *out)
     out[3] = q[0] / nq; out[4] = q[1] / nq; out[5] = q[2] / nq; out[6] = q[3] / nq;
 }
 
+// rotation part of se3_plus alone: out = exp(w) * b renormalised, b a unit quaternion (x, y, z, w) taken as it is
+__device__ inline void quat_plus_left(const double b[4], const double w[3], double out[4])
+{
+    const double eps = 1e-10;
+    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    double imag, real;
+    if (th2 < eps * eps) {
+        const double th4 = th2 * th2;
+        imag = 0.5 - (1.0 / 48.0) * th2 + (1.0 / 3840.0) * th4;
+        real = 1.0 - (1.0 / 8.0) * th2 + (1.0 / 384.0) * th4;
+    } else {
+        const double theta = sqrt(th2);
+        const double half = 0.5 * theta;
+        imag = sin(half) / theta;
+        real = cos(half);
+    }
+    const double a[4] = {imag * w[0], imag * w[1], imag * w[2], real};
+    double q[4];
+    q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+    q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+    const double nq = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    out[0] = q[0] / nq; out[1] = q[1] / nq; out[2] = q[2] / nq; out[3] = q[3] / nq;
+}
+
 // ---- the host mirror's form (SE3::fromRt of ov2_host.cpp) ---------------------------------------------------------
 
 // rotation matrix -> quaternion (x, y, z, w), in the mirror's branch order

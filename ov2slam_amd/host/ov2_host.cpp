@@ -969,7 +969,7 @@ bool MultiViewGeometry::compute5ptEssentialMatrix(ov2_ctx *ctx, const std::vecto
                                                   double Rwc[9], double twc[3], std::vector<int> &voutliersidx, ov2_status *st)
 {   // src/multi_view_geometry.cpp:596-697
     if (st) *st = OV2_OK;
-    if (boptimize) { if (st) *st = OV2_ERR_UNSUPPORTED; return false; }   // optimizeModelCoefficients (:676-683) is not built
+    if (boptimize) { if (st) *st = OV2_ERR_UNSUPPORTED; return false; }   // the refined form is compute5ptEssentialMatrixOpt
     if (bvs1.size() != bvs2.size()) return false;                         // the reference asserts (:622)
     const int n = (int)bvs1.size();
     const double K[4] = {fx, fy, 0., 0.};
@@ -982,6 +982,33 @@ bool MultiViewGeometry::compute5ptEssentialMatrix(ov2_ctx *ctx, const std::vecto
     if (status < 1) return false;   // < 8 pairs, no model or < 10 inliers (:665)
     for (int i = 0; i < n; ++i)
         if (out[i]) voutliersidx.push_back(i);
+    return true;
+}
+
+ov2_status MultiViewGeometry::refine5pt(ov2_ctx *ctx, int B, const int *n, const double *bvs1, const double *bvs2,
+                                        const uint8_t *outlier, const double *K, double *R, double *t, int *status, int *info)
+{   // src/multi_view_geometry.cpp:672-681; t comes back of unit length (twc.normalize())
+    return ov2_relpose_refine_batch(ctx, B, n, bvs1, bvs2, outlier, K, kRefine5ptIters, R, t, status, info, nullptr);
+}
+
+bool MultiViewGeometry::compute5ptEssentialMatrixOpt(ov2_ctx *ctx, const std::vector<Vec3> &bvs1, const std::vector<Vec3> &bvs2,
+                                                     int nmaxiter, float errth, uint64_t seed, float fx, float fy, double Rwc[9],
+                                                     double twc[3], std::vector<int> &voutliersidx, ov2_status *st, int *refine)
+{   // src/multi_view_geometry.cpp:596-697 with do_optimize = true
+    if (refine) refine[0] = refine[1] = 0;
+    ov2_status s = OV2_OK;
+    const bool ok = compute5ptEssentialMatrix(ctx, bvs1, bvs2, nmaxiter, errth, false, seed, fx, fy, Rwc, twc, voutliersidx, &s);
+    if (st) *st = s;
+    if (!ok) return false;
+    const int n = (int)bvs1.size();
+    std::vector<uint8_t> out((size_t)n + 1, 0);
+    for (const int i : voutliersidx) out[(size_t)i] = 1;
+    const double K[4] = {fx, fy, 0., 0.};
+    int status = 0, info[2] = {0, 0};
+    s = refine5pt(ctx, 1, &n, &bvs1[0].x, &bvs2[0].x, out.data(), K, Rwc, twc, &status, info);
+    if (st) *st = s;
+    if (s != OV2_OK) return false;
+    if (refine) { refine[0] = status; refine[1] = info[0]; }
     return true;
 }
 
@@ -1047,8 +1074,8 @@ ov2_status VisualFrontEnd::epipolar2d2dFiltering(EpiStats *stats)
     if (nbkps < 8) return OV2_OK;                                        // :521-525, a repeat of the first test (kept as written)
     avg_parallax /= (float)nbparallax;                                   // :528
     if (avg_parallax < 2. * S.fransac_err_) return OV2_OK;               // :530-535
-    if (S.mono_ && pmap_->map_pkfs_.size() > 2 && pcurframe_->nb3dkps_ < 30)   // do_optimize (:537-544): not built
-        return OV2_ERR_UNSUPPORTED;
+    // in the monocular case the resulting motion is used if tracking is poor (:537-544)
+    const bool do_optimize = S.mono_ && pmap_->map_pkfs_.size() > 2 && pcurframe_->nb3dkps_ < 30;
     // the Sampson gate of :611-648 rides in the same launch: every 2D keypoint with the keyframe's keypoint of the same id
     // (a default Keypoint, unpx (0, 0), where the keyframe lacks it -- the reference's getKeypointById)
     std::vector<float> gkf, gcur;
@@ -1064,13 +1091,7 @@ ov2_status VisualFrontEnd::epipolar2d2dFiltering(EpiStats *stats)
         }
     const CameraCalibration &c = *pcurframe_->pcalib_leftcam_;
     const double K[4] = {c.fx_, c.fy_, c.cx_, c.cy_};
-    uint64_t seed = S.epi_seed_;
-    if (S.bdo_random_) {   // a different stream per frame, reproducible from (epi_seed_, frame id)
-        uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)(int64_t)pcurframe_->id_ + 1);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        seed = z ^ (z >> 31);
-    }
+    const uint64_t seed = epiSeed();
     const int n = (int)vkfbvs.size(), ng = (int)vgateids.size();
     std::vector<uint8_t> out((size_t)n + 1), bad((size_t)ng + 1);
     double R[9], t[3];
@@ -1079,15 +1100,141 @@ ov2_status VisualFrontEnd::epipolar2d2dFiltering(EpiStats *stats)
                                                    ng ? gkf.data() : nullptr, ng ? gcur.data() : nullptr, K, S.nransac_iter_,
                                                    S.fransac_err_, &seed, R, t, out.data(), bad.data(), &status, nullptr);
     if (s != OV2_OK) return s;
-    if (stats) { stats->status = status; stats->pairs = n; }
+    if (stats) { stats->status = status; stats->pairs = n; stats->do_optimize = do_optimize; }
+    if (do_optimize && status >= 1) {                                    // do_optimize inside compute5ptEssentialMatrix
+        int rst = 0, rinfo[2] = {0, 0};
+        const ov2_status rs = MultiViewGeometry::refine5pt(ctx_, 1, &n, &vkfbvs[0].x, &vcurbvs[0].x, out.data(), K, R, t, &rst, rinfo);
+        if (rs != OV2_OK) return rs;
+        if (stats) { stats->refine_status = rst; stats->refine_iters = rinfo[0]; }
+    }
     if (status < 2) return OV2_OK;                                       // no model (:573-578) / too many outliers (:580-585)
     int removed = 0, gate_removed = 0;
     for (int i = 0; i < n; ++i)                                          // :587-590
         if (out[i]) { pmap_->removeObsFromCurFrameById(vkpsids[i]); ++removed; }
+    if (do_optimize && pmap_->map_pkfs_.size() > 2) {                    // :594-608
+        const SE3 Tkfcur = pkf->getTcw() * pcurframe_->getTwc();         // translation scale of the motion model
+        const double scale = std::sqrt(Tkfcur.v[0] * Tkfcur.v[0] + Tkfcur.v[1] * Tkfcur.v[1] + Tkfcur.v[2] * Tkfcur.v[2]);
+        const double tn = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+        const double st[3] = {scale * (t[0] / tn), scale * (t[1] / tn), scale * (t[2] / tn)};
+        pcurframe_->setTwc(pkf->getTwc() * SE3::fromRt(R, st));
+    }
     for (int i = 0; i < ng; ++i)                                         // :641-643
         if (bad[i]) { pmap_->removeObsFromCurFrameById(vgateids[i]); ++gate_removed; }
     if (stats) { stats->removed = removed; stats->gate_removed = gate_removed; }
     return OV2_OK;
+}
+
+uint64_t VisualFrontEnd::epiSeed() const
+{
+    uint64_t seed = pslamstate_->epi_seed_;
+    if (pslamstate_->bdo_random_) {   // a different stream per frame, reproducible from (epi_seed_, frame id)
+        uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)(int64_t)pcurframe_->id_ + 1);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        seed = z ^ (z >> 31);
+    }
+    return seed;
+}
+
+float computeParallax(const Frame &cur, const Frame *pkf, bool do_unrot, bool bmedian, bool b2donly)
+{   // src/visual_front_end.cpp:1069-1142
+    if (!pkf) return 0.f;
+    double Rkfcur[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (do_unrot) {
+        double Rkfw[9], Rwcur[9];
+        pkf->getTcw().rotation(Rkfw);
+        cur.getTwc().rotation(Rwcur);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) Rkfcur[3 * i + j] = Rkfw[3 * i] * Rwcur[j] + Rkfw[3 * i + 1] * Rwcur[3 + j] + Rkfw[3 * i + 2] * Rwcur[6 + j];
+    }
+    float avg_parallax = 0.f;
+    int nbparallax = 0;
+    std::set<float> set_parallax;
+    for (const auto &it : cur.mapkps_) {
+        const Keypoint &kp = it.second;
+        if (b2donly && kp.is3d_) continue;
+        const Keypoint kfkp = pkf->getKeypointById(kp.lmid_);
+        if (kfkp.lmid_ != kp.lmid_) continue;
+        Point2f unpx = kp.unpx_;
+        if (do_unrot) {
+            const Vec3 b{Rkfcur[0] * kp.bv_.x + Rkfcur[1] * kp.bv_.y + Rkfcur[2] * kp.bv_.z, Rkfcur[3] * kp.bv_.x + Rkfcur[4] * kp.bv_.y + Rkfcur[5] * kp.bv_.z,
+                         Rkfcur[6] * kp.bv_.x + Rkfcur[7] * kp.bv_.y + Rkfcur[8] * kp.bv_.z};
+            const Vec3 px = pkf->pcalib_leftcam_->projectCamToImage(b);
+            unpx = Point2f{(float)px.x, (float)px.y};
+        }
+        const float dx = unpx.x - kfkp.unpx_.x, dy = unpx.y - kfkp.unpx_.y;
+        const float parallax = (float)std::sqrt((double)dx * dx + (double)dy * dy);   // cv::norm(Point2f)
+        avg_parallax += parallax;
+        nbparallax++;
+        if (bmedian) set_parallax.insert(parallax);
+    }
+    if (nbparallax == 0) return 0.f;
+    avg_parallax /= nbparallax;
+    if (bmedian) { auto it = set_parallax.begin(); std::advance(it, set_parallax.size() / 2); avg_parallax = *it; }
+    return avg_parallax;
+}
+
+bool VisualFrontEnd::checkReadyForInit(EpiStats *stats, ov2_status *st)
+{   // src/visual_front_end.cpp:855-984
+    if (stats) *stats = EpiStats();
+    if (st) *st = OV2_OK;
+    const SlamParams &S = *pslamstate_;
+    auto pkf = pmap_->getKeyframe(pcurframe_->kfid_);
+    const double avg_rot_parallax0 = computeParallax(*pcurframe_, pkf.get(), false, true, false);   // :857 (median, not unrotated)
+    if (!(avg_rot_parallax0 > S.finit_parallax_)) return false;          // :861, :983
+    if (!pkf) return false;                                              // :865-868
+    const size_t nbkps = pcurframe_->nbkps_;
+    if (nbkps < 8) return false;                                         // :873-876
+    double Rkfw[9], Rwcur[9], Rkfcur[9];                                 // :887
+    pkf->getTcw().rotation(Rkfw);
+    pcurframe_->getTwc().rotation(Rwcur);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Rkfcur[3 * i + j] = Rkfw[3 * i] * Rwcur[j] + Rkfw[3 * i + 1] * Rwcur[3 + j] + Rkfw[3 * i + 2] * Rwcur[6 + j];
+    // ascending lmids, as in epipolar2d2dFiltering: the float sum and the sampler's draws have a defined order
+    std::vector<int> order;
+    for (const auto &it : pcurframe_->mapkps_) order.push_back(it.first);
+    std::sort(order.begin(), order.end());
+    std::vector<Vec3> vkfbvs, vcurbvs;
+    std::vector<int> vkpsids, voutliersidx;
+    int nbparallax = 0;
+    float avg_rot_parallax = 0.f;
+    const CameraCalibration &c = *pcurframe_->pcalib_leftcam_;
+    for (const int lmid : order) {                                       // :893-915
+        const Keypoint &kp = pcurframe_->mapkps_.at(lmid);
+        const Keypoint kfkp = pkf->getKeypointById(kp.lmid_);
+        if (kfkp.lmid_ != kp.lmid_) continue;
+        vkfbvs.push_back(kfkp.bv_);
+        vcurbvs.push_back(kp.bv_);
+        vkpsids.push_back(kp.lmid_);
+        const Vec3 b{Rkfcur[0] * kp.bv_.x + Rkfcur[1] * kp.bv_.y + Rkfcur[2] * kp.bv_.z,
+                     Rkfcur[3] * kp.bv_.x + Rkfcur[4] * kp.bv_.y + Rkfcur[5] * kp.bv_.z,
+                     Rkfcur[6] * kp.bv_.x + Rkfcur[7] * kp.bv_.y + Rkfcur[8] * kp.bv_.z};
+        const double ux = c.fx_ * b.x + c.cx_ * b.z, uy = c.fy_ * b.y + c.cy_ * b.z;   // K_ * rotbv (:910), then / z (:911)
+        const float dx = (float)(ux / b.z) - kfkp.unpx_.x, dy = (float)(uy / b.z) - kfkp.unpx_.y;
+        avg_rot_parallax = (float)((double)avg_rot_parallax + std::sqrt((double)dx * dx + (double)dy * dy));   // float += cv::norm
+        nbparallax++;
+    }
+    if (nbparallax < 8) return false;                                    // :917-920
+    avg_rot_parallax /= (float)nbparallax;                               // :923
+    if (avg_rot_parallax < S.finit_parallax_) return false;              // :925-928
+    double Rkfc[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tkfc[3] = {0, 0, 0};   // :932-935
+    ov2_status s = OV2_OK;
+    int refine[2] = {0, 0};
+    const bool success = MultiViewGeometry::compute5ptEssentialMatrixOpt(ctx_, vkfbvs, vcurbvs, S.nransac_iter_, S.fransac_err_,
+                                                                         epiSeed(), (float)c.fx_, (float)c.fy_, Rkfc, tkfc,
+                                                                         voutliersidx, &s, refine);   // :945-952
+    if (st) *st = s;
+    if (stats) {
+        stats->status = success ? 1 : 0; stats->pairs = (int)vkfbvs.size(); stats->do_optimize = 1;
+        stats->refine_status = refine[0]; stats->refine_iters = refine[1];
+    }
+    if (!success) return false;                                          // :956-959
+    for (const int idx : voutliersidx) pmap_->removeObsFromCurFrameById(vkpsids.at((size_t)idx));   // :962-965
+    if (stats) stats->removed = (int)voutliersidx.size();
+    const double tn = std::sqrt(tkfc[0] * tkfc[0] + tkfc[1] * tkfc[1] + tkfc[2] * tkfc[2]);   // arbitrary scale (:968-969)
+    const double t[3] = {tkfc[0] / tn * 0.25, tkfc[1] / tn * 0.25, tkfc[2] / tn * 0.25};
+    pcurframe_->setTwc(SE3::fromRt(Rkfc, t));                            // :973
+    return true;
 }
 
 void VisualFrontEnd::resetFrame()

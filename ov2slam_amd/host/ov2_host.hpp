@@ -264,11 +264,25 @@ public:
                          bool bapply_l2_after_robust, float fx, float fy, float cx, float cy,
                          std::vector<int> &voutliersidx);
     // src/multi_view_geometry.cpp:596-697 (OpenGV 5-point RANSAC) through ov2_epipolar_filter_batch with B = 1: bvs1 = keyframe
-    // bearings, bvs2 = current-frame bearings; Rwc / twc = [R12 | t12], t of unit length.  boptimize (OpenGV's nonlinear
-    // refinement) is not built: *st = OV2_ERR_UNSUPPORTED.  The sampler seed replaces the reference's bdorandom clock seed.
+    // bearings, bvs2 = current-frame bearings; Rwc / twc = [R12 | t12], t of unit length.  boptimize is refused here
+    // (*st = OV2_ERR_UNSUPPORTED): the refined form has a name of its own, compute5ptEssentialMatrixOpt.  The sampler seed
+    // replaces the reference's bdorandom clock seed.
     static bool compute5ptEssentialMatrix(ov2_ctx *ctx, const std::vector<Vec3> &bvs1, const std::vector<Vec3> &bvs2,
                                           int nmaxiter, float errth, bool boptimize, uint64_t seed, float fx, float fy,
                                           double Rwc[9], double twc[3], std::vector<int> &voutliersidx, ov2_status *st);
+    // the do_optimize = true branch of opengv5ptEssentialMatrix (src/multi_view_geometry.cpp:672-681) for B frames in one
+    // library call (ov2_relpose_refine_batch): the models R (B x 9) / t (B x 3) are refined on the pairs `outlier` (sum(n),
+    // the RANSAC mask; NULL = all) admits, t comes back of unit length (twc.normalize()), the outlier list is not touched.
+    // DEVIATION: the cost is this project's (include/ov2slam_hip.h), not OpenGV's.  status[b] = 1 where the model moved;
+    // info (B x 2, may be NULL): LM iterations, termination.
+    static constexpr int kRefine5ptIters = 10;
+    static ov2_status refine5pt(ov2_ctx *ctx, int B, const int *n, const double *bvs1, const double *bvs2, const uint8_t *outlier,
+                                const double *K, double *R, double *t, int *status, int *info);
+    // compute5ptEssentialMatrix(..., boptimize = true, ...) of the reference: the RANSAC above, then refine5pt on its inliers.
+    // refine[2] (may be NULL): refine5pt's status and LM iterations.
+    static bool compute5ptEssentialMatrixOpt(ov2_ctx *ctx, const std::vector<Vec3> &bvs1, const std::vector<Vec3> &bvs2,
+                                             int nmaxiter, float errth, uint64_t seed, float fx, float fy, double Rwc[9],
+                                             double twc[3], std::vector<int> &voutliersidx, ov2_status *st, int *refine = nullptr);
     // src/multi_view_geometry.cpp:144-163 (-> opengvP3PLMeds :257-343 / opengvP3PRansac :168-254) through
     // ov2_p3p_ransac_batch with B = 1, the reference's argument order; Twc is written only when the call returns true.
     // boptimize (OpenGV's nonlinear refinement) is not built: *st = OV2_ERR_UNSUPPORTED.  bdorandom is the reference's
@@ -313,6 +327,8 @@ struct TemporalStats {   // Mapper::triangulateTemporal on the last keyframe
 struct EpiStats {   // what VisualFrontEnd::epipolar2d2dFiltering did on the last frame
     int status = -1;         // -1 not run / returned before the RANSAC; else the ov2_epipolar_filter_batch status 0 / 1 / 2
     int pairs = 0, removed = 0, gate_removed = 0;
+    int do_optimize = 0;     // 1: the mono branch that refines the model and uses its motion (:537-544), or checkReadyForInit
+    int refine_status = 0, refine_iters = 0;   // MultiViewGeometry::refine5pt on that frame: status, LM iterations
 };
 
 // owning handle of an ov2_pyr (the std::vector<cv::Mat> pyramid of the reference)
@@ -358,6 +374,9 @@ private:
     std::vector<Point2f> detect(const Pyramid &pyr, int ncellsize, int mode, const std::vector<Point2f> &vcurkps, const int roi[4]);
 };
 
+// VisualFrontEnd::computeParallax (src/visual_front_end.cpp:1069-1142) of frame `cur` against keyframe `pkf` (null: 0)
+float computeParallax(const Frame &cur, const Frame *pkf, bool do_unrot, bool bmedian, bool b2donly);
+
 class VisualFrontEnd {   // src/visual_front_end.cpp (preprocessImage, kltTracking, epipolar2d2dFiltering, computePose)
 public:
     VisualFrontEnd(ov2_ctx *ctx, std::shared_ptr<SlamParams> pstate, std::shared_ptr<Frame> pframe,
@@ -370,8 +389,15 @@ public:
     ov2_status computePose(P3pStats *stats = nullptr);
     void resetFrame();                                                               // :1181-1203
     // :446-655, one ov2_epipolar_filter_batch call (RANSAC + the Sampson gate of the 2D keypoints in the same launch); pairs
-    // in ascending lmid order.  The mono do_optimize branch (:537-544, :590-608) returns OV2_ERR_UNSUPPORTED.
+    // in ascending lmid order.  The mono do_optimize branch (:537-544, :590-608: more than 2 keyframes, fewer than 30 3D
+    // keypoints) refines the model (MultiViewGeometry::refine5pt) and, after the outlier removal, sets the pose from it with
+    // the translation scale of the current Tkfcur.
     ov2_status epipolar2d2dFiltering(EpiStats *stats = nullptr);
+    // :855-984 statement by statement (mono initialisation): true when the current frame has the parallax and a refined
+    // 5-point model against its keyframe; then the RANSAC outliers are removed from the current frame and its pose is
+    // [R | 0.25 t / |t|].  Pairs in ascending lmid order.  *st: the status of the library calls.
+    bool checkReadyForInit(EpiStats *stats = nullptr, ov2_status *st = nullptr);
+    uint64_t epiSeed() const;   // the sampler seed of the frame: epi_seed_, mixed with the frame id under bdo_random_
     bool bp3preq_ = false;
     Pyramid prev_pyr_, cur_pyr_;
     ov2_ctx *ctx_;

@@ -24,6 +24,7 @@ struct HostMap {
     LocalBAProblem pb;
     bool bp3preq = false;    // VisualFrontEnd::bp3preq_, carried from one ov2h_compute_pose call to the next
     P3pStats last_p3p;       // the P3P branch of the last ov2h_compute_pose
+    EpiStats last_epi;       // the last ov2h_epipolar_filtering / ov2h_check_ready_for_init
 };
 }  // namespace
 
@@ -1078,7 +1079,7 @@ int ov2h_compute_pose(void *p, void *ctx, int kfid, const double *Twc7_init, int
 // VisualFrontEnd::epipolar2d2dFiltering (:446-655) with keyframe kf_cur taken as the current frame and kf_prev as its previous
 // keyframe, nransac_iter / fransac_err as the YAML keys, bdo_random off (seed used as is).  removed[cap]: the ids the stage
 // removed from kf_cur, ascending; stats[4] (may be NULL): as ov2h_slam_epi_stats.  Returns the number of removed ids, or a
-// negative ov2_status (OV2_ERR_UNSUPPORTED: the mono do_optimize branch).
+// negative ov2_status.  The fields EpiStats gained with the mono do_optimize branch are read through ov2h_epi_opt_stats.
 int ov2h_epipolar_filtering(void *p, void *ctx, int kf_prev, int kf_cur, int nransac_iter, float fransac_err,
                             unsigned long long seed, int cap, int *removed, double *stats)
 {
@@ -1097,12 +1098,75 @@ int ov2h_epipolar_filtering(void *p, void *ctx, int kf_prev, int kf_cur, int nra
     EpiStats es;
     const ov2_status s = fe.epipolar2d2dFiltering(&es);
     f->kfid_ = own;
+    m->last_epi = es;
     if (stats) { stats[0] = es.status; stats[1] = es.pairs; stats[2] = es.removed; stats[3] = es.gate_removed; }
     if (s != OV2_OK) return (int)s;
     int n = 0;
     for (const int id : before)
         if (!f->mapkps_.count(id)) { if (n < cap) removed[n] = id; ++n; }
     return n;
+}
+
+// the do_optimize fields of the EpiStats of the last ov2h_epipolar_filtering / ov2h_check_ready_for_init on this map:
+// out[3] = do_optimize, the refinement's status, its LM iterations
+void ov2h_epi_opt_stats(void *p, int *out)
+{
+    const EpiStats &e = ((HostMap *)p)->last_epi;
+    out[0] = e.do_optimize; out[1] = e.refine_status; out[2] = e.refine_iters;
+}
+
+// VisualFrontEnd::checkReadyForInit (:855-984) with keyframe kf_cur taken as the current frame and kf_prev as its keyframe;
+// nransac_iter / fransac_err / finit_parallax as the YAML keys, bdo_random off (seed used as is).  removed[cap]: the ids the
+// stage removed from kf_cur, ascending (count in *n_removed); stats[4] as ov2h_epipolar_filtering (status: the 5-point call's
+// bool).  Returns the reference's bool (0 / 1) or a negative ov2_status.
+int ov2h_check_ready_for_init(void *p, void *ctx, int kf_prev, int kf_cur, int nransac_iter, float fransac_err,
+                              float finit_parallax, unsigned long long seed, int cap, int *removed, int *n_removed, double *stats)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kf_cur);
+    if (!f || !m->map->getKeyframe(kf_prev)) return (int)OV2_ERR_INVALID;
+    std::vector<int> before;
+    for (const auto &kv : f->mapkps_) before.push_back(kv.first);
+    std::sort(before.begin(), before.end());
+    SlamParams &S = *m->st;
+    S.nransac_iter_ = nransac_iter; S.fransac_err_ = fransac_err; S.finit_parallax_ = finit_parallax;
+    S.bdo_random_ = false; S.epi_seed_ = (uint64_t)seed;
+    const int own = f->kfid_;
+    f->kfid_ = kf_prev;
+    m->map->pcurframe_ = f;
+    VisualFrontEnd fe((ov2_ctx *)ctx, m->st, f, m->map, nullptr);
+    EpiStats es;
+    ov2_status s = OV2_OK;
+    const bool ready = fe.checkReadyForInit(&es, &s);
+    f->kfid_ = own;
+    m->last_epi = es;
+    if (stats) { stats[0] = es.status; stats[1] = es.pairs; stats[2] = es.removed; stats[3] = es.gate_removed; }
+    if (s != OV2_OK) return (int)s;
+    int n = 0;
+    for (const int id : before)
+        if (!f->mapkps_.count(id)) { if (n < cap) removed[n] = id; ++n; }
+    if (n_removed) *n_removed = n;
+    return ready ? 1 : 0;
+}
+
+// MultiViewGeometry::compute5ptEssentialMatrixOpt (the reference's call with do_optimize = true): returns its bool (0 / 1) or
+// a negative ov2_status; R9 / t3 / outidx / n_out as ov2h_compute5pt, refine[2] = the refinement's status and LM iterations
+int ov2h_compute5pt_opt(void *ctx, int n, const double *bvs1, const double *bvs2, int nmaxiter, float errth, float fx, float fy,
+                        unsigned long long seed, double *R9, double *t3, int *outidx, int *n_out, int *refine)
+{
+    std::vector<Vec3> a((size_t)n), b((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        a[i] = Vec3{bvs1[3 * i], bvs1[3 * i + 1], bvs1[3 * i + 2]};
+        b[i] = Vec3{bvs2[3 * i], bvs2[3 * i + 1], bvs2[3 * i + 2]};
+    }
+    std::vector<int> out;
+    ov2_status st = OV2_OK;
+    const bool ok = MultiViewGeometry::compute5ptEssentialMatrixOpt((ov2_ctx *)ctx, a, b, nmaxiter, errth, seed, fx, fy, R9, t3,
+                                                                    out, &st, refine);
+    if (st != OV2_OK) return (int)st;
+    for (size_t i = 0; i < out.size(); ++i) outidx[i] = out[i];
+    *n_out = (int)out.size();
+    return ok ? 1 : 0;
 }
 
 // MultiViewGeometry::compute5ptEssentialMatrix (src/multi_view_geometry.cpp:596-697) with the reference's arguments:

@@ -194,41 +194,7 @@ bool SlamManager::checkNewKfReq()
 
 float SlamManager::computeParallax(int kfid, bool do_unrot, bool bmedian, bool b2donly)
 {   // src/visual_front_end.cpp:1069-1142
-    auto pkf = pmap_->getKeyframe(kfid);
-    if (!pkf) return 0.f;
-    double Rkfcur[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (do_unrot) {
-        double Rkfw[9], Rwcur[9];
-        pkf->getTcw().rotation(Rkfw);
-        pcurframe_->getTwc().rotation(Rwcur);
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) Rkfcur[3 * i + j] = Rkfw[3 * i] * Rwcur[j] + Rkfw[3 * i + 1] * Rwcur[3 + j] + Rkfw[3 * i + 2] * Rwcur[6 + j];
-    }
-    float avg_parallax = 0.f;
-    int nbparallax = 0;
-    std::set<float> set_parallax;
-    for (const auto &it : pcurframe_->mapkps_) {
-        const Keypoint &kp = it.second;
-        if (b2donly && kp.is3d_) continue;
-        const Keypoint kfkp = pkf->getKeypointById(kp.lmid_);
-        if (kfkp.lmid_ != kp.lmid_) continue;
-        Point2f unpx = kp.unpx_;
-        if (do_unrot) {
-            const Vec3 b{Rkfcur[0] * kp.bv_.x + Rkfcur[1] * kp.bv_.y + Rkfcur[2] * kp.bv_.z, Rkfcur[3] * kp.bv_.x + Rkfcur[4] * kp.bv_.y + Rkfcur[5] * kp.bv_.z,
-                         Rkfcur[6] * kp.bv_.x + Rkfcur[7] * kp.bv_.y + Rkfcur[8] * kp.bv_.z};
-            const Vec3 px = pkf->pcalib_leftcam_->projectCamToImage(b);
-            unpx = Point2f{(float)px.x, (float)px.y};
-        }
-        const float dx = unpx.x - kfkp.unpx_.x, dy = unpx.y - kfkp.unpx_.y;
-        const float parallax = (float)std::sqrt((double)dx * dx + (double)dy * dy);   // cv::norm(Point2f)
-        avg_parallax += parallax;
-        nbparallax++;
-        if (bmedian) set_parallax.insert(parallax);
-    }
-    if (nbparallax == 0) return 0.f;
-    avg_parallax /= nbparallax;
-    if (bmedian) { auto it = set_parallax.begin(); std::advance(it, set_parallax.size() / 2); avg_parallax = *it; }
-    return avg_parallax;
+    return ov2::computeParallax(*pcurframe_, pmap_->getKeyframe(kfid).get(), do_unrot, bmedian, b2donly);
 }
 
 // ---------------------------------------------------------------------------------------------- MapManager::createKeyframe

@@ -139,6 +139,11 @@ def lib():
                                               C.c_int, ip, dp]
         L.ov2h_compute5pt.argtypes = [C.c_void_p, C.c_int, dp, dp, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
                                       C.c_ulonglong, dp, dp, ip, ip]
+        L.ov2h_epi_opt_stats.argtypes, L.ov2h_epi_opt_stats.restype = [C.c_void_p, ip], None
+        L.ov2h_check_ready_for_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                C.c_ulonglong, C.c_int, ip, ip, dp]
+        L.ov2h_compute5pt_opt.argtypes = [C.c_void_p, C.c_int, dp, dp, C.c_int, C.c_float, C.c_float, C.c_float,
+                                          C.c_ulonglong, dp, dp, ip, ip, ip]
         L.ov2h_get_pose.argtypes = [C.c_void_p, C.c_int, dp]
         L.ov2h_get_landmark.argtypes = [C.c_void_p, C.c_int, dp, ip]
         L.ov2h_count_keypoints.argtypes = [C.c_void_p, C.c_int, ip, ip, ip]
@@ -790,6 +795,22 @@ def compute5pt_essential(ctx, bvs1, bvs2, nmaxiter, errth, boptimize, fx, fy, se
     return bool(r), R.reshape(3, 3), t, out[:nout.value].copy()
 
 
+def compute5pt_essential_opt(ctx, bvs1, bvs2, nmaxiter, errth, fx, fy, seed):
+    """the C++ MultiViewGeometry::compute5ptEssentialMatrixOpt (the reference's call with do_optimize = true: RANSAC, then
+    refine5pt on its inliers) over the C ABI.  returns (success, R (3,3), t (3,), voutliersidx, (refinement status, LM
+    iterations)); a negative status raises"""
+    b1 = np.ascontiguousarray(bvs1, np.float64).reshape(-1, 3)
+    b2 = np.ascontiguousarray(bvs2, np.float64).reshape(-1, 3)
+    n = len(b1)
+    R, t, out, nout, ref = np.zeros(9), np.zeros(3), np.zeros(max(n, 1), np.int32), C.c_int(0), np.zeros(2, np.int32)
+    ip = C.POINTER(C.c_int)
+    r = lib().ov2h_compute5pt_opt(ctx.h, n, _dp(b1), _dp(b2), int(nmaxiter), float(errth), float(fx), float(fy), int(seed),
+                                  _dp(R), _dp(t), out.ctypes.data_as(ip), C.byref(nout), ref.ctypes.data_as(ip))
+    if r < 0:
+        raise RuntimeError(f"compute5ptEssentialMatrixOpt: status {r}")
+    return bool(r), R.reshape(3, 3), t, out[:nout.value].copy(), (int(ref[0]), int(ref[1]))
+
+
 def p3p_ransac(ctx, bvs, vwpts, nmaxiter, errth, boptimize, bdorandom, fx, fy, Twc, use_lmeds=True, seed=0):
     """the C++ MultiViewGeometry::p3pRansac (src/multi_view_geometry.cpp:144-163) over the C ABI.
     returns (success, Twc (7,), voutliersidx); a negative status raises"""
@@ -837,6 +858,51 @@ class TwoViewMap:
 
     def __del__(self):
         self.close()
+
+
+class MonoMap(TwoViewMap):
+    """a monocular map (stereo = 0 sets mono_) of the C++ host mirror: keyframes 0 .. N-1 at the given poses with chosen
+    keypoints; the last one is taken as the current frame and the one before it as its keyframe, to run the mono branch of
+    VisualFrontEnd::epipolar2d2dFiltering and VisualFrontEnd::checkReadyForInit"""
+
+    def __init__(self, K, poses, w=752, h=480):
+        L = lib()
+        K = np.ascontiguousarray(K, np.float64)
+        t_lr7 = np.ascontiguousarray([0.0, 0, 0, 0, 0, 0, 1.0])
+        self.h = L.ov2h_map_create(0, 1, _dp(K), _dp(K), _dp(t_lr7), w, h, 25)
+        self.nkf = len(poses)
+        for kfid, T in enumerate(poses):
+            L.ov2h_map_add_keyframe(self.h, kfid, _dp(np.ascontiguousarray(T, np.float64)))
+
+    def _opt_stats(self, st):
+        o = np.zeros(3, np.int32)
+        lib().ov2h_epi_opt_stats(self.h, o.ctypes.data_as(C.POINTER(C.c_int)))
+        return dict(status=int(st[0]), pairs=int(st[1]), removed=int(st[2]), gate_removed=int(st[3]), do_optimize=int(o[0]),
+                    refine_status=int(o[1]), refine_iters=int(o[2]))
+
+    def epipolar_filtering(self, ctx, nransac_iter=100, fransac_err=3.0, seed=0, cap=1 << 16):
+        """returns (removed ids ascending, stats dict with the do_optimize fields); a negative status raises"""
+        rm, st = np.zeros(cap, np.int32), np.zeros(4)
+        n = lib().ov2h_epipolar_filtering(self.h, ctx.h, self.nkf - 2, self.nkf - 1, int(nransac_iter), float(fransac_err),
+                                          int(seed), cap, rm.ctypes.data_as(C.POINTER(C.c_int)), _dp(st))
+        if n < 0:
+            raise RuntimeError(f"epipolar2d2dFiltering: status {n}")
+        return rm[:n].copy(), self._opt_stats(st)
+
+    def check_ready_for_init(self, ctx, finit_parallax=20.0, nransac_iter=100, fransac_err=3.0, seed=0, cap=1 << 16):
+        """VisualFrontEnd::checkReadyForInit: returns (ready, removed ids ascending, stats dict); a negative status raises"""
+        rm, st, n = np.zeros(cap, np.int32), np.zeros(4), C.c_int(0)
+        r = lib().ov2h_check_ready_for_init(self.h, ctx.h, self.nkf - 2, self.nkf - 1, int(nransac_iter), float(fransac_err),
+                                            float(finit_parallax), int(seed), cap, rm.ctypes.data_as(C.POINTER(C.c_int)),
+                                            C.byref(n), _dp(st))
+        if r < 0:
+            raise RuntimeError(f"checkReadyForInit: status {r}")
+        return bool(r), rm[:n.value].copy(), self._opt_stats(st)
+
+    def pose(self, kfid=None):
+        out = np.zeros(7)
+        assert lib().ov2h_get_pose(self.h, self.nkf - 1 if kfid is None else int(kfid), _dp(out)) == 0
+        return out
 
 
 class TemporalMap(HostMap):

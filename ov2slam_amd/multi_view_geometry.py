@@ -141,6 +141,59 @@ class MultiViewGeometry:
                                                         p(d_seed), p(d_R), p(d_t), p(d_outlier), p(d_gate_bad),
                                                         p(d_status), p(d_info)))
 
+    # -- mono do_optimize: refinement of the 5-point model on its inliers (csrc/relpose.hip) ------------------------------
+    def refine5pt_batch(self, bvs1_list, bvs2_list, K, R0, t0, nmaxiter=10, skip_list=None):
+        """B frames in one launch (ov2_relpose_refine_batch): Levenberg-Marquardt on the spherical Sampson cost of
+        [R | t], |t| = 1, over the pairs skip_list (the RANSAC outlier masks; None = all pairs) admits.  returns dict(status
+        (B,), R (B,3,3), t (B,3) -- the arguments bit for bit where status is 0 --, info (B,2): LM iterations, termination,
+        cost (B,2): initial, final)."""
+        B = len(bvs1_list)
+        n = np.array([len(np.asarray(b).reshape(-1, 3)) for b in bvs1_list], np.int32)
+        if any(len(np.asarray(b).reshape(-1, 3)) != k for b, k in zip(bvs2_list, n)):
+            raise ValueError("bvs1.size() != bvs2.size()")
+        tot = int(n.sum())
+        cat = lambda xs, k, dt: (np.concatenate([np.asarray(x, dt).reshape(-1, k) for x in xs]) if tot
+                                 else np.zeros((1, k), dt))
+        b1, b2 = np.ascontiguousarray(cat(bvs1_list, 3, np.float64)), np.ascontiguousarray(cat(bvs2_list, 3, np.float64))
+        sk = None
+        if skip_list is not None:
+            if any(len(np.asarray(s).reshape(-1)) != k for s, k in zip(skip_list, n)):
+                raise ValueError("skip mask size differs from the pair count")
+            sk = np.ascontiguousarray(cat(skip_list, 1, np.uint8).ravel())
+        K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(B, 4))
+        R = np.ascontiguousarray(np.array(R0, np.float64).reshape(B, 9))
+        t = np.ascontiguousarray(np.array(t0, np.float64).reshape(B, 3))
+        st, info = np.zeros(max(B, 1), np.int32), np.zeros((max(B, 1), 2), np.int32)
+        cost = np.zeros((max(B, 1), 2))
+        c = self.ctx
+        _check(c.h, c.lib.ov2_relpose_refine_batch(c.h, B, _vp(n), _vp(b1), _vp(b2), None if sk is None else _vp(sk), _vp(K),
+                                                   int(nmaxiter), _vp(R), _vp(t), _vp(st), _vp(info), _vp(cost)))
+        return dict(status=st[:B], R=R.reshape(B, 3, 3), t=t, info=info[:B], cost=cost[:B])
+
+    def refine5pt_batch_dev(self, B, d_off, d_bv_kf, d_bv_cur, d_skip, d_K, nmaxiter, d_in_status, d_R, d_t, d_status,
+                            d_info=None, d_cost=None):
+        """device-resident, asynchronous form (ov2_relpose_refine_batch_dev): DeviceArrays in, nothing synchronised.  d_skip,
+        d_R, d_t, d_in_status take the d_outlier, d_R, d_t, d_status of compute5ptEssentialMatrix_batch_dev as they are."""
+        p = lambda a: None if a is None else a.ptr
+        c = self.ctx
+        _check(c.h, c.lib.ov2_relpose_refine_batch_dev(c.h, int(B), p(d_off), p(d_bv_kf), p(d_bv_cur), p(d_skip), p(d_K),
+                                                       int(nmaxiter), p(d_in_status), p(d_R), p(d_t), p(d_status),
+                                                       p(d_info), p(d_cost)))
+
+    def compute5ptEssentialMatrix_opt(self, bvs1, bvs2, nmaxiter, errth, bdorandom, fx, fy, seed=0, nrefine=10):
+        """compute5ptEssentialMatrix(..., boptimize = true, ...) of the reference as this project builds it: the RANSAC
+        (ov2_epipolar_filter_batch, B = 1), then refine5pt on its inliers (src/multi_view_geometry.cpp:672-681); the
+        outlier list stays the RANSAC's.  returns (success, Rwc (3,3), twc (3,) unit, voutliersidx, refined: the
+        refinement's status)."""
+        K = np.array([[fx, fy, 0., 0.]])
+        r = self.compute5ptEssentialMatrix_batch([bvs1], [bvs2], nmaxiter, errth, K, [seed])
+        ok = r["status"][0] >= 1
+        R, t, refined = r["R"][0], r["t"][0], 0
+        if ok:
+            q = self.refine5pt_batch([bvs1], [bvs2], K, R, t, nrefine, [r["outlier"][0]])
+            R, t, refined = q["R"][0], q["t"][0], int(q["status"][0])
+        return bool(ok), R, t, np.flatnonzero(r["outlier"][0]).astype(np.int32), refined
+
     def dbg_fivept(self, bv1, bv2):
         """the device 5-point solver on n samples (ov2_dbg_fivept): bv1, bv2 (n,5,3) -> E (n,10,3,3), nsol (n,)"""
         bv1, bv2 = np.ascontiguousarray(bv1, np.float64).reshape(-1, 5, 3), np.ascontiguousarray(bv2, np.float64).reshape(-1, 5, 3)
