@@ -941,8 +941,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KLT_WAVES(WI
 // stereoMatching has no such rule and long list-B waves: there list B's descent is cut in two at a pyramid level, its upper
 // levels run in the first launch beside list A and the rest in the second launch behind list C (unsplit: all of it in the
 // second launch, in front of list C).
-__global__ __launch_bounds__(256) void klt_compact_kernel(int n, int pass, const unsigned char *__restrict__ has_prior,
-                                                          const unsigned char *__restrict__ out_status,
+// Eight keypoints per thread, so a workgroup lists 2048 keypoints and pays ONE returning atomic per list: the atomics on
+// the list lengths serialise, and with a keypoint per thread (1024 of them at the bench shape) they were most of the
+// kernel's duration.  A wave takes 512 consecutive keypoints, slot k of lane l is keypoint 64 k + l of
+// them: the ranks come from a ballot and its prefix count per slot (no cross-lane move), the lanes of every load and store
+// instruction touch consecutive addresses, and BOTH LISTS STAY IN ASCENDING ORDER inside a workgroup.  The tracking
+// kernels are correct for any order but not equally fast: their waves take 21 consecutive list entries, and neighbours in
+// the caller's arrays are neighbours in the image (with each thread's eight keypoints side by side, i.e. list entries eight
+// keypoints apart, the frame rate was a quarter lower).  Every global store stands behind the atomic, so the kernel waits for
+// memory three times (flags, atomic, stores) as it did with a keypoint per thread.
+#define KLT_COMPACT_KPT 8
+#define KLT_COMPACT_KPWG (256 * KLT_COMPACT_KPT)
+__global__ __launch_bounds__(256) void klt_compact_kernel(int n, const unsigned char *__restrict__ has_prior,
                                                           unsigned *__restrict__ iters, int *__restrict__ list_a,
                                                           int *__restrict__ list_b, unsigned *__restrict__ cnt,
                                                           int *__restrict__ p3p_req, int batch, int wave_prio)
@@ -950,35 +960,43 @@ __global__ __launch_bounds__(256) void klt_compact_kernel(int n, int pass, const
     ov2wave::set_wave_prio(wave_prio);
     __shared__ int wsum[2][4];
     __shared__ int wbase[2];
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    bool la = false, lb = false;
-    if (f < n) {
-        const bool hp = has_prior[f] != 0;
-        if (pass == 1) {
-            la = hp; lb = !hp;
-            if (iters) iters[hp ? n + f : f] = 0;   // the slot of the stage the keypoint does not take (so far)
-        } else {
-            la = hp && out_status[f] == 0;
-        }
-    }
-    if (pass == 1 && p3p_req)
-        for (int k = f; k < batch; k += gridDim.x * 256) p3p_req[k] = 0;
-    const unsigned long long ma = __ballot(la), mb = __ballot(lb);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const int ra = __popcll(ma & below), rb = __popcll(mb & below);
-    if (lane == 0) { wsum[0][wv] = __popcll(ma); wsum[1][wv] = __popcll(mb); }
+    const int f0 = blockIdx.x * KLT_COMPACT_KPWG + wv * (64 * KLT_COMPACT_KPT) + lane;   // slot k: keypoint f0 + 64 k
+    unsigned char hp[KLT_COMPACT_KPT];
+#pragma unroll
+    for (int k = 0; k < KLT_COMPACT_KPT; ++k) hp[k] = f0 + 64 * k < n ? has_prior[f0 + 64 * k] : 0;
+    int pos[KLT_COMPACT_KPT];   // rank of the slot's keypoint among the wave's entries of its list
+    int ta = 0, tb = 0;
+#pragma unroll
+    for (int k = 0; k < KLT_COMPACT_KPT; ++k) {
+        const bool v = f0 + 64 * k < n, p = hp[k] != 0;
+        const unsigned long long ba = __ballot(v && p), bb = __ballot(v && !p);
+        const int ra = ta + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ba >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ba, 0u));
+        const int rb = tb + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bb, 0u));
+        ta += __popcll(ba); tb += __popcll(bb);
+        pos[k] = p ? ra : rb;
+    }
+    if (lane == 0) { wsum[0][wv] = ta; wsum[1][wv] = tb; }
     __syncthreads();
     if (threadIdx.x < 2) {
         const int q = threadIdx.x;
         const int tot = wsum[q][0] + wsum[q][1] + wsum[q][2] + wsum[q][3];
-        wbase[q] = tot ? (int)atomicAdd(&cnt[pass == 1 ? q : 2], (unsigned)tot) : 0;
+        wbase[q] = tot ? (int)atomicAdd(&cnt[q], (unsigned)tot) : 0;
     }
     __syncthreads();
     int oa = wbase[0], ob = wbase[1];
     for (int k = 0; k < wv; ++k) { oa += wsum[0][k]; ob += wsum[1][k]; }
-    if (la) list_a[oa + ra] = f;
-    if (lb) list_b[ob + rb] = f;
+#pragma unroll
+    for (int k = 0; k < KLT_COMPACT_KPT; ++k) {
+        const int f = f0 + 64 * k;
+        if (f < n) {
+            const bool p = hp[k] != 0;
+            (p ? list_a : list_b)[(p ? oa : ob) + pos[k]] = f;
+            if (iters) iters[p ? n + f : f] = 0;   // the slot of the stage the keypoint does not take (so far)
+        }
+    }
+    if (p3p_req)
+        for (int k = blockIdx.x * 256 + threadIdx.x; k < batch; k += gridDim.x * 256) p3p_req[k] = 0;
 }
 
 // what the first launch does with a finished keypoint: result, status, work word, the per-image tally of list A and the
@@ -1359,7 +1377,7 @@ ov2_status ov2_klt_two_stage_dev(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr 
         OV2_HIP(c, hipEventRecord(c->kf.fork, c->stream.h));
         c->kf.want_stereo_ev = false;
     }
-    const dim3 cgrid((n + 255) / 256);
+    const dim3 cgrid((n + KLT_COMPACT_KPWG - 1) / KLT_COMPACT_KPWG);
     // which launch tracks list B: the first for kltTracking (the 33 % rule orders the re-tracking behind list A's tally, and
     // B fills the first launch), the second for stereoMatching (see klt_stage2_kernel).  The other launch reads B's length
     // from word 3 of the list-length block, which nothing writes: zero, so its B segment is empty
@@ -1374,8 +1392,8 @@ ov2_status ov2_klt_two_stage_dev(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr 
     do {                                                                                                        \
         /* two disjoint lists of the n keypoints: groups of the one + groups of the other <= ceil(n / KPW) + 2 */ \
         const dim3 tgrid((n + klt_map<G>::KPW - 1) / klt_map<G>::KPW + 2);                                      \
-        OV2_LAUNCH(c, OV2_K_DETECT + 4, klt_compact_kernel, cgrid, dim3(256), 0, c->stream, n, 1, d_has_prior,  \
-                   d_out_status, d_iters, list_a, list_b, live_cnt, d_p3p_req, B, P.wave_prio);                 \
+        OV2_LAUNCH(c, OV2_K_DETECT + 4, klt_compact_kernel, cgrid, dim3(256), 0, c->stream, n, d_has_prior,     \
+                   d_iters, list_a, list_b, live_cnt, d_p3p_req, B, P.wave_prio);                               \
         if (split_k >= 0)                                                                                       \
             OV2_LAUNCH(c, OV2_K_KLT_STAGE1, (klt_stage1_kernel<W, G, true>), tgrid, dim3(64), 0, c->stream,     \
                        prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps),          \
