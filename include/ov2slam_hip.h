@@ -65,6 +65,48 @@ ov2_status ov2_ctx_set_kf_overlap(ov2_ctx *ctx, int on);
 #define OV2_WAVE_PRIO_HIGH 2
 ov2_status ov2_ctx_set_wave_prio(ov2_ctx *ctx, int level);
 int ov2_ctx_get_wave_prio(const ov2_ctx *ctx);   /* -1 for a null context */
+/* A CU share: a context whose three kernel streams (main, pyramid, keyframe side stream) run on n_cus compute units of
+ * the device only, through one CU mask shared by the three (hipExtStreamCreateWithCUMask).  It is for the context that
+ * yields (the local-BA worker): confined to its share it leaves the other compute units, with their wave slots, registers
+ * and LDS, to the contexts it shares the GPU with.  The copy stream of the batched BA upload launches no kernel and is
+ * not masked.  Results do not depend on the share.
+ *   n_cus == 0            no mask: the streams of ov2_ctx_create_ex
+ *   0 < n_cus < device's  masked; layout OV2_CU_LAYOUT_SPREAD deals the compute units evenly over the XCDs,
+ *                         OV2_CU_LAYOUT_PACKED fills whole XCDs first
+ *   OV2_ERR_INVALID       n_cus < 0, n_cus >= the device's compute units, another layout, and n_cus > 0 together with
+ *                         high_priority (the masked create call of HIP has no priority argument)
+ * What confines, as measured on an MI355X (scripts/micro/cu_mask_probe.hip): bit k of a mask is a
+ * compute unit of XCD k % 8, and an XCD runs on as many compute units as the mask gives it bits -- but on ALL of its
+ * compute units when the mask gives it none.  A share is therefore confined to n_cus compute units only when every XCD
+ * gets a bit: the spread layout with n_cus >= 8.  A smaller spread share and every packed share that leaves an XCD out
+ * are accepted and compute the same results, but run on the whole of the XCDs left out (spread n_cus = 1: 1 + 7 x 32
+ * compute units); the matcher's automatic sizing counts those.
+ * What a share changes besides the confinement: the masked streams have NORMAL stream priority (the streams of a
+ * normal-priority context without a share have the lowest), and they are BLOCKING streams: they order against the legacy
+ * default stream of the device, so work the process puts on the default stream (a library that was not given a stream)
+ * waits for the context's kernels in flight and the other way round.  Nothing deadlocks; the two serialise.
+ * The matcher's automatic sizing (ov2_knn2_hamming_batch, ov2_lcd_search2_batch) counts the compute units the share
+ * runs on in place of the device's.
+ *
+ * Default rule of ov2_ctx_create / ov2_ctx_create_ex: a context created with high_priority == 0 WHILE a high-priority
+ * context of this process is alive on the same device takes the default share OV2_WORKER_CUS_DEFAULT in layout
+ * OV2_WORKER_CU_LAYOUT_DEFAULT; a normal-priority context alone on the device is never masked, nor is one created
+ * before the high-priority context.  OV2_WORKER_CUS=n (0 = off) and OV2_WORKER_CU_LAYOUT=0|1 in the environment replace
+ * the two defaults; they are read once per process.  A default the device cannot give (n >= its compute units) is off. */
+#define OV2_CU_LAYOUT_SPREAD 0
+#define OV2_CU_LAYOUT_PACKED 1
+#define OV2_WORKER_CUS_DEFAULT 128         /* 0 = off; half an MI355X ("A CU share for the worker") */
+#define OV2_WORKER_CU_LAYOUT_DEFAULT OV2_CU_LAYOUT_SPREAD
+ov2_status ov2_ctx_create_cu(int device, int high_priority, int n_cus, int layout, ov2_ctx **out);
+int ov2_ctx_get_cu_share(const ov2_ctx *ctx);    /* n_cus of the context, 0 without a share, -1 for a null context */
+/* what hipExtStreamGetCUMask reports for the context's main stream, `words` 32-bit words of it */
+ov2_status ov2_ctx_get_cu_mask(ov2_ctx *ctx, int words, uint32_t *out);
+/* The mask of a share, a plain host function (no device needed): (total_cus + 31) / 32 words, n_cus bits set, none at or
+ * past total_cus.  Bit k of a mask is compute unit k / OV2_CU_MASK_XCDS of XCD k % OV2_CU_MASK_XCDS.  Spread sets bits
+ * 0 .. n_cus - 1; packed sets every bit of XCD 0, then of XCD 1, ...  OV2_ERR_INVALID for n_cus <= 0, n_cus >= total_cus,
+ * another layout or a null pointer. */
+#define OV2_CU_MASK_XCDS 8
+ov2_status ov2_cu_mask_build(int total_cus, int n_cus, int layout, uint32_t *words_out);
 /* Depth of the pyramid pool's ring, n = 1 .. 8 (anything else: OV2_ERR_INVALID, the depth stays; default 3; OV2_PYR_RING=n
  * in the environment starts a context with depth n).  Released pyramid buffers go back to a pool per context.  A build
  * takes a pooled buffer of its geometry whose readers have finished if there is one; otherwise it allocates a new buffer
@@ -627,6 +669,10 @@ ov2_status ov2_knn2_hamming_batch_dev(ov2_ctx *ctx, int B, int total_query, cons
 /* Lanes that share one query and split its train rows between them: 1, 4, 16 or 64 forces that mapping (tests, tuning; all
  * give the same bits), 0 (default) picks by the number of query rows of the call.  Anything else is OV2_ERR_INVALID. */
 ov2_status ov2_knn_set_lanes(ov2_ctx *ctx, int lanes);
+/* The lanes per query a call of total_query query rows takes on this context (no device work): the forced mapping, or
+ * with 0 set the automatic choice -- the fewest lanes that give every compute unit the context runs on (its CU share,
+ * ov2_ctx_create_cu, else the device) a workgroup of 256 threads.  -1 for a null context or a negative count. */
+int ov2_knn_lanes_for(ov2_ctx *ctx, int total_query);
 
 /* ---------------------------------------------------------------------------------------------------
  * Loop detection: the visual-word table of one incremental index, resident in HBM, and the exact search in it.

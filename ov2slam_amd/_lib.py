@@ -26,6 +26,10 @@ SIGNATURES = {
     "ov2_ctx_set_kf_overlap": (C.c_int, [vp, C.c_int]),
     "ov2_ctx_set_wave_prio": (C.c_int, [vp, C.c_int]),
     "ov2_ctx_get_wave_prio": (C.c_int, [vp]),
+    "ov2_ctx_create_cu": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vpp]),
+    "ov2_ctx_get_cu_share": (C.c_int, [vp]),
+    "ov2_ctx_get_cu_mask": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint32)]),
+    "ov2_cu_mask_build": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "ov2_ctx_set_pyr_ring": (C.c_int, [vp, C.c_int]),
     "ov2_ctx_pyr_pool_stats": (C.c_int, [vp, C.POINTER(C.c_int32)]),
     "ov2_ctx_pyr_wait_stats": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -127,6 +131,7 @@ SIGNATURES = {
     "ov2_knn2_hamming_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     "ov2_knn2_hamming_batch_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "ov2_knn_set_lanes": (C.c_int, [vp, C.c_int]),
+    "ov2_knn_lanes_for": (C.c_int, [vp, C.c_int]),
     "ov2_lcd_table_create": (C.c_int, [vp, C.c_int, vpp]),
     "ov2_lcd_table_destroy": (None, [vp]),
     "ov2_lcd_table_append": (C.c_int, [vp, vp, C.c_int, vp, ip]),

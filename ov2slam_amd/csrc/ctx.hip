@@ -34,7 +34,92 @@ extern "C" const char *ov2_last_error(const ov2_ctx *ctx) { return ctx ? ctx->er
 
 extern "C" ov2_status ov2_ctx_create(int device, ov2_ctx **out) { return ov2_ctx_create_ex(device, 0, out); }
 
+// ---- CU share ---------------------------------------------------------------------------------------
+// Bit k of a stream's CU mask is compute unit k / OV2_CU_MASK_XCDS of XCD k % OV2_CU_MASK_XCDS: the driver deals the bits
+// of a mask round-robin over the XCDs of the device, and an XCD that gets no bit runs on all of its compute units
+// (measured with scripts/micro/cu_mask_probe.hip).
+extern "C" ov2_status ov2_cu_mask_build(int total_cus, int n_cus, int layout, uint32_t *words_out)
+{
+    if (!words_out || total_cus <= 0 || n_cus <= 0 || n_cus >= total_cus || (layout != OV2_CU_LAYOUT_SPREAD && layout != OV2_CU_LAYOUT_PACKED))
+        return OV2_ERR_INVALID;
+    const int words = (total_cus + 31) / 32;
+    for (int w = 0; w < words; ++w) words_out[w] = 0;
+    int left = n_cus;
+    if (layout == OV2_CU_LAYOUT_SPREAD) {
+        // dealt evenly: the first n bits visit the XCDs in turn
+        for (int k = 0; k < n_cus; ++k) words_out[k >> 5] |= 1u << (k & 31);
+        return OV2_OK;
+    }
+    // packed: every compute unit of XCD 0, then of XCD 1, ...
+    for (int x = 0; x < OV2_CU_MASK_XCDS && left > 0; ++x)
+        for (int k = x; k < total_cus && left > 0; k += OV2_CU_MASK_XCDS, --left) words_out[k >> 5] |= 1u << (k & 31);
+    return OV2_OK;
+}
+
+namespace {
+
+constexpr int MAX_DEVICES = 64;
+constexpr int MAX_MASK_WORDS = 32;   // 1024 compute units
+std::mutex g_live_mu;
+int g_live_high[MAX_DEVICES];        // live high-priority contexts of this process per device (under g_live_mu)
+
+struct cu_share_defaults {
+    int cus, layout;
+};
+
+// OV2_WORKER_CUS (0 = off, or a count) and OV2_WORKER_CU_LAYOUT (0 = spread, 1 = packed) override the built-in default
+// share of a normal-priority context that is created beside a high-priority one; read once per process
+const cu_share_defaults &worker_cu_defaults()
+{
+    static const cu_share_defaults d = [] {
+        cu_share_defaults v = {OV2_WORKER_CUS_DEFAULT, OV2_WORKER_CU_LAYOUT_DEFAULT};
+        if (const char *e = getenv("OV2_WORKER_CUS")) v.cus = atoi(e);
+        if (const char *e = getenv("OV2_WORKER_CU_LAYOUT")) v.layout = atoi(e);
+        if (v.cus < 0) v.cus = 0;
+        if (v.layout != OV2_CU_LAYOUT_SPREAD && v.layout != OV2_CU_LAYOUT_PACKED) v.layout = OV2_WORKER_CU_LAYOUT_DEFAULT;
+        return v;
+    }();
+    return d;
+}
+
+int device_cus(int device)
+{
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
+    return cus;
+}
+
+ov2_status ctx_create(int device, int high_priority, int n_cus, int layout, ov2_ctx **out);
+
+}  // namespace
+
 extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx **out)
+{
+    // the default rule: a normal-priority context takes the default share while a high-priority context of this process
+    // lives on the same device -- it is the one that yields; alone on the device it is never masked
+    int n_cus = 0, layout = OV2_CU_LAYOUT_SPREAD;
+    if (!high_priority && device >= 0 && device < MAX_DEVICES && worker_cu_defaults().cus > 0) {
+        bool beside_high;
+        { std::lock_guard<std::mutex> g(g_live_mu); beside_high = g_live_high[device] > 0; }
+        if (beside_high && worker_cu_defaults().cus < device_cus(device)) {   // a share the device cannot give is no share
+            n_cus = worker_cu_defaults().cus;
+            layout = worker_cu_defaults().layout;
+        }
+    }
+    return ctx_create(device, high_priority, n_cus, layout, out);
+}
+
+extern "C" ov2_status ov2_ctx_create_cu(int device, int high_priority, int n_cus, int layout, ov2_ctx **out)
+{
+    if (!out) return OV2_ERR_INVALID;
+    *out = nullptr;
+    if (n_cus < 0 || (n_cus > 0 && high_priority) || (layout != OV2_CU_LAYOUT_SPREAD && layout != OV2_CU_LAYOUT_PACKED)) return OV2_ERR_INVALID;
+    return ctx_create(device, high_priority, n_cus, layout, out);
+}
+
+namespace {
+
+ov2_status ctx_create(int device, int high_priority, int n_cus, int layout, ov2_ctx **out)
 {
     if (!out) return OV2_ERR_INVALID;
     *out = nullptr;
@@ -42,6 +127,19 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return OV2_ERR_NODEVICE;  // never a CPU fallback
     if (device < 0 || device >= ndev) return OV2_ERR_INVALID;
     if (hipSetDevice(device) != hipSuccess) return OV2_ERR_HIP;
+    uint32_t mask[MAX_MASK_WORDS];
+    int mask_words = 0, effective_cus = 0;
+    if (n_cus > 0) {
+        const int total = device_cus(device);
+        if (n_cus >= total || total > 32 * MAX_MASK_WORDS || ov2_cu_mask_build(total, n_cus, layout, mask) != OV2_OK) return OV2_ERR_INVALID;
+        mask_words = (total + 31) / 32;
+        // an XCD the mask gives no bit is not confined: it runs on all of its compute units (header, ov2_ctx_create_cu)
+        for (int x = 0; x < OV2_CU_MASK_XCDS; ++x) {
+            int bits = 0, own = 0;
+            for (int k = x; k < total; k += OV2_CU_MASK_XCDS, ++own) bits += (int)(mask[k >> 5] >> (k & 31) & 1u);
+            effective_cus += bits ? bits : own;
+        }
+    }
     ov2_ctx *c = new ov2_ctx();
     c->device = device;
     c->scratch_dev = nullptr;
@@ -52,7 +150,10 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     c->klt_lanes = 0;
     c->klt_stereo_split = -1;
     c->knn_lanes = 0;
-    c->knn_cus = 0;
+    c->knn_cus = effective_cus;   // compute units the share runs on; 0 (no share): the device's count, read on first use
+    c->cu_share = n_cus;
+    c->cu_layout = layout;
+    c->counts_as_high = false;
     c->lcd_splits = 0;
     c->lcd_calls = 0;
     c->ba_arena = nullptr;
@@ -90,23 +191,42 @@ extern "C" ov2_status ov2_ctx_create_ex(int device, int high_priority, ov2_ctx *
     c->pyr_waits[2].store(0);
     // three streams of one priority: tracking / BA, pyramid builds, keyframe detector chain (a pyramid stream one level
     // more urgent than the other two was measured and changes nothing, DESIGN.md section 7 "A ring for the pyramid pool")
-    int prio_least = 0, prio_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    const int prio = high_priority ? prio_greatest : prio_least;
-    const hipError_t e1 = hipStreamCreateWithPriority(&c->stream.h, hipStreamNonBlocking, prio);
-    const hipError_t e2 = hipStreamCreateWithPriority(&c->stream_pyr, hipStreamNonBlocking, prio);
-    const hipError_t e3 = hipStreamCreateWithPriority(&c->stream_kf, hipStreamNonBlocking, prio);
+    hipError_t e1, e2, e3;
+    if (n_cus > 0) {
+        // a CU share: the three streams carry one mask.  The masked create call takes neither a priority nor flags: these
+        // are blocking streams of normal priority (include/ov2slam_hip.h, ov2_ctx_create_cu)
+        e1 = hipExtStreamCreateWithCUMask(&c->stream.h, (uint32_t)mask_words, mask);
+        e2 = hipExtStreamCreateWithCUMask(&c->stream_pyr, (uint32_t)mask_words, mask);
+        e3 = hipExtStreamCreateWithCUMask(&c->stream_kf, (uint32_t)mask_words, mask);
+    } else {
+        int prio_least = 0, prio_greatest = 0;
+        (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+        const int prio = high_priority ? prio_greatest : prio_least;
+        e1 = hipStreamCreateWithPriority(&c->stream.h, hipStreamNonBlocking, prio);
+        e2 = hipStreamCreateWithPriority(&c->stream_pyr, hipStreamNonBlocking, prio);
+        e3 = hipStreamCreateWithPriority(&c->stream_kf, hipStreamNonBlocking, prio);
+    }
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess ||
         hipEventCreateWithFlags(&c->kf.fork, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
         hipEventCreateWithFlags(&c->kf.done, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreateWithFlags(&c->stage_ev, hipEventDisableTiming) != hipSuccess) {
+        if (e1 == hipSuccess) (void)hipStreamDestroy(c->stream.h);
+        if (e2 == hipSuccess) (void)hipStreamDestroy(c->stream_pyr);
+        if (e3 == hipSuccess) (void)hipStreamDestroy(c->stream_kf);
         delete c;
         return OV2_ERR_HIP;
+    }
+    if (high_priority && device < MAX_DEVICES) {
+        std::lock_guard<std::mutex> g(g_live_mu);
+        ++g_live_high[device];
+        c->counts_as_high = true;
     }
     *out = c;
     return OV2_OK;
 }
+
+}  // namespace
 
 extern "C" void ov2_ctx_destroy(ov2_ctx *c)
 {
@@ -139,6 +259,10 @@ extern "C" void ov2_ctx_destroy(ov2_ctx *c)
     (void)hipStreamDestroy(c->stream_kf);
     (void)hipStreamDestroy(c->stream_pyr);
     (void)hipStreamDestroy(c->stream.h);
+    if (c->counts_as_high) {
+        std::lock_guard<std::mutex> g(g_live_mu);
+        --g_live_high[c->device];
+    }
     delete c;
 }
 
@@ -168,6 +292,16 @@ extern "C" ov2_status ov2_ctx_set_wave_prio(ov2_ctx *c, int level)
 }
 
 extern "C" int ov2_ctx_get_wave_prio(const ov2_ctx *c) { return c ? c->wave_prio : -1; }
+
+extern "C" int ov2_ctx_get_cu_share(const ov2_ctx *c) { return c ? c->cu_share : -1; }
+
+extern "C" ov2_status ov2_ctx_get_cu_mask(ov2_ctx *c, int words, uint32_t *out)
+{
+    if (!c || !out || words <= 0) return OV2_ERR_INVALID;
+    OV2_HIP(c, hipSetDevice(c->device));
+    OV2_HIP(c, hipExtStreamGetCUMask(c->stream.h, (uint32_t)words, out));
+    return OV2_OK;
+}
 
 void ov2_pyr_buf_free(ov2_pyr_buf *b)
 {

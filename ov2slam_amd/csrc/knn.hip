@@ -88,8 +88,8 @@ __global__ __launch_bounds__(KNN_THREADS) void knn2_kernel(const knn_args A)
 
 inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
-// Lanes per query when ov2_knn_set_lanes is 0: the fewest lanes that still give every compute unit of the device a
-// workgroup.  Measured on an MI355X (scripts/knn_time.py, profiles/README.md).
+// Lanes per query when ov2_knn_set_lanes is 0: the fewest lanes that still give every compute unit the context runs on
+// (its CU share, else the device: ov2_ctx::knn_cus) a workgroup.  Measured on an MI355X (scripts/knn_time.py, profiles/README.md).
 int knn_lanes_for(const ov2_ctx *c, int total_q)
 {
     if (c->knn_lanes) return c->knn_lanes;
@@ -98,7 +98,23 @@ int knn_lanes_for(const ov2_ctx *c, int total_q)
     return 64;
 }
 
+ov2_status knn_cus(ov2_ctx *c)
+{
+    if (!c->knn_cus) {
+        int cus = 0;
+        OV2_HIP(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        c->knn_cus = cus > 0 ? cus : 1;
+    }
+    return OV2_OK;
+}
+
 }  // namespace
+
+extern "C" int ov2_knn_lanes_for(ov2_ctx *c, int total_query)
+{
+    if (!c || total_query < 0 || knn_cus(c) != OV2_OK) return -1;
+    return knn_lanes_for(c, total_query);
+}
 
 extern "C" ov2_status ov2_knn_set_lanes(ov2_ctx *c, int lanes)
 {
@@ -125,11 +141,8 @@ extern "C" ov2_status ov2_knn2_hamming_batch_dev(ov2_ctx *c, int B, int total_qu
         return ov2_set_err(c, OV2_ERR_INVALID, "ov2_knn2_hamming_batch_dev: descriptor arrays must be 16-byte aligned");
     if (B == 0 || total_query == 0) return OV2_OK;
     OV2_HIP(c, hipSetDevice(c->device));
-    if (!c->knn_cus) {
-        int cus = 0;
-        OV2_HIP(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        c->knn_cus = cus > 0 ? cus : 1;
-    }
+    const ov2_status cs = knn_cus(c);
+    if (cs != OV2_OK) return cs;
     knn_args A;
     A.B = B; A.total_q = total_query; A.q_off = d_q_off; A.t_off = d_t_off;
     A.query = (const uint4 *)d_query; A.train = (const uint4 *)d_train; A.idx = d_idx; A.dist = d_dist;

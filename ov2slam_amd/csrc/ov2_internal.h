@@ -144,7 +144,10 @@ struct ov2_ctx {
     int klt_lanes;                       // ov2_klt_set_lanes: 0 = by call size, 3 / 8 / 16 = forced lanes per keypoint
     int klt_stereo_split;                // ov2_klt_set_stereo_split: the level stereoMatching's list B resumes at in the second launch, -1 = built-in
     int knn_lanes;                       // ov2_knn_set_lanes: 0 = by call size, 1 / 4 / 16 / 64 = forced lanes per query
-    int knn_cus;                         // compute units of the device (read on first use by the matcher's automatic choice)
+    int knn_cus;                         // compute units the matcher's automatic choice sizes for: the context's CU share, or the
+                                         //   device's count (read on first use)
+    int cu_share, cu_layout;             // ov2_ctx_create_cu: compute units the three kernel streams are masked to (0 = no mask)
+    bool counts_as_high;                 // counted among the live high-priority contexts of its device (the default share rule)
     int lcd_splits;                      // ov2_lcd_set_splits: 0 = by call size, otherwise the forced number of train-axis splits
     long long lcd_calls;                 // ov2_lcd_search2_batch(_dev) calls that launched (ov2_lcd_search_calls)
     std::vector<struct ov2_lcd_table *> lcd_tables;   // live word tables (their device memory is released with the ctx)

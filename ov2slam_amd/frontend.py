@@ -16,6 +16,19 @@ from . import _lib
 WAVE_PRIO_HIGH = 2   # OV2_WAVE_PRIO_HIGH of include/ov2slam_hip.h: the wave priority a high-priority context starts at
 
 
+CU_LAYOUT_SPREAD, CU_LAYOUT_PACKED = 0, 1   # OV2_CU_LAYOUT_* of include/ov2slam_hip.h
+CU_MASK_XCDS = 8                            # OV2_CU_MASK_XCDS: bit k of a CU mask is compute unit k // 8 of XCD k % 8
+
+
+def cu_mask_build(total_cus, n_cus, layout=CU_LAYOUT_SPREAD):
+    """ov2_cu_mask_build: the mask of a share as (total_cus + 31) // 32 uint32 words (a host function, no device needed)"""
+    out = (C.c_uint32 * ((int(total_cus) + 31) // 32 if total_cus > 0 else 1))()
+    st = _lib.load().ov2_cu_mask_build(int(total_cus), int(n_cus), int(layout), out)
+    if st != 0:
+        raise _lib.Ov2Error(f"ov2_cu_mask_build({total_cus}, {n_cus}, {layout}): status {st}")
+    return np.array(out, np.uint32)
+
+
 def _check(ctx_handle, status):
     if status != 0:
         lib = _lib.load()
@@ -26,10 +39,18 @@ def _check(ctx_handle, status):
 class Context:
     """one device + one HIP stream (reference: one per calling thread, T1 front-end / T3 mapper)."""
 
-    def __init__(self, device=0, high_priority=False):
+    def __init__(self, device=0, high_priority=False, cu_share=None, cu_layout=CU_LAYOUT_SPREAD):
+        """cu_share None: ov2_ctx_create_ex and its default rule (a normal-priority context created while a high-priority
+        one lives on the device takes the default share); a number: ov2_ctx_create_cu with exactly that share (0 = none)"""
         self.lib = _lib.load()
         h = C.c_void_p()
-        st = self.lib.ov2_ctx_create_ex(device, int(bool(high_priority)), C.byref(h))
+        if cu_share is None:
+            st = self.lib.ov2_ctx_create_ex(device, int(bool(high_priority)), C.byref(h))
+        else:
+            st = self.lib.ov2_ctx_create_cu(device, int(bool(high_priority)), int(cu_share), int(cu_layout), C.byref(h))
+            if st == -1:
+                raise _lib.Ov2Error(f"ov2_ctx_create_cu(device={device}, high_priority={bool(high_priority)}, n_cus={cu_share}, "
+                                    f"layout={cu_layout}): {self.lib.ov2_status_string(st).decode()}")
         if st != 0:
             raise _lib.Ov2Error(f"ov2_ctx_create(device={device}): {self.lib.ov2_status_string(st).decode()} -- "
                                 "an MI355X/gfx950 device is required, there is no CPU fallback")
@@ -67,6 +88,16 @@ class Context:
     def get_wave_prio(self):
         """ov2_ctx_get_wave_prio: OV2_WAVE_PRIO_HIGH on a fresh high-priority context, 0 on any other"""
         return int(self.lib.ov2_ctx_get_wave_prio(self.h))
+
+    def get_cu_share(self):
+        """ov2_ctx_get_cu_share: compute units the context's kernel streams are masked to, 0 = no mask"""
+        return int(self.lib.ov2_ctx_get_cu_share(self.h))
+
+    def get_cu_mask(self, words):
+        """ov2_ctx_get_cu_mask: the CU mask HIP reports for the main stream, `words` uint32"""
+        out = (C.c_uint32 * int(words))()
+        _check(self.h, self.lib.ov2_ctx_get_cu_mask(self.h, int(words), out))
+        return np.array(out, np.uint32)
 
     def set_pyr_ring(self, n):
         """ov2_ctx_set_pyr_ring: released pyramid buffers of one geometry, readers still pending, that the pool holds before
