@@ -1142,6 +1142,66 @@ typedef struct ov2_match_input {
 ov2_status ov2_match_to_map(ov2_ctx *ctx, const ov2_match_input *in, float fmaxprojerr, float fdistratio,
                             int32_t *match_cand /* n_kp */, float *match_dist /* n_kp */);
 
+/* Mapper::matchToMap for B frames in one call, one local map each: the algorithm of ov2_match_to_map (NOT the loop closer's
+ * below), the layout of ov2_loop_match_input.
+ *
+ * Layout: frame b owns keypoints kp_off[b] .. kp_off[b + 1], candidates cand_off[b] .. cand_off[b + 1] and keyframe poses
+ * kf_off[b] .. kf_off[b + 1] of the flat arrays (n_kp = kp_off[B], n_cand = cand_off[B]; every offset array starts at 0); the
+ * *_ptr arrays are prefix offsets over the WHOLE flat arrays (n + 1 entries).  Keypoints, candidates, descriptor sets,
+ * keyframe lists and kp_kf_px are what ov2_match_input lists, per frame.  A keyframe id names the pose kf_off[b] + kfid of
+ * kf_Twc; an id outside [0, kf_off[b + 1] - kf_off[b]) is skipped in the mean-reprojection loop, as ov2_match_to_map skips
+ * kfid >= n_kf.  grid: one CSR grid per frame, frame b's cells at grid_ptr[b * ncells .. (b + 1) * ncells] (ncells =
+ * ceil(img_w / cell) * ceil(img_h / cell), row-major, B * ncells + 1 entries over the flat grid_kp); grid_kp holds keypoint
+ * indices WITHIN the frame, in Frame::vgridkps_ order (it decides ties).  One camera per call.
+ *
+ * Per frame the semantics are exactly those of ov2_match_to_map: Mapper's view_th (the QUOTIENTS 0.5 * img_h / fy and
+ * 0.5 * img_w / fx of :586-587), dmaxpxdist = fmaxprojerr DOUBLED for a frame with nb3dkps[b] < 30 (:599-602, a per-frame value
+ * inside one launch), the pixel gate, the co-observation test, the mean reprojection distance in the keypoint's keyframes
+ * (:700-719, 0 / 0 compares false), MapPoint::computeMinDescDist, best / second best replayed in order with `<=`, the 0.9
+ * ratio; per keypoint the smallest distance wins, the LATER candidate on ties.
+ *
+ * match_cand[k] = the candidate's index WITHIN ITS OWN FRAME, or -1; match_dist[k] = its Hamming distance (0 with -1).
+ * Only integers and gate decisions come out: a frame's results are bit-identical to ov2_match_to_map on that frame alone,
+ * whatever the batch contains, in any order, for any workgroup shape, in either form.
+ * Host form: host pointers (cam included); one staging block, one upload, one memset, two launches, one download and one
+ * synchronisation whatever B is.  B = 0, a frame without keypoints and a frame without candidates are OV2_OK (and write
+ * -1 / 0).  OV2_ERR_INVALID with nothing enqueued: negative counts; offsets that do not start at 0, that decrease or that do
+ * not span the totals; a grid entry outside its frame; a null array that a non-empty call needs; null outputs; an unknown
+ * lens model.
+ * _dev form: every array pointer of `in` is a DEVICE pointer (cam stays a host pointer) and n_kp / n_cand must be given;
+ * d_work = n_kp 64-bit words of scratch; descriptor arrays 8-byte aligned; nothing is synchronised and the arrays are not
+ * read on the host, so the _dev form trusts the offsets (a grid entry outside its frame is still skipped). */
+typedef struct ov2_match_batch_input {
+    int32_t B;
+    int32_t n_kp, n_cand;          /* totals (host form: checked against kp_off[B] / cand_off[B]) */
+    double K[4];
+    int32_t img_w, img_h, cell;
+    const ov2_cam_model *cam;      /* HOST pointer in both forms, NULL = pinhole K */
+    const double *Twc;             /* B x 7 [t, qx qy qz qw] */
+    const int32_t *nb3dkps;        /* B */
+    const int32_t *kp_off;         /* B + 1 */
+    const int32_t *cand_off;       /* B + 1 */
+    const int32_t *kf_off;         /* B + 1 */
+    const float *kp_px;            /* n_kp x 2 */
+    const int32_t *kp_desc_ptr;    /* n_kp + 1 */
+    const uint8_t *kp_descs;
+    const int32_t *kp_kf_ptr;      /* n_kp + 1 */
+    const int32_t *kp_kfids;
+    const float *kp_kf_px;         /* per kp_kfids entry x 2 */
+    const int32_t *grid_ptr;       /* B * ncells + 1 */
+    const int32_t *grid_kp;        /* keypoint indices within the frame */
+    const double *cand_wpt;        /* n_cand x 3 */
+    const int32_t *cand_desc_ptr;  /* n_cand + 1 */
+    const uint8_t *cand_descs;
+    const int32_t *cand_kf_ptr;    /* n_cand + 1 */
+    const int32_t *cand_kfids;
+    const double *kf_Twc;          /* kf_off[B] x 7 */
+} ov2_match_batch_input;
+ov2_status ov2_match_to_map_batch(ov2_ctx *ctx, const ov2_match_batch_input *in, float fmaxprojerr, float fdistratio,
+                                  int32_t *match_cand /* n_kp */, float *match_dist /* n_kp */);
+ov2_status ov2_match_to_map_batch_dev(ov2_ctx *ctx, const ov2_match_batch_input *in, float fmaxprojerr, float fdistratio,
+                                      uint64_t *d_work /* n_kp */, int32_t *d_match_cand, float *d_match_dist);
+
 /* LoopCloser::matchToMap(frame, Tcw, fmaxprojerr, fdistratio, vmatchedkpids, set_local_lmids) (include/loop_closer.hpp,
  * src/loop_closer.cpp:586-763) for B candidate pairs in one call.  It is NOT Mapper::matchToMap: the projection pose is an
  * argument (Twc, one per pair: the P3P result, not the frame's stored pose), dmaxpxdist = fmaxprojerr is never doubled,

@@ -448,6 +448,63 @@ int ov2h_map_merge_points(void *p, int prevlmid, int newlmid)
     return 0;
 }
 
+static void fill_match_job(HostMap *m, int kfid, int n_local, const int *local, MatchJob &J)
+{
+    J.pmap = m->map.get(); J.kfid = kfid;
+    J.set_local_lmids.insert(local, local + n_local);
+}
+
+// what Mapper::matchToMap assembles for keyframe kfid and the local set `local` in front of its matcher
+// (SlamManager::assembleMatchToMap), no GPU context needed: kp_lmid (cap) the keypoints offered, in grid order; cand_lmid (cap)
+// the candidates offered, in the iteration order of the set; n[2] = their counts (both 0 when there is nothing to match).
+// OV2_ERR_INVALID when the keyframe is not in the map or a count exceeds cap
+int ov2h_match_assemble(void *p, int kfid, int n_local, const int *local, int cap, int *n, int *kp_lmid, int *cand_lmid)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kfid);
+    if (!f || n_local < 0) return (int)OV2_ERR_INVALID;
+    MatchJob J;
+    fill_match_job(m, kfid, n_local, local, J);
+    SlamManager::assembleMatchToMap(*f, J.set_local_lmids, J);
+    n[0] = J.offered ? (int)J.kp_lmid.size() : 0; n[1] = J.offered ? (int)J.cand_lmid.size() : 0;
+    if (n[0] > cap || n[1] > cap) return (int)OV2_ERR_INVALID;
+    std::copy(J.kp_lmid.begin(), J.kp_lmid.begin() + n[0], kp_lmid);
+    std::copy(J.cand_lmid.begin(), J.cand_lmid.begin() + n[1], cand_lmid);
+    return 0;
+}
+
+// SlamManager::matchToLocalMaps on B maps of one context: keyframe kfid[b] of maps[b] against the n_local[b] lmids of map b,
+// one list after the other in `local`, with the two gates of Mapper::matchToMap; merge: MapManager::mergeMapPoints per pair
+// afterwards; single: one ov2_match_to_map call per job instead of one ov2_match_to_map_batch call.  pairs (cap x 2): the
+// (previous lmid, new lmid) pairs job after job, ascending previous lmid, n_pairs[b] each; stats[5]: jobs, jobs offered,
+// keypoints offered, candidates offered, library calls.  Returns 0 or a negative ov2_status (OV2_ERR_INVALID also when cap
+// is too small)
+int ov2h_match_local_maps(int B, void *const *maps, void *ctx, const int *kfid, const int *n_local, const int *local, float fmaxprojerr,
+                          float fdistratio, int merge, int single, int cap, int *n_pairs, int *pairs, int *stats)
+{
+    if (B < 0) return (int)OV2_ERR_INVALID;
+    std::vector<MatchJob> jobs((size_t)B);
+    size_t o = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!maps[b] || n_local[b] < 0) return (int)OV2_ERR_INVALID;
+        fill_match_job((HostMap *)maps[b], kfid[b], n_local[b], local + o, jobs[b]);
+        o += (size_t)n_local[b];
+    }
+    MatchBatchStats st;
+    const ov2_status s = SlamManager::matchToLocalMaps((ov2_ctx *)ctx, jobs, fmaxprojerr, fdistratio, merge != 0, single != 0, st);
+    const int sv[5] = {st.jobs, st.match_jobs, st.n_kp, st.n_cand, st.match_calls};
+    std::copy(sv, sv + 5, stats);
+    if (s != OV2_OK) return (int)s;
+    o = 0;
+    for (int b = 0; b < B; ++b) {
+        const auto &mp = jobs[b].map_previd_newid;
+        if (o + mp.size() > (size_t)cap) return (int)OV2_ERR_INVALID;
+        n_pairs[b] = (int)mp.size();
+        for (const auto &q : mp) { pairs[2 * o] = q.first; pairs[2 * o + 1] = q.second; ++o; }
+    }
+    return 0;
+}
+
 // LoopCloser::processLoopCandidates on B pairs: branch (B, ov2::LoopBranch of the 2D-2D half), n_passed (B: pairs it passed on),
 // then the rows of ov2h_loop_verify (a pair that did not pass keeps the row of an untouched LoopVerifyResult); stats[13]: the five
 // of ov2h_loop_match followed by the eight of ov2h_loop_verify

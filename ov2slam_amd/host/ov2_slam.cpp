@@ -401,92 +401,198 @@ ov2_status SlamManager::matchingToLocalMap(Frame &frame)
 
 ov2_status SlamManager::matchToMap(const Frame &frame, float fmaxprojerr, float fdistratio, std::unordered_set<int> &set_local_lmids,
                                    std::map<int, int> &map_previd_newid)
-{   // src/mapper.cpp:576-774 on flat arrays (ov2_match_input): this function lists what the reference's loops look at -- the frame's
-    // keypoints with the descriptor sets / observers / pixels of their map points, the local map points that pass the
-    // tests made before the projection (:613-624), the keyframe poses -- and ov2_match_to_map does the rest
-    if (set_local_lmids.empty()) return OV2_OK;
+{   // src/mapper.cpp:576-774: assembleMatchToMap lists what the reference's loops look at, ov2_match_to_map does the rest
+    MatchJob job;
+    job.pmap = pmap_.get(); job.kfid = frame.kfid_;
+    assembleMatchToMap(frame, set_local_lmids, job);
+    if (!job.offered) return OV2_OK;
+    ov2_match_input in;
+    matchInput(job, in);
+    std::vector<int32_t> match_cand(job.kp_lmid.size(), -1);
+    std::vector<float> match_dist(job.kp_lmid.size(), 0.f);
+    const ov2_status s = ov2_match_to_map(ctx_, &in, fmaxprojerr, fdistratio, match_cand.data(), match_dist.data());
+    if (s != OV2_OK) return s;
+    applyMatches(job, match_cand.data());
+    map_previd_newid.insert(job.map_previd_newid.begin(), job.map_previd_newid.end());
+    return OV2_OK;
+}
+
+void SlamManager::assembleMatchToMap(const Frame &frame, const std::unordered_set<int> &set_local_lmids, MatchJob &J)
+{   // the flat arrays of ov2_match_input: the frame's keypoints with the descriptor sets / observers / pixels of their map points,
+    // the local map points that pass the tests made before the projection (:613-624), the keyframe poses
+    MapManager &map = *J.pmap;
+    J.offered = false;
+    J.kp_lmid.clear(); J.cand_lmid.clear(); J.map_previd_newid.clear();
+    if (set_local_lmids.empty()) return;
     // keypoints: every keypoint of the frame (kp.lmid_ >= 0 always here), in grid order so that the cells list them contiguously
-    std::vector<int> kp_lmid; std::unordered_map<int, int> kp_index;
-    std::vector<int32_t> grid_ptr(1, 0), grid_kp;
+    J.grid_ptr.assign(1, 0); J.grid_kp.clear();
     for (const auto &cell : frame.vgridkps_) {
         for (int lmid : cell) {
             auto it = frame.mapkps_.find(lmid);
             if (it == frame.mapkps_.end()) continue;
-            kp_index.emplace(lmid, (int)kp_lmid.size());
-            grid_kp.push_back((int32_t)kp_lmid.size());
-            kp_lmid.push_back(lmid);
+            J.grid_kp.push_back((int32_t)J.kp_lmid.size());
+            J.kp_lmid.push_back(lmid);
         }
-        grid_ptr.push_back((int32_t)grid_kp.size());
+        J.grid_ptr.push_back((int32_t)J.grid_kp.size());
     }
-    const int n_kp = (int)kp_lmid.size();
-    if (n_kp == 0) return OV2_OK;
+    const int n_kp = (int)J.kp_lmid.size();
+    if (n_kp == 0) return;
     int max_kf = frame.kfid_;
-    std::vector<float> kp_px(2 * (size_t)n_kp), kp_kf_px;
-    std::vector<int32_t> kp_desc_ptr(1, 0), kp_kf_ptr(1, 0), kp_kfids;
-    std::vector<uint8_t> kp_descs;
+    J.kp_px.assign(2 * (size_t)n_kp, 0.f); J.kp_kf_px.clear();
+    J.kp_desc_ptr.assign(1, 0); J.kp_kf_ptr.assign(1, 0); J.kp_kfids.clear(); J.kp_descs.clear();
     for (int k = 0; k < n_kp; ++k) {
-        const Keypoint &kp = frame.mapkps_.at(kp_lmid[k]);
-        kp_px[2 * k] = kp.px_.x; kp_px[2 * k + 1] = kp.px_.y;
-        auto pkplm = pmap_->getMapPoint(kp.lmid_);
+        const Keypoint &kp = frame.mapkps_.at(J.kp_lmid[k]);
+        J.kp_px[2 * k] = kp.px_.x; J.kp_px[2 * k + 1] = kp.px_.y;
+        auto pkplm = map.getMapPoint(kp.lmid_);
         if (pkplm && pkplm->has_desc_) {   // (a keypoint whose map point is gone or has no descriptor offers nothing: :676-685)
-            for (const auto &kd : pkplm->map_kf_desc_) kp_descs.insert(kp_descs.end(), kd.second.begin(), kd.second.end());
+            for (const auto &kd : pkplm->map_kf_desc_) J.kp_descs.insert(J.kp_descs.end(), kd.second.begin(), kd.second.end());
             for (int kfid : pkplm->getKfObsSet()) {
-                auto pcokf = pmap_->getKeyframe(kfid);
+                auto pcokf = map.getKeyframe(kfid);
                 const Keypoint cokp = pcokf ? pcokf->getKeypointById(kp.lmid_) : Keypoint();
                 if (cokp.lmid_ != kp.lmid_) continue;   // (:706-713 removes such a stale observation; it cannot arise through this class)
-                kp_kfids.push_back(kfid); kp_kf_px.push_back(cokp.px_.x); kp_kf_px.push_back(cokp.px_.y);
+                J.kp_kfids.push_back(kfid); J.kp_kf_px.push_back(cokp.px_.x); J.kp_kf_px.push_back(cokp.px_.y);
                 max_kf = std::max(max_kf, kfid);
             }
         }
-        kp_desc_ptr.push_back((int32_t)(kp_descs.size() / 32));
-        kp_kf_ptr.push_back((int32_t)kp_kfids.size());
+        J.kp_desc_ptr.push_back((int32_t)(J.kp_descs.size() / 32));
+        J.kp_kf_ptr.push_back((int32_t)J.kp_kfids.size());
     }
     // candidates, in the iteration order of the set (it decides ties between candidates of one keypoint: :754-771)
-    std::vector<int> cand_lmid;
-    std::vector<double> cand_wpt;
-    std::vector<int32_t> cand_desc_ptr(1, 0), cand_kf_ptr(1, 0), cand_kfids;
-    std::vector<uint8_t> cand_descs;
+    J.cand_wpt.clear(); J.cand_desc_ptr.assign(1, 0); J.cand_kf_ptr.assign(1, 0); J.cand_kfids.clear(); J.cand_descs.clear();
     for (const int lmid : set_local_lmids) {
         if (frame.isObservingKp(lmid)) continue;
-        auto plm = pmap_->getMapPoint(lmid);
+        auto plm = map.getMapPoint(lmid);
         if (!plm || !plm->is3d_ || !plm->has_desc_) continue;
         const Vec3 w = plm->getPoint();
-        cand_lmid.push_back(lmid);
-        cand_wpt.push_back(w.x); cand_wpt.push_back(w.y); cand_wpt.push_back(w.z);
-        for (const auto &kd : plm->map_kf_desc_) cand_descs.insert(cand_descs.end(), kd.second.begin(), kd.second.end());
-        for (int kfid : plm->getKfObsSet()) { cand_kfids.push_back(kfid); max_kf = std::max(max_kf, kfid); }
-        cand_desc_ptr.push_back((int32_t)(cand_descs.size() / 32));
-        cand_kf_ptr.push_back((int32_t)cand_kfids.size());
+        J.cand_lmid.push_back(lmid);
+        J.cand_wpt.push_back(w.x); J.cand_wpt.push_back(w.y); J.cand_wpt.push_back(w.z);
+        for (const auto &kd : plm->map_kf_desc_) J.cand_descs.insert(J.cand_descs.end(), kd.second.begin(), kd.second.end());
+        for (int kfid : plm->getKfObsSet()) { J.cand_kfids.push_back(kfid); max_kf = std::max(max_kf, kfid); }
+        J.cand_desc_ptr.push_back((int32_t)(J.cand_descs.size() / 32));
+        J.cand_kf_ptr.push_back((int32_t)J.cand_kfids.size());
     }
-    if (cand_lmid.empty()) return OV2_OK;
-    std::vector<double> kf_Twc(7 * (size_t)(max_kf + 1), 0.0);
+    if (J.cand_lmid.empty()) return;
+    J.kf_Twc.assign(7 * (size_t)(max_kf + 1), 0.0);
     for (int k = 0; k <= max_kf; ++k) {
-        auto pkf = pmap_->getKeyframe(k);
+        auto pkf = map.getKeyframe(k);
         const SE3 T = pkf ? pkf->getTwc() : SE3();
-        for (int i = 0; i < 7; ++i) kf_Twc[7 * (size_t)k + i] = T.v[i];
+        for (int i = 0; i < 7; ++i) J.kf_Twc[7 * (size_t)k + i] = T.v[i];
     }
     const CameraCalibration &c = *frame.pcalib_leftcam_;
-    ov2_match_input in;
-    memset(&in, 0, sizeof(in));
     const SE3 Twc = frame.getTwc();
-    for (int i = 0; i < 7; ++i) in.Twc[i] = Twc.v[i];
-    in.K[0] = c.fx_; in.K[1] = c.fy_; in.K[2] = c.cx_; in.K[3] = c.cy_;
-    in.img_w = c.img_w_; in.img_h = c.img_h_; in.cell = (int32_t)frame.ncellsize_; in.nb3dkps = (int32_t)frame.nb3dkps_;
-    in.n_kp = n_kp; in.kp_px = kp_px.data(); in.kp_desc_ptr = kp_desc_ptr.data(); in.kp_descs = kp_descs.data();
-    in.kp_kf_ptr = kp_kf_ptr.data(); in.kp_kfids = kp_kfids.data(); in.kp_kf_px = kp_kf_px.data();
-    in.grid_ptr = grid_ptr.data(); in.grid_kp = grid_kp.data();
-    in.n_cand = (int32_t)cand_lmid.size(); in.cand_wpt = cand_wpt.data(); in.cand_desc_ptr = cand_desc_ptr.data(); in.cand_descs = cand_descs.data();
-    in.cand_kf_ptr = cand_kf_ptr.data(); in.cand_kfids = cand_kfids.data();
-    in.n_kf = max_kf + 1; in.kf_Twc = kf_Twc.data();
-    ov2_cam_model cam;
-    const bool dist = c.fillCamModel(&cam);
-    in.cam = dist ? &cam : nullptr;
-    std::vector<int32_t> match_cand((size_t)n_kp, -1);
-    std::vector<float> match_dist((size_t)n_kp, 0.f);
-    const ov2_status s = ov2_match_to_map(ctx_, &in, fmaxprojerr, fdistratio, match_cand.data(), match_dist.data());
-    if (s != OV2_OK) return s;
-    for (int k = 0; k < n_kp; ++k)
-        if (match_cand[k] >= 0) map_previd_newid.emplace(kp_lmid[k], cand_lmid[match_cand[k]]);
+    for (int i = 0; i < 7; ++i) J.Twc[i] = Twc.v[i];
+    J.K[0] = c.fx_; J.K[1] = c.fy_; J.K[2] = c.cx_; J.K[3] = c.cy_;
+    J.img_w = c.img_w_; J.img_h = c.img_h_; J.cell = (int)frame.ncellsize_; J.nb3dkps = (int)frame.nb3dkps_;
+    memset(&J.cam, 0, sizeof(J.cam));
+    J.distorted = c.fillCamModel(&J.cam);
+    J.offered = true;
+}
+
+void SlamManager::matchInput(const MatchJob &J, ov2_match_input &in)
+{
+    memset(&in, 0, sizeof(in));
+    for (int i = 0; i < 7; ++i) in.Twc[i] = J.Twc[i];
+    for (int i = 0; i < 4; ++i) in.K[i] = J.K[i];
+    in.img_w = J.img_w; in.img_h = J.img_h; in.cell = J.cell; in.nb3dkps = J.nb3dkps;
+    in.n_kp = (int32_t)J.kp_lmid.size(); in.kp_px = J.kp_px.data(); in.kp_desc_ptr = J.kp_desc_ptr.data(); in.kp_descs = J.kp_descs.data();
+    in.kp_kf_ptr = J.kp_kf_ptr.data(); in.kp_kfids = J.kp_kfids.data(); in.kp_kf_px = J.kp_kf_px.data();
+    in.grid_ptr = J.grid_ptr.data(); in.grid_kp = J.grid_kp.data();
+    in.n_cand = (int32_t)J.cand_lmid.size(); in.cand_wpt = J.cand_wpt.data(); in.cand_desc_ptr = J.cand_desc_ptr.data();
+    in.cand_descs = J.cand_descs.data(); in.cand_kf_ptr = J.cand_kf_ptr.data(); in.cand_kfids = J.cand_kfids.data();
+    in.n_kf = (int32_t)(J.kf_Twc.size() / 7); in.kf_Twc = J.kf_Twc.data();
+    in.cam = J.distorted ? &J.cam : nullptr;
+}
+
+void SlamManager::applyMatches(MatchJob &J, const int32_t *match_cand)
+{
+    for (size_t k = 0; k < J.kp_lmid.size(); ++k)
+        if (match_cand[k] >= 0) J.map_previd_newid.emplace(J.kp_lmid[k], J.cand_lmid[match_cand[k]]);
+}
+
+ov2_status SlamManager::matchToLocalMaps(ov2_ctx *ctx, std::vector<MatchJob> &jobs, float fmaxprojerr, float fdistratio, bool merge, bool single,
+                                         MatchBatchStats &stats)
+{
+    stats = MatchBatchStats();
+    stats.jobs = (int)jobs.size();
+    std::vector<MatchJob *> offered;
+    for (MatchJob &J : jobs) {
+        auto pkf = J.pmap ? J.pmap->getKeyframe(J.kfid) : nullptr;
+        if (!pkf) return OV2_ERR_INVALID;
+        assembleMatchToMap(*pkf, J.set_local_lmids, J);
+        if (!J.offered) continue;
+        offered.push_back(&J);
+        stats.n_kp += (int)J.kp_lmid.size(); stats.n_cand += (int)J.cand_lmid.size();
+    }
+    stats.match_jobs = (int)offered.size();
+    if (offered.empty()) return OV2_OK;
+    const MatchJob &J0 = *offered[0];
+    for (const MatchJob *J : offered) {   // one camera per call
+        bool same = J->img_w == J0.img_w && J->img_h == J0.img_h && J->cell == J0.cell && J->distorted == J0.distorted &&
+                    J->grid_ptr.size() == J0.grid_ptr.size();
+        for (int i = 0; i < 4; ++i) same = same && J->K[i] == J0.K[i];
+        if (same && J->distorted) {
+            same = J->cam.model == J0.cam.model && J->cam.n_coeffs == J0.cam.n_coeffs;
+            for (int i = 0; same && i < J0.cam.n_coeffs && i < 5; ++i) same = J->cam.D[i] == J0.cam.D[i];
+        }
+        if (!same) return OV2_ERR_INVALID;
+    }
+    std::vector<int32_t> match_cand((size_t)stats.n_kp, -1);
+    std::vector<float> match_dist((size_t)stats.n_kp, 0.f);
+    std::vector<int32_t> kp_off(1, 0);
+    if (single) {
+        for (const MatchJob *J : offered) {
+            ov2_match_input in;
+            matchInput(*J, in);
+            const ov2_status s = ov2_match_to_map(ctx, &in, fmaxprojerr, fdistratio, match_cand.data() + kp_off.back(), match_dist.data() + kp_off.back());
+            if (s != OV2_OK) return s;
+            ++stats.match_calls;
+            kp_off.push_back(kp_off.back() + (int32_t)J->kp_lmid.size());
+        }
+    } else {
+        // the jobs' arrays back to back; the prefix arrays run over the whole flat arrays, the grids stay indices within the frame
+        const size_t B = offered.size();
+        std::vector<double> Twc, cand_wpt, kf_Twc;
+        std::vector<int32_t> nb3dkps, cand_off(1, 0), kf_off(1, 0), kp_desc_ptr(1, 0), kp_kf_ptr(1, 0), kp_kfids, grid_ptr(1, 0), grid_kp,
+            cand_desc_ptr(1, 0), cand_kf_ptr(1, 0), cand_kfids;
+        std::vector<float> kp_px, kp_kf_px;
+        std::vector<uint8_t> kp_descs, cand_descs;
+        auto append = [](auto &dst, const auto &src) { dst.insert(dst.end(), src.begin(), src.end()); };
+        auto append_ptr = [](std::vector<int32_t> &dst, const std::vector<int32_t> &src) {
+            const int32_t base = dst.back();
+            for (size_t i = 1; i < src.size(); ++i) dst.push_back(base + src[i]);
+        };
+        for (const MatchJob *J : offered) {
+            Twc.insert(Twc.end(), J->Twc, J->Twc + 7);
+            nb3dkps.push_back(J->nb3dkps);
+            kp_off.push_back(kp_off.back() + (int32_t)J->kp_lmid.size());
+            cand_off.push_back(cand_off.back() + (int32_t)J->cand_lmid.size());
+            kf_off.push_back(kf_off.back() + (int32_t)(J->kf_Twc.size() / 7));
+            append(kp_px, J->kp_px); append(kp_kf_px, J->kp_kf_px); append(kp_kfids, J->kp_kfids); append(kp_descs, J->kp_descs);
+            append(grid_kp, J->grid_kp); append(cand_wpt, J->cand_wpt); append(cand_descs, J->cand_descs); append(cand_kfids, J->cand_kfids);
+            append(kf_Twc, J->kf_Twc);
+            append_ptr(kp_desc_ptr, J->kp_desc_ptr); append_ptr(kp_kf_ptr, J->kp_kf_ptr); append_ptr(grid_ptr, J->grid_ptr);
+            append_ptr(cand_desc_ptr, J->cand_desc_ptr); append_ptr(cand_kf_ptr, J->cand_kf_ptr);
+        }
+        ov2_match_batch_input in;
+        memset(&in, 0, sizeof(in));
+        in.B = (int32_t)B; in.n_kp = kp_off.back(); in.n_cand = cand_off.back();
+        for (int i = 0; i < 4; ++i) in.K[i] = J0.K[i];
+        in.img_w = J0.img_w; in.img_h = J0.img_h; in.cell = J0.cell; in.cam = J0.distorted ? &J0.cam : nullptr;
+        in.Twc = Twc.data(); in.nb3dkps = nb3dkps.data(); in.kp_off = kp_off.data(); in.cand_off = cand_off.data(); in.kf_off = kf_off.data();
+        in.kp_px = kp_px.data(); in.kp_desc_ptr = kp_desc_ptr.data(); in.kp_descs = kp_descs.data(); in.kp_kf_ptr = kp_kf_ptr.data();
+        in.kp_kfids = kp_kfids.data(); in.kp_kf_px = kp_kf_px.data(); in.grid_ptr = grid_ptr.data(); in.grid_kp = grid_kp.data();
+        in.cand_wpt = cand_wpt.data(); in.cand_desc_ptr = cand_desc_ptr.data(); in.cand_descs = cand_descs.data();
+        in.cand_kf_ptr = cand_kf_ptr.data(); in.cand_kfids = cand_kfids.data(); in.kf_Twc = kf_Twc.data();
+        const ov2_status s = ov2_match_to_map_batch(ctx, &in, fmaxprojerr, fdistratio, match_cand.data(), match_dist.data());
+        if (s != OV2_OK) return s;
+        stats.match_calls = 1;
+    }
+    for (size_t b = 0; b < offered.size(); ++b) {
+        MatchJob &J = *offered[b];
+        applyMatches(J, match_cand.data() + kp_off[b]);
+        if (merge)
+            for (const auto &ids : J.map_previd_newid) J.pmap->mergeMapPoints(ids.first, ids.second);   // Mapper::mergeMatches (:556-574)
+    }
     return OV2_OK;
 }
 

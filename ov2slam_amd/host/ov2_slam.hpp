@@ -6,6 +6,8 @@
 //   MapManager::createKeyframe       src/map_manager.cpp:43-60  prepareFrame :64-115  extractKeypoints :286-340
 //               addKeypointsToFrame  :196-211   addKeyframe :621-634   addMapPoint :636-659
 //   Mapper::run (one keyframe)       src/mapper.cpp:38-189      triangulateStereo :346-461   triangulateTemporal :191-344
+//                   matchingToLocalMap :469-554  matchToMap :576-774 (ov2_match_to_map; B keyframes of B maps at once:
+//                   SlamManager::matchToLocalMaps on ov2_match_to_map_batch)
 //   SlamManager::run (one image)     src/ov2slam.cpp:152-205    Estimator::applyLocalBA  src/estimator.cpp:67-98
 // The reference runs front-end, mapper and estimator on three threads; here one call processes one stereo frame to the
 // end (keyframe work included), i.e. the reference with bforce_realtime = 0 and an idle back-end: deterministic.
@@ -65,6 +67,36 @@ struct SlamStats {   // per frame, for tests / profiles
     double ba_cost0 = 0., ba_cost1 = 0.;
 };
 
+// One Mapper::matchToMap call (src/mapper.cpp:576-774) taken apart: what the reference's loops look at as the flat arrays of
+// ov2_match_input (SlamManager::assembleMatchToMap fills them), and what its result means for the map.
+struct MatchJob {
+    // in: the map, and for SlamManager::matchToLocalMaps the keyframe and the local map points offered (the iteration order of
+    // the set decides ties)
+    MapManager *pmap = nullptr;
+    int kfid = -1;
+    std::unordered_set<int> set_local_lmids;
+    // assembled: kp_lmid / cand_lmid name the rows; offered = false when there is nothing to match (an empty local set, no
+    // keypoint or no candidate): such a job takes no slot in a call
+    bool offered = false;
+    std::vector<int> kp_lmid, cand_lmid;
+    double Twc[7] = {0}, K[4] = {0};
+    int img_w = 0, img_h = 0, cell = 0, nb3dkps = 0;
+    bool distorted = false;
+    ov2_cam_model cam{};
+    std::vector<float> kp_px, kp_kf_px;
+    std::vector<int32_t> kp_desc_ptr, kp_kf_ptr, kp_kfids, grid_ptr, grid_kp, cand_desc_ptr, cand_kf_ptr, cand_kfids;
+    std::vector<uint8_t> kp_descs, cand_descs;
+    std::vector<double> cand_wpt, kf_Twc;
+    // out: keypoint lmid -> local map point id (the reference's map_previd_newid)
+    std::map<int, int> map_previd_newid;
+};
+
+struct MatchBatchStats {   // one matchToLocalMaps call
+    int jobs = 0, match_jobs = 0;      // jobs given, jobs with something to offer
+    int n_kp = 0, n_cand = 0;          // keypoints and candidates offered over all jobs
+    int match_calls = 0;               // library calls made: 0 or 1 batched, one per offered job with `single`
+};
+
 class SlamManager {   // src/ov2slam.cpp (the stereo branch of run())
 public:
     SlamManager(ov2_ctx *ctx, std::shared_ptr<SlamParams> pstate, std::shared_ptr<CameraCalibration> cl,
@@ -102,6 +134,19 @@ public:
     // tests hold exact counts recorded without the stage.  Selection and bookkeeping run here, the per-pair arithmetic is one
     // ov2_triangulate_pairs call over all source keyframes.  Static so that a bare MapManager (tests) can run it too.
     static ov2_status triangulateTemporal(ov2_ctx *ctx, MapManager &map, const SlamParams &st, Frame &frame, TemporalStats &stats);
+    // Mapper::matchToMap (src/mapper.cpp:576-774) in three parts.  assembleMatchToMap reads job.pmap, `frame` and the local set and fills the flat
+    // arrays (no GPU context needed); the library call is ov2_match_to_map on matchInput(job), or ov2_match_to_map_batch on several
+    // jobs at once; applyMatches turns match_cand (one entry per keypoint of the job) into job.map_previd_newid.
+    static void assembleMatchToMap(const Frame &frame, const std::unordered_set<int> &set_local_lmids, MatchJob &job);
+    static void matchInput(const MatchJob &job, ov2_match_input &in);
+    static void applyMatches(MatchJob &job, const int32_t *match_cand);
+    // The re-matching of B new keyframes against their local maps -- distinct maps that share `ctx` --: assemble every job, ONE
+    // ov2_match_to_map_batch call whatever B is (none when no job has anything to offer), apply per job and, with `merge`,
+    // MapManager::mergeMapPoints per pair (Mapper::mergeMatches, :556-574).  A job whose keyframe is not in its map, or a camera
+    // that differs among the offered jobs (the call takes one), is OV2_ERR_INVALID before anything is enqueued.  single: the same
+    // jobs as one ov2_match_to_map call each, the shape of the per-keyframe path.
+    static ov2_status matchToLocalMaps(ov2_ctx *ctx, std::vector<MatchJob> &jobs, float fmaxprojerr, float fdistratio, bool merge, bool single,
+                                       MatchBatchStats &stats);
     std::vector<SlamStats> stats_;
     std::vector<SE3> traj_;
 

@@ -173,6 +173,9 @@ def lib():
         L.ov2h_loop_candidate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, C.c_int, C.c_float, C.c_int, ip, ip, ip, ip]
         L.ov2h_loop_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, C.POINTER(C.c_ulonglong), C.c_int, C.c_float, C.c_int,
                                       ip, ip, ip, dp, ip, ip, ip]
+        L.ov2h_match_assemble.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip]
+        L.ov2h_match_local_maps.argtypes = [C.c_int, C.c_void_p, C.c_void_p, ip, ip, ip, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
+                                            ip, ip, ip]
         _lib = L
     return _lib
 
@@ -1245,6 +1248,46 @@ def loop_close_batch(ctx, maps, newkf, lckf, Twc, lists, cap=1 << 14, single=Fal
     if rc != 0:
         raise RuntimeError(f"closeLoops: status {rc}")
     return [unpack_close(ints[b], dbl[b], merged[b], st) for b in range(B)]
+
+
+def match_assemble(m, kfid, local, cap=1 << 14):
+    """what Mapper::matchToMap hands to its matcher for keyframe kfid of the LoopMap m and the local lmid list `local`
+    (SlamManager::assembleMatchToMap, no GPU context): (keypoint lmids in grid order, candidate lmids in the order offered)"""
+    ip = C.POINTER(C.c_int)
+    lo = np.ascontiguousarray(local, np.int32)
+    n, kp, ca = np.zeros(2, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    rc = lib().ov2h_match_assemble(m.h, int(kfid), len(lo), lo.ctypes.data_as(ip), cap, n.ctypes.data_as(ip), kp.ctypes.data_as(ip),
+                                   ca.ctypes.data_as(ip))
+    if rc != 0:
+        raise RuntimeError(f"ov2h_match_assemble: status {rc}")
+    return kp[:n[0]].tolist(), ca[:n[1]].tolist()
+
+
+MATCH_STATS = ("jobs", "match_jobs", "n_kp", "n_cand", "match_calls")
+
+
+def match_local_maps(ctx, maps, kfids, locals, fmaxprojerr=2.0, fdistratio=0.2, merge=False, single=False, cap=1 << 16):
+    """SlamManager::matchToLocalMaps on B LoopMaps of one context: keyframe kfids[b] of maps[b] re-matched against the lmid list
+    locals[b] (Mapper::matchToMap) with ONE ov2_match_to_map_batch call for all; merge: MapManager::mergeMapPoints per pair
+    afterwards (Mapper::mergeMatches); single: the same jobs as one ov2_match_to_map call each.  Returns (per-job lists of
+    (previous lmid, new lmid) in ascending previous lmid, stats dict); a negative status raises"""
+    L, B = lib(), len(maps)
+    ip = C.POINTER(C.c_int)
+    kf = np.ascontiguousarray(kfids, np.int32)
+    n_local = np.ascontiguousarray([len(v) for v in locals], np.int32)
+    lo = np.ascontiguousarray([l for v in locals for l in v], np.int32)
+    n_pairs, pairs, st = np.zeros(max(B, 1), np.int32), np.zeros((cap, 2), np.int32), np.zeros(5, np.int32)
+    hs = (C.c_void_p * max(B, 1))(*[m.h for m in maps])
+    rc = L.ov2h_match_local_maps(B, hs, ctx.h, kf.ctypes.data_as(ip), n_local.ctypes.data_as(ip), lo.ctypes.data_as(ip), float(fmaxprojerr),
+                                 float(fdistratio), int(bool(merge)), int(bool(single)), cap, n_pairs.ctypes.data_as(ip),
+                                 pairs.ctypes.data_as(ip), st.ctypes.data_as(ip))
+    if rc != 0:
+        raise RuntimeError(f"matchToLocalMaps: status {rc}")
+    out, o = [], 0
+    for b in range(B):
+        out.append([tuple(r) for r in pairs[o:o + n_pairs[b]].tolist()])
+        o += n_pairs[b]
+    return out, dict(zip(MATCH_STATS, st.tolist()))
 
 
 class FrontEndFrame:

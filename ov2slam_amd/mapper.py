@@ -1,6 +1,7 @@
 """Host-side mirror of the keyframe descriptor path over the C ABI (first half):
   describeBRIEF  <- FeatureExtractor::describeBRIEF  src/feature_extractor.cpp:224-285
   matchToMap     <- Mapper::matchToMap               src/mapper.cpp:576-774 (flat inputs: MatchInput)
+  matchToMap_batch(_dev) <- the same for B frames, one local map each, in one call (flat inputs: MatchBatchInput)
 Plumbing only (ctypes + numpy); the box sums, projections and Hamming distances run in csrc/match.hip."""
 import ctypes as C
 
@@ -29,10 +30,12 @@ def _csr(lists, dtype, width=1):
 class MatchInput:
     """owns the flat arrays of one Mapper::matchToMap call.
     kps: list of dict(px (2,), descs (d,32) u8, kfids [ascending], kf_px (len(kfids),2)); cands: list of dict(wpt (3,), descs,
-    kfids); kf_Twc: (n_kf, 7) indexed by kfid; the grid (Frame::vgridkps_) is rebuilt from kp order = insertion order."""
+    kfids); kf_Twc: (n_kf, 7) indexed by kfid; the grid (Frame::vgridkps_) is rebuilt from kp order = insertion order.
+    cam: None or ba_types.CamModelC, the lens model of the projections."""
 
-    def __init__(self, Twc, K, img_w, img_h, cell, nb3dkps, kps, cands, kf_Twc):
+    def __init__(self, Twc, K, img_w, img_h, cell, nb3dkps, kps, cands, kf_Twc, cam=None):
         c = np.ascontiguousarray
+        self.cam = cam   # None or ba_types.CamModelC
         self.kp_px = c([k["px"] for k in kps], np.float32).reshape(-1, 2)
         self.kp_desc_ptr, self.kp_descs = _csr([k["descs"] for k in kps], np.uint8, 32)
         self.kp_kf_ptr, self.kp_kfids = _csr([k["kfids"] for k in kps], np.int32)
@@ -52,6 +55,7 @@ class MatchInput:
         m.K[:] = np.asarray(K, np.float64).tolist()
         m.img_w, m.img_h, m.cell, m.nb3dkps = int(img_w), int(img_h), int(cell), int(nb3dkps)
         m.n_kp, m.n_cand, m.n_kf = len(kps), len(cands), len(self.kf_Twc)
+        m.cam = None if cam is None else C.addressof(cam)
         p = lambda a, t: a.ctypes.data_as(t)
         m.kp_px, m.kp_desc_ptr, m.kp_descs = p(self.kp_px, f32p), p(self.kp_desc_ptr, i32p), p(self.kp_descs, u8p)
         m.kp_kf_ptr, m.kp_kfids, m.kp_kf_px = p(self.kp_kf_ptr, i32p), p(self.kp_kfids, i32p), p(self.kp_kf_px, f32p)
@@ -77,6 +81,111 @@ def matchToMap(ctx, inp, fmaxprojerr=2.0, fdistratio=0.2):
     mc, md = np.full(max(n, 1), -1, np.int32), np.zeros(max(n, 1), np.float32)
     _check(ctx.h, ctx.lib.ov2_match_to_map(ctx.h, C.addressof(inp.c), float(fmaxprojerr), float(fdistratio), mc.ctypes.data, md.ctypes.data))
     return mc[:n], md[:n]
+
+
+class MatchBatchInputC(C.Structure):
+    _fields_ = [("B", C.c_int32), ("n_kp", C.c_int32), ("n_cand", C.c_int32), ("K", C.c_double * 4), ("img_w", C.c_int32),
+                ("img_h", C.c_int32), ("cell", C.c_int32), ("cam", C.c_void_p), ("Twc", f64p), ("nb3dkps", i32p), ("kp_off", i32p),
+                ("cand_off", i32p), ("kf_off", i32p), ("kp_px", f32p), ("kp_desc_ptr", i32p), ("kp_descs", u8p), ("kp_kf_ptr", i32p),
+                ("kp_kfids", i32p), ("kp_kf_px", f32p), ("grid_ptr", i32p), ("grid_kp", i32p), ("cand_wpt", f64p),
+                ("cand_desc_ptr", i32p), ("cand_descs", u8p), ("cand_kf_ptr", i32p), ("cand_kfids", i32p), ("kf_Twc", f64p)]
+
+
+BATCH_ARRAYS = (("Twc", f64p), ("nb3dkps", i32p), ("kp_off", i32p), ("cand_off", i32p), ("kf_off", i32p), ("kp_px", f32p),
+                ("kp_desc_ptr", i32p), ("kp_descs", u8p), ("kp_kf_ptr", i32p), ("kp_kfids", i32p), ("kp_kf_px", f32p), ("grid_ptr", i32p),
+                ("grid_kp", i32p), ("cand_wpt", f64p), ("cand_desc_ptr", i32p), ("cand_descs", u8p), ("cand_kf_ptr", i32p),
+                ("cand_kfids", i32p), ("kf_Twc", f64p))
+MATCH_BATCH_WAVES = 4   # candidates per workgroup of match_batch_cand_kernel (csrc/match.hip); the results do not depend on it
+
+
+class MatchBatchInput:
+    """owns the flat arrays of one ov2_match_to_map_batch call.
+    frames: list of dict(Twc (7,), kps, cands, kf_Twc (n_kf, 7)) with kps / cands as MatchInput takes them; nb3dkps: one count
+    per frame (Frame::nb3dkps_: under 30 the pixel gate of that frame doubles).  Each frame's grid (Frame::vgridkps_) is rebuilt
+    from its kp order = insertion order.  cam: None or ba_types.CamModelC (one camera per call)."""
+
+    def __init__(self, frames, K, img_w, img_h, cell, nb3dkps, cam=None):
+        c = np.ascontiguousarray
+        B = len(frames)
+        kps = [k for f in frames for k in f["kps"]]
+        cands = [q for f in frames for q in f["cands"]]
+        off = lambda key: np.concatenate([[0], np.cumsum([len(f[key]) for f in frames])]).astype(np.int32)
+        self.Twc = c([f["Twc"] for f in frames], np.float64).reshape(-1, 7)
+        self.nb3dkps = c(np.broadcast_to(np.asarray(nb3dkps, np.int32), (B,)))
+        self.kp_off, self.cand_off, self.kf_off = off("kps"), off("cands"), off("kf_Twc")
+        self.kp_px = c([k["px"] for k in kps], np.float32).reshape(-1, 2)
+        self.kp_desc_ptr, self.kp_descs = _csr([k["descs"] for k in kps], np.uint8, 32)
+        self.kp_kf_ptr, self.kp_kfids = _csr([k["kfids"] for k in kps], np.int32)
+        _, self.kp_kf_px = _csr([k["kf_px"] for k in kps], np.float32, 2)
+        nbw, nbh = int(np.ceil(np.float32(img_w) / np.float32(cell))), int(np.ceil(np.float32(img_h) / np.float32(cell)))
+        cells = [[] for _ in range(B * nbw * nbh)]
+        for b, f in enumerate(frames):
+            for i, k in enumerate(f["kps"]):
+                r = int(np.floor(np.float32(k["px"][1]) / np.float32(cell)))
+                cc = int(np.floor(np.float32(k["px"][0]) / np.float32(cell)))
+                cells[b * nbw * nbh + r * nbw + cc].append(i)
+        self.ncells = nbw * nbh
+        self.grid_ptr, self.grid_kp = _csr(cells, np.int32)
+        self.cand_wpt = c([q["wpt"] for q in cands], np.float64).reshape(-1, 3)
+        self.cand_desc_ptr, self.cand_descs = _csr([q["descs"] for q in cands], np.uint8, 32)
+        self.cand_kf_ptr, self.cand_kfids = _csr([q["kfids"] for q in cands], np.int32)
+        self.kf_Twc = c(np.concatenate([np.asarray(f["kf_Twc"], np.float64).reshape(-1, 7) for f in frames]) if B else np.zeros((0, 7)))
+        self.cam = cam
+        m = MatchBatchInputC()
+        m.B, m.n_kp, m.n_cand = B, len(kps), len(cands)
+        m.K[:] = np.asarray(K, np.float64).tolist()
+        m.img_w, m.img_h, m.cell = int(img_w), int(img_h), int(cell)
+        m.cam = None if cam is None else C.addressof(cam)
+        for name, t in BATCH_ARRAYS:
+            setattr(m, name, getattr(self, name).ctypes.data_as(t))
+        self.c = m
+
+    def split(self, mc, md):
+        """the per-frame slices of a call's outputs"""
+        o = self.kp_off
+        return [(mc[o[b]:o[b + 1]], md[o[b]:o[b + 1]]) for b in range(len(o) - 1)]
+
+
+def matchToMap_batch(ctx, inp, fmaxprojerr=2.0, fdistratio=0.2):
+    """host form.  returns (match_cand (n_kp,) int32: candidate index within the frame or -1, match_dist (n_kp,) f32); slice them
+    with inp.split"""
+    n = inp.c.n_kp
+    mc, md = np.full(max(n, 1), -7, np.int32), np.full(max(n, 1), -7, np.float32)
+    _check(ctx.h, ctx.lib.ov2_match_to_map_batch(ctx.h, C.addressof(inp.c), float(fmaxprojerr), float(fdistratio), mc.ctypes.data,
+                                                 md.ctypes.data))
+    return mc[:n], md[:n]
+
+
+class MatchBatchInputDev:
+    """a MatchBatchInput resident in HBM, with the work and output arrays of ov2_match_to_map_batch_dev; the outputs start as
+    `fill` so that untouched slots show"""
+
+    def __init__(self, ctx, inp, fill=-7):
+        self.ctx, self.host, n = ctx, inp, inp.c.n_kp
+        self.dev = {name: ctx.to_device(getattr(inp, name)) for name, _ in BATCH_ARRAYS}
+        self.c = MatchBatchInputC()
+        C.memmove(C.addressof(self.c), C.addressof(inp.c), C.sizeof(self.c))
+        for name, t in BATCH_ARRAYS:
+            setattr(self.c, name, C.cast(self.dev[name].ptr, t))
+        self.d_work = ctx.to_device(np.zeros(max(n, 1), np.uint64))
+        self.d_mc, self.d_md = ctx.to_device(np.full(max(n, 1), fill, np.int32)), ctx.to_device(np.full(max(n, 1), fill, np.float32))
+
+    def enqueue(self, fmaxprojerr=2.0, fdistratio=0.2):
+        """asynchronous: nothing is synchronised"""
+        _check(self.ctx.h, self.ctx.lib.ov2_match_to_map_batch_dev(self.ctx.h, C.addressof(self.c), float(fmaxprojerr), float(fdistratio),
+                                                                   self.d_work.ptr, self.d_mc.ptr, self.d_md.ptr))
+
+    def get(self):
+        n = self.host.c.n_kp
+        self.ctx.synchronize()
+        return self.d_mc.get()[:n], self.d_md.get()[:n]
+
+
+def matchToMap_batch_dev(ctx, inp, fmaxprojerr=2.0, fdistratio=0.2, fill=-7):
+    """the device-resident form on arrays uploaded here.  Returns (match_cand, match_dist) after a synchronisation of its own."""
+    d = MatchBatchInputDev(ctx, inp, fill)
+    d.enqueue(fmaxprojerr, fdistratio)
+    return d.get()
 
 
 def random_brief_pattern(seed=0):
