@@ -1031,6 +1031,66 @@ ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *ctx, int B, ov2_map *const *
                                            const int32_t *chain_off /* B + 1 */, const int32_t *chain_kfid,
                                            const double *chain_Twc /* x 7 */, ov2_map_pg_update *out /* B, or NULL */);
 
+/* MapManager::mergeMapPoints (src/map_manager.cpp:801-882) on the tables of B map mirrors of one context, for maps that have
+ * no host objects beside them: what Mapper::mergeMatches (src/mapper.cpp:556-574) does per match and LoopCloser
+ * (src/loop_closer.cpp:302-372) per merged pair.  (With a host mirror attached a merge arrives through ov2_map_remove_obs
+ * and re-added rows; that path is unchanged.)  Map b owns the pairs [pair_off[b], pair_off[b + 1]) of prev_lmid / new_lmid
+ * (pair_off[0] = 0).  EIGHT launches whatever B and the pair counts are (map = blockIdx.y; sizes come from device memory):
+ * the clear of the stage's own scratch block, the mark of the landmarks the pairs name, the count of their live rows, the
+ * three launches of the exclusive scan over the landmarks, the scatter of those rows into a per-landmark index, and the
+ * walk -- one workgroup per map -- which also writes the headers and the status bytes.  The cost per map is
+ * O(rows + landmarks + pairs x rows of the pair's two landmarks), never O(rows x pairs); the tables do not grow.
+ *
+ * Per map the pairs are applied ONE AFTER THE OTHER IN LIST ORDER, each against the tables as the pairs before it left
+ * them.  Pair (p, n) is skipped -- it counts in n_skipped, and its status byte names the first reason that applies --
+ * when p or n lies outside [0, max_lm) (OV2_MERGE_SKIP_RANGE), p == n (OV2_MERGE_SKIP_SAME), p is not OV2_LM_ALIVE
+ * (OV2_MERGE_SKIP_PREV_DEAD), n is not OV2_LM_ALIVE (OV2_MERGE_SKIP_NEW_DEAD), n is not OV2_LM_3D
+ * (OV2_MERGE_SKIP_NEW_NOT3D, :812-827).  p == n is a departure: the reference would erase the point, and neither of its
+ * callers ever passes it (closeLoop filters prev != new, matchToMap never offers a map point the frame observes).
+ * Otherwise (OV2_MERGE_DONE) every live row (k, p) -- row, keyframe and landmark alive -- is taken: where a live row (k, n)
+ * exists Frame::updateKeypointId returns false (src/frame.cpp:380-402), the row stays as it is and counts in
+ * n_rows_conflict (its landmark dies, so it is no longer live, as after the host stage); otherwise its landmark id becomes
+ * n IN PLACE -- pixel, right pixel, scale and stereo flag kept -- and it counts in n_rows_moved.  Then lm_state[p] = 0
+ * (map_plms_.erase) and, with cur_obs[i] != 0, lm_state[n] |= OV2_LM_OBS (setMapPointObs(newlmid), :860-866: the caller
+ * knows whether the current frame held p).  The point and the other bits of n are untouched.  n_merged counts the pairs not
+ * skipped; n_pairs = n_merged + n_skipped.  So (a, b), (b, c) moves a's rows twice; (a, b), (a, c) skips the second pair;
+ * (a, n), (b, n) with a and b seen by one keyframe keeps the second pair's row of that keyframe as a conflict.
+ * Descriptors (addDesc), covisibility maps, anchors and nblms_ are not mirror state: a caller that keeps them replays them
+ * from pair_status.
+ *
+ * Host form: prev_lmid / new_lmid / cur_obs (or NULL = all 0) are host arrays staged through the context's pinned block;
+ * out (B, or NULL) takes the headers, pair_status (pair_off[B] bytes, or NULL) the statuses; with both NULL the call is
+ * fully asynchronous, otherwise it synchronises once (one copy brings headers and statuses back).
+ * _dev form: d_prev_lmid / d_new_lmid / d_cur_obs / d_n_pairs / d_pair_status are DEVICE pointers, pair_off stays a HOST array
+ * and gives every map's SEGMENT; d_n_pairs (B, or NULL = whole segments) is how many pairs of the segment count (clamped
+ * to [0, segment]); it is read on the device only, and the status bytes of the rest of the segment become
+ * OV2_MERGE_NOT_RUN.  The call synchronises once when `out` is given; d_pair_status stays on the device and asks for none.
+ *
+ * Like the keyframe filter the call ends what the last set-up of a map with a NON-EMPTY segment can be updated from
+ * (ov2_map_local_ba_update_batch then refuses the map); a map with an empty segment is left alone.  ov2_map_compact
+ * afterwards squeezes out the conflict rows like any dead row.  B = 0 and all-empty lists are OV2_OK.  Refused with
+ * OV2_ERR_INVALID before anything is enqueued, from host state only and without a synchronisation: B < 0 or a null array
+ * that a non-empty call needs; a pair_off that does not start at 0 or that decreases; a map listed twice; a map of another
+ * context; a map that holds a state saved by ov2_map_save_state (the snapshot does not cover the landmark ids of the rows,
+ * so a restore could not undo a relabel). */
+#define OV2_MERGE_DONE            0
+#define OV2_MERGE_SKIP_RANGE      1
+#define OV2_MERGE_SKIP_SAME       2
+#define OV2_MERGE_SKIP_PREV_DEAD  3
+#define OV2_MERGE_SKIP_NEW_DEAD   4
+#define OV2_MERGE_SKIP_NEW_NOT3D  5
+#define OV2_MERGE_NOT_RUN         255
+typedef struct ov2_map_merge {
+    int32_t n_pairs, n_merged, n_skipped, n_rows_moved, n_rows_conflict;
+} ov2_map_merge;
+ov2_status ov2_map_merge_points_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *pair_off /* B + 1 */,
+                                      const int32_t *prev_lmid, const int32_t *new_lmid, const uint8_t *cur_obs /* or NULL */,
+                                      ov2_map_merge *out /* B, or NULL */, uint8_t *pair_status /* pair_off[B], or NULL */);
+ov2_status ov2_map_merge_points_batch_dev(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *pair_off /* HOST, B + 1 */,
+                                          const int32_t *d_prev_lmid, const int32_t *d_new_lmid, const uint8_t *d_cur_obs,
+                                          const int32_t *d_n_pairs /* B, or NULL */, ov2_map_merge *out /* B, or NULL */,
+                                          uint8_t *d_pair_status /* or NULL */);
+
 /* Test / bench support.  ov2_map_save_state keeps a device copy of the mutable state of the tables (poses, landmark points
  * and states, observation flags); ov2_map_restore_state_batch rewinds B maps to it in one launch, asynchronously (every
  * bench job starts from the same noisy map, as a new keyframe of a live sequence would bring it).  ov2_map_download copies
@@ -1201,6 +1261,20 @@ ov2_status ov2_match_to_map_batch(ov2_ctx *ctx, const ov2_match_batch_input *in,
                                   int32_t *match_cand /* n_kp */, float *match_dist /* n_kp */);
 ov2_status ov2_match_to_map_batch_dev(ov2_ctx *ctx, const ov2_match_batch_input *in, float fmaxprojerr, float fdistratio,
                                       uint64_t *d_work /* n_kp */, int32_t *d_match_cand, float *d_match_dist);
+
+/* The output of ov2_match_to_map_batch_dev as the ordered pair lists ov2_map_merge_points_batch_dev takes (the
+ * map_previd_newid of Mapper::matchToMap as Mapper::mergeMatches walks it, src/mapper.cpp:556-574), on the device: one
+ * launch, one workgroup per frame, nothing synchronised.  Every pointer is a DEVICE pointer; d_kp_off / d_cand_off are the
+ * matcher's (B + 1 each).  Frame b's pairs are (kp_lmid[k], cand_lmid[cand_off[b] + match_cand[k]]) for its keypoints with
+ * match_cand[k] >= 0 (an index beyond the frame's candidates gives no pair), written from kp_off[b] on in ASCENDING
+ * prev_lmid -- the iteration order of the reference's std::map<int, int>; the keypoint lmids of a frame are distinct, so a
+ * rank among the matched keypoints gives the slot --, the rest of the segment filled with -1, the count in d_n_pairs[b].
+ * The host's kp_off is then the pair_off of ov2_map_merge_points_batch_dev: match -> pairs -> merge is three enqueues on
+ * one stream.  OV2_ERR_INVALID: negative counts, a null array that a non-empty call needs. */
+ov2_status ov2_match_pairs_dev(ov2_ctx *ctx, int B, int n_kp, const int32_t *d_kp_off, const int32_t *d_cand_off /* B + 1 each */,
+                               const int32_t *d_kp_lmid /* n_kp */, const int32_t *d_cand_lmid /* n_cand */,
+                               const int32_t *d_match_cand /* n_kp */, int32_t *d_prev_lmid, int32_t *d_new_lmid /* n_kp each */,
+                               int32_t *d_n_pairs /* B */);
 
 /* LoopCloser::matchToMap(frame, Tcw, fmaxprojerr, fdistratio, vmatchedkpids, set_local_lmids) (include/loop_closer.hpp,
  * src/loop_closer.cpp:586-763) for B candidate pairs in one call.  It is NOT Mapper::matchToMap: the projection pose is an

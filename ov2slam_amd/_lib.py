@@ -94,6 +94,9 @@ SIGNATURES = {
     "ov2_pose_graph_solve": (C.c_int, [vp, vp, vp, vp]),
     "ov2_pose_graph_solve_batch": (C.c_int, [vp, C.c_int, vp, vp, vp]),
     "ov2_map_pose_graph_update_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "ov2_map_merge_points_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "ov2_map_merge_points_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ov2_match_pairs_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ov2_map_compact": (C.c_int, [vp, ip, ip]),
     "ov2_map_obs_rows": (C.c_int, [vp, ip, ip, ip]),
     "ov2_map_local_ba_setup": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),

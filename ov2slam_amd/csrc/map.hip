@@ -67,6 +67,13 @@ struct ov2_map {
     int *fl_rows;                                                   // [max_obs] live rows grouped by keyframe
     int *fl_unset;                                                  // [max_lm] landmarks whose OV2_LM_3D the walk cleared
     int *fl_removed_h; int fl_removed_cap;                          // pinned: the removed keyframes of the last call
+    // ov2_map_merge_points_batch: scratch of its own again
+    unsigned char *mg_zero; size_t mg_zero_bytes;                   // hdr (MH_N ints) | mg_cnt | mg_fill | mg_next | mg_stamp | mg_mark: one clear per call
+    int *mg_cnt, *mg_fill, *mg_next;                                // [max_lm] live rows of a named landmark, rows scattered so far, adopted segment + 1
+    int *mg_stamp;                                                  // [max_kf] pair index + 1 of the last pair whose `new` the keyframe observes
+    unsigned char *mg_mark;                                         // [max_lm] named by a pair of the call
+    int *mg_start;                                                  // [max_lm] exclusive scan of mg_cnt: where the landmark's rows start in mg_rows
+    int *mg_rows;                                                   // [max_obs] live rows of the named landmarks, grouped by landmark
 };
 
 namespace {
@@ -78,6 +85,8 @@ enum { MH_NBKPS = 0, MH_NB3D, MH_ABORT, MH_NMAXKF, MH_NPOSE, MH_NRES, MH_NLM, MH
        MH_N = 16 };
 // header of the keyframe filter (its own block, cleared per call): what ov2_map_filter reports, and the scan total of the rows
 enum { FH_CANDIDATES = 0, FH_REMOVED, FH_FEW3D, FH_UNSET3D, FH_ROWS };
+// header of the map-point merge (its own block as well): the five counts of ov2_map_merge, and the scan total of the rows
+enum { GH_PAIRS = 0, GH_MERGED, GH_SKIPPED, GH_MOVED, GH_CONFLICT, GH_ROWS };
 #define ANCH_TOP 0x40000000   // anchor keyframe stored as ANCH_TOP - kfid under atomicMax: 0 = none, so the array lives in the zeroed block
 enum { OBS_ALIVE = 1, OBS_STEREO = 2 };
 enum { MAP_COMPACT_MIN_ROWS = 4096 };   // below this the scans cost nothing worth a reallocation
@@ -182,6 +191,15 @@ struct map_job {
     int pg_n;                                    // free keyframes of the graph, 0: nothing to do for this map
     const int *pg_kfid; const double *pg_Twc;    // their ids (ascending, last = newkf) and optimised poses, in the staging block
     double *pg_tmp;                              // 14 doubles behind hdr_out: inverse(old(newkf)) | T_corr
+    // merge of map points (hdr / zero_blk point at the stage's own block in its job records)
+    int mg_seg;                                  // pairs in this map's segment of the lists, 0: nothing to do for this map
+    const int *mg_prev, *mg_new;                 // the segment: prevlmid / newlmid per pair, in list order
+    const unsigned char *mg_cur;                 // per pair: the current frame held prevlmid (may be null)
+    const int *mg_n_dev;                         // null, or how many pairs of the segment count (device memory)
+    unsigned char *mg_status;                    // per pair: OV2_MERGE_* (may be null)
+    int *mg_cnt, *mg_fill, *mg_next, *mg_stamp, *mg_start, *mg_rows;
+    unsigned char *mg_mark;
+    int *obs_lm_w;                               // writable twin of obs_lm (the walk relabels rows)
 };
 
 // the flat problem of one map inside its output block: the same carve on the device (emitters, update stage) and on the
@@ -448,7 +466,8 @@ __global__ __launch_bounds__(256) void ms_res_count_kernel(const map_job *__rest
 // block sums -> their scan -> block offsets.  `which` selects the array of the map: SC_LM the landmark flags (64-bit,
 // total -> NLM | NBAD), SC_RES the residual counts (total -> NRES), SC_LIVE the keep flags of a compaction (total -> NLIVE),
 // SC_KF the live rows per keyframe of the keyframe filter (total -> FH_ROWS of its header)
-enum { SC_LM = 0, SC_RES, SC_LIVE, SC_KF };
+// SC_MG the live rows per named landmark of the map-point merge (total -> GH_ROWS of its header)
+enum { SC_LM = 0, SC_RES, SC_LIVE, SC_KF, SC_MG };
 
 template <typename T>
 __device__ __forceinline__ T shfl_up_t(T v, int o)
@@ -471,6 +490,9 @@ __device__ __forceinline__ void scan_args(const map_job &j, int which, const T *
     } else if (which == SC_KF) {
         in = reinterpret_cast<const T *>(j.fl_cnt); out = reinterpret_cast<T *>(j.fl_start); n = j.fl_active ? j.M.max_kf : 0;
         total = reinterpret_cast<T *>(j.hdr + FH_ROWS);
+    } else if (which == SC_MG) {
+        in = reinterpret_cast<const T *>(j.mg_cnt); out = reinterpret_cast<T *>(j.mg_start); n = j.mg_seg ? j.M.max_lm : 0;
+        total = reinterpret_cast<T *>(j.hdr + GH_ROWS);
     } else {
         in = reinterpret_cast<const T *>(j.obs_cnt); out = reinterpret_cast<T *>(j.obs_off); n = j.M.n_obs;
         total = reinterpret_cast<T *>(j.hdr + (which == SC_RES ? MH_NRES : MH_NLIVE));
@@ -1045,6 +1067,126 @@ __global__ __launch_bounds__(MF_THREADS) void mf_walk_kernel(const map_job *__re
     }
 }
 
+// ---- MapManager::mergeMapPoints (src/map_manager.cpp:801-882) on the tables ---------------------------------------------
+// The pairs of a map are applied one after the other, each against the tables as the pairs before it left them.  Three
+// scans build an index of the rows of the landmarks the list names (mark, count, scan, scatter: a counting sort by
+// landmark, as the keyframe filter sorts by keyframe), then one workgroup per map walks the list.  A landmark owns the
+// segment of its rows as they stood before the call; a merged `prev` hands its segments on: its chain is linked behind
+// the chain of `new`, so a later pair that names `new` finds the adopted rows too and passes over rows whose label has
+// moved on (conflict rows keep the dead label).  A pair costs the rows of its two chains, never the table.
+__device__ __forceinline__ void st_int(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// pairs of the segment that count: all of them, or the device-side count clamped to the segment
+__device__ __forceinline__ int mg_npairs(const map_job &j)
+{
+    return j.mg_n_dev ? min(j.mg_seg, max(*j.mg_n_dev, 0)) : j.mg_seg;
+}
+
+__global__ __launch_bounds__(256) void mg_mark_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= mg_npairs(j)) return;
+    const int p = j.mg_prev[i], n = j.mg_new[i];
+    if ((unsigned)p >= (unsigned)j.M.max_lm || (unsigned)n >= (unsigned)j.M.max_lm) return;   // the walk skips the pair
+    j.mg_mark[p] = 1; j.mg_mark[n] = 1;
+}
+
+__global__ __launch_bounds__(256) void mg_count_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (!j.mg_seg || (int)blockIdx.x * 256 >= M.n_obs) return;   // uniform per workgroup
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf = 0, lm = 0;
+    if (i < M.n_obs && obs_live(M, i, kf, lm) && j.mg_mark[lm]) atomicAdd(&j.mg_cnt[lm], 1);
+}
+
+// row i joins the rows of its landmark, in any order (the walk's edits do not depend on it)
+__global__ __launch_bounds__(256) void mg_index_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (!j.mg_seg || (int)blockIdx.x * 256 >= M.n_obs) return;   // uniform per workgroup
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf = 0, lm = 0;
+    // mg_start[lm] + mg_cnt[lm] <= GH_ROWS <= n_obs <= max_obs: the slot lies inside mg_rows
+    if (i < M.n_obs && obs_live(M, i, kf, lm) && j.mg_mark[lm]) j.mg_rows[j.mg_start[lm] + atomicAdd(&j.mg_fill[lm], 1)] = i;
+}
+
+// One workgroup per map walks its pairs in list order; its tail writes the header into the gathered copy.  Labels, landmark
+// states, stamps and links that a pair edits are read again by other lanes for the next pair: they go through device-scope
+// atomics, and barriers separate the stamps of `new` from the test of `prev`'s rows, and a pair's edits from the next pair's
+// reads.  Everything that decides the control flow (the pair, its status, the chains) is uniform over the workgroup.
+#define MG_THREADS 256
+__global__ __launch_bounds__(MG_THREADS) void mg_walk_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ int s_moved[MG_THREADS / 64], s_conf[MG_THREADS / 64];
+    const int np = mg_npairs(j);
+    int nmerged = 0, nskipped = 0;   // the same in every lane
+    int moved = 0, conflict = 0;     // this lane's rows
+    for (int i = 0; i < np; ++i) {
+        const int p = j.mg_prev[i], n = j.mg_new[i];
+        int status = OV2_MERGE_DONE, sn = 0;
+        if ((unsigned)p >= (unsigned)M.max_lm || (unsigned)n >= (unsigned)M.max_lm) status = OV2_MERGE_SKIP_RANGE;
+        else if (p == n) status = OV2_MERGE_SKIP_SAME;
+        else {
+            sn = ld_u8(j.lm_state_w + n);
+            if (!(ld_u8(j.lm_state_w + p) & OV2_LM_ALIVE)) status = OV2_MERGE_SKIP_PREV_DEAD;
+            else if (!(sn & OV2_LM_ALIVE)) status = OV2_MERGE_SKIP_NEW_DEAD;
+            else if (!(sn & OV2_LM_3D)) status = OV2_MERGE_SKIP_NEW_NOT3D;   // :812-827
+        }
+        if (tid == 0 && j.mg_status) j.mg_status[i] = (unsigned char)status;
+        if (status != OV2_MERGE_DONE) { ++nskipped; continue; }   // nothing was edited: no barrier owed
+        ++nmerged;
+        // the keyframes that hold `new` (Frame::mapkps_.count(newlmid)); both landmarks are alive, so a row of their chains
+        // that still carries the label is a live row
+        int tail = n;
+        for (int s = n; s >= 0; s = ld_int(j.mg_next + s) - 1) {
+            tail = s;
+            const int *rows = j.mg_rows + j.mg_start[s];
+            const int cnt = j.mg_cnt[s];
+            for (int t = tid; t < cnt; t += MG_THREADS) {
+                const int r = rows[t];
+                if (ld_int(j.obs_lm_w + r) == n) st_int(j.mg_stamp + M.obs_kf[r], i + 1);
+            }
+        }
+        __syncthreads();
+        // Frame::updateKeypointId(prevlmid, newlmid) per observer of `prev`: false where the keyframe holds `new` already
+        for (int s = p; s >= 0; s = ld_int(j.mg_next + s) - 1) {
+            const int *rows = j.mg_rows + j.mg_start[s];
+            const int cnt = j.mg_cnt[s];
+            for (int t = tid; t < cnt; t += MG_THREADS) {
+                const int r = rows[t];
+                if (ld_int(j.obs_lm_w + r) != p) continue;
+                if (ld_int(j.mg_stamp + M.obs_kf[r]) == i + 1) ++conflict;
+                else { st_int(j.obs_lm_w + r, n); ++moved; }
+            }
+        }
+        if (tid == 0) {
+            st_int(j.mg_next + tail, p + 1);   // the chains are disjoint: no lane reads this link before the barrier
+            st_u8(j.lm_state_w + p, 0);        // map_plms_.erase(prevlmid)
+            if (j.mg_cur && j.mg_cur[i]) st_u8(j.lm_state_w + n, sn | OV2_LM_OBS);   // setMapPointObs(newlmid), :860-866
+        }
+        __syncthreads();
+    }
+    if (j.mg_status)   // the pairs of the segment beyond the device-side count
+        for (int t = np + tid; t < j.mg_seg; t += MG_THREADS) j.mg_status[t] = OV2_MERGE_NOT_RUN;
+    for (int o = 32; o; o >>= 1) { moved += __shfl_xor(moved, o); conflict += __shfl_xor(conflict, o); }
+    if (lane == 0) { s_moved[wv] = moved; s_conf[wv] = conflict; }
+    __syncthreads();
+    if (tid == 0) {
+        moved = conflict = 0;
+        for (int w = 0; w < MG_THREADS / 64; ++w) { moved += s_moved[w]; conflict += s_conf[w]; }
+        int *H = j.hdr_out;
+        for (int t = 0; t < MH_N; ++t) H[t] = 0;
+        H[GH_PAIRS] = np; H[GH_MERGED] = nmerged; H[GH_SKIPPED] = nskipped; H[GH_MOVED] = moved; H[GH_CONFLICT] = conflict;
+    }
+}
+
 // ---- update stage of Optimizer::localPoseGraph (src/optimizer.cpp:2476-2577) on the tables ------------------------------
 // The free keyframes of the graph (listed, ascending, last = newkf) take their optimised poses, every younger keyframe k
 // moves rigidly with the new one (opt * (ini * old(k)), ini = inverse(old(newkf))), and a landmark moves with the keyframe
@@ -1210,6 +1352,7 @@ map_job job_of(const ov2_map *m, int newkf, int cur_kfid)
     j.snap_kf_pose = m->snap_kf_pose; j.snap_lm_xyz = m->snap_lm_xyz; j.snap_kf_state = m->snap_kf_state;
     j.snap_lm_state = m->snap_lm_state; j.snap_obs_flag = m->snap_obs_flag;
     j.snap_kf = m->snap_kf; j.snap_lm = m->snap_lm; j.snap_obs = m->snap_obs;
+    j.obs_lm_w = m->obs_lm;
     return j;
 }
 
@@ -1329,6 +1472,13 @@ static ov2_status alloc_tables(ov2_map *m)
         m->fl_cnt = m->fl_n3d + K; m->fl_fill = m->fl_cnt + K;
         m->fl_new = reinterpret_cast<unsigned char *>(m->fl_fill + K);
     }
+    m->mg_zero_bytes = (sizeof(int) * (MH_N + 3 * L + K) + L + 15) & ~(size_t)15;
+    A(mg_zero, m->mg_zero_bytes); A(mg_start, L); A(mg_rows, N);
+    if (s == OV2_OK) {
+        m->mg_cnt = reinterpret_cast<int *>(m->mg_zero) + MH_N; m->mg_fill = m->mg_cnt + L; m->mg_next = m->mg_fill + L;
+        m->mg_stamp = m->mg_next + L;
+        m->mg_mark = reinterpret_cast<unsigned char *>(m->mg_stamp + K);
+    }
 #undef A
     return s;
 }
@@ -1337,7 +1487,8 @@ static void free_capacity_arrays(ov2_map *m)
 {
     void *dev[] = {m->kf_pose, m->kf_state, m->lm_xyz, m->lm_state, m->obs_kf, m->obs_lm, m->obs_scale, m->obs_uv, m->obs_ruv,
                    m->obs_flag, m->zero_blk, m->kf_idx, m->lm_flag, m->lm_pack, m->lm_pidx, m->obs_cnt, m->obs_off, m->blk,
-                   m->tt_zero, m->tt_int, m->tt_dbl, m->fl_zero, m->fl_start, m->fl_rows, m->fl_unset};
+                   m->tt_zero, m->tt_int, m->tt_dbl, m->fl_zero, m->fl_start, m->fl_rows, m->fl_unset,
+                   m->mg_zero, m->mg_start, m->mg_rows};
     for (void *p : dev) if (p) (void)hipFree(p);
 }
 
@@ -1355,6 +1506,7 @@ static ov2_status ensure_capacity(ov2_map *m, int need_kf, int need_lm, int need
     m->zero_blk = nullptr; m->kf_idx = m->lm_flag = m->obs_cnt = m->obs_off = m->blk = nullptr; m->lm_pack = m->lm_pidx = nullptr;
     m->tt_zero = nullptr; m->tt_int = nullptr; m->tt_dbl = nullptr;
     m->fl_zero = nullptr; m->fl_start = m->fl_rows = m->fl_unset = nullptr;
+    m->mg_zero = nullptr; m->mg_start = m->mg_rows = nullptr;
     ov2_status s = alloc_tables(m);
     unsigned char *alive = s == OV2_OK ? (unsigned char *)calloc((size_t)m->max_kf, 1) : nullptr;
     if (s == OV2_OK && !alive) s = ov2_set_err(c, OV2_ERR_NOMEM, "map keyframe list of %d entries", m->max_kf);
@@ -2148,6 +2300,107 @@ extern "C" ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *c, int B, ov2_map
         memcpy(out[b].T_corr, (const double *)(H + MH_N) + 7, 7 * sizeof(double));
     }
     return OV2_OK;
+}
+
+// ---- map-point merges of B maps: eight launches whatever B and the pair counts are (clear, mark, count, three of the scan,
+// index, walk), no synchronisation unless headers or host-side statuses are asked for ---------------------------------------
+namespace {
+
+ov2_status merge_batch_impl(ov2_ctx *c, const char *who, bool dev, int B, ov2_map *const *maps, const int32_t *pair_off,
+                            const int32_t *prev, const int32_t *nw, const uint8_t *cur, const int32_t *d_n_pairs, ov2_map_merge *out,
+                            uint8_t *status)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps || !pair_off) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null argument", who);
+    if (pair_off[0] != 0) return ov2_set_err(c, OV2_ERR_INVALID, "%s: pair_off[0] must be 0", who);
+    ov2_status s;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
+        if (pair_off[b + 1] < pair_off[b]) return ov2_set_err(c, OV2_ERR_INVALID, "map %d: pair_off descends", b);
+        if (m->snap_kf_pose)   // the snapshot does not cover obs_lm: a restore could not undo a relabel
+            return ov2_set_err(c, OV2_ERR_INVALID, "map %d holds a saved state: its rows cannot be relabelled", b);
+    }
+    const size_t total = (size_t)pair_off[B];
+    if (total && (!prev || !nw)) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null pair list", who);
+    if (out) memset(out, 0, (size_t)B * sizeof(*out));
+    if (!total) return OV2_OK;
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // host form: [statuses | prev | new | cur_obs] behind the gathered headers, so that headers and statuses come back in one copy
+    const size_t st_bytes = (total + 15) & ~(size_t)15, id_bytes = (total * sizeof(int32_t) + 15) & ~(size_t)15;
+    job_table JT;
+    if ((s = JT.begin(c, B, 0, dev ? 0 : 2 * st_bytes + 2 * id_bytes)) != OV2_OK) return s;
+    const int32_t *d_prev = prev, *d_new = nw;
+    const uint8_t *d_cur = cur;
+    uint8_t *d_status = status;
+    if (!dev) {
+        memcpy(JT.tail_host + st_bytes, prev, total * sizeof(int32_t));
+        memcpy(JT.tail_host + st_bytes + id_bytes, nw, total * sizeof(int32_t));
+        if (cur) memcpy(JT.tail_host + st_bytes + 2 * id_bytes, cur, total);
+        d_status = status ? JT.tail_dev : nullptr;
+        d_prev = (const int32_t *)(JT.tail_dev + st_bytes); d_new = (const int32_t *)(JT.tail_dev + st_bytes + id_bytes);
+        d_cur = cur ? JT.tail_dev + st_bytes + 2 * id_bytes : nullptr;
+    }
+    int nmax = 0, lmax = 0, pmax = 0; unsigned zmax = 0;
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = maps[b];
+        map_job j = job_of(m, -1, -1);
+        j.mg_seg = pair_off[b + 1] - pair_off[b];
+        stage_block(j, m->mg_zero, j.mg_seg ? m->mg_zero_bytes : 0);
+        j.mg_prev = d_prev + pair_off[b]; j.mg_new = d_new + pair_off[b];
+        j.mg_cur = d_cur ? d_cur + pair_off[b] : nullptr;
+        j.mg_n_dev = d_n_pairs ? d_n_pairs + b : nullptr;
+        j.mg_status = d_status ? d_status + pair_off[b] : nullptr;
+        j.mg_cnt = m->mg_cnt; j.mg_fill = m->mg_fill; j.mg_next = m->mg_next; j.mg_stamp = m->mg_stamp; j.mg_mark = m->mg_mark;
+        j.mg_start = m->mg_start; j.mg_rows = m->mg_rows;
+        JT.set(b, j);
+        if (!j.mg_seg) continue;   // an empty list leaves the map alone
+        nmax = std::max(nmax, m->n_obs); lmax = std::max(lmax, m->max_lm); pmax = std::max(pmax, j.mg_seg); zmax = std::max(zmax, j.zero_vec16);
+        m->last_valid = 0;   // its tables change under the last set-up: no update stage from it any more
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), gP((pmax + 255) / 256, B), b256(256);
+    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::min(64u, (zmax + 255) / 256), B), b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mg_mark_kernel, gP, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mg_count_kernel, gN, b256, 0, st, JT.dev);
+    if ((s = exclusive_scan<int>(c, JT, SC_MG, lmax)) != OV2_OK) return s;
+    OV2_LAUNCH(c, OV2_K_MAP, mg_index_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mg_walk_kernel, dim3(1, B), dim3(MG_THREADS), 0, st, JT.dev);
+    OV2_HIP(c, hipGetLastError());
+    if (!out && (dev || !status)) return OV2_OK;   // asynchronous: nothing to hand to the host
+    if (dev) {
+        if ((s = JT.fetch_headers()) != OV2_OK) return s;
+    } else {   // the headers and, right behind them, the statuses
+        const size_t bytes = (size_t)(JT.tail_host - (unsigned char *)JT.hdr_host) + total;
+        OV2_HIP(c, hipMemcpyAsync(JT.hdr_host, JT.hdr_dev, bytes, hipMemcpyDeviceToHost, st));
+        OV2_HIP(c, hipStreamSynchronize(st));
+        if (status) memcpy(status, JT.tail_host, total);
+    }
+    for (int b = 0; b < B && out; ++b) {
+        const int *H = JT.hdr_host + (size_t)b * JT.stride;
+        out[b].n_pairs = H[GH_PAIRS]; out[b].n_merged = H[GH_MERGED]; out[b].n_skipped = H[GH_SKIPPED];
+        out[b].n_rows_moved = H[GH_MOVED]; out[b].n_rows_conflict = H[GH_CONFLICT];
+    }
+    return OV2_OK;
+}
+
+}  // namespace
+
+extern "C" ov2_status ov2_map_merge_points_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *pair_off, const int32_t *prev_lmid,
+                                                 const int32_t *new_lmid, const uint8_t *cur_obs, ov2_map_merge *out, uint8_t *pair_status)
+{
+    return merge_batch_impl(c, "ov2_map_merge_points_batch", false, B, maps, pair_off, prev_lmid, new_lmid, cur_obs, nullptr, out, pair_status);
+}
+
+extern "C" ov2_status ov2_map_merge_points_batch_dev(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *pair_off,
+                                                     const int32_t *d_prev_lmid, const int32_t *d_new_lmid, const uint8_t *d_cur_obs,
+                                                     const int32_t *d_n_pairs, ov2_map_merge *out, uint8_t *d_pair_status)
+{
+    return merge_batch_impl(c, "ov2_map_merge_points_batch_dev", true, B, maps, pair_off, d_prev_lmid, d_new_lmid, d_cur_obs, d_n_pairs, out,
+                            d_pair_status);
 }
 
 // ---- saved state (bench / tests: every job starts from the same map) ----------------------------------------------

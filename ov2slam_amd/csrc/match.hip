@@ -545,6 +545,74 @@ extern "C" ov2_status ov2_match_to_map_batch(ov2_ctx *c, const ov2_match_batch_i
     return OV2_OK;
 }
 
+// ---- the matcher's output as ordered pair lists (Mapper::mergeMatches, src/mapper.cpp:556-574) --------------------------
+
+namespace {
+
+#define PAIRS_THREADS 256
+// One workgroup per frame.  map_previd_newid is a std::map: the pairs leave it in ascending prevlmid, so a pair's slot is its
+// rank among the frame's matched keypoints (ties, which a frame's distinct lmids never give, fall back to the keypoint index:
+// the ranks stay a permutation and every write stays inside the frame's segment).  The keys go through LDS 256 at a time.
+__global__ __launch_bounds__(PAIRS_THREADS) void match_pairs_kernel(const int *__restrict__ kp_off, const int *__restrict__ cand_off,
+                                                                    const int *__restrict__ kp_lmid, const int *__restrict__ cand_lmid,
+                                                                    const int *__restrict__ match_cand, int *__restrict__ prev_lmid,
+                                                                    int *__restrict__ new_lmid, int *__restrict__ n_pairs)
+{
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int k0 = kp_off[b], n = kp_off[b + 1] - k0, c0 = cand_off[b], nc = cand_off[b + 1] - c0;
+    __shared__ int s_key[PAIRS_THREADS], s_on[PAIRS_THREADS], s_count;
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    int count = 0;   // matched keypoints of the frame, the same in every lane after the loop
+    for (int base = 0; base < n; base += PAIRS_THREADS) {   // n is uniform: every lane takes every turn
+        const int k = base + tid;
+        const int mc = k < n ? match_cand[k0 + k] : -1;
+        const bool on = mc >= 0 && mc < nc;   // (a candidate index outside the frame cannot be looked up: no pair)
+        const int key = on ? kp_lmid[k0 + k] : 0;
+        int rank = 0;
+        for (int cb = 0; cb < n; cb += PAIRS_THREADS) {
+            const int q = cb + tid;
+            const int mq = q < n ? match_cand[k0 + q] : -1;
+            __syncthreads();
+            s_on[tid] = mq >= 0 && mq < nc;
+            s_key[tid] = s_on[tid] ? kp_lmid[k0 + q] : 0;
+            __syncthreads();
+            if (!on) continue;
+            const int m = min(PAIRS_THREADS, n - cb);
+            for (int t = 0; t < m; ++t)
+                rank += s_on[t] && (s_key[t] < key || (s_key[t] == key && cb + t < k));
+        }
+        if (on) {
+            prev_lmid[k0 + rank] = key;
+            new_lmid[k0 + rank] = cand_lmid[c0 + mc];
+        }
+        const unsigned long long bal = __ballot(on);
+        if ((tid & 63) == 0 && bal) atomicAdd(&s_count, __popcll(bal));
+    }
+    __syncthreads();
+    count = s_count;
+    for (int t = count + tid; t < n; t += PAIRS_THREADS) { prev_lmid[k0 + t] = -1; new_lmid[k0 + t] = -1; }
+    if (tid == 0) n_pairs[b] = count;
+}
+
+}  // namespace
+
+extern "C" ov2_status ov2_match_pairs_dev(ov2_ctx *c, int B, int n_kp, const int32_t *d_kp_off, const int32_t *d_cand_off,
+                                          const int32_t *d_kp_lmid, const int32_t *d_cand_lmid, const int32_t *d_match_cand,
+                                          int32_t *d_prev_lmid, int32_t *d_new_lmid, int32_t *d_n_pairs)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B < 0 || n_kp < 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_pairs_dev: negative count");
+    if (B == 0) return OV2_OK;
+    if (!d_kp_off || !d_cand_off || !d_n_pairs || (n_kp && (!d_kp_lmid || !d_cand_lmid || !d_match_cand || !d_prev_lmid || !d_new_lmid)))
+        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_pairs_dev: null argument");
+    OV2_HIP(c, hipSetDevice(c->device));
+    OV2_LAUNCH(c, K_MATCH, match_pairs_kernel, dim3(B), dim3(PAIRS_THREADS), 0, c->stream, d_kp_off, d_cand_off, d_kp_lmid, d_cand_lmid,
+               d_match_cand, d_prev_lmid, d_new_lmid, d_n_pairs);
+    OV2_HIP(c, hipGetLastError());
+    return OV2_OK;
+}
+
 // ---- LoopCloser::matchToMap for B candidate pairs (src/loop_closer.cpp:586-763) -------------------------------------
 
 namespace {

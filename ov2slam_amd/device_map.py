@@ -41,6 +41,27 @@ class PgUpdateC(C.Structure):
     _fields_ = [("n_kf_chain", C.c_int32), ("n_kf_younger", C.c_int32), ("n_lm_moved", C.c_int32), ("T_corr", C.c_double * 7)]
 
 
+class MergeC(C.Structure):
+    """ov2_map_merge"""
+    _fields_ = [("n_pairs", C.c_int32), ("n_merged", C.c_int32), ("n_skipped", C.c_int32), ("n_rows_moved", C.c_int32),
+                ("n_rows_conflict", C.c_int32)]
+
+
+# OV2_MERGE_* status bytes (include/ov2slam_hip.h)
+MERGE_DONE, MERGE_SKIP_RANGE, MERGE_SKIP_SAME, MERGE_SKIP_PREV_DEAD, MERGE_SKIP_NEW_DEAD, MERGE_SKIP_NEW_NOT3D = range(6)
+MERGE_NOT_RUN = 255
+
+
+class DevPairs:
+    """device-resident pair lists as ov2_map_merge_points_batch_dev takes them: pair_off (host, B + 1), d_prev / d_new
+    (DeviceArray int32 over pair_off[B] slots), d_n_pairs (DeviceArray int32 (B,) or None = whole segments), d_cur_obs
+    (DeviceArray uint8 or None)"""
+
+    def __init__(self, pair_off, d_prev, d_new, d_n_pairs=None, d_cur_obs=None):
+        self.pair_off = np.ascontiguousarray(pair_off, np.int32)
+        self.d_prev, self.d_new, self.d_n_pairs, self.d_cur_obs = d_prev, d_new, d_n_pairs, d_cur_obs
+
+
 class UpdateC(C.Structure):
     """ov2_local_ba_update"""
     _fields_ = [("n_removed_lm", C.c_int32), ("n_removed_obs", C.c_int32), ("n_stereo_off", C.c_int32),
@@ -171,6 +192,10 @@ class DeviceMap:
     def pose_graph_update_batch(self, others=(), newkf=None, chain_kfid=(), chain_Twc=(), want_header=True):
         """ov2_map_pose_graph_update_batch on this map and `others` in one call; see pose_graph_update_batch"""
         return pose_graph_update_batch(self.ctx, [self] + list(others), newkf, chain_kfid, chain_Twc, want_header)
+
+    def merge_points_batch(self, others=(), pairs=(), cur_obs=None, want_header=True):
+        """ov2_map_merge_points_batch on this map and `others` in one call; see merge_points_batch"""
+        return merge_points_batch(self.ctx, [self] + list(others), pairs, cur_obs, want_header)
 
     def close(self):
         if getattr(self, "h", None):
@@ -329,6 +354,53 @@ def pose_graph_update_batch(ctx, maps, newkf=None, chain_kfid=(), chain_Twc=(), 
         return None
     return [dict(n_kf_chain=u.n_kf_chain, n_kf_younger=u.n_kf_younger, n_lm_moved=u.n_lm_moved, T_corr=np.array(u.T_corr[:]))
             for u in out]
+
+
+def merge_points_batch(ctx, maps, pairs, cur_obs=None, want_header=True, dev=False):
+    """MapManager::mergeMapPoints on the tables of the maps (DeviceMap objects or raw ov2_map handles): pairs[b] is map b's
+    ordered list of (prevlmid, newlmid), cur_obs[b] (optional) one flag per pair -- the current frame held prevlmid.
+    dev=False: ov2_map_merge_points_batch on host arrays.  dev=True: ov2_map_merge_points_batch_dev, either on the same lists
+    uploaded here or on a DevPairs (then cur_obs is the DevPairs' own).  Returns (per map dict(n_pairs, n_merged, n_skipped,
+    n_rows_moved, n_rows_conflict), per map uint8 array of OV2_MERGE_* statuses over its segment) -- or None
+    (want_header=False: fully asynchronous, nothing is read back)"""
+    B = len(maps)
+    hs = (C.c_void_p * B)(*[getattr(m, "h", m) for m in maps])
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    if isinstance(pairs, DevPairs):
+        assert dev
+        dp_ = pairs
+    else:
+        ps = [np.ascontiguousarray(q, np.int32).reshape(-1, 2) for q in pairs]
+        assert len(ps) == B
+        off = np.concatenate([[0], np.cumsum([len(q) for q in ps])]).astype(np.int32)
+        prev = np.ascontiguousarray(np.concatenate([q[:, 0] for q in ps] + [np.zeros(0, np.int32)]), np.int32)
+        new = np.ascontiguousarray(np.concatenate([q[:, 1] for q in ps] + [np.zeros(0, np.int32)]), np.int32)
+        cur = None
+        if cur_obs is not None:
+            cs = [np.zeros(len(q), np.uint8) if c is None else np.ascontiguousarray(c, np.uint8).reshape(-1) for q, c in zip(ps, cur_obs)]
+            assert all(len(c) == len(q) for c, q in zip(cs, ps))
+            cur = np.ascontiguousarray(np.concatenate(cs + [np.zeros(0, np.uint8)]), np.uint8)
+        if dev:
+            pad = lambda a: a if len(a) else np.zeros(1, a.dtype)
+            dp_ = DevPairs(off, ctx.to_device(pad(prev)), ctx.to_device(pad(new)), None, None if cur is None else ctx.to_device(pad(cur)))
+    out = (MergeC * B)() if want_header else None
+    if dev:
+        total = int(dp_.pair_off[-1]) if B else 0
+        d_st = ctx.to_device(np.full(max(total, 1), MERGE_NOT_RUN, np.uint8)) if want_header else None
+        ptr = lambda a: None if a is None else a.ptr
+        _check(ctx.h, ctx.lib.ov2_map_merge_points_batch_dev(ctx.h, B, hs, p(dp_.pair_off), ptr(dp_.d_prev), ptr(dp_.d_new),
+                                                            ptr(dp_.d_cur_obs), ptr(dp_.d_n_pairs), out, ptr(d_st)))
+        if not want_header:
+            return None
+        off, st = dp_.pair_off, d_st.get()[:total]
+    else:
+        st = np.full(max(int(off[-1]), 1), MERGE_NOT_RUN, np.uint8) if want_header else None
+        _check(ctx.h, ctx.lib.ov2_map_merge_points_batch(ctx.h, B, hs, p(off), p(prev), p(new), p(cur), out, p(st)))
+        if not want_header:
+            return None
+    hdr = [dict(n_pairs=u.n_pairs, n_merged=u.n_merged, n_skipped=u.n_skipped, n_rows_moved=u.n_rows_moved,
+                n_rows_conflict=u.n_rows_conflict) for u in out]
+    return hdr, [st[off[b]:off[b + 1]].copy() for b in range(B)]
 
 
 def restore_state_batch(ctx, maps):

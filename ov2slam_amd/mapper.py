@@ -180,6 +180,23 @@ class MatchBatchInputDev:
         self.ctx.synchronize()
         return self.d_mc.get()[:n], self.d_md.get()[:n]
 
+    def pairs(self, kp_lmid, cand_lmid):
+        """ov2_match_pairs_dev behind enqueue(): the matches as the ordered (prevlmid, newlmid) lists of Mapper::mergeMatches,
+        one segment per frame (kp_off), ascending prevlmid, -1 behind the pairs.  kp_lmid (n_kp) / cand_lmid (n_cand): the
+        lmids of the keypoints and of the candidates, host arrays or DeviceArrays.  Asynchronous; returns the
+        device_map.DevPairs that device_map.merge_points_batch(..., dev=True) takes"""
+        from .device_map import DevPairs
+        ctx, n = self.ctx, self.host.c.n_kp
+        up = lambda a: a if hasattr(a, "ptr") else ctx.to_device(np.ascontiguousarray(a, np.int32) if len(a) else np.zeros(1, np.int32))
+        d_kl, d_cl = up(kp_lmid), up(cand_lmid)
+        d_prev, d_new = ctx.empty(max(n, 1), np.int32), ctx.empty(max(n, 1), np.int32)
+        d_np = ctx.empty(max(self.host.c.B, 1), np.int32)
+        _check(ctx.h, ctx.lib.ov2_match_pairs_dev(ctx.h, self.host.c.B, n, self.dev["kp_off"].ptr, self.dev["cand_off"].ptr, d_kl.ptr,
+                                                  d_cl.ptr, self.d_mc.ptr, d_prev.ptr, d_new.ptr, d_np.ptr))
+        out = DevPairs(self.host.kp_off, d_prev, d_new, d_np)
+        out.keep = (d_kl, d_cl)   # the launch may still be reading them
+        return out
+
 
 def matchToMap_batch_dev(ctx, inp, fmaxprojerr=2.0, fdistratio=0.2, fill=-7):
     """the device-resident form on arrays uploaded here.  Returns (match_cand, match_dist) after a synchronisation of its own."""
