@@ -1198,7 +1198,11 @@ typedef struct ov2_match_input {
  * keypoints of the 2 x 2 grid cells around the projection (Frame::getSurroundingKeypoints, src/frame.cpp:624-650) within
  * dmaxpxdist, never co-observed (:686-695), mean reprojection distance in the keypoint's keyframes <= dmaxpxdist
  * (:700-719), MapPoint::computeMinDescDist (Hamming), best / second best with the 0.9 ratio (:723-740); per keypoint the
- * candidate with the smallest distance, the later one on ties (:754-771).  Host pointers, synchronous. */
+ * candidate with the smallest distance, the later one on ties (:754-771).  Host pointers, synchronous.
+ * The call is the B = 1 case of ov2_match_to_map_batch below (n_kf < 0 reads as 0) and refuses what that form refuses:
+ * OV2_ERR_INVALID, with nothing enqueued and the outputs at most pre-filled with -1 / 0, for a prefix array (kp_desc_ptr,
+ * kp_kf_ptr, cand_desc_ptr, cand_kf_ptr, grid_ptr) that decreases or does not start at 0, a grid entry outside [0, n_kp), a
+ * null array that a non-empty call needs, an unknown lens model. */
 ov2_status ov2_match_to_map(ov2_ctx *ctx, const ov2_match_input *in, float fmaxprojerr, float fdistratio,
                             int32_t *match_cand /* n_kp */, float *match_dist /* n_kp */);
 
@@ -1221,8 +1225,9 @@ ov2_status ov2_match_to_map(ov2_ctx *ctx, const ov2_match_input *in, float fmaxp
  * ratio; per keypoint the smallest distance wins, the LATER candidate on ties.
  *
  * match_cand[k] = the candidate's index WITHIN ITS OWN FRAME, or -1; match_dist[k] = its Hamming distance (0 with -1).
- * Only integers and gate decisions come out: a frame's results are bit-identical to ov2_match_to_map on that frame alone,
- * whatever the batch contains, in any order, for any workgroup shape, in either form.
+ * Only integers and gate decisions come out: a frame's results are bit-identical to those of the frame alone, whatever the
+ * batch contains, in any order, for any workgroup shape, in either form -- and to ov2_match_to_map on that frame by
+ * construction: that call is this one with B = 1.
  * Host form: host pointers (cam included); one staging block, one upload, one memset, two launches, one download and one
  * synchronisation whatever B is.  B = 0, a frame without keypoints and a frame without candidates are OV2_OK (and write
  * -1 / 0).  OV2_ERR_INVALID with nothing enqueued: negative counts; offsets that do not start at 0, that decrease or that do

@@ -1,17 +1,20 @@
 // match.hip -- keyframe descriptors and map matching (first half):
 //   brief_kernel   FeatureExtractor::describeBRIEF src/feature_extractor.cpp:224-285 (cv::xfeatures2d::BriefDescriptorExtractor:
 //                  32 bytes, patch 48, 9 x 9 box sums at the rounded keypoint) with a caller-supplied test table
-//   match_*        Mapper::matchToMap src/mapper.cpp:576-774 on flat arrays (ov2_match_input)
-//   match_batch_*  the same for B frames, one local map each (ov2_match_batch_input)
-//   loop_match_*   LoopCloser::matchToMap src/loop_closer.cpp:586-763 for B candidate pairs (ov2_loop_match_input)
+//   match_cand_kernel<false>  Mapper::matchToMap src/mapper.cpp:576-774 for B frames, one local map each
+//                  (ov2_match_batch_input; ov2_match_input is its B = 1 case)
+//   match_cand_kernel<true>   LoopCloser::matchToMap src/loop_closer.cpp:586-763 for B candidate pairs (ov2_loop_match_input)
 // Integer box sums and Hamming distances => bit-exact against the oracle; the float gates are evaluated in its order.
+#include <type_traits>
+
 #include "ov2_internal.h"
 #include "ov2_cam.h"
 #include "ov2_se3.h"
 
 namespace {
 
-enum { K_BRIEF = OV2_K_MAP + 4, K_MATCH = OV2_K_MAP + 5 };
+enum { K_BRIEF = OV2_K_MAP + 4, K_MATCH = OV2_K_MAP + 5, K_LOOP_MATCH = OV2_K_MAP + 15 };
+enum { MATCH_WAVES = 4 };   // candidates per workgroup of match_cand_kernel
 
 // one wave per keypoint: the 57 x 57 pixels the 256 tests can touch are staged in LDS, lane l evaluates tests l, l + 64, ...
 __global__ __launch_bounds__(64) void brief_kernel(ov2_pyr_view pv, int n, const float2 *__restrict__ pts,
@@ -62,14 +65,18 @@ __global__ __launch_bounds__(64) void brief_kernel(ov2_pyr_view pv, int n, const
     if (lane == 0) valid[i] = 1;
 }
 
-struct match_dev {   // device twin of ov2_match_input
-    double Twc[7], K[4];
-    ov2_cam_model cam;   // Frame::projWorldToImageDist (model 0: the pinhole map with K)
-    int img_w, img_h, cell, nb3dkps, n_kp, n_cand, n_kf, nbw, ncells;
-    const float2 *kp_px; const int *kp_desc_ptr; const unsigned char *kp_descs; const int *kp_kf_ptr, *kp_kfids; const float2 *kp_kf_px;
+// The arrays of a matcher call: the device twin of ov2_match_batch_input and of ov2_loop_match_input (cam normalised, with
+// the call's K), and on the host the form both are checked and staged in (host pointers then).  Mapper's extras stay null
+// for the loop closer, the loop closer's for Mapper.
+struct match_dev {
+    ov2_cam_model cam;
+    int B, n_kp, n_cand, img_w, img_h, cell, nbw, ncells;
+    const double *Twc; const int *kp_off, *cand_off;
+    const float2 *kp_px; const int *kp_desc_ptr; const unsigned char *kp_descs; const int *kp_kf_ptr, *kp_kfids;
     const int *grid_ptr, *grid_kp;
     const double *cand_wpt; const int *cand_desc_ptr; const unsigned char *cand_descs; const int *cand_kf_ptr, *cand_kfids;
-    const double *kf_Twc;
+    const int *nb3dkps, *kf_off; const float2 *kp_kf_px; const double *kf_Twc;   // Mapper
+    const unsigned char *kp_matched;                                               // loop closer
 };
 
 __device__ inline void world_to_cam(const double *Twc, const double *p, double c[3])
@@ -150,7 +157,7 @@ __device__ inline int match_walk_cells(float px, float py, int cell, int nbw, in
 }
 
 // The per-keypoint test of Mapper::matchToMap (src/mapper.cpp:676-721) for candidate c (descriptors cd0 .. cd1, world point wpt,
-// projected to (px, py)) and keypoint k, both indices into the flat arrays of M (match_dev or match_batch_dev): pixel gate,
+// projected to (px, py)) and keypoint k, both indices into the flat arrays of M (match_dev): pixel gate,
 // descriptors present, co-observation test, mean reprojection distance in the keypoint's keyframes -- kf_Twc / n_kf are the
 // pose table those ids index, ids outside it are skipped, 0 / 0 compares false --, then the minimum Hamming distance over the
 // two descriptor sets.  < 0: the keypoint is not a candidate.
@@ -180,32 +187,70 @@ __device__ inline float match_kp_dist(const Arrays &M, int c, int k, int cd0, in
     return min_desc_dist(M.cand_descs, cd0, cd1, M.kp_descs, kd0, kd1);
 }
 
-// one wave per candidate map point: gates, then the neighbouring keypoints 64 at a time (one per lane: match_kp_dist), and the
-// best / second-best bookkeeping replayed in the reference's order (it breaks ties by position).  The winner goes to
-// the keypoint's slot by a 64-bit atomicMin on (distance, ~candidate index): smallest distance, later candidate on ties.
-__global__ __launch_bounds__(64) void match_cand_kernel(match_dev M, float dmaxpxdist, float mindist, float view_th,
-                                                        unsigned long long *__restrict__ kp_best)
+// The per-keypoint test of LoopCloser::matchToMap (src/loop_closer.cpp:672-709), arguments as match_kp_dist: the matched mask
+// first, pixel gate, descriptors present, co-observation test, minimum Hamming distance; no mean-reprojection gate.
+__device__ inline float loop_kp_dist(const match_dev &M, int c, int k, int cd0, int cd1, float px, float py, float dmaxpxdist)
 {
-    const int c = blockIdx.x, lane = threadIdx.x;
+    if (M.kp_matched[k]) return -1.f;                                               // :672-675
+    const float dx = px - M.kp_px[k].x, dy = py - M.kp_px[k].y;
+    const float pxdist = (float)sqrt((double)dx * dx + (double)dy * dy);
+    const int kd0 = M.kp_desc_ptr[k], kd1 = M.kp_desc_ptr[k + 1];
+    if (pxdist > dmaxpxdist || kd1 <= kd0) return -1.f;                             // :683, :690-695
+    if (kf_lists_meet(M.cand_kfids, M.cand_kf_ptr[c], M.cand_kf_ptr[c + 1], M.kp_kfids, M.kp_kf_ptr[k], M.kp_kf_ptr[k + 1])) return -1.f;
+    return min_desc_dist(M.cand_descs, cd0, cd1, M.kp_descs, kd0, kd1);             // :709
+}
+
+// One wave per candidate map point, MATCH_WAVES candidates per workgroup (the waves share nothing, so the result does not
+// depend on it).  The frame -- for the loop closer: the pair -- of a candidate is found in the B + 1 offsets; its pose, its
+// grid and its keypoint block follow from it.  Then the gates, the neighbouring keypoints 64 at a time, one per lane, and the
+// best / second-best bookkeeping replayed in the reference's order (match_walk_cells).  The winner goes to the keypoint's slot
+// by a 64-bit atomicMin on (distance, ~candidate index within its frame): smallest distance, later candidate on ties.
+// LOOP = false, Mapper::matchToMap: match_kp_dist on the frame's keyframe-pose block, the pixel gate doubled under 30 3-D
+// keypoints (src/mapper.cpp:599-602).  LOOP = true, LoopCloser::matchToMap: loop_kp_dist.
+template <bool LOOP>
+__global__ __launch_bounds__(64 * MATCH_WAVES) void match_cand_kernel(match_dev M, float fmaxprojerr, float mindist, float view_th,
+                                                                     unsigned long long *__restrict__ kp_best)
+{
+    const int c = blockIdx.x * MATCH_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= M.n_cand) return;
+    int lo = 0, hi = M.B;   // the frame b with cand_off[b] <= c < cand_off[b + 1] (empty frames are stepped over)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (M.cand_off[mid] <= c) lo = mid; else hi = mid;
+    }
+    const int b = lo, c0 = M.cand_off[b], k0 = M.kp_off[b], nkp = M.kp_off[b + 1] - k0;
+    if (nkp <= 0) return;
     const int cd0 = M.cand_desc_ptr[c], cd1 = M.cand_desc_ptr[c + 1];
     if (cd1 == cd0) return;
     const double *wpt = M.cand_wpt + 3 * (size_t)c;
     double campt[3];
-    world_to_cam(M.Twc, wpt, campt);
+    world_to_cam(M.Twc + 7 * (size_t)b, wpt, campt);
     if (campt[2] < 0.1) return;
     const float view_angle = (float)(campt[2] / sqrt(campt[0] * campt[0] + campt[1] * campt[1] + campt[2] * campt[2]));
     if (fabsf(view_angle) < view_th) return;
     float px, py;
     ov2_cam_project_dist(M.cam, campt, px, py);
     if (!(px >= 0 && py >= 0 && px < (float)M.img_w && py < (float)M.img_h)) return;
+    float dmaxpxdist = fmaxprojerr;
+    const double *kf_Twc = nullptr;
+    int n_kf = 0;
+    if constexpr (!LOOP) {
+        if (M.nb3dkps[b] < 30) dmaxpxdist = fmaxprojerr * 2.f;
+        const int kf0 = M.kf_off[b];
+        n_kf = M.kf_off[b + 1] - kf0;
+        kf_Twc = M.kf_Twc + 7 * (size_t)kf0;
+    }
     float bestdist;
-    const int bestid = match_walk_cells(px, py, M.cell, M.nbw, M.ncells, M.grid_ptr, M.grid_kp, lane, mindist, bestdist, [&](int k) {
-        return match_kp_dist(M, c, k, cd0, cd1, wpt, px, py, dmaxpxdist, M.kf_Twc, M.n_kf);
+    const int bestid = match_walk_cells(px, py, M.cell, M.nbw, M.ncells, M.grid_ptr + (size_t)b * M.ncells, M.grid_kp, lane, mindist, bestdist,
+                                        [&](int kl) {
+        if ((unsigned)kl >= (unsigned)nkp) return -1.f;   // (the host form refuses such a grid; the _dev form cannot look)
+        if constexpr (LOOP) return loop_kp_dist(M, c, k0 + kl, cd0, cd1, px, py, dmaxpxdist);
+        else return match_kp_dist(M, c, k0 + kl, cd0, cd1, wpt, px, py, dmaxpxdist, kf_Twc, n_kf);
     });
     if (bestid < 0) return;
     if (lane == 0)   // Hamming distances are small integers: exact in the key
-        atomicMin(&kp_best[bestid], ((unsigned long long)(unsigned)(int)bestdist << 32) | (unsigned long long)(0xffffffffu - (unsigned)c));
+        atomicMin(&kp_best[k0 + bestid],
+                  ((unsigned long long)(unsigned)(int)bestdist << 32) | (unsigned long long)(0xffffffffu - (unsigned)(c - c0)));
 }
 
 __global__ void match_out_kernel(int n_kp, const unsigned long long *__restrict__ kp_best, int *__restrict__ match_cand,
@@ -283,128 +328,10 @@ extern "C" ov2_status ov2_describe_brief_batch(ov2_ctx *c, const ov2_pyr *pyr, i
     return describe_brief_host(c, pyr, 0, n, pts_xy, img_idx, pattern, desc, valid);
 }
 
-extern "C" ov2_status ov2_match_to_map(ov2_ctx *c, const ov2_match_input *in, float fmaxprojerr, float fdistratio,
-                                       int32_t *match_cand, float *match_dist)
-{
-    if (!c) return OV2_ERR_INVALID;
-    if (!in || !match_cand || !match_dist || in->n_kp < 0 || in->n_cand < 0 || in->cell <= 0 || in->img_w <= 0 || in->img_h <= 0)
-        return ov2_set_err(c, OV2_ERR_INVALID, "bad ov2_match_input");
-    const int nkp = in->n_kp, nc = in->n_cand;
-    for (int k = 0; k < nkp; ++k) { match_cand[k] = -1; match_dist[k] = 0.f; }
-    if (nkp == 0 || nc == 0) return OV2_OK;                                  // src/mapper.cpp:580-583
-    const int nbw = (int)ceilf((float)in->img_w / (float)in->cell), nbh = (int)ceilf((float)in->img_h / (float)in->cell);
-    const int ncells = nbw * nbh;
-    const size_t n_kpd = (size_t)in->kp_desc_ptr[nkp], n_kpk = (size_t)in->kp_kf_ptr[nkp], n_g = (size_t)in->grid_ptr[ncells];
-    const size_t n_cd = (size_t)in->cand_desc_ptr[nc], n_ck = (size_t)in->cand_kf_ptr[nc];
-    // one staging block, every array 16-byte aligned
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off += (bytes + 15) / 16 * 16; return o; };
-    const size_t o_kpx = place(nkp * 8), o_kdp = place((nkp + 1) * 4), o_kd = place(n_kpd * 32), o_kkp = place((nkp + 1) * 4),
-                 o_kk = place(n_kpk * 4), o_kkx = place(n_kpk * 8), o_gp = place((ncells + 1) * 4), o_gk = place(n_g * 4),
-                 o_cw = place((size_t)nc * 24), o_cdp = place((nc + 1) * 4), o_cd = place(n_cd * 32), o_ckp = place((nc + 1) * 4),
-                 o_ck = place(n_ck * 4), o_kf = place((size_t)std::max(in->n_kf, 0) * 56), o_in = off;
-    const size_t o_best = place((size_t)nkp * 8), o_mc = place((size_t)nkp * 4), o_md = place((size_t)nkp * 4);
-    void *hs = nullptr, *ds = nullptr;
-    ov2_status s = ov2_staging(c, off + 64, &hs, &ds);
-    if (s != OV2_OK) return s;
-    char *h = (char *)hs, *d = (char *)ds;
-    memcpy(h + o_kpx, in->kp_px, nkp * 8); memcpy(h + o_kdp, in->kp_desc_ptr, (nkp + 1) * 4); memcpy(h + o_kd, in->kp_descs, n_kpd * 32);
-    memcpy(h + o_kkp, in->kp_kf_ptr, (nkp + 1) * 4); memcpy(h + o_kk, in->kp_kfids, n_kpk * 4); memcpy(h + o_kkx, in->kp_kf_px, n_kpk * 8);
-    memcpy(h + o_gp, in->grid_ptr, (ncells + 1) * 4); memcpy(h + o_gk, in->grid_kp, n_g * 4);
-    memcpy(h + o_cw, in->cand_wpt, (size_t)nc * 24); memcpy(h + o_cdp, in->cand_desc_ptr, (nc + 1) * 4); memcpy(h + o_cd, in->cand_descs, n_cd * 32);
-    memcpy(h + o_ckp, in->cand_kf_ptr, (nc + 1) * 4); memcpy(h + o_ck, in->cand_kfids, n_ck * 4);
-    if (in->n_kf > 0) memcpy(h + o_kf, in->kf_Twc, (size_t)in->n_kf * 56);
-    OV2_HIP(c, hipSetDevice(c->device));
-    OV2_HIP(c, hipMemcpyAsync(d, h, o_in, hipMemcpyHostToDevice, c->stream));
-    OV2_HIP(c, hipMemsetAsync(d + o_best, 0xff, (size_t)nkp * 8, c->stream));
-    match_dev M;
-    for (int i = 0; i < 7; ++i) M.Twc[i] = in->Twc[i];
-    for (int i = 0; i < 4; ++i) M.K[i] = in->K[i];
-    M.cam = ov2_cam_normalised(in->cam);
-    for (int i = 0; i < 4; ++i) M.cam.K[i] = in->K[i];   // one set of intrinsics: the frame's
-    if (M.cam.model < 0 || M.cam.model > 2) return ov2_set_err(c, OV2_ERR_INVALID, "unknown lens model %d", M.cam.model);
-    M.img_w = in->img_w; M.img_h = in->img_h; M.cell = in->cell; M.nb3dkps = in->nb3dkps; M.n_kp = nkp; M.n_cand = nc; M.n_kf = in->n_kf;
-    M.nbw = nbw; M.ncells = ncells;
-    M.kp_px = (const float2 *)(d + o_kpx); M.kp_desc_ptr = (const int *)(d + o_kdp); M.kp_descs = (const unsigned char *)(d + o_kd);
-    M.kp_kf_ptr = (const int *)(d + o_kkp); M.kp_kfids = (const int *)(d + o_kk); M.kp_kf_px = (const float2 *)(d + o_kkx);
-    M.grid_ptr = (const int *)(d + o_gp); M.grid_kp = (const int *)(d + o_gk);
-    M.cand_wpt = (const double *)(d + o_cw); M.cand_desc_ptr = (const int *)(d + o_cdp); M.cand_descs = (const unsigned char *)(d + o_cd);
-    M.cand_kf_ptr = (const int *)(d + o_ckp); M.cand_kfids = (const int *)(d + o_ck); M.kf_Twc = (const double *)(d + o_kf);
-    // thresholds exactly as the reference forms them (:586-603, :651)
-    const float vfov = (float)(0.5 * in->img_h / in->K[1]), hfov = (float)(0.5 * in->img_w / in->K[0]);
-    const float maxradfov = hfov > vfov ? atanf(hfov) : atanf(vfov);
-    const float view_th = cosf(maxradfov);
-    float dmaxpxdist = fmaxprojerr;
-    if (in->nb3dkps < 30) dmaxpxdist *= 2.f;
-    const float mindist = (float)((double)(32.f * fdistratio) * 8.);
-    OV2_LAUNCH(c, K_MATCH, match_cand_kernel, dim3(nc), dim3(64), 0, c->stream, M, dmaxpxdist, mindist, view_th,
-               (unsigned long long *)(d + o_best));
-    OV2_LAUNCH(c, K_MATCH, match_out_kernel, dim3((nkp + 255) / 256), dim3(256), 0, c->stream, nkp, (const unsigned long long *)(d + o_best),
-               (int *)(d + o_mc), (float *)(d + o_md));
-    OV2_HIP(c, hipMemcpyAsync(h + o_mc, d + o_mc, (o_md - o_mc) + (size_t)nkp * 4, hipMemcpyDeviceToHost, c->stream));
-    OV2_HIP(c, hipStreamSynchronize(c->stream));
-    memcpy(match_cand, h + o_mc, (size_t)nkp * 4);
-    memcpy(match_dist, h + o_md, (size_t)nkp * 4);
-    return OV2_OK;
-}
-
-// ---- Mapper::matchToMap for B frames (src/mapper.cpp:576-774), one local map each ------------------------------------
+// ---- Mapper::matchToMap (src/mapper.cpp:576-774) for B frames, one local map each, and LoopCloser::matchToMap
+// ---- (src/loop_closer.cpp:586-763) for B candidate pairs: one path, `loop` picks the rules ------------------------------
 
 namespace {
-
-enum { MATCH_WAVES = 4 };   // candidates per workgroup of match_batch_cand_kernel
-
-struct match_batch_dev {   // device twin of ov2_match_batch_input
-    ov2_cam_model cam;
-    int B, n_kp, n_cand, img_w, img_h, cell, nbw, ncells;
-    const double *Twc; const int *nb3dkps, *kp_off, *cand_off, *kf_off;
-    const float2 *kp_px; const int *kp_desc_ptr; const unsigned char *kp_descs; const int *kp_kf_ptr, *kp_kfids; const float2 *kp_kf_px;
-    const int *grid_ptr, *grid_kp;
-    const double *cand_wpt; const int *cand_desc_ptr; const unsigned char *cand_descs; const int *cand_kf_ptr, *cand_kfids;
-    const double *kf_Twc;
-};
-
-// match_cand_kernel for B frames: one wave per candidate, MATCH_WAVES candidates per workgroup (the waves share nothing, so
-// the result does not depend on it).  The frame of a candidate is found in the B + 1 offsets; its pose, its pixel gate
-// (doubled under 30 3-D keypoints, :599-602), its grid, its keypoint block and its keyframe-pose block follow from it.  The
-// winner key holds the candidate's index within its frame.
-__global__ __launch_bounds__(64 * MATCH_WAVES) void match_batch_cand_kernel(match_batch_dev M, float fmaxprojerr, float mindist, float view_th,
-                                                                           unsigned long long *__restrict__ kp_best)
-{
-    const int c = blockIdx.x * MATCH_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (c >= M.n_cand) return;
-    int lo = 0, hi = M.B;   // the frame b with cand_off[b] <= c < cand_off[b + 1] (empty frames are stepped over)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (M.cand_off[mid] <= c) lo = mid; else hi = mid;
-    }
-    const int b = lo, c0 = M.cand_off[b], k0 = M.kp_off[b], nkp = M.kp_off[b + 1] - k0;
-    if (nkp <= 0) return;
-    const int cd0 = M.cand_desc_ptr[c], cd1 = M.cand_desc_ptr[c + 1];
-    if (cd1 == cd0) return;
-    const double *wpt = M.cand_wpt + 3 * (size_t)c;
-    double campt[3];
-    world_to_cam(M.Twc + 7 * (size_t)b, wpt, campt);
-    if (campt[2] < 0.1) return;
-    const float view_angle = (float)(campt[2] / sqrt(campt[0] * campt[0] + campt[1] * campt[1] + campt[2] * campt[2]));
-    if (fabsf(view_angle) < view_th) return;
-    float px, py;
-    ov2_cam_project_dist(M.cam, campt, px, py);
-    if (!(px >= 0 && py >= 0 && px < (float)M.img_w && py < (float)M.img_h)) return;
-    const float dmaxpxdist = M.nb3dkps[b] < 30 ? fmaxprojerr * 2.f : fmaxprojerr;
-    const int kf0 = M.kf_off[b], n_kf = M.kf_off[b + 1] - kf0;
-    const double *kf_Twc = M.kf_Twc + 7 * (size_t)kf0;
-    float bestdist;
-    const int bestid = match_walk_cells(px, py, M.cell, M.nbw, M.ncells, M.grid_ptr + (size_t)b * M.ncells, M.grid_kp, lane, mindist, bestdist,
-                                        [&](int kl) {
-        if ((unsigned)kl >= (unsigned)nkp) return -1.f;   // (the host form refuses such a grid; the _dev form cannot look)
-        return match_kp_dist(M, c, k0 + kl, cd0, cd1, wpt, px, py, dmaxpxdist, kf_Twc, n_kf);
-    });
-    if (bestid < 0) return;
-    if (lane == 0)   // Hamming distances are small integers: exact in the key
-        atomicMin(&kp_best[k0 + bestid],
-                  ((unsigned long long)(unsigned)(int)bestdist << 32) | (unsigned long long)(0xffffffffu - (unsigned)(c - c0)));
-}
 
 // thresholds exactly as the reference forms them (src/mapper.cpp:586-598, :651): the quotients are Mapper's
 void match_thresholds(const double *K, int img_w, int img_h, float fdistratio, float &mindist, float &view_th)
@@ -415,134 +342,197 @@ void match_thresholds(const double *K, int img_w, int img_h, float fdistratio, f
     mindist = (float)((double)(32.f * fdistratio) * 8.);
 }
 
-}  // namespace
-
-extern "C" ov2_status ov2_match_to_map_batch_dev(ov2_ctx *c, const ov2_match_batch_input *in, float fmaxprojerr, float fdistratio,
-                                                 uint64_t *d_work, int32_t *d_match_cand, float *d_match_dist)
+// thresholds exactly as the reference forms them (src/loop_closer.cpp:595-607, :656): the products and the one-sided atan
+// are the reference's
+void loop_match_thresholds(const double *K, int img_w, int img_h, float fdistratio, float &mindist, float &view_th)
 {
-    if (!c) return OV2_ERR_INVALID;
-    if (!in || in->B < 0 || in->n_kp < 0 || in->n_cand < 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch_dev: negative count");
-    if (in->B == 0 || in->n_kp == 0) return OV2_OK;
-    if (in->cell <= 0 || in->img_w <= 0 || in->img_h <= 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch_dev: bad image / cell size");
-    if (!d_work || !d_match_cand || !d_match_dist || !in->kp_off || !in->cand_off || !in->kf_off)
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch_dev: null argument");
-    if (in->n_cand && (!in->Twc || !in->nb3dkps || !in->kp_px || !in->kp_desc_ptr || !in->kp_kf_ptr || !in->grid_ptr || !in->cand_wpt ||
-                       !in->cand_desc_ptr || !in->cand_kf_ptr))
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch_dev: null array");
-    if (((uintptr_t)in->kp_descs | (uintptr_t)in->cand_descs) & 7)   // descriptors are read 8 bytes at a time
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch_dev: descriptor arrays must be 8-byte aligned");
-    match_batch_dev M;
+    const float vfov = (float)(0.5 * (double)img_h * K[1]), hfov = (float)(0.5 * (double)img_w * K[0]);
+    float maxradfov = 0.f;
+    if (hfov > vfov) maxradfov = atanf(hfov);
+    else maxradfov = atanf(hfov);
+    view_th = cosf(maxradfov);
+    mindist = (float)((double)(32.f * fdistratio) * 8.);
+}
+
+// the arrays of a call from either public input; a null input reads as a negative count, which every path refuses first
+template <class In>
+match_dev match_arrays(const In *in)
+{
+    match_dev M{};
+    M.B = -1;
+    if (!in) return M;
     M.cam = ov2_cam_normalised(in->cam);
     for (int i = 0; i < 4; ++i) M.cam.K[i] = in->K[i];   // one set of intrinsics: the call's
-    if (M.cam.model < 0 || M.cam.model > 2) return ov2_set_err(c, OV2_ERR_INVALID, "unknown lens model %d", M.cam.model);
     M.B = in->B; M.n_kp = in->n_kp; M.n_cand = in->n_cand; M.img_w = in->img_w; M.img_h = in->img_h; M.cell = in->cell;
-    M.nbw = (int)ceilf((float)in->img_w / (float)in->cell);
-    M.ncells = M.nbw * (int)ceilf((float)in->img_h / (float)in->cell);
-    M.Twc = in->Twc; M.nb3dkps = in->nb3dkps; M.kp_off = in->kp_off; M.cand_off = in->cand_off; M.kf_off = in->kf_off;
+    M.Twc = in->Twc; M.kp_off = in->kp_off; M.cand_off = in->cand_off;
     M.kp_px = (const float2 *)in->kp_px; M.kp_desc_ptr = in->kp_desc_ptr; M.kp_descs = in->kp_descs;
-    M.kp_kf_ptr = in->kp_kf_ptr; M.kp_kfids = in->kp_kfids; M.kp_kf_px = (const float2 *)in->kp_kf_px;
-    M.grid_ptr = in->grid_ptr; M.grid_kp = in->grid_kp;
+    M.kp_kf_ptr = in->kp_kf_ptr; M.kp_kfids = in->kp_kfids; M.grid_ptr = in->grid_ptr; M.grid_kp = in->grid_kp;
     M.cand_wpt = in->cand_wpt; M.cand_desc_ptr = in->cand_desc_ptr; M.cand_descs = in->cand_descs; M.cand_kf_ptr = in->cand_kf_ptr;
-    M.cand_kfids = in->cand_kfids; M.kf_Twc = in->kf_Twc;
+    M.cand_kfids = in->cand_kfids;
+    if constexpr (std::is_same_v<In, ov2_loop_match_input>) M.kp_matched = in->kp_matched;
+    else { M.nb3dkps = in->nb3dkps; M.kf_off = in->kf_off; M.kp_kf_px = (const float2 *)in->kp_kf_px; M.kf_Twc = in->kf_Twc; }
+    return M;
+}
+
+// The _dev entry points: every array of M is a device pointer.  Checks, the 0xff fill of the work array, the two launches;
+// nothing is synchronised.  name: the public entry point, for the messages.
+ov2_status match_enqueue(ov2_ctx *c, const char *name, bool loop, match_dev M, float fmaxprojerr, float fdistratio, uint64_t *d_work,
+                         int32_t *d_match_cand, float *d_match_dist)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (M.B < 0 || M.n_kp < 0 || M.n_cand < 0) return ov2_set_err(c, OV2_ERR_INVALID, "%s: negative count", name);
+    if (M.B == 0 || M.n_kp == 0) return OV2_OK;
+    if (M.cell <= 0 || M.img_w <= 0 || M.img_h <= 0) return ov2_set_err(c, OV2_ERR_INVALID, "%s: bad image / cell size", name);
+    if (!d_work || !d_match_cand || !d_match_dist || !M.kp_off || !M.cand_off || (!loop && !M.kf_off))
+        return ov2_set_err(c, OV2_ERR_INVALID, "%s: null argument", name);
+    if (M.n_cand && (!M.Twc || !M.kp_px || !M.kp_desc_ptr || !M.kp_kf_ptr || !M.grid_ptr || !M.cand_wpt || !M.cand_desc_ptr ||
+                     !M.cand_kf_ptr || (loop ? !M.kp_matched : !M.nb3dkps)))
+        return ov2_set_err(c, OV2_ERR_INVALID, "%s: null array", name);
+    if (((uintptr_t)M.kp_descs | (uintptr_t)M.cand_descs) & 7)   // descriptors are read 8 bytes at a time
+        return ov2_set_err(c, OV2_ERR_INVALID, "%s: descriptor arrays must be 8-byte aligned", name);
+    if (M.cam.model < 0 || M.cam.model > 2) return ov2_set_err(c, OV2_ERR_INVALID, "unknown lens model %d", M.cam.model);
+    M.nbw = (int)ceilf((float)M.img_w / (float)M.cell);
+    M.ncells = M.nbw * (int)ceilf((float)M.img_h / (float)M.cell);
     float mindist, view_th;
-    match_thresholds(in->K, in->img_w, in->img_h, fdistratio, mindist, view_th);
+    (loop ? loop_match_thresholds : match_thresholds)(M.cam.K, M.img_w, M.img_h, fdistratio, mindist, view_th);
+    const int tag = loop ? K_LOOP_MATCH : K_MATCH;
     OV2_HIP(c, hipSetDevice(c->device));
-    OV2_HIP(c, hipMemsetAsync(d_work, 0xff, (size_t)in->n_kp * 8, c->stream));
-    if (in->n_cand > 0)
-        OV2_LAUNCH(c, K_MATCH, match_batch_cand_kernel, dim3((in->n_cand + MATCH_WAVES - 1) / MATCH_WAVES), dim3(64 * MATCH_WAVES), 0,
-                   c->stream, M, fmaxprojerr, mindist, view_th, (unsigned long long *)d_work);
-    OV2_LAUNCH(c, K_MATCH, match_out_kernel, dim3((in->n_kp + 255) / 256), dim3(256), 0, c->stream, in->n_kp,
-               (const unsigned long long *)d_work, d_match_cand, d_match_dist);
+    OV2_HIP(c, hipMemsetAsync(d_work, 0xff, (size_t)M.n_kp * 8, c->stream));
+    if (M.n_cand > 0)
+        OV2_LAUNCH(c, tag, loop ? match_cand_kernel<true> : match_cand_kernel<false>, dim3((M.n_cand + MATCH_WAVES - 1) / MATCH_WAVES),
+                   dim3(64 * MATCH_WAVES), 0, c->stream, M, fmaxprojerr, mindist, view_th, (unsigned long long *)d_work);
+    OV2_LAUNCH(c, tag, match_out_kernel, dim3((M.n_kp + 255) / 256), dim3(256), 0, c->stream, M.n_kp, (const unsigned long long *)d_work,
+               d_match_cand, d_match_dist);
     OV2_HIP(c, hipGetLastError());
     return OV2_OK;
 }
 
-extern "C" ov2_status ov2_match_to_map_batch(ov2_ctx *c, const ov2_match_batch_input *in, float fmaxprojerr, float fdistratio,
-                                             int32_t *match_cand, float *match_dist)
+// The host-pointer entry points: every array of M is a host pointer.  Checks of everything the kernel indexes with, one staging
+// block [inputs || work | match_cand | match_dist], one upload, match_enqueue, one download and one synchronisation.
+ov2_status match_host(ov2_ctx *c, const char *name, bool loop, const match_dev &M, float fmaxprojerr, float fdistratio,
+                      int32_t *match_cand, float *match_dist)
 {
     if (!c) return OV2_ERR_INVALID;
-    if (!in || in->B < 0 || in->n_kp < 0 || in->n_cand < 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch: negative count");
-    const int B = in->B;
+    if (M.B < 0 || M.n_kp < 0 || M.n_cand < 0) return ov2_set_err(c, OV2_ERR_INVALID, "%s: negative count", name);
+    const int B = M.B, nkp = M.n_kp, nc = M.n_cand;
+    const char *unit = loop ? "pair" : "frame";
     if (B == 0) return OV2_OK;
-    if (!in->kp_off || !in->cand_off || !in->kf_off) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch: null offsets");
-    if (in->kp_off[0] != 0 || in->cand_off[0] != 0 || in->kf_off[0] != 0 || in->kp_off[B] != in->n_kp || in->cand_off[B] != in->n_cand)
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch: offsets do not start at 0 or do not span n_kp / n_cand");
+    if (!M.kp_off || !M.cand_off || (!loop && !M.kf_off)) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null offsets", name);
+    if (M.kp_off[0] != 0 || M.cand_off[0] != 0 || (!loop && M.kf_off[0] != 0) || M.kp_off[B] != nkp || M.cand_off[B] != nc)
+        return ov2_set_err(c, OV2_ERR_INVALID, "%s: offsets do not start at 0 or do not span n_kp / n_cand", name);
     for (int b = 0; b < B; ++b)
-        if (in->kp_off[b + 1] < in->kp_off[b] || in->cand_off[b + 1] < in->cand_off[b] || in->kf_off[b + 1] < in->kf_off[b])
-            return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch: frame %d has a negative count", b);
-    const int nkp = in->n_kp, nc = in->n_cand;
-    if (nkp && (!match_cand || !match_dist)) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch: null output");
+        if (M.kp_off[b + 1] < M.kp_off[b] || M.cand_off[b + 1] < M.cand_off[b] || (!loop && M.kf_off[b + 1] < M.kf_off[b]))
+            return ov2_set_err(c, OV2_ERR_INVALID, "%s: %s %d has a negative count", name, unit, b);
+    if (nkp && (!match_cand || !match_dist)) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null output", name);
     for (int k = 0; k < nkp; ++k) { match_cand[k] = -1; match_dist[k] = 0.f; }
-    if (nkp == 0 || nc == 0) return OV2_OK;                                  // src/mapper.cpp:580-583
-    if (in->cell <= 0 || in->img_w <= 0 || in->img_h <= 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch: bad image / cell size");
-    if (!in->Twc || !in->nb3dkps || !in->kp_px || !in->kp_desc_ptr || !in->kp_kf_ptr || !in->grid_ptr || !in->cand_wpt ||
-        !in->cand_desc_ptr || !in->cand_kf_ptr)
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch: null array");
-    const int cam_model = ov2_cam_normalised(in->cam).model;
-    if (cam_model < 0 || cam_model > 2) return ov2_set_err(c, OV2_ERR_INVALID, "unknown lens model %d", cam_model);
-    const int nbw = (int)ceilf((float)in->img_w / (float)in->cell), nbh = (int)ceilf((float)in->img_h / (float)in->cell);
+    if (nkp == 0 || nc == 0) return OV2_OK;                                  // src/mapper.cpp:580-583, src/loop_closer.cpp:591-593
+    if (M.cell <= 0 || M.img_w <= 0 || M.img_h <= 0) return ov2_set_err(c, OV2_ERR_INVALID, "%s: bad image / cell size", name);
+    if (!M.Twc || !M.kp_px || !M.kp_desc_ptr || !M.kp_kf_ptr || !M.grid_ptr || !M.cand_wpt || !M.cand_desc_ptr || !M.cand_kf_ptr ||
+        (loop ? !M.kp_matched : !M.nb3dkps))
+        return ov2_set_err(c, OV2_ERR_INVALID, "%s: null array", name);
+    if (!loop && (M.cam.model < 0 || M.cam.model > 2))   // (the loop closer's form leaves this refusal to match_enqueue)
+        return ov2_set_err(c, OV2_ERR_INVALID, "unknown lens model %d", M.cam.model);
+    const int nbw = (int)ceilf((float)M.img_w / (float)M.cell), nbh = (int)ceilf((float)M.img_h / (float)M.cell);
     const size_t ncells = (size_t)nbw * nbh, ng_ptr = (size_t)B * ncells + 1;
     // the kernel indexes with these: every prefix array starts at 0 and never decreases, every grid entry lies in its frame
-    auto csr_ok = [](const int32_t *p, size_t n) {
+    auto csr_ok = [](const int *p, size_t n) {
         if (p[0] != 0) return false;
         for (size_t i = 0; i < n; ++i) if (p[i + 1] < p[i]) return false;
         return true;
     };
-    if (!csr_ok(in->kp_desc_ptr, nkp) || !csr_ok(in->kp_kf_ptr, nkp) || !csr_ok(in->cand_desc_ptr, nc) || !csr_ok(in->cand_kf_ptr, nc) ||
-        !csr_ok(in->grid_ptr, ng_ptr - 1))
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch: a prefix array decreases or does not start at 0");
-    const size_t n_kpd = (size_t)in->kp_desc_ptr[nkp], n_kpk = (size_t)in->kp_kf_ptr[nkp], n_g = (size_t)in->grid_ptr[ng_ptr - 1];
-    const size_t n_cd = (size_t)in->cand_desc_ptr[nc], n_ck = (size_t)in->cand_kf_ptr[nc], n_kf = (size_t)in->kf_off[B];
-    if ((n_kpd && !in->kp_descs) || (n_kpk && (!in->kp_kfids || !in->kp_kf_px)) || (n_g && !in->grid_kp) || (n_cd && !in->cand_descs) ||
-        (n_ck && !in->cand_kfids) || (n_kf && !in->kf_Twc))
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch: null array");
+    if (!csr_ok(M.kp_desc_ptr, nkp) || !csr_ok(M.kp_kf_ptr, nkp) || !csr_ok(M.cand_desc_ptr, nc) || !csr_ok(M.cand_kf_ptr, nc) ||
+        !csr_ok(M.grid_ptr, ng_ptr - 1))
+        return ov2_set_err(c, OV2_ERR_INVALID, "%s: a prefix array decreases or does not start at 0", name);
+    const size_t n_kpd = (size_t)M.kp_desc_ptr[nkp], n_kpk = (size_t)M.kp_kf_ptr[nkp], n_g = (size_t)M.grid_ptr[ng_ptr - 1];
+    const size_t n_cd = (size_t)M.cand_desc_ptr[nc], n_ck = (size_t)M.cand_kf_ptr[nc], n_kf = loop ? 0 : (size_t)M.kf_off[B];
+    if ((n_kpd && !M.kp_descs) || (n_kpk && (!M.kp_kfids || (!loop && !M.kp_kf_px))) || (n_g && !M.grid_kp) || (n_cd && !M.cand_descs) ||
+        (n_ck && !M.cand_kfids) || (n_kf && !M.kf_Twc))
+        return ov2_set_err(c, OV2_ERR_INVALID, "%s: null array", name);
     for (int b = 0; b < B; ++b) {
-        const int nb = in->kp_off[b + 1] - in->kp_off[b];
-        for (int g = in->grid_ptr[(size_t)b * ncells]; g < in->grid_ptr[(size_t)(b + 1) * ncells]; ++g)
-            if (in->grid_kp[g] < 0 || in->grid_kp[g] >= nb)
-                return ov2_set_err(c, OV2_ERR_INVALID, "ov2_match_to_map_batch: grid entry %d of frame %d outside its %d keypoints", in->grid_kp[g], b, nb);
+        const int nb = M.kp_off[b + 1] - M.kp_off[b];
+        for (int g = M.grid_ptr[(size_t)b * ncells]; g < M.grid_ptr[(size_t)(b + 1) * ncells]; ++g)
+            if (M.grid_kp[g] < 0 || M.grid_kp[g] >= nb)
+                return ov2_set_err(c, OV2_ERR_INVALID, "%s: grid entry %d of %s %d outside its %d keypoints", name, M.grid_kp[g], unit, b, nb);
     }
-    // one staging block, every array 16-byte aligned: [inputs || work | match_cand | match_dist]
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off += (bytes + 15) / 16 * 16; return o; };
-    const size_t o_T = place((size_t)B * 56), o_n3 = place((size_t)B * 4), o_ko = place((B + 1) * 4), o_co = place((B + 1) * 4),
-                 o_fo = place((B + 1) * 4), o_kpx = place((size_t)nkp * 8), o_kdp = place(((size_t)nkp + 1) * 4), o_kd = place(n_kpd * 32),
-                 o_kkp = place(((size_t)nkp + 1) * 4), o_kk = place(n_kpk * 4), o_kkx = place(n_kpk * 8), o_gp = place(ng_ptr * 4),
-                 o_gk = place(n_g * 4), o_cw = place((size_t)nc * 24), o_cdp = place(((size_t)nc + 1) * 4), o_cd = place(n_cd * 32),
-                 o_ckp = place(((size_t)nc + 1) * 4), o_ck = place(n_ck * 4), o_kf = place(n_kf * 56), o_in = off;
-    const size_t o_best = place((size_t)nkp * 8), o_mc = place((size_t)nkp * 4), o_md = place((size_t)nkp * 4);
+    match_dev D = M;
+    auto arrays = [&](auto &&f) {   // every array the call reads, with its size in bytes
+        f(D.Twc, (size_t)B * 56); f(D.kp_off, ((size_t)B + 1) * 4); f(D.cand_off, ((size_t)B + 1) * 4);
+        f(D.kp_px, (size_t)nkp * 8); f(D.kp_desc_ptr, ((size_t)nkp + 1) * 4); f(D.kp_descs, n_kpd * 32);
+        f(D.kp_kf_ptr, ((size_t)nkp + 1) * 4); f(D.kp_kfids, n_kpk * 4); f(D.grid_ptr, ng_ptr * 4); f(D.grid_kp, n_g * 4);
+        f(D.cand_wpt, (size_t)nc * 24); f(D.cand_desc_ptr, ((size_t)nc + 1) * 4); f(D.cand_descs, n_cd * 32);
+        f(D.cand_kf_ptr, ((size_t)nc + 1) * 4); f(D.cand_kfids, n_ck * 4);
+        if (loop) f(D.kp_matched, (size_t)nkp);
+        else { f(D.nb3dkps, (size_t)B * 4); f(D.kf_off, ((size_t)B + 1) * 4); f(D.kp_kf_px, n_kpk * 8); f(D.kf_Twc, n_kf * 56); }
+    };
+    // one staging block, every array 16-byte aligned
+    auto pad = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+    size_t o_in = 0;
+    arrays([&](auto *&, size_t bytes) { o_in += pad(bytes); });
+    const size_t o_best = o_in, o_mc = o_best + pad((size_t)nkp * 8), o_md = o_mc + pad((size_t)nkp * 4), total = o_md + pad((size_t)nkp * 4);
     void *hs = nullptr, *ds = nullptr;
-    ov2_status s = ov2_staging(c, off + 64, &hs, &ds);
+    ov2_status s = ov2_staging(c, total + 64, &hs, &ds);
     if (s != OV2_OK) return s;
     char *h = (char *)hs, *d = (char *)ds;
-    memcpy(h + o_T, in->Twc, (size_t)B * 56); memcpy(h + o_n3, in->nb3dkps, (size_t)B * 4); memcpy(h + o_ko, in->kp_off, (B + 1) * 4);
-    memcpy(h + o_co, in->cand_off, (B + 1) * 4); memcpy(h + o_fo, in->kf_off, (B + 1) * 4);
-    memcpy(h + o_kpx, in->kp_px, (size_t)nkp * 8);
-    memcpy(h + o_kdp, in->kp_desc_ptr, ((size_t)nkp + 1) * 4); if (n_kpd) memcpy(h + o_kd, in->kp_descs, n_kpd * 32);
-    memcpy(h + o_kkp, in->kp_kf_ptr, ((size_t)nkp + 1) * 4);
-    if (n_kpk) { memcpy(h + o_kk, in->kp_kfids, n_kpk * 4); memcpy(h + o_kkx, in->kp_kf_px, n_kpk * 8); }
-    memcpy(h + o_gp, in->grid_ptr, ng_ptr * 4); if (n_g) memcpy(h + o_gk, in->grid_kp, n_g * 4);
-    memcpy(h + o_cw, in->cand_wpt, (size_t)nc * 24); memcpy(h + o_cdp, in->cand_desc_ptr, ((size_t)nc + 1) * 4);
-    if (n_cd) memcpy(h + o_cd, in->cand_descs, n_cd * 32);
-    memcpy(h + o_ckp, in->cand_kf_ptr, ((size_t)nc + 1) * 4); if (n_ck) memcpy(h + o_ck, in->cand_kfids, n_ck * 4);
-    if (n_kf) memcpy(h + o_kf, in->kf_Twc, n_kf * 56);
+    size_t off = 0;
+    arrays([&](auto *&p, size_t bytes) {   // the array into the block, p to its device copy
+        if (bytes) memcpy(h + off, p, bytes);
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(d + off);
+        off += pad(bytes);
+    });
     OV2_HIP(c, hipSetDevice(c->device));
     OV2_HIP(c, hipMemcpyAsync(d, h, o_in, hipMemcpyHostToDevice, c->stream));
-    ov2_match_batch_input D = *in;
-    D.Twc = (const double *)(d + o_T); D.nb3dkps = (const int32_t *)(d + o_n3); D.kp_off = (const int32_t *)(d + o_ko);
-    D.cand_off = (const int32_t *)(d + o_co); D.kf_off = (const int32_t *)(d + o_fo);
-    D.kp_px = (const float *)(d + o_kpx); D.kp_desc_ptr = (const int32_t *)(d + o_kdp); D.kp_descs = (const uint8_t *)(d + o_kd);
-    D.kp_kf_ptr = (const int32_t *)(d + o_kkp); D.kp_kfids = (const int32_t *)(d + o_kk); D.kp_kf_px = (const float *)(d + o_kkx);
-    D.grid_ptr = (const int32_t *)(d + o_gp); D.grid_kp = (const int32_t *)(d + o_gk); D.cand_wpt = (const double *)(d + o_cw);
-    D.cand_desc_ptr = (const int32_t *)(d + o_cdp); D.cand_descs = (const uint8_t *)(d + o_cd); D.cand_kf_ptr = (const int32_t *)(d + o_ckp);
-    D.cand_kfids = (const int32_t *)(d + o_ck); D.kf_Twc = (const double *)(d + o_kf);
-    s = ov2_match_to_map_batch_dev(c, &D, fmaxprojerr, fdistratio, (uint64_t *)(d + o_best), (int32_t *)(d + o_mc), (float *)(d + o_md));
+    s = match_enqueue(c, name, loop, D, fmaxprojerr, fdistratio, (uint64_t *)(d + o_best), (int32_t *)(d + o_mc), (float *)(d + o_md));
     if (s != OV2_OK) return s;
     OV2_HIP(c, hipMemcpyAsync(h + o_mc, d + o_mc, (o_md - o_mc) + (size_t)nkp * 4, hipMemcpyDeviceToHost, c->stream));
     OV2_HIP(c, hipStreamSynchronize(c->stream));
     memcpy(match_cand, h + o_mc, (size_t)nkp * 4);
     memcpy(match_dist, h + o_md, (size_t)nkp * 4);
     return OV2_OK;
+}
+
+}  // namespace
+
+// the B = 1 case of ov2_match_to_map_batch
+extern "C" ov2_status ov2_match_to_map(ov2_ctx *c, const ov2_match_input *in, float fmaxprojerr, float fdistratio,
+                                       int32_t *match_cand, float *match_dist)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (!in || !match_cand || !match_dist || in->n_kp < 0 || in->n_cand < 0 || in->cell <= 0 || in->img_w <= 0 || in->img_h <= 0)
+        return ov2_set_err(c, OV2_ERR_INVALID, "bad ov2_match_input");
+    const int32_t kp_off[2] = {0, in->n_kp}, cand_off[2] = {0, in->n_cand}, kf_off[2] = {0, std::max(in->n_kf, 0)};
+    ov2_match_batch_input b;
+    b.B = 1; b.n_kp = in->n_kp; b.n_cand = in->n_cand; b.img_w = in->img_w; b.img_h = in->img_h; b.cell = in->cell; b.cam = in->cam;
+    for (int i = 0; i < 4; ++i) b.K[i] = in->K[i];
+    b.Twc = in->Twc; b.nb3dkps = &in->nb3dkps; b.kp_off = kp_off; b.cand_off = cand_off; b.kf_off = kf_off;
+    b.kp_px = in->kp_px; b.kp_desc_ptr = in->kp_desc_ptr; b.kp_descs = in->kp_descs; b.kp_kf_ptr = in->kp_kf_ptr; b.kp_kfids = in->kp_kfids;
+    b.kp_kf_px = in->kp_kf_px; b.grid_ptr = in->grid_ptr; b.grid_kp = in->grid_kp; b.cand_wpt = in->cand_wpt;
+    b.cand_desc_ptr = in->cand_desc_ptr; b.cand_descs = in->cand_descs; b.cand_kf_ptr = in->cand_kf_ptr; b.cand_kfids = in->cand_kfids;
+    b.kf_Twc = in->kf_Twc;
+    return match_host(c, "ov2_match_to_map", false, match_arrays(&b), fmaxprojerr, fdistratio, match_cand, match_dist);
+}
+
+extern "C" ov2_status ov2_match_to_map_batch_dev(ov2_ctx *c, const ov2_match_batch_input *in, float fmaxprojerr, float fdistratio,
+                                                 uint64_t *d_work, int32_t *d_match_cand, float *d_match_dist)
+{
+    return match_enqueue(c, "ov2_match_to_map_batch_dev", false, match_arrays(in), fmaxprojerr, fdistratio, d_work, d_match_cand, d_match_dist);
+}
+
+extern "C" ov2_status ov2_match_to_map_batch(ov2_ctx *c, const ov2_match_batch_input *in, float fmaxprojerr, float fdistratio,
+                                             int32_t *match_cand, float *match_dist)
+{
+    return match_host(c, "ov2_match_to_map_batch", false, match_arrays(in), fmaxprojerr, fdistratio, match_cand, match_dist);
+}
+
+extern "C" ov2_status ov2_loop_match_to_map_batch_dev(ov2_ctx *c, const ov2_loop_match_input *in, float fmaxprojerr, float fdistratio,
+                                                      uint64_t *d_work, int32_t *d_match_cand, float *d_match_dist)
+{
+    return match_enqueue(c, "ov2_loop_match_to_map_batch_dev", true, match_arrays(in), fmaxprojerr, fdistratio, d_work, d_match_cand, d_match_dist);
+}
+
+extern "C" ov2_status ov2_loop_match_to_map_batch(ov2_ctx *c, const ov2_loop_match_input *in, float fmaxprojerr, float fdistratio,
+                                                  int32_t *match_cand, float *match_dist)
+{
+    return match_host(c, "ov2_loop_match_to_map_batch", true, match_arrays(in), fmaxprojerr, fdistratio, match_cand, match_dist);
 }
 
 // ---- the matcher's output as ordered pair lists (Mapper::mergeMatches, src/mapper.cpp:556-574) --------------------------
@@ -610,201 +600,5 @@ extern "C" ov2_status ov2_match_pairs_dev(ov2_ctx *c, int B, int n_kp, const int
     OV2_LAUNCH(c, K_MATCH, match_pairs_kernel, dim3(B), dim3(PAIRS_THREADS), 0, c->stream, d_kp_off, d_cand_off, d_kp_lmid, d_cand_lmid,
                d_match_cand, d_prev_lmid, d_new_lmid, d_n_pairs);
     OV2_HIP(c, hipGetLastError());
-    return OV2_OK;
-}
-
-// ---- LoopCloser::matchToMap for B candidate pairs (src/loop_closer.cpp:586-763) -------------------------------------
-
-namespace {
-
-enum { K_LOOP_MATCH = OV2_K_MAP + 15, LOOP_WAVES = 4 };
-
-struct loop_match_dev {   // device twin of ov2_loop_match_input
-    ov2_cam_model cam;
-    int B, n_kp, n_cand, img_w, img_h, cell, nbw, ncells;
-    const double *Twc; const int *kp_off, *cand_off;
-    const float2 *kp_px; const unsigned char *kp_matched; const int *kp_desc_ptr; const unsigned char *kp_descs;
-    const int *kp_kf_ptr, *kp_kfids, *grid_ptr, *grid_kp;
-    const double *cand_wpt; const int *cand_desc_ptr; const unsigned char *cand_descs; const int *cand_kf_ptr, *cand_kfids;
-};
-
-// match_cand_kernel for the loop closer: one wave per candidate, LOOP_WAVES candidates per workgroup (the waves share
-// nothing, so the result does not depend on it).  The pair of a candidate is found in the B + 1 offsets; its pose, its grid
-// and its keypoint block follow from it.  Differences from Mapper's matcher: the pose is the pair's, the matched mask comes
-// first, no mean-reprojection gate.  The winner key holds the candidate's index within its pair.
-__global__ __launch_bounds__(64 * LOOP_WAVES) void loop_match_cand_kernel(loop_match_dev M, float dmaxpxdist, float mindist, float view_th,
-                                                                         unsigned long long *__restrict__ kp_best)
-{
-    const int c = blockIdx.x * LOOP_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (c >= M.n_cand) return;
-    int lo = 0, hi = M.B;   // the pair b with cand_off[b] <= c < cand_off[b + 1] (empty pairs are stepped over)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (M.cand_off[mid] <= c) lo = mid; else hi = mid;
-    }
-    const int b = lo, c0 = M.cand_off[b], k0 = M.kp_off[b], nkp = M.kp_off[b + 1] - k0;
-    if (nkp <= 0) return;
-    const int cd0 = M.cand_desc_ptr[c], cd1 = M.cand_desc_ptr[c + 1];
-    if (cd1 == cd0) return;
-    const double *wpt = M.cand_wpt + 3 * (size_t)c;
-    double campt[3];
-    world_to_cam(M.Twc + 7 * (size_t)b, wpt, campt);
-    if (campt[2] < 0.1) return;
-    const float view_angle = (float)(campt[2] / sqrt(campt[0] * campt[0] + campt[1] * campt[1] + campt[2] * campt[2]));
-    if (fabsf(view_angle) < view_th) return;
-    float px, py;
-    ov2_cam_project_dist(M.cam, campt, px, py);
-    if (!(px >= 0 && py >= 0 && px < (float)M.img_w && py < (float)M.img_h)) return;
-    float bestdist;
-    const int bestid = match_walk_cells(px, py, M.cell, M.nbw, M.ncells, M.grid_ptr + (size_t)b * M.ncells, M.grid_kp, lane, mindist, bestdist,
-                                        [&](int kl) {
-        if ((unsigned)kl >= (unsigned)nkp || M.kp_matched[k0 + kl]) return -1.f;        // src/loop_closer.cpp:672-675
-        const int k = k0 + kl;
-        const float dx = px - M.kp_px[k].x, dy = py - M.kp_px[k].y;
-        const float pxdist = (float)sqrt((double)dx * dx + (double)dy * dy);
-        const int kd0 = M.kp_desc_ptr[k], kd1 = M.kp_desc_ptr[k + 1];
-        if (pxdist > dmaxpxdist || kd1 <= kd0) return -1.f;                             // :683, :690-695
-        if (kf_lists_meet(M.cand_kfids, M.cand_kf_ptr[c], M.cand_kf_ptr[c + 1], M.kp_kfids, M.kp_kf_ptr[k], M.kp_kf_ptr[k + 1])) return -1.f;
-        return min_desc_dist(M.cand_descs, cd0, cd1, M.kp_descs, kd0, kd1);             // :709
-    });
-    if (bestid < 0) return;
-    if (lane == 0)   // Hamming distances are small integers: exact in the key
-        atomicMin(&kp_best[k0 + bestid],
-                  ((unsigned long long)(unsigned)(int)bestdist << 32) | (unsigned long long)(0xffffffffu - (unsigned)(c - c0)));
-}
-
-// thresholds exactly as the reference forms them (src/loop_closer.cpp:595-607, :656): the products and the one-sided atan
-// are the reference's
-void loop_match_thresholds(const ov2_loop_match_input *in, float fmaxprojerr, float fdistratio, float &dmaxpxdist, float &mindist,
-                           float &view_th)
-{
-    const float vfov = (float)(0.5 * (double)in->img_h * in->K[1]), hfov = (float)(0.5 * (double)in->img_w * in->K[0]);
-    float maxradfov = 0.f;
-    if (hfov > vfov) maxradfov = atanf(hfov);
-    else maxradfov = atanf(hfov);
-    view_th = cosf(maxradfov);
-    dmaxpxdist = fmaxprojerr;
-    mindist = (float)((double)(32.f * fdistratio) * 8.);
-}
-
-}  // namespace
-
-extern "C" ov2_status ov2_loop_match_to_map_batch_dev(ov2_ctx *c, const ov2_loop_match_input *in, float fmaxprojerr, float fdistratio,
-                                                      uint64_t *d_work, int32_t *d_match_cand, float *d_match_dist)
-{
-    if (!c) return OV2_ERR_INVALID;
-    if (!in || in->B < 0 || in->n_kp < 0 || in->n_cand < 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch_dev: negative count");
-    if (in->B == 0 || in->n_kp == 0) return OV2_OK;
-    if (in->cell <= 0 || in->img_w <= 0 || in->img_h <= 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch_dev: bad image / cell size");
-    if (!d_work || !d_match_cand || !d_match_dist || !in->kp_off || !in->cand_off)
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch_dev: null argument");
-    if (in->n_cand && (!in->Twc || !in->kp_px || !in->kp_matched || !in->kp_desc_ptr || !in->kp_kf_ptr || !in->grid_ptr || !in->cand_wpt ||
-                       !in->cand_desc_ptr || !in->cand_kf_ptr))
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch_dev: null array");
-    if (((uintptr_t)in->kp_descs | (uintptr_t)in->cand_descs) & 7)   // descriptors are read 8 bytes at a time
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch_dev: descriptor arrays must be 8-byte aligned");
-    loop_match_dev M;
-    M.cam = ov2_cam_normalised(in->cam);
-    for (int i = 0; i < 4; ++i) M.cam.K[i] = in->K[i];   // one set of intrinsics: the call's
-    if (M.cam.model < 0 || M.cam.model > 2) return ov2_set_err(c, OV2_ERR_INVALID, "unknown lens model %d", M.cam.model);
-    M.B = in->B; M.n_kp = in->n_kp; M.n_cand = in->n_cand; M.img_w = in->img_w; M.img_h = in->img_h; M.cell = in->cell;
-    M.nbw = (int)ceilf((float)in->img_w / (float)in->cell);
-    M.ncells = M.nbw * (int)ceilf((float)in->img_h / (float)in->cell);
-    M.Twc = in->Twc; M.kp_off = in->kp_off; M.cand_off = in->cand_off;
-    M.kp_px = (const float2 *)in->kp_px; M.kp_matched = in->kp_matched; M.kp_desc_ptr = in->kp_desc_ptr; M.kp_descs = in->kp_descs;
-    M.kp_kf_ptr = in->kp_kf_ptr; M.kp_kfids = in->kp_kfids; M.grid_ptr = in->grid_ptr; M.grid_kp = in->grid_kp;
-    M.cand_wpt = in->cand_wpt; M.cand_desc_ptr = in->cand_desc_ptr; M.cand_descs = in->cand_descs; M.cand_kf_ptr = in->cand_kf_ptr;
-    M.cand_kfids = in->cand_kfids;
-    float dmaxpxdist, mindist, view_th;
-    loop_match_thresholds(in, fmaxprojerr, fdistratio, dmaxpxdist, mindist, view_th);
-    OV2_HIP(c, hipSetDevice(c->device));
-    OV2_HIP(c, hipMemsetAsync(d_work, 0xff, (size_t)in->n_kp * 8, c->stream));
-    if (in->n_cand > 0)
-        OV2_LAUNCH(c, K_LOOP_MATCH, loop_match_cand_kernel, dim3((in->n_cand + LOOP_WAVES - 1) / LOOP_WAVES), dim3(64 * LOOP_WAVES), 0,
-                   c->stream, M, dmaxpxdist, mindist, view_th, (unsigned long long *)d_work);
-    OV2_LAUNCH(c, K_LOOP_MATCH, match_out_kernel, dim3((in->n_kp + 255) / 256), dim3(256), 0, c->stream, in->n_kp,
-               (const unsigned long long *)d_work, d_match_cand, d_match_dist);
-    OV2_HIP(c, hipGetLastError());
-    return OV2_OK;
-}
-
-extern "C" ov2_status ov2_loop_match_to_map_batch(ov2_ctx *c, const ov2_loop_match_input *in, float fmaxprojerr, float fdistratio,
-                                                  int32_t *match_cand, float *match_dist)
-{
-    if (!c) return OV2_ERR_INVALID;
-    if (!in || in->B < 0 || in->n_kp < 0 || in->n_cand < 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch: negative count");
-    const int B = in->B;
-    if (B == 0) return OV2_OK;
-    if (!in->kp_off || !in->cand_off) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch: null offsets");
-    if (in->kp_off[0] != 0 || in->cand_off[0] != 0 || in->kp_off[B] != in->n_kp || in->cand_off[B] != in->n_cand)
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch: offsets do not span n_kp / n_cand");
-    for (int b = 0; b < B; ++b)
-        if (in->kp_off[b + 1] < in->kp_off[b] || in->cand_off[b + 1] < in->cand_off[b])
-            return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch: pair %d has a negative count", b);
-    const int nkp = in->n_kp, nc = in->n_cand;
-    if (nkp && (!match_cand || !match_dist)) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch: null output");
-    for (int k = 0; k < nkp; ++k) { match_cand[k] = -1; match_dist[k] = 0.f; }
-    if (nkp == 0 || nc == 0) return OV2_OK;                                  // src/loop_closer.cpp:591-593
-    if (in->cell <= 0 || in->img_w <= 0 || in->img_h <= 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch: bad image / cell size");
-    if (!in->Twc || !in->kp_px || !in->kp_matched || !in->kp_desc_ptr || !in->kp_kf_ptr || !in->grid_ptr || !in->cand_wpt ||
-        !in->cand_desc_ptr || !in->cand_kf_ptr)
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch: null array");
-    const int nbw = (int)ceilf((float)in->img_w / (float)in->cell), nbh = (int)ceilf((float)in->img_h / (float)in->cell);
-    const size_t ncells = (size_t)nbw * nbh, ng_ptr = (size_t)B * ncells + 1;
-    // the kernel indexes with these: every prefix array starts at 0 and never decreases, every grid entry lies in its pair
-    auto csr_ok = [](const int32_t *p, size_t n) {
-        if (p[0] != 0) return false;
-        for (size_t i = 0; i < n; ++i) if (p[i + 1] < p[i]) return false;
-        return true;
-    };
-    if (!csr_ok(in->kp_desc_ptr, nkp) || !csr_ok(in->kp_kf_ptr, nkp) || !csr_ok(in->cand_desc_ptr, nc) || !csr_ok(in->cand_kf_ptr, nc) ||
-        !csr_ok(in->grid_ptr, ng_ptr - 1))
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch: a prefix array decreases or does not start at 0");
-    const size_t n_kpd = (size_t)in->kp_desc_ptr[nkp], n_kpk = (size_t)in->kp_kf_ptr[nkp], n_g = (size_t)in->grid_ptr[ng_ptr - 1];
-    const size_t n_cd = (size_t)in->cand_desc_ptr[nc], n_ck = (size_t)in->cand_kf_ptr[nc];
-    if ((n_kpd && !in->kp_descs) || (n_kpk && !in->kp_kfids) || (n_g && !in->grid_kp) || (n_cd && !in->cand_descs) || (n_ck && !in->cand_kfids))
-        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch: null array");
-    for (int b = 0; b < B; ++b) {
-        const int nb = in->kp_off[b + 1] - in->kp_off[b];
-        for (int g = in->grid_ptr[(size_t)b * ncells]; g < in->grid_ptr[(size_t)(b + 1) * ncells]; ++g)
-            if (in->grid_kp[g] < 0 || in->grid_kp[g] >= nb)
-                return ov2_set_err(c, OV2_ERR_INVALID, "ov2_loop_match_to_map_batch: grid entry %d of pair %d outside its %d keypoints", in->grid_kp[g], b, nb);
-    }
-    // one staging block, every array 16-byte aligned: [inputs || work | match_cand | match_dist]
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off += (bytes + 15) / 16 * 16; return o; };
-    const size_t o_T = place((size_t)B * 56), o_ko = place((B + 1) * 4), o_co = place((B + 1) * 4), o_kpx = place((size_t)nkp * 8),
-                 o_km = place(nkp), o_kdp = place(((size_t)nkp + 1) * 4), o_kd = place(n_kpd * 32), o_kkp = place(((size_t)nkp + 1) * 4),
-                 o_kk = place(n_kpk * 4), o_gp = place(ng_ptr * 4), o_gk = place(n_g * 4), o_cw = place((size_t)nc * 24),
-                 o_cdp = place(((size_t)nc + 1) * 4), o_cd = place(n_cd * 32), o_ckp = place(((size_t)nc + 1) * 4), o_ck = place(n_ck * 4),
-                 o_in = off;
-    const size_t o_best = place((size_t)nkp * 8), o_mc = place((size_t)nkp * 4), o_md = place((size_t)nkp * 4);
-    void *hs = nullptr, *ds = nullptr;
-    ov2_status s = ov2_staging(c, off + 64, &hs, &ds);
-    if (s != OV2_OK) return s;
-    char *h = (char *)hs, *d = (char *)ds;
-    memcpy(h + o_T, in->Twc, (size_t)B * 56); memcpy(h + o_ko, in->kp_off, (B + 1) * 4); memcpy(h + o_co, in->cand_off, (B + 1) * 4);
-    memcpy(h + o_kpx, in->kp_px, (size_t)nkp * 8); memcpy(h + o_km, in->kp_matched, nkp);
-    memcpy(h + o_kdp, in->kp_desc_ptr, ((size_t)nkp + 1) * 4); if (n_kpd) memcpy(h + o_kd, in->kp_descs, n_kpd * 32);
-    memcpy(h + o_kkp, in->kp_kf_ptr, ((size_t)nkp + 1) * 4); if (n_kpk) memcpy(h + o_kk, in->kp_kfids, n_kpk * 4);
-    memcpy(h + o_gp, in->grid_ptr, ng_ptr * 4); if (n_g) memcpy(h + o_gk, in->grid_kp, n_g * 4);
-    memcpy(h + o_cw, in->cand_wpt, (size_t)nc * 24); memcpy(h + o_cdp, in->cand_desc_ptr, ((size_t)nc + 1) * 4);
-    if (n_cd) memcpy(h + o_cd, in->cand_descs, n_cd * 32);
-    memcpy(h + o_ckp, in->cand_kf_ptr, ((size_t)nc + 1) * 4); if (n_ck) memcpy(h + o_ck, in->cand_kfids, n_ck * 4);
-    OV2_HIP(c, hipSetDevice(c->device));
-    OV2_HIP(c, hipMemcpyAsync(d, h, o_in, hipMemcpyHostToDevice, c->stream));
-    ov2_loop_match_input D = *in;
-    D.Twc = (const double *)(d + o_T); D.kp_off = (const int32_t *)(d + o_ko); D.cand_off = (const int32_t *)(d + o_co);
-    D.kp_px = (const float *)(d + o_kpx); D.kp_matched = (const uint8_t *)(d + o_km); D.kp_desc_ptr = (const int32_t *)(d + o_kdp);
-    D.kp_descs = (const uint8_t *)(d + o_kd); D.kp_kf_ptr = (const int32_t *)(d + o_kkp); D.kp_kfids = (const int32_t *)(d + o_kk);
-    D.grid_ptr = (const int32_t *)(d + o_gp); D.grid_kp = (const int32_t *)(d + o_gk); D.cand_wpt = (const double *)(d + o_cw);
-    D.cand_desc_ptr = (const int32_t *)(d + o_cdp); D.cand_descs = (const uint8_t *)(d + o_cd); D.cand_kf_ptr = (const int32_t *)(d + o_ckp);
-    D.cand_kfids = (const int32_t *)(d + o_ck);
-    s = ov2_loop_match_to_map_batch_dev(c, &D, fmaxprojerr, fdistratio, (uint64_t *)(d + o_best), (int32_t *)(d + o_mc), (float *)(d + o_md));
-    if (s != OV2_OK) return s;
-    OV2_HIP(c, hipMemcpyAsync(h + o_mc, d + o_mc, (o_md - o_mc) + (size_t)nkp * 4, hipMemcpyDeviceToHost, c->stream));
-    OV2_HIP(c, hipStreamSynchronize(c->stream));
-    memcpy(match_cand, h + o_mc, (size_t)nkp * 4);
-    memcpy(match_dist, h + o_md, (size_t)nkp * 4);
     return OV2_OK;
 }

@@ -83,6 +83,57 @@ def test_other_gates_and_lens_model(ctx, oracle, frames):
         assert sum(int((mc >= 0).sum()) for mc, _ in got) > 20
 
 
+def test_single_call_dense_cells_gates_and_lens_model(ctx, oracle, frames):
+    """ov2_match_to_map, the B = 1 case of the batch form, against the checker on the inputs of the two tests above"""
+    assert np.diff(SM.single_input(frames["dense"], cell=SM.CELL_DENSE).grid_ptr).max() > 64
+    for name in ("dense", "plain_a"):
+        inp = SM.single_input(frames[name], cell=SM.CELL_DENSE)
+        got = mapper.matchToMap(ctx, inp, *GATES)
+        assert _same(got, oracle.match_to_map(inp, *GATES)), name
+        assert (got[0] >= 0).sum() > 20, name
+    cam = CamModelC.make(SM.K4, "radtan", SM.RADTAN)
+    for gates, cm in (((4.0, 0.35), None), (GATES, cam)):
+        n = 0
+        for name in ("plain_a", "few3d", "borders", "plain_b"):
+            inp = SM.single_input(frames[name], cam=cm)
+            got = mapper.matchToMap(ctx, inp, *gates)
+            assert _same(got, oracle.match_to_map(inp, *gates)), (name, gates)
+            n += int((got[0] >= 0).sum())
+        assert n > 20
+
+
+def test_single_call_without_pose_table(ctx, oracle, frames):
+    """n_kf = 0 and kf_Twc = NULL with keyframe ids in the lists: every id is skipped, 0 / 0 compares false"""
+    f = dict(frames["plain_a"], kf_Twc=np.zeros((0, 7)))
+    inp = SM.single_input(f)
+    inp.c.kf_Twc = None
+    assert inp.c.n_kf == 0 and len(inp.kp_kfids) > 0
+    exp = oracle.match_to_map(inp, *GATES)
+    assert (exp[0] >= 0).sum() > 20
+    assert _same(mapper.matchToMap(ctx, inp, *GATES), exp)
+
+
+def test_single_call_refuses_what_the_batch_form_refuses(ctx, frames):
+    """host-side refusals: nothing is launched for the bad inputs, the outputs keep the caller's values or the (-1, 0) pre-fill"""
+    def call(edit):
+        inp = SM.single_input(frames["borders"])
+        mc, md = np.full(inp.c.n_kp, -7, np.int32), np.full(inp.c.n_kp, -7, np.float32)   # no output is negative but -1
+        edit(inp)
+        return ctx.lib.ov2_match_to_map(ctx.h, C.addressof(inp.c), 2.0, 0.2, mc.ctypes.data, md.ctypes.data), mc, md
+
+    def raise_above_successor(i):
+        i.kp_desc_ptr[3] = i.kp_desc_ptr[4] + 1
+    n_kp = len(frames["borders"]["kps"])
+    st, mc, md = call(lambda i: None)
+    assert st == 0 and (mc >= 0).sum() > 0 and not (mc == -7).any() and not (md == -7).any()
+    for edit in (lambda i: i.grid_kp.__setitem__(0, n_kp), lambda i: i.grid_kp.__setitem__(0, -1), raise_above_successor,
+                 lambda i: i.cand_kf_ptr.__setitem__(0, 1)):
+        st, mc, md = call(edit)
+        assert st == -1                                                       # OV2_ERR_INVALID
+        assert ((mc == -7) & (md == -7) | (mc == -1) & (md == 0)).all()
+    assert (mapper.matchToMap(ctx, SM.single_input(frames["plain_a"]), *GATES)[0] >= 0).sum() > 20   # the context still works
+
+
 def test_empty_and_invalid_arguments(ctx, frames):
     lib, INVALID = ctx.lib, -1                                          # OV2_ERR_INVALID
     empty = SM.batch_input([])
