@@ -435,27 +435,44 @@ __device__ __forceinline__ int lk_level(const level_ptrs &I, const level_ptrs &J
 //     cut out by v_perm_b32 with per-lane selectors (the byte shift is a constant of the lane for the whole window);
 //   - the template rows (I: 8 B, gradient: 16 B per lane and row) go from global memory straight to registers -- no
 //     LDS for them;
-//   - the SEARCH image is staged once per level pass as a 14-row x 48-byte region around the start position
-//     (margin 2 rows / >= 11 columns): the later iterations of the pass read it from LDS without another trip to
+//   - the SEARCH image is staged once per level pass as a 14-row x 32-byte region around the start position
+//     (margin 2 rows / >= 9 columns): the later iterations of the pass read it from LDS without another trip to
 //     memory, and a window that leaves the region re-stages it (rare);
 //   - sums over the three lanes: whole-wave DPP shifts by one lane (groups 5 and 10 straddle a DPP row) + two selects.
 // Arithmetic per window pixel is the one of lk_level (same taps, exact integer sums), so results are bit-identical.
 #ifndef KLT3_RROWS
 #define KLT3_RROWS 14
 #endif
-#ifndef KLT3_RBYTES
-#define KLT3_RBYTES 48
+// Waves per SIMD of the three-lane kernels.  A level pass needs 117 VGPRs and 9744 B of LDS, which the hardware would place
+// four deep; amdgpu_waves_per_eu's upper bound only gives the register allocator room, it does not keep a wave out.  At
+// three per SIMD the tracking launch is faster alone AND beside the local-BA worker (same title: 329.3 k
+// against 324.1 k frames/s front end alone, 305.8 k against 295.8 k beside the worker), so the kernels CLAIM the allocation
+// granule that ends the fourth wave -- 129 .. 136 registers, by naming v135 as clobbered at the head of a pass.  Twelve
+// workgroups then hold 408 of a SIMD's 512 registers and 114 KB of a CU's 160 KB of LDS (before: 432 and 155 KB).
+// 2 = claim the 171 .. 176 granule (measured slower), 4 = claim nothing.
+#ifndef KLT3_WAVES
+#define KLT3_WAVES 3
+#endif
+#if KLT3_WAVES == 3
+#define KLT3_VGPR_CLAIM "v135"
+#elif KLT3_WAVES == 2
+#define KLT3_VGPR_CLAIM "v175"
 #endif
 struct klt3 {
-    // Region rows are 48 bytes (one 16-byte piece per lane: a load instruction touches ONE image row per keypoint; the
-    // vector memory front end spends ~2 cycles per distinct cache line of an instruction, scripts/micro/ta_bench.hip) or
-    // 32 bytes (pieces dealt out 3 per instruction over the 2 x RROWS pieces: smaller LDS block and fewer registers in flight).
-    static constexpr int RROWS = KLT3_RROWS, RBYTES = KLT3_RBYTES;
+    // Region rows are 32 bytes: the 2 x RROWS 16-byte pieces are dealt out three per load instruction over the group's lanes.
+    // 464 B per keypoint, 9744 B per wave: sixteen workgroups per CU fit by LDS.  (The 48-byte rows of before, a piece per
+    // lane and row, took 14 448 B per wave -- eleven workgroups filled a CU's LDS -- and are gone: DESIGN.md section 7
+    // "Tracking kernels: a footprint that leaves room beside the solver".)
+    static constexpr int RROWS = KLT3_RROWS, RBYTES = 32;
     static constexpr int RSZ = RROWS * RBYTES + 16;   // +16: the regions of a wave start in different banks
-    static constexpr int NLD = RBYTES == 48 ? RROWS : (2 * RROWS + 2) / 3;   // 16-byte loads per lane
+    static constexpr int NLD = (2 * RROWS + 2) / 3;   // 16-byte loads per lane
     static constexpr int ROW_SPAN = RROWS - 10, ROW_MARGIN = ROW_SPAN / 2;   // the window's first row may sit ROW_SPAN rows into the region
-    static constexpr int COL_ALIGN = RBYTES == 48 ? 16 : 4;
-    static constexpr int COL_LEAD = RBYTES == 48 ? 12 : 9, COL_SPAN = RBYTES == 48 ? 38 : 20;   // ... and its first column 0 .. COL_SPAN bytes
+    static constexpr int COL_ALIGN = 4;
+    // ... and its first column 0 .. COL_SPAN bytes: the last lane's dword pair then ends with the row.  An origin clamped at
+    // the row pitch - RBYTES can leave a window up to two bytes further in where the pitch has under two spare bytes (level
+    // widths of 38 or 39 mod 64, window hanging over the right border): such an iteration re-stages every time and reads its ten
+    // columns correctly, the unused half of its last dword pair coming from the next row or the 16 spare bytes
+    static constexpr int COL_LEAD = 9, COL_SPAN = 20;
 };
 
 // lane -> (keypoint slot of the wave, lane of the group); GL = 8 / 16: power-of-two groups, GL = 3: see above
@@ -512,31 +529,55 @@ __device__ __forceinline__ void klt3_region_origin(const level_ptrs &J, int pad,
     cc0 = min(max((OV2_LM + inx - klt3::COL_LEAD) & ~(klt3::COL_ALIGN - 1), 0), J.istride - klt3::RBYTES);
 }
 
-// the group's three lanes fetch the region: 48-byte rows: lane c takes bytes 16c .. 16c + 15 of every row; 32-byte rows:
-// the 2 x RROWS pieces are dealt out three per instruction (piece s = 3t + c: row s / 2, half s % 2)
-struct klt3_segs { uint4 v[klt3::NLD]; };
-__device__ __forceinline__ void klt3_load_region(const level_ptrs &J, int rr0, int cc0, int c, klt3_segs &S)
+// the group's three lanes fetch the region: the 2 x RROWS pieces are dealt out three per instruction (piece s = 3t + c: row
+// s / 2, half s % 2).
+// A lane's loads come in batches of NLD / KLT3_REGION_BATCHES: a batch is loaded and stored to LDS before the next one is
+// issued (klt3_stage_region), so only a batch's registers are in flight -- what the whole region held at once was the
+// register peak of a pass, both where it travels with the template rows and where an iteration re-stages it.  Measured
+// (headline frames/s, same section of DESIGN.md): one batch 302.8 k at 126 VGPRs, two 305.8 k at 117, five 295.8 k
+#ifndef KLT3_REGION_BATCHES
+#define KLT3_REGION_BATCHES 2
+#endif
+template <int T0, int T1>
+struct klt3_segs { uint4 v[T1 - T0]; };
+template <int T0, int T1>
+__device__ __forceinline__ void klt3_load_region(const level_ptrs &J, int rr0, int cc0, int c, klt3_segs<T0, T1> &S)
 {
     const unsigned o = J.img_o + (unsigned)(rr0 * J.istride + cc0);
+    // piece 3t + c sits (3t + c) / 2 rows down in half (3t + c) % 2.  Two instructions further on it is three
+    // rows down in the same half, so a lane's addresses are two chains (even t, odd t) of uniform steps from two starts --
+    // formed from c per piece they were twenty lane constants the compiler kept across the whole level loop
+    const unsigned a0 = o + (unsigned)((c >> 1) * J.istride + (c & 1) * 16);
+    const unsigned a1 = a0 + (unsigned)((c & 1) ? 2 * J.istride - 16 : J.istride + 16);
 #pragma unroll
-    for (int t = 0; t < klt3::NLD; ++t) {
-        unsigned a;
-        if (klt3::RBYTES == 48) a = o + (unsigned)(t * J.istride + 16 * c);
-        else {
-            const int sg = min(3 * t + c, 2 * klt3::RROWS - 1);
-            a = o + (unsigned)((sg >> 1) * J.istride + (sg & 1) * 16);
-        }
-        S.v[t] = ld_b128(J.base + (size_t)a);
+    for (int t = T0; t < T1; ++t) {
+        unsigned a = ((t & 1) ? a1 : a0) + (unsigned)((t >> 1) * 3 * J.istride);
+        // past the region's last piece (lanes 1 and 2 of the last instruction): re-read the piece before, never stored
+        if (3 * t + 2 >= 2 * klt3::RROWS && 3 * t + c >= 2 * klt3::RROWS) a = ((t & 1) ? a0 : a1) + (unsigned)(((t - 1) >> 1) * 3 * J.istride);
+        S.v[t - T0] = ld_b128(J.base + (size_t)a);
     }
 }
-__device__ __forceinline__ void klt3_store_region(const klt3_segs &S, int c, bool store, unsigned char *lj)
+template <int T0, int T1>
+__device__ __forceinline__ void klt3_store_region(const klt3_segs<T0, T1> &S, int c, bool store, unsigned char *lj)
 {
     if (store) {
 #pragma unroll
-        for (int t = 0; t < klt3::NLD; ++t) {
-            if (klt3::RBYTES == 48) *reinterpret_cast<uint4 *>(lj + t * klt3::RBYTES + 16 * c) = S.v[t];
-            else if (3 * t + c < 2 * klt3::RROWS) *reinterpret_cast<uint4 *>(lj + (3 * t + c) * 16) = S.v[t];
+        for (int t = T0; t < T1; ++t) {
+            if (3 * t + 2 < 2 * klt3::RROWS || 3 * t + c < 2 * klt3::RROWS) *reinterpret_cast<uint4 *>(lj + (3 * t + c) * 16) = S.v[t - T0];
         }
+    }
+}
+// batches B .. NB - 1 of the region's NB, one behind the other
+template <int B, int NB>
+__device__ __forceinline__ void klt3_stage_region(const level_ptrs &J, int rr0, int cc0, int c, bool store, unsigned char *lj)
+{
+    if constexpr (B < NB) {
+        constexpr int T0 = klt3::NLD * B / NB, T1 = klt3::NLD * (B + 1) / NB;
+        klt3_segs<T0, T1> S;
+        klt3_load_region(J, rr0, cc0, c, S);
+        klt3_store_region(S, c, store, lj);
+        __builtin_amdgcn_sched_barrier(0);   // the next batch's loads stay behind this batch's stores
+        klt3_stage_region<B + 1, NB>(J, rr0, cc0, c, store, lj);
     }
 }
 
@@ -549,6 +590,9 @@ __device__ __forceinline__ int lk_level3(const level_ptrs &I, const level_ptrs &
                                          unsigned char *lj)
 {
     static_assert(WIN == 9, "three lanes x three columns");
+#ifdef KLT3_VGPR_CLAIM
+    asm volatile("" ::: KLT3_VGPR_CLAIM);   // see KLT3_WAVES
+#endif
     constexpr int NPX = 3 * WIN, NQ = (NPX + 1) / 2;   // window pixels per lane, flat e = 3 * row + column; pairs of them
     const float FLT_SCALE = 1.f / (float)(1 << 20);
     const float half = (float)(WIN - 1) * 0.5f;
@@ -597,15 +641,20 @@ __device__ __forceinline__ int lk_level3(const level_ptrs &I, const level_ptrs &
         const int dr = (p) == 0 ? (by > 0 ? -1 : 0) : ((p) == WIN + 2 ? (by + WIN + 1 < I.rows ? WIN + 1 : WIN) : (p) - 1); \
         __builtin_memcpy(&irow[p], __builtin_assume_aligned(I.base + (size_t)(io + (unsigned)(dr * I.istride)), 4), 12);   \
     } while (0)
-        // two batches (the first travels with the region, the second sits behind the barrier that publishes the region):
-        // keeps the registers in flight down
+        // two batches (the first travels with the region's first batch, the second sits behind the barrier that publishes
+        // the region): keeps the registers in flight down
         constexpr int R1 = 6;
         __syncthreads();   // the previous pass may still read the region
-        klt3_segs S;
-        klt3_load_region(J, rr0, cc0, c, S);
+        {
+            constexpr int T1 = klt3::NLD / KLT3_REGION_BATCHES;
+            klt3_segs<0, T1> S;
+            klt3_load_region(J, rr0, cc0, c, S);
 #pragma unroll
-        for (int p = 0; p < R1; ++p) KLT3_LOAD_ROW(p);
-        klt3_store_region(S, c, lane_ok, lj);
+            for (int p = 0; p < R1; ++p) KLT3_LOAD_ROW(p);
+            klt3_store_region(S, c, lane_ok, lj);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        klt3_stage_region<1, KLT3_REGION_BATCHES>(J, rr0, cc0, c, lane_ok, lj);
         __syncthreads();   // region staged
 #pragma unroll
         for (int p = R1; p < WIN + 3; ++p) KLT3_LOAD_ROW(p);
@@ -728,9 +777,7 @@ __device__ __forceinline__ int lk_level3(const level_ptrs &I, const level_ptrs &
             __syncthreads();
             if (out) {
                 klt3_region_origin(J, pad, inx, iny, rr0, cc0);
-                klt3_segs S;
-                klt3_load_region(J, rr0, cc0, c, S);
-                klt3_store_region(S, c, lane_ok, lj);
+                klt3_stage_region<0, KLT3_REGION_BATCHES>(J, rr0, cc0, c, lane_ok, lj);
                 rb = iny + pad - rr0; cb = OV2_LM + inx - cc0;
             }
             __syncthreads();
@@ -896,10 +943,11 @@ __device__ __forceinline__ int fb_track(const ov2_pyr_view &pv, const ov2_pyr_vi
 #ifndef KLT_WAVE_CAP
 #define KLT_WAVE_CAP 4
 #endif
+// the three-lane kernels: at least two, at most KLT3_WAVES (above), which is what they run at
 #ifndef KLT3_WAVE_MIN
 #define KLT3_WAVE_MIN 2
 #endif
-#define KLT_WAVES(W, G) ((G) == 3 ? KLT3_WAVE_MIN : 1), KLT_WAVE_CAP
+#define KLT_WAVES(W, G) ((G) == 3 ? KLT3_WAVE_MIN : 1), ((G) == 3 ? KLT3_WAVES : KLT_WAVE_CAP)
 
 // 64 threads = 64 / GL keypoints.  grid = ceil(n / (64 / GL))
 template <int WIN, int KLT_GL>
