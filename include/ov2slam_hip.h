@@ -822,6 +822,37 @@ ov2_status ov2_map_set_obs_stereo(ov2_map *m, int n, const int32_t *kfid, const 
                                   const double *runpx);
 ov2_status ov2_map_remove_landmarks(ov2_map *m, int n, const int32_t *lmid);
 ov2_status ov2_map_remove_keyframe(ov2_map *m, int kfid);
+
+/* Match columns: what Mapper::matchToMap reads of an observation beyond the set-up's columns, kept per observation row so that
+ * the matcher's input can be assembled on the device (ov2_map_match_gather_batch_dev below):
+ *   obs_px       float x 2   Keypoint::px_, the raw pixel (obs_uv is unpx_)
+ *   obs_desc     32 bytes    MapPoint::map_kf_desc_[kfid], 16-byte aligned
+ *   obs_hasdesc  1 byte      0 where describeBRIEF gave none (within 28 px of the border, src/feature_extractor.cpp:224-285)
+ * INVARIANT: the descriptor set of a landmark (map_kf_desc_) is the set of descriptors of its LIVE rows that carry one;
+ * desc_.empty() means that set is empty.  MapPoint::removeKfObs drops the keyframe's descriptor (src/map_point.cpp:106-162): a
+ * dead row counts for nothing.  The representative desc_ (the medoid MapPoint::addDesc maintains, :164-213) is NOT mirrored:
+ * matchToMap only tests it for emptiness.
+ * ov2_map_enable_match_columns allocates the columns (idempotent); rows already present get pixel 0 and no descriptor.  A map
+ * that never calls it allocates and costs nothing more than before, and every entry point below refuses it.  The columns
+ * follow every growth and every squeeze of the table (the same stable scatter).  They are NOT part of ov2_map_save_state /
+ * ov2_map_restore_state_batch: a restore rewinds liveness, not pixels or descriptors.
+ *   ov2_map_add_keyframe_px   ov2_map_add_keyframe plus px (n x 2 floats) and desc (n x 32) / has_desc (n), both NULL = no
+ *                             descriptors (MapManager::addKeyframe + MapPoint::addKfObs / addDesc, src/map_manager.cpp:621-634,
+ *                             :351-360).  ov2_map_add_keyframe on a map with columns appends pixel 0 / no descriptor.
+ *   ov2_map_set_obs_desc      MapPoint::addDesc(kfid, desc) for a keyframe that observes the point (src/map_point.cpp:164-213):
+ *                             the live row (kfid, lmid) takes px (NULL = keep), desc and has_desc; a pair without a live row is
+ *                             passed over, as ov2_map_remove_obs passes it over.
+ * Both return OV2_ERR_INVALID on a map without the columns.
+ * Merges (ov2_map_merge_points_batch): a relabelled row keeps its pixel and descriptor, as MapManager::mergeMapPoints re-adds
+ * prev's descriptors under the same keyframe ids (src/map_manager.cpp:854-856); on a conflict row -- the keyframe holds prev
+ * and new -- new's row of that keyframe takes prev's descriptor if and only if it has none (addDesc returns early otherwise,
+ * src/map_point.cpp:164-171).  Without the columns the merge does what it did. */
+ov2_status ov2_map_enable_match_columns(ov2_map *m);
+ov2_status ov2_map_add_keyframe_px(ov2_map *m, int kfid, const double *Twc, int n, const int32_t *lmid, const double *unpx,
+                                   const double *runpx, const uint8_t *is_stereo, const int32_t *scale, const float *px,
+                                   const uint8_t *desc /* n x 32, or NULL */, const uint8_t *has_desc /* n, or NULL */);
+ov2_status ov2_map_set_obs_desc(ov2_map *m, int n, const int32_t *kfid, const int32_t *lmid, const float *px /* n x 2, or NULL */,
+                                const uint8_t *desc /* n x 32 */, const uint8_t *has_desc /* n */);
 /* Removals leave dead rows in the observation table (the reference erases the entries from its hash maps,
  * src/map_manager.cpp:885-1019).  ov2_map_local_ba_setup squeezes them out (stable: the order of the live rows, and so
  * every result, is unchanged) when fewer than half of >= 4096 rows are live, so the table stays within 2x the live
@@ -978,8 +1009,9 @@ ov2_status ov2_map_triangulate_temporal_batch(ov2_ctx *ctx, int B, ov2_map *cons
  *    the bit is the Keypoint::is3d_ of its observations, and it has none left (what MapManager::attachDevice gives it).
  * Deviations from the reference: a row whose landmark or keyframe is dead is not live in the mirror (obs_live), so the
  * branches "missing map point" (:151-154) and "keyframe gone" (:135-138) have nothing to do here; the candidates come from
- * the recount, not from a stored Frame::map_covkfs_; anchors (MapPoint::kfid_) and descriptors are not mirror state (the
- * update stage recounts the oldest observer).
+ * the recount, not from a stored Frame::map_covkfs_; anchors (MapPoint::kfid_) are not mirror state (the update stage
+ * recounts the oldest observer).  Descriptors, where the map has the match columns, live on the observation rows: a removed
+ * keyframe's rows are dead, and with them their descriptors (MapPoint::removeKfObs) -- nothing to replay.
  * map = blockIdx.y of every launch, sizes come from device memory, seven launches whatever B: zero, row scan (observers,
  * landmarks of newkf, rows and 3D rows per keyframe), the three scan kernels over the rows per keyframe, covisibility +
  * scatter into the per-keyframe row index (a counting sort over obs_kf: O(rows) per map), and one workgroup per map that
@@ -1055,8 +1087,10 @@ ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *ctx, int B, ov2_map *const *
  * knows whether the current frame held p).  The point and the other bits of n are untouched.  n_merged counts the pairs not
  * skipped; n_pairs = n_merged + n_skipped.  So (a, b), (b, c) moves a's rows twice; (a, b), (a, c) skips the second pair;
  * (a, n), (b, n) with a and b seen by one keyframe keeps the second pair's row of that keyframe as a conflict.
- * Descriptors (addDesc), covisibility maps, anchors and nblms_ are not mirror state: a caller that keeps them replays them
- * from pair_status.
+ * Covisibility maps, anchors and nblms_ are not mirror state: a caller that keeps them replays them from pair_status.
+ * Descriptors are mirror state on a map with the match columns (see ov2_map_enable_match_columns): a moved row carries its
+ * descriptor, and on a conflict row new's row of that keyframe takes prev's descriptor if and only if it has none
+ * (:854-856, src/map_point.cpp:164-171); on a map without the columns a caller still replays addDesc from pair_status.
  *
  * Host form: prev_lmid / new_lmid / cur_obs (or NULL = all 0) are host arrays staged through the context's pinned block;
  * out (B, or NULL) takes the headers, pair_status (pair_off[B] bytes, or NULL) the statuses; with both NULL the call is
@@ -1099,6 +1133,9 @@ ov2_status ov2_map_save_state(ov2_map *m);
 ov2_status ov2_map_restore_state_batch(ov2_ctx *ctx, int B, ov2_map *const *maps);
 ov2_status ov2_map_download(ov2_map *m, int *n_kf, int *n_lm, int *n_obs, double *kf_pose, uint8_t *kf_state, double *lm_xyz,
                             uint8_t *lm_state, int32_t *obs_kf, int32_t *obs_lm, uint8_t *obs_flag, double *obs_uv, double *obs_ruv);
+/* ... and the match columns of the same n_obs rows (n x 2 floats, n x 32 bytes, n bytes; any pointer may be NULL);
+ * OV2_ERR_INVALID on a map without them. */
+ov2_status ov2_map_download_match_columns(ov2_map *m, float *obs_px, uint8_t *obs_desc, uint8_t *obs_hasdesc);
 
 /* The flat problem of the last set-up where the kernels left it ON THE DEVICE: `dev` = `host` with every array pointer
  * translated (same validity: until the next set-up call of this map).  These are the pointers ov2_ba_solve_batch_dev
@@ -1280,6 +1317,71 @@ ov2_status ov2_match_pairs_dev(ov2_ctx *ctx, int B, int n_kp, const int32_t *d_k
                                const int32_t *d_kp_lmid /* n_kp */, const int32_t *d_cand_lmid /* n_cand */,
                                const int32_t *d_match_cand /* n_kp */, int32_t *d_prev_lmid, int32_t *d_new_lmid /* n_kp each */,
                                int32_t *d_n_pairs /* B */);
+
+/* The input of ov2_match_to_map_batch_dev assembled ON THE DEVICE from B map mirrors that have the match columns
+ * (ov2_map_enable_match_columns), for servers whose maps live in mirrors only: what Mapper::matchingToLocalMap collects by
+ * walking Frame / MapPoint objects (src/mapper.cpp:469-554) and Mapper::matchToMap reads from them (:576-774).  The caller
+ * passes ids only, all HOST arrays, uploaded once:
+ *   newkf, nb3dkps   B          the new keyframe of every map and its Frame::nb3dkps_
+ *   kp_off, kp_lmid  B + 1, x   the new keyframe's keypoints with a map point, in grid order (frame b owns kp_off[b] .. kp_off[b + 1])
+ *   grid_ptr, grid_kp           Frame::vgridkps_ as ov2_match_batch_input takes it (its order decides ties and is not mirror state)
+ *   cand_off, cand_lmid         set_local_mapids_ in the caller's iteration order, UNFILTERED
+ * and the call fills *out with DEVICE pointers:
+ *   Twc[b] = the mirror's pose of newkf[b]; kf_Twc / kf_off = every map's pose table (kf_off[b + 1] - kf_off[b] = its keyframe
+ *   capacity), so that kfid indexes it;
+ *   keypoint k with landmark L: kp_px = the pixel of L's live row in newkf ((0, 0) without one).  L alive with at least one
+ *   described live row: kp_descs = the descriptors of its live rows, in any order (MapPoint::computeMinDescDist is a
+ *   minimum), kp_kfids = the keyframes of ALL its live rows, ASCENDING (MapPoint::set_kfids_ is a std::set; the co-observation
+ *   test merges two ascending lists and the f32 mean-reprojection sum runs in this order), kp_kf_px = those rows' pixels in
+ *   the same order.  Otherwise both ranges are empty (:676-685);
+ *   candidate c with landmark L: cand_wpt = its point (0 where L is not alive), observers and descriptors as above.  BOTH
+ *   ranges are empty -- the matcher passes over a candidate without descriptors -- when L is out of range, not OV2_LM_ALIVE,
+ *   not OV2_LM_3D, observed by newkf (a live row there, Frame::isObservingKp) or without a descriptor (:613-624).  Refused
+ *   candidates STAY in the list: indices, and with them the later-candidate-wins tie rule, are the caller's.
+ * The *_ptr arrays are contiguous prefix offsets over the whole batch (one flat scan, not one per map).  Twelve launches
+ * whatever B and the list lengths are, one upload, no synchronisation, nothing read back: the arrays are sized from the
+ * row counts the host knows.  They live in the context's scratch block and stay valid until the next call of this family
+ * on the context or the next host-pointer entry point that takes that block; d_kp_lmid / d_cand_lmid (may be NULL) receive
+ * the device copies of the id lists (what ov2_match_pairs_dev takes).
+ * B = 0 and a call without any keypoint are OV2_OK with nothing enqueued (out->n_kp = 0); a frame without keypoints or without
+ * candidates is fine.  OV2_ERR_INVALID with nothing enqueued and the maps untouched: a map without the columns, of another
+ * context or twice in the call; newkf not alive in its map; offsets that decrease or do not start at 0; a grid entry outside
+ * its frame; a landmark twice among a frame's keypoints or among its candidates; null arrays that a non-empty call needs. */
+ov2_status ov2_map_match_gather_batch_dev(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf, const int32_t *nb3dkps,
+                                          const int32_t *kp_off, const int32_t *kp_lmid, const int32_t *grid_ptr,
+                                          const int32_t *grid_kp, const int32_t *cand_off, const int32_t *cand_lmid,
+                                          const double *K /* fx fy cx cy */, int img_w, int img_h, int cell,
+                                          const ov2_cam_model *cam /* or NULL */, ov2_match_batch_input *out,
+                                          const int32_t **d_kp_lmid, const int32_t **d_cand_lmid);
+
+/* Mapper::matchingToLocalMap from the mirrors: the gather above, then ov2_match_to_map_batch_dev on what it left (the matcher's
+ * kernels, unchanged), then -- _dev form with pairs != 0 -- ov2_match_pairs_dev.  One camera and one fmaxprojerr / fdistratio
+ * per call, as in the batch matcher; status and refusals as for the gather.
+ * Host-result form: match_lmid[k] = the lmid of the candidate matched to keypoint k or -1, match_dist[k] = its Hamming
+ * distance; one download, one synchronisation.
+ * _dev form: nothing is synchronised; *out holds DEVICE pointers into the context's scratch block (validity as above):
+ * match_cand / match_dist as ov2_match_to_map_batch_dev leaves them and, with pairs, prev_lmid / new_lmid / n_pairs laid out
+ * as ov2_map_merge_points_batch_dev takes them with pair_off = the caller's kp_off.  For a mirror-only map, gather -> match ->
+ * pairs -> merge is then enqueued on one stream with no host arrays beyond ids.  All pointers are NULL after a call that had
+ * nothing to do. */
+typedef struct ov2_map_match_local {
+    const int32_t *d_kp_off, *d_cand_off;     /* B + 1 each */
+    const int32_t *d_kp_lmid, *d_cand_lmid;   /* n_kp, n_cand */
+    const int32_t *d_match_cand;              /* n_kp: index within the frame's candidates, or -1 */
+    const float *d_match_dist;                /* n_kp */
+    const int32_t *d_prev_lmid, *d_new_lmid;  /* n_kp each (pairs) */
+    const int32_t *d_n_pairs;                 /* B (pairs) */
+} ov2_map_match_local;
+ov2_status ov2_map_match_local_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf, const int32_t *nb3dkps,
+                                     const int32_t *kp_off, const int32_t *kp_lmid, const int32_t *grid_ptr, const int32_t *grid_kp,
+                                     const int32_t *cand_off, const int32_t *cand_lmid, const double *K, int img_w, int img_h,
+                                     int cell, const ov2_cam_model *cam, float fmaxprojerr, float fdistratio,
+                                     int32_t *match_lmid /* n_kp */, float *match_dist /* n_kp */);
+ov2_status ov2_map_match_local_batch_dev(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf, const int32_t *nb3dkps,
+                                         const int32_t *kp_off, const int32_t *kp_lmid, const int32_t *grid_ptr,
+                                         const int32_t *grid_kp, const int32_t *cand_off, const int32_t *cand_lmid, const double *K,
+                                         int img_w, int img_h, int cell, const ov2_cam_model *cam, float fmaxprojerr,
+                                         float fdistratio, int pairs, ov2_map_match_local *out);
 
 /* LoopCloser::matchToMap(frame, Tcw, fmaxprojerr, fdistratio, vmatchedkpids, set_local_lmids) (include/loop_closer.hpp,
  * src/loop_closer.cpp:586-763) for B candidate pairs in one call.  It is NOT Mapper::matchToMap: the projection pose is an

@@ -97,6 +97,16 @@ SIGNATURES = {
     "ov2_map_merge_points_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "ov2_map_merge_points_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ov2_match_pairs_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ov2_map_enable_match_columns": (C.c_int, [vp]),
+    "ov2_map_download_match_columns": (C.c_int, [vp, vp, vp, vp]),
+    "ov2_map_add_keyframe_px": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ov2_map_set_obs_desc": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+    "ov2_map_match_gather_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp,
+                                                 vp, vp, vp]),
+    "ov2_map_match_local_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp,
+                                            C.c_float, C.c_float, vp, vp]),
+    "ov2_map_match_local_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp,
+                                                C.c_float, C.c_float, C.c_int, vp]),
     "ov2_map_compact": (C.c_int, [vp, ip, ip]),
     "ov2_map_obs_rows": (C.c_int, [vp, ip, ip, ip]),
     "ov2_map_local_ba_setup": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),

@@ -74,6 +74,10 @@ struct ov2_map {
     unsigned char *mg_mark;                                         // [max_lm] named by a pair of the call
     int *mg_start;                                                  // [max_lm] exclusive scan of mg_cnt: where the landmark's rows start in mg_rows
     int *mg_rows;                                                   // [max_obs] live rows of the named landmarks, grouped by landmark
+    // ov2_map_enable_match_columns: raw pixel, descriptor and "has a descriptor" per observation row (all null without it)
+    float *obs_px; unsigned char *obs_desc, *obs_hasdesc;           // [max_obs] x 2 floats, x 32 bytes, x 1
+    int *mg_srow;                                                   // [max_kf] the row behind mg_stamp: `new`'s row of the keyframe
+    int *gt_seen_h; int gt_gen;                                     // host, [max_lm]: the call that last listed the landmark (duplicates are refused)
 };
 
 namespace {
@@ -96,6 +100,7 @@ struct map_view {
     const double *kf_pose; const unsigned char *kf_state;
     const double *lm_xyz; const unsigned char *lm_state;
     const int *obs_kf, *obs_lm, *obs_scale; const double *obs_uv, *obs_ruv; const unsigned char *obs_flag;
+    const float2 *obs_px; const uint4 *obs_desc; const unsigned char *obs_hasdesc;   // match columns, null without them
 };
 
 // an observation counts when it, its keyframe and its landmark are alive (MapPoint::set_kfids_ / Frame::mapkps_ agree)
@@ -157,6 +162,34 @@ __global__ __launch_bounds__(256) void map_edit_obs_kernel(int n_obs, const int 
     }
 }
 
+// MapPoint::addDesc(kfid, desc) for keyframes that observe the point: the same search, the live row (kfid, lmid) takes the
+// pixel (where given), the descriptor and its flag
+__global__ __launch_bounds__(256) void map_set_desc_kernel(int n_obs, const int *__restrict__ obs_kf, const int *__restrict__ obs_lm,
+                                                           const unsigned char *__restrict__ obs_flag, float2 *__restrict__ obs_px,
+                                                           uint4 *__restrict__ obs_desc, unsigned char *__restrict__ obs_hasdesc, int n,
+                                                           const int *__restrict__ kfid, const int *__restrict__ lmid,
+                                                           const float2 *__restrict__ px, const uint4 *__restrict__ desc,
+                                                           const unsigned char *__restrict__ has)
+{
+    __shared__ int sk[256], sl[256];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < n_obs && (obs_flag[i] & OBS_ALIVE);
+    const int k = live ? obs_kf[i] : -1, l = live ? obs_lm[i] : -1;
+    for (int base = 0; base < n; base += 256) {
+        const int m = min(256, n - base);
+        __syncthreads();
+        if ((int)threadIdx.x < m) { sk[threadIdx.x] = kfid[base + threadIdx.x]; sl[threadIdx.x] = lmid[base + threadIdx.x]; }
+        __syncthreads();
+        if (!live) continue;
+        for (int j = 0; j < m; ++j)
+            if (sl[j] == l && sk[j] == k) {
+                if (px) obs_px[i] = px[base + j];
+                obs_hasdesc[i] = has[base + j] ? 1 : 0;
+                if (has[base + j]) { obs_desc[2 * (size_t)i] = desc[2 * (size_t)(base + j)]; obs_desc[2 * (size_t)i + 1] = desc[2 * (size_t)(base + j) + 1]; }
+            }
+    }
+}
+
 // ---- batched set-up / update ---------------------------------------------------------------------------
 // Every kernel below serves B maps in one launch: the map is blockIdx.y, its tables and scratch arrays come from a
 // device table of map_job records (one H2D copy per call).  Sizes that a later kernel needs (poses, landmarks, residual
@@ -200,6 +233,21 @@ struct map_job {
     int *mg_cnt, *mg_fill, *mg_next, *mg_stamp, *mg_start, *mg_rows;
     unsigned char *mg_mark;
     int *obs_lm_w;                               // writable twin of obs_lm (the walk relabels rows)
+    // match columns: what the walk's conflict rule edits (null without the columns)
+    uint4 *obs_desc_w; unsigned char *obs_hasdesc_w; int *mg_srow;
+    // match gather (hdr / zero_blk point at the merge stage's block; mg_seg = entries of this map, 0: nothing to do)
+    int gt_on;                                   // 1: the mark kernel reads the two id lists below instead of the pairs
+    int gt_nkp, gt_ncand, gt_kp0, gt_cand0, gt_kf0;   // this map's keypoints / candidates and where they and its poses start in the flat arrays
+    const int *gt_kp_lmid, *gt_cand_lmid;        // this map's segments of the id lists
+    // flat scans of the gather (records behind the B maps): the array is scanned in place, the total lands behind it
+    int *gt_scan; int gt_scan_n;
+};
+
+// the flat arrays of a gather call (ov2_match_batch_input as the kernels write it) and their row capacity
+struct gather_out {
+    double *Twc; float2 *kp_px; int *kp_desc_ptr, *kp_kf_ptr, *kp_kfids; float2 *kp_kf_px; uint4 *kp_descs;
+    double *cand_wpt; int *cand_desc_ptr, *cand_kf_ptr, *cand_kfids; uint4 *cand_descs; double *kf_Twc;
+    int cap_rows;                                // entries kp_kfids / cand_kfids (and the descriptor arrays) can hold
 };
 
 // the flat problem of one map inside its output block: the same carve on the device (emitters, update stage) and on the
@@ -300,7 +348,7 @@ __global__ __launch_bounds__(256) void mc_mark_kernel(map_view M, snap_view S, i
     keep[i] = k ? 1 : 0;
 }
 
-struct obs_cols { int *kf, *lm, *scale; double *uv, *ruv; unsigned char *flag, *snap_flag; };
+struct obs_cols { int *kf, *lm, *scale; double *uv, *ruv; unsigned char *flag, *snap_flag; float *px; unsigned char *desc, *hasdesc; };
 
 __global__ __launch_bounds__(256) void mc_scatter_kernel(map_view M, const unsigned char *__restrict__ snap_flag, const int *__restrict__ keep,
                                                          const int *__restrict__ pos, obs_cols O)
@@ -312,6 +360,12 @@ __global__ __launch_bounds__(256) void mc_scatter_kernel(map_view M, const unsig
     if (snap_flag) O.snap_flag[j] = snap_flag[i];
     reinterpret_cast<double2 *>(O.uv)[j] = reinterpret_cast<const double2 *>(M.obs_uv)[i];
     reinterpret_cast<double2 *>(O.ruv)[j] = reinterpret_cast<const double2 *>(M.obs_ruv)[i];
+    if (M.obs_hasdesc) {   // the match columns travel with the row
+        reinterpret_cast<float2 *>(O.px)[j] = M.obs_px[i];
+        reinterpret_cast<uint4 *>(O.desc)[2 * (size_t)j] = M.obs_desc[2 * (size_t)i];
+        reinterpret_cast<uint4 *>(O.desc)[2 * (size_t)j + 1] = M.obs_desc[2 * (size_t)i + 1];
+        O.hasdesc[j] = M.obs_hasdesc[i];
+    }
 }
 
 // MapManager::updateFrameCovisibility (src/map_manager.cpp:117-193): co-observed landmarks per other keyframe
@@ -467,7 +521,8 @@ __global__ __launch_bounds__(256) void ms_res_count_kernel(const map_job *__rest
 // total -> NLM | NBAD), SC_RES the residual counts (total -> NRES), SC_LIVE the keep flags of a compaction (total -> NLIVE),
 // SC_KF the live rows per keyframe of the keyframe filter (total -> FH_ROWS of its header)
 // SC_MG the live rows per named landmark of the map-point merge (total -> GH_ROWS of its header)
-enum { SC_LM = 0, SC_RES, SC_LIVE, SC_KF, SC_MG };
+// SC_GT a flat count array of the match gather, in place (total -> the entry behind the array: the n + 1 prefix offsets)
+enum { SC_LM = 0, SC_RES, SC_LIVE, SC_KF, SC_MG, SC_GT };
 
 template <typename T>
 __device__ __forceinline__ T shfl_up_t(T v, int o)
@@ -493,6 +548,9 @@ __device__ __forceinline__ void scan_args(const map_job &j, int which, const T *
     } else if (which == SC_MG) {
         in = reinterpret_cast<const T *>(j.mg_cnt); out = reinterpret_cast<T *>(j.mg_start); n = j.mg_seg ? j.M.max_lm : 0;
         total = reinterpret_cast<T *>(j.hdr + GH_ROWS);
+    } else if (which == SC_GT) {
+        in = reinterpret_cast<const T *>(j.gt_scan); out = reinterpret_cast<T *>(j.gt_scan); n = j.gt_scan_n;
+        total = reinterpret_cast<T *>(j.gt_scan + j.gt_scan_n);
     } else {
         in = reinterpret_cast<const T *>(j.obs_cnt); out = reinterpret_cast<T *>(j.obs_off); n = j.M.n_obs;
         total = reinterpret_cast<T *>(j.hdr + (which == SC_RES ? MH_NRES : MH_NLIVE));
@@ -1086,6 +1144,12 @@ __global__ __launch_bounds__(256) void mg_mark_kernel(const map_job *__restrict_
 {
     const map_job &j = J[blockIdx.y];
     const int i = blockIdx.x * 256 + threadIdx.x;
+    if (j.gt_on) {   // the match gather names the landmarks of its keypoints and candidates; an id out of range names none
+        if (i >= j.gt_nkp + j.gt_ncand) return;
+        const int l = i < j.gt_nkp ? j.gt_kp_lmid[i] : j.gt_cand_lmid[i - j.gt_nkp];
+        if ((unsigned)l < (unsigned)j.M.max_lm) j.mg_mark[l] = 1;
+        return;
+    }
     if (i >= mg_npairs(j)) return;
     const int p = j.mg_prev[i], n = j.mg_new[i];
     if ((unsigned)p >= (unsigned)j.M.max_lm || (unsigned)n >= (unsigned)j.M.max_lm) return;   // the walk skips the pair
@@ -1151,7 +1215,10 @@ __global__ __launch_bounds__(MG_THREADS) void mg_walk_kernel(const map_job *__re
             const int cnt = j.mg_cnt[s];
             for (int t = tid; t < cnt; t += MG_THREADS) {
                 const int r = rows[t];
-                if (ld_int(j.obs_lm_w + r) == n) st_int(j.mg_stamp + M.obs_kf[r], i + 1);
+                if (ld_int(j.obs_lm_w + r) == n) {
+                    if (j.mg_srow) st_int(j.mg_srow + M.obs_kf[r], r);   // read only behind a matching stamp
+                    st_int(j.mg_stamp + M.obs_kf[r], i + 1);
+                }
             }
         }
         __syncthreads();
@@ -1162,8 +1229,21 @@ __global__ __launch_bounds__(MG_THREADS) void mg_walk_kernel(const map_job *__re
             for (int t = tid; t < cnt; t += MG_THREADS) {
                 const int r = rows[t];
                 if (ld_int(j.obs_lm_w + r) != p) continue;
-                if (ld_int(j.mg_stamp + M.obs_kf[r]) == i + 1) ++conflict;
-                else { st_int(j.obs_lm_w + r, n); ++moved; }
+                if (ld_int(j.mg_stamp + M.obs_kf[r]) == i + 1) {
+                    ++conflict;
+                    // MapPoint::addDesc(kfid, prev's descriptor) returns early where `new` has one for the keyframe
+                    // (src/map_manager.cpp:854-856, src/map_point.cpp:164-171): `new`'s row takes it only if it has none.  A
+                    // keyframe holds one live row of `prev`, so one lane writes a given row of `new`.
+                    if (j.obs_hasdesc_w && ld_u8(j.obs_hasdesc_w + r)) {
+                        const int r2 = ld_int(j.mg_srow + M.obs_kf[r]);
+                        if (!ld_u8(j.obs_hasdesc_w + r2)) {
+                            j.obs_desc_w[2 * (size_t)r2] = j.obs_desc_w[2 * (size_t)r];
+                            j.obs_desc_w[2 * (size_t)r2 + 1] = j.obs_desc_w[2 * (size_t)r + 1];
+                            __threadfence();   // the descriptor before its flag, for the lanes that read both for a later pair
+                            st_u8(j.obs_hasdesc_w + r2, 1);
+                        }
+                    }
+                } else { st_int(j.obs_lm_w + r, n); ++moved; }
             }
         }
         if (tid == 0) {
@@ -1184,6 +1264,128 @@ __global__ __launch_bounds__(MG_THREADS) void mg_walk_kernel(const map_job *__re
         int *H = j.hdr_out;
         for (int t = 0; t < MH_N; ++t) H[t] = 0;
         H[GH_PAIRS] = np; H[GH_MERGED] = nmerged; H[GH_SKIPPED] = nskipped; H[GH_MOVED] = moved; H[GH_CONFLICT] = conflict;
+    }
+}
+
+// ---- match gather: the flat input of Mapper::matchToMap (src/mapper.cpp:576-774) from the tables -------------------------------
+// The merge stage's mark / count / scan / index kernels group the live rows of the landmarks a call names -- here the
+// landmarks of the new keyframe's keypoints and of the candidates -- by landmark (mg_start / mg_cnt / mg_rows).  One entry
+// (keypoint or candidate) then belongs to a 16-lane quarter of a wave: a landmark has a row per observing keyframe, a dozen
+// on average, so a whole wave per entry would idle three quarters of its lanes.  The counting pass leaves the entry's
+// observer and descriptor counts where the prefix offsets go, a flat in-place scan over the WHOLE batch turns them into the
+// contiguous *_ptr arrays the matcher reads across frame boundaries, and the filling pass ranks the entry's rows by kfid
+// (MapPoint::set_kfids_ is a std::set: ascending; table order is not keyframe order once rows were appended late or
+// relabelled) and copies.  No LDS: the ranks come from 16-lane shuffles, the descriptors move as 16-byte halves, lane h of
+// the quarter taking half h of the chunk so that the quarter's stores are one contiguous run.
+#define GT_SUB 16
+
+// the quarter's 16 bits of a wave-wide vote
+__device__ __forceinline__ unsigned gt_vote(bool p) { return (unsigned)((__ballot(p) >> (threadIdx.x & 48)) & 0xffffull); }
+
+struct gt_entry { bool is_kp; int flat, lm, state, cnt; const int *rows; };
+
+// entry e of map j: its landmark, the landmark's state (0 = out of range) and its live rows (none for a dead landmark)
+__device__ __forceinline__ gt_entry gt_entry_of(const map_job &j, int e)
+{
+    gt_entry E;
+    E.is_kp = e < j.gt_nkp;
+    E.flat = E.is_kp ? j.gt_kp0 + e : j.gt_cand0 + (e - j.gt_nkp);
+    E.lm = E.is_kp ? j.gt_kp_lmid[e] : j.gt_cand_lmid[e - j.gt_nkp];
+    const bool inr = (unsigned)E.lm < (unsigned)j.M.max_lm;
+    E.state = inr ? j.M.lm_state[E.lm] : 0;
+    const bool alive = E.state & OV2_LM_ALIVE;
+    E.cnt = alive ? j.mg_cnt[E.lm] : 0;
+    E.rows = j.mg_rows + (alive ? j.mg_start[E.lm] : 0);
+    return E;
+}
+
+__global__ __launch_bounds__(256) void gt_count_kernel(const map_job *__restrict__ J, gather_out G)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int tid = threadIdx.x, sl = tid & (GT_SUB - 1);
+    // the map's pose table behind those of the maps before it (kfid indexes it), and the pose the candidates are projected with
+    for (size_t t = (size_t)blockIdx.x * 256 + tid; t < 7 * (size_t)M.max_kf; t += (size_t)gridDim.x * 256)
+        G.kf_Twc[7 * (size_t)j.gt_kf0 + t] = M.kf_pose[t];
+    if (blockIdx.x == 0 && tid < 7) G.Twc[7 * blockIdx.y + tid] = M.kf_pose[7 * (size_t)j.newkf + tid];
+    const int e = (blockIdx.x * 256 + tid) / GT_SUB;
+    if (e >= j.gt_nkp + j.gt_ncand) return;   // uniform per quarter
+    const gt_entry E = gt_entry_of(j, e);
+    int nd = 0; unsigned in_new = 0;
+    for (int t0 = 0; t0 < E.cnt; t0 += GT_SUB) {   // the trip count is uniform per quarter
+        const bool on = t0 + sl < E.cnt;
+        const int r = on ? E.rows[t0 + sl] : 0;
+        nd += __popc(gt_vote(on && M.obs_hasdesc[r]));
+        in_new |= gt_vote(on && M.obs_kf[r] == j.newkf);
+    }
+    // keypoint: map point present with descriptors (src/mapper.cpp:676-685); candidate: alive, 3-D, not observed by the new
+    // keyframe, with descriptors (:613-624).  Everything else gets two empty ranges.
+    const bool ok = nd > 0 && (E.is_kp || ((E.state & OV2_LM_3D) && !in_new));
+    if (sl == 0) {
+        (E.is_kp ? G.kp_kf_ptr : G.cand_kf_ptr)[E.flat] = ok ? E.cnt : 0;
+        (E.is_kp ? G.kp_desc_ptr : G.cand_desc_ptr)[E.flat] = ok ? nd : 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void gt_fill_kernel(const map_job *__restrict__ J, gather_out G)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int tid = threadIdx.x, sl = tid & (GT_SUB - 1);
+    const int e = (blockIdx.x * 256 + tid) / GT_SUB;
+    if (e >= j.gt_nkp + j.gt_ncand) return;   // uniform per quarter
+    const gt_entry E = gt_entry_of(j, e);
+    if (E.is_kp) {   // Keypoint::px_ of the new keyframe's own row; (0, 0) where the keyframe holds no live row of the landmark
+        unsigned found = 0;
+        for (int t0 = 0; t0 < E.cnt; t0 += GT_SUB) {
+            const bool on = t0 + sl < E.cnt;
+            const int r = on ? E.rows[t0 + sl] : 0;
+            const bool hit = on && M.obs_kf[r] == j.newkf;
+            if (hit) G.kp_px[E.flat] = M.obs_px[r];
+            found |= gt_vote(hit);
+        }
+        if (!found && sl == 0) G.kp_px[E.flat] = make_float2(0.f, 0.f);
+    } else if (sl < 3) {
+        G.cand_wpt[3 * (size_t)E.flat + sl] = (E.state & OV2_LM_ALIVE) ? M.lm_xyz[3 * (size_t)E.lm + sl] : 0.0;
+    }
+    const int *kf_ptr = E.is_kp ? G.kp_kf_ptr : G.cand_kf_ptr, *desc_ptr = E.is_kp ? G.kp_desc_ptr : G.cand_desc_ptr;
+    const int k0 = kf_ptr[E.flat], kn = kf_ptr[E.flat + 1] - k0, d0 = desc_ptr[E.flat];
+    // an accepted entry lists all its live rows (kn == cnt); distinct landmarks per list keep the total within the tables' rows
+    if (kn <= 0 || kn != E.cnt || k0 + kn > G.cap_rows) return;
+    int *kfids = E.is_kp ? G.kp_kfids : G.cand_kfids;
+    uint4 *descs = E.is_kp ? G.kp_descs : G.cand_descs;
+    int dbase = 0;
+    for (int t0 = 0; t0 < E.cnt; t0 += GT_SUB) {
+        const int t = t0 + sl;
+        const bool on = t < E.cnt;
+        const int r = on ? E.rows[t] : 0;
+        const int kf = on ? M.obs_kf[r] : 0x7fffffff;
+        int rank = 0;   // rows of the landmark with a smaller keyframe (equal ones, which one landmark never has, by their place)
+        for (int u0 = 0; u0 < E.cnt; u0 += GT_SUB) {
+            const int v = u0 + sl < E.cnt ? M.obs_kf[E.rows[u0 + sl]] : 0x7fffffff;
+#pragma unroll
+            for (int s = 0; s < GT_SUB; ++s) {
+                const int kv = __shfl(v, s, GT_SUB);
+                rank += (kv < kf || (kv == kf && u0 + s < t)) ? 1 : 0;
+            }
+        }
+        if (on) {
+            kfids[k0 + rank] = kf;
+            if (E.is_kp) G.kp_kf_px[k0 + rank] = M.obs_px[r];
+        }
+        // the described rows of the chunk, 32 bytes each: half h of the chunk's run goes through lane h (and h + 16)
+        const unsigned mask = gt_vote(on && M.obs_hasdesc[r]);
+        const int nh = 2 * __popc(mask);
+#pragma unroll
+        for (int h0 = 0; h0 < 2 * GT_SUB; h0 += GT_SUB) {
+            const int h = h0 + sl, q = h >> 1;
+            unsigned mm = mask;
+            for (int i = 0; i < q && mm; ++i) mm &= mm - 1;   // drop the q lowest described lanes
+            const int src = mm ? __ffs(mm) - 1 : 0;
+            const int rr = __shfl(r, src, GT_SUB);
+            if (h < nh) descs[2 * (size_t)(d0 + dbase + q) + (h & 1)] = M.obs_desc[2 * (size_t)rr + (h & 1)];
+        }
+        dbase += nh >> 1;
     }
 }
 
@@ -1332,6 +1534,8 @@ map_view view_of(const ov2_map *m)
     v.kf_pose = m->kf_pose; v.kf_state = m->kf_state; v.lm_xyz = m->lm_xyz; v.lm_state = m->lm_state;
     v.obs_kf = m->obs_kf; v.obs_lm = m->obs_lm; v.obs_scale = m->obs_scale; v.obs_uv = m->obs_uv; v.obs_ruv = m->obs_ruv;
     v.obs_flag = m->obs_flag;
+    v.obs_px = reinterpret_cast<const float2 *>(m->obs_px); v.obs_desc = reinterpret_cast<const uint4 *>(m->obs_desc);
+    v.obs_hasdesc = m->obs_hasdesc;
     return v;
 }
 
@@ -1353,6 +1557,7 @@ map_job job_of(const ov2_map *m, int newkf, int cur_kfid)
     j.snap_lm_state = m->snap_lm_state; j.snap_obs_flag = m->snap_obs_flag;
     j.snap_kf = m->snap_kf; j.snap_lm = m->snap_lm; j.snap_obs = m->snap_obs;
     j.obs_lm_w = m->obs_lm;
+    j.obs_desc_w = reinterpret_cast<uint4 *>(m->obs_desc); j.obs_hasdesc_w = m->obs_hasdesc; j.mg_srow = m->mg_srow;
     return j;
 }
 
@@ -1483,8 +1688,37 @@ static ov2_status alloc_tables(ov2_map *m)
     return s;
 }
 
+// the match columns at the current capacities (ov2_map_enable_match_columns, and every growth of a map that has them): no row
+// carries a descriptor, every pixel is 0; pointers must be null on entry
+static ov2_status alloc_match_columns(ov2_map *m)
+{
+    ov2_ctx *c = m->c;
+    ov2_status s = OV2_OK;
+    const size_t K = m->max_kf, L = m->max_lm, N = m->max_obs;
+    if (s == OV2_OK) s = dmalloc(c, &m->obs_px, 2 * N);
+    if (s == OV2_OK) s = dmalloc(c, &m->obs_desc, 32 * N);   // hipMalloc aligns far beyond the 16 bytes the lane copies need
+    if (s == OV2_OK) s = dmalloc(c, &m->obs_hasdesc, N);
+    if (s == OV2_OK) s = dmalloc(c, &m->mg_srow, K);
+    if (s == OV2_OK && !(m->gt_seen_h = (int *)calloc(std::max<size_t>(L, 1), sizeof(int))))
+        s = ov2_set_err(c, OV2_ERR_NOMEM, "map landmark list of %zu entries", L);
+    m->gt_gen = 0;
+    if (s != OV2_OK) return s;
+    OV2_HIP(c, hipMemsetAsync(m->obs_px, 0, 2 * std::max<size_t>(N, 1) * sizeof(float), c->stream));
+    OV2_HIP(c, hipMemsetAsync(m->obs_hasdesc, 0, std::max<size_t>(N, 1), c->stream));
+    return OV2_OK;
+}
+
+static void free_match_columns(ov2_map *m)
+{
+    void *dev[] = {m->obs_px, m->obs_desc, m->obs_hasdesc, m->mg_srow};
+    for (void *p : dev) if (p) (void)hipFree(p);
+    free(m->gt_seen_h);
+    m->obs_px = nullptr; m->obs_desc = m->obs_hasdesc = nullptr; m->mg_srow = nullptr; m->gt_seen_h = nullptr;
+}
+
 static void free_capacity_arrays(ov2_map *m)
 {
+    free_match_columns(m);
     void *dev[] = {m->kf_pose, m->kf_state, m->lm_xyz, m->lm_state, m->obs_kf, m->obs_lm, m->obs_scale, m->obs_uv, m->obs_ruv,
                    m->obs_flag, m->zero_blk, m->kf_idx, m->lm_flag, m->lm_pack, m->lm_pidx, m->obs_cnt, m->obs_off, m->blk,
                    m->tt_zero, m->tt_int, m->tt_dbl, m->fl_zero, m->fl_start, m->fl_rows, m->fl_unset,
@@ -1507,7 +1741,9 @@ static ov2_status ensure_capacity(ov2_map *m, int need_kf, int need_lm, int need
     m->tt_zero = nullptr; m->tt_int = nullptr; m->tt_dbl = nullptr;
     m->fl_zero = nullptr; m->fl_start = m->fl_rows = m->fl_unset = nullptr;
     m->mg_zero = nullptr; m->mg_start = m->mg_rows = nullptr;
+    m->obs_px = nullptr; m->obs_desc = m->obs_hasdesc = nullptr; m->mg_srow = nullptr; m->gt_seen_h = nullptr;
     ov2_status s = alloc_tables(m);
+    if (s == OV2_OK && old.obs_hasdesc) s = alloc_match_columns(m);   // a map that has the columns keeps them
     unsigned char *alive = s == OV2_OK ? (unsigned char *)calloc((size_t)m->max_kf, 1) : nullptr;
     if (s == OV2_OK && !alive) s = ov2_set_err(c, OV2_ERR_NOMEM, "map keyframe list of %d entries", m->max_kf);
     if (s != OV2_OK) {
@@ -1526,6 +1762,7 @@ static ov2_status ensure_capacity(ov2_map *m, int need_kf, int need_lm, int need
 #define CP(p, n) if ((n) > 0) OV2_HIP(c, hipMemcpyAsync(m->p, old.p, (n) * sizeof(*m->p), hipMemcpyDeviceToDevice, st))
     CP(kf_pose, 7 * K); CP(kf_state, K); CP(lm_xyz, 3 * L); CP(lm_state, L);
     CP(obs_kf, N); CP(obs_lm, N); CP(obs_scale, N); CP(obs_uv, 2 * N); CP(obs_ruv, 2 * N); CP(obs_flag, N);
+    if (old.obs_hasdesc) { CP(obs_px, 2 * N); CP(obs_desc, 32 * N); CP(obs_hasdesc, N); }
 #undef CP
     OV2_HIP(c, hipStreamSynchronize(st));
     free_capacity_arrays(&old);
@@ -1554,12 +1791,12 @@ static ov2_status compact_obs(ov2_map *m)
     if (N <= 0) return OV2_OK;
     // the fresh column arrays are released on every early return, kept once they have replaced the old ones
     struct fresh_cols {
-        obs_cols O = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        obs_cols O = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         bool committed = false;
         ~fresh_cols()
         {
             if (committed) return;
-            void *p[] = {O.kf, O.lm, O.scale, O.uv, O.ruv, O.flag, O.snap_flag};
+            void *p[] = {O.kf, O.lm, O.scale, O.uv, O.ruv, O.flag, O.snap_flag, O.px, O.desc, O.hasdesc};
             for (void *q : p) if (q) (void)hipFree(q);
         }
     } F;
@@ -1571,6 +1808,7 @@ static ov2_status compact_obs(ov2_map *m)
     // a saved state of exactly these rows and capacities (the only one ov2_map_restore_state_batch accepts) survives
     const bool keep_snap = m->snap_kf_pose && m->snap_obs_flag && m->snap_obs == N && m->snap_kf == m->max_kf && m->snap_lm == m->max_lm;
     if (keep_snap) A(snap_flag, (size_t)N);
+    if (m->obs_hasdesc) { A(px, 2 * cap); A(desc, 32 * cap); A(hasdesc, cap); }
 #undef A
     if (s != OV2_OK) return s;
     const map_view M = view_of(m);
@@ -1581,6 +1819,10 @@ static ov2_status compact_obs(ov2_map *m)
     JT.set(0, job_of(m, -1, -1));
     if ((s = JT.upload()) != OV2_OK) return s;
     OV2_HIP(c, hipMemsetAsync(O.flag, 0, cap, st));
+    if (O.hasdesc) {   // rows beyond the squeezed ones: as ov2_map_enable_match_columns leaves them
+        OV2_HIP(c, hipMemsetAsync(O.hasdesc, 0, cap, st));
+        OV2_HIP(c, hipMemsetAsync(O.px, 0, 2 * cap * sizeof(float), st));
+    }
     OV2_LAUNCH(c, OV2_K_MAP, mc_mark_kernel, g, b, 0, st, M, SV, m->obs_cnt);
     if ((s = exclusive_scan<int>(c, JT, SC_LIVE, N)) != OV2_OK) return s;
     OV2_LAUNCH(c, OV2_K_MAP, mc_scatter_kernel, g, b, 0, st, M, SV.obs_flag, (const int *)m->obs_cnt, (const int *)m->obs_off, O);
@@ -1589,6 +1831,11 @@ static ov2_status compact_obs(ov2_map *m)
     void *old[] = {m->obs_kf, m->obs_lm, m->obs_scale, m->obs_uv, m->obs_ruv, m->obs_flag};
     for (void *p : old) (void)hipFree(p);
     m->obs_kf = O.kf; m->obs_lm = O.lm; m->obs_scale = O.scale; m->obs_uv = O.uv; m->obs_ruv = O.ruv; m->obs_flag = O.flag;
+    if (O.hasdesc) {
+        void *oldc[] = {m->obs_px, m->obs_desc, m->obs_hasdesc};
+        for (void *p : oldc) (void)hipFree(p);
+        m->obs_px = O.px; m->obs_desc = O.desc; m->obs_hasdesc = O.hasdesc;
+    }
     F.committed = true;
     m->n_obs = m->hdr_host[MH_NLIVE];
     m->n_compactions++;
@@ -1682,11 +1929,23 @@ extern "C" void ov2_map_destroy(ov2_map *m)
     delete m;
 }
 
-extern "C" ov2_status ov2_map_add_keyframe(ov2_map *m, int kfid, const double *Twc, int n, const int32_t *lmid,
-                                           const double *unpx, const double *runpx, const uint8_t *is_stereo,
-                                           const int32_t *scale)
+extern "C" ov2_status ov2_map_enable_match_columns(ov2_map *m)
 {
     if (!m || !m->c) return OV2_ERR_INVALID;
+    if (m->obs_hasdesc) return OV2_OK;
+    ov2_ctx *c = m->c;
+    OV2_HIP(c, hipSetDevice(c->device));
+    const ov2_status s = alloc_match_columns(m);
+    if (s != OV2_OK) { free_match_columns(m); return s; }
+    OV2_HIP(c, hipStreamSynchronize(c->stream));
+    return OV2_OK;
+}
+
+// px (n x 2 floats) / desc (n x 32) / has_desc (n) are read on a map with the match columns only; null there = pixel 0 / no descriptor
+static ov2_status add_keyframe_impl(ov2_map *m, int kfid, const double *Twc, int n, const int32_t *lmid, const double *unpx,
+                                    const double *runpx, const uint8_t *is_stereo, const int32_t *scale, const float *px,
+                                    const uint8_t *desc, const uint8_t *has_desc)
+{
     ov2_ctx *c = m->c;
     if (!Twc || n < 0 || (n && (!lmid || !unpx))) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_add_keyframe: null argument");
     if (kfid < 0) return ov2_set_err(c, OV2_ERR_INVALID, "negative kfid %d", kfid);
@@ -1702,11 +1961,15 @@ extern "C" ov2_status ov2_map_add_keyframe(ov2_map *m, int kfid, const double *T
     }
     // the rows are appended as they are: assemble them in the staging block, then plain copies into the tables
     stager S{c};
-    ov2_status s = S.begin((size_t)n * (3 * sizeof(int) + 4 * sizeof(double) + 1) + 7 * sizeof(double) + 256);
+    const bool cols = m->obs_hasdesc != nullptr;
+    if (!(desc && has_desc)) desc = has_desc = nullptr;
+    ov2_status s = S.begin((size_t)n * (3 * sizeof(int) + 4 * sizeof(double) + 1 + (cols ? 2 * sizeof(float) + 33 : 0)) + 7 * sizeof(double) + 512);
     if (s != OV2_OK) return s;
     const double *dT = S.put(Twc, 7);
     const int *dl = S.put(lmid, n);
     const double *du = S.put(unpx, 2 * (size_t)n);
+    const float *dpx = cols ? S.put(px, 2 * (size_t)n) : nullptr;
+    const uint8_t *ddesc = cols ? S.put(desc, 32 * (size_t)n) : nullptr, *dhas = cols ? S.put(has_desc, (size_t)n) : nullptr;
     // derived columns are built in place in the pinned block
     S.off = (S.off + 15) & ~(size_t)15;
     int *hk = reinterpret_cast<int *>(S.h + S.off); const int *dk = reinterpret_cast<const int *>(S.d + S.off); S.off += sizeof(int) * n;
@@ -1735,11 +1998,37 @@ extern "C" ov2_status ov2_map_add_keyframe(ov2_map *m, int kfid, const double *T
         OV2_HIP(c, hipMemcpyAsync(m->obs_scale + o, ds, sizeof(int) * n, hipMemcpyDeviceToDevice, st));
         OV2_HIP(c, hipMemcpyAsync(m->obs_ruv + 2 * o, dr, sizeof(double) * 2 * n, hipMemcpyDeviceToDevice, st));
         OV2_HIP(c, hipMemcpyAsync(m->obs_flag + o, df, n, hipMemcpyDeviceToDevice, st));
+        if (cols) {   // the slots may have held rows that a squeeze moved away
+            if (dpx) OV2_HIP(c, hipMemcpyAsync(m->obs_px + 2 * o, dpx, sizeof(float) * 2 * n, hipMemcpyDeviceToDevice, st));
+            else OV2_HIP(c, hipMemsetAsync(m->obs_px + 2 * o, 0, sizeof(float) * 2 * n, st));
+            if (ddesc) {
+                OV2_HIP(c, hipMemcpyAsync(m->obs_desc + 32 * o, ddesc, 32 * (size_t)n, hipMemcpyDeviceToDevice, st));
+                OV2_HIP(c, hipMemcpyAsync(m->obs_hasdesc + o, dhas, n, hipMemcpyDeviceToDevice, st));
+            } else OV2_HIP(c, hipMemsetAsync(m->obs_hasdesc + o, 0, n, st));
+        }
     }
     m->n_obs += n;
     m->kf_alive_h[kfid] = 1;
     OV2_HIP(c, hipStreamSynchronize(st));   // the staging block is free again
     return OV2_OK;
+}
+
+extern "C" ov2_status ov2_map_add_keyframe(ov2_map *m, int kfid, const double *Twc, int n, const int32_t *lmid,
+                                           const double *unpx, const double *runpx, const uint8_t *is_stereo,
+                                           const int32_t *scale)
+{
+    if (!m || !m->c) return OV2_ERR_INVALID;
+    return add_keyframe_impl(m, kfid, Twc, n, lmid, unpx, runpx, is_stereo, scale, nullptr, nullptr, nullptr);
+}
+
+extern "C" ov2_status ov2_map_add_keyframe_px(ov2_map *m, int kfid, const double *Twc, int n, const int32_t *lmid,
+                                              const double *unpx, const double *runpx, const uint8_t *is_stereo,
+                                              const int32_t *scale, const float *px, const uint8_t *desc, const uint8_t *has_desc)
+{
+    if (!m || !m->c) return OV2_ERR_INVALID;
+    if (!m->obs_hasdesc) return ov2_set_err(m->c, OV2_ERR_INVALID, "ov2_map_add_keyframe_px: the map has no match columns");
+    if (n > 0 && !px) return ov2_set_err(m->c, OV2_ERR_INVALID, "ov2_map_add_keyframe_px: null pixels");
+    return add_keyframe_impl(m, kfid, Twc, n, lmid, unpx, runpx, is_stereo, scale, px, desc, has_desc);
 }
 
 extern "C" ov2_status ov2_map_set_landmarks(ov2_map *m, int n, const int32_t *lmid, const double *xyz, const uint8_t *state)
@@ -1823,6 +2112,31 @@ extern "C" ov2_status ov2_map_set_obs_stereo(ov2_map *m, int n, const int32_t *k
     if (n < 0 || (n && (!kfid || !lmid || !is_stereo || !runpx)))
         return ov2_set_err(m->c, OV2_ERR_INVALID, "ov2_map_set_obs_stereo: null argument");
     return edit_obs(m, n, kfid, lmid, 1, is_stereo, runpx);
+}
+
+extern "C" ov2_status ov2_map_set_obs_desc(ov2_map *m, int n, const int32_t *kfid, const int32_t *lmid, const float *px,
+                                           const uint8_t *desc, const uint8_t *has_desc)
+{
+    if (!m || !m->c) return OV2_ERR_INVALID;
+    ov2_ctx *c = m->c;
+    if (!m->obs_hasdesc) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_set_obs_desc: the map has no match columns");
+    if (n < 0 || (n && (!kfid || !lmid || !desc || !has_desc))) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_set_obs_desc: null argument");
+    if (!n || !m->n_obs) return OV2_OK;
+    OV2_HIP(c, hipSetDevice(c->device));
+    stager S{c};
+    ov2_status s = S.begin((size_t)n * (2 * sizeof(int) + 2 * sizeof(float) + 33) + 256);
+    if (s != OV2_OK) return s;
+    const int *dk = S.put(kfid, n);
+    const int *dl = S.put(lmid, n);
+    const float *dp = S.put(px, 2 * (size_t)n);
+    const uint8_t *dd = S.put(desc, 32 * (size_t)n), *dh = S.put(has_desc, (size_t)n);
+    if ((s = S.flush()) != OV2_OK) return s;
+    OV2_LAUNCH(c, OV2_K_MAP, map_set_desc_kernel, dim3((m->n_obs + 255) / 256), dim3(256), 0, c->stream, m->n_obs, (const int *)m->obs_kf,
+               (const int *)m->obs_lm, (const unsigned char *)m->obs_flag, reinterpret_cast<float2 *>(m->obs_px),
+               reinterpret_cast<uint4 *>(m->obs_desc), m->obs_hasdesc, n, dk, dl, reinterpret_cast<const float2 *>(dp),
+               reinterpret_cast<const uint4 *>(dd), dh);
+    OV2_HIP(c, hipStreamSynchronize(c->stream));
+    return OV2_OK;
 }
 
 extern "C" ov2_status ov2_map_remove_landmarks(ov2_map *m, int n, const int32_t *lmid)
@@ -2403,6 +2717,268 @@ extern "C" ov2_status ov2_map_merge_points_batch_dev(ov2_ctx *c, int B, ov2_map 
                             d_pair_status);
 }
 
+// ---- local-map matching from the mirrors: gather (twelve launches whatever B and the list lengths are: clear, mark, count,
+// three of the per-map scan, index, entry counts + poses, three of the flat scan, fill), then the matcher's own path --------
+namespace {
+
+struct gather_args {
+    int B; ov2_map *const *maps; const int32_t *newkf, *nb3dkps, *kp_off, *kp_lmid, *grid_ptr, *grid_kp, *cand_off, *cand_lmid;
+    const double *K; int img_w, img_h, cell; const ov2_cam_model *cam;
+};
+
+// what a call leaves in the ctx scratch behind the gathered arrays: the matcher's work array and the results
+struct gather_extra { uint64_t *work; int32_t *match_cand; float *match_dist; int32_t *prev_lmid, *new_lmid, *n_pairs; };
+
+// nothing_to_do: B == 0 or no keypoint at all (OV2_OK, nothing enqueued, *in describes the empty call)
+ov2_status gather_impl(ov2_ctx *c, const char *who, const gather_args &A, ov2_match_batch_input *in, const int32_t **d_kp_lmid,
+                       const int32_t **d_cand_lmid, gather_extra *X, size_t result_host_bytes, unsigned char **result_host,
+                       bool *nothing_to_do)
+{
+    *nothing_to_do = true;
+    if (!c) return OV2_ERR_INVALID;
+    if (!in) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null output", who);
+    memset(in, 0, sizeof(*in));
+    const int B = A.B;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !A.maps || !A.newkf || !A.nb3dkps || !A.kp_off || !A.cand_off || !A.K)
+        return ov2_set_err(c, OV2_ERR_INVALID, "%s: null argument", who);
+    if (A.kp_off[0] != 0 || A.cand_off[0] != 0) return ov2_set_err(c, OV2_ERR_INVALID, "%s: offsets must start at 0", who);
+    ov2_status s;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = A.maps[b];
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
+        if ((s = batch_map_once(c, A.maps, b)) != OV2_OK) return s;
+        if (!m->obs_hasdesc) return ov2_set_err(c, OV2_ERR_INVALID, "%s: map %d has no match columns", who, b);
+        if ((s = batch_kf_alive(c, m, A.newkf[b], b)) != OV2_OK) return s;
+        if (A.kp_off[b + 1] < A.kp_off[b] || A.cand_off[b + 1] < A.cand_off[b])
+            return ov2_set_err(c, OV2_ERR_INVALID, "%s: frame %d has a negative count", who, b);
+    }
+    const int nkp = A.kp_off[B], nc = A.cand_off[B];
+    if ((nkp && !A.kp_lmid) || (nc && !A.cand_lmid)) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null id list", who);
+    if (A.cell <= 0 || A.img_w <= 0 || A.img_h <= 0) return ov2_set_err(c, OV2_ERR_INVALID, "%s: bad image / cell size", who);
+    const int nbw = (int)ceilf((float)A.img_w / (float)A.cell), nbh = (int)ceilf((float)A.img_h / (float)A.cell);
+    const size_t ncells = (size_t)nbw * nbh, ng_ptr = (size_t)B * ncells + 1;
+    size_t n_g = 0;
+    if (nkp && nc) {   // the grid is read by the matcher only
+        if (!A.grid_ptr) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null grid", who);
+        if (A.grid_ptr[0] != 0) return ov2_set_err(c, OV2_ERR_INVALID, "%s: grid_ptr must start at 0", who);
+        for (size_t i = 0; i + 1 < ng_ptr; ++i)
+            if (A.grid_ptr[i + 1] < A.grid_ptr[i]) return ov2_set_err(c, OV2_ERR_INVALID, "%s: grid_ptr decreases", who);
+        n_g = (size_t)A.grid_ptr[ng_ptr - 1];
+        if (n_g && !A.grid_kp) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null grid", who);
+        for (int b = 0; b < B; ++b) {
+            const int nb = A.kp_off[b + 1] - A.kp_off[b];
+            for (int g = A.grid_ptr[(size_t)b * ncells]; g < A.grid_ptr[(size_t)(b + 1) * ncells]; ++g)
+                if (A.grid_kp[g] < 0 || A.grid_kp[g] >= nb)
+                    return ov2_set_err(c, OV2_ERR_INVALID, "%s: grid entry %d of frame %d outside its %d keypoints", who, A.grid_kp[g], b, nb);
+        }
+    }
+    // a landmark at most once per list (the reference's lists are keyed by lmid): that bounds the gathered rows by the tables'
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = A.maps[b];
+        for (int pass = 0; pass < 2; ++pass) {
+            const int32_t *ids = pass ? A.cand_lmid : A.kp_lmid;
+            const int i0 = pass ? A.cand_off[b] : A.kp_off[b], i1 = pass ? A.cand_off[b + 1] : A.kp_off[b + 1];
+            if (m->gt_gen == 0x7fffffff) { memset(m->gt_seen_h, 0, (size_t)m->max_lm * sizeof(int)); m->gt_gen = 0; }
+            const int gen = ++m->gt_gen;
+            for (int i = i0; i < i1; ++i) {
+                const int l = ids[i];
+                if (l < 0 || l >= m->max_lm) continue;
+                if (m->gt_seen_h[l] == gen)
+                    return ov2_set_err(c, OV2_ERR_INVALID, "%s: landmark %d twice among the %s of frame %d", who, l, pass ? "candidates" : "keypoints", b);
+                m->gt_seen_h[l] = gen;
+            }
+        }
+    }
+    in->B = B; in->n_kp = nkp; in->n_cand = nc; in->img_w = A.img_w; in->img_h = A.img_h; in->cell = A.cell; in->cam = A.cam;
+    for (int i = 0; i < 4; ++i) in->K[i] = A.K[i];
+    if (nkp == 0) return OV2_OK;
+    *nothing_to_do = false;
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    // the id lists behind the job records: one pinned image, one upload
+    enum { T_NB3D = 0, T_KPOFF, T_CANDOFF, T_KFOFF, T_KPLM, T_CANDLM, T_GPTR, T_GKP, T_N };
+    const size_t t_bytes[T_N] = {(size_t)B * 4, ((size_t)B + 1) * 4, ((size_t)B + 1) * 4, ((size_t)B + 1) * 4, (size_t)nkp * 4, (size_t)nc * 4,
+                                 (nkp && nc) ? ng_ptr * 4 : 0, n_g * 4};
+    size_t t_off[T_N], tail = 0;
+    for (int i = 0; i < T_N; ++i) { t_off[i] = tail; tail += pad(t_bytes[i]); }
+    job_table JT;
+    if ((s = JT.begin(c, B + 4, 0, tail + pad(result_host_bytes))) != OV2_OK) return s;
+    JT.tail_bytes = tail;   // what goes up; the rest of the block takes the results on their way back
+    if (result_host) *result_host = JT.tail_host + tail;
+    // the gathered arrays, sized from what the host knows: an entry lists at most the live rows of its landmark
+    size_t rows = 0, kfs = 0;
+    for (int b = 0; b < B; ++b) { rows += (size_t)A.maps[b]->n_obs; kfs += (size_t)A.maps[b]->max_kf; }
+    if (rows > 0x7fffffff / 2 || kfs > 0x7fffffff / 8) return ov2_set_err(c, OV2_ERR_INVALID, "%s: the batch holds too many rows", who);
+    enum { G_TWC = 0, G_KPPX, G_KPDPTR, G_KPKPTR, G_KPKF, G_KPKFPX, G_KPDESC, G_CWPT, G_CDPTR, G_CKPTR, G_CKF, G_CDESC, G_KFTWC,
+           G_BLK0, G_BLK1, G_BLK2, G_BLK3, G_WORK, G_MC, G_MD, G_PREV, G_NEW, G_NP, G_N };
+    const size_t blk_kp = ((size_t)nkp + 1023) / 1024 + 1, blk_c = ((size_t)nc + 1023) / 1024 + 1;
+    const size_t g_bytes[G_N] = {(size_t)B * 56, (size_t)nkp * 8, ((size_t)nkp + 1) * 4, ((size_t)nkp + 1) * 4, rows * 4, rows * 8, rows * 32,
+                                 (size_t)nc * 24, ((size_t)nc + 1) * 4, ((size_t)nc + 1) * 4, rows * 4, rows * 32, kfs * 56,
+                                 blk_kp * 4, blk_kp * 4, blk_c * 4, blk_c * 4,
+                                 X ? (size_t)nkp * 8 : 0, X ? (size_t)nkp * 4 : 0, X ? (size_t)nkp * 4 : 0, X ? (size_t)nkp * 4 : 0,
+                                 X ? (size_t)nkp * 4 : 0, X ? (size_t)B * 4 : 0};
+    size_t g_off[G_N], total = pad(JT.tail_off + tail);
+    for (int i = 0; i < G_N; ++i) { g_off[i] = total; total += pad(g_bytes[i]); }
+    void *scr = nullptr;
+    if ((s = ov2_scratch(c, total, &scr)) != OV2_OK) return s;
+    unsigned char *D = (unsigned char *)scr;
+    // the job records and the id lists go to the scratch block, not to the staging block's device twin: what the call hands
+    // out must outlive the next call that stages
+    JT.hdr_dev = (int *)(D + ((unsigned char *)JT.hdr_host - (unsigned char *)JT.host));
+    JT.dev = (const map_job *)D; JT.tail_dev = D + JT.tail_off;
+    auto tail_put = [&](int k, const void *src) { if (t_bytes[k] && src) memcpy(JT.tail_host + t_off[k], src, t_bytes[k]); };
+    tail_put(T_NB3D, A.nb3dkps); tail_put(T_KPOFF, A.kp_off); tail_put(T_CANDOFF, A.cand_off); tail_put(T_KPLM, A.kp_lmid);
+    tail_put(T_CANDLM, A.cand_lmid); tail_put(T_GPTR, A.grid_ptr); tail_put(T_GKP, A.grid_kp);
+    int32_t *kf_off_h = (int32_t *)(JT.tail_host + t_off[T_KFOFF]);
+    kf_off_h[0] = 0;
+    for (int b = 0; b < B; ++b) kf_off_h[b + 1] = kf_off_h[b] + A.maps[b]->max_kf;
+    gather_out G;
+    G.Twc = (double *)(D + g_off[G_TWC]); G.kp_px = (float2 *)(D + g_off[G_KPPX]); G.kp_desc_ptr = (int *)(D + g_off[G_KPDPTR]);
+    G.kp_kf_ptr = (int *)(D + g_off[G_KPKPTR]); G.kp_kfids = (int *)(D + g_off[G_KPKF]); G.kp_kf_px = (float2 *)(D + g_off[G_KPKFPX]);
+    G.kp_descs = (uint4 *)(D + g_off[G_KPDESC]); G.cand_wpt = (double *)(D + g_off[G_CWPT]); G.cand_desc_ptr = (int *)(D + g_off[G_CDPTR]);
+    G.cand_kf_ptr = (int *)(D + g_off[G_CKPTR]); G.cand_kfids = (int *)(D + g_off[G_CKF]); G.cand_descs = (uint4 *)(D + g_off[G_CDESC]);
+    G.kf_Twc = (double *)(D + g_off[G_KFTWC]); G.cap_rows = (int)rows;
+    const int32_t *dkp = (const int32_t *)(JT.tail_dev + t_off[T_KPLM]), *dcand = (const int32_t *)(JT.tail_dev + t_off[T_CANDLM]);
+    int nmax = 0, lmax = 0, emax = 0; unsigned zmax = 0;
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = A.maps[b];
+        map_job j = job_of(m, A.newkf[b], -1);
+        j.gt_on = 1;
+        j.gt_nkp = A.kp_off[b + 1] - A.kp_off[b]; j.gt_ncand = A.cand_off[b + 1] - A.cand_off[b];
+        j.gt_kp0 = A.kp_off[b]; j.gt_cand0 = A.cand_off[b]; j.gt_kf0 = kf_off_h[b];
+        j.gt_kp_lmid = dkp + A.kp_off[b]; j.gt_cand_lmid = dcand + A.cand_off[b];
+        j.mg_seg = j.gt_nkp + j.gt_ncand;
+        stage_block(j, m->mg_zero, j.mg_seg ? m->mg_zero_bytes : 0);
+        j.mg_cnt = m->mg_cnt; j.mg_fill = m->mg_fill; j.mg_next = m->mg_next; j.mg_stamp = m->mg_stamp; j.mg_mark = m->mg_mark;
+        j.mg_start = m->mg_start; j.mg_rows = m->mg_rows;
+        JT.set(b, j);
+        nmax = std::max(nmax, m->n_obs); lmax = std::max(lmax, m->max_lm); emax = std::max(emax, j.mg_seg); zmax = std::max(zmax, j.zero_vec16);
+    }
+    int *scan_arr[4] = {G.kp_kf_ptr, G.kp_desc_ptr, G.cand_kf_ptr, G.cand_desc_ptr};
+    for (int q = 0; q < 4; ++q) {   // the flat scans: four records behind the maps'
+        map_job j;
+        memset(&j, 0, sizeof(j));
+        j.gt_scan = scan_arr[q]; j.gt_scan_n = q < 2 ? nkp : nc;
+        j.blk = D + g_off[G_BLK0 + q];
+        JT.set(B + q, j);
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    job_table MJ = JT, SJ = JT;
+    MJ.B = B; SJ.B = 4; SJ.dev = JT.dev + B;
+    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), gE((std::max(emax, 1) + 255) / 256, B), b256(256);
+    const dim3 gQ(((size_t)std::max(emax, 1) * GT_SUB + 255) / 256, B);
+    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::max(1u, std::min(64u, (zmax + 255) / 256)), B), b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mg_mark_kernel, gE, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mg_count_kernel, gN, b256, 0, st, JT.dev);
+    if ((s = exclusive_scan<int>(c, MJ, SC_MG, lmax)) != OV2_OK) return s;
+    OV2_LAUNCH(c, OV2_K_MAP, mg_index_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, gt_count_kernel, gQ, b256, 0, st, JT.dev, G);
+    if ((s = exclusive_scan<int>(c, SJ, SC_GT, std::max(nkp, std::max(nc, 1)))) != OV2_OK) return s;
+    OV2_LAUNCH(c, OV2_K_MAP, gt_fill_kernel, gQ, b256, 0, st, JT.dev, G);
+    OV2_HIP(c, hipGetLastError());
+    in->Twc = G.Twc; in->nb3dkps = (const int32_t *)(JT.tail_dev + t_off[T_NB3D]);
+    in->kp_off = (const int32_t *)(JT.tail_dev + t_off[T_KPOFF]); in->cand_off = (const int32_t *)(JT.tail_dev + t_off[T_CANDOFF]);
+    in->kf_off = (const int32_t *)(JT.tail_dev + t_off[T_KFOFF]);
+    in->kp_px = (const float *)G.kp_px; in->kp_desc_ptr = G.kp_desc_ptr; in->kp_descs = (const uint8_t *)G.kp_descs;
+    in->kp_kf_ptr = G.kp_kf_ptr; in->kp_kfids = G.kp_kfids; in->kp_kf_px = (const float *)G.kp_kf_px;
+    in->grid_ptr = (const int32_t *)(JT.tail_dev + t_off[T_GPTR]); in->grid_kp = (const int32_t *)(JT.tail_dev + t_off[T_GKP]);
+    in->cand_wpt = G.cand_wpt; in->cand_desc_ptr = G.cand_desc_ptr; in->cand_descs = (const uint8_t *)G.cand_descs;
+    in->cand_kf_ptr = G.cand_kf_ptr; in->cand_kfids = G.cand_kfids; in->kf_Twc = G.kf_Twc;
+    if (d_kp_lmid) *d_kp_lmid = dkp;
+    if (d_cand_lmid) *d_cand_lmid = dcand;
+    if (X) {
+        X->work = (uint64_t *)(D + g_off[G_WORK]); X->match_cand = (int32_t *)(D + g_off[G_MC]); X->match_dist = (float *)(D + g_off[G_MD]);
+        X->prev_lmid = (int32_t *)(D + g_off[G_PREV]); X->new_lmid = (int32_t *)(D + g_off[G_NEW]); X->n_pairs = (int32_t *)(D + g_off[G_NP]);
+    }
+    return OV2_OK;
+}
+
+gather_args gather_args_of(int B, ov2_map *const *maps, const int32_t *newkf, const int32_t *nb3dkps, const int32_t *kp_off,
+                           const int32_t *kp_lmid, const int32_t *grid_ptr, const int32_t *grid_kp, const int32_t *cand_off,
+                           const int32_t *cand_lmid, const double *K, int img_w, int img_h, int cell, const ov2_cam_model *cam)
+{
+    return gather_args{B, maps, newkf, nb3dkps, kp_off, kp_lmid, grid_ptr, grid_kp, cand_off, cand_lmid, K, img_w, img_h, cell, cam};
+}
+
+}  // namespace
+
+extern "C" ov2_status ov2_map_match_gather_batch_dev(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf, const int32_t *nb3dkps,
+                                                     const int32_t *kp_off, const int32_t *kp_lmid, const int32_t *grid_ptr,
+                                                     const int32_t *grid_kp, const int32_t *cand_off, const int32_t *cand_lmid,
+                                                     const double *K, int img_w, int img_h, int cell, const ov2_cam_model *cam,
+                                                     ov2_match_batch_input *out, const int32_t **d_kp_lmid, const int32_t **d_cand_lmid)
+{
+    bool nothing;
+    if (d_kp_lmid) *d_kp_lmid = nullptr;
+    if (d_cand_lmid) *d_cand_lmid = nullptr;
+    return gather_impl(c, "ov2_map_match_gather_batch_dev",
+                       gather_args_of(B, maps, newkf, nb3dkps, kp_off, kp_lmid, grid_ptr, grid_kp, cand_off, cand_lmid, K, img_w, img_h, cell, cam),
+                       out, d_kp_lmid, d_cand_lmid, nullptr, 0, nullptr, &nothing);
+}
+
+extern "C" ov2_status ov2_map_match_local_batch_dev(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf, const int32_t *nb3dkps,
+                                                    const int32_t *kp_off, const int32_t *kp_lmid, const int32_t *grid_ptr,
+                                                    const int32_t *grid_kp, const int32_t *cand_off, const int32_t *cand_lmid,
+                                                    const double *K, int img_w, int img_h, int cell, const ov2_cam_model *cam,
+                                                    float fmaxprojerr, float fdistratio, int pairs, ov2_map_match_local *out)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (!out) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_match_local_batch_dev: null output");
+    memset(out, 0, sizeof(*out));
+    ov2_match_batch_input in;
+    gather_extra X;
+    const int32_t *dkp = nullptr, *dcand = nullptr;
+    bool nothing;
+    ov2_status s = gather_impl(c, "ov2_map_match_local_batch_dev",
+                               gather_args_of(B, maps, newkf, nb3dkps, kp_off, kp_lmid, grid_ptr, grid_kp, cand_off, cand_lmid, K, img_w, img_h, cell, cam),
+                               &in, &dkp, &dcand, &X, 0, nullptr, &nothing);
+    if (s != OV2_OK || nothing) return s;
+    if ((s = ov2_match_to_map_batch_dev(c, &in, fmaxprojerr, fdistratio, X.work, X.match_cand, X.match_dist)) != OV2_OK) return s;
+    out->d_kp_off = in.kp_off; out->d_cand_off = in.cand_off; out->d_kp_lmid = dkp; out->d_cand_lmid = dcand;
+    out->d_match_cand = X.match_cand; out->d_match_dist = X.match_dist;
+    if (pairs) {
+        if ((s = ov2_match_pairs_dev(c, B, in.n_kp, in.kp_off, in.cand_off, dkp, dcand, X.match_cand, X.prev_lmid, X.new_lmid, X.n_pairs)) != OV2_OK)
+            return s;
+        out->d_prev_lmid = X.prev_lmid; out->d_new_lmid = X.new_lmid; out->d_n_pairs = X.n_pairs;
+    }
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_map_match_local_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf, const int32_t *nb3dkps,
+                                                const int32_t *kp_off, const int32_t *kp_lmid, const int32_t *grid_ptr,
+                                                const int32_t *grid_kp, const int32_t *cand_off, const int32_t *cand_lmid,
+                                                const double *K, int img_w, int img_h, int cell, const ov2_cam_model *cam,
+                                                float fmaxprojerr, float fdistratio, int32_t *match_lmid, float *match_dist)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B > 0 && kp_off && kp_off[0] == 0 && kp_off[B] > 0 && (!match_lmid || !match_dist))
+        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_match_local_batch: null output");
+    ov2_match_batch_input in;
+    gather_extra X;
+    bool nothing;
+    unsigned char *res = nullptr;
+    const size_t res_bytes = (B > 0 && kp_off && kp_off[B] > 0) ? 2 * (((size_t)kp_off[B] * 4 + 255) & ~(size_t)255) : 0;
+    ov2_status s = gather_impl(c, "ov2_map_match_local_batch",
+                               gather_args_of(B, maps, newkf, nb3dkps, kp_off, kp_lmid, grid_ptr, grid_kp, cand_off, cand_lmid, K, img_w, img_h, cell, cam),
+                               &in, nullptr, nullptr, &X, res_bytes, &res, &nothing);
+    if (s != OV2_OK || nothing) return s;
+    if ((s = ov2_match_to_map_batch_dev(c, &in, fmaxprojerr, fdistratio, X.work, X.match_cand, X.match_dist)) != OV2_OK) return s;
+    // match_cand and match_dist lie behind each other in the scratch block (each padded to 256 bytes): one download
+    const size_t n = (size_t)in.n_kp, stride = (n * 4 + 255) & ~(size_t)255;
+    OV2_HIP(c, hipMemcpyAsync(res, X.match_cand, stride + n * 4, hipMemcpyDeviceToHost, c->stream));
+    OV2_HIP(c, hipStreamSynchronize(c->stream));
+    const int32_t *mc = (const int32_t *)res;
+    memcpy(match_dist, res + stride, n * 4);
+    for (int b = 0; b < B; ++b) {
+        const int nc = cand_off[b + 1] - cand_off[b];
+        for (int k = kp_off[b]; k < kp_off[b + 1]; ++k)
+            match_lmid[k] = (mc[k] >= 0 && mc[k] < nc) ? cand_lmid[cand_off[b] + mc[k]] : -1;
+    }
+    return OV2_OK;
+}
+
 // ---- saved state (bench / tests: every job starts from the same map) ----------------------------------------------
 extern "C" ov2_status ov2_map_save_state(ov2_map *m)
 {
@@ -2477,5 +3053,19 @@ extern "C" ov2_status ov2_map_download(ov2_map *m, int *n_kf, int *n_lm, int *n_
     DL(obs_kf, m->obs_kf, N * 4); DL(obs_lm, m->obs_lm, N * 4); DL(obs_flag, m->obs_flag, N); DL(obs_uv, m->obs_uv, 2 * N * 8);
     DL(obs_ruv, m->obs_ruv, 2 * N * 8);
 #undef DL
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_map_download_match_columns(ov2_map *m, float *obs_px, uint8_t *obs_desc, uint8_t *obs_hasdesc)
+{
+    if (!m || !m->c) return OV2_ERR_INVALID;
+    ov2_ctx *c = m->c;
+    if (!m->obs_hasdesc) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_download_match_columns: the map has no match columns");
+    OV2_HIP(c, hipSetDevice(c->device));
+    OV2_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t N = m->n_obs;
+    if (obs_px && N) OV2_HIP(c, hipMemcpy(obs_px, m->obs_px, 2 * N * sizeof(float), hipMemcpyDeviceToHost));
+    if (obs_desc && N) OV2_HIP(c, hipMemcpy(obs_desc, m->obs_desc, 32 * N, hipMemcpyDeviceToHost));
+    if (obs_hasdesc && N) OV2_HIP(c, hipMemcpy(obs_hasdesc, m->obs_hasdesc, N, hipMemcpyDeviceToHost));
     return OV2_OK;
 }

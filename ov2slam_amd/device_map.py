@@ -47,6 +47,12 @@ class MergeC(C.Structure):
                 ("n_rows_conflict", C.c_int32)]
 
 
+class MatchLocalC(C.Structure):
+    """ov2_map_match_local"""
+    _fields_ = [(n, C.c_void_p) for n in ("d_kp_off", "d_cand_off", "d_kp_lmid", "d_cand_lmid", "d_match_cand", "d_match_dist",
+                                          "d_prev_lmid", "d_new_lmid", "d_n_pairs")]
+
+
 # OV2_MERGE_* status bytes (include/ov2slam_hip.h)
 MERGE_DONE, MERGE_SKIP_RANGE, MERGE_SKIP_SAME, MERGE_SKIP_PREV_DEAD, MERGE_SKIP_NEW_DEAD, MERGE_SKIP_NEW_NOT3D = range(6)
 MERGE_NOT_RUN = 255
@@ -184,6 +190,66 @@ class DeviceMap:
             dm.add_keyframe(int(k), m["poses"][k], m["obs_lm"][sel], m["obs_uv"][sel].astype(np.float64))
         dm.set_landmarks(seen, np.where((m["lm_3d"][seen] != 0)[:, None], m["lm_xyz"][seen], 0.0), st)
         return dm
+
+    @classmethod
+    def from_scene(cls, ctx, s, spare=(8, 8, 64), capacity=None):
+        """the mirror of a synth_revisit.make_local_map_scene dict, with the match columns, through the public hooks: what
+        host_map.LoopMap builds from the same dict.  A map point is 3D when its first keyframe saw it with a 3D keypoint, its
+        point is the scene's; `forget_lm` landmarks are removed; a descriptor of `desc` sits on the row of the landmark's
+        oldest observer, one of `descs` on the row of the keyframe it names -- where that keyframe does not observe the
+        landmark there is no row to carry it and it is left out (MapPoint::addDesc is only ever called for an observer).
+        capacity: (max_kf, max_lm, max_obs) to start from instead of a fit"""
+        rows = scene_rows(s)
+        top_lm = max(int(v["lmid"].max()) for v in s["kps"].values() if len(v["lmid"]))
+        cap = capacity or (max(s["kfids"]) + 1 + spare[0], top_lm + 1 + spare[1], sum(len(r["lmid"]) for r in rows.values()) + spare[2])
+        m = cls(ctx, *cap)
+        m.enable_match_columns()
+        m.newkf = int(s["pairs"]["revisit"][0])
+        for k in s["kfids"]:
+            r = rows[k]
+            m.add_keyframe_px(k, s["poses"][k], r["lmid"], r["px"].astype(np.float64), r["px"], r["desc"], r["has_desc"])
+        lmid, xyz, state = scene_landmarks(s)
+        m.set_landmarks(lmid, xyz, state)
+        return m
+
+    def enable_match_columns(self):
+        _check(self.ctx.h, self.L.ov2_map_enable_match_columns(self.h))
+
+    def add_keyframe_px(self, kfid, Twc, lmid, unpx, px, desc=None, has_desc=None, runpx=None, is_stereo=None, scale=None):
+        """ov2_map_add_keyframe_px: add_keyframe plus the raw pixels (n x 2 float) and, optionally, desc (n x 32) / has_desc (n)"""
+        c = np.ascontiguousarray
+        Twc, lmid, unpx, px = c(Twc, np.float64), c(lmid, np.int32), c(unpx, np.float64), c(px, np.float32)
+        desc = None if desc is None else c(desc, np.uint8).reshape(-1, 32)
+        has_desc = None if has_desc is None else c(has_desc, np.uint8)
+        assert len(px) == len(lmid) and (desc is None) == (has_desc is None) and (desc is None or len(desc) == len(has_desc) == len(lmid))
+        runpx = None if runpx is None else c(runpx, np.float64)
+        is_stereo = None if is_stereo is None else c(is_stereo, np.uint8)
+        scale = None if scale is None else c(scale, np.int32)
+        _check(self.ctx.h, self.L.ov2_map_add_keyframe_px(self.h, int(kfid), self._p(Twc), len(lmid), self._p(lmid), self._p(unpx),
+                                                          self._p(runpx), self._p(is_stereo), self._p(scale), self._p(px),
+                                                          self._p(desc), self._p(has_desc)))
+
+    def set_obs_desc(self, kfid, lmid, desc, has_desc=None, px=None):
+        """ov2_map_set_obs_desc: MapPoint::addDesc for the live rows (kfid[i], lmid[i]); px: None = keep the pixels"""
+        c = np.ascontiguousarray
+        k, l, d = c(kfid, np.int32).reshape(-1), c(lmid, np.int32).reshape(-1), c(desc, np.uint8).reshape(-1, 32)
+        h = np.ones(len(k), np.uint8) if has_desc is None else c(has_desc, np.uint8).reshape(-1)
+        px = None if px is None else c(px, np.float32).reshape(-1, 2)
+        assert len(k) == len(l) == len(d) == len(h) and (px is None or len(px) == len(k))
+        _check(self.ctx.h, self.L.ov2_map_set_obs_desc(self.h, len(k), self._p(k), self._p(l), self._p(px), self._p(d), self._p(h)))
+
+    def download_match_columns(self):
+        """dict(obs_kf, obs_lm, obs_flag, obs_px, obs_desc, obs_hasdesc): the rows with their match columns (host copies)"""
+        d = self.download()
+        n = len(d["obs_kf"])
+        out = dict(obs_kf=d["obs_kf"], obs_lm=d["obs_lm"], obs_flag=d["obs_flag"], obs_px=np.zeros((n, 2), np.float32),
+                   obs_desc=np.zeros((n, 32), np.uint8), obs_hasdesc=np.zeros(n, np.uint8))
+        _check(self.ctx.h, self.L.ov2_map_download_match_columns(self.h, self._p(out["obs_px"]), self._p(out["obs_desc"]),
+                                                                 self._p(out["obs_hasdesc"])))
+        return out
+
+    def remove_keyframe(self, kfid):
+        _check(self.ctx.h, self.L.ov2_map_remove_keyframe(self.h, int(kfid)))
 
     def filter_keyframes_batch(self, others=(), newkf=None, nmin_covscore=25, ratio=0.9):
         """ov2_map_filter_keyframes_batch on this map and `others` in one call; see filter_keyframes_batch"""
@@ -401,6 +467,151 @@ def merge_points_batch(ctx, maps, pairs, cur_obs=None, want_header=True, dev=Fal
     hdr = [dict(n_pairs=u.n_pairs, n_merged=u.n_merged, n_skipped=u.n_skipped, n_rows_moved=u.n_rows_moved,
                 n_rows_conflict=u.n_rows_conflict) for u in out]
     return hdr, [st[off[b]:off[b + 1]].copy() for b in range(B)]
+
+
+def scene_rows(s):
+    """kfid -> dict(lmid, px (float32), desc (n x 32), has_desc) of a synth_revisit.make_local_map_scene dict: the observation
+    rows of every keyframe with the descriptors they carry (see DeviceMap.from_scene)"""
+    first = {}
+    for k in sorted(s["kfids"]):
+        for l in s["kps"][k]["lmid"].tolist():
+            first.setdefault(l, k)
+    rows = {}
+    for k in s["kfids"]:
+        v = s["kps"][k]
+        n = len(v["lmid"])
+        desc, has = np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        for i, l in enumerate(v["lmid"].tolist()):
+            d = s["desc"].get(l) if first[l] == k else None
+            for q, dq in s.get("descs", {}).get(l, []):     # a later addDesc for a keyframe that already has one is ignored
+                if q == k and d is None:
+                    d = dq
+            if d is not None:
+                desc[i], has[i] = d, 1
+        rows[k] = dict(lmid=np.ascontiguousarray(v["lmid"], np.int32), px=np.ascontiguousarray(v["uv"], np.float32).reshape(-1, 2),
+                       desc=desc, has_desc=has)
+    return rows
+
+
+def scene_landmarks(s):
+    """(lmid, xyz, state) of the landmarks of a make_local_map_scene dict as host_map.LoopMap creates them: 3D (and its
+    keypoints 3D) when the first keyframe that sees it holds a 3D keypoint, at the scene's point; not alive when forgotten"""
+    first = {}
+    for k in sorted(s["kfids"]):
+        v = s["kps"][k]
+        for i, l in enumerate(v["lmid"].tolist()):
+            first.setdefault(l, (bool(v["kp3d"][i]), v["xyz"][i]))
+    gone = set(int(l) for l in s["forget_lm"])
+    lmid = np.array(sorted(first), np.int32)
+    is3d = np.array([first[int(l)][0] for l in lmid])
+    xyz = np.array([first[int(l)][1] if first[int(l)][0] else np.zeros(3) for l in lmid], np.float64).reshape(-1, 3)
+    state = np.where(is3d, LM_ALIVE | LM_OBS | LM_3D | LM_KP3D, LM_ALIVE | LM_OBS).astype(np.uint8)
+    state[[int(l) in gone for l in lmid]] = 0
+    return lmid, xyz, state
+
+
+def _match_ids(maps, newkf, nb3dkps, kp_lists, grids, cand_lists):
+    """the id arrays of the match calls: grids = (grid_ptr over B * ncells + 1 cells, grid_kp) or None"""
+    B = len(maps)
+    c = np.ascontiguousarray
+    cat = lambda ls: c(np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in ls] + [np.zeros(0, np.int32)]), np.int32)
+    off = lambda ls: np.concatenate([[0], np.cumsum([len(x) for x in ls])]).astype(np.int32)
+    a = dict(hs=(C.c_void_p * max(B, 1))(*[getattr(m, "h", m) for m in maps]),
+             newkf=c([m.newkf for m in maps] if newkf is None else newkf, np.int32), nb3dkps=c(np.broadcast_to(np.asarray(nb3dkps, np.int32), (B,))),
+             kp_off=off(kp_lists), kp_lmid=cat(kp_lists), cand_off=off(cand_lists), cand_lmid=cat(cand_lists),
+             grid_ptr=None if grids is None else c(grids[0], np.int32), grid_kp=None if grids is None else c(grids[1], np.int32))
+    return a
+
+
+def _match_call_args(ctx, a, camera, cam):
+    K, w, h, cell = camera
+    K = np.ascontiguousarray(K, np.float64)
+    a["K"] = K
+    p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+    return [ctx.h, len(a["kp_off"]) - 1, a["hs"], p(a["newkf"]), p(a["nb3dkps"]), p(a["kp_off"]), p(a["kp_lmid"]), p(a["grid_ptr"]),
+            p(a["grid_kp"]), p(a["cand_off"]), p(a["cand_lmid"]), p(K), int(w), int(h), int(cell), None if cam is None else C.addressof(cam)]
+
+
+def match_gather_batch(ctx, maps, newkf, nb3dkps, kp_lists, grids, cand_lists, camera, cam=None):
+    """ov2_map_match_gather_batch_dev on the maps (DeviceMap objects or raw ov2_map handles), then every gathered array
+    downloaded: a dict keyed like mapper.MatchBatchInput (Twc, nb3dkps, kp_off, cand_off, kf_off, kp_px, kp_desc_ptr, kp_descs,
+    kp_kf_ptr, kp_kfids, kp_kf_px, grid_ptr, grid_kp, cand_wpt, cand_desc_ptr, cand_descs, cand_kf_ptr, cand_kfids, kf_Twc) plus
+    kp_lmid / cand_lmid, the device copies of the id lists.  camera = (K4, img_w, img_h, cell).  For tests."""
+    from .mapper import MatchBatchInputC
+    a = _match_ids(maps, newkf, nb3dkps, kp_lists, grids, cand_lists)
+    out, dk, dc = MatchBatchInputC(), C.c_void_p(), C.c_void_p()
+    _check(ctx.h, ctx.lib.ov2_map_match_gather_batch_dev(*_match_call_args(ctx, a, camera, cam), C.byref(out), C.byref(dk), C.byref(dc)))
+    ctx.synchronize()
+    B, nkp, nc = out.B, out.n_kp, out.n_cand
+
+    def get(ptr, shape, dt):
+        arr = np.zeros(shape, dt)
+        addr = ptr if isinstance(ptr, int) or ptr is None else C.cast(ptr, C.c_void_p).value
+        if arr.nbytes and addr:
+            _check(ctx.h, ctx.lib.ov2_memcpy_d2h(ctx.h, arr.ctypes.data_as(C.c_void_p), C.c_void_p(addr), arr.nbytes))
+        return arr
+    g = dict(B=B, n_kp=nkp, n_cand=nc)
+    if nkp == 0:
+        return g
+    g["Twc"], g["nb3dkps"] = get(out.Twc, (B, 7), np.float64), get(out.nb3dkps, B, np.int32)
+    for k in ("kp_off", "cand_off", "kf_off"):
+        g[k] = get(getattr(out, k), B + 1, np.int32)
+    g["kp_px"] = get(out.kp_px, (nkp, 2), np.float32)
+    g["kp_desc_ptr"], g["kp_kf_ptr"] = get(out.kp_desc_ptr, nkp + 1, np.int32), get(out.kp_kf_ptr, nkp + 1, np.int32)
+    g["kp_descs"] = get(out.kp_descs, (int(g["kp_desc_ptr"][-1]), 32), np.uint8)
+    g["kp_kfids"] = get(out.kp_kfids, int(g["kp_kf_ptr"][-1]), np.int32)
+    g["kp_kf_px"] = get(out.kp_kf_px, (int(g["kp_kf_ptr"][-1]), 2), np.float32)
+    g["cand_wpt"] = get(out.cand_wpt, (nc, 3), np.float64)
+    g["cand_desc_ptr"], g["cand_kf_ptr"] = get(out.cand_desc_ptr, nc + 1, np.int32), get(out.cand_kf_ptr, nc + 1, np.int32)
+    g["cand_descs"] = get(out.cand_descs, (int(g["cand_desc_ptr"][-1]), 32), np.uint8)
+    g["cand_kfids"] = get(out.cand_kfids, int(g["cand_kf_ptr"][-1]), np.int32)
+    g["kf_Twc"] = get(out.kf_Twc, (int(g["kf_off"][-1]), 7), np.float64)
+    if nc:
+        ncell = (len(a["grid_ptr"]) - 1)
+        g["grid_ptr"] = get(out.grid_ptr, ncell + 1, np.int32)
+        g["grid_kp"] = get(out.grid_kp, int(g["grid_ptr"][-1]), np.int32)
+    g["kp_lmid"], g["cand_lmid"] = get(dk.value, nkp, np.int32), get(dc.value, nc, np.int32)
+    return g
+
+
+def match_local_batch(ctx, maps, newkf, nb3dkps, kp_lists, grids, cand_lists, camera, cam=None, fmaxprojerr=2.0, fdistratio=0.2,
+                      pairs=False, dev=False):
+    """Mapper::matchingToLocalMap from the mirrors (ov2_map_match_local_batch): keyframe newkf[b] of maps[b], its keypoints'
+    lmids kp_lists[b] in grid order, grids = (grid_ptr, grid_kp) as ov2_match_batch_input takes them, the unfiltered local ids
+    cand_lists[b]; camera = (K4, img_w, img_h, cell).
+    dev=False: returns per map (match_lmid, match_dist) over its keypoints, the outputs pre-filled with -7 so that untouched
+    slots show.  dev=True: ov2_map_match_local_batch_dev, asynchronous; returns (MatchLocalC, DevPairs or None): with pairs the
+    DevPairs is what merge_points_batch(..., dev=True) takes."""
+    a = _match_ids(maps, newkf, nb3dkps, kp_lists, grids, cand_lists)
+    args = _match_call_args(ctx, a, camera, cam)
+    n = int(a["kp_off"][-1])
+    if dev:
+        out = MatchLocalC()
+        _check(ctx.h, ctx.lib.ov2_map_match_local_batch_dev(*args, float(fmaxprojerr), float(fdistratio), int(bool(pairs)), C.byref(out)))
+        dp_ = None
+        if pairs and out.d_prev_lmid:
+            dp_ = DevPairs(a["kp_off"], _DevPtr(out.d_prev_lmid), _DevPtr(out.d_new_lmid), _DevPtr(out.d_n_pairs))
+        return out, dp_
+    ml, md = np.full(max(n, 1), -7, np.int32), np.full(max(n, 1), -7, np.float32)
+    _check(ctx.h, ctx.lib.ov2_map_match_local_batch(*args, float(fmaxprojerr), float(fdistratio), ml.ctypes.data_as(C.c_void_p),
+                                                    md.ctypes.data_as(C.c_void_p)))
+    o = a["kp_off"]
+    return [(ml[o[b]:o[b + 1]].copy(), md[o[b]:o[b + 1]].copy()) for b in range(len(o) - 1)]
+
+
+class _DevPtr:
+    """a device address that somebody else owns, where a DeviceArray's .ptr is expected"""
+
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+
+def fetch_dev(ctx, ptr, shape, dtype):
+    """host copy of a device array (one synchronising copy)"""
+    arr = np.zeros(shape, dtype)
+    if arr.nbytes and ptr:
+        _check(ctx.h, ctx.lib.ov2_memcpy_d2h(ctx.h, arr.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), arr.nbytes))
+    return arr
 
 
 def restore_state_batch(ctx, maps):

@@ -574,6 +574,7 @@ void MapManager::mergeMapPoints(int prevlmid, int newlmid)
         }
     }
     for (const auto &kfid_desc : map_prev_kf_desc) pnew->addDesc(kfid_desc.first, kfid_desc.second);
+    touchDesc(newlmid);
     if (pcurframe_ && pcurframe_->isObservingKp(prevlmid) && pcurframe_->updateKeypointId(prevlmid, newlmid, pnew->is3d_)) setMapPointObs(newlmid);
     map_plms_.erase(prevlmid);
     touchMapPoint(prevlmid);   // gone: the mirror's row dies with the next flush
@@ -626,11 +627,34 @@ static uint8_t lm_state_of(const MapManager &map, const MapPoint &lm)
     return (uint8_t)(OV2_LM_ALIVE | (lm.is3d_ ? OV2_LM_3D : 0) | (lm.isobs_ ? OV2_LM_OBS : 0) | (kp3d ? OV2_LM_KP3D : 0));
 }
 
+// the match columns of rows (kfid, lmid[i]): Keypoint::px_ and the descriptor the map point holds for the keyframe
+struct MatchCols {
+    std::vector<float> px; std::vector<uint8_t> desc, has;
+    void push(const MapManager &map, int kfid, const Keypoint &kp)
+    {
+        px.push_back(kp.px_.x); px.push_back(kp.px_.y);
+        auto plm = map.getMapPoint(kp.lmid_);
+        const Desc *d = nullptr;
+        if (plm) { auto it = plm->map_kf_desc_.find(kfid); if (it != plm->map_kf_desc_.end()) d = &it->second; }
+        has.push_back(d ? 1 : 0);
+        if (d) desc.insert(desc.end(), d->begin(), d->end()); else desc.insert(desc.end(), 32, 0);
+    }
+};
+
+void MapManager::addDesc(int lmid, int kfid, const Desc &d)
+{
+    auto plm = getMapPoint(lmid);
+    if (!plm) return;
+    plm->addDesc(kfid, d);
+    touchDesc(lmid);
+}
+
 ov2_status MapManager::addKeyframeToDevice(const Frame &kf)
 {
     if (!dev_) return OV2_OK;
     const size_t n = kf.mapkps_.size();
     std::vector<int32_t> lmid, scale; std::vector<double> un, run; std::vector<uint8_t> st;
+    MatchCols mc;
     lmid.reserve(n); scale.reserve(n); un.reserve(2 * n); run.reserve(2 * n); st.reserve(n);
     for (const auto &kv : kf.mapkps_) {
         const Keypoint &kp = kv.second;
@@ -638,10 +662,37 @@ ov2_status MapManager::addKeyframeToDevice(const Frame &kf)
         un.push_back(kp.unpx_.x); un.push_back(kp.unpx_.y);
         run.push_back(kp.runpx_.x); run.push_back(kp.runpx_.y);
         st.push_back(kp.is_stereo_ ? 1 : 0);
+        if (dev_match_cols_) mc.push(*this, kf.kfid_, kp);
     }
     const SE3 T = kf.getTwc();
     dev_kfs_.insert(kf.kfid_);
+    if (dev_match_cols_)
+        return ov2_map_add_keyframe_px(dev_, kf.kfid_, T.v.data(), (int)n, lmid.data(), un.data(), run.data(), st.data(), scale.data(),
+                                       mc.px.data(), mc.desc.data(), mc.has.data());
     return ov2_map_add_keyframe(dev_, kf.kfid_, T.v.data(), (int)n, lmid.data(), un.data(), run.data(), st.data(), scale.data());
+}
+
+ov2_status MapManager::enableMatchColumns()
+{
+    if (!dev_) return OV2_ERR_INVALID;
+    if (dev_match_cols_) return OV2_OK;
+    ov2_status s = flushDevice();   // the rows the mirror is owed, before their columns
+    if (s != OV2_OK) return s;
+    if ((s = ov2_map_enable_match_columns(dev_)) != OV2_OK) return s;
+    dev_match_cols_ = true;
+    // the rows the mirror holds already: pixel and descriptor of every keypoint of every mirrored keyframe
+    std::vector<int32_t> kfid, lmid;
+    MatchCols mc;
+    for (int k : dev_kfs_) {
+        auto pkf = getKeyframe(k);
+        if (!pkf) continue;
+        for (const auto &kv : pkf->mapkps_) {
+            kfid.push_back(k); lmid.push_back(kv.second.lmid_);
+            mc.push(*this, k, kv.second);
+        }
+    }
+    if (kfid.empty()) return OV2_OK;
+    return ov2_map_set_obs_desc(dev_, (int)kfid.size(), kfid.data(), lmid.data(), mc.px.data(), mc.desc.data(), mc.has.data());
 }
 
 ov2_status MapManager::attachDevice(ov2_ctx *ctx, int max_kf, int max_lm, int max_obs)
@@ -660,6 +711,7 @@ ov2_status MapManager::attachDevice(ov2_ctx *ctx, int max_kf, int max_lm, int ma
     for (const auto &kv : map_pkfs_)
         if ((s = addKeyframeToDevice(*kv.second)) != OV2_OK) return s;
     dev_lm_dirty_.clear(); dev_pose_dirty_.clear(); dev_rm_kf_.clear(); dev_rm_lm_.clear(); dev_st_kf_.clear(); dev_st_lm_.clear();
+    dev_match_cols_ = false; dev_desc_dirty_.clear();   // a fresh mirror has no match columns until enableMatchColumns
     return OV2_OK;
 }
 
@@ -679,17 +731,40 @@ ov2_status MapManager::flushDevice()
             auto pkf = getKeyframe(kv.first);
             if (!pkf) continue;
             std::vector<int32_t> lmid, scale; std::vector<double> un, run; std::vector<uint8_t> st;
+            MatchCols mc;
             for (int l : kv.second) {
                 const Keypoint kp = pkf->getKeypointById(l);
                 if (kp.lmid_ != l) continue;   // removed again since
                 lmid.push_back(l); scale.push_back(kp.scale_);
                 un.push_back(kp.unpx_.x); un.push_back(kp.unpx_.y); run.push_back(kp.runpx_.x); run.push_back(kp.runpx_.y);
                 st.push_back(kp.is_stereo_ ? 1 : 0);
+                if (dev_match_cols_) mc.push(*this, kv.first, kp);
             }
             const SE3 T = pkf->getTwc();
-            if (!lmid.empty() && (s = ov2_map_add_keyframe(dev_, kv.first, T.v.data(), (int)lmid.size(), lmid.data(), un.data(), run.data(), st.data(),
-                                                           scale.data())) != OV2_OK) return s;
+            if (lmid.empty()) continue;
+            s = dev_match_cols_ ? ov2_map_add_keyframe_px(dev_, kv.first, T.v.data(), (int)lmid.size(), lmid.data(), un.data(), run.data(), st.data(),
+                                                          scale.data(), mc.px.data(), mc.desc.data(), mc.has.data())
+                                : ov2_map_add_keyframe(dev_, kv.first, T.v.data(), (int)lmid.size(), lmid.data(), un.data(), run.data(), st.data(),
+                                                       scale.data());
+            if (s != OV2_OK) return s;
         }
+    }
+    if (!dev_desc_dirty_.empty()) {   // MapPoint::addDesc since the last flush: every descriptor of the touched map points, behind the new rows
+        std::sort(dev_desc_dirty_.begin(), dev_desc_dirty_.end());
+        dev_desc_dirty_.erase(std::unique(dev_desc_dirty_.begin(), dev_desc_dirty_.end()), dev_desc_dirty_.end());
+        std::vector<int32_t> kfid, lmid; std::vector<uint8_t> desc, has;
+        for (int l : dev_desc_dirty_) {
+            auto plm = getMapPoint(l);
+            if (!plm) continue;
+            for (const auto &kd : plm->map_kf_desc_) {
+                if (!dev_kfs_.count(kd.first)) continue;   // (a keyframe the mirror does not hold has no row to carry it)
+                kfid.push_back(kd.first); lmid.push_back(l); has.push_back(1);
+                desc.insert(desc.end(), kd.second.begin(), kd.second.end());
+            }
+        }
+        dev_desc_dirty_.clear();
+        if (!kfid.empty() && (s = ov2_map_set_obs_desc(dev_, (int)kfid.size(), kfid.data(), lmid.data(), nullptr, desc.data(), has.data())) != OV2_OK)
+            return s;
     }
     if (!dev_st_kf_.empty()) {
         std::vector<uint8_t> off(dev_st_kf_.size(), 0);

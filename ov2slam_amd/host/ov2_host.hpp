@@ -210,6 +210,15 @@ public:
     void touchMapPoint(int lmid) { if (dev_) dev_lm_dirty_.push_back(lmid); }
     void touchPose(int kfid) { if (dev_) dev_pose_dirty_.push_back(kfid); }
     void touchStereoOff(int kfid, int lmid) { if (dev_) { dev_st_kf_.push_back(kfid); dev_st_lm_.push_back(lmid); } }
+    // Match columns of the mirror (ov2_map_enable_match_columns): after enableMatchColumns, rows go up with Keypoint::px_ and
+    // the descriptor their map point holds for the keyframe, and a MapPoint::addDesc is forwarded with the next flush
+    // (ov2_map_set_obs_desc) -- whoever calls addDesc on a map point of this map says so with touchDesc.  Without it nothing
+    // changes.
+    ov2_status enableMatchColumns();
+    void touchDesc(int lmid) { if (dev_ && dev_match_cols_) dev_desc_dirty_.push_back(lmid); }
+    void addDesc(int lmid, int kfid, const Desc &d);        // MapPoint::addDesc + touchDesc
+    bool dev_match_cols_ = false;
+    std::vector<int32_t> dev_desc_dirty_;
     ov2_map *dev_ = nullptr;
     std::vector<int32_t> dev_lm_dirty_, dev_pose_dirty_, dev_rm_kf_, dev_rm_lm_, dev_st_kf_, dev_st_lm_;
     std::vector<std::pair<int, int>> dev_add_obs_;   // (kfid, lmid): observations a merge gave to keyframes the mirror already holds

@@ -196,6 +196,7 @@ int ov2h_map_add_desc(void *p, int lmid, int kfid, const uint8_t *desc32)
     Desc d;
     std::copy(desc32, desc32 + 32, d.begin());
     lm->addDesc(kfid, d);
+    ((HostMap *)p)->map->touchDesc(lmid);
     return 0;
 }
 
@@ -479,8 +480,25 @@ int ov2h_match_assemble(void *p, int kfid, int n_local, const int *local, int ca
 // (previous lmid, new lmid) pairs job after job, ascending previous lmid, n_pairs[b] each; stats[5]: jobs, jobs offered,
 // keypoints offered, candidates offered, library calls.  Returns 0 or a negative ov2_status (OV2_ERR_INVALID also when cap
 // is too small)
+static int match_local_maps_impl(int B, void *const *maps, void *ctx, const int *kfid, const int *n_local, const int *local, float fmaxprojerr,
+                                 float fdistratio, int merge, int single, int cap, int *n_pairs, int *pairs, int *stats, bool mirror);
+
 int ov2h_match_local_maps(int B, void *const *maps, void *ctx, const int *kfid, const int *n_local, const int *local, float fmaxprojerr,
                           float fdistratio, int merge, int single, int cap, int *n_pairs, int *pairs, int *stats)
+{
+    return match_local_maps_impl(B, maps, ctx, kfid, n_local, local, fmaxprojerr, fdistratio, merge, single, cap, n_pairs, pairs, stats, false);
+}
+
+// the same with the mirror path asked for (SlamManager::matchToLocalMaps(..., mirror = true)): taken when every map has a device
+// mirror with the match columns
+int ov2h_match_local_maps_mirror(int B, void *const *maps, void *ctx, const int *kfid, const int *n_local, const int *local, float fmaxprojerr,
+                                 float fdistratio, int merge, int single, int cap, int *n_pairs, int *pairs, int *stats)
+{
+    return match_local_maps_impl(B, maps, ctx, kfid, n_local, local, fmaxprojerr, fdistratio, merge, single, cap, n_pairs, pairs, stats, true);
+}
+
+static int match_local_maps_impl(int B, void *const *maps, void *ctx, const int *kfid, const int *n_local, const int *local, float fmaxprojerr,
+                                 float fdistratio, int merge, int single, int cap, int *n_pairs, int *pairs, int *stats, bool mirror)
 {
     if (B < 0) return (int)OV2_ERR_INVALID;
     std::vector<MatchJob> jobs((size_t)B);
@@ -491,7 +509,7 @@ int ov2h_match_local_maps(int B, void *const *maps, void *ctx, const int *kfid, 
         o += (size_t)n_local[b];
     }
     MatchBatchStats st;
-    const ov2_status s = SlamManager::matchToLocalMaps((ov2_ctx *)ctx, jobs, fmaxprojerr, fdistratio, merge != 0, single != 0, st);
+    const ov2_status s = SlamManager::matchToLocalMaps((ov2_ctx *)ctx, jobs, fmaxprojerr, fdistratio, merge != 0, single != 0, st, mirror);
     const int sv[5] = {st.jobs, st.match_jobs, st.n_kp, st.n_cand, st.match_calls};
     std::copy(sv, sv + 5, stats);
     if (s != OV2_OK) return (int)s;
@@ -796,6 +814,9 @@ int ov2h_map_attach_device(void *p, void *ctx, int max_kf, int max_lm, int max_o
     HostMap *m = (HostMap *)p;
     return (int)m->map->attachDevice((ov2_ctx *)ctx, max_kf, max_lm, max_obs);
 }
+
+// MapManager::enableMatchColumns: the mirror keeps Keypoint::px_ and the descriptors from here on
+int ov2h_map_enable_match_columns(void *p) { return (int)((HostMap *)p)->map->enableMatchColumns(); }
 
 // the ov2_map behind the host map (tests compare its tables with a map updated on the device)
 void *ov2h_map_device_handle(void *p) { return ((HostMap *)p)->map->dev_; }

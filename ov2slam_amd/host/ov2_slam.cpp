@@ -258,7 +258,7 @@ ov2_status SlamManager::describeKeypoints(const std::vector<Keypoint> &vkps, con
         if (!valid[i]) continue;
         pcurframe_->updateKeypointDesc(vkps[i].lmid_, vdescs[i]);
         auto plm = pmap_->getMapPoint(vkps[i].lmid_);
-        if (plm) plm->addDesc(pcurframe_->kfid_, vdescs[i]);   // (the reference's map_plms_.at() throws for a missing point)
+        if (plm) { plm->addDesc(pcurframe_->kfid_, vdescs[i]); pmap_->touchDesc(vkps[i].lmid_); }   // (the reference's map_plms_.at() throws for a missing point)
         ++last_.n_described;
     }
     return OV2_OK;
@@ -509,11 +509,90 @@ void SlamManager::applyMatches(MatchJob &J, const int32_t *match_cand)
         if (match_cand[k] >= 0) J.map_previd_newid.emplace(J.kp_lmid[k], J.cand_lmid[match_cand[k]]);
 }
 
+void SlamManager::assembleMatchIds(const Frame &frame, const std::unordered_set<int> &set_local_lmids, MatchJob &J)
+{
+    J.offered = false;
+    J.kp_lmid.clear(); J.cand_lmid.clear(); J.map_previd_newid.clear();
+    if (set_local_lmids.empty()) return;
+    J.grid_ptr.assign(1, 0); J.grid_kp.clear();
+    for (const auto &cell : frame.vgridkps_) {
+        for (int lmid : cell) {
+            if (!frame.mapkps_.count(lmid)) continue;
+            J.grid_kp.push_back((int32_t)J.kp_lmid.size());
+            J.kp_lmid.push_back(lmid);
+        }
+        J.grid_ptr.push_back((int32_t)J.grid_kp.size());
+    }
+    if (J.kp_lmid.empty()) return;
+    J.cand_lmid.assign(set_local_lmids.begin(), set_local_lmids.end());
+    const CameraCalibration &c = *frame.pcalib_leftcam_;
+    J.K[0] = c.fx_; J.K[1] = c.fy_; J.K[2] = c.cx_; J.K[3] = c.cy_;
+    J.img_w = c.img_w_; J.img_h = c.img_h_; J.cell = (int)frame.ncellsize_; J.nb3dkps = (int)frame.nb3dkps_;
+    memset(&J.cam, 0, sizeof(J.cam));
+    J.distorted = c.fillCamModel(&J.cam);
+    J.offered = true;
+}
+
 ov2_status SlamManager::matchToLocalMaps(ov2_ctx *ctx, std::vector<MatchJob> &jobs, float fmaxprojerr, float fdistratio, bool merge, bool single,
-                                         MatchBatchStats &stats)
+                                         MatchBatchStats &stats, bool mirror)
 {
     stats = MatchBatchStats();
     stats.jobs = (int)jobs.size();
+    for (const MatchJob &J : jobs) mirror = mirror && J.pmap && J.pmap->dev_ && J.pmap->dev_match_cols_;
+    if (mirror && !single) {
+        std::vector<MatchJob *> offered;
+        for (MatchJob &J : jobs) {
+            auto pkf = J.pmap->getKeyframe(J.kfid);
+            if (!pkf) return OV2_ERR_INVALID;
+            assembleMatchIds(*pkf, J.set_local_lmids, J);
+            if (!J.offered) continue;
+            offered.push_back(&J);
+            stats.n_kp += (int)J.kp_lmid.size(); stats.n_cand += (int)J.cand_lmid.size();
+        }
+        stats.match_jobs = (int)offered.size();
+        if (offered.empty()) return OV2_OK;
+        const MatchJob &J0 = *offered[0];
+        std::vector<ov2_map *> maps;
+        std::vector<int32_t> newkf, nb3dkps, kp_off(1, 0), cand_off(1, 0), kp_lmid, cand_lmid, grid_ptr(1, 0), grid_kp;
+        for (MatchJob *J : offered) {   // one camera per call
+            bool same = J->img_w == J0.img_w && J->img_h == J0.img_h && J->cell == J0.cell && J->distorted == J0.distorted &&
+                        J->grid_ptr.size() == J0.grid_ptr.size();
+            for (int i = 0; i < 4; ++i) same = same && J->K[i] == J0.K[i];
+            if (same && J->distorted) {
+                same = J->cam.model == J0.cam.model && J->cam.n_coeffs == J0.cam.n_coeffs;
+                for (int i = 0; same && i < J0.cam.n_coeffs && i < 5; ++i) same = J->cam.D[i] == J0.cam.D[i];
+            }
+            if (!same) return OV2_ERR_INVALID;
+        }
+        for (MatchJob *J : offered) {
+            const ov2_status fs = J->pmap->flushDevice();
+            if (fs != OV2_OK) return fs;
+            maps.push_back(J->pmap->dev_); newkf.push_back(J->kfid); nb3dkps.push_back(J->nb3dkps);
+            kp_off.push_back(kp_off.back() + (int32_t)J->kp_lmid.size());
+            cand_off.push_back(cand_off.back() + (int32_t)J->cand_lmid.size());
+            kp_lmid.insert(kp_lmid.end(), J->kp_lmid.begin(), J->kp_lmid.end());
+            cand_lmid.insert(cand_lmid.end(), J->cand_lmid.begin(), J->cand_lmid.end());
+            grid_kp.insert(grid_kp.end(), J->grid_kp.begin(), J->grid_kp.end());
+            const int32_t base = grid_ptr.back();
+            for (size_t i = 1; i < J->grid_ptr.size(); ++i) grid_ptr.push_back(base + J->grid_ptr[i]);
+        }
+        std::vector<int32_t> match_lmid((size_t)stats.n_kp, -1);
+        std::vector<float> match_dist((size_t)stats.n_kp, 0.f);
+        const ov2_status s = ov2_map_match_local_batch(ctx, (int)offered.size(), maps.data(), newkf.data(), nb3dkps.data(), kp_off.data(),
+                                                       kp_lmid.data(), grid_ptr.data(), grid_kp.data(), cand_off.data(), cand_lmid.data(), J0.K,
+                                                       J0.img_w, J0.img_h, J0.cell, J0.distorted ? &J0.cam : nullptr, fmaxprojerr, fdistratio,
+                                                       match_lmid.data(), match_dist.data());
+        if (s != OV2_OK) return s;
+        stats.match_calls = 1;
+        for (size_t b = 0; b < offered.size(); ++b) {
+            MatchJob &J = *offered[b];
+            for (size_t k = 0; k < J.kp_lmid.size(); ++k)
+                if (match_lmid[kp_off[b] + k] >= 0) J.map_previd_newid.emplace(J.kp_lmid[k], match_lmid[kp_off[b] + k]);
+            if (merge)
+                for (const auto &ids : J.map_previd_newid) J.pmap->mergeMapPoints(ids.first, ids.second);
+        }
+        return OV2_OK;
+    }
     std::vector<MatchJob *> offered;
     for (MatchJob &J : jobs) {
         auto pkf = J.pmap ? J.pmap->getKeyframe(J.kfid) : nullptr;

@@ -145,8 +145,14 @@ public:
     // MapManager::mergeMapPoints per pair (Mapper::mergeMatches, :556-574).  A job whose keyframe is not in its map, or a camera
     // that differs among the offered jobs (the call takes one), is OV2_ERR_INVALID before anything is enqueued.  single: the same
     // jobs as one ov2_match_to_map call each, the shape of the per-keyframe path.
+    // mirror (off by default): when every job's map has a device mirror with the match columns (MapManager::enableMatchColumns),
+    // the maps are flushed and the call is ov2_map_match_local_batch on the mirrors -- only ids go up: the keypoints' lmids in
+    // grid order, the grid, the local set unfiltered in its iteration order (n_cand then counts the unfiltered ids).  Otherwise
+    // the flag is ignored.
     static ov2_status matchToLocalMaps(ov2_ctx *ctx, std::vector<MatchJob> &jobs, float fmaxprojerr, float fdistratio, bool merge, bool single,
-                                       MatchBatchStats &stats);
+                                       MatchBatchStats &stats, bool mirror = false);
+    // the ids of a job for the mirror path: kp_lmid / grid as assembleMatchToMap lists them, cand_lmid = the local set as it iterates
+    static void assembleMatchIds(const Frame &frame, const std::unordered_set<int> &set_local_lmids, MatchJob &job);
     std::vector<SlamStats> stats_;
     std::vector<SE3> traj_;
 

@@ -176,6 +176,8 @@ def lib():
         L.ov2h_match_assemble.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip]
         L.ov2h_match_local_maps.argtypes = [C.c_int, C.c_void_p, C.c_void_p, ip, ip, ip, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                             ip, ip, ip]
+        L.ov2h_match_local_maps_mirror.argtypes = L.ov2h_match_local_maps.argtypes
+        L.ov2h_map_enable_match_columns.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -1006,6 +1008,25 @@ class LoopMap:
         for a, b, score in s["cov"]:
             assert L.ov2h_map_set_covscore(self.h, int(a), int(b), int(score)) == 0
 
+    def attach_device(self, ctx, max_kf=None, max_lm=None, max_obs=None):
+        """MapManager::attachDevice: mirror the whole map into an ov2_map"""
+        s = self.s
+        top = max(int(v["lmid"].max()) for v in s["kps"].values() if len(v["lmid"]))
+        rc = lib().ov2h_map_attach_device(self.h, ctx.h, max_kf or max(s["kfids"]) + 9, max_lm or top + 9,
+                                          max_obs or sum(len(v["lmid"]) for v in s["kps"].values()) + 64)
+        if rc != 0:
+            raise RuntimeError(f"attachDevice failed (status {rc})")
+
+    def enable_match_columns(self):
+        """MapManager::enableMatchColumns: the attached mirror keeps raw pixels and descriptors from here on"""
+        rc = lib().ov2h_map_enable_match_columns(self.h)
+        if rc != 0:
+            raise RuntimeError(f"enableMatchColumns failed (status {rc})")
+
+    def device_handle(self):
+        """the ov2_map* of the attached device mirror"""
+        return C.c_void_p(lib().ov2h_map_device_handle(self.h))
+
     def keypoint_order(self, kfid, cap=1 << 16):
         """lmids of keyframe kfid in the mirror's iteration order (Frame::getKeypoints)"""
         lm, px, a, b, rpx = np.zeros(cap, np.int32), np.zeros((cap, 2), np.float32), np.zeros(cap, np.uint8), np.zeros(cap, np.uint8), \
@@ -1266,7 +1287,7 @@ def match_assemble(m, kfid, local, cap=1 << 14):
 MATCH_STATS = ("jobs", "match_jobs", "n_kp", "n_cand", "match_calls")
 
 
-def match_local_maps(ctx, maps, kfids, locals, fmaxprojerr=2.0, fdistratio=0.2, merge=False, single=False, cap=1 << 16):
+def match_local_maps(ctx, maps, kfids, locals, fmaxprojerr=2.0, fdistratio=0.2, merge=False, single=False, cap=1 << 16, mirror=False):
     """SlamManager::matchToLocalMaps on B LoopMaps of one context: keyframe kfids[b] of maps[b] re-matched against the lmid list
     locals[b] (Mapper::matchToMap) with ONE ov2_match_to_map_batch call for all; merge: MapManager::mergeMapPoints per pair
     afterwards (Mapper::mergeMatches); single: the same jobs as one ov2_match_to_map call each.  Returns (per-job lists of
@@ -1278,7 +1299,8 @@ def match_local_maps(ctx, maps, kfids, locals, fmaxprojerr=2.0, fdistratio=0.2, 
     lo = np.ascontiguousarray([l for v in locals for l in v], np.int32)
     n_pairs, pairs, st = np.zeros(max(B, 1), np.int32), np.zeros((cap, 2), np.int32), np.zeros(5, np.int32)
     hs = (C.c_void_p * max(B, 1))(*[m.h for m in maps])
-    rc = L.ov2h_match_local_maps(B, hs, ctx.h, kf.ctypes.data_as(ip), n_local.ctypes.data_as(ip), lo.ctypes.data_as(ip), float(fmaxprojerr),
+    # mirror: ONE ov2_map_match_local_batch call on the maps' device mirrors instead, taken when every map has the match columns
+    rc = (L.ov2h_match_local_maps_mirror if mirror else L.ov2h_match_local_maps)(B, hs, ctx.h, kf.ctypes.data_as(ip), n_local.ctypes.data_as(ip), lo.ctypes.data_as(ip), float(fmaxprojerr),
                                  float(fdistratio), int(bool(merge)), int(bool(single)), cap, n_pairs.ctypes.data_as(ip),
                                  pairs.ctypes.data_as(ip), st.ctypes.data_as(ip))
     if rc != 0:
