@@ -57,6 +57,33 @@ ov2_status ov2_ctx_synchronize(ov2_ctx *ctx);
  * it when the two provably touch different arrays (see both entry points).  Results and the ordering of the calls are the
  * same either way; off = the chain is enqueued on the context's main stream. */
 ov2_status ov2_ctx_set_kf_overlap(ov2_ctx *ctx, int on);
+/* Lazy join of the detector chain (on by default; OV2_KF_LAZY_JOIN=0 in the environment starts a context with it off).
+ * With the keyframe overlap on, ov2_detect_grid_batch_dev leaves its chain pending on the side stream instead of making
+ * the context's main stream wait for it.  Every later call on the context is still ordered behind the chain: the first
+ * one that enqueues on the main stream waits for the chain's end first.  Only ov2_klt_tracking_frame_dev and
+ * ov2_stereo_matching_dev run beside a pending chain, and only when none of the arrays they read meets what the chain
+ * writes (d_thresh, d_n_out, d_out_xy up to out_cap) and none they write meets what it reads (d_thresh, d_cur_xy,
+ * d_cur_img, d_cur_valid) or writes; any overlap joins first.  The pyramid the chain reads may be released at once: a
+ * build that reuses its buffer waits for the chain.  ov2_ctx_synchronize, ov2_timer_stop and ov2_ctx_destroy complete a
+ * pending chain.  Results are the same either way; off = the detector call joins its chain itself.  Both setters join a
+ * pending chain before they change the setting. */
+ov2_status ov2_ctx_set_kf_lazy_join(ov2_ctx *ctx, int on);
+int ov2_ctx_get_kf_lazy_join(const ov2_ctx *ctx);   /* -1 for a null context */
+/* Counters of the detector chains on the side stream since the context was created (no device work):
+ *   out[0] chains started            out[1] joined by a tracking / stereo call whose arrays meet the chain's
+ *   out[2] joined by the first other use of the main stream
+ *   out[3] completed by ov2_ctx_synchronize or ov2_timer_stop
+ *   out[4] never joined: covered by the next chain or by a synchronisation of the side stream
+ *   out[5] joined inside the detector call (lazy join off, a failed launch, a pyramid of another context)
+ *   out[6] pyramid builds that waited for a chain reading the buffer they reuse
+ *   out[7] 1 while a chain is pending, else 0
+ * out[0] = out[1] + ... + out[5] + out[7]. */
+ov2_status ov2_ctx_kf_join_stats(ov2_ctx *ctx, int64_t out[8]);
+/* The range rule behind the lazy join, a plain host function (no device needed).  Each list holds n (address, bytes)
+ * pairs, at most 16; address 0 = an absent array, which meets nothing.  1 when nothing in wr meets anything in chain_rd or
+ * chain_wr and nothing in rd meets anything in chain_wr, 0 when something does, -1 for a bad argument. */
+int ov2_kf_ranges_independent(const uintptr_t *rd, int nrd, const uintptr_t *wr, int nwr, const uintptr_t *chain_rd, int nchain_rd,
+                              const uintptr_t *chain_wr, int nchain_wr);
 /* Wave priority of the context's kernels, level = 0 .. 3 (anything else: OV2_ERR_INVALID, the level stays).  A SIMD
  * arbitrates instruction issue between its resident waves by this priority, then by age, so where the waves of two
  * contexts share a SIMD the higher level wins every conflict; the stream priority of ov2_ctx_create_ex only orders the

@@ -24,6 +24,11 @@ SIGNATURES = {
     "ov2_status_string": (C.c_char_p, [C.c_int]),
     "ov2_ctx_synchronize": (C.c_int, [vp]),
     "ov2_ctx_set_kf_overlap": (C.c_int, [vp, C.c_int]),
+    "ov2_ctx_set_kf_lazy_join": (C.c_int, [vp, C.c_int]),
+    "ov2_ctx_get_kf_lazy_join": (C.c_int, [vp]),
+    "ov2_ctx_kf_join_stats": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+    "ov2_kf_ranges_independent": (C.c_int, [C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_size_t), C.c_int,
+                                            C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_size_t), C.c_int]),
     "ov2_ctx_set_wave_prio": (C.c_int, [vp, C.c_int]),
     "ov2_ctx_get_wave_prio": (C.c_int, [vp]),
     "ov2_ctx_create_cu": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vpp]),

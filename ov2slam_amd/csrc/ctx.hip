@@ -180,6 +180,9 @@ ov2_status ctx_create(int device, int high_priority, int n_cus, int layout, ov2_
     // OV2_KF_OVERLAP=0: the keyframe detector chain stays on the main stream (default 1, ov2_ctx_set_kf_overlap)
     const char *kf_env = getenv("OV2_KF_OVERLAP");
     c->kf_overlap = (kf_env ? atoi(kf_env) : 1) > 0 ? 1 : 0;
+    // OV2_KF_LAZY_JOIN=0: the detector call joins its chain itself (default 1, ov2_ctx_set_kf_lazy_join)
+    const char *lazy_env = getenv("OV2_KF_LAZY_JOIN");
+    c->kf_lazy_join = (lazy_env ? atoi(lazy_env) : 1) > 0 ? 1 : 0;
     // OV2_PYR_RING=1..8: depth of the pyramid pool's ring (ov2_ctx_set_pyr_ring); any other value is ignored
     const char *ring_env = getenv("OV2_PYR_RING");
     const int ring = ring_env ? atoi(ring_env) : 0;
@@ -272,6 +275,7 @@ extern "C" ov2_status ov2_ctx_synchronize(ov2_ctx *c)
     OV2_HIP(c, hipSetDevice(c->device));   // HIP's current device is per thread
     OV2_HIP(c, hipStreamSynchronize(c->stream_pyr));
     OV2_HIP(c, hipStreamSynchronize(c->stream_kf));
+    c->stream.settle(OV2_KFJ_SYNC);   // a pending detector chain has ended with its stream: nothing is left to join
     OV2_HIP(c, hipStreamSynchronize(c->stream));
     return OV2_OK;
 }
@@ -279,8 +283,51 @@ extern "C" ov2_status ov2_ctx_synchronize(ov2_ctx *c)
 extern "C" ov2_status ov2_ctx_set_kf_overlap(ov2_ctx *c, int on)
 {
     if (!c) return OV2_ERR_INVALID;
+    OV2_HIP(c, hipSetDevice(c->device));
+    c->stream.join(OV2_KFJ_DEFAULT);   // a chain of the old setting is not left pending under the new one
     c->kf_overlap = on ? 1 : 0;
     return OV2_OK;
+}
+
+extern "C" ov2_status ov2_ctx_set_kf_lazy_join(ov2_ctx *c, int on)
+{
+    if (!c) return OV2_ERR_INVALID;
+    OV2_HIP(c, hipSetDevice(c->device));
+    c->stream.join(OV2_KFJ_DEFAULT);
+    c->kf_lazy_join = on ? 1 : 0;
+    return OV2_OK;
+}
+
+extern "C" int ov2_ctx_get_kf_lazy_join(const ov2_ctx *c) { return c ? c->kf_lazy_join : -1; }
+
+extern "C" ov2_status ov2_ctx_kf_join_stats(ov2_ctx *c, int64_t out[8])
+{
+    if (!c || !out) return OV2_ERR_INVALID;
+    for (int i = 0; i < OV2_KFJ_N; ++i) out[i] = c->stream.kfj[i].load(std::memory_order_relaxed);
+    out[OV2_KFJ_N] = c->stream.pend.done ? 1 : 0;
+    return OV2_OK;
+}
+
+extern "C" int ov2_kf_ranges_independent(const uintptr_t *rd, int nrd, const uintptr_t *wr, int nwr, const uintptr_t *chain_rd,
+                                         int nchain_rd, const uintptr_t *chain_wr, int nchain_wr)
+{
+    if (nrd < 0 || nwr < 0 || nchain_rd < 0 || nchain_wr < 0 || nrd > 16 || nwr > 16 || nchain_rd > 16 || nchain_wr > 16) return -1;
+    if ((nrd && !rd) || (nwr && !wr) || (nchain_rd && !chain_rd) || (nchain_wr && !chain_wr)) return -1;
+    ov2_byte_range r[4][16];
+    const uintptr_t *src[4] = {rd, wr, chain_rd, chain_wr};
+    const int cnt[4] = {nrd, nwr, nchain_rd, nchain_wr};
+    for (int k = 0; k < 4; ++k)
+        for (int i = 0; i < cnt[k]; ++i) r[k][i] = ov2_range((const void *)src[k][2 * i], (size_t)src[k][2 * i + 1]);
+    return ov2_ranges_independent(r[0], nrd, r[1], nwr, r[2], nchain_rd, r[3], nchain_wr) ? 1 : 0;
+}
+
+hipStream_t ov2_kf_stream_for(ov2_ctx *c, bool known, const ov2_byte_range *rd, int nrd, const ov2_byte_range *wr, int nwr)
+{
+    const ov2_kf_pending &p = c->stream.pend;
+    if (!p.done) return c->stream;
+    if (known && !p.opaque && ov2_ranges_independent(rd, nrd, wr, nwr, p.rd, 4, p.wr, 3)) return c->stream.unjoined();
+    c->stream.join(OV2_KFJ_CONFLICT);
+    return c->stream;
 }
 
 extern "C" ov2_status ov2_ctx_set_wave_prio(ov2_ctx *c, int level)
@@ -309,6 +356,7 @@ void ov2_pyr_buf_free(ov2_pyr_buf *b)
     (void)hipEventDestroy(b->grad_ev);
     (void)hipEventDestroy(b->free_ev);
     (void)hipEventDestroy(b->free_ev2);
+    (void)hipEventDestroy(b->free_ev3);
     (void)hipFree(b->base);
     if (b->lut) (void)hipFree(b->lut);
     delete b;
@@ -328,6 +376,7 @@ extern "C" ov2_status ov2_ctx_set_pyr_ring(ov2_ctx *c, int n)
     OV2_HIP(c, hipSetDevice(c->device));
     OV2_HIP(c, hipStreamSynchronize(c->stream_pyr));
     OV2_HIP(c, hipStreamSynchronize(c->stream_kf));
+    c->stream.settle(OV2_KFJ_COVERED);
     OV2_HIP(c, hipStreamSynchronize(c->stream.h));
     std::vector<ov2_pyr_buf *> drop;
     {
@@ -392,6 +441,7 @@ extern "C" ov2_status ov2_timer_stop(ov2_ctx *c, float *ms)
 {
     if (!c || !ms) return OV2_ERR_INVALID;
     OV2_HIP(c, hipSetDevice(c->device));   // HIP's current device is per thread
+    c->stream.join(OV2_KFJ_SYNC);   // the interval ends behind a detector chain still pending on the side stream
     OV2_HIP(c, hipEventRecord(c->ev1, c->stream));
     OV2_HIP(c, hipEventSynchronize(c->ev1));
     OV2_HIP(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
@@ -465,6 +515,7 @@ ov2_status ov2_kf_scratch(ov2_ctx *c, size_t bytes, void **out)
 {
     if (bytes > c->kf_scratch_bytes) {
         OV2_HIP(c, hipStreamSynchronize(c->stream_kf));   // the chain that used the old block; the main stream is left alone
+        c->stream.settle(OV2_KFJ_COVERED);                // ... and a chain that was pending has ended
         if (c->kf_scratch_dev) OV2_HIP(c, hipFree(c->kf_scratch_dev));
         c->kf_scratch_dev = nullptr;
         c->kf_scratch_bytes = 0;
@@ -592,6 +643,7 @@ extern "C" ov2_status ov2_ktime_report(ov2_ctx *c, int max_kernels, const char *
     if (!c || !n_out || max_kernels < 0) return OV2_ERR_INVALID;
     OV2_HIP(c, hipStreamSynchronize(c->stream_pyr));
     OV2_HIP(c, hipStreamSynchronize(c->stream_kf));
+    c->stream.settle(OV2_KFJ_COVERED);
     OV2_HIP(c, hipStreamSynchronize(c->stream));
     double tot[OV2_K_MAX] = {0};
     long long cnt[OV2_K_MAX] = {0};

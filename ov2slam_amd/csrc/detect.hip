@@ -547,7 +547,19 @@ __global__ __launch_bounds__(64) void subpix_kernel(const unsigned char *__restr
     if (act && sub == 0) pts[ref] = make_float2(cIx, cIy);
 }
 
-bool ranges_meet(const ov2_byte_range &a, const ov2_byte_range &b) { return a.lo && b.lo && a.lo < b.hi && b.lo < a.hi; }
+// what the chain reads (thresholds, keypoints, their image indices and flags) and writes (thresholds, counts, corners)
+void chain_ranges(int B, const double *d_thresh, int n_cur, const float *d_cur_xy, const int32_t *d_cur_img, const uint8_t *d_cur_valid,
+                  const int32_t *d_n_out, const float *d_out_xy, int out_cap, ov2_byte_range rd[4], ov2_byte_range wr[3])
+{
+    const size_t N = (size_t)n_cur;
+    wr[0] = ov2_range(d_thresh, sizeof(double) * B);
+    wr[1] = ov2_range(d_n_out, sizeof(int) * B);
+    wr[2] = ov2_range(d_out_xy, 8 * (size_t)B * out_cap);
+    rd[0] = wr[0];
+    rd[1] = ov2_range(d_cur_xy, 8 * N);
+    rd[2] = ov2_range(d_cur_img, 4 * N);
+    rd[3] = ov2_range(d_cur_valid, N);
+}
 
 // May the chain start from the event ov2_stereo_matching_dev recorded in front of its first kernel, i.e. run beside that
 // call?  Only when every point below is proven; anything else starts from the tail of the main stream.
@@ -561,17 +573,15 @@ bool fork_at_stereo(const ov2_ctx *c, const ov2_pyr *pyr, int B, const double *d
     const ov2_kf_fork &k = c->kf;
     if (!k.stereo_valid || k.uses != c->stream.uses.load(std::memory_order_relaxed)) return false;
     if (pyr->buf != k.pyr[0] && pyr->buf != k.pyr[1]) return false;
-    auto range = [](const void *p, size_t bytes) { return ov2_byte_range{(const char *)p, p ? (const char *)p + bytes : nullptr}; };
-    const size_t N = (size_t)n_cur;
-    const ov2_byte_range wr[3] = {range(d_thresh, sizeof(double) * B), range(d_n_out, sizeof(int) * B),
-                                  range(d_out_xy, 8 * (size_t)B * out_cap)};
-    const ov2_byte_range rd[4] = {wr[0], range(d_cur_xy, 8 * N), range(d_cur_img, 4 * N), range(d_cur_valid, N)};
-    for (const ov2_byte_range &w : wr) {
-        for (const ov2_byte_range &r : k.rd) if (ranges_meet(w, r)) return false;
-        for (const ov2_byte_range &r : k.wr) if (ranges_meet(w, r)) return false;
-    }
-    for (const ov2_byte_range &r : rd)
-        for (const ov2_byte_range &w : k.wr) if (ranges_meet(r, w)) return false;
+    ov2_byte_range rd[4], wr[3];
+    chain_ranges(B, d_thresh, n_cur, d_cur_xy, d_cur_img, d_cur_valid, d_n_out, d_out_xy, out_cap, rd, wr);
+    return ov2_ranges_independent(rd, 4, wr, 3, k.rd, 5, k.wr, 3);
+}
+
+bool same_ranges(const ov2_byte_range *a, const ov2_byte_range *b, int n)
+{
+    for (int i = 0; i < n; ++i)
+        if (a[i].lo != b[i].lo || a[i].hi != b[i].hi) return false;
     return true;
 }
 
@@ -583,10 +593,18 @@ bool fork_at_stereo(const ov2_ctx *c, const ov2_pyr *pyr, int B, const double *d
 // device-side counters.
 //
 // Where it runs: with the keyframe overlap on (ov2_ctx_set_kf_overlap, OV2_KF_OVERLAP; the default) the chain is enqueued on
-// the context's keyframe side stream and the main stream waits for its end, so the call is ordered like any other.  When
-// the call directly follows ov2_stereo_matching_dev on the same context and touches none of that call's arrays
-// (fork_at_stereo above states the rule), the chain starts in front of the stereo kernels and runs beside them.  With
-// the overlap off the chain is enqueued on the main stream with no events, as before.
+// the context's keyframe side stream.  When the call directly follows ov2_stereo_matching_dev on the same context and
+// touches none of that call's arrays (fork_at_stereo above states the rule), the chain starts in front of the stereo
+// kernels and runs beside them.
+//
+// Where it ends: the call leaves the chain pending (ov2_main_stream::pend: its end event and the byte ranges it reads and
+// writes) instead of making the main stream wait.  The first later enqueue on the main stream waits for the chain, so every
+// call stays ordered behind this one -- except ov2_klt_tracking_frame_dev and ov2_stereo_matching_dev, which enqueue
+// beside the chain when none of their arrays meets the chain's (ov2_kf_stream_for).  The pyramid the chain reads is kept
+// from reuse by a mark of its own (ov2_pyr_buf::free_ev3).  ov2_ctx_synchronize, ov2_timer_stop and the context's
+// destructor complete a pending chain; a second detector call runs behind it on the side stream.  With
+// ov2_ctx_set_kf_lazy_join(0) (OV2_KF_LAZY_JOIN=0), behind a failed launch and on a pyramid of another context the call
+// joins the chain itself, as it always did.  With the overlap off the chain is enqueued on the main stream with no events.
 extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, int cell, int mode, double *d_thresh,
                                                 int n_cur, const float *d_cur_xy, const int32_t *d_cur_img,
                                                 const uint8_t *d_cur_valid, const int *roi, int do_subpix,
@@ -626,8 +644,8 @@ extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, 
     const size_t off_ref = off_work + up(sizeof(int2) * 4 * (size_t)list_cap), off_pimg = off_ref + up(sizeof(int) * (size_t)nb * B);
     const size_t total = off_pimg + up(sizeof(int) * (size_t)nb * B);
     // the chain runs on the keyframe side stream with a scratch block of its own, between two events: it starts from
-    // kf.fork and the main stream waits for kf.done before this call returns, so the call stays ordered behind every
-    // earlier call on the context and in front of every later one
+    // kf.fork, so the call stays ordered behind every earlier call on the context, and ends at kf.done, which the main
+    // stream waits for in front of the first later call that is not proven apart from the chain (see above)
     const bool side = c->kf_overlap != 0 && c->stream_kf != c->stream.h;
     const bool early = side && fork_at_stereo(c, pyr, B, d_thresh, n_cur, d_cur_xy, d_cur_img, d_cur_valid, d_n_out, d_out_xy, out_cap);
     c->kf.stereo_valid = false;
@@ -680,9 +698,35 @@ extern "C" ov2_status ov2_detect_grid_batch_dev(ov2_ctx *c, const ov2_pyr *pyr, 
                    pt_img, pt_ref, cnt + 4, L.istride, w, h, reinterpret_cast<float2 *>(d_out_xy), 30, 0.01 * 0.01, wts, c->wave_prio);
     }
     const hipError_t le = hipGetLastError();
-    if (side) {   // joined even behind a failed launch: nothing may stay behind on the side stream unordered
-        OV2_HIP(c, hipEventRecord(c->kf.done, st));
-        OV2_HIP(c, hipStreamWaitEvent(c->stream.h, c->kf.done, 0));
+    if (side) {
+        // The end of the chain.  The main stream is not made to wait here: the chain is noted as pending and the first
+        // call that needs the stream behind it joins (ov2_main_stream).  An earlier chain still noted is not joined
+        // either: this one runs behind it on the same stream and, writing the same arrays, stands for both; on other
+        // arrays the note turns opaque unless the earlier chain has ended.  The eager setting and a failed launch join at
+        // once, and an event that could not be recorded leaves nothing pending: the host waits for the side stream.
+        ov2_main_stream &ms = c->stream;
+        ov2_kf_pending &p = ms.pend;
+        ov2_byte_range rd[4], wr[3];
+        chain_ranges(B, d_thresh, n_cur, d_cur_xy, d_cur_img, d_cur_valid, d_n_out, d_out_xy, out_cap, rd, wr);
+        bool opaque = false;
+        if (p.done) {
+            opaque = p.opaque || !(same_ranges(p.rd, rd, 4) && same_ranges(p.wr, wr, 3));
+            if (opaque && hipEventQuery(c->kf.done) == hipSuccess) opaque = false;   // still the earlier chain's record
+            p.done = nullptr;
+            ms.kfj[OV2_KFJ_COVERED].fetch_add(1, std::memory_order_relaxed);
+        }
+        if (hipEventRecord(c->kf.done, st) != hipSuccess) {
+            (void)hipStreamSynchronize(st);
+            ms.joined_seq.store(p.seq, std::memory_order_release);
+            return ov2_set_err(c, OV2_ERR_HIP, "hipEventRecord(kf.done) failed");
+        }
+        p.seq = (unsigned long long)ms.kfj[OV2_KFJ_STARTED].fetch_add(1, std::memory_order_relaxed) + 1;
+        p.opaque = opaque;
+        for (int i = 0; i < 4; ++i) p.rd[i] = rd[i];
+        for (int i = 0; i < 3; ++i) p.wr[i] = wr[i];
+        p.done = c->kf.done;
+        if (pyr->ctx == c) pyr->buf->kf_seq = p.seq;   // the release of this pyramid must know a side-stream reader
+        if (!c->kf_lazy_join || le != hipSuccess || pyr->ctx != c) ms.join(OV2_KFJ_EAGER);
     }
     if (le != hipSuccess) return ov2_set_err(c, OV2_ERR_HIP, "detector chain launch failed: %s", hipGetErrorString(le));
     return OV2_OK;
@@ -726,6 +770,7 @@ extern "C" ov2_status ov2_detect_grid_batch(ov2_ctx *c, const ov2_pyr *pyr, int 
                                   (const int32_t *)(dp + o_ci), nullptr, roi, do_subpix, (int32_t *)(dp + o_no),
                                   (float *)(dp + o_ox), out_cap);
     if (s != OV2_OK) return s;
+    st = c->stream;   // the copies read what the chain writes: taken again, the stream is behind the chain's end (ov2_main_stream)
     OV2_HIP(c, hipMemcpyAsync(hp, dp, o_ci, hipMemcpyDeviceToHost, st));          // thresholds + counts
     OV2_HIP(c, hipMemcpyAsync(hp + o_ox, dp + o_ox, 8 * (size_t)B * out_cap, hipMemcpyDeviceToHost, st));
     OV2_HIP(c, hipStreamSynchronize(st));

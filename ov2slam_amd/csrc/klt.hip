@@ -1421,6 +1421,14 @@ ov2_status ov2_klt_two_stage_dev(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr 
     unsigned *next_counts = c->klt_counts[c->klt_counts_cur ^ 1];
     const int next_words = (int)c->klt_counts_words;
     int *list_a = (int *)scr, *list_b = list_a + n, *list_c = list_b + n;
+    // A detector chain still pending on the keyframe side stream keeps running beside this call when nothing the call reads
+    // meets what the chain writes and nothing it writes meets what the chain reads or writes; any overlap joins the chain
+    // first (ov2_kf_stream_for).  The lists, counters and hand-over records are the context's own, apart from the chain's scratch.
+    const size_t N = (size_t)n;
+    const ov2_byte_range kf_rd[4] = {ov2_range(d_kps, 8 * N), ov2_range(d_prior, 8 * N), ov2_range(d_has_prior, N), ov2_range(d_img_idx, 4 * N)};
+    const ov2_byte_range kf_wr[4] = {ov2_range(d_out_xy, 8 * N), ov2_range(d_out_status, N), ov2_range(d_p3p_req, sizeof(int32_t) * (size_t)B),
+                                     ov2_range(d_iters, 8 * N)};
+    const hipStream_t ms = ov2_kf_stream_for(c, true, kf_rd, 4, kf_wr, 4);
     if (c->kf.want_stereo_ev) {   // ov2_stereo_matching_dev: the point a following detector call may fork from (detect.hip)
         OV2_HIP(c, hipEventRecord(c->kf.fork, c->stream.h));
         c->kf.want_stereo_ev = false;
@@ -1440,19 +1448,19 @@ ov2_status ov2_klt_two_stage_dev(ov2_ctx *c, const ov2_pyr *prev, const ov2_pyr 
     do {                                                                                                        \
         /* two disjoint lists of the n keypoints: groups of the one + groups of the other <= ceil(n / KPW) + 2 */ \
         const dim3 tgrid((n + klt_map<G>::KPW - 1) / klt_map<G>::KPW + 2);                                      \
-        OV2_LAUNCH(c, OV2_K_DETECT + 4, klt_compact_kernel, cgrid, dim3(256), 0, c->stream, n, d_has_prior,     \
+        OV2_LAUNCH_ON(c, OV2_K_DETECT + 4, ms, klt_compact_kernel, cgrid, dim3(256), 0, ms, n, d_has_prior,     \
                    d_iters, list_a, list_b, live_cnt, d_p3p_req, B, P.wave_prio);                               \
         if (split_k >= 0)                                                                                       \
-            OV2_LAUNCH(c, OV2_K_KLT_STAGE1, (klt_stage1_kernel<W, G, true>), tgrid, dim3(64), 0, c->stream,     \
+            OV2_LAUNCH_ON(c, OV2_K_KLT_STAGE1, ms, (klt_stage1_kernel<W, G, true>), tgrid, dim3(64), 0, ms,     \
                        prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps),          \
                        reinterpret_cast<const float2 *>(d_prior), d_img_idx, reinterpret_cast<float2 *>(d_out_xy), \
                        d_out_status, counts, d_iters, list_a, list_b, live_cnt, list_c, b_word1, split_k, hand); \
         else                                                                                                    \
-            OV2_LAUNCH(c, OV2_K_KLT_STAGE1, (klt_stage1_kernel<W, G, false>), tgrid, dim3(64), 0, c->stream,    \
+            OV2_LAUNCH_ON(c, OV2_K_KLT_STAGE1, ms, (klt_stage1_kernel<W, G, false>), tgrid, dim3(64), 0, ms,    \
                        prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps),          \
                        reinterpret_cast<const float2 *>(d_prior), d_img_idx, reinterpret_cast<float2 *>(d_out_xy), \
                        d_out_status, counts, d_iters, list_a, list_b, live_cnt, list_c, b_word1, split_k, hand); \
-        OV2_LAUNCH(c, OV2_K_KLT_STAGE2, (klt_stage2_kernel<W, G>), tgrid, dim3(64), 0, c->stream,               \
+        OV2_LAUNCH_ON(c, OV2_K_KLT_STAGE2, ms, (klt_stage2_kernel<W, G>), tgrid, dim3(64), 0, ms,               \
                    prev->buf->view, cur->buf->view, P, n, reinterpret_cast<const float2 *>(d_kps), d_img_idx,   \
                    reinterpret_cast<float2 *>(d_out_xy), d_out_status, counts, d_p3p_req, d_iters, list_c,      \
                    live_cnt, B, next_counts, next_words, list_b, b_word2,                                       \

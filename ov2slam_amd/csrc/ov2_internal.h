@@ -51,6 +51,12 @@ struct ov2_pyr_buf {  // pooled allocation; geometry key = (w,h,pad,max_level,ba
     bool has_free_ev;
     hipEvent_t free_ev2; // recorded on ANOTHER context's main stream by ov2_pyr_release_from (the mapper's readers); the next build waits on it too
     bool has_free_ev2;
+    // A detector chain of the owning ctx that reads the buffer from the keyframe side stream: free_ev does not cover it
+    // while the main stream has not been put behind the chain (ov2_main_stream::joined_seq < kf_seq), so the release then
+    // marks the side stream as well and the next build waits for that mark too.
+    unsigned long long kf_seq;   // the last chain of the owning ctx that reads this build (0: none)
+    hipEvent_t free_ev3; // recorded on the owning ctx's keyframe side stream when the last handle is released under a pending chain
+    bool has_free_ev3;
     // the int16 (Ix, Iy) planes are written on demand (ov2_pyr_need_grad): the 9 x 9 tracking path derives the Scharr
     // values inside its kernel and never reads them.  Both fields are guarded by the owning ctx's mutex.
     bool grad_built;
@@ -67,25 +73,98 @@ enum ov2_kernel_id {
 };
 extern const char *ov2_kernel_names[OV2_K_MAX];
 
+struct ov2_byte_range {
+    const char *lo, *hi;   // [lo, hi); lo == nullptr: absent
+};
+
+static inline ov2_byte_range ov2_range(const void *p, size_t bytes)
+{
+    return ov2_byte_range{(const char *)p, p ? (const char *)p + bytes : nullptr};
+}
+
+static inline bool ranges_meet(const ov2_byte_range &a, const ov2_byte_range &b) { return a.lo && b.lo && a.lo < b.hi && b.lo < a.hi; }
+
+// May a call that reads rd[] and writes wr[] run beside one that reads ord[] and writes owr[]?  Nothing the one writes may
+// meet anything the other reads or writes.  An absent range meets nothing: the caller decides what an absent array means.
+static inline bool ov2_ranges_independent(const ov2_byte_range *rd, int nrd, const ov2_byte_range *wr, int nwr,
+                                          const ov2_byte_range *ord, int nord, const ov2_byte_range *owr, int nowr)
+{
+    for (int i = 0; i < nwr; ++i) {
+        for (int j = 0; j < nord; ++j) if (ranges_meet(wr[i], ord[j])) return false;
+        for (int j = 0; j < nowr; ++j) if (ranges_meet(wr[i], owr[j])) return false;
+    }
+    for (int i = 0; i < nrd; ++i)
+        for (int j = 0; j < nowr; ++j) if (ranges_meet(rd[i], owr[j])) return false;
+    return true;
+}
+
+// ov2_ctx_kf_join_stats: what became of the detector chains started on the keyframe side stream
+enum ov2_kf_join_stat {
+    OV2_KFJ_STARTED = 0,  // chains enqueued on the side stream
+    OV2_KFJ_CONFLICT,     // joined by a tracking / stereo call whose arrays meet the chain's (or could not be proven apart)
+    OV2_KFJ_DEFAULT,      // joined by the first other use of the main stream
+    OV2_KFJ_SYNC,         // completed by ov2_ctx_synchronize / ov2_timer_stop
+    OV2_KFJ_COVERED,      // never joined: the next chain (same stream, same arrays) or a synchronisation of the side stream covered it
+    OV2_KFJ_EAGER,        // joined inside the detector call (ov2_ctx_set_kf_lazy_join(0), or a failed launch)
+    OV2_KFJ_PYR,          // pyramid builds that waited for a chain still reading the buffer they reuse
+    OV2_KFJ_N
+};
+
+// A detector chain on the keyframe side stream whose end the main stream has not been put behind (detect.hip).
+struct ov2_kf_pending {
+    hipEvent_t done = nullptr;           // the chain's end (ov2_kf_fork::done); nullptr: no chain is pending
+    unsigned long long seq = 0;          // number of the chain, 1 = the first of the context
+    bool opaque = false;                 // an earlier chain on other arrays may still run under this note: no call is proven apart
+    ov2_byte_range rd[4], wr[3];         // what the chain reads (thresholds, keypoints, image indices, flags) / writes
+                                         //   (thresholds, counts, corners up to out_cap)
+};
+
 // The main stream of a context.  It converts to hipStream_t wherever one is expected, and every conversion counts as a use:
 // ov2_detect_grid_batch_dev may fork its chain from the event ov2_stereo_matching_dev left in front of its kernels only
 // while NOTHING has been enqueued on this stream since (ov2_kf_fork::uses), and a count taken at the one place every
 // enqueue passes through cannot miss a call site.  Pure ordering bookkeeping (event records and waits of the pyramid
 // pool, which move no data) reads `.h` instead and does not count.
+//
+// The same place ends a pending detector chain: while one is pending the first conversion puts the stream behind the
+// chain's end, so every call is ordered behind the chain exactly as if the detector call had joined it.  Only a call that
+// has proven its arrays apart from the chain's (ov2_kf_stream_for) enqueues through unjoined() and leaves the chain
+// running beside it.
 struct ov2_main_stream {
     hipStream_t h = nullptr;
     mutable std::atomic<unsigned long long> uses{0};
-    operator hipStream_t() const { uses.fetch_add(1, std::memory_order_relaxed); return h; }
+    mutable ov2_kf_pending pend;
+    mutable std::atomic<unsigned long long> joined_seq{0};   // the last chain this stream is behind, or that has ended
+    mutable std::atomic<long long> kfj[OV2_KFJ_N] = {};
+    operator hipStream_t() const
+    {
+        uses.fetch_add(1, std::memory_order_relaxed);
+        if (pend.done) join(OV2_KFJ_DEFAULT);
+        return h;
+    }
+    hipStream_t unjoined() const { uses.fetch_add(1, std::memory_order_relaxed); return h; }
+    // puts the stream behind the pending chain (a wait the device cannot take is taken by the host)
+    void join(int why) const
+    {
+        if (!pend.done) return;
+        if (hipStreamWaitEvent(h, pend.done, 0) != hipSuccess) (void)hipEventSynchronize(pend.done);
+        settle(why);
+    }
+    // the pending chain has ended, or the stream is behind it: nothing is pending any more
+    void settle(int why) const
+    {
+        if (!pend.done) return;
+        joined_seq.store(pend.seq, std::memory_order_release);
+        pend.done = nullptr;
+        kfj[why].fetch_add(1, std::memory_order_relaxed);
+    }
 };
 
-struct ov2_byte_range {
-    const char *lo, *hi;   // [lo, hi); lo == nullptr: absent
-};
-
-// keyframe side stream: the detector chain runs here beside the stereo matching of the same keyframe (detect.hip)
+// keyframe side stream: the detector chain runs here beside the stereo matching of the same keyframe and, until a call
+// needs what it reads or writes, beside the calls that follow (detect.hip; the pending end is ov2_main_stream::pend)
 struct ov2_kf_fork {
     hipEvent_t fork, done;               // fork: point of the main stream the chain starts from (recorded by the detector call at
-                                         //   the tail, or by ov2_stereo_matching_dev in front of its first kernel); done: end of the chain
+                                         //   the tail, or by ov2_stereo_matching_dev in front of its first kernel); done: end of the
+                                         //   chain, waited for by the main stream when a call joins it (ov2_main_stream::join)
     bool want_stereo_ev;                 // set by ov2_stereo_matching_dev for the two-stage tracking call it makes
     bool stereo_valid;                   // `fork` is the stereo call's, and `uses` and the ranges below describe that call
     unsigned long long uses;             // ov2_main_stream::uses right behind that call's last enqueue
@@ -104,6 +183,7 @@ struct ov2_ctx {
     hipStream_t stream_pyr;              // pyramid builds run here so that frame t+1's pyramid overlaps frame t's KLT
     hipStream_t stream_kf;               // keyframe side stream: the detector chain while kf_overlap is on (always a stream of its own)
     int kf_overlap;                      // ov2_ctx_set_kf_overlap / OV2_KF_OVERLAP: 0 = the chain stays on the main stream
+    int kf_lazy_join;                    // ov2_ctx_set_kf_lazy_join / OV2_KF_LAZY_JOIN: 0 = the detector call itself joins its chain
     ov2_kf_fork kf;
     void *kf_scratch_dev;                // scratch of the chain on the side stream (grown on demand; growth waits for
     size_t kf_scratch_bytes;             //   the side stream alone)
@@ -186,6 +266,10 @@ void ov2_pyr_buf_free(ov2_pyr_buf *b);
 ov2_status ov2_scratch(ov2_ctx *ctx, size_t bytes, void **out);
 // the same for the keyframe side stream's own buffer
 ov2_status ov2_kf_scratch(ov2_ctx *ctx, size_t bytes, void **out);
+// The main stream for a call that reads rd[] and writes wr[]: while a detector chain is pending and every range is proven
+// apart from the chain's, the stream as it is (the chain keeps running beside the call); otherwise the stream behind the
+// chain's end.  `known` = false (an array of the call has no known extent) joins as well.
+hipStream_t ov2_kf_stream_for(ov2_ctx *ctx, bool known, const ov2_byte_range *rd, int nrd, const ov2_byte_range *wr, int nwr);
 // pinned host block of `bytes` and a device block of the same size (grown on demand, kept by the ctx)
 ov2_status ov2_staging(ov2_ctx *ctx, size_t bytes, void **host, void **dev);
 // ov2_ctx_destroy: free the device side of a map that outlives its ctx (the handle stays valid for ov2_map_destroy)

@@ -971,7 +971,8 @@ ov2_status acquire_buf(ov2_ctx *c, int w, int h, int pad, int max_level, int bat
             ov2_pyr_buf *b = c->pool[i];
             if (!(b->w == w && b->h == h && b->pad == pad && b->max_level == max_level && b->batch == batch)) continue;
             if ((!b->has_free_ev || hipEventQuery(b->free_ev) == hipSuccess) &&
-                (!b->has_free_ev2 || hipEventQuery(b->free_ev2) == hipSuccess)) {
+                (!b->has_free_ev2 || hipEventQuery(b->free_ev2) == hipSuccess) &&
+                (!b->has_free_ev3 || hipEventQuery(b->free_ev3) == hipSuccess)) {
                 c->pool.erase(c->pool.begin() + i);
                 ++c->pyr_acquires[0];
                 *out = b;
@@ -1027,13 +1028,16 @@ ov2_status acquire_buf(ov2_ctx *c, int w, int h, int pad, int max_level, int bat
     if (hipEventCreateWithFlags(&b->ready_ev, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
         hipEventCreateWithFlags(&b->grad_ev, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
         hipEventCreateWithFlags(&b->free_ev, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
-        hipEventCreateWithFlags(&b->free_ev2, OV2_ORDER_EVENT_FLAGS) != hipSuccess) {
+        hipEventCreateWithFlags(&b->free_ev2, OV2_ORDER_EVENT_FLAGS) != hipSuccess ||
+        hipEventCreateWithFlags(&b->free_ev3, OV2_ORDER_EVENT_FLAGS) != hipSuccess) {
         (void)hipFree(b->base);
         delete b;
         return ov2_set_err(c, OV2_ERR_HIP, "hipEventCreate failed");
     }
     b->has_free_ev = false;
     b->has_free_ev2 = false;
+    b->has_free_ev3 = false;
+    b->kf_seq = 0;
     b->grad_built = false;
     b->build_seq = b->ready_waited_seq = b->grad_waited_seq = 0;
     v.base = b->base;
@@ -1072,6 +1076,12 @@ extern "C" ov2_status ov2_pyramid_build_images(ov2_ctx *c, const ov2_images *im,
         OV2_HIP(c, hipStreamWaitEvent(sp, buf->free_ev2, 0));
         buf->has_free_ev2 = false;
     }
+    if (buf->has_free_ev3) {   // a detector chain that read it from the keyframe side stream beside the main stream (ov2_pyr_release)
+        OV2_HIP(c, hipStreamWaitEvent(sp, buf->free_ev3, 0));
+        buf->has_free_ev3 = false;
+        c->stream.kfj[OV2_KFJ_PYR].fetch_add(1, std::memory_order_relaxed);
+    }
+    buf->kf_seq = 0;
 
     float inv_tw = 0.f, inv_th = 0.f;
     if (use_clahe) {
@@ -1196,6 +1206,12 @@ extern "C" void ov2_pyr_release(ov2_pyr *p)
         // when those readers were enqueued on the same ctx.  Cross-ctx readers must synchronise before release.
         // every consumer of this pyramid was enqueued on the main stream before this release: mark that point
         if (hipEventRecord(p->buf->free_ev, p->ctx->stream.h) == hipSuccess) p->buf->has_free_ev = true;
+        // ... except a detector chain that reads it on the keyframe side stream while the main stream is not behind that
+        // chain: everything the side stream holds is marked too (a mark that cannot be recorded is waited out here)
+        if (p->buf->kf_seq > p->ctx->stream.joined_seq.load(std::memory_order_acquire)) {
+            if (hipEventRecord(p->buf->free_ev3, p->ctx->stream_kf) == hipSuccess) p->buf->has_free_ev3 = true;
+            else (void)hipStreamSynchronize(p->ctx->stream_kf);
+        }
         std::lock_guard<std::mutex> g(p->ctx->mu);
         p->ctx->pool.push_back(p->buf);
         delete p;

@@ -294,7 +294,11 @@ extern "C" ov2_status ov2_stereo_matching_dev(ov2_ctx *c, const ov2_pyr *left, c
     G.wave_prio = c->wave_prio;
     G.rcam = ov2_cam_normalised(right_cam);
     if (G.rcam.model < 0 || G.rcam.model > 2) return ov2_set_err(c, OV2_ERR_INVALID, "unknown lens model %d", G.rcam.model);
-    OV2_LAUNCH(c, K_GATE, epi_gate_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, G,
+    // the gate beside a detector chain still pending, by the rule of the tracking call in front of it (ov2_kf_stream_for)
+    const ov2_byte_range gate_rd[2] = {ov2_range(d_kps_xy, 8 * (size_t)n), ov2_range(d_lunpx_xy, 8 * (size_t)n)};
+    const ov2_byte_range gate_wr[2] = {ov2_range(d_out_rxy, 8 * (size_t)n), ov2_range(d_out_status, (size_t)n)};
+    const hipStream_t ms = ov2_kf_stream_for(c, true, gate_rd, 2, gate_wr, 2);
+    OV2_LAUNCH_ON(c, K_GATE, ms, epi_gate_kernel, dim3((n + 255) / 256), dim3(256), 0, ms, n, G,
                reinterpret_cast<const float2 *>(d_kps_xy), reinterpret_cast<const float2 *>(d_lunpx_xy),
                reinterpret_cast<float2 *>(d_out_rxy), d_out_status);
     OV2_HIP(c, hipGetLastError());

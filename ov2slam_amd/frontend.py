@@ -99,6 +99,17 @@ class Context:
         _check(self.h, self.lib.ov2_ctx_get_cu_mask(self.h, int(words), out))
         return np.array(out, np.uint32)
 
+    def set_kf_lazy_join(self, on):
+        """ov2_ctx_set_kf_lazy_join: the detector chain stays pending on the side stream until a call needs the main stream
+        behind it (default on); off = the detector call joins its chain itself"""
+        _check(self.h, self.lib.ov2_ctx_set_kf_lazy_join(self.h, int(bool(on))))
+
+    def kf_join_stats(self):
+        """ov2_ctx_kf_join_stats: dict(started, conflict, default, sync, covered, eager, pyr_waits, pending)"""
+        out = (C.c_int64 * 8)()
+        _check(self.h, self.lib.ov2_ctx_kf_join_stats(self.h, out))
+        return dict(zip(("started", "conflict", "default", "sync", "covered", "eager", "pyr_waits", "pending"), (int(v) for v in out)))
+
     def set_pyr_ring(self, n):
         """ov2_ctx_set_pyr_ring: released pyramid buffers of one geometry, readers still pending, that the pool holds before
         a build reuses the oldest (1 .. 8, default 3); lowering it synchronises and frees the buffers beyond n"""

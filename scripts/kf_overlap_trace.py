@@ -10,6 +10,8 @@ A second table splits the stereo interval kernel by kernel (klt_compact_kernel, 
 epi_gate_kernel and the gaps between them) with the detector chain's interval, the period, the idle time of the tracking
 kernels' queue and that of the pyramid builds' queue (over the period, and the part of it inside the stereo interval) beside
 it, and closes with the mean and the lower quartile / median / upper quartile of every column.
+A third table shows what follows each keyframe: the tracking queue's idle time in front of the next plain tracking call,
+cornerSubPix, and the klt_stage1_kernel launch it may run beside (the lazy join of the chain, detect.hip).
 usage: kf_overlap_trace.py <kernel_trace.csv or a directory holding one> [more traces ...]"""
 import csv
 import glob
@@ -93,6 +95,7 @@ def report(path):
     if n:
         print("mean " + "  ".join(f"{k} {v / n:.1f}" for k, v in tot.items()) + f"  (us, {n} periods)")
     split(rows, kfs)
+    after_keyframe(rows, kfs)
 
 
 SPLIT = ("klt_compact_kernel", "klt_stage1_kernel", "klt_stage2_kernel", "epi_gate_kernel")
@@ -159,6 +162,35 @@ def split(rows, kfs):
     if table:
         n = len(table)
         print("mean split " + "  ".join(f"{k} {sum(c) / n:.1f}" for k, c in zip(names, zip(*table))) + f"  (us, {n} periods)")
+        print("lower quartile / median / upper quartile  " +
+              "  ".join(f"{k} {'/'.join(f'{q:.1f}' for q in quartiles(c))}" for k, c in zip(names, zip(*table))))
+
+
+def after_keyframe(rows, kfs):
+    """what follows a keyframe: the idle time of the tracking queue between the stereo call's epi_gate_kernel and the next
+    plain call's klt_compact_kernel, cornerSubPix, the klt_stage1_kernel of that plain call beside the mean of the period's
+    other plain calls, and how far subpix_kernel runs past the start of that launch (negative: it ended before)"""
+    us = lambda ns: ns / 1000.0
+    names = ("idle_before_next_call", "subpix", "next_stage1", "other_stage1_mean", "subpix_past_next_stage1_start")
+    print("kf  " + "  ".join(f"{c:>30s}" for c in names))
+    table = []
+    for k, (i0, i1) in enumerate(kfs):
+        if k + 1 >= len(kfs):
+            continue
+        s0, gate_end, nxt, q = rows[i0][0], rows[i1][1], rows[kfs[k + 1][0]][0], rows[i0][3]
+        plain = [r for r in rows if r[3] == q and r[2] in ("klt_compact_kernel", "klt_stage1_kernel") and gate_end <= r[0] < nxt]
+        compacts = [r for r in plain if r[2] == "klt_compact_kernel"]
+        stage1 = [r for r in plain if r[2] == "klt_stage1_kernel"]
+        sub = [r for r in rows if r[2] == "subpix_kernel" and s0 <= r[0] < nxt]
+        if not compacts or len(stage1) < 2 or not sub:
+            continue
+        vals = [us(idle(rows, q, gate_end, compacts[0][0])), us(sub[0][1] - sub[0][0]), us(stage1[0][1] - stage1[0][0]),
+                sum(us(r[1] - r[0]) for r in stage1[1:]) / (len(stage1) - 1), us(sub[0][1] - stage1[0][0])]
+        print(f"{k:2d}  " + "  ".join(f"{v:30.1f}" for v in vals))
+        table.append(vals)
+    if table:
+        n = len(table)
+        print("mean after keyframe " + "  ".join(f"{k} {sum(c) / n:.1f}" for k, c in zip(names, zip(*table))) + f"  (us, {n} periods)")
         print("lower quartile / median / upper quartile  " +
               "  ".join(f"{k} {'/'.join(f'{q:.1f}' for q in quartiles(c))}" for k, c in zip(names, zip(*table))))
 
