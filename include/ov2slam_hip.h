@@ -1152,6 +1152,67 @@ ov2_status ov2_map_merge_points_batch_dev(ov2_ctx *ctx, int B, ov2_map *const *m
                                           const int32_t *d_n_pairs /* B, or NULL */, ov2_map_merge *out /* B, or NULL */,
                                           uint8_t *d_pair_status /* or NULL */);
 
+/* Optimizer::structureOnlyBA(vlm2optids) (src/optimizer.cpp:2594-2781) on the tables of B map mirrors of one context, for maps
+ * that have no host objects beside them: the statement that follows the merges of an accepted loop (src/loop_closer.cpp:353).
+ * Map b owns the ids [lm_off[b], lm_off[b + 1]) of lmid (lm_off[0] = 0) and works on its tables as they are when the kernels
+ * run.  EIGHT launches whatever B and the list lengths are (map = blockIdx.y; sizes come from device memory): the clear of the
+ * merge stage's scratch block, which this stage borrows, the mark of the listed landmarks, the count of their live rows, the
+ * three launches of the exclusive scan over the landmarks, the scatter of those rows into a per-landmark index, and ONE solver
+ * launch -- one workgroup per map -- that selects, runs the whole Levenberg-Marquardt loop, writes the points and the map's
+ * record.  A map with an empty list costs no work and gets a zero record with OV2_BA_TERM_SKIPPED.
+ *
+ * Selection, per map: a listed id enters when it lies in [0, max_lm), is OV2_LM_ALIVE and OV2_LM_3D and has at least one live
+ * row (row, keyframe and landmark alive); every other entry counts in n_skipped.  An id listed twice enters once, at its first
+ * place, and its later occurrences count in n_skipped.  n_listed = n_lm + n_skipped.  Every live row of an entered point gives
+ * one OV2_BA_L_XYZ block from its left pixel and, where it carries the stereo flag, one OV2_BA_R_XYZ block from its right
+ * pixel, both with sigma = 2^scale (:2692-2729); n_res counts the blocks.  The poses (from the keyframe table), the
+ * calibrations and T_rl (cam[b], laid out as in ov2_ba_problem) are constant.
+ * Departures from the reference: (1) there a repeated id doubles its residual blocks, which leaves the point's own minimiser
+ * where it is and only changes its weight in the joint acceptance test; (2) there a point that is not 3D would enter and
+ * start from the origin -- here it is passed over.
+ *
+ * Solve: ONE problem per map over all its points jointly, as Ceres solves it -- one trust-region radius and one accept /
+ * reject decision per iteration, Jacobi scaling, Huber loss through the Ceres corrector, o->max_iters (the reference's 10)
+ * iterations, function_tolerance and the other fields of ov2_ba_options as ov2_ba_solve reads them; l2_refine, l2_max_iters
+ * and chi2_th are ignored.  All poses being constant, the normal equations are one 3 x 3 system per point.  A point's rows
+ * are summed in ascending keyframe order, left block before right block, the points in list order of first occurrence, every
+ * reduction in a fixed order: a map's points, record and log are bitwise the same whatever else the batch holds, wherever
+ * the map stands in it, from run to run, and for two tables that hold the same rows in a different order.
+ * Update: lm_xyz of every entered point takes the minimiser's final state (:2769-2777), the last accepted x -- also when the
+ * run ends OV2_BA_TERM_FAILURE.  Nothing else changes: no state, no pose, no row, no point that did not enter.
+ * The record: the four counts, termination (OV2_BA_TERM_SKIPPED when n_res == 0, costs 0 and no log), the costs and the
+ * iteration log, iteration 0 included, zeros behind n_log.
+ *
+ * Host form: lmid is a host array staged through the context's pinned block; with out == NULL the call is fully
+ * asynchronous, otherwise it synchronises once.  _dev form: d_lmid / d_n / d_status are DEVICE pointers in the shape
+ * ov2_map_merge_points_batch_dev leaves behind (its d_new_lmid, d_n_pairs, d_pair_status), lm_off stays a HOST array and gives
+ * every map's SEGMENT; d_n (B, or NULL = whole segments) is how many entries of the segment are looked at (clamped to
+ * [0, segment]) and, with d_status, an entry counts if and only if its byte is OV2_MERGE_DONE -- the others are neither
+ * listed nor skipped.  cam and o are host pointers in both forms.  The _dev form synchronises only when `out` is given: pose
+ * graph update -> merge -> structure-only BA of a mirror-only map is three enqueues on one stream.
+ *
+ * The solver keeps O(listed entries) of state per map in a block of the map's own that the first call allocates (a map that
+ * never calls allocates nothing); there is no per-row workspace.  Like the merge, a call ends what the last set-up of a map
+ * with a NON-EMPTY segment can be updated from (ov2_map_local_ba_update_batch then refuses the map); a map with an empty
+ * segment is left alone.  A state saved by ov2_map_save_state covers lm_xyz and stays restorable.  B = 0 and all-empty lists
+ * are OV2_OK.  Refused with OV2_ERR_INVALID before anything is enqueued, from host state only: B < 0 or a null array that a
+ * non-empty call needs; an lm_off that does not start at 0 or that decreases; a map listed twice; a map of another context;
+ * o->max_iters outside [0, OV2_BA_MAX_LOG - 1]. */
+typedef struct ov2_map_sba_cam { double calib_l[4], calib_r[4], T_rl[7]; } ov2_map_sba_cam;   /* as in ov2_ba_problem */
+typedef struct ov2_map_sba {
+    int32_t n_listed, n_lm, n_skipped, n_res;   /* entries counted, points that entered, entries passed over, residual blocks */
+    int32_t termination, n_log;                 /* OV2_BA_TERM_*; OV2_BA_TERM_SKIPPED when n_res == 0 */
+    double initial_cost, final_cost;
+    ov2_ba_iter log[OV2_BA_MAX_LOG];            /* iteration 0 included, zeros behind n_log */
+} ov2_map_sba;
+ov2_status ov2_map_structure_ba_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *lm_off /* B + 1 */,
+                                      const int32_t *lmid, const ov2_map_sba_cam *cam /* B */, const ov2_ba_options *o,
+                                      ov2_map_sba *out /* B, or NULL */);
+ov2_status ov2_map_structure_ba_batch_dev(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *lm_off /* HOST, B + 1 */,
+                                          const int32_t *d_lmid, const int32_t *d_n /* B, or NULL */,
+                                          const uint8_t *d_status /* or NULL */, const ov2_map_sba_cam *cam /* B */,
+                                          const ov2_ba_options *o, ov2_map_sba *out /* B, or NULL */);
+
 /* Test / bench support.  ov2_map_save_state keeps a device copy of the mutable state of the tables (poses, landmark points
  * and states, observation flags); ov2_map_restore_state_batch rewinds B maps to it in one launch, asynchronously (every
  * bench job starts from the same noisy map, as a new keyframe of a live sequence would bring it).  ov2_map_download copies

@@ -101,6 +101,8 @@ SIGNATURES = {
     "ov2_map_pose_graph_update_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     "ov2_map_merge_points_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "ov2_map_merge_points_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ov2_map_structure_ba_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "ov2_map_structure_ba_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ov2_match_pairs_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ov2_map_enable_match_columns": (C.c_int, [vp]),
     "ov2_map_download_match_columns": (C.c_int, [vp, vp, vp, vp]),

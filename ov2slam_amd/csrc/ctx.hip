@@ -597,7 +597,7 @@ const char *ov2_kernel_names[OV2_K_MAX] = {"clahe_lut_kernel", "level0_kernel", 
                                            "ba_eval_kernel", "ba_colnorm_kernel", "ba_scale_kernels", "ba_lmdiag_kernel",
                                            "ba_sinit_kernel", "ba_schur_kernel", "ba_chol_kernel", "ba_backsub_kernel",
                                            "ba_plus_kernel", "ba_flag_kernel", "ba_reduce_kernel", "ba_misc_kernels",
-                                           "relpose_kernel", nullptr, "detect_cell_kernels", "detect_mask_kernel", "subpix_kernel",
+                                           "relpose_kernel", "map_sba_kernel", "detect_cell_kernels", "detect_mask_kernel", "subpix_kernel",
                                            "pnp_kernel", "klt_compact_kernel",
                                            "detect_list_kernels", "map_setup_kernels", "tri_kernel", "stereo_sad_kernel",
                                            "stereo_gate_kernel", "brief_kernel", "match_kernels", "pose_graph_kernel",

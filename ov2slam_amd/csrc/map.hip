@@ -17,6 +17,7 @@
 
 #include "ov2_internal.h"
 #include "ov2_se3.h"
+#include "ov2_wave.h"
 #include "tri_pair.h"
 
 struct ov2_map {
@@ -78,6 +79,8 @@ struct ov2_map {
     float *obs_px; unsigned char *obs_desc, *obs_hasdesc;           // [max_obs] x 2 floats, x 32 bytes, x 1
     int *mg_srow;                                                   // [max_kf] the row behind mg_stamp: `new`'s row of the keyframe
     int *gt_seen_h; int gt_gen;                                     // host, [max_lm]: the call that last listed the landmark (duplicates are refused)
+    // ov2_map_structure_ba_batch: the solver's state, O(listed entries), allocated with the first call (null before it)
+    unsigned char *sb_ws; int sb_cap;                               // sb_cap entries: SP_N doubles per point | the entered ids
 };
 
 namespace {
@@ -241,6 +244,12 @@ struct map_job {
     const int *gt_kp_lmid, *gt_cand_lmid;        // this map's segments of the id lists
     // flat scans of the gather (records behind the B maps): the array is scanned in place, the total lands behind it
     int *gt_scan; int gt_scan_n;
+    // structure-only BA (hdr / zero_blk point at the merge stage's block; mg_seg = entries of this map's segment, mg_new = the
+    // segment of the id list, mg_n_dev = how many of them are looked at; hdr_out takes the map's ov2_map_sba record)
+    int sb_on;                                   // 1: the mark kernel reads the id list instead of the pairs
+    const unsigned char *sb_status;              // null, or per entry: it counts iff its byte is OV2_MERGE_DONE
+    const double *sb_cam;                        // this map's ov2_map_sba_cam
+    double *sb_pt; int *sb_lm;                   // the solver's block: SP_N doubles per entered point | their ids in list order
 };
 
 // the flat arrays of a gather call (ov2_match_batch_input as the kernels write it) and their row capacity
@@ -1151,6 +1160,13 @@ __global__ __launch_bounds__(256) void mg_mark_kernel(const map_job *__restrict_
         return;
     }
     if (i >= mg_npairs(j)) return;
+    if (j.sb_on) {   // structure-only BA names the landmarks of its list; the first place an id stands at is the one that enters
+        const int l = j.mg_new[i];
+        if ((j.sb_status && j.sb_status[i] != OV2_MERGE_DONE) || (unsigned)l >= (unsigned)j.M.max_lm) return;
+        j.mg_mark[l] = 1;
+        atomicMax(&j.mg_next[l], ANCH_TOP - i);   // 0 = not listed: the array lives in the cleared block
+        return;
+    }
     const int p = j.mg_prev[i], n = j.mg_new[i];
     if ((unsigned)p >= (unsigned)j.M.max_lm || (unsigned)n >= (unsigned)j.M.max_lm) return;   // the walk skips the pair
     j.mg_mark[p] = 1; j.mg_mark[n] = 1;
@@ -1265,6 +1281,400 @@ __global__ __launch_bounds__(MG_THREADS) void mg_walk_kernel(const map_job *__re
         for (int t = 0; t < MH_N; ++t) H[t] = 0;
         H[GH_PAIRS] = np; H[GH_MERGED] = nmerged; H[GH_SKIPPED] = nskipped; H[GH_MOVED] = moved; H[GH_CONFLICT] = conflict;
     }
+}
+
+// ---- structure-only BA: Optimizer::structureOnlyBA (src/optimizer.cpp:2594-2781) on the tables ---------------------------------
+// The merge stage's mark / count / scan / index kernels group the live rows of the listed landmarks by landmark; then ONE
+// workgroup per map runs the whole minimisation (trust_region_minimizer.cc as oracle/ov2_oracle_ba.c restates it, the loop of
+// pg_minimize_kernel).  Every pose is constant, so J'J is block diagonal: a point keeps its 3 x 3 block and its gradient, and
+// the model cost change -m.(r + m/2), m = J step, is -(step.g + step'Hstep / 2) -- no row is needed again once its point
+// has been evaluated, and a candidate is evaluated WITH its block so that an accepted step costs one pass over the rows.
+// A point belongs to a 16-lane quarter of a wave (3-80 rows: a dozen on average), rows strided over the lanes in keyframe
+// order, sums by the fixed butterfly of ov2_wave.h; quarter q takes the points q, q + 16, ... of the list of entered points, in
+// that order, and its running sums meet the other quarters' in a fixed tree.  What a point needs between passes (x, candidate,
+// scale, LM diagonal, two blocks and gradients) lives in SP_N doubles of the map's solver block and is only ever touched by
+// its own quarter; a row is re-evaluated from the tables every pass (pose -> R, projection, corrector): f64 arithmetic is not
+// what bounds a single workgroup, the dependent loads row -> keyframe -> pose are.  The sorted rows of a point go to obs_off:
+// the call ends what the last set-up can be updated from, so that array is free until the next set-up writes it.
+#define SB_THREADS 256
+#define SB_SUB 16
+#define SB_GROUPS (SB_THREADS / SB_SUB)
+enum { SP_X = 0, SP_CAND = 3, SP_SCALE = 6, SP_DIAG = 9, SP_H = 12 /* 2 x 6: upper triangles */, SP_G = 24 /* 2 x 3 */, SP_N = 30 };
+
+struct sb_cam { double Kl[4], Kr[4], Rrl[9], trl[3]; };
+struct sb_opt {
+    double huber_a, ftol, initial_radius, max_radius, min_radius, min_d, max_d, min_rel, ptol, gtol;
+    int max_iters, jacobi, max_invalid;
+};
+
+// ordered sum of one double per thread, total to every thread: the wave tree of ov2_wave.h, then the four waves as (0 + 1) + (2 + 3)
+__device__ __forceinline__ double sb_block_sum(double v, double *sh4)
+{
+    v = ov2wave::wave_sum_f64(v);
+    __syncthreads();   // the readers of the last sum are done with sh4
+    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
+}
+
+__device__ __forceinline__ double sb_block_max(double v, double *sh4)
+{
+    for (int o = 32; o; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmax(fmax(sh4[0], sh4[1]), fmax(sh4[2], sh4[3]));
+}
+
+// One residual block of an XYZ point: what eval_row / huber / the corrector of ba.hip compute for OV2_BA_L_XYZ and
+// OV2_BA_R_XYZ (src/ceres_parametrization.cpp:107-298, corrector.cc:42-157), restated for a constant pose.  Mr maps world
+// directions into the measuring camera, cam is the point there.  Adds the block's cost, J'J (upper triangle) and J'r.
+__device__ __forceinline__ void sb_block(const double *K, const double *Mr, const double *cam, double u, double v, double inv_sigma,
+                                         double huber_a, double &cost, double *H, double *g)
+{
+    const double invz = 1.0 / cam[2];
+    double r0 = inv_sigma * ((K[0] * cam[0] * invz + K[2]) - u);
+    double r1 = inv_sigma * ((K[1] * cam[1] * invz + K[3]) - v);
+    const double chi2 = r0 * r0 + r1 * r1;
+    const bool use_loss = huber_a > 0.0;
+    double rho0 = chi2, rho1 = 1.0, rho2 = 0.0;
+    if (use_loss) {
+        const double b = huber_a * huber_a;
+        if (chi2 > b) {
+            const double r = sqrt(chi2);
+            rho0 = 2.0 * huber_a * r - b;
+            rho1 = fmax(2.2250738585072014e-308, huber_a / r);
+            rho2 = -rho1 / (2.0 * chi2);
+        }
+    }
+    cost += 0.5 * rho0;
+    const double invz2 = invz * invz;
+    const double a0 = invz * K[0], a2 = -cam[0] * invz2 * K[0], b1 = invz * K[1], b2 = -cam[1] * invz2 * K[1];
+    double Ja[3], Jb[3];   // the two rows of d r / d X = J_proj * Mr / sigma
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        Ja[c] = inv_sigma * (a0 * Mr[c] + 0.0 * Mr[3 + c] + a2 * Mr[6 + c]);
+        Jb[c] = inv_sigma * (0.0 * Mr[c] + b1 * Mr[3 + c] + b2 * Mr[6 + c]);
+    }
+    if (use_loss) {
+        const double sqrt_rho1 = sqrt(rho1);
+        double rs = sqrt_rho1, asn = 0.0;
+        if (!(chi2 == 0.0 || rho2 <= 0.0)) {   // never for Huber (rho'' <= 0): kept as the corrector states it
+            const double D = 1.0 + 2.0 * chi2 * rho2 / rho1;
+            const double alpha = 1.0 - sqrt(D);
+            rs = sqrt_rho1 / (1 - alpha);
+            asn = alpha / chi2;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (asn == 0.0) { Ja[c] *= sqrt_rho1; Jb[c] *= sqrt_rho1; }
+            else {
+                const double rtj = Ja[c] * r0 + Jb[c] * r1;
+                Ja[c] = sqrt_rho1 * (Ja[c] - asn * r0 * rtj);
+                Jb[c] = sqrt_rho1 * (Jb[c] - asn * r1 * rtj);
+            }
+        }
+        r0 *= rs; r1 *= rs;
+    }
+    H[0] += Ja[0] * Ja[0] + Jb[0] * Jb[0]; H[1] += Ja[0] * Ja[1] + Jb[0] * Jb[1]; H[2] += Ja[0] * Ja[2] + Jb[0] * Jb[2];
+    H[3] += Ja[1] * Ja[1] + Jb[1] * Jb[1]; H[4] += Ja[1] * Ja[2] + Jb[1] * Jb[2]; H[5] += Ja[2] * Ja[2] + Jb[2] * Jb[2];
+    g[0] += Ja[0] * r0 + Jb[0] * r1; g[1] += Ja[1] * r0 + Jb[1] * r1; g[2] += Ja[2] * r0 + Jb[2] * r1;
+}
+
+// cost, J'J and J'r of one point at X over its `cnt` rows (sorted by keyframe): lane sl of the quarter takes the rows sl,
+// sl + 16, ... in that order, left block before right block; the totals reach every lane of the quarter
+__device__ __forceinline__ void sb_eval_point(const map_view &M, const sb_cam &C, double huber_a, const int *rows, int cnt, const double *X,
+                                              int sl, double &cost, double *H, double *g)
+{
+    cost = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) H[i] = 0.0;
+    g[0] = g[1] = g[2] = 0.0;
+    for (int t = sl; t < cnt; t += SB_SUB) {
+        const int r = rows[t];
+        const int flag = M.obs_flag[r];
+        const double inv_sigma = 1.0 / (double)(1 << M.obs_scale[r]);   // sqrt_info = I / 2^scale
+        double Rwc[9], twc[3], lcam[3], Mr[9];
+        ov2se3::pose_Rt(M.kf_pose + 7 * (size_t)M.obs_kf[r], Rwc, twc);
+        const double dd[3] = {X[0] - twc[0], X[1] - twc[1], X[2] - twc[2]};
+#pragma unroll
+        for (int q = 0; q < 3; ++q) lcam[q] = Rwc[q] * dd[0] + Rwc[3 + q] * dd[1] + Rwc[6 + q] * dd[2];   // Tcw * X
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Mr[3 * q + c] = Rwc[3 * c + q];
+        sb_block(C.Kl, Mr, lcam, M.obs_uv[2 * (size_t)r], M.obs_uv[2 * (size_t)r + 1], inv_sigma, huber_a, cost, H, g);
+        if (flag & OBS_STEREO) {
+            double rcam[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) rcam[q] = (C.Rrl[3 * q] * lcam[0] + C.Rrl[3 * q + 1] * lcam[1] + C.Rrl[3 * q + 2] * lcam[2]) + C.trl[q];
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    double s = 0;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) s += C.Rrl[3 * q + k] * Rwc[3 * c + k];
+                    Mr[3 * q + c] = s;
+                }
+            sb_block(C.Kr, Mr, rcam, M.obs_ruv[2 * (size_t)r], M.obs_ruv[2 * (size_t)r + 1], inv_sigma, huber_a, cost, H, g);
+        }
+    }
+    cost = ov2wave::row_sum_f64<SB_SUB>(cost);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) H[i] = ov2wave::row_sum_f64<SB_SUB>(H[i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) g[i] = ov2wave::row_sum_f64<SB_SUB>(g[i]);
+}
+
+__device__ __forceinline__ void sb_logit(ov2_map_sba *R, int &n_log, double cost, double change, double radius, double rel, double model,
+                                         int valid, int ok)
+{
+    if (n_log >= OV2_BA_MAX_LOG) return;
+    if (threadIdx.x == 0) {
+        ov2_ba_iter *it = &R->log[n_log];
+        it->cost = cost; it->cost_change = change; it->radius = radius; it->relative_decrease = rel;
+        it->model_cost_change = model; it->step_is_valid = valid; it->step_is_successful = ok;
+    }
+    ++n_log;
+}
+
+// Every thread carries the scalar state of the minimiser redundantly (all sums are broadcast), so the control flow is
+// uniform over the workgroup; a quarter's loop over its points has a trip count of its own, and every barrier stands outside.
+__global__ __launch_bounds__(SB_THREADS) void sb_solve_kernel(const map_job *__restrict__ J, sb_opt o)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, sl = tid & (SB_SUB - 1), grp = tid / SB_SUB;
+    __shared__ sb_cam C;
+    __shared__ double sh4[4];
+    __shared__ int s_ent[SB_THREADS / 64], s_cnt[SB_THREADS / 64];
+    ov2_map_sba *R = reinterpret_cast<ov2_map_sba *>(j.hdr_out);
+    {   // the record starts as zeros: thread 0 alone writes it from here on, behind the barriers below
+        int *Rw = reinterpret_cast<int *>(R);
+        for (int k = tid; k < (int)(sizeof(ov2_map_sba) / sizeof(int)); k += SB_THREADS) Rw[k] = 0;
+    }
+    if (tid == 0 && j.mg_seg) {
+        const double *c = j.sb_cam;   // ov2_map_sba_cam: calib_l | calib_r | T_rl
+        for (int k = 0; k < 4; ++k) { C.Kl[k] = c[k]; C.Kr[k] = c[4 + k]; }
+        ov2se3::pose_Rt(c + 8, C.Rrl, C.trl);
+    }
+    __syncthreads();
+    if (!j.mg_seg) {   // uniform: an empty list leaves the map alone
+        if (tid == 0) R->termination = OV2_BA_TERM_SKIPPED;
+        return;
+    }
+    // ---- selection: the entries that count, and of them the points that enter, numbered in list order ----
+    const int np = mg_npairs(j);
+    int n_listed = 0, n_lm = 0;
+    for (int base = 0; base < np; base += SB_THREADS) {
+        const int i = base + tid;
+        const bool counted = i < np && (!j.sb_status || j.sb_status[i] == OV2_MERGE_DONE);
+        const int l = counted ? j.mg_new[i] : -1;
+        bool enter = false;
+        if ((unsigned)l < (unsigned)M.max_lm) {
+            const int st = M.lm_state[l];
+            enter = (st & OV2_LM_ALIVE) && (st & OV2_LM_3D) && j.mg_cnt[l] > 0 && j.mg_next[l] == ANCH_TOP - i;
+        }
+        const unsigned long long be = __ballot(enter), bc = __ballot(counted);
+        if (lane == 0) { s_ent[wv] = __popcll(be); s_cnt[wv] = __popcll(bc); }
+        __syncthreads();
+        int before = n_lm;
+        for (int w = 0; w < SB_THREADS / 64; ++w) {
+            if (w < wv) before += s_ent[w];
+            n_lm += s_ent[w]; n_listed += s_cnt[w];
+        }
+        // n_lm <= entries of the segment <= the entries the block was sized for
+        if (enter) st_int(j.sb_lm + before + __popcll(be & ((1ull << lane) - 1ull)), l);
+        __syncthreads();
+    }
+    __threadfence_block();
+    __syncthreads();
+    // ---- a point's rows in keyframe order (ranked as gt_fill_kernel ranks them), its block count, its start ----
+    int nres = 0;
+    for (int k = grp; k < n_lm; k += SB_GROUPS) {
+        const int l = ld_int(j.sb_lm + k);
+        const int cnt = j.mg_cnt[l];
+        const int *rows = j.mg_rows + j.mg_start[l];
+        int *srt = j.obs_off + j.mg_start[l];   // mg_start[l] + cnt <= GH_ROWS <= n_obs: inside the array
+        for (int t0 = 0; t0 < cnt; t0 += SB_SUB) {
+            const int t = t0 + sl;
+            const bool on = t < cnt;
+            const int r = on ? rows[t] : 0;
+            const int kf = on ? M.obs_kf[r] : 0x7fffffff;
+            int rank = 0;
+            for (int u0 = 0; u0 < cnt; u0 += SB_SUB) {
+                const int v = u0 + sl < cnt ? M.obs_kf[rows[u0 + sl]] : 0x7fffffff;
+#pragma unroll
+                for (int s = 0; s < SB_SUB; ++s) {
+                    const int kv = __shfl(v, s, SB_SUB);
+                    rank += (kv < kf || (kv == kf && u0 + s < t)) ? 1 : 0;
+                }
+            }
+            if (on) {
+                srt[rank] = r;
+                nres += (M.obs_flag[r] & OBS_STEREO) ? 2 : 1;
+            }
+        }
+        if (sl < 3) j.sb_pt[(size_t)k * SP_N + SP_X + sl] = M.lm_xyz[3 * (size_t)l + sl];
+    }
+    for (int s = 32; s; s >>= 1) nres += __shfl_xor(nres, s);
+    if (lane == 0) s_ent[wv] = nres;
+    __threadfence_block();
+    __syncthreads();
+    nres = 0;
+    for (int w = 0; w < SB_THREADS / 64; ++w) nres += s_ent[w];
+    if (tid == 0) { R->n_listed = n_listed; R->n_lm = n_lm; R->n_skipped = n_listed - n_lm; R->n_res = nres; }
+    if (nres == 0) {   // uniform
+        if (tid == 0) R->termination = OV2_BA_TERM_SKIPPED;
+        return;
+    }
+    // ---- iteration zero: cost, blocks and gradients at x, the Jacobi scale, the gradient's max norm ----
+    int cur = 0;   // which of a point's two (block, gradient) slots belongs to x; the other takes the candidate's
+    double x_cost, gmax;
+    {
+        double cs = 0.0, gm = 0.0;
+        for (int k = grp; k < n_lm; k += SB_GROUPS) {
+            const int l = j.sb_lm[k];
+            double *P = j.sb_pt + (size_t)k * SP_N;
+            const double X[3] = {P[SP_X], P[SP_X + 1], P[SP_X + 2]};
+            double c, H[6], g[3];
+            sb_eval_point(M, C, o.huber_a, j.obs_off + j.mg_start[l], j.mg_cnt[l], X, sl, c, H, g);
+            cs += c;
+            // gradient_max_norm = || x - Plus(x, -g) ||_inf with the gradient of the unscaled problem
+#pragma unroll
+            for (int q = 0; q < 3; ++q) gm = fmax(gm, fabs(X[q] - (X[q] + (-g[q]))));
+            if (sl == 0) {
+#pragma unroll
+                for (int q = 0; q < 6; ++q) P[SP_H + q] = H[q];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) P[SP_G + q] = g[q];
+                P[SP_SCALE] = o.jacobi ? 1.0 / (1.0 + sqrt(H[0])) : 1.0;
+                P[SP_SCALE + 1] = o.jacobi ? 1.0 / (1.0 + sqrt(H[3])) : 1.0;
+                P[SP_SCALE + 2] = o.jacobi ? 1.0 / (1.0 + sqrt(H[5])) : 1.0;
+            }
+        }
+        x_cost = sb_block_sum(sl == 0 ? cs : 0.0, sh4);
+        gmax = sb_block_max(gm, sh4);
+    }
+    const double initial_cost = x_cost;
+    double x_norm = -1.0, radius = o.initial_radius, decrease_factor = 2.0;
+    int reuse_diagonal = 0, invalid_steps = 0, iteration = 0, last_ok = 1, term = OV2_BA_TERM_MAX_ITER, n_log = 0;
+    sb_logit(R, n_log, x_cost, 0.0, radius, 0.0, 0.0, 1, 1);
+    for (;;) {
+        if (iteration >= o.max_iters) { term = OV2_BA_TERM_MAX_ITER; break; }
+        if (last_ok && gmax <= o.gtol) { term = OV2_BA_TERM_GTOL; break; }
+        if (radius <= o.min_radius) { term = OV2_BA_TERM_MIN_RADIUS; break; }
+        ++iteration;
+        // LevenbergMarquardtStrategy::ComputeStep per point: (H + D'D) y = g on the scaled block, step = -y, candidate = x + scale * step
+        double mc = 0.0, sn = 0.0;
+        int bad = 0;
+        for (int k = grp; k < n_lm; k += SB_GROUPS) {
+            double *P = j.sb_pt + (size_t)k * SP_N;
+            const double *Hu = P + SP_H + 6 * cur, *gu = P + SP_G + 3 * cur;
+            const double s0 = P[SP_SCALE], s1 = P[SP_SCALE + 1], s2 = P[SP_SCALE + 2];
+            const double h00 = Hu[0] * s0 * s0, h01 = Hu[1] * s0 * s1, h02 = Hu[2] * s0 * s2, h11 = Hu[3] * s1 * s1, h12 = Hu[4] * s1 * s2,
+                         h22 = Hu[5] * s2 * s2;
+            const double g0 = gu[0] * s0, g1 = gu[1] * s1, g2 = gu[2] * s2;
+            double d0, d1, d2;
+            if (!reuse_diagonal) {
+                d0 = fmin(fmax(h00, o.min_d), o.max_d); d1 = fmin(fmax(h11, o.min_d), o.max_d); d2 = fmin(fmax(h22, o.min_d), o.max_d);
+                if (sl == 0) { P[SP_DIAG] = d0; P[SP_DIAG + 1] = d1; P[SP_DIAG + 2] = d2; }
+            } else { d0 = P[SP_DIAG]; d1 = P[SP_DIAG + 1]; d2 = P[SP_DIAG + 2]; }
+            const double l0 = sqrt(d0 / radius), l1 = sqrt(d1 / radius), l2 = sqrt(d2 / radius);
+            // lower Cholesky of the 3 x 3 block and the two triangular solves, in the oracle's order
+            const double a00 = l0 * l0 + h00, a11 = l1 * l1 + h11, a22 = l2 * l2 + h22;
+            bool ok = a00 > 0.0;
+            const double c00 = sqrt(a00), c10 = h01 / c00, c20 = h02 / c00;
+            const double e1 = a11 - c10 * c10;
+            ok = ok && e1 > 0.0;
+            const double c11 = sqrt(e1), c21 = (h12 - c20 * c10) / c11;
+            const double e2 = (a22 - c20 * c20) - c21 * c21;
+            ok = ok && e2 > 0.0;
+            const double c22 = sqrt(e2);
+            const double z0 = g0 / c00, z1 = (g1 - c10 * z0) / c11, z2 = ((g2 - c20 * z0) - c21 * z1) / c22;
+            const double y2 = z2 / c22, y1 = (z1 - c21 * y2) / c11, y0 = ((z0 - c10 * y1) - c20 * y2) / c00;
+            const double t0 = -y0, t1 = -y1, t2 = -y2;
+            if (!ok || !isfinite(t0) || !isfinite(t1) || !isfinite(t2)) { bad = 1; continue; }
+            // model_cost_change = -m.(r + m / 2), m = J step, summed over the point's rows: -(step.g + step'H step / 2)
+            const double Hs0 = h00 * t0 + h01 * t1 + h02 * t2, Hs1 = h01 * t0 + h11 * t1 + h12 * t2, Hs2 = h02 * t0 + h12 * t1 + h22 * t2;
+            mc -= (t0 * g0 + t1 * g1 + t2 * g2) + 0.5 * (t0 * Hs0 + t1 * Hs1 + t2 * Hs2);
+            const double x0 = P[SP_X], x1 = P[SP_X + 1], x2 = P[SP_X + 2];
+            const double q0 = x0 + t0 * s0, q1 = x1 + t1 * s1, q2 = x2 + t2 * s2;
+            sn += (x0 - q0) * (x0 - q0) + (x1 - q1) * (x1 - q1) + (x2 - q2) * (x2 - q2);
+            if (sl == 0) { P[SP_CAND] = q0; P[SP_CAND + 1] = q1; P[SP_CAND + 2] = q2; }
+        }
+        reuse_diagonal = 1;
+        const bool finite = !__syncthreads_or(bad);
+        double model_change = 0.0;
+        bool valid = false;
+        if (finite) {
+            model_change = sb_block_sum(sl == 0 ? mc : 0.0, sh4);
+            valid = model_change > 0.0;
+        }
+        if (!valid) {   // HandleInvalidStep
+            if (++invalid_steps >= o.max_invalid) { term = OV2_BA_TERM_FAILURE; break; }
+            radius = radius / decrease_factor; decrease_factor *= 2.0;
+            last_ok = 0;
+            sb_logit(R, n_log, x_cost, 0.0, radius, 0.0, model_change, 0, 0);
+            continue;
+        }
+        invalid_steps = 0;
+        const double step_norm = sqrt(sb_block_sum(sl == 0 ? sn : 0.0, sh4));
+        // the candidate: its cost, and its blocks and gradients into the points' other slots
+        double cs = 0.0, gm = 0.0, xs = 0.0;
+        for (int k = grp; k < n_lm; k += SB_GROUPS) {
+            const int l = j.sb_lm[k];
+            double *P = j.sb_pt + (size_t)k * SP_N;
+            const double X[3] = {P[SP_CAND], P[SP_CAND + 1], P[SP_CAND + 2]};
+            double c, H[6], g[3];
+            sb_eval_point(M, C, o.huber_a, j.obs_off + j.mg_start[l], j.mg_cnt[l], X, sl, c, H, g);
+            cs += c;
+            xs += X[0] * X[0] + X[1] * X[1] + X[2] * X[2];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) gm = fmax(gm, fabs(X[q] - (X[q] + (-g[q]))));
+            if (sl == 0) {
+#pragma unroll
+                for (int q = 0; q < 6; ++q) P[SP_H + 6 * (cur ^ 1) + q] = H[q];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) P[SP_G + 3 * (cur ^ 1) + q] = g[q];
+            }
+        }
+        const double cand_cost = sb_block_sum(sl == 0 ? cs : 0.0, sh4);
+        if (step_norm <= o.ptol * (x_norm + o.ptol)) { term = OV2_BA_TERM_PTOL; break; }
+        const double cost_change = x_cost - cand_cost;
+        if (fabs(cost_change) <= o.ftol * x_cost) {   // FunctionToleranceReached: returns WITHOUT taking the candidate
+            term = OV2_BA_TERM_FTOL;
+            sb_logit(R, n_log, x_cost, cost_change, radius, 0.0, model_change, 1, 0);
+            break;
+        }
+        const double rel = (cand_cost >= 1.7976931348623157e308) ? -1.7976931348623157e308 : (x_cost - cand_cost) / model_change;
+        if (rel > o.min_rel) {   // HandleSuccessfulStep: x <- candidate, whose evaluation stands in the other slots
+            for (int k = grp; k < n_lm; k += SB_GROUPS) {
+                double *P = j.sb_pt + (size_t)k * SP_N;
+                if (sl < 3) P[SP_X + sl] = P[SP_CAND + sl];
+            }
+            cur ^= 1;
+            x_norm = sqrt(sb_block_sum(sl == 0 ? xs : 0.0, sh4));
+            x_cost = cand_cost;
+            gmax = sb_block_max(gm, sh4);
+            radius = fmin(o.max_radius, radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3)));   // StepAccepted
+            decrease_factor = 2.0;
+            reuse_diagonal = 0;
+            last_ok = 1;
+            sb_logit(R, n_log, x_cost, cost_change, radius, rel, model_change, 1, 1);
+        } else {                 // StepRejected
+            radius = radius / decrease_factor; decrease_factor *= 2.0;
+            last_ok = 0;
+            sb_logit(R, n_log, cand_cost, cost_change, radius, rel, model_change, 1, 0);
+        }
+    }
+    // the minimiser's final state: the last accepted x (an accepted step lowered the cost, so it is the best one too)
+    for (int k = grp; k < n_lm; k += SB_GROUPS) {
+        const int l = j.sb_lm[k];
+        if (sl < 3) j.lm_xyz_w[3 * (size_t)l + sl] = j.sb_pt[(size_t)k * SP_N + SP_X + sl];
+    }
+    if (tid == 0) { R->termination = term; R->n_log = n_log; R->initial_cost = initial_cost; R->final_cost = x_cost; }
 }
 
 // ---- match gather: the flat input of Mapper::matchToMap (src/mapper.cpp:576-774) from the tables -------------------------------
@@ -1902,6 +2312,7 @@ static void free_tables(ov2_map *m)
     if (m->out_host) (void)hipHostFree(m->out_host);
     if (m->hdr_host) (void)hipHostFree(m->hdr_host);
     if (m->fl_removed_h) (void)hipHostFree(m->fl_removed_h);
+    if (m->sb_ws) (void)hipFree(m->sb_ws);
     free(m->kf_alive_h); free(m->snap_kf_alive_h);
 }
 
@@ -2715,6 +3126,117 @@ extern "C" ov2_status ov2_map_merge_points_batch_dev(ov2_ctx *c, int B, ov2_map 
 {
     return merge_batch_impl(c, "ov2_map_merge_points_batch_dev", true, B, maps, pair_off, d_prev_lmid, d_new_lmid, d_cur_obs, d_n_pairs, out,
                             d_pair_status);
+}
+
+// ---- structure-only BA of B maps: eight launches whatever B and the list lengths are (clear, mark, count, three of the scan,
+// index, solve), no synchronisation unless the records are asked for ---------------------------------------------------------
+namespace {
+
+ov2_status grow_sba(ov2_map *m, int entries)
+{
+    ov2_ctx *c = m->c;
+    if (entries <= m->sb_cap) return OV2_OK;
+    OV2_HIP(c, hipStreamSynchronize(c->stream));   // an earlier call may still be working in the old block
+    if (m->sb_ws) OV2_HIP(c, hipFree(m->sb_ws));
+    m->sb_ws = nullptr; m->sb_cap = 0;
+    const int want = entries + entries / 2 + 64;
+    if (hipMalloc((void **)&m->sb_ws, (size_t)want * (SP_N * sizeof(double) + sizeof(int))) != hipSuccess)
+        return ov2_set_err(c, OV2_ERR_NOMEM, "structure-only BA block of %d entries", want);
+    m->sb_cap = want;
+    return OV2_OK;
+}
+
+ov2_status structure_ba_impl(ov2_ctx *c, const char *who, bool dev, int B, ov2_map *const *maps, const int32_t *lm_off, const int32_t *lmid,
+                             const int32_t *d_n, const uint8_t *d_status, const ov2_map_sba_cam *cam, const ov2_ba_options *o,
+                             ov2_map_sba *out)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps || !lm_off) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null argument", who);
+    if (lm_off[0] != 0) return ov2_set_err(c, OV2_ERR_INVALID, "%s: lm_off[0] must be 0", who);
+    ov2_status s;
+    for (int b = 0; b < B; ++b) {
+        if ((s = batch_map_ok(c, maps[b], b)) != OV2_OK) return s;
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
+        if (lm_off[b + 1] < lm_off[b]) return ov2_set_err(c, OV2_ERR_INVALID, "map %d: lm_off descends", b);
+    }
+    if (o && (o->max_iters < 0 || o->max_iters > OV2_BA_MAX_LOG - 1))
+        return ov2_set_err(c, OV2_ERR_INVALID, "%s: max_iters %d outside [0, %d]", who, o->max_iters, OV2_BA_MAX_LOG - 1);
+    const size_t total = (size_t)lm_off[B];
+    if (total && (!lmid || !cam || !o)) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null id list, cameras or options", who);
+    if (out) {
+        memset(out, 0, (size_t)B * sizeof(*out));
+        for (int b = 0; b < B; ++b) out[b].termination = OV2_BA_TERM_SKIPPED;
+    }
+    if (!total) return OV2_OK;
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    for (int b = 0; b < B; ++b)
+        if (lm_off[b + 1] > lm_off[b] && (s = grow_sba(maps[b], lm_off[b + 1] - lm_off[b])) != OV2_OK) return s;
+    // behind the gathered records: [cameras | ids (host form)]
+    static_assert(sizeof(ov2_map_sba) % 8 == 0 && sizeof(ov2_map_sba) >= MH_N * sizeof(int), "the record stands where a header stands");
+    const size_t cam_bytes = ((size_t)B * sizeof(ov2_map_sba_cam) + 15) & ~(size_t)15;
+    job_table JT;
+    if ((s = JT.begin(c, B, (int)(sizeof(ov2_map_sba) / sizeof(int)) - MH_N, cam_bytes + (dev ? 0 : total * sizeof(int32_t)))) != OV2_OK) return s;
+    memcpy(JT.tail_host, cam, (size_t)B * sizeof(ov2_map_sba_cam));
+    const int32_t *d_ids = lmid;
+    if (!dev) {
+        memcpy(JT.tail_host + cam_bytes, lmid, total * sizeof(int32_t));
+        d_ids = (const int32_t *)(JT.tail_dev + cam_bytes);
+    }
+    int nmax = 0, lmax = 0, pmax = 0; unsigned zmax = 0;
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = maps[b];
+        map_job j = job_of(m, -1, -1);
+        j.mg_seg = lm_off[b + 1] - lm_off[b];
+        stage_block(j, m->mg_zero, j.mg_seg ? m->mg_zero_bytes : 0);
+        j.sb_on = 1;
+        j.mg_new = d_ids + lm_off[b];
+        j.mg_n_dev = d_n ? d_n + b : nullptr;
+        j.sb_status = d_status ? d_status + lm_off[b] : nullptr;
+        j.sb_cam = (const double *)(JT.tail_dev + (size_t)b * sizeof(ov2_map_sba_cam));
+        j.sb_pt = (double *)m->sb_ws;
+        j.sb_lm = (int *)(m->sb_ws + (size_t)m->sb_cap * SP_N * sizeof(double));
+        j.mg_cnt = m->mg_cnt; j.mg_fill = m->mg_fill; j.mg_next = m->mg_next; j.mg_stamp = m->mg_stamp; j.mg_mark = m->mg_mark;
+        j.mg_start = m->mg_start; j.mg_rows = m->mg_rows;
+        JT.set(b, j);
+        if (!j.mg_seg) continue;   // an empty list leaves the map alone
+        nmax = std::max(nmax, m->n_obs); lmax = std::max(lmax, m->max_lm); pmax = std::max(pmax, j.mg_seg); zmax = std::max(zmax, j.zero_vec16);
+        m->last_valid = 0;   // the sorted rows go where its set-up left its offsets: no update stage from it any more
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    sb_opt so;
+    so.huber_a = o->huber_delta; so.ftol = o->function_tolerance; so.initial_radius = o->initial_radius; so.max_radius = o->max_radius;
+    so.min_radius = o->min_radius; so.min_d = o->min_lm_diagonal; so.max_d = o->max_lm_diagonal; so.min_rel = o->min_relative_decrease;
+    so.ptol = o->parameter_tolerance; so.gtol = o->gradient_tolerance; so.max_iters = o->max_iters; so.jacobi = o->jacobi_scaling;
+    so.max_invalid = o->max_consecutive_invalid_steps;
+    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), gP((pmax + 255) / 256, B), b256(256);
+    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::min(64u, (zmax + 255) / 256), B), b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mg_mark_kernel, gP, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mg_count_kernel, gN, b256, 0, st, JT.dev);
+    if ((s = exclusive_scan<int>(c, JT, SC_MG, lmax)) != OV2_OK) return s;
+    OV2_LAUNCH(c, OV2_K_MAP, mg_index_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP_SBA, sb_solve_kernel, dim3(1, B), dim3(SB_THREADS), 0, st, JT.dev, so);
+    OV2_HIP(c, hipGetLastError());
+    if (!out) return OV2_OK;   // asynchronous: nothing to hand to the host
+    if ((s = JT.fetch_headers()) != OV2_OK) return s;
+    for (int b = 0; b < B; ++b) memcpy(&out[b], JT.hdr_host + (size_t)b * JT.stride, sizeof(ov2_map_sba));
+    return OV2_OK;
+}
+
+}  // namespace
+
+extern "C" ov2_status ov2_map_structure_ba_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *lm_off, const int32_t *lmid,
+                                                 const ov2_map_sba_cam *cam, const ov2_ba_options *o, ov2_map_sba *out)
+{
+    return structure_ba_impl(c, "ov2_map_structure_ba_batch", false, B, maps, lm_off, lmid, nullptr, nullptr, cam, o, out);
+}
+
+extern "C" ov2_status ov2_map_structure_ba_batch_dev(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *lm_off, const int32_t *d_lmid,
+                                                     const int32_t *d_n, const uint8_t *d_status, const ov2_map_sba_cam *cam,
+                                                     const ov2_ba_options *o, ov2_map_sba *out)
+{
+    return structure_ba_impl(c, "ov2_map_structure_ba_batch_dev", true, B, maps, lm_off, d_lmid, d_n, d_status, cam, o, out);
 }
 
 // ---- local-map matching from the mirrors: gather (twelve launches whatever B and the list lengths are: clear, mark, count,

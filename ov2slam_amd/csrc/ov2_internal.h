@@ -67,6 +67,7 @@ struct ov2_pyr_buf {  // pooled allocation; geometry key = (w,h,pad,max_level,ba
 enum ov2_kernel_id {
     OV2_K_CLAHE_LUT = 0, OV2_K_LEVEL0, OV2_K_LEVEL, OV2_K_KLT_FB, OV2_K_KLT_STAGE1, OV2_K_KLT_STAGE2,
     OV2_K_BA_FIRST,  // BA kernels register from here (ba.hip): 12 ids
+    OV2_K_MAP_SBA = 19,  // structure-only BA solver of the map mirrors (map.hip)
     OV2_K_DETECT = 20,
     OV2_K_MAP = 26,  // map mirror scans (map.hip)
     OV2_K_MAX = 48

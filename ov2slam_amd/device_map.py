@@ -8,7 +8,7 @@ import numpy as np
 
 from . import ba_types as T
 from . import synth_ba
-from .ba_types import BaProblemC, BaResultC, dp, i32p, u8p
+from .ba_types import MAX_LOG, BaIterC, BaOptionsC, BaProblemC, BaResultC, dp, i32p, u8p
 from .frontend import _check
 
 LM_ALIVE, LM_3D, LM_OBS, LM_KP3D = 1, 2, 4, 8
@@ -45,6 +45,25 @@ class MergeC(C.Structure):
     """ov2_map_merge"""
     _fields_ = [("n_pairs", C.c_int32), ("n_merged", C.c_int32), ("n_skipped", C.c_int32), ("n_rows_moved", C.c_int32),
                 ("n_rows_conflict", C.c_int32)]
+
+
+class SbaCamC(C.Structure):
+    """ov2_map_sba_cam"""
+    _fields_ = [("calib_l", C.c_double * 4), ("calib_r", C.c_double * 4), ("T_rl", C.c_double * 7)]
+
+    @classmethod
+    def of(cls, prob):
+        """the calibrations and the extrinsic of a BaProblem (or anything with calib_l, calib_r, T_rl)"""
+        c = cls()
+        c.calib_l[:], c.calib_r[:], c.T_rl[:] = list(prob.calib_l), list(prob.calib_r), list(prob.T_rl)
+        return c
+
+
+class SbaC(C.Structure):
+    """ov2_map_sba"""
+    _fields_ = [("n_listed", C.c_int32), ("n_lm", C.c_int32), ("n_skipped", C.c_int32), ("n_res", C.c_int32),
+                ("termination", C.c_int32), ("n_log", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("log", BaIterC * MAX_LOG)]
 
 
 class MatchLocalC(C.Structure):
@@ -131,12 +150,15 @@ class DeviceMap:
         self.newkf = -1
 
     @classmethod
-    def from_problem(cls, ctx, prob, isobs="newest", spare=(8, 8, 64)):
+    def from_problem(cls, ctx, prob, isobs="newest", spare=(8, 8, 64), scale=None):
         """the map a flat BaProblem was read from: its keyframes, landmarks (at their initial world points) and
         observations.  isobs: 'all' (every MapPoint::isobs_ set, as tests/HostMap builds them), 'newest' (only the landmarks
         the newest keyframe observes: what a live sequence looks like) or 'none'.  spare: capacity beyond the problem
-        (keyframes, landmarks, observation rows) before the tables have to grow."""
+        (keyframes, landmarks, observation rows) before the tables have to grow.  scale: the pyramid level of every observation
+        (Keypoint::scale_), in the order of observations_of -- which is the order of the rows; kept as m.row_scale."""
         kf, lm, un, st, run = observations_of(prob)
+        scale = None if scale is None else np.ascontiguousarray(scale, np.int32)
+        assert scale is None or scale.shape == kf.shape
         nk, nl = len(prob.pose), len(prob.lm)
         m = cls(ctx, nk + spare[0], nl + spare[1], len(kf) + spare[2])
         m.prob, m.newkf = prob, nk - 1
@@ -150,7 +172,8 @@ class DeviceMap:
         cut = np.searchsorted(kf, np.arange(nk + 1))
         for k in range(nk):
             a, b = cut[k], cut[k + 1]
-            m.add_keyframe(k, prob.pose[k], lm[a:b], un[a:b], run[a:b], st[a:b])
+            m.add_keyframe(k, prob.pose[k], lm[a:b], un[a:b], run[a:b], st[a:b], None if scale is None else scale[a:b])
+        m.row_scale = np.zeros(len(kf), np.int32) if scale is None else scale
         return m
 
     @classmethod
@@ -262,6 +285,13 @@ class DeviceMap:
     def merge_points_batch(self, others=(), pairs=(), cur_obs=None, want_header=True):
         """ov2_map_merge_points_batch on this map and `others` in one call; see merge_points_batch"""
         return merge_points_batch(self.ctx, [self] + list(others), pairs, cur_obs, want_header)
+
+    def structure_ba_batch(self, others=(), lmids=(), cam=None, max_iters=10, want_header=True):
+        """ov2_map_structure_ba_batch on this map and `others` in one call: lmids[b] the ids of map b, cam one SbaCamC for
+        all maps or one per map (default: of each map's problem); see structure_ba_batch"""
+        maps = [self] + list(others)
+        cams = [SbaCamC.of(m.prob) for m in maps] if cam is None else (list(cam) if isinstance(cam, (list, tuple)) else [cam] * len(maps))
+        return structure_ba_batch(self.ctx, maps, lmids, cams, structure_ba_options(self.ctx, max_iters), want_header)
 
     def close(self):
         if getattr(self, "h", None):
@@ -467,6 +497,64 @@ def merge_points_batch(ctx, maps, pairs, cur_obs=None, want_header=True, dev=Fal
     hdr = [dict(n_pairs=u.n_pairs, n_merged=u.n_merged, n_skipped=u.n_skipped, n_rows_moved=u.n_rows_moved,
                 n_rows_conflict=u.n_rows_conflict) for u in out]
     return hdr, [st[off[b]:off[b + 1]].copy() for b in range(B)]
+
+
+class DevIds:
+    """device-resident id lists as ov2_map_structure_ba_batch_dev takes them: lm_off (host, B + 1), d_lmid (DeviceArray int32
+    over lm_off[B] slots), d_n (DeviceArray int32 (B,) or None = whole segments)"""
+
+    def __init__(self, lm_off, d_lmid, d_n=None):
+        self.lm_off = np.ascontiguousarray(lm_off, np.int32)
+        self.d_lmid, self.d_n = d_lmid, d_n
+
+
+def structure_ba_options(ctx, max_iters=10):
+    """the options Optimizer::structureOnlyBA runs with (src/optimizer.cpp:2733-2751): those of the local BA, 10 iterations"""
+    o = BaOptionsC()
+    ctx.lib.ov2_ba_default_options(C.byref(o), 5.9915)
+    o.max_iters, o.l2_refine = int(max_iters), 0
+    return o
+
+
+def structure_ba_batch(ctx, maps, lmid_lists, cams, options=None, want_header=True, dev=False, d_status=None):
+    """Optimizer::structureOnlyBA on the tables of the maps (DeviceMap objects or raw ov2_map handles): lmid_lists[b] the ids of
+    map b, cams[b] its SbaCamC, options a BaOptionsC (default: structure_ba_options).
+    dev=False: ov2_map_structure_ba_batch on host lists.  dev=True: ov2_map_structure_ba_batch_dev, either on the same lists
+    uploaded here or on a DevIds; d_status (DeviceArray uint8 over the segments, or None) passes over the entries whose byte is
+    not OV2_MERGE_DONE.  Returns per map dict(n_listed, n_lm, n_skipped, n_res, termination, n_log, initial_cost, final_cost,
+    log: list of dicts as BaResult.log, raw: the bytes of the ov2_map_sba record) -- or None (want_header=False: fully
+    asynchronous, nothing is read back)"""
+    B = len(maps)
+    hs = (C.c_void_p * max(B, 1))(*[getattr(m, "h", m) for m in maps])
+    o = structure_ba_options(ctx) if options is None else options
+    assert len(cams) == B
+    cc = (SbaCamC * max(B, 1))(*cams)
+    out = (SbaC * max(B, 1))() if want_header else None
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    ptr = lambda a: None if a is None else a.ptr
+    if isinstance(lmid_lists, DevIds):
+        assert dev
+        ids = lmid_lists
+    else:
+        ls = [np.ascontiguousarray(q, np.int32).reshape(-1) for q in lmid_lists]
+        assert len(ls) == B
+        off = np.concatenate([[0], np.cumsum([len(q) for q in ls])]).astype(np.int32)
+        flat = np.ascontiguousarray(np.concatenate(ls + [np.zeros(0, np.int32)]), np.int32)
+        if dev:
+            ids = DevIds(off, ctx.to_device(flat if len(flat) else np.zeros(1, np.int32)))
+    if dev:
+        _check(ctx.h, ctx.lib.ov2_map_structure_ba_batch_dev(ctx.h, B, hs, p(ids.lm_off), ptr(ids.d_lmid), ptr(ids.d_n), ptr(d_status),
+                                                            cc, C.byref(o), out))
+    else:
+        assert d_status is None
+        _check(ctx.h, ctx.lib.ov2_map_structure_ba_batch(ctx.h, B, hs, p(off), p(flat), cc, C.byref(o), out))
+    if not want_header:
+        return None
+    return [dict(n_listed=u.n_listed, n_lm=u.n_lm, n_skipped=u.n_skipped, n_res=u.n_res, termination=u.termination, n_log=u.n_log,
+                 initial_cost=u.initial_cost, final_cost=u.final_cost,
+                 log=[dict(cost=i.cost, cost_change=i.cost_change, radius=i.radius, relative_decrease=i.relative_decrease,
+                           model_cost_change=i.model_cost_change, valid=bool(i.step_is_valid), ok=bool(i.step_is_successful))
+                      for i in u.log[:u.n_log]], raw=bytes(u)) for u in out[:B]]
 
 
 def scene_rows(s):
