@@ -934,7 +934,8 @@ ov2_status ov2_map_local_ba_setup(ov2_map *m, int newkf, int nmin_covscore, int 
  *    the map's next set-up; dev[b].res_outlier is a zeroed n_res-byte array for the solve's outlier flags,
  *  - a mostly dead observation table is squeezed BEFORE the chain (from the live count of the map's previous set-up), never
  *    after it: the update stage needs this set-up's row indices.
- * calib_l: B x 4 left intrinsics (fx fy cx cy) -- needed by the update stage of the inverse-depth form -- or NULL.
+ * calib_l: B x 4 left intrinsics (fx fy cx cy) -- needed by the update stage of the inverse-depth form -- or NULL; they are
+ * stored with the maps once every map of the call has passed its checks, so a refused call changes none of them.
  * newkf[b] = the new keyframe of map b.  A map may appear only once per call. */
 ov2_status ov2_map_local_ba_setup_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf, int nmin_covscore,
                                         int nmin_cst_kfs, int inv_depth, const double *calib_l, ov2_local_ba_setup *dev);
@@ -1212,6 +1213,85 @@ ov2_status ov2_map_structure_ba_batch_dev(ov2_ctx *ctx, int B, ov2_map *const *m
                                           const int32_t *d_lmid, const int32_t *d_n /* B, or NULL */,
                                           const uint8_t *d_status /* or NULL */, const ov2_map_sba_cam *cam /* B */,
                                           const ov2_ba_options *o, ov2_map_sba *out /* B, or NULL */);
+
+/* Optimizer::looseBA(inikfid, nkfid, buse_robust_cost) (src/optimizer.cpp:900-1672) -- the last of the four statements that
+ * close an accepted loop (src/loop_closer.cpp:302-372) -- on the tables of B map mirrors: set-up, solve and update, each
+ * batched (map = blockIdx.y, sizes from device memory, nothing synchronised inside a chain).
+ *
+ * ov2_map_loose_ba_setup_batch is the set-up stage (:985-1270).  It leaves device views in the shape
+ * ov2_map_local_ba_setup_batch leaves them (same ov2_local_ba_setup, same layout, zeroed res_outlier, the same
+ * squeeze-before-the-chain rule, one synchronisation for the gathered headers); only the selection differs:
+ *  - the live keyframes of [inikfid[b], nkfid[b]] in ascending id: the first nmin_cst_kfs of them are constant (1 stereo, 2
+ *    mono), the rest optimised; the count runs over the live keyframes of the range only, so a dead first keyframe hands
+ *    constness to the next live one.  No covisibility score, no abort: `aborted` is always 0;
+ *  - local landmarks: the OV2_LM_KP3D landmarks of the optimised keyframes' live rows; MapPoint::isBad() ones go to
+ *    bad_lmid and lose OV2_LM_3D;
+ *  - observers: live rows with kf <= nkfid[b] (:1056); observers outside the range enter as constant poses; with inv_depth
+ *    the smallest observing kfid anchors the landmark; residual blocks as in the local set-up; arrays in ascending kfid /
+ *    lmid.
+ * A range with inikfid > nkfid, or one that yields no residual block, is a no-op: the view has n_res = 0 and the update does
+ * nothing for that map (the host stage returns OV2_OK there).  The set-up records its kind in the map:
+ * ov2_map_local_ba_update_batch refuses a loose set-up, ov2_map_loose_ba_update_batch a local one (OV2_ERR_INVALID).
+ * Refused with OV2_ERR_INVALID before anything is enqueued, from host state only: nkfid[b] dead or out of range, inikfid[b] <
+ * 0, a map listed twice, a map of another context, B < 0, a null array that a non-empty call needs.
+ *
+ * ov2_map_loose_ba_update_batch is the update stage (:1330-1657) from the flat problems of the maps' last loose set-up, whose
+ * pose / lm arrays now hold the solved states, and the per-block flags d_outlier[b] (device, NULL = nothing flagged).  Seven
+ * launches whatever B; with lists == NULL and out == NULL fully asynchronous, otherwise one synchronisation.  In the
+ * reference's order, each step reading the tables as the step before left them:
+ *  1. ini = inverse(old(nkfid)), opt = the solved pose of nkfid, T_corr = opt * ini;
+ *  2. local landmarks, observers counted before any removal: isBad() -> bad set (OV2_LM_3D cleared, no point written);
+ *     inverse depth with 1 / rho <= 0 -> bad set; otherwise the new point old(a) * (K^-1 [u v 1] / rho), a = the landmark's
+ *     oldest live observer (MapPoint::kfid_), old(a) its pose BEFORE this update writes any pose (:1499-1511; localBA's update
+ *     uses the updated pose), a outside the problem -> bad set; XYZ form: the solved point.  A written point ends
+ *     OV2_LM_3D | OV2_LM_KP3D (MapManager::updateMapPoint);
+ *  3. a landmark that is OV2_LM_ALIVE and OV2_LM_KP3D, not a local landmark of the problem (an isBad() one of the set-up is
+ *     eligible), whose oldest live observer a is younger than nkfid moves once:
+ *     xyz' = (opt * (ini * old(a))) * (inverse(old(a)) * xyz), and ends OV2_LM_3D (:1571-1592);
+ *  4. every non-constant keyframe of the problem takes its solved pose, every live keyframe k > nkfid opt * (ini * old(k));
+ *  5. flagged blocks, over the set-up's rows only: a right block demotes the row to mono, a left block kills it (and clears
+ *     OV2_LM_OBS for a row of cur_kfid[b]); both put the landmark into the bad set.  A row that died since the set-up is
+ *     neither removed again nor reported;
+ *  6. culling over the bad set (the set-up's bad list, step 2's additions, step 5's landmarks), observers and oldest observer
+ *     recounted AFTER step 5: isBad() removes the landmark, otherwise it goes when it has fewer than 3 observers, its oldest
+ *     observer is below nkfid - 3 and OV2_LM_OBS is clear.  looseBA has no first-pass culling of the local landmarks.
+ * Departures: a row of a dead keyframe or landmark is not live in the mirror, so the reference's "keyframe gone" / "map point
+ * gone" branches (removeMapPointObs inside the set-up and the propagation) have nothing to do; MapPoint::kfid_ is taken to be
+ * the oldest live observer.  Edits allowed between set-up and update: those of ov2_map_local_ba_update_batch.  The call ends
+ * what the map's last set-up can be updated from (a second update is refused); a state saved by ov2_map_save_state covers
+ * everything the update writes and stays restorable.  lists[b]: as after ov2_map_local_ba_update_batch (same meaning and
+ * validity), for a caller that keeps host objects.  out[b].T_corr is what the caller applies to MapManager::pcurframe_
+ * (:1652-1657): the mirror holds no current frame.
+ *
+ * ov2_map_loose_ba_batch is the whole statement: the set-up (nmin_cst_kfs = stereo ? 1 : 2, calib_l = cam[b].calib_l),
+ * ov2_ba_solve_batch_dev on the views of the maps with n_res > 0 (flags into the views' res_outlier), the update.  The solve
+ * synchronises, so this call is NOT asynchronous.  out[b] also carries the solve's termination, costs, n_outliers_pass1 and
+ * iteration log.  ov2_ba_loose_options fills the reference's options (:1298-1299): ov2_ba_default_options plus max_iters = 5,
+ * function_tolerance = 1e-4, l2_refine = 0, and huber_delta = 0 when not robust. */
+typedef struct ov2_map_loose_ba {
+    int32_t ran;                                  /* 0: no-op map (n_res == 0), everything else zero, termination SKIPPED */
+    int32_t n_pose, n_free_pose, n_lm, n_res;     /* the flat problem; n_free_pose counts its non-constant poses, whether or
+                                                     not the keyframe is still alive at the update (a dead one is not written) */
+    int32_t n_bad;                                /* landmarks the culling looked at (step 6's bad set) */
+    int32_t n_flagged_left, n_flagged_right;      /* flagged blocks by camera */
+    int32_t n_removed_obs, n_stereo_off, n_removed_lm;
+    int32_t n_written, n_propagated, n_kf_younger;   /* points of step 2, landmarks of step 3, younger keyframes of step 4 */
+    int32_t termination, n_outliers_pass1, n_log, reserved;   /* of the solve (ov2_map_loose_ba_batch only) */
+    double T_corr[7];
+    double initial_cost, final_cost;
+    ov2_ba_iter log[OV2_BA_MAX_LOG];
+} ov2_map_loose_ba;
+ov2_status ov2_map_loose_ba_setup_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *inikfid, const int32_t *nkfid,
+                                        int nmin_cst_kfs, int inv_depth, const double *calib_l /* B x 4 */,
+                                        ov2_local_ba_setup *dev /* B */);
+ov2_status ov2_map_loose_ba_update_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const uint8_t *const *d_outlier,
+                                         const int32_t *cur_kfid, ov2_local_ba_update *lists /* B, or NULL */,
+                                         ov2_map_loose_ba *out /* B, or NULL */);
+void ov2_ba_loose_options(ov2_ba_options *o, float robust_mono_th, int robust);
+ov2_status ov2_map_loose_ba_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *inikfid, const int32_t *nkfid,
+                                  const ov2_map_sba_cam *cam /* B */, int stereo, int inv_depth, const ov2_ba_options *o,
+                                  const int32_t *cur_kfid, ov2_local_ba_update *lists /* B, or NULL */,
+                                  ov2_map_loose_ba *out /* B, or NULL */);
 
 /* Test / bench support.  ov2_map_save_state keeps a device copy of the mutable state of the tables (poses, landmark points
  * and states, observation flags); ov2_map_restore_state_batch rewinds B maps to it in one launch, asynchronously (every

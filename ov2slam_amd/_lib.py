@@ -103,6 +103,10 @@ SIGNATURES = {
     "ov2_map_merge_points_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ov2_map_structure_ba_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     "ov2_map_structure_ba_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ov2_map_loose_ba_setup_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
+    "ov2_map_loose_ba_update_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+    "ov2_ba_loose_options": (None, [vp, C.c_float, C.c_int]),
+    "ov2_map_loose_ba_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "ov2_match_pairs_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ov2_map_enable_match_columns": (C.c_int, [vp]),
     "ov2_map_download_match_columns": (C.c_int, [vp, vp, vp, vp]),

@@ -46,6 +46,7 @@ struct ov2_map {
     int last_newkf, last_inv, last_valid;
     int last_n_obs;                                                 // rows the last set-up saw (only they carry its obs_cnt / obs_off)
     int last_updated;                                               // its update stage has been enqueued: a second one is refused
+    int last_kind;                                                  // 0: set-up of localBA, 1: of looseBA (each update stage takes its own kind only)
     int live_rows, live_known;                                      // live rows of the table as the last set-up counted them
     double last_K[4]; int have_K;                                   // left intrinsics (anchored inverse depth -> world point)
     // ov2_map_save_state / ov2_map_restore_state_batch
@@ -250,6 +251,10 @@ struct map_job {
     const unsigned char *sb_status;              // null, or per entry: it counts iff its byte is OV2_MERGE_DONE
     const double *sb_cam;                        // this map's ov2_map_sba_cam
     double *sb_pt; int *sb_lm;                   // the solver's block: SP_N doubles per entered point | their ids in list order
+    // looseBA: set-up (lb_lo = first keyframe of the range, newkf = the loop keyframe) and update (lb_on = 0: no-op map;
+    // lb_cnt / lb_tmp: LB_N counters and inverse(old(newkf)) | opt | T_corr behind the map's gathered header)
+    int lb_lo, lb_on;
+    int *lb_cnt; double *lb_tmp;
 };
 
 // the flat arrays of a gather call (ov2_match_batch_input as the kernels write it) and their row capacity
@@ -1918,6 +1923,219 @@ __global__ __launch_bounds__(256) void mp_poses_kernel(const map_job *__restrict
     }
 }
 
+// ---- Optimizer::looseBA (src/optimizer.cpp:900-1672) on the tables ------------------------------------------------------
+// Set-up (:985-1270): the chain of localBA's set-up with another keyframe selection.  The live keyframes of
+// [lb_lo, newkf] in ascending id: the first nmin_cst are constant, the rest optimised (:1004-1030); no covisibility, no
+// abort.  One wave per map, 64 keyframes per step; the constants handed out so far ride in a wave-uniform register.
+__global__ __launch_bounds__(64) void ml_select_kernel(const map_job *__restrict__ J, int nmin_cst)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int lane = threadIdx.x, hi = min(j.newkf, M.max_kf - 1);
+    int nlive = 0;
+    for (int base = j.lb_lo; base <= hi; base += 64) {
+        const int kf = base + lane;
+        const bool live = kf <= hi && M.kf_state[kf];
+        const unsigned long long bal = __ballot(live);
+        const int rank = nlive + __popcll(bal & ((1ull << lane) - 1ull));   // live keyframes of the range before this one
+        if (live) j.kf_role[kf] = rank < nmin_cst ? 2 : 1;
+        nlive += __popcll(bal);
+    }
+    if (lane == 0) j.hdr[MH_NMAXKF] = j.newkf;   // observers younger than the loop keyframe are left out (:1056)
+}
+
+// Update (:1330-1657).  Counters of the stage, behind the map's gathered header (the set-up's header keeps MH_NRM_LM,
+// MH_NRM_OBS and MH_NST_OFF, which mu_obs_kernel counts):
+enum { LB_FLAG_L = 0, LB_FLAG_R, LB_WRITTEN, LB_PROP, LB_YOUNGER, LB_BAD, LB_FREE, LB_N = 8 };
+enum { LB_EXTRA_INTS = LB_N + 42 };   // + 21 doubles: inverse(old(newkf)) | opt | T_corr
+
+__device__ __forceinline__ void lb_count(const map_job &j, int which, bool hit)
+{
+    const unsigned long long bal = __ballot(hit);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&j.lb_cnt[which], __popcll(bal));
+}
+
+// launch 1, one lane per landmark: observer counts and oldest observers start from zero; one lane of the map's first
+// workgroup works out the constants of the statement from the OLD pose of the loop keyframe and its solved one (:1432-1436)
+__global__ __launch_bounds__(256) void ml_clear_kernel(const map_job *__restrict__ J, int inv)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (blockIdx.x == 0 && (int)threadIdx.x < LB_N) j.lb_cnt[threadIdx.x] = 0;
+    if (!j.lb_on) return;
+    if (blockIdx.x == 0 && threadIdx.x == 64) {
+        const flat_out O = flat_of(j, inv);
+        const double *opt = O.pose + 7 * (size_t)j.kf_idx[j.newkf];
+        double ini[7], corr[7];
+        se3_inverse(M.kf_pose + 7 * (size_t)j.newkf, ini);
+        se3_mul(opt, ini, corr);
+#pragma unroll
+        for (int q = 0; q < 7; ++q) { j.lb_tmp[q] = ini[q]; j.lb_tmp[7 + q] = opt[q]; j.lb_tmp[14 + q] = corr[q]; }
+    }
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l < M.max_lm) { j.lm_nobs[l] = 0; j.lm_pack[l] = 0ull; }
+}
+
+// launch 2, one lane per row of the table as it is now: observers and the oldest observer (MapPoint::kfid_, with its row
+// for the anchor pixel) of EVERY landmark, before anything is removed; the rows of the set-up also count their flagged
+// blocks by camera
+__global__ __launch_bounds__(256) void ml_observers_kernel(const map_job *__restrict__ J, int inv)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (!j.lb_on || (int)blockIdx.x * 256 >= M.n_obs) return;   // uniform per workgroup
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf, lm;
+    if (i < M.n_obs && obs_live(M, i, kf, lm)) {
+        atomicAdd(&j.lm_nobs[lm], 1);
+        atomicMax(&j.lm_pack[lm], ((unsigned long long)(ANCH_TOP - kf) << 32) | (unsigned)i);
+    }
+    int nl = 0, nr = 0;
+    if (j.outlier && i < j.last_n_obs) {
+        const int c = j.obs_cnt[i];
+        if (c) {
+            const flat_out O = flat_of(j, inv);
+            const int o = j.obs_off[i];
+            for (int k = 0; k < c; ++k)
+                if (j.outlier[o + k]) {
+                    const int t = O.res_type[o + k];
+                    if (t == OV2_BA_L_XYZ || t == OV2_BA_L_INV) ++nl; else ++nr;
+                }
+        }
+    }
+    // at most two blocks per row: two ballots count them
+    lb_count(j, LB_FLAG_L, nl > 0);
+    lb_count(j, LB_FLAG_R, nr > 0);
+}
+
+// launch 3, one lane per landmark, every pose still the OLD one.  A local landmark (:1440-1526): isBad() / non-positive
+// depth / anchor outside the problem -> the bad set (bit 8 of lm_sel); otherwise its new point -- with inverse depth from
+// the pose of its oldest observer BEFORE the update (:1499-1511) --, 3D with its keypoints (MapManager::updateMapPoint).
+// Any other landmark whose keypoints are 3D and whose oldest observer is younger than the loop keyframe moves with that
+// keyframe (:1571-1592): xyz' = (opt * (ini * old(a))) * (inverse(old(a)) * xyz).
+__global__ __launch_bounds__(256) void ml_landmarks_kernel(const map_job *__restrict__ J, int inv)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (!j.lb_on || (int)blockIdx.x * 256 >= M.max_lm) return;   // uniform per workgroup
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    bool written = false, moved = false;
+    if (l < M.max_lm) {
+        int st = M.lm_state[l];
+        const unsigned long long oldest = j.lm_pack[l];   // 0: no live observer
+        const int a = oldest ? ANCH_TOP - (int)(oldest >> 32) : -1;
+        if ((st & OV2_LM_ALIVE) && j.lm_sel[l] == 1) {
+            const int nobs = j.lm_nobs[l];
+            const bool isobs = st & OV2_LM_OBS;
+            bool bad = false;
+            double w[3] = {0.0, 0.0, 0.0};
+            if ((nobs < 2 && !isobs && (st & OV2_LM_3D)) || (nobs == 0 && !isobs)) {   // MapPoint::isBad clears is3d_
+                bad = true;
+                j.lm_state_w[l] = (unsigned char)(st & ~OV2_LM_3D);
+            } else if (!j.lm_flag[l]) {
+                bad = true;                                          // not in the problem (:1455)
+            } else {
+                const flat_out O = flat_of(j, inv);
+                const int q = (int)(j.lm_pidx[l] & 0xffffffffull);
+                if (inv) {
+                    const double zanch = 1.0 / O.lm[q];
+                    if (zanch <= 0.0 || a < 0 || j.kf_role[a] == 0) bad = true;   // :1470, :1478
+                    else {
+                        const int r = (int)(oldest & 0xffffffffull);
+                        const double u = M.obs_uv[2 * (size_t)r], v = M.obs_uv[2 * (size_t)r + 1];
+                        const double cam[3] = {zanch * (u - j.K[2]) / j.K[0], zanch * (v - j.K[3]) / j.K[1], zanch};
+                        se3_apply(M.kf_pose + 7 * (size_t)a, cam, w);
+                        written = true;
+                    }
+                } else {
+                    w[0] = O.lm[3 * (size_t)q]; w[1] = O.lm[3 * (size_t)q + 1]; w[2] = O.lm[3 * (size_t)q + 2];
+                    written = true;
+                }
+            }
+            if (bad) atomicOr(&j.lm_sel[l], 8);
+            if (written) {
+                j.lm_xyz_w[3 * (size_t)l] = w[0]; j.lm_xyz_w[3 * (size_t)l + 1] = w[1]; j.lm_xyz_w[3 * (size_t)l + 2] = w[2];
+                j.lm_state_w[l] = (unsigned char)(st | OV2_LM_3D | OV2_LM_KP3D);
+            }
+        } else if ((st & OV2_LM_ALIVE) && (st & OV2_LM_KP3D) && a > j.newkf) {
+            double rel[7], Tnew[7], Tcw[7], cam[3], w[3];
+            const double *Told = M.kf_pose + 7 * (size_t)a;
+            se3_mul(j.lb_tmp, Told, rel);
+            se3_mul(j.lb_tmp + 7, rel, Tnew);
+            se3_inverse(Told, Tcw);
+            se3_apply(Tcw, M.lm_xyz + 3 * (size_t)l, cam);          // Frame::projWorldToCam
+            se3_apply(Tnew, cam, w);
+            j.lm_xyz_w[3 * (size_t)l] = w[0]; j.lm_xyz_w[3 * (size_t)l + 1] = w[1]; j.lm_xyz_w[3 * (size_t)l + 2] = w[2];
+            j.lm_state_w[l] = (unsigned char)(st | OV2_LM_3D);
+            moved = true;
+        }
+    }
+    lb_count(j, LB_WRITTEN, written);
+    lb_count(j, LB_PROP, moved);
+}
+
+// launch 4, one lane per keyframe: the solved pose of a non-constant keyframe of the problem (:1533-1548), or
+// opt * (ini * old(k)) for a keyframe younger than the loop keyframe (:1560).  A lane reads its own old pose only.
+__global__ __launch_bounds__(256) void ml_poses_kernel(const map_job *__restrict__ J, int inv)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if (!j.lb_on || (int)blockIdx.x * 256 >= M.max_kf) return;   // uniform per workgroup
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    bool free_ = false, younger = false;
+    if (k < M.max_kf) {
+        free_ = j.kf_role[k] == 1;   // counted as a free pose of the PROBLEM, alive now or not (only a live one is written)
+        if (M.kf_state[k]) {
+            if (free_) {
+                const flat_out O = flat_of(j, inv);
+                const double *T = O.pose + 7 * (size_t)j.kf_idx[k];
+#pragma unroll
+                for (int q = 0; q < 7; ++q) j.kf_pose_w[7 * (size_t)k + q] = T[q];
+            } else if (k > j.newkf) {
+                double rel[7], T[7];
+                se3_mul(j.lb_tmp, M.kf_pose + 7 * (size_t)k, rel);
+                se3_mul(j.lb_tmp + 7, rel, T);
+#pragma unroll
+                for (int q = 0; q < 7; ++q) j.kf_pose_w[7 * (size_t)k + q] = T[q];
+                younger = true;
+            }
+        }
+    }
+    lb_count(j, LB_FREE, free_);
+    lb_count(j, LB_YOUNGER, younger);
+}
+
+// launch 7 (after mu_obs_kernel and mu_recount_kernel: the flagged blocks are gone, observers and oldest observers of the
+// problem's landmarks are counted again), one lane per landmark of the problem or of its bad list: the culling over
+// set_badlmids (:1623-1650) -- the set-up's isBad() landmarks, launch 3's additions and every landmark with a flagged block
+__global__ __launch_bounds__(256) void ml_cull_kernel(const map_job *__restrict__ J, int inv)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int *H = j.hdr;
+    if (!j.lb_on) return;
+    const int idx = blockIdx.x * 256 + threadIdx.x, NL = H[MH_NLM], NB = H[MH_NBAD];
+    bool member = false;
+    if (idx < NL + NB) {
+        const flat_out O = flat_of(j, inv);
+        const int l = idx < NL ? O.lm_lmid[idx] : O.bad_lmid[idx - NL];
+        const int st = M.lm_state[l];
+        member = idx >= NL || (j.lm_sel[l] & (4 | 8));
+        if (member && (st & OV2_LM_ALIVE)) {
+            const int nobs = j.lm_nobs[l];
+            const bool isobs = st & OV2_LM_OBS;
+            const unsigned long long oldest = j.lm_pack[l];
+            const int lm_kfid = oldest ? ANCH_TOP - (int)(oldest >> 32) : -1;
+            const bool bad = (nobs < 2 && !isobs && (st & OV2_LM_3D)) || (nobs == 0 && !isobs);
+            if (bad || (nobs < 3 && lm_kfid < j.newkf - 3 && !isobs)) {
+                j.lm_state_w[l] = 0;
+                O.rm_lm[atomicAdd(&j.hdr[MH_NRM_LM], 1)] = l;
+            }
+        }
+    }
+    lb_count(j, LB_BAD, member);
+}
+
 // gathers the headers of all maps (update counts) for one D2H
 __global__ __launch_bounds__(64) void mb_hdr_gather_kernel(const map_job *__restrict__ J)
 {
@@ -2606,8 +2824,9 @@ void fill_view(const ov2_map *m, unsigned char *base, ov2_local_ba_setup *out)
 }
 
 // enqueues the set-up chain for the maps of `sel` (indices into maps[]), fetches their headers (one synchronisation)
+// lo != nullptr: the set-up of looseBA over the keyframes [lo[b], newkf[b]] (its own selection kernel, the rest of the chain as it is)
 ov2_status setup_pass(ov2_ctx *c, const std::vector<int> &sel, ov2_map *const *maps, const int32_t *newkf, int nmin_cov, int nmin_cst,
-                      int inv)
+                      int inv, const int32_t *lo)
 {
     const int B = (int)sel.size();
     hipStream_t st = c->stream;
@@ -2618,7 +2837,9 @@ ov2_status setup_pass(ov2_ctx *c, const std::vector<int> &sel, ov2_map *const *m
     for (int b = 0; b < B; ++b) {
         ov2_map *m = maps[sel[b]];
         if (!m->out_dev && (s = grow_out(m, 1u << 20)) != OV2_OK) return s;
-        JT.set(b, job_of(m, newkf[sel[b]], -1));
+        map_job j = job_of(m, newkf[sel[b]], -1);
+        j.lb_lo = lo ? lo[sel[b]] : 0;
+        JT.set(b, j);
         nmax = std::max(nmax, m->n_obs); lmax = std::max(lmax, m->max_lm); kmax = std::max(kmax, m->max_kf);
         zmax = std::max(zmax, (unsigned)(m->zero_bytes / 16));
     }
@@ -2627,8 +2848,11 @@ ov2_status setup_pass(ov2_ctx *c, const std::vector<int> &sel, ov2_map *const *m
     const map_job *J = JT.dev;
     OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::min(64u, (zmax + 255) / 256), B), b, 0, st, J);
     OV2_LAUNCH(c, OV2_K_MAP, ms_count_kernel, gN, b, 0, st, J);
-    OV2_LAUNCH(c, OV2_K_MAP, ms_cov_kernel, gN, b, 0, st, J);
-    OV2_LAUNCH(c, OV2_K_MAP, ms_select_kernel, one, dim3(64), 0, st, J, nmin_cov);
+    if (lo) OV2_LAUNCH(c, OV2_K_MAP, ml_select_kernel, one, dim3(64), 0, st, J, nmin_cst);
+    else {
+        OV2_LAUNCH(c, OV2_K_MAP, ms_cov_kernel, gN, b, 0, st, J);
+        OV2_LAUNCH(c, OV2_K_MAP, ms_select_kernel, one, dim3(64), 0, st, J, nmin_cov);
+    }
     OV2_LAUNCH(c, OV2_K_MAP, ms_local_lm_kernel, gN, b, 0, st, J);
     OV2_LAUNCH(c, OV2_K_MAP, ms_observers_kernel, gN, b, 0, st, J);
     OV2_LAUNCH(c, OV2_K_MAP, ms_poses_kernel, one, dim3(1024), 0, st, J, nmin_cst);
@@ -2643,7 +2867,7 @@ ov2_status setup_pass(ov2_ctx *c, const std::vector<int> &sel, ov2_map *const *m
         ov2_map *m = maps[sel[b2]];
         memcpy(m->last_hdr, JT.hdr_host + (size_t)b2 * MH_N, MH_N * sizeof(int));
         m->last_newkf = newkf[sel[b2]]; m->last_inv = inv; m->last_valid = 1;
-        m->last_n_obs = m->n_obs; m->last_updated = 0;
+        m->last_n_obs = m->n_obs; m->last_updated = 0; m->last_kind = lo ? 1 : 0;
         m->live_rows = m->last_hdr[MH_NLIVE]; m->live_known = 1;
     }
     return OV2_OK;
@@ -2677,14 +2901,19 @@ void stage_block(map_job &j, unsigned char *blk, size_t bytes)
 }
 
 ov2_status setup_batch_impl(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf, int nmin_cov, int nmin_cst, int inv,
-                            const double *calib_l, bool squeeze_first)
+                            const double *calib_l, bool squeeze_first, const int32_t *lo = nullptr)
 {
     ov2_status s;
     for (int b = 0; b < B; ++b) {
         ov2_map *m = maps[b];
         if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
         if (newkf[b] < 0 || newkf[b] >= m->max_kf) return ov2_set_err(c, OV2_ERR_INVALID, "kfid %d outside the capacity of map %d", newkf[b], b);
+        if (lo && (s = batch_kf_alive(c, m, newkf[b], b)) != OV2_OK) return s;
+        if (lo && lo[b] < 0) return ov2_set_err(c, OV2_ERR_INVALID, "map %d: the range starts at keyframe %d", b, lo[b]);
         if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
+    }
+    for (int b = 0; b < B; ++b) {   // nothing of a refused call reaches a map (the local set-up's intrinsics included)
+        ov2_map *m = maps[b];
         m->have_K = calib_l != nullptr;
         for (int k = 0; k < 4; ++k) m->last_K[k] = calib_l ? calib_l[4 * b + k] : 0.0;
     }
@@ -2700,7 +2929,7 @@ ov2_status setup_batch_impl(ov2_ctx *c, int B, ov2_map *const *maps, const int32
     std::vector<int> sel((size_t)B);
     for (int b = 0; b < B; ++b) sel[b] = b;
     for (int pass = 0; pass < 3 && !sel.empty(); ++pass) {
-        if ((s = setup_pass(c, sel, maps, newkf, nmin_cov, nmin_cst, inv)) != OV2_OK) return s;
+        if ((s = setup_pass(c, sel, maps, newkf, nmin_cov, nmin_cst, inv, lo)) != OV2_OK) return s;
         // a flat problem that did not fit its block: grow the block, run that map again (first calls / growing windows only)
         std::vector<int> again;
         for (int b : sel) {
@@ -2791,6 +3020,8 @@ extern "C" ov2_status ov2_map_local_ba_update_batch(ov2_ctx *c, int B, ov2_map *
                                "/ restored since)", b);
         if (m->last_updated)
             return ov2_set_err(c, OV2_ERR_INVALID, "map %d: the update stage of its last set-up has already run", b);
+        if (m->last_kind != 0)
+            return ov2_set_err(c, OV2_ERR_INVALID, "map %d: its last set-up is looseBA's (ov2_map_loose_ba_update_batch updates from it)", b);
         if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
         if (inv < 0) inv = m->last_inv;
         if (m->last_inv != inv) return ov2_set_err(c, OV2_ERR_INVALID, "the maps of a batch must share one landmark parametrisation (map %d)", b);
@@ -2836,6 +3067,163 @@ extern "C" ov2_status ov2_map_local_ba_update_batch(ov2_ctx *c, int B, ov2_map *
         out[b].n_removed_lm = H[MH_NRM_LM]; out[b].n_removed_obs = H[MH_NRM_OBS]; out[b].n_stereo_off = H[MH_NST_OFF];
         out[b].removed_lmid = O.rm_lm; out[b].removed_obs = (const int32_t *)O.rm_obs; out[b].stereo_off = (const int32_t *)O.st_off;
     }
+    return OV2_OK;
+}
+
+// ---- looseBA of B maps: the set-up chain with its own selection, the update in seven launches whatever B ----------------
+extern "C" ov2_status ov2_map_loose_ba_setup_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *inikfid, const int32_t *nkfid,
+                                                   int nmin_cst_kfs, int inv_depth, const double *calib_l, ov2_local_ba_setup *dev)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps || !inikfid || !nkfid || !dev) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_loose_ba_setup_batch: null argument");
+    const ov2_status s = setup_batch_impl(c, B, maps, nkfid, 0, nmin_cst_kfs, inv_depth ? 1 : 0, calib_l, true, inikfid);
+    if (s != OV2_OK) return s;
+    for (int b = 0; b < B; ++b) fill_view(maps[b], maps[b]->out_dev, &dev[b]);
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_map_loose_ba_update_batch(ov2_ctx *c, int B, ov2_map *const *maps, const uint8_t *const *d_outlier,
+                                                    const int32_t *cur_kfid, ov2_local_ba_update *lists, ov2_map_loose_ba *out)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_loose_ba_update_batch: null argument");
+    int inv = -1;
+    ov2_status s;
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = maps[b];
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
+        if (!m->last_valid)
+            return ov2_set_err(c, OV2_ERR_INVALID, "map %d: no set-up to update from (none ran, or the tables grew / were squeezed "
+                               "/ restored / edited by another stage since)", b);
+        if (m->last_updated)
+            return ov2_set_err(c, OV2_ERR_INVALID, "map %d: the update stage of its last set-up has already run", b);
+        if (m->last_kind != 1)
+            return ov2_set_err(c, OV2_ERR_INVALID, "map %d: its last set-up is localBA's (ov2_map_local_ba_update_batch updates from it)", b);
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
+        if (inv < 0) inv = m->last_inv;
+        if (m->last_inv != inv) return ov2_set_err(c, OV2_ERR_INVALID, "the maps of a batch must share one landmark parametrisation (map %d)", b);
+        if (inv && !m->have_K && m->last_hdr[MH_NRES])
+            return ov2_set_err(c, OV2_ERR_INVALID, "map %d: the inverse-depth update needs the left intrinsics (calib_l of the set-up)", b);
+    }
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    job_table JT;
+    if ((s = JT.begin(c, B, LB_EXTRA_INTS)) != OV2_OK) return s;
+    int nset = 0, nnow = 0, lmax = 0, kmax = 0, lmmax = 0;
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = maps[b];
+        map_job j = job_of(m, m->last_newkf, cur_kfid ? cur_kfid[b] : -1);
+        j.outlier = d_outlier ? d_outlier[b] : nullptr;
+        j.last_n_obs = m->last_n_obs;
+        j.lb_on = m->last_hdr[MH_NRES] > 0;   // a problem without a residual block changes nothing (:1272)
+        if (!j.lb_on) { j.outlier = nullptr; j.last_n_obs = 0; }
+        JT.set(b, j);
+        JT.host[b].lb_cnt = JT.host[b].hdr_out + MH_N;
+        JT.host[b].lb_tmp = (double *)(JT.host[b].hdr_out + MH_N + LB_N);
+        if (!j.lb_on) continue;
+        nset = std::max(nset, m->last_n_obs); nnow = std::max(nnow, m->n_obs); kmax = std::max(kmax, m->max_kf);
+        lmax = std::max(lmax, m->last_hdr[MH_NLM] + m->last_hdr[MH_NBAD]); lmmax = std::max(lmmax, m->max_lm);
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    const dim3 b256(256);
+    const int gN = (nset + 255) / 256, gNow = (nnow + 255) / 256, gLM = (lmax + 255) / 256;
+    const dim3 gL((std::max(lmmax, 1) + 255) / 256, B), gK((std::max(kmax, 1) + 255) / 256, B);
+    OV2_LAUNCH(c, OV2_K_MAP, ml_clear_kernel, gL, b256, 0, st, JT.dev, inv);
+    if (gNow > 0) {
+        OV2_LAUNCH(c, OV2_K_MAP, ml_observers_kernel, dim3(gNow, B), b256, 0, st, JT.dev, inv);
+        OV2_LAUNCH(c, OV2_K_MAP, ml_landmarks_kernel, gL, b256, 0, st, JT.dev, inv);
+        OV2_LAUNCH(c, OV2_K_MAP, ml_poses_kernel, gK, b256, 0, st, JT.dev, inv);
+        if (gN + gLM > 0) OV2_LAUNCH(c, OV2_K_MAP, mu_obs_kernel, dim3(gN + gLM, B), b256, 0, st, JT.dev, gN, inv);
+        if (gLM > 0) {
+            OV2_LAUNCH(c, OV2_K_MAP, mu_recount_kernel, dim3(gNow, B), b256, 0, st, JT.dev);
+            OV2_LAUNCH(c, OV2_K_MAP, ml_cull_kernel, dim3(gLM, B), b256, 0, st, JT.dev, inv);
+        }
+    }
+    for (int b = 0; b < B; ++b) maps[b]->last_updated = 1;
+    if (!out && !lists) return OV2_OK;   // asynchronous: the caller did not ask for anything
+    OV2_LAUNCH(c, OV2_K_MAP, mb_hdr_gather_kernel, dim3(1, B), dim3(64), 0, st, JT.dev);
+    if ((s = JT.fetch_headers()) != OV2_OK) return s;
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = maps[b];
+        const int *H = JT.hdr_host + (size_t)b * JT.stride, *C = H + MH_N;
+        const bool ran = m->last_hdr[MH_NRES] > 0;
+        if (lists) {
+            memset(&lists[b], 0, sizeof(lists[b]));
+            if (ran) {
+                size_t off[FO_N];
+                flat_layout((size_t)m->last_hdr[MH_NPOSE], (size_t)m->last_hdr[MH_NLM], (size_t)m->last_hdr[MH_NRES],
+                            (size_t)m->last_hdr[MH_NBAD], inv ? 1 : 3, off);
+                const flat_out O = flat_ptrs(m->out_dev, off);
+                lists[b].n_removed_lm = H[MH_NRM_LM]; lists[b].n_removed_obs = H[MH_NRM_OBS]; lists[b].n_stereo_off = H[MH_NST_OFF];
+                lists[b].removed_lmid = O.rm_lm; lists[b].removed_obs = (const int32_t *)O.rm_obs; lists[b].stereo_off = (const int32_t *)O.st_off;
+            }
+        }
+        if (!out) continue;
+        ov2_map_loose_ba &r = out[b];
+        memset(&r, 0, sizeof(r));
+        r.termination = OV2_BA_TERM_SKIPPED;
+        if (!ran) continue;
+        r.ran = 1;
+        r.n_pose = H[MH_NPOSE]; r.n_free_pose = C[LB_FREE]; r.n_lm = H[MH_NLM]; r.n_res = H[MH_NRES]; r.n_bad = C[LB_BAD];
+        r.n_flagged_left = C[LB_FLAG_L]; r.n_flagged_right = C[LB_FLAG_R]; r.n_removed_obs = H[MH_NRM_OBS]; r.n_stereo_off = H[MH_NST_OFF];
+        r.n_removed_lm = H[MH_NRM_LM]; r.n_written = C[LB_WRITTEN]; r.n_propagated = C[LB_PROP]; r.n_kf_younger = C[LB_YOUNGER];
+        memcpy(r.T_corr, (const double *)(C + LB_N) + 14, 7 * sizeof(double));
+    }
+    return OV2_OK;
+}
+
+extern "C" void ov2_ba_loose_options(ov2_ba_options *o, float robust_mono_th, int robust)
+{
+    ov2_ba_default_options(o, robust_mono_th);
+    if (!robust) o->huber_delta = 0.0;
+    o->max_iters = 5; o->function_tolerance = 1e-4;   // src/optimizer.cpp:1298-1299
+    o->l2_refine = 0;                                 // one solve; the flags only pick what is removed
+}
+
+extern "C" ov2_status ov2_map_loose_ba_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *inikfid, const int32_t *nkfid,
+                                             const ov2_map_sba_cam *cam, int stereo, int inv_depth, const ov2_ba_options *o,
+                                             const int32_t *cur_kfid, ov2_local_ba_update *lists, ov2_map_loose_ba *out)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps || !inikfid || !nkfid || !cam || !o) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_loose_ba_batch: null argument");
+    std::vector<double> K((size_t)B * 4);
+    for (int b = 0; b < B; ++b) memcpy(&K[4 * (size_t)b], cam[b].calib_l, 4 * sizeof(double));
+    std::vector<ov2_local_ba_setup> V((size_t)B);
+    ov2_status s = ov2_map_loose_ba_setup_batch(c, B, maps, inikfid, nkfid, stereo ? 1 : 2, inv_depth, K.data(), V.data());
+    if (s != OV2_OK) return s;
+    std::vector<ov2_ba_problem> P;
+    std::vector<ov2_ba_result> R;
+    std::vector<int> who;
+    std::vector<const uint8_t *> flags((size_t)B, nullptr);
+    for (int b = 0; b < B; ++b) {
+        const ov2_local_ba_setup &v = V[b];
+        if (v.n_res <= 0) continue;
+        ov2_ba_problem p;
+        memset(&p, 0, sizeof(p));
+        memcpy(p.calib_l, cam[b].calib_l, sizeof(p.calib_l)); memcpy(p.calib_r, cam[b].calib_r, sizeof(p.calib_r));
+        memcpy(p.T_rl, cam[b].T_rl, sizeof(p.T_rl));
+        p.inv_depth = inv_depth ? 1 : 0;
+        p.n_pose = v.n_pose; p.pose = v.pose; p.pose_const = v.pose_const;
+        p.n_lm = v.n_lm; p.lm = v.lm; p.lm_anchor_pose = v.lm_anchor_pose; p.lm_anchor_uv = v.lm_anchor_uv;
+        p.n_res = v.n_res; p.res_type = v.res_type; p.res_pose = v.res_pose; p.res_lm = v.res_lm; p.res_uv = v.res_uv; p.res_sigma = v.res_sigma;
+        ov2_ba_result r;
+        memset(&r, 0, sizeof(r));
+        r.outlier = v.res_outlier;
+        P.push_back(p); R.push_back(r); who.push_back(b);
+        flags[b] = v.res_outlier;
+    }
+    if (!P.empty() && (s = ov2_ba_solve_batch_dev(c, (int)P.size(), P.data(), o, R.data())) != OV2_OK) return s;
+    if ((s = ov2_map_loose_ba_update_batch(c, B, maps, flags.data(), cur_kfid, lists, out)) != OV2_OK) return s;
+    if (out)
+        for (size_t w = 0; w < who.size(); ++w) {
+            ov2_map_loose_ba &r = out[who[w]];
+            r.termination = R[w].termination; r.n_outliers_pass1 = R[w].n_outliers_pass1; r.n_log = R[w].n_log;
+            r.initial_cost = R[w].initial_cost; r.final_cost = R[w].final_cost;
+            memcpy(r.log, R[w].log, sizeof(r.log));
+        }
     return OV2_OK;
 }
 

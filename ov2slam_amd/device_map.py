@@ -87,6 +87,14 @@ class DevPairs:
         self.d_prev, self.d_new, self.d_n_pairs, self.d_cur_obs = d_prev, d_new, d_n_pairs, d_cur_obs
 
 
+class LooseBaC(C.Structure):
+    """ov2_map_loose_ba"""
+    _fields_ = [(n, C.c_int32) for n in ("ran", "n_pose", "n_free_pose", "n_lm", "n_res", "n_bad", "n_flagged_left", "n_flagged_right",
+                                         "n_removed_obs", "n_stereo_off", "n_removed_lm", "n_written", "n_propagated", "n_kf_younger",
+                                         "termination", "n_outliers_pass1", "n_log", "reserved")] + [
+        ("T_corr", C.c_double * 7), ("initial_cost", C.c_double), ("final_cost", C.c_double), ("log", BaIterC * MAX_LOG)]
+
+
 class UpdateC(C.Structure):
     """ov2_local_ba_update"""
     _fields_ = [("n_removed_lm", C.c_int32), ("n_removed_obs", C.c_int32), ("n_stereo_off", C.c_int32),
@@ -292,6 +300,14 @@ class DeviceMap:
         maps = [self] + list(others)
         cams = [SbaCamC.of(m.prob) for m in maps] if cam is None else (list(cam) if isinstance(cam, (list, tuple)) else [cam] * len(maps))
         return structure_ba_batch(self.ctx, maps, lmids, cams, structure_ba_options(self.ctx, max_iters), want_header)
+
+    def loose_ba_batch(self, others=(), inikfid=None, nkfid=None, cam=None, stereo=True, inv_depth=True, options=None, cur_kfid=None,
+                       want=True):
+        """ov2_map_loose_ba_batch on this map and `others` in one call: cam one SbaCamC for all maps or one per map (default: of
+        each map's problem); see loose_ba_batch"""
+        maps = [self] + list(others)
+        cams = [SbaCamC.of(m.prob) for m in maps] if cam is None else (list(cam) if isinstance(cam, (list, tuple)) else [cam] * len(maps))
+        return loose_ba_batch(self.ctx, maps, inikfid, nkfid, cams, stereo, inv_depth, options, cur_kfid, want)
 
     def close(self):
         if getattr(self, "h", None):
@@ -780,6 +796,111 @@ def update_batch(ctx, maps, views, cur_kfid=None, want_lists=True, outliers=None
         res.append(dict(removed_lmid=np.sort(fetch(u.removed_lmid, u.n_removed_lm, 1)),
                         removed_obs=fetch(u.removed_obs, u.n_removed_obs, 2), stereo_off=fetch(u.stereo_off, u.n_stereo_off, 2)))
     return res
+
+
+def loose_setup_batch(ctx, maps, inikfid, nkfid, nmin_cst_kfs=1, inv_depth=True, calib_l=None):
+    """ov2_map_loose_ba_setup_batch over the keyframes [inikfid[b], nkfid[b]]: returns the array of SetupC device views (one
+    synchronisation for all maps)"""
+    B = len(maps)
+    hs = (C.c_void_p * max(B, 1))(*[getattr(m, "h", m) for m in maps])
+    lo, hi = np.ascontiguousarray(inikfid, np.int32).reshape(-1), np.ascontiguousarray(nkfid, np.int32).reshape(-1)
+    assert len(lo) == B and len(hi) == B
+    K = None if calib_l is None else np.ascontiguousarray(np.broadcast_to(np.asarray(calib_l, np.float64), (B, 4)))
+    out = (SetupC * max(B, 1))()
+    _check(ctx.h, ctx.lib.ov2_map_loose_ba_setup_batch(ctx.h, B, hs, lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p),
+                                                       int(nmin_cst_kfs), int(bool(inv_depth)),
+                                                       None if K is None else K.ctypes.data_as(C.c_void_p), out))
+    return out
+
+
+def loose_ba_options(ctx, robust_mono_th=5.9915, robust=True):
+    """ov2_ba_loose_options: the options Optimizer::looseBA runs with (src/optimizer.cpp:1298-1299)"""
+    o = BaOptionsC()
+    ctx.lib.ov2_ba_loose_options(C.byref(o), float(robust_mono_th), int(bool(robust)))
+    return o
+
+
+def _fetch_lists(ctx, u):
+    def fetch(ptr, n, cols):
+        a = np.zeros((n, cols) if cols > 1 else (n,), np.int32)
+        if n:
+            _check(ctx.h, ctx.lib.ov2_memcpy_d2h(ctx.h, a.ctypes.data_as(C.c_void_p), ptr, a.nbytes))
+        return a
+    return dict(removed_lmid=np.sort(fetch(u.removed_lmid, u.n_removed_lm, 1)), removed_obs=fetch(u.removed_obs, u.n_removed_obs, 2),
+                stereo_off=fetch(u.stereo_off, u.n_stereo_off, 2))
+
+
+_LOOSE_COUNTS = ("ran", "n_pose", "n_free_pose", "n_lm", "n_res", "n_bad", "n_flagged_left", "n_flagged_right", "n_removed_obs",
+                 "n_stereo_off", "n_removed_lm", "n_written", "n_propagated", "n_kf_younger", "termination", "n_outliers_pass1", "n_log")
+
+
+def _loose_records(ctx, out, lists, fetch_lists=True):
+    res = []
+    for b, u in enumerate(out):
+        d = {k: getattr(u, k) for k in _LOOSE_COUNTS}
+        d.update(T_corr=np.array(u.T_corr[:]), initial_cost=u.initial_cost, final_cost=u.final_cost,
+                 log=[dict(cost=i.cost, cost_change=i.cost_change, radius=i.radius, relative_decrease=i.relative_decrease,
+                           model_cost_change=i.model_cost_change, valid=bool(i.step_is_valid), ok=bool(i.step_is_successful))
+                      for i in u.log[:u.n_log]], raw=bytes(u))
+        if fetch_lists:   # three synchronising copies per map
+            d.update(_fetch_lists(ctx, lists[b]))
+        res.append(d)
+    return res
+
+
+def loose_update_batch(ctx, maps, views, cur_kfid=None, want=True, outliers=None, fetch_lists=True):
+    """ov2_map_loose_ba_update_batch with the outlier flags the solve left in the maps' blocks, or -- outliers[b], a host array
+    of n_res flags per map (None: the solve's) -- flags uploaded for the call; returns per map the ov2_map_loose_ba record as
+    a dict plus (fetch_lists) removed_lmid, removed_obs (n x 2: kfid, lmid), stereo_off (n x 2) -- or None (want=False:
+    asynchronous)"""
+    B = len(maps)
+    hs = (C.c_void_p * max(B, 1))(*[getattr(m, "h", m) for m in maps])
+    ptrs, owned = [], []
+    try:
+        for b, v in enumerate(views):
+            f = None if outliers is None else outliers[b]
+            if f is None or v.n_res == 0:
+                ptrs.append(v.res_outlier if v.n_res else None)
+                continue
+            f = np.ascontiguousarray(f, np.uint8)
+            assert f.shape == (v.n_res,)
+            d = C.c_void_p()
+            _check(ctx.h, ctx.lib.ov2_dev_alloc(ctx.h, max(f.nbytes, 1), C.byref(d)))
+            owned.append(d)
+            _check(ctx.h, ctx.lib.ov2_memcpy_h2d(ctx.h, d, f.ctypes.data_as(C.c_void_p), f.nbytes))
+            ptrs.append(d.value)
+        outl = (C.c_void_p * max(B, 1))(*ptrs)
+        ck = None if cur_kfid is None else np.ascontiguousarray(cur_kfid, np.int32)
+        out = (LooseBaC * max(B, 1))() if want else None
+        lists = (UpdateC * max(B, 1))() if want else None
+        _check(ctx.h, ctx.lib.ov2_map_loose_ba_update_batch(ctx.h, B, hs, outl, None if ck is None else ck.ctypes.data_as(C.c_void_p),
+                                                            lists, out))
+    finally:
+        if owned:   # the update may still be reading them
+            ctx.lib.ov2_ctx_synchronize(ctx.h)
+            for d in owned:
+                ctx.lib.ov2_dev_free(ctx.h, d)
+    return _loose_records(ctx, out[:B], lists, fetch_lists) if want else None
+
+
+def loose_ba_batch(ctx, maps, inikfid, nkfid, cams, stereo=True, inv_depth=True, options=None, cur_kfid=None, want=True, fetch_lists=True):
+    """Optimizer::looseBA(inikfid[b], nkfid[b], .) on the tables of the maps (DeviceMap objects or raw ov2_map handles): set-up,
+    ov2_ba_solve_batch_dev, update in one call (ov2_map_loose_ba_batch); cams[b] an SbaCamC, options a BaOptionsC (default:
+    loose_ba_options).  Returns per map the record dict of loose_update_batch with the solve's termination, costs,
+    n_outliers_pass1 and log filled in -- or None (want=False)"""
+    B = len(maps)
+    hs = (C.c_void_p * max(B, 1))(*[getattr(m, "h", m) for m in maps])
+    lo, hi = np.ascontiguousarray(inikfid, np.int32).reshape(-1), np.ascontiguousarray(nkfid, np.int32).reshape(-1)
+    assert len(lo) == B and len(hi) == B and len(cams) == B
+    o = loose_ba_options(ctx) if options is None else options
+    cc = (SbaCamC * max(B, 1))(*cams)
+    ck = None if cur_kfid is None else np.ascontiguousarray(cur_kfid, np.int32)
+    out = (LooseBaC * max(B, 1))() if want else None
+    lists = (UpdateC * max(B, 1))() if want else None
+    _check(ctx.h, ctx.lib.ov2_map_loose_ba_batch(ctx.h, B, hs, lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), cc,
+                                                 int(bool(stereo)), int(bool(inv_depth)), C.byref(o),
+                                                 None if ck is None else ck.ctypes.data_as(C.c_void_p), lists, out))
+    return _loose_records(ctx, out[:B], lists, fetch_lists) if want else None
 
 
 def fetch_view(ctx, v, inv_depth):

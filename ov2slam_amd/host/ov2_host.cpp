@@ -1840,7 +1840,16 @@ ov2_status Optimizer::looseBA(int inikfid, const int nkfid, const bool buse_robu
     std::memset(&last_result_, 0, sizeof(last_result_));
     last_result_.chi2 = chi2.data(); last_result_.depth_positive = depth.data(); last_result_.outlier = outlier.data();
     const ov2_status s = ov2_ba_solve(ctx_, &p, &o, &last_result_);
-    if (s != OV2_OK) { last_result_.chi2 = nullptr; last_result_.depth_positive = nullptr; last_result_.outlier = nullptr; return s; }
+    last_result_.chi2 = nullptr; last_result_.depth_positive = nullptr; last_result_.outlier = nullptr;
+    if (s != OV2_OK) return s;
+    applyLooseBA(newframe, pb, outlier.data());
+    return OV2_OK;
+}
+
+// the update stage of looseBA (:1330-1657) from a flat problem whose pose / lm arrays hold the solved states and the
+// per-block flags of the solve: split off so that a test can hand it a crafted state (ov2h_apply_loose_ba)
+void Optimizer::applyLooseBA(Frame &newframe, LocalBAProblem &pb, const uint8_t *outlier, SE3 *T_corr)
+{
     const bool inv = pslamstate_->buse_inv_depth_;
     // flags (:1330-1426)
     std::vector<std::pair<int, int>> vbadkflmids, vbadstereokflmids;
@@ -1852,11 +1861,11 @@ ov2_status Optimizer::looseBA(int inikfid, const int nkfid, const bool buse_robu
         else vbadstereokflmids.emplace_back(kfid, lmid);
         pb.set_badlmids.insert(lmid);
     }
-    last_result_.chi2 = nullptr; last_result_.depth_positive = nullptr; last_result_.outlier = nullptr;
     // new states (:1432-1526)
     const SE3 iniTnewkfw = newframe.getTcw();
     SE3 optTwnewkf;
     { const int idx = pb.kfid_to_pose.at(newframe.kfid_); for (int k = 0; k < 7; ++k) optTwnewkf.v[k] = pb.pose[7 * idx + k]; }
+    if (T_corr) *T_corr = optTwnewkf * iniTnewkfw;   // what the current frame moves by (:1653-1656)
     std::vector<std::pair<int, Vec3>> vlm;
     for (const auto &kv : pb.map_local_plms) {
         const int lmid = kv.first;
@@ -1930,7 +1939,6 @@ ov2_status Optimizer::looseBA(int inikfid, const int nkfid, const bool buse_robu
         auto pc = pmap_->pcurframe_;
         pc->setTwc(optTwnewkf * (iniTnewkfw * pc->getTwc()));
     }
-    return OV2_OK;
 }
 
 // ---- pose graphs ------------------------------------------------------------------------------------------------

@@ -459,6 +459,9 @@ public:
     // constant), one robust solve of 5 iterations (function_tolerance 1e-4), then the corrections are propagated to the
     // younger keyframes, their own landmarks and the current frame
     ov2_status looseBA(int inikfid, const int nkfid, const bool buse_robust_cost);
+    // its update stage alone (:1330-1657): pb.pose / pb.lm hold the solved states, outlier the per-block flags of the solve;
+    // T_corr (may be null) takes optTwnewkf * iniTnewkfw, the correction the younger keyframes and the current frame move by
+    void applyLooseBA(Frame &newframe, LocalBAProblem &pb, const uint8_t *outlier, SE3 *T_corr = nullptr);
     // src/optimizer.cpp:2346-2592 (LoopCloser, src/loop_closer.cpp:320): keyframes kfloop_id .. newframe joined by their
     // relative poses + the loop edge kfloop_id -> newframe from the P3P pose newTwc, loop keyframe constant; solved by
     // ov2_pose_graph_solve (10 iterations, 1e-4); rejected when the optimised new pose lands > 0.3 m from newTwc (stereo);

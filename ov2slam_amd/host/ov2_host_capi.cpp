@@ -1069,6 +1069,51 @@ int ov2h_loose_ba(void *p, void *ctx, int inikfid, int nkfid, int robust, int *n
     return s;
 }
 
+// MapManager::removeKeyframe(kfid): its observations leave their map points, its covisibility entries go; with a mirror
+// attached the removal reaches it at once (ov2_map_remove_keyframe)
+int ov2h_map_remove_keyframe(void *p, int kfid)
+{
+    return (int)((HostMap *)p)->map->removeKeyframe(kfid);
+}
+
+// MapManager::pcurframe_ as a live sequence has it: a Frame of its own that carries keyframe kfid's id, pose and keypoints
+// (ov2h_map_finalize makes the newest keyframe OBJECT the current frame, which then takes every current-frame update on
+// top of its keyframe update); kfid < 0: no current frame
+int ov2h_map_set_cur_frame(void *p, int kfid)
+{
+    HostMap *m = (HostMap *)p;
+    if (kfid < 0) { m->map->pcurframe_ = nullptr; return 0; }
+    auto f = m->map->getKeyframe(kfid);
+    if (!f) return -1;
+    m->map->pcurframe_ = std::make_shared<Frame>(*f);
+    return 0;
+}
+
+// Optimizer::applyLooseBA alone: the assembly of looseBA(inikfid, nkfid, .), then the free poses (n_pose x 7), the landmarks
+// (n_lm x 1 or 3) and the per-block flags (n_res bytes) of the flat problem are overwritten with the given arrays -- in the
+// order ov2h_range_ba_setup(inikfid, nkfid, nkfid, 0) lists them -- and the update stage runs.  Needs no GPU context.
+// T_corr7 (may be NULL): opt * inverse(old(nkfid)), the correction of the loop keyframe, as the stage formed it.
+// returns 1 ran, 0 no-op (no residual block), < 0 error (-1 nkfid not alive, -2 the sizes are not those of the problem)
+int ov2h_apply_loose_ba(void *p, int inikfid, int nkfid, int n_pose, const double *pose, int n_lm, const double *lm, int n_res,
+                        const uint8_t *outlier, double *T_corr7)
+{
+    HostMap *m = (HostMap *)p;
+    auto pnew = m->map->getKeyframe(nkfid);
+    if (!pnew) return -1;
+    Optimizer opt(nullptr, m->st, m->map);
+    LocalBAProblem pb;
+    opt.setupRangeBA(inikfid, nkfid, pnew->kfid_, 0, pb);
+    if (pb.res_type.empty() || !pb.kfid_to_pose.count(pnew->kfid_)) return 0;
+    if (n_pose != (int)pb.pose_const.size() || n_lm != (int)pb.lm_lmid.size() || n_res != (int)pb.res_type.size()) return -2;
+    for (int i = 0; i < n_pose; ++i)
+        if (!pb.pose_const[i]) std::copy(pose + 7 * (size_t)i, pose + 7 * (size_t)i + 7, pb.pose.begin() + 7 * (size_t)i);
+    std::copy(lm, lm + pb.lm.size(), pb.lm.begin());
+    SE3 T;
+    opt.applyLooseBA(*pnew, pb, outlier, &T);
+    if (T_corr7) std::copy(T.v.begin(), T.v.end(), T_corr7);
+    return 1;
+}
+
 // Optimizer::localPoseGraph(newframe = keyframe newkf, kfloop_id, newTwc). returns 1 accepted, 0 rejected, < 0 error
 int ov2h_local_pose_graph(void *p, void *ctx, int newkf, int kfloop_id, const double *newTwc7, double *final_cost, int *n_log)
 {

@@ -40,6 +40,9 @@ def lib():
         L.ov2h_apply_local_pose_graph.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp]
         L.ov2h_full_pose_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, dp, C.POINTER(C.c_uint8), C.POINTER(C.c_double)]
         L.ov2h_loose_ba.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_double)]
+        L.ov2h_map_set_cur_frame.argtypes = [C.c_void_p, C.c_int]
+        L.ov2h_apply_loose_ba.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, C.c_int, u8, dp]
+        L.ov2h_map_remove_keyframe.argtypes = [C.c_void_p, C.c_int]
         L.ov2h_map_remove_obs.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ov2h_map_remove_landmark.argtypes = [C.c_void_p, C.c_int]
         L.ov2h_map_set_isobs.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -323,6 +326,33 @@ class HostMap:
         n1, fc = C.c_int(), C.c_double()
         st = lib().ov2h_loose_ba(self.h, ctx.h, int(inikfid), int(nkfid), int(robust), C.byref(n1), C.byref(fc))
         return st, n1.value, fc.value
+
+    def remove_keyframe(self, kfid):
+        """MapManager::removeKeyframe"""
+        assert lib().ov2h_map_remove_keyframe(self.h, int(kfid)) == 0
+
+    def set_cur_frame(self, kfid):
+        """MapManager::pcurframe_ becomes a Frame of its own with keyframe kfid's id, pose and keypoints (None: no current
+        frame).  The constructor leaves the newest keyframe OBJECT as the current frame, which then receives the
+        current-frame updates of looseBA / localPoseGraph on top of its keyframe update."""
+        assert lib().ov2h_map_set_cur_frame(self.h, -1 if kfid is None else int(kfid)) == 0
+
+    def apply_loose_ba(self, inikfid, nkfid, pose, lm, outlier):
+        """Optimizer::applyLooseBA alone: looseBA's assembly, then the free poses (n_pose x 7), landmarks (n_lm x 1 or 3)
+        and per-block flags (n_res bytes) replace those of the flat problem -- in the order setup_range_ba(inikfid, nkfid,
+        kf_obs_max=nkfid, min_obs=0) lists them -- and the update stage runs.  Needs no GPU context; with a device mirror
+        attached the edits wait in its dirty lists for flush_device().  returns T_corr = opt * inverse(old(nkfid)) as the
+        stage formed it (7 doubles), or None when the range yields no residual block and nothing ran."""
+        P = np.ascontiguousarray(pose, np.float64).reshape(-1, 7)
+        Lm = np.ascontiguousarray(lm, np.float64)
+        n_lm = Lm.shape[0] if Lm.ndim > 1 else (Lm.size if self.prob.inv_depth else Lm.size // 3)
+        F = np.ascontiguousarray(outlier, np.uint8)
+        T = np.zeros(7)
+        rc = lib().ov2h_apply_loose_ba(self.h, int(inikfid), int(nkfid), len(P), _dp(P), int(n_lm), _dp(Lm), len(F),
+                                       F.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(T))
+        if rc < 0:
+            raise RuntimeError(f"applyLooseBA failed ({rc})")
+        return T if rc else None
 
     def local_pose_graph(self, ctx, newkf, kfloop_id, newTwc):
         """Optimizer::localPoseGraph. returns (1 accepted / 0 rejected, final cost, logged iterations)"""
