@@ -809,6 +809,18 @@ ov2_status ov2_pose_graph_solve(ov2_ctx *ctx, const ov2_pg_problem *p, const ov2
 #define OV2_PG_MAX_BATCH 65535
 ov2_status ov2_pose_graph_solve_batch(ov2_ctx *ctx, int B, const ov2_pg_problem *p, const ov2_ba_options *o, ov2_pg_result *r);
 
+/* The batch solve on device-resident values: p[b].pose and p[b].T_ij are DEVICE pointers (the poses are solved in place) and
+ * d_r is a DEVICE array of B result records.  The structure fields (n_pose, pose_const, n_edge, edge_i, edge_j) stay HOST
+ * arrays, so validation, its statuses and the solver's plan are those of ov2_pose_graph_solve_batch.  The call enqueues a
+ * clear of the records, ONE upload (descriptors and structure arrays, out of a pinned area of the solver's own) and ONE
+ * launch of the same minimiser on the context's stream and returns: no download, no synchronisation.  Descriptors,
+ * structure and workspaces live in a device block the context keeps for this solver alone, so a later call that hands the
+ * shared staging block out again cannot touch a queued solve; the pinned area is rewritten only once the stream has passed
+ * the upload.  Every graph takes a workgroup; one without a free pose or without an edge only marks its record
+ * OV2_BA_TERM_SKIPPED.  Poses, records and logs are bit-identical to ov2_pose_graph_solve_batch on the same inputs. */
+ov2_status ov2_pose_graph_solve_batch_dev(ov2_ctx *ctx, int B, const ov2_pg_problem *p, const ov2_ba_options *o,
+                                          ov2_pg_result *d_r /* DEVICE, B */);
+
 /* ---------------------------------------------------------------------------------------------------
  * Flat device-resident map mirror: keyframe poses, landmark states and the observation table
  * (keyframe, landmark, unpx, runpx, scale, stereo flag) as SoA arrays in HBM, kept in step with the reference's
@@ -1090,6 +1102,67 @@ typedef struct ov2_map_pg_update {
 ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf,
                                            const int32_t *chain_off /* B + 1 */, const int32_t *chain_kfid,
                                            const double *chain_Twc /* x 7 */, ov2_map_pg_update *out /* B, or NULL */);
+/* The same update with the optimised poses where a solve left them: d_chain_Twc is a DEVICE array laid out as chain_Twc
+ * (for ov2_pose_graph_solve_batch_dev: the solved pose block past its constant first pose), chain_off and chain_kfid stay
+ * HOST arrays.  d_skip (B bytes in DEVICE memory, or NULL) gates the maps on the device: where the byte is non-zero when the
+ * kernels run, the map is left alone -- tables untouched, zero header and zero T_corr -- without the host knowing.  The four
+ * kernels are those of the host form; everything else (launch count, refusals, `out`) is as above. */
+ov2_status ov2_map_pose_graph_update_batch_dev(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf,
+                                               const int32_t *chain_off /* HOST, B + 1 */, const int32_t *chain_kfid /* HOST */,
+                                               const double *d_chain_Twc /* x 7 */, const uint8_t *d_skip /* B, or NULL */,
+                                               ov2_map_pg_update *out /* B, or NULL */);
+
+/* Optimizer::localPoseGraph(newframe, kfloop_id, newTwc) (src/optimizer.cpp:2346-2592), the first statement of a loop closure
+ * (src/loop_closer.cpp:320), on B map mirrors of one context that have no host objects beside them: assembly, solve, the
+ * degenerate-solution test and the update are enqueued on the context's stream, and the launch count does not depend on B.
+ *   newkf, kfloop_id   B        the new keyframe and the keyframe the chain starts from (the caller's inikfid)
+ *   newTwc             B x 7    HOST: the loop pose of the new keyframe (the P3P / PnP result)
+ *   stereo                      SlamParams::stereo_: the degenerate test only refuses a stereo map
+ *   o                           the options of the solve; NULL = localPoseGraph's (the trust-region defaults, 10 iterations, 1e-4)
+ *   d_n_pairs          B        DEVICE int32, or NULL: the entry of every map whose verdict is not OV2_LPG_DONE is set to 0 --
+ *                               the array ov2_map_merge_points_batch_dev and ov2_map_structure_ba_batch_dev read their counts
+ *                               from, so that a refused loop merges nothing without the host learning of it
+ * The chain (:2368-2425) is derived on the host from its copy of the keyframe states, without a synchronisation: a dead
+ * kfloop_id walks up to the next live keyframe, dead keyframes inside the range are skipped; a dead (or out-of-range) newkf,
+ * no live loop keyframe below newkf, or fewer than two poses give the map OV2_LPG_NO_CHAIN and no work on the device.
+ * Launches (map = blockIdx.y or one lane per map):
+ *  1. assembly: the n_pose poses (loop keyframe first, then the live keyframes up to newkf in ascending id), the n_pose - 1
+ *     odometry edges T_ij = inverse(Twc_i) * Twc_j between consecutive listed keyframes and the closing edge (0, n_pose - 1)
+ *     with inverse(Twc_loop) * newTwc, in the SE(3) product and inverse of the host mirror's SE3: bitwise what
+ *     Optimizer::assembleLocalPoseGraph of ov2slam_amd/host computes;
+ *  2. the minimiser of ov2_pose_graph_solve_batch_dev, one workgroup per map that has a chain, loop keyframe constant;
+ *  3. the gate, one lane per map: stereo && |t(newTwc) - t(optimised pose of newkf)| > 0.3 (:2468-2474, the f64 expression of
+ *     the host stage) gives OV2_LPG_DEGENERATE; the lane writes the map's skip byte and clears its d_n_pairs entry;
+ *  4. - 7. the four launches of ov2_map_pose_graph_update_batch_dev on the solved block, gated by the skip bytes;
+ *  8. with `out`, the header gather.
+ * out = NULL: nothing synchronises.  With `out` the call synchronises once; out[b] carries the verdict, the loop keyframe
+ * used after the walk-up (-1 without a chain), n_pose, the update's header (zero unless OV2_LPG_DONE; T_corr is what the
+ * caller applies to its current frame, :2580-2585) and the solve's record (OV2_BA_TERM_SKIPPED without a chain).
+ * A map whose verdict is not OV2_LPG_DONE keeps its tables bit for bit.  Refused with OV2_ERR_INVALID before anything is
+ * enqueued: B < 0, a null array, a map named twice, a map of another context, max_iters outside [0, OV2_BA_MAX_LOG - 1].
+ * Like the update call it ends what the last set-up of a map with a chain can be updated from, and borrows the temporal
+ * stage's cleared block.  The problem block lives in a device block of the context that the next call of this entry point
+ * reuses (in stream order). */
+#define OV2_LPG_DONE       0
+#define OV2_LPG_DEGENERATE 1
+#define OV2_LPG_NO_CHAIN   2
+typedef struct ov2_map_local_pg {
+    int32_t verdict;                /* OV2_LPG_* */
+    int32_t kfloop_id;              /* the loop keyframe after the walk-up, -1: none */
+    int32_t n_pose, reserved;
+    ov2_map_pg_update update;
+    ov2_pg_result result;
+} ov2_map_local_pg;
+ov2_status ov2_map_local_pose_graph_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf,
+                                          const int32_t *kfloop_id, const double *newTwc /* HOST, B x 7 */, int stereo,
+                                          const ov2_ba_options *o /* or NULL */, int32_t *d_n_pairs /* DEVICE B, or NULL */,
+                                          ov2_map_local_pg *out /* B, or NULL */);
+/* Test hook: the assembly launch alone, downloaded (one synchronisation).  chain_off (B + 1) receives where map b's poses and
+ * edges start in kfid / pose / T_ij, which have room for `cap` poses (OV2_ERR_INVALID when the chains need more); a map
+ * without a chain lists nothing.  Edge e < n - 1 of a map joins its poses (e, e + 1), edge n - 1 is the closing edge. */
+ov2_status ov2_map_local_pose_graph_assemble(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf,
+                                             const int32_t *kfloop_id, const double *newTwc /* HOST, B x 7 */, int cap,
+                                             int32_t *chain_off, int32_t *kfid, double *pose /* x 7 */, double *T_ij /* x 7 */);
 
 /* MapManager::mergeMapPoints (src/map_manager.cpp:801-882) on the tables of B map mirrors of one context, for maps that have
  * no host objects beside them: what Mapper::mergeMatches (src/mapper.cpp:556-574) does per match and LoopCloser

@@ -99,6 +99,10 @@ SIGNATURES = {
     "ov2_pose_graph_solve": (C.c_int, [vp, vp, vp, vp]),
     "ov2_pose_graph_solve_batch": (C.c_int, [vp, C.c_int, vp, vp, vp]),
     "ov2_map_pose_graph_update_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "ov2_pose_graph_solve_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    "ov2_map_pose_graph_update_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "ov2_map_local_pose_graph_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]),
+    "ov2_map_local_pose_graph_assemble": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
     "ov2_map_merge_points_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "ov2_map_merge_points_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ov2_map_structure_ba_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),

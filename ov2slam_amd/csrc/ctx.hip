@@ -172,6 +172,10 @@ ov2_status ctx_create(int device, int high_priority, int n_cus, int layout, ov2_
     c->stage_cap = 0;
     c->stage_ev = nullptr;
     c->stage_ev_pending = false;
+    c->pg_dev = c->pg_pin = c->lpg_dev = nullptr;
+    c->pg_dev_cap = c->pg_pin_cap = c->lpg_dev_cap = 0;
+    c->pg_ev = nullptr;
+    c->pg_ev_pending = false;
     c->stream_kf = nullptr;
     c->kf_scratch_dev = nullptr;
     c->kf_scratch_bytes = 0;
@@ -257,6 +261,10 @@ extern "C" void ov2_ctx_destroy(ov2_ctx *c)
     (void)hipEventDestroy(c->ev0);
     (void)hipEventDestroy(c->ev1);
     if (c->stage_ev) (void)hipEventDestroy(c->stage_ev);
+    if (c->pg_dev) (void)hipFree(c->pg_dev);
+    if (c->pg_pin) (void)hipHostFree(c->pg_pin);
+    if (c->lpg_dev) (void)hipFree(c->lpg_dev);
+    if (c->pg_ev) (void)hipEventDestroy(c->pg_ev);
     if (c->kf.fork) (void)hipEventDestroy(c->kf.fork);
     if (c->kf.done) (void)hipEventDestroy(c->kf.done);
     (void)hipStreamDestroy(c->stream_kf);
@@ -547,6 +555,39 @@ ov2_status ov2_staging(ov2_ctx *c, size_t bytes, void **host, void **dev)
     }
     *host = c->stage_host;
     *dev = c->stage_dev;
+    return OV2_OK;
+}
+
+ov2_status ov2_dev_block(ov2_ctx *c, void **blk, size_t *cap, size_t bytes)
+{
+    if (bytes <= *cap) return OV2_OK;
+    OV2_HIP(c, hipStreamSynchronize(c->stream));   // a queued kernel may still work in the old block
+    if (*blk) OV2_HIP(c, hipFree(*blk));
+    *blk = nullptr;
+    *cap = 0;
+    const size_t want = bytes + bytes / 2 + 4096;
+    if (hipMalloc(blk, want) != hipSuccess) return ov2_set_err(c, OV2_ERR_NOMEM, "device block of %zu bytes", want);
+    *cap = want;
+    return OV2_OK;
+}
+
+ov2_status ov2_pg_pinned(ov2_ctx *c, size_t bytes, void **host)
+{
+    if (!c->pg_ev) OV2_HIP(c, hipEventCreateWithFlags(&c->pg_ev, hipEventDisableTiming));
+    if (c->pg_ev_pending) {   // the upload of the solve before this one may still be reading the area
+        OV2_HIP(c, hipEventSynchronize(c->pg_ev));
+        c->pg_ev_pending = false;
+    }
+    if (bytes > c->pg_pin_cap) {
+        if (c->pg_pin) OV2_HIP(c, hipHostFree(c->pg_pin));
+        c->pg_pin = nullptr;
+        c->pg_pin_cap = 0;
+        const size_t want = bytes + bytes / 2 + 4096;
+        if (hipHostMalloc(&c->pg_pin, want, hipHostMallocDefault) != hipSuccess)
+            return ov2_set_err(c, OV2_ERR_NOMEM, "pinned pose-graph area of %zu bytes", want);
+        c->pg_pin_cap = want;
+    }
+    *host = c->pg_pin;
     return OV2_OK;
 }
 

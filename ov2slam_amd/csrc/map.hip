@@ -228,6 +228,14 @@ struct map_job {
     int pg_n;                                    // free keyframes of the graph, 0: nothing to do for this map
     const int *pg_kfid; const double *pg_Twc;    // their ids (ascending, last = newkf) and optimised poses, in the staging block
     double *pg_tmp;                              // 14 doubles behind hdr_out: inverse(old(newkf)) | T_corr
+    const unsigned char *pg_skip;                // null (host form), or one byte in device memory: non-zero = leave this map alone
+    // local pose graph, assembly and gate (hdr / zero_blk as for the update): the lp_n poses of the chain (0: no chain) are
+    // the keyframes lp_kfid (the loop keyframe, then ascending up to newkf); pg_kfid / pg_Twc / pg_skip above name the same
+    // block past its first pose
+    int lp_n, lp_stereo;
+    const int *lp_kfid; const double *lp_newTwc; // the loop pose the graph is built for
+    double *lp_pose, *lp_Tij;                    // the problem block: lp_n poses | lp_n edges, the closing edge last
+    unsigned char *lp_skip; int *lp_verdict, *lp_npairs;   // what the gate writes (lp_npairs may be null)
     // merge of map points (hdr / zero_blk point at the stage's own block in its job records)
     int mg_seg;                                  // pairs in this map's segment of the lists, 0: nothing to do for this map
     const int *mg_prev, *mg_new;                 // the segment: prevlmid / newlmid per pair, in list order
@@ -1823,6 +1831,56 @@ __device__ __forceinline__ void se3_apply(const double *T, const double *p, doub
     out[2] = R[6] * p[0] + R[7] * p[1] + R[8] * p[2] + T[2];
 }
 
+// the device-side gate of a map (ov2_map_pose_graph_update_batch_dev, ov2_map_local_pose_graph_batch); uniform per map
+__device__ __forceinline__ bool pg_skipped(const map_job &j) { return j.pg_skip && *j.pg_skip; }
+
+// ---- Optimizer::assembleLocalPoseGraph (src/optimizer.cpp:2361-2425) from the pose table --------------------------------
+// The host derived the chain (loop keyframe after the walk-up, then the live keyframes up to newkf) from its copy of the
+// keyframe states; only the values come from the device.  Lane i copies pose i of the chain and writes the edge that ENDS
+// in it: T_ij = Tciw * Twcj with Tciw = inverse(pose i - 1) (:2400-2415), in the host mirror's SE3 arithmetic; lane 0
+// writes the closing edge (0, lp_n - 1), inverse(Twc_loop) * newTwc (:2387, :2422-2425), behind the lp_n - 1 odometry
+// edges.  Every lane reads the table and writes its own seven + seven doubles: nothing is shared, nothing is reduced, and
+// the launch is bounded by the latency of two dependent loads per lane (the id, then the poses).
+__global__ __launch_bounds__(256) void mp_assemble_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= j.lp_n) return;
+    const double *Tj = j.M.kf_pose + 7 * (size_t)j.lp_kfid[i];
+    double Tciw[7], T[7];
+    if (i == 0) {
+        se3_inverse(Tj, Tciw);
+        se3_mul(Tciw, j.lp_newTwc, T);
+    } else {
+        se3_inverse(j.M.kf_pose + 7 * (size_t)j.lp_kfid[i - 1], Tciw);
+        se3_mul(Tciw, Tj, T);
+    }
+    double *e = j.lp_Tij + 7 * (size_t)(i == 0 ? j.lp_n - 1 : i - 1);
+#pragma unroll
+    for (int q = 0; q < 7; ++q) { j.lp_pose[7 * (size_t)i + q] = Tj[q]; e[q] = T[q]; }
+}
+
+// the degenerate-solution test of Optimizer::applyLocalPoseGraph (:2468-2474) on the solved block, one lane per map:
+// stereo && |t(newTwc) - t(optimised pose of newkf)| > 0.3, the f64 expression of the host stage.  The lane leaves the
+// map's skip byte for the update kernels, its verdict behind the gathered header and, for a map that is not DONE, a zero
+// in its slot of the caller's pair counts.
+__global__ __launch_bounds__(64) void mp_gate_kernel(const map_job *__restrict__ J, int B)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const map_job &j = J[b];
+    int verdict = OV2_LPG_NO_CHAIN;
+    if (j.lp_n) {
+        const double *opt = j.lp_pose + 7 * (size_t)(j.lp_n - 1), *nw = j.lp_newTwc;
+        const double dx = nw[0] - opt[0], dy = nw[1] - opt[1], dz = nw[2] - opt[2];
+        const bool deg = __dsqrt_rn(dx * dx + dy * dy + dz * dz) > 0.3 && j.lp_stereo;
+        verdict = deg ? OV2_LPG_DEGENERATE : OV2_LPG_DONE;
+        *j.lp_skip = deg ? 1 : 0;
+    }
+    *j.lp_verdict = verdict;
+    if (j.lp_npairs && verdict != OV2_LPG_DONE) *j.lp_npairs = 0;
+}
+
 // place of keyframe kf in the ascending list, -1 when it is not listed
 __device__ __forceinline__ int pg_listed(const map_job &j, int kf)
 {
@@ -1857,13 +1915,15 @@ __global__ __launch_bounds__(256) void mp_anchor_kernel(const map_job *__restric
     const map_job &j = J[blockIdx.y];
     const map_view &M = j.M;
     if (!j.pg_n) return;
+    const bool skip = pg_skipped(j);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         double ini[7], corr[7];
         se3_inverse(M.kf_pose + 7 * (size_t)j.newkf, ini);
         se3_mul(j.pg_Twc + 7 * (size_t)(j.pg_n - 1), ini, corr);
 #pragma unroll
-        for (int q = 0; q < 7; ++q) { j.pg_tmp[q] = ini[q]; j.pg_tmp[7 + q] = corr[q]; }
+        for (int q = 0; q < 7; ++q) { j.pg_tmp[q] = skip ? 0.0 : ini[q]; j.pg_tmp[7 + q] = skip ? 0.0 : corr[q]; }
     }
+    if (skip) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     int kf, lm;
     if (i >= M.n_obs || !obs_live(M, i, kf, lm)) return;
@@ -1875,7 +1935,7 @@ __global__ __launch_bounds__(256) void mp_landmarks_kernel(const map_job *__rest
 {
     const map_job &j = J[blockIdx.y];
     const map_view &M = j.M;
-    if (!j.pg_n || (int)blockIdx.x * 256 >= M.max_lm) return;   // uniform per workgroup
+    if (!j.pg_n || (int)blockIdx.x * 256 >= M.max_lm || pg_skipped(j)) return;   // uniform per workgroup
     const int l = blockIdx.x * 256 + threadIdx.x;
     bool moved = false;
     if (l < M.max_lm) {
@@ -1905,7 +1965,7 @@ __global__ __launch_bounds__(256) void mp_poses_kernel(const map_job *__restrict
 {
     const map_job &j = J[blockIdx.y];
     const map_view &M = j.M;
-    if (!j.pg_n || (int)blockIdx.x * 256 >= M.max_kf) return;   // uniform per workgroup
+    if (!j.pg_n || (int)blockIdx.x * 256 >= M.max_kf || pg_skipped(j)) return;   // uniform per workgroup
     const int k = blockIdx.x * 256 + threadIdx.x;
     bool listed = false, moved = false;
     if (k < M.max_kf && M.kf_state[k]) {
@@ -3344,16 +3404,37 @@ extern "C" ov2_status ov2_map_filter_keyframes_batch(ov2_ctx *c, int B, ov2_map 
 }
 
 // ---- pose-graph update of B maps: four launches whatever B, no synchronisation unless the headers are asked for -------
-extern "C" ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf,
-                                                      const int32_t *chain_off, const int32_t *chain_kfid, const double *chain_Twc,
-                                                      ov2_map_pg_update *out)
+namespace {
+
+// the update stage over a filled job table: the clear, the anchor scan, the landmarks, the poses
+void pg_update_launches(ov2_ctx *c, const job_table &JT, int nmax, int lmax, int kmax, unsigned zmax)
+{
+    hipStream_t st = c->stream;
+    const int B = JT.B;
+    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), gL((lmax + 255) / 256, B), gK((kmax + 255) / 256, B), b256(256);
+    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::min(64u, (zmax + 255) / 256), B), b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mp_anchor_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mp_landmarks_kernel, gL, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mp_poses_kernel, gK, b256, 0, st, JT.dev);
+}
+
+void pg_update_record(ov2_map_pg_update &u, const int *H)
+{
+    u.n_kf_chain = H[PH_KF_CHAIN]; u.n_kf_younger = H[PH_KF_YOUNGER]; u.n_lm_moved = H[PH_LM_MOVED];
+    memcpy(u.T_corr, (const double *)(H + MH_N) + 7, 7 * sizeof(double));
+}
+
+// both forms of the update call: dev = chain_Twc is a device array (and d_skip, if given, one byte per map in device memory)
+ov2_status pg_update_impl(ov2_ctx *c, const char *who, bool dev, int B, ov2_map *const *maps, const int32_t *newkf,
+                          const int32_t *chain_off, const int32_t *chain_kfid, const double *chain_Twc, const uint8_t *d_skip,
+                          ov2_map_pg_update *out)
 {
     if (!c) return OV2_ERR_INVALID;
     if (B == 0) return OV2_OK;
-    if (B < 0 || !maps || !newkf || !chain_off) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_pose_graph_update_batch: null argument");
+    if (B < 0 || !maps || !newkf || !chain_off) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null argument", who);
     ov2_status s;
     int n_active = 0;
-    if (chain_off[0] != 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_pose_graph_update_batch: chain_off[0] must be 0");
+    if (chain_off[0] != 0) return ov2_set_err(c, OV2_ERR_INVALID, "%s: chain_off[0] must be 0", who);
     for (int b = 0; b < B; ++b) {
         const ov2_map *m = maps[b];
         if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
@@ -3361,7 +3442,7 @@ extern "C" ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *c, int B, ov2_map
         const int n = chain_off[b + 1] - chain_off[b];
         if (n < 0) return ov2_set_err(c, OV2_ERR_INVALID, "map %d: chain_off descends", b);
         if (!n) continue;
-        if (!chain_kfid || !chain_Twc) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_pose_graph_update_batch: null argument");
+        if (!chain_kfid || !chain_Twc) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null argument", who);
         if ((s = batch_kf_alive(c, m, newkf[b], b)) != OV2_OK) return s;
         const int32_t *ids = chain_kfid + chain_off[b];
         for (int i = 0; i < n; ++i) {
@@ -3379,9 +3460,13 @@ extern "C" ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *c, int B, ov2_map
     const size_t total = (size_t)chain_off[B];
     const size_t ids_bytes = (total * sizeof(int32_t) + 15) & ~(size_t)15;
     job_table JT;
-    if ((s = JT.begin(c, B, 28, ids_bytes + total * 7 * sizeof(double))) != OV2_OK) return s;   // 28 ints = 14 doubles per map
+    if ((s = JT.begin(c, B, 28, ids_bytes + (dev ? 0 : total * 7 * sizeof(double)))) != OV2_OK) return s;   // 28 ints = 14 doubles per map
     memcpy(JT.tail_host, chain_kfid, total * sizeof(int32_t));
-    memcpy(JT.tail_host + ids_bytes, chain_Twc, total * 7 * sizeof(double));
+    const double *d_Twc = chain_Twc;
+    if (!dev) {
+        memcpy(JT.tail_host + ids_bytes, chain_Twc, total * 7 * sizeof(double));
+        d_Twc = (const double *)(JT.tail_dev + ids_bytes);
+    }
     int nmax = 0, lmax = 0, kmax = 0; unsigned zmax = 0;
     for (int b = 0; b < B; ++b) {
         ov2_map *m = maps[b];
@@ -3390,7 +3475,8 @@ extern "C" ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *c, int B, ov2_map
         stage_block(j, m->tt_zero, j.pg_n ? m->tt_zero_bytes : 0);
         j.tt_old = m->tt_old;
         j.pg_kfid = (const int *)JT.tail_dev + chain_off[b];
-        j.pg_Twc = (const double *)(JT.tail_dev + ids_bytes) + 7 * (size_t)chain_off[b];
+        j.pg_Twc = d_Twc + 7 * (size_t)chain_off[b];
+        j.pg_skip = d_skip ? d_skip + b : nullptr;
         JT.set(b, j);
         JT.host[b].pg_tmp = (double *)(JT.host[b].hdr_out + MH_N);
         if (!j.pg_n) continue;
@@ -3398,20 +3484,226 @@ extern "C" ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *c, int B, ov2_map
         m->last_valid = 0;   // its tables change under the last set-up: no update stage from it any more
     }
     if ((s = JT.upload()) != OV2_OK) return s;
-    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), gL((lmax + 255) / 256, B), gK((kmax + 255) / 256, B), b256(256);
-    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::min(64u, (zmax + 255) / 256), B), b256, 0, st, JT.dev);
-    OV2_LAUNCH(c, OV2_K_MAP, mp_anchor_kernel, gN, b256, 0, st, JT.dev);
-    OV2_LAUNCH(c, OV2_K_MAP, mp_landmarks_kernel, gL, b256, 0, st, JT.dev);
-    OV2_LAUNCH(c, OV2_K_MAP, mp_poses_kernel, gK, b256, 0, st, JT.dev);
+    pg_update_launches(c, JT, nmax, lmax, kmax, zmax);
     if (!out) return OV2_OK;   // fully asynchronous
     OV2_LAUNCH(c, OV2_K_MAP, mb_hdr_gather_kernel, dim3(1, B), dim3(64), 0, st, JT.dev);
     if ((s = JT.fetch_headers()) != OV2_OK) return s;
+    for (int b = 0; b < B; ++b)
+        if (chain_off[b + 1] != chain_off[b]) pg_update_record(out[b], JT.hdr_host + (size_t)b * JT.stride);
+    return OV2_OK;
+}
+
+// what the host knows of map b's chain without asking the device (Optimizer::assembleLocalPoseGraph :2368-2425 on the host
+// copy of the keyframe states): ids = the loop keyframe after the walk-up, then the live keyframes up to newkf; empty = no chain
+void lpg_chain(const ov2_map *m, int newkf, int kfloop_id, std::vector<int32_t> &ids)
+{
+    ids.clear();
+    auto alive = [&](int k) { return k >= 0 && k < m->max_kf && m->kf_alive_h[k]; };
+    if (!alive(newkf)) return;                              // a dead new keyframe
+    int loop = std::max(kfloop_id, 0);                      // the walk-up stops at the first live keyframe (:2368-2371) ...
+    while (loop < newkf && !alive(loop)) ++loop;
+    if (loop >= newkf) return;                              // ... and one at or past newkf leaves fewer than two poses
+    ids.push_back(loop);
+    for (int k = loop + 1; k <= newkf; ++k)
+        if (alive(k)) ids.push_back(k);
+}
+
+// [ids of every chain | newTwc of every map] behind the gathered headers; per map 28 ints of pg_tmp and the verdict (+ pad)
+enum { LPG_EXTRA_INTS = 30, LPG_VERDICT = MH_N + 28 };
+
+struct lpg_plan {
+    std::vector<std::vector<int32_t>> ids;   // per map, empty = NO_CHAIN
+    std::vector<size_t> off;                 // first pose of map b in the flat block (B + 1)
+    int n_active = 0;
+    size_t total() const { return off.back(); }
+};
+
+ov2_status lpg_validate(ov2_ctx *c, const char *who, int B, ov2_map *const *maps, const int32_t *newkf, const int32_t *kfloop_id,
+                        const double *newTwc, lpg_plan &pl)
+{
+    if (B < 0 || !maps || !newkf || !kfloop_id || !newTwc) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null argument or B < 0", who);
+    ov2_status s;
+    pl.ids.resize((size_t)B);
+    pl.off.assign((size_t)B + 1, 0);
     for (int b = 0; b < B; ++b) {
-        if (chain_off[b + 1] == chain_off[b]) continue;
-        const int *H = JT.hdr_host + (size_t)b * JT.stride;
-        out[b].n_kf_chain = H[PH_KF_CHAIN]; out[b].n_kf_younger = H[PH_KF_YOUNGER]; out[b].n_lm_moved = H[PH_LM_MOVED];
-        memcpy(out[b].T_corr, (const double *)(H + MH_N) + 7, 7 * sizeof(double));
+        if ((s = batch_map_ok(c, maps[b], b)) != OV2_OK) return s;
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
+        lpg_chain(maps[b], newkf[b], kfloop_id[b], pl.ids[b]);
+        pl.off[b + 1] = pl.off[b] + pl.ids[b].size();
+        pl.n_active += pl.ids[b].empty() ? 0 : 1;
     }
+    return OV2_OK;
+}
+
+// the job table of the statement, its problem block in the ctx's own device block, and the assembly launch.
+// Layout of the block: poses (7 x total) | T_ij (7 x total) | result records (one per map) | skip bytes (one per map)
+struct lpg_block { double *pose, *Tij; ov2_pg_result *res; unsigned char *skip; };
+
+ov2_status lpg_assemble(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf, const double *newTwc, int stereo,
+                        int32_t *d_n_pairs, const lpg_plan &pl, size_t host_tail, job_table &JT, lpg_block &K)
+{
+    ov2_status s;
+    const size_t total = pl.total();
+    const size_t o_T = (total * 7 * sizeof(double) + 255) & ~(size_t)255, o_res = 2 * o_T;
+    const size_t o_skip = o_res + (((size_t)B * sizeof(ov2_pg_result) + 255) & ~(size_t)255);
+    if ((s = ov2_dev_block(c, &c->lpg_dev, &c->lpg_dev_cap, o_skip + (size_t)B)) != OV2_OK) return s;
+    unsigned char *blk = (unsigned char *)c->lpg_dev;
+    K.pose = (double *)blk; K.Tij = (double *)(blk + o_T); K.res = (ov2_pg_result *)(blk + o_res); K.skip = blk + o_skip;
+    const size_t ids_bytes = (total * sizeof(int32_t) + 15) & ~(size_t)15, up_bytes = ids_bytes + (size_t)B * 7 * sizeof(double);
+    if ((s = JT.begin(c, B, LPG_EXTRA_INTS, up_bytes + host_tail)) != OV2_OK) return s;
+    JT.tail_bytes = up_bytes;   // what goes up; the rest of the tail is the pinned landing area of the call's downloads
+    memcpy(JT.tail_host + ids_bytes, newTwc, (size_t)B * 7 * sizeof(double));
+    int nmax = 0;
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = maps[b];
+        const std::vector<int32_t> &ids = pl.ids[b];
+        const int n = (int)ids.size();
+        map_job j = job_of(m, newkf[b], -1);
+        stage_block(j, m->tt_zero, n ? m->tt_zero_bytes : 0);
+        j.tt_old = m->tt_old;
+        j.lp_n = n; j.lp_stereo = stereo;
+        j.lp_kfid = (const int *)JT.tail_dev + pl.off[b];
+        j.lp_newTwc = (const double *)(JT.tail_dev + ids_bytes) + 7 * (size_t)b;
+        j.lp_pose = K.pose + 7 * pl.off[b]; j.lp_Tij = K.Tij + 7 * pl.off[b];
+        j.lp_skip = K.skip + b;
+        j.lp_npairs = d_n_pairs ? d_n_pairs + b : nullptr;
+        // the update stage reads the same block past the constant loop keyframe
+        j.pg_n = n ? n - 1 : 0; j.pg_kfid = j.lp_kfid + 1; j.pg_Twc = j.lp_pose + 7; j.pg_skip = j.lp_skip;
+        JT.set(b, j);
+        JT.host[b].pg_tmp = (double *)(JT.host[b].hdr_out + MH_N);
+        JT.host[b].lp_verdict = JT.host[b].hdr_out + LPG_VERDICT;
+        if (n) memcpy((int32_t *)JT.tail_host + pl.off[b], ids.data(), (size_t)n * sizeof(int32_t));
+        nmax = std::max(nmax, n);
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    OV2_LAUNCH(c, OV2_K_MAP, mp_assemble_kernel, dim3((std::max(nmax, 1) + 255) / 256, B), dim3(256), 0, c->stream, JT.dev);
+    OV2_HIP(c, hipGetLastError());
+    return OV2_OK;
+}
+
+}  // namespace
+
+extern "C" ov2_status ov2_map_pose_graph_update_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf,
+                                                      const int32_t *chain_off, const int32_t *chain_kfid, const double *chain_Twc,
+                                                      ov2_map_pg_update *out)
+{
+    return pg_update_impl(c, "ov2_map_pose_graph_update_batch", false, B, maps, newkf, chain_off, chain_kfid, chain_Twc, nullptr, out);
+}
+
+extern "C" ov2_status ov2_map_pose_graph_update_batch_dev(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf,
+                                                          const int32_t *chain_off, const int32_t *chain_kfid, const double *d_chain_Twc,
+                                                          const uint8_t *d_skip, ov2_map_pg_update *out)
+{
+    return pg_update_impl(c, "ov2_map_pose_graph_update_batch_dev", true, B, maps, newkf, chain_off, chain_kfid, d_chain_Twc, d_skip, out);
+}
+
+extern "C" ov2_status ov2_map_local_pose_graph_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf,
+                                                     const int32_t *kfloop_id, const double *newTwc, int stereo, const ov2_ba_options *o,
+                                                     int32_t *d_n_pairs, ov2_map_local_pg *out)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    const char *who = "ov2_map_local_pose_graph_batch";
+    ov2_status s;
+    lpg_plan pl;
+    if ((s = lpg_validate(c, who, B, maps, newkf, kfloop_id, newTwc, pl)) != OV2_OK) return s;
+    if (B > OV2_PG_MAX_BATCH) return ov2_set_err(c, OV2_ERR_INVALID, "%s: B %d above %d", who, B, OV2_PG_MAX_BATCH);
+    ov2_ba_options od;
+    if (!o) {   // Optimizer::localPoseGraphOptions (:2442-2446)
+        ov2_ba_default_options(&od, 5.9915f);
+        od.max_iters = 10; od.function_tolerance = 1e-4;
+        o = &od;
+    }
+    if (o->max_iters < 0 || o->max_iters > OV2_BA_MAX_LOG - 1)
+        return ov2_set_err(c, OV2_ERR_INVALID, "%s: max_iters %d outside [0, %d]", who, o->max_iters, OV2_BA_MAX_LOG - 1);
+    if (out) {
+        memset(out, 0, (size_t)B * sizeof(*out));
+        for (int b = 0; b < B; ++b) {
+            out[b].verdict = OV2_LPG_NO_CHAIN; out[b].kfloop_id = -1;
+            out[b].result.termination = OV2_BA_TERM_SKIPPED;
+        }
+    }
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (!pl.n_active) {   // no work on the device beyond the refused counts
+        if (d_n_pairs) OV2_HIP(c, hipMemsetAsync(d_n_pairs, 0, (size_t)B * sizeof(int32_t), st));
+        return OV2_OK;
+    }
+    job_table JT;
+    lpg_block K;
+    if ((s = lpg_assemble(c, B, maps, newkf, newTwc, stereo ? 1 : 0, d_n_pairs, pl, out ? (size_t)B * sizeof(ov2_pg_result) : 0, JT, K)) != OV2_OK)
+        return s;
+    // the solve: one graph per map that has a chain, in batch order; structure from the host, values where the assembly left them
+    std::vector<ov2_pg_problem> P;
+    std::vector<int> act;
+    const size_t total = pl.total();
+    std::vector<int32_t> ei(total), ej(total);
+    std::vector<uint8_t> cst(total, 0);
+    int nmax = 0, lmax = 0, kmax = 0; unsigned zmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int n = (int)pl.ids[b].size();
+        if (!n) continue;
+        const size_t o0 = pl.off[b];
+        for (int i = 0; i + 1 < n; ++i) { ei[o0 + i] = i; ej[o0 + i] = i + 1; }
+        ei[o0 + n - 1] = 0; ej[o0 + n - 1] = n - 1;
+        cst[o0] = 1;
+        ov2_pg_problem G;
+        G.n_pose = n; G.pose = K.pose + 7 * o0; G.pose_const = cst.data() + o0;
+        G.n_edge = n; G.edge_i = ei.data() + o0; G.edge_j = ej.data() + o0; G.T_ij = K.Tij + 7 * o0;
+        P.push_back(G); act.push_back(b);
+        ov2_map *m = maps[b];
+        nmax = std::max(nmax, m->n_obs); lmax = std::max(lmax, m->max_lm); kmax = std::max(kmax, m->max_kf);
+        zmax = std::max(zmax, JT.host[b].zero_vec16);
+        m->last_valid = 0;   // its tables change under the last set-up: no update stage from it any more
+    }
+    if ((s = ov2_pg_solve_dev(c, who, (int)P.size(), P.data(), o, K.res)) != OV2_OK) return s;
+    OV2_LAUNCH(c, OV2_K_MAP, mp_gate_kernel, dim3((B + 63) / 64), dim3(64), 0, st, JT.dev, B);
+    pg_update_launches(c, JT, nmax, lmax, kmax, zmax);
+    OV2_HIP(c, hipGetLastError());
+    if (!out) return OV2_OK;   // fully asynchronous
+    OV2_LAUNCH(c, OV2_K_MAP, mb_hdr_gather_kernel, dim3(1, B), dim3(64), 0, st, JT.dev);
+    unsigned char *res_host = JT.tail_host + ((JT.tail_bytes + 255) & ~(size_t)255);
+    OV2_HIP(c, hipMemcpyAsync(res_host, K.res, P.size() * sizeof(ov2_pg_result), hipMemcpyDeviceToHost, st));
+    if ((s = JT.fetch_headers()) != OV2_OK) return s;
+    for (size_t a = 0; a < act.size(); ++a) {
+        const int b = act[a];
+        const int *H = JT.hdr_host + (size_t)b * JT.stride;
+        ov2_map_local_pg &r = out[b];
+        r.verdict = H[LPG_VERDICT]; r.kfloop_id = pl.ids[b][0]; r.n_pose = (int)pl.ids[b].size();
+        if (r.verdict == OV2_LPG_DONE) pg_update_record(r.update, H);
+        memcpy(&r.result, res_host + a * sizeof(ov2_pg_result), sizeof(ov2_pg_result));
+    }
+    return OV2_OK;
+}
+
+// test hook: the assembly stage of ov2_map_local_pose_graph_batch alone, downloaded.  chain_off (B + 1) receives where map
+// b's poses and edges start, kfid / pose / T_ij (cap poses) the chains; a map without a chain lists nothing.
+extern "C" ov2_status ov2_map_local_pose_graph_assemble(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf,
+                                                        const int32_t *kfloop_id, const double *newTwc, int cap, int32_t *chain_off,
+                                                        int32_t *kfid, double *pose, double *T_ij)
+{
+    if (!c) return OV2_ERR_INVALID;
+    const char *who = "ov2_map_local_pose_graph_assemble";
+    if (B <= 0 || !chain_off || !kfid || !pose || !T_ij) return ov2_set_err(c, OV2_ERR_INVALID, "%s: null argument or B <= 0", who);
+    ov2_status s;
+    lpg_plan pl;
+    if ((s = lpg_validate(c, who, B, maps, newkf, kfloop_id, newTwc, pl)) != OV2_OK) return s;
+    const size_t total = pl.total();
+    if (total > (size_t)std::max(cap, 0)) return ov2_set_err(c, OV2_ERR_INVALID, "%s: %zu poses, room for %d", who, total, cap);
+    for (int b = 0; b <= B; ++b) chain_off[b] = (int32_t)pl.off[b];
+    for (int b = 0; b < B; ++b) std::copy(pl.ids[b].begin(), pl.ids[b].end(), kfid + pl.off[b]);
+    if (!total) return OV2_OK;
+    OV2_HIP(c, hipSetDevice(c->device));
+    job_table JT;
+    lpg_block K;
+    if ((s = lpg_assemble(c, B, maps, newkf, newTwc, 0, nullptr, pl, 2 * total * 7 * sizeof(double), JT, K)) != OV2_OK) return s;
+    hipStream_t st = c->stream;
+    unsigned char *land = JT.tail_host + ((JT.tail_bytes + 255) & ~(size_t)255);
+    OV2_HIP(c, hipMemcpyAsync(land, K.pose, total * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+    OV2_HIP(c, hipMemcpyAsync(land + total * 7 * sizeof(double), K.Tij, total * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+    OV2_HIP(c, hipStreamSynchronize(st));
+    memcpy(pose, land, total * 7 * sizeof(double));
+    memcpy(T_ij, land + total * 7 * sizeof(double), total * 7 * sizeof(double));
     return OV2_OK;
 }
 

@@ -211,6 +211,16 @@ struct ov2_ctx {
     size_t stage_cap;
     hipEvent_t stage_ev;                 // recorded behind an asynchronous upload out of the pinned staging block;
     bool stage_ev_pending;               //   ov2_staging waits for it before handing the block out again
+    // ov2_pose_graph_solve_batch_dev: descriptors, structure arrays and workspaces of the queued solve in a device block of
+    // its own (the staging block may be handed out again while the minimiser is still queued), uploaded from a pinned
+    // area that is rewritten only after pg_ev, recorded behind the upload, has passed
+    void *pg_dev, *pg_pin;
+    size_t pg_dev_cap, pg_pin_cap;
+    hipEvent_t pg_ev;
+    bool pg_ev_pending;
+    // ov2_map_local_pose_graph_batch: the assembled problems (poses | T_ij), result records and skip bytes of the last call
+    void *lpg_dev;
+    size_t lpg_dev_cap;
     void *ba_arena2;                     // second device block: cell / pair structure of the Schur complement (sized after the build learns the counts)
     size_t ba_arena2_cap;
     void *ba_host;                       // pinned host mirror of the uploaded head of the arena (same offsets)
@@ -273,6 +283,14 @@ ov2_status ov2_kf_scratch(ov2_ctx *ctx, size_t bytes, void **out);
 hipStream_t ov2_kf_stream_for(ov2_ctx *ctx, bool known, const ov2_byte_range *rd, int nrd, const ov2_byte_range *wr, int nwr);
 // pinned host block of `bytes` and a device block of the same size (grown on demand, kept by the ctx)
 ov2_status ov2_staging(ov2_ctx *ctx, size_t bytes, void **host, void **dev);
+// a device block the ctx keeps for one purpose (*blk / *cap are its fields), grown on demand behind a synchronisation of
+// the main stream; calls that follow each other on that stream may reuse it without one
+ov2_status ov2_dev_block(ov2_ctx *ctx, void **blk, size_t *cap, size_t bytes);
+// the pinned area the device-pointer pose-graph solve uploads from: handed out once the previous upload out of it has
+// passed (the caller records ctx->pg_ev behind its copy and sets pg_ev_pending)
+ov2_status ov2_pg_pinned(ov2_ctx *ctx, size_t bytes, void **host);
+// posegraph.hip: the batch solve on device-resident poses / T_ij / result records, enqueued on the main stream
+ov2_status ov2_pg_solve_dev(ov2_ctx *ctx, const char *who, int B, const ov2_pg_problem *p, const ov2_ba_options *o, ov2_pg_result *d_r);
 // ov2_ctx_destroy: free the device side of a map that outlives its ctx (the handle stays valid for ov2_map_destroy)
 void ov2_map_orphan(struct ov2_map *m);
 // the same for a word table of the loop detector (lcd.hip)

@@ -432,6 +432,10 @@ __global__ __launch_bounds__(256) void pg_minimize_kernel(const pg_dev *__restri
     __shared__ int flag;
     const pg_dev d = dv[blockIdx.x];
     ov2_pg_result *R = d.res;
+    if (d.nf == 0) {   // a skipped graph of the device-pointer form (the host form gives it no workgroup): it marks its record
+        if (threadIdx.x == 0) R->termination = OV2_BA_TERM_SKIPPED;
+        return;
+    }
     if (threadIdx.x == 0) { R->n_log = 0; R->termination = OV2_BA_TERM_MAX_ITER; }
     const int m = 6 * d.nf;
     for (int k = threadIdx.x; k < m; k += 256) d.scale[k] = 1.0;
@@ -592,6 +596,16 @@ ov2_status pg_plan_build(ov2_ctx *c, const char *who, const ov2_pg_problem *P, p
     return OV2_OK;
 }
 
+pg_opt pg_options(const ov2_ba_options *o)
+{
+    pg_opt po;
+    po.max_iters = o->max_iters; po.jacobi = o->jacobi_scaling; po.max_invalid = o->max_consecutive_invalid_steps;
+    po.ftol = o->function_tolerance; po.initial_radius = o->initial_radius; po.max_radius = o->max_radius; po.min_radius = o->min_radius;
+    po.min_d = o->min_lm_diagonal; po.max_d = o->max_lm_diagonal; po.min_rel = o->min_relative_decrease;
+    po.ptol = o->parameter_tolerance; po.gtol = o->gradient_tolerance;
+    return po;
+}
+
 // B graphs, one launch: `who` as above (nullptr: the batch form, which names the graph itself)
 ov2_status pg_solve_graphs(ov2_ctx *c, const char *who, int B, const ov2_pg_problem *P, const ov2_ba_options *o, ov2_pg_result *R)
 {
@@ -669,12 +683,7 @@ ov2_status pg_solve_graphs(ov2_ctx *c, const char *who, int B, const ov2_pg_prob
     memset(hp + in_end, 0, io_end - in_end);
     hipStream_t st = c->stream;
     OV2_HIP(c, hipMemcpyAsync(dp, hp, io_end, hipMemcpyHostToDevice, st));
-    pg_opt po;
-    po.max_iters = o->max_iters; po.jacobi = o->jacobi_scaling; po.max_invalid = o->max_consecutive_invalid_steps;
-    po.ftol = o->function_tolerance; po.initial_radius = o->initial_radius; po.max_radius = o->max_radius; po.min_radius = o->min_radius;
-    po.min_d = o->min_lm_diagonal; po.max_d = o->max_lm_diagonal; po.min_rel = o->min_relative_decrease;
-    po.ptol = o->parameter_tolerance; po.gtol = o->gradient_tolerance;
-    OV2_LAUNCH(c, OV2_K_MAP + 6, pg_minimize_kernel, dim3(na), dim3(256), 0, st, (const pg_dev *)(dp + o_dev), po);
+    OV2_LAUNCH(c, OV2_K_MAP + 6, pg_minimize_kernel, dim3(na), dim3(256), 0, st, (const pg_dev *)(dp + o_dev), pg_options(o));
     OV2_HIP(c, hipGetLastError());
     OV2_HIP(c, hipMemcpyAsync(hp + x_begin, dp + x_begin, io_end - x_begin, hipMemcpyDeviceToHost, st));
     OV2_HIP(c, hipStreamSynchronize(st));
@@ -686,6 +695,97 @@ ov2_status pg_solve_graphs(ov2_ctx *c, const char *who, int B, const ov2_pg_prob
 }
 
 }  // namespace
+
+// B graphs whose poses, T_ij and result records live on the device: the structure arrays come from the host, so the plans are
+// those of the host form; descriptors and structure go up with ONE copy out of the solver's pinned area into the solver's own
+// device block, which also holds the workspaces.  Every graph takes a workgroup (a skipped one only marks its record), one
+// launch, no download, no synchronisation.
+ov2_status ov2_pg_solve_dev(ov2_ctx *c, const char *who, int B, const ov2_pg_problem *P, const ov2_ba_options *o, ov2_pg_result *d_R)
+{
+    std::vector<pg_plan> plans((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        char name[64];
+        snprintf(name, sizeof(name), "%s: graph %d: ", who, b);
+        const ov2_status s = pg_plan_build(c, name, P + b, plans[b]);
+        if (s != OV2_OK) return s;
+    }
+    OV2_HIP(c, hipSetDevice(c->device));
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o_ = off; off += up(bytes); return o_; };
+    auto active = [&](int b) { return plans[b].nf != 0 && plans[b].E != 0; };
+    const size_t o_dev = carve(sizeof(pg_dev) * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        if (!active(b)) continue;
+        pg_plan &q = plans[b];
+        const size_t E = (size_t)q.E, n = (size_t)q.n, nf = (size_t)q.nf, ns = (size_t)q.n_seg;
+        q.o_ei = carve(sizeof(int) * E); q.o_ej = carve(sizeof(int) * E); q.o_fi = carve(sizeof(int) * n); q.o_pf = carve(sizeof(int) * nf);
+        q.o_ip = carve(sizeof(int) * (nf + 1)); q.o_in = carve(sizeof(int) * (q.inc_flat.size() + 1));
+        q.o_s0 = carve(sizeof(int) * ns); q.o_s1 = carve(sizeof(int) * ns);
+    }
+    const size_t head_end = off;      // what the pinned area mirrors
+    for (int b = 0; b < B; ++b) {
+        if (!active(b)) continue;
+        pg_plan &q = plans[b];
+        const size_t E = (size_t)q.E, n = (size_t)q.n, nf = (size_t)q.nf;
+        q.o_cand = carve(sizeof(double) * 7 * n); q.o_best = carve(sizeof(double) * 7 * n);
+        q.o_r = carve(sizeof(double) * 6 * E); q.o_Ji = carve(sizeof(double) * 36 * E); q.o_Jj = carve(sizeof(double) * 36 * E);
+        q.o_D = carve(sizeof(double) * 36 * nf); q.o_O = carve(sizeof(double) * 36 * nf); q.o_Ld = carve(sizeof(double) * 36 * nf);
+        q.o_Lo = carve(sizeof(double) * 36 * nf); q.o_v = carve(sizeof(double) * 6 * nf * 8); q.o_part = carve(sizeof(double) * 256);
+    }
+    ov2_status s;
+    if ((s = ov2_dev_block(c, &c->pg_dev, &c->pg_dev_cap, off)) != OV2_OK) return s;
+    char *hp = nullptr, *dp = (char *)c->pg_dev;
+    if ((s = ov2_pg_pinned(c, head_end, (void **)&hp)) != OV2_OK) return s;
+    pg_dev *hd = (pg_dev *)(hp + o_dev);
+    for (int b = 0; b < B; ++b) {
+        pg_dev d;
+        memset(&d, 0, sizeof(d));
+        d.res = d_R + b;
+        if (active(b)) {
+            const ov2_pg_problem *G = P + b;
+            const pg_plan &q = plans[b];
+            const int E = q.E, n = q.n, nf = q.nf, n_seg = q.n_seg;
+            memcpy(hp + q.o_ei, G->edge_i, sizeof(int) * E); memcpy(hp + q.o_ej, G->edge_j, sizeof(int) * E);
+            memcpy(hp + q.o_fi, q.fidx.data(), sizeof(int) * n); memcpy(hp + q.o_pf, q.pose_of_f.data(), sizeof(int) * nf);
+            memcpy(hp + q.o_ip, q.inc_ptr.data(), sizeof(int) * (nf + 1));
+            if (!q.inc_flat.empty()) memcpy(hp + q.o_in, q.inc_flat.data(), sizeof(int) * q.inc_flat.size());
+            memcpy(hp + q.o_s0, q.seg0.data(), sizeof(int) * n_seg); memcpy(hp + q.o_s1, q.seg1.data(), sizeof(int) * n_seg);
+            d.n_pose = n; d.n_edge = E; d.nf = nf; d.n_seg = n_seg;
+            d.edge_i = (const int *)(dp + q.o_ei); d.edge_j = (const int *)(dp + q.o_ej); d.fidx = (const int *)(dp + q.o_fi);
+            d.pose_of_f = (const int *)(dp + q.o_pf); d.inc_ptr = (const int *)(dp + q.o_ip); d.inc = (const int *)(dp + q.o_in);
+            d.seg0 = (const int *)(dp + q.o_s0); d.seg1 = (const int *)(dp + q.o_s1);
+            d.T_ij = G->T_ij; d.x = G->pose;                                   // the caller's device arrays, solved in place
+            d.cand = (double *)(dp + q.o_cand); d.best = (double *)(dp + q.o_best);
+            d.r = (double *)(dp + q.o_r); d.Ji = (double *)(dp + q.o_Ji); d.Jj = (double *)(dp + q.o_Jj);
+            d.D = (double *)(dp + q.o_D); d.O = (double *)(dp + q.o_O); d.Ld = (double *)(dp + q.o_Ld); d.Lo = (double *)(dp + q.o_Lo);
+            double *v = (double *)(dp + q.o_v);
+            const size_t m = 6 * (size_t)nf;
+            d.g = v; d.sqn = v + m; d.scale = v + 2 * m; d.diag = v + 3 * m; d.lmd = v + 4 * m; d.step = v + 5 * m; d.y = v + 6 * m;
+            d.part = (double *)(dp + q.o_part);
+        }
+        hd[b] = d;
+    }
+    hipStream_t st = c->stream;
+    // the records start zeroed, as the host form uploads them: the log entries behind n_log read as zeros
+    OV2_HIP(c, hipMemsetAsync(d_R, 0, sizeof(ov2_pg_result) * (size_t)B, st));
+    OV2_HIP(c, hipMemcpyAsync(dp, hp, head_end, hipMemcpyHostToDevice, st));
+    OV2_HIP(c, hipEventRecord(c->pg_ev, st));
+    c->pg_ev_pending = true;
+    OV2_LAUNCH(c, OV2_K_MAP + 6, pg_minimize_kernel, dim3(B), dim3(256), 0, st, (const pg_dev *)(dp + o_dev), pg_options(o));
+    OV2_HIP(c, hipGetLastError());
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_pose_graph_solve_batch_dev(ov2_ctx *c, int B, const ov2_pg_problem *P, const ov2_ba_options *o, ov2_pg_result *d_R)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B < 0 || B > OV2_PG_MAX_BATCH)
+        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_pose_graph_solve_batch_dev: B %d outside [0, %d]", B, OV2_PG_MAX_BATCH);
+    if (B == 0) return OV2_OK;
+    if (!P || !o || !d_R) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_pose_graph_solve_batch_dev: null argument");
+    return ov2_pg_solve_dev(c, "ov2_pose_graph_solve_batch_dev", B, P, o, d_R);
+}
 
 extern "C" ov2_status ov2_pose_graph_solve(ov2_ctx *c, const ov2_pg_problem *P, const ov2_ba_options *o, ov2_pg_result *R)
 {

@@ -290,6 +290,11 @@ class DeviceMap:
         """ov2_map_pose_graph_update_batch on this map and `others` in one call; see pose_graph_update_batch"""
         return pose_graph_update_batch(self.ctx, [self] + list(others), newkf, chain_kfid, chain_Twc, want_header)
 
+    def local_pose_graph_batch(self, others=(), newkf=None, kfloop_id=(), newTwc=(), stereo=True, options=None, d_n_pairs=None,
+                               want=True):
+        """ov2_map_local_pose_graph_batch on this map and `others` in one call; see local_pose_graph_batch"""
+        return local_pose_graph_batch(self.ctx, [self] + list(others), newkf, kfloop_id, newTwc, stereo, options, d_n_pairs, want)
+
     def merge_points_batch(self, others=(), pairs=(), cur_obs=None, want_header=True):
         """ov2_map_merge_points_batch on this map and `others` in one call; see merge_points_batch"""
         return merge_points_batch(self.ctx, [self] + list(others), pairs, cur_obs, want_header)
@@ -466,6 +471,81 @@ def pose_graph_update_batch(ctx, maps, newkf=None, chain_kfid=(), chain_Twc=(), 
         return None
     return [dict(n_kf_chain=u.n_kf_chain, n_kf_younger=u.n_kf_younger, n_lm_moved=u.n_lm_moved, T_corr=np.array(u.T_corr[:]))
             for u in out]
+
+
+def pose_graph_update_batch_dev(ctx, maps, newkf, chain_kfid, d_chain_Twc, d_skip=None, want_header=True):
+    """ov2_map_pose_graph_update_batch_dev: pose_graph_update_batch with the optimised poses in device memory.  chain_kfid[b]
+    lists the free keyframes of map b (host); d_chain_Twc is ONE device array (DeviceArray, torch tensor or address) holding
+    their poses map after map, d_skip (device, one byte per map, or None) the maps to leave alone.  Returns the headers as
+    pose_graph_update_batch does -- or None (want_header=False: fully asynchronous)"""
+    from .pose_graph import _addr
+    B = len(maps)
+    hs = (C.c_void_p * max(B, 1))(*[getattr(m, "h", m) for m in maps])
+    nk = np.ascontiguousarray([m.newkf for m in maps] if newkf is None else newkf, np.int32)
+    ids = [np.ascontiguousarray(k, np.int32).reshape(-1) for k in chain_kfid]
+    assert len(ids) == B
+    off = np.concatenate([[0], np.cumsum([len(k) for k in ids])]).astype(np.int32)
+    kid = np.ascontiguousarray(np.concatenate(ids + [np.zeros(0, np.int32)]), np.int32)
+    out = (PgUpdateC * max(B, 1))() if want_header else None
+    _check(ctx.h, ctx.lib.ov2_map_pose_graph_update_batch_dev(ctx.h, B, hs, nk.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p),
+                                                              kid.ctypes.data_as(C.c_void_p), C.c_void_p(_addr(d_chain_Twc)),
+                                                              C.c_void_p(_addr(d_skip)), out))
+    if not want_header:
+        return None
+    return [dict(n_kf_chain=u.n_kf_chain, n_kf_younger=u.n_kf_younger, n_lm_moved=u.n_lm_moved, T_corr=np.array(u.T_corr[:]))
+            for u in out[:B]]
+
+
+LPG_DONE, LPG_DEGENERATE, LPG_NO_CHAIN = 0, 1, 2   # OV2_LPG_* (include/ov2slam_hip.h)
+
+
+class LocalPgC(C.Structure):
+    """ov2_map_local_pg"""
+    _fields_ = [("verdict", C.c_int32), ("kfloop_id", C.c_int32), ("n_pose", C.c_int32), ("reserved", C.c_int32),
+                ("update", PgUpdateC), ("result", T.PgResultC)]
+
+
+def _lpg_args(maps, newkf, kfloop_id, newTwc):
+    B = len(maps)
+    hs = (C.c_void_p * max(B, 1))(*[getattr(m, "h", m) for m in maps])
+    nk = np.ascontiguousarray([m.newkf for m in maps] if newkf is None else newkf, np.int32).reshape(-1)
+    lo = np.ascontiguousarray(kfloop_id, np.int32).reshape(-1)
+    Tw = None if newTwc is None else np.ascontiguousarray(newTwc, np.float64).reshape(-1, 7)
+    assert len(nk) == B and len(lo) == B and (Tw is None or len(Tw) == B)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    return B, hs, (nk, lo, Tw), [p(nk), p(lo), p(Tw)]
+
+
+def local_pose_graph_batch(ctx, maps, newkf, kfloop_id, newTwc, stereo=True, options=None, d_n_pairs=None, want=True):
+    """Optimizer::localPoseGraph(keyframe newkf[b], kfloop_id[b], newTwc[b]) on the tables of the maps (DeviceMap objects or raw
+    ov2_map handles) in one call (ov2_map_local_pose_graph_batch): assembly, solve, degenerate gate and update on the device.
+    options: a BaOptionsC (None: localPoseGraph's); d_n_pairs: device int32 (B,) whose entries the refused maps clear (DeviceArray,
+    torch tensor, address or None).  Returns per map dict(verdict, kfloop_id, n_pose, n_kf_chain, n_kf_younger, n_lm_moved,
+    T_corr, result: the PgResultC of the solve, raw: the bytes of the record) -- or None (want=False: nothing synchronises)"""
+    from .pose_graph import _addr
+    B, hs, keep, args = _lpg_args(maps, newkf, kfloop_id, newTwc)
+    out = (LocalPgC * max(B, 1))() if want else None
+    _check(ctx.h, ctx.lib.ov2_map_local_pose_graph_batch(ctx.h, B, hs, *args, int(bool(stereo)),
+                                                         None if options is None else C.addressof(options),
+                                                         C.c_void_p(_addr(d_n_pairs)), out))
+    if not want:
+        return None
+    return [dict(verdict=u.verdict, kfloop_id=u.kfloop_id, n_pose=u.n_pose, n_kf_chain=u.update.n_kf_chain,
+                 n_kf_younger=u.update.n_kf_younger, n_lm_moved=u.update.n_lm_moved, T_corr=np.array(u.update.T_corr[:]),
+                 result=T.PgResultC.from_buffer_copy(u.result), raw=bytes(u)) for u in out[:B]]
+
+
+def local_pose_graph_assemble(ctx, maps, newkf, kfloop_id, newTwc):
+    """the assembly launch of local_pose_graph_batch alone, downloaded (ov2_map_local_pose_graph_assemble; for tests): per map
+    None (no chain) or dict(kfids, pose (n x 7), T_ij (n x 7): the n - 1 odometry edges, then the closing edge)"""
+    B, hs, (nk, _, _), args = _lpg_args(maps, newkf, kfloop_id, newTwc)
+    cap = int(np.maximum(nk, 0).sum()) + B + 1
+    off, kid = np.zeros(B + 1, np.int32), np.zeros(cap, np.int32)
+    pose, Tij = np.zeros((cap, 7)), np.zeros((cap, 7))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(ctx.h, ctx.lib.ov2_map_local_pose_graph_assemble(ctx.h, B, hs, *args, cap, p(off), p(kid), p(pose), p(Tij)))
+    return [None if off[b] == off[b + 1] else dict(kfids=kid[off[b]:off[b + 1]].copy(), pose=pose[off[b]:off[b + 1]].copy(),
+                                                   T_ij=Tij[off[b]:off[b + 1]].copy()) for b in range(B)]
 
 
 def merge_points_batch(ctx, maps, pairs, cur_obs=None, want_header=True, dev=False):

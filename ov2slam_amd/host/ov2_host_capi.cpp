@@ -1130,6 +1130,31 @@ int ov2h_local_pose_graph(void *p, void *ctx, int newkf, int kfloop_id, const do
     return s != OV2_OK ? -2 : (ok ? 1 : 0);
 }
 
+// Optimizer::assembleLocalPoseGraph alone: the graph localPoseGraph(newframe = keyframe newkf, kfloop_id, newTwc) would solve.
+// Needs no GPU context.  kfids / cst (cap), pose (cap x 7): the chain, loop keyframe first; ei / ej (cap), Tij (cap x 7): its
+// n edges, the closing edge last.  returns n = poses = edges (>= 2), 0 no chain (a dead newkf included), -2 cap too small
+int ov2h_assemble_local_pose_graph(void *p, int newkf, int kfloop_id, const double *newTwc7, int cap, int *kfids, double *pose,
+                                   uint8_t *cst, int *ei, int *ej, double *Tij)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(newkf);
+    if (!f) return 0;
+    SE3 T;
+    for (int k = 0; k < 7; ++k) T.v[k] = newTwc7[k];
+    Optimizer opt(nullptr, m->st, m->map);
+    LocalPoseGraph g;
+    if (!opt.assembleLocalPoseGraph(*f, kfloop_id, T, g)) return 0;
+    const int n = (int)g.kfids.size();
+    if (n > cap || (int)g.ei.size() > cap) return -2;
+    std::copy(g.kfids.begin(), g.kfids.end(), kfids);
+    std::copy(g.pose.begin(), g.pose.end(), pose);
+    std::copy(g.cst.begin(), g.cst.end(), cst);
+    std::copy(g.ei.begin(), g.ei.end(), ei);
+    std::copy(g.ej.begin(), g.ej.end(), ej);
+    std::copy(g.Tij.begin(), g.Tij.end(), Tij);
+    return n;
+}
+
 // Optimizer::applyLocalPoseGraph alone (test hook): the n free keyframes kfids (ascending, last = newkf) take the poses
 // Twc7 as if a solve had produced them; the loop pose is taken equal to the new keyframe's pose, so the degenerate test
 // passes.  returns 1 applied, 0 rejected, -1 a keyframe is missing

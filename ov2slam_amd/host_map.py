@@ -38,6 +38,7 @@ def lib():
         L.ov2h_full_ba.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, C.POINTER(C.c_double), ip]
         L.ov2h_local_pose_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, dp, C.POINTER(C.c_double), ip]
         L.ov2h_apply_local_pose_graph.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp]
+        L.ov2h_assemble_local_pose_graph.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, C.c_int, ip, dp, u8, ip, ip, dp]
         L.ov2h_full_pose_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, dp, C.POINTER(C.c_uint8), C.POINTER(C.c_double)]
         L.ov2h_loose_ba.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_double)]
         L.ov2h_map_set_cur_frame.argtypes = [C.c_void_p, C.c_int]
@@ -362,6 +363,23 @@ class HostMap:
         if rc < 0:
             raise RuntimeError(f"localPoseGraph failed ({rc})")
         return rc, fc.value, nl.value
+
+    def assemble_local_pose_graph(self, newkf, kfloop_id, newTwc, cap=4096):
+        """Optimizer::assembleLocalPoseGraph alone (no GPU context): None when there is no chain, else dict(kfids, pose (n x 7),
+        pose_const, edge_i, edge_j, T_ij (n x 7)) -- the loop keyframe first, the closing edge last"""
+        T = np.ascontiguousarray(newTwc, np.float64)
+        ids, ei, ej = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        pose, Tij, cst = np.zeros((cap, 7)), np.zeros((cap, 7)), np.zeros(cap, np.uint8)
+        ip = C.POINTER(C.c_int)
+        n = lib().ov2h_assemble_local_pose_graph(self.h, int(newkf), int(kfloop_id), _dp(T), cap, ids.ctypes.data_as(ip), _dp(pose),
+                                                 cst.ctypes.data_as(C.POINTER(C.c_uint8)), ei.ctypes.data_as(ip), ej.ctypes.data_as(ip),
+                                                 _dp(Tij))
+        if n < 0:
+            raise RuntimeError(f"assembleLocalPoseGraph failed ({n})")
+        if n == 0:
+            return None
+        return dict(kfids=ids[:n].copy(), pose=pose[:n].copy(), pose_const=cst[:n].copy(), edge_i=ei[:n].copy(), edge_j=ej[:n].copy(),
+                    T_ij=Tij[:n].copy())
 
     def apply_local_pose_graph(self, newkf, kfids, Twc):
         """Optimizer::applyLocalPoseGraph alone: the free keyframes `kfids` (ascending, last = newkf) take the poses Twc
@@ -994,8 +1012,8 @@ class FilterMap(TemporalMap):
     flags, covisibility counted by MapManager::updateFrameCovisibility -- to run Estimator::mapFiltering (map_filtering) on.
     Needs no GPU context unless a device mirror is attached."""
 
-    def __init__(self, m):
-        TemporalMap.__init__(self, dict(m, forget_kp=(), forget_lm=(), forget_kf=()))
+    def __init__(self, m, stereo=True):
+        TemporalMap.__init__(self, dict(m, forget_kp=(), forget_lm=(), forget_kf=()), stereo)
         L = lib()
         for l in np.intersect1d(np.flatnonzero(m["lm_isobs"] == 0), m["obs_lm"]):   # map points are created observed
             assert L.ov2h_map_set_isobs(self.h, int(l), 0) == 0

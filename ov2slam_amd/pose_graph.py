@@ -4,7 +4,7 @@ the whole LM loop on the MI355X.  Plumbing only."""
 import ctypes as C
 
 from . import _lib
-from .ba_types import BaOptionsC, PgProblemC, PgResultC
+from .ba_types import BaOptionsC, PgProblemC, PgResultC, dp
 from .frontend import _check
 
 
@@ -36,3 +36,29 @@ def solve_batch(ctx, problems, options=None):
     rcs = (PgResultC * max(B, 1))()
     _check(ctx.h, ctx.lib.ov2_pose_graph_solve_batch(ctx.h, B, pcs, C.byref(o), rcs))
     return [PgResultC.from_buffer_copy(rcs[k]) for k in range(B)]
+
+
+def _addr(a):
+    """the device address behind an int, a DeviceArray (.ptr) or a torch tensor (.data_ptr())"""
+    if a is None:
+        return None
+    if hasattr(a, "data_ptr"):
+        return a.data_ptr()
+    p = getattr(a, "ptr", a)
+    return getattr(p, "value", p)
+
+
+def solve_batch_dev(ctx, problems, d_pose, d_T_ij, d_results, options=None):
+    """ov2_pose_graph_solve_batch_dev: the structure (sizes, pose_const, edge_i, edge_j) of every PgProblem of `problems` comes
+    from the host; d_pose[b] / d_T_ij[b] are the device arrays (n_pose x 7, n_edge x 7 float64: int address, DeviceArray or
+    torch tensor) the graph is solved in, d_results the device array of len(problems) ov2_pg_result records
+    (ctypes.sizeof(PgResultC) bytes each).  Enqueues and returns: nothing is read back, nothing synchronises."""
+    o = options if options is not None else default_options()
+    B = len(problems)
+    assert len(d_pose) == len(d_T_ij) == B
+    pcs = (PgProblemC * max(B, 1))()
+    for b, p in enumerate(problems):
+        pc = p.as_c()
+        pc.pose, pc.T_ij = C.cast(C.c_void_p(_addr(d_pose[b])), dp), C.cast(C.c_void_p(_addr(d_T_ij[b])), dp)
+        pcs[b] = pc
+    _check(ctx.h, ctx.lib.ov2_pose_graph_solve_batch_dev(ctx.h, B, pcs, C.byref(o), C.c_void_p(_addr(d_results))))
