@@ -1072,6 +1072,79 @@ typedef struct ov2_map_filter {
 ov2_status ov2_map_filter_keyframes_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf,
                                           int nmin_covscore, float kf_filtering_ratio, ov2_map_filter *out /* B */);
 
+/* ---- the local map of a keyframe: Frame::set_local_mapids_ and Frame::map_covkfs_ from the mirror alone --------------------
+ * Mirror state, opt-in like the match columns: ov2_map_enable_local_sets (idempotent; pool_hint = entries the id pool starts
+ * with, 0 is fine) makes the map keep, for every keyframe id, a set of lmids stored in ASCENDING lmid: a start and a count per
+ * keyframe (device columns that follow every growth of the keyframe capacity, with host copies of both) and one id pool in
+ * device memory that new sets are appended to.  A map that never calls it allocates nothing and behaves as before.
+ *  - A set that is replaced, or whose keyframe is removed (ov2_map_remove_keyframe, the removals of
+ *    ov2_map_filter_keyframes_batch), is garbage.  The pool is squeezed -- the sets that count, in ascending kfid, into a fresh
+ *    pool -- under the observation table's rule: once at least 4096 entries have been appended and fewer than half of them
+ *    belong to a set that counts.  It grows on demand (by half).  Both happen before anything that appends is enqueued: the
+ *    host knows every count, because every call that stores a set synchronises.  Either costs one synchronisation and moves
+ *    the device list a previous ov2_map_local_ids points into.
+ *  - The set of a removed keyframe is unreadable: ov2_map_get_local_set and ov2_map_set_local_set refuse a keyframe that is
+ *    not alive, and ov2_map_local_ids_batch reads it as empty.  A keyframe that ov2_map_restore_state_batch brings back has no
+ *    set, and one that it takes out of the map (it entered after the save) loses its set like any removed keyframe.
+ *  - ov2_map_save_state / ov2_map_restore_state_batch leave the sets alone: they are not part of the saved state (the
+ *    reference's BA never touches set_local_mapids_ either).
+ * ov2_map_set_local_set stores the n ids as the set of keyframe kfid (alive): any order is accepted and stored ascending; a
+ * duplicate or a negative id is OV2_ERR_INVALID and nothing is stored.  An id beyond the landmark capacity grows the
+ * landmark tables to cover it (stored ids index the stage's per-landmark marks, so the id of a map point the mirror never
+ * held costs table rows: about 150 bytes of device memory per id of the range, tables and scratch together).  An id at or
+ * beyond the capacity + OV2_LOCAL_SET_LMID_SPAN is therefore refused with OV2_ERR_INVALID, nothing stored: a stray id from a
+ * host map must not ask for gigabytes.  ov2_map_get_local_set synchronises, writes min(cap, *n) ids and always reports the
+ * full count in *n.  ov2_map_local_pool: entries appended / allocated / of the sets that count, and squeezes so far. */
+#define OV2_LOCAL_SET_LMID_SPAN (1 << 20)
+ov2_status ov2_map_enable_local_sets(ov2_map *m, int pool_hint);
+ov2_status ov2_map_set_local_set(ov2_map *m, int kfid, int n, const int32_t *lmid);
+ov2_status ov2_map_get_local_set(ov2_map *m, int kfid, int cap, int32_t *lmid, int *n);
+ov2_status ov2_map_local_pool(const ov2_map *m, int *used, int *capacity, int *live, int *squeezes);
+
+/* MapManager::updateFrameCovisibility (src/map_manager.cpp:117-193) and the set assembly of Mapper::matchingToLocalMap
+ * (src/mapper.cpp:475-517) for the new keyframes of B map mirrors of one context that have the local sets.  Per map, with
+ * k = newkf[b] and "live row" as everywhere (row, keyframe and landmark alive):
+ *  - Obs(k) = the landmarks with a live row in k, 2D and 3D keypoints alike (Frame::getKeypoints);
+ *  - cov[j], j != k alive = live rows (j, L) with L in Obs(k); C = { j : cov[j] > 0 };
+ *  - S = every L with a live row in some j of C whose landmark carries OV2_LM_KP3D (Frame::getKeypoints3d, as the keyframe
+ *    filter reads it) and L not in Obs(k);
+ *  - store rule (:185-189), old = the stored set of k: 2 |S| > |old| -> the set of k becomes S (swapped = 1), otherwise
+ *    old + S;
+ *  - extend != 0 and C not empty (:481-497): when the count after the store rule is < nmax_local the branch is taken
+ *    (extended = 1) and the stored set of min C is added; a keyframe without a stored set contributes nothing.  The second
+ *    round of :499-516 asks for the same keyframe again and has no effect.
+ * The set of k is stored (appended to the pool, ascending) and reported.  cov_kfid (ascending) / cov_score / lmid are pinned
+ * HOST arrays of the map, d_lmid / d_n_local DEVICE pointers to the same id list (in the pool) and to its count (the
+ * keyframe's entry of the count column); all valid until the map's next call of this function, d_lmid also only until the
+ * pool next grows or is squeezed and d_n_local until the keyframe capacity grows.
+ * Departures from the reference: the set is iterated in ascending lmid where the reference iterates a std::unordered_set
+ * (the order only decides the matcher's later-candidate-wins ties); covisibility is a recount from the live rows, not the
+ * incrementally kept map_covkfs_, and the reciprocal write pkf->map_covkfs_[frame.kfid_] = score has no mirror counterpart;
+ * the "missing map point" (:131-135) and "keyframe gone" (:172-174) branches have nothing to do, dead rows are not live; an
+ * empty C with extend does nothing where the reference dereferences begin() of an empty map.
+ * map = blockIdx.y of every launch, sizes come from device memory, nine launches whatever B and the list lengths are: the
+ * clear of the stage's own scratch block, three row scans (Obs(k); cov and min C, one atomic per wave and keyframe; the marks
+ * of S, counted where a mark is first set, one add per wave), one workgroup per map (covisibility lists by a block scan over
+ * the keyframes, then the two rules from the device counts over the two stored lists), the three scan kernels over the
+ * landmark marks, and the compaction into the pool and the gathered copy.  All counting is integer: results are bit-identical
+ * from run to run and whatever else the batch holds.  The arrays of the last BA set-up stay as they are and the call does
+ * NOT end what that set-up can be updated from: it changes no table the update reads.
+ * One synchronisation per call (all headers and lists in one D2H), after which the host copies of the per-keyframe starts
+ * and counts are updated.  B = 0 is OV2_OK.  OV2_ERR_INVALID with nothing enqueued and every map untouched: a map without
+ * local sets, of another context or listed twice; newkf[b] not alive; out == NULL; nmax_local < 0. */
+typedef struct ov2_map_local_ids {
+    int32_t n_cov, oldest_cov;     /* |C|, min C or -1 (the inikfid of LoopCloser::closeLoop) */
+    int32_t n_fresh, n_local;      /* |S|, the size of the set of k as stored */
+    int32_t swapped, extended;     /* the store rule swapped / the extension branch was taken */
+    const int32_t *cov_kfid;       /* HOST (pinned, the map's), n_cov, ascending */
+    const int32_t *cov_score;      /* HOST, n_cov: cov[cov_kfid[i]] */
+    const int32_t *lmid;           /* HOST, n_local, ascending: the set of k */
+    const int32_t *d_lmid;         /* DEVICE, the same list */
+    const int32_t *d_n_local;      /* DEVICE, one int: its count */
+} ov2_map_local_ids;
+ov2_status ov2_map_local_ids_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf, int extend, int nmax_local,
+                                   ov2_map_local_ids *out /* B */);
+
 /* The update stage of Optimizer::localPoseGraph (src/optimizer.cpp:2476-2577) on the tables of B map mirrors of one context,
  * for maps that have no host objects beside them (with a host mirror attached the same edit arrives through
  * ov2_map_set_poses / ov2_map_set_landmarks).  Four launches whatever B is (map = blockIdx.y): the clear of the scratch

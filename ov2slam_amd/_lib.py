@@ -130,6 +130,11 @@ SIGNATURES = {
     "ov2_map_local_ba_update_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
     "ov2_map_triangulate_temporal_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_float, vp]),
     "ov2_map_filter_keyframes_batch": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_float, vp]),
+    "ov2_map_enable_local_sets": (C.c_int, [vp, C.c_int]),
+    "ov2_map_set_local_set": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+    "ov2_map_get_local_set": (C.c_int, [vp, C.c_int, C.c_int, vp, ip]),
+    "ov2_map_local_pool": (C.c_int, [vp, ip, ip, ip, ip]),
+    "ov2_map_local_ids_batch": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp]),
     "ov2_map_save_state": (C.c_int, [vp]),
     "ov2_map_restore_state_batch": (C.c_int, [vp, C.c_int, vp]),
     "ov2_map_download": (C.c_int, [vp, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -82,6 +82,19 @@ struct ov2_map {
     int *gt_seen_h; int gt_gen;                                     // host, [max_lm]: the call that last listed the landmark (duplicates are refused)
     // ov2_map_structure_ba_batch: the solver's state, O(listed entries), allocated with the first call (null before it)
     unsigned char *sb_ws; int sb_cap;                               // sb_cap entries: SP_N doubles per point | the entered ids
+    // ov2_map_enable_local_sets: Frame::set_local_mapids_ per keyframe, ascending lmid, in one id pool (all null / 0 without it)
+    int ls_on;
+    int *ls_start, *ls_count;                                       // [max_kf] where the keyframe's set starts in the pool, its size (0: none)
+    int *ls_start_h, *ls_count_h;                                   // host copies of both
+    int *ls_pool; int ls_pool_cap, ls_pool_used, ls_live;           // the pool: entries allocated / appended so far / of the sets that count
+    int ls_squeezes;                                                // times the pool was squeezed
+    // ov2_map_local_ids_batch: scratch of its own
+    unsigned char *ls_zero; size_t ls_zero_bytes;                   // hdr (MH_N ints) | ls_cov | ls_mark | ls_obs: one clear per call
+    int *ls_cov;                                                    // [max_kf] covisibility with the new keyframe
+    int *ls_mark;                                                   // [max_lm] 1: the landmark is in the set being built
+    unsigned char *ls_obs;                                          // [max_lm] observed by the new keyframe
+    int *ls_pos;                                                    // [max_lm] exclusive scan of ls_mark: the landmark's place in the set
+    int *ls_out_h; int ls_out_cap;                                  // pinned: cov_kfid | cov_score | lmid of the last call
 };
 
 namespace {
@@ -95,6 +108,9 @@ enum { MH_NBKPS = 0, MH_NB3D, MH_ABORT, MH_NMAXKF, MH_NPOSE, MH_NRES, MH_NLM, MH
 enum { FH_CANDIDATES = 0, FH_REMOVED, FH_FEW3D, FH_UNSET3D, FH_ROWS };
 // header of the map-point merge (its own block as well): the five counts of ov2_map_merge, and the scan total of the rows
 enum { GH_PAIRS = 0, GH_MERGED, GH_SKIPPED, GH_MOVED, GH_CONFLICT, GH_ROWS };
+// header of the local-map selection (its own block too): what ov2_map_local_ids reports.  LH_OLDMAX is the smallest covisible
+// kfid as ANCH_TOP - kfid under atomicMax (0 = none), LH_NLOCAL the scan total of the marks
+enum { LH_NCOV = 0, LH_OLDMAX, LH_NFRESH, LH_NLOCAL, LH_SWAPPED, LH_EXTENDED, LH_OLDEST };
 #define ANCH_TOP 0x40000000   // anchor keyframe stored as ANCH_TOP - kfid under atomicMax: 0 = none, so the array lives in the zeroed block
 enum { OBS_ALIVE = 1, OBS_STEREO = 2 };
 enum { MAP_COMPACT_MIN_ROWS = 4096 };   // below this the scans cost nothing worth a reallocation
@@ -263,6 +279,14 @@ struct map_job {
     // lb_cnt / lb_tmp: LB_N counters and inverse(old(newkf)) | opt | T_corr behind the map's gathered header)
     int lb_lo, lb_on;
     int *lb_cnt; double *lb_tmp;
+    // local-map selection (hdr / zero_blk point at the stage's own block in its job records; hdr_out is followed by
+    // ls_kcap covisible kfids | ls_kcap scores | ls_room lmids)
+    int ls_on;                                   // 1 in the records of ov2_map_local_ids_batch: the scan reads ls_mark
+    int ls_extend, ls_nmax;                      // the extension of Mapper::matchingToLocalMap is asked for / its size gate
+    int ls_kcap, ls_room;                        // entries of the two covisibility lists / of the id list, in the gathered copy and in the pool
+    int ls_pool_off;                             // where the new set starts in the pool (ls_pool_off + ls_room <= its capacity)
+    int *ls_cov, *ls_mark, *ls_pos, *ls_pool, *ls_start, *ls_count;
+    unsigned char *ls_obs;
 };
 
 // the flat arrays of a gather call (ov2_match_batch_input as the kernels write it) and their row capacity
@@ -544,7 +568,8 @@ __global__ __launch_bounds__(256) void ms_res_count_kernel(const map_job *__rest
 // SC_KF the live rows per keyframe of the keyframe filter (total -> FH_ROWS of its header)
 // SC_MG the live rows per named landmark of the map-point merge (total -> GH_ROWS of its header)
 // SC_GT a flat count array of the match gather, in place (total -> the entry behind the array: the n + 1 prefix offsets)
-enum { SC_LM = 0, SC_RES, SC_LIVE, SC_KF, SC_MG, SC_GT };
+// SC_LS the landmark marks of the local-map selection (total -> LH_NLOCAL of its header)
+enum { SC_LM = 0, SC_RES, SC_LIVE, SC_KF, SC_MG, SC_GT, SC_LS };
 
 template <typename T>
 __device__ __forceinline__ T shfl_up_t(T v, int o)
@@ -573,6 +598,9 @@ __device__ __forceinline__ void scan_args(const map_job &j, int which, const T *
     } else if (which == SC_GT) {
         in = reinterpret_cast<const T *>(j.gt_scan); out = reinterpret_cast<T *>(j.gt_scan); n = j.gt_scan_n;
         total = reinterpret_cast<T *>(j.gt_scan + j.gt_scan_n);
+    } else if (which == SC_LS) {
+        in = reinterpret_cast<const T *>(j.ls_mark); out = reinterpret_cast<T *>(j.ls_pos); n = j.ls_on ? j.M.max_lm : 0;
+        total = reinterpret_cast<T *>(j.hdr + LH_NLOCAL);
     } else {
         in = reinterpret_cast<const T *>(j.obs_cnt); out = reinterpret_cast<T *>(j.obs_off); n = j.M.n_obs;
         total = reinterpret_cast<T *>(j.hdr + (which == SC_RES ? MH_NRES : MH_NLIVE));
@@ -1144,6 +1172,131 @@ __global__ __launch_bounds__(MF_THREADS) void mf_walk_kernel(const map_job *__re
         int *H = j.hdr_out;
         for (int t = 0; t < MH_N; ++t) H[t] = 0;
         H[FH_CANDIDATES] = ncand; H[FH_REMOVED] = nrem; H[FH_FEW3D] = nfew; H[FH_UNSET3D] = s_unset;
+    }
+}
+
+// ---- the local map of a new keyframe: MapManager::updateFrameCovisibility (src/map_manager.cpp:117-193) and the extension of
+// Mapper::matchingToLocalMap (src/mapper.cpp:475-517) on the tables and the per-keyframe id sets ------------------------------
+// row scan: Obs(k), the landmarks with a live row in the new keyframe (2D and 3D keypoints alike, Frame::getKeypoints)
+__global__ __launch_bounds__(256) void li_obs_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf, lm;
+    if (i >= M.n_obs || !obs_live(M, i, kf, lm)) return;
+    if (kf == j.newkf) j.ls_obs[lm] = 1;   // every writer stores the same value
+}
+
+// row scan: cov[j] as ms_cov_kernel counts it, one atomic per wave and keyframe (rows of a keyframe are mostly adjacent: a
+// wave would otherwise queue 64 adds on one counter), and the smallest covisible kfid beside it
+__global__ __launch_bounds__(256) void li_cov_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if ((int)blockIdx.x * 256 >= M.n_obs) return;   // uniform per workgroup
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf = 0, lm = 0;
+    const bool live = i < M.n_obs && obs_live(M, i, kf, lm);
+    const bool cov = live && kf != j.newkf && j.ls_obs[lm];
+    int n, first;
+    wave_rank_by_key(cov, kf, n, first);
+    if (cov && (int)(threadIdx.x & 63) == first) {
+        atomicAdd(&j.ls_cov[kf], n);
+        atomicMax(&j.hdr[LH_OLDMAX], ANCH_TOP - kf);
+    }
+}
+
+// row scan: S, the Frame::getKeypoints3d landmarks of the covisible keyframes that the new keyframe does not observe.  A
+// landmark is marked by the first of its rows to arrive (an exchange on its word; rows that find the mark set pass by
+// without an atomic) and counted there: one add per wave, behind a ballot
+__global__ __launch_bounds__(256) void li_fresh_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if ((int)blockIdx.x * 256 >= M.n_obs) return;   // uniform per workgroup
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf = 0, lm = 0;
+    const bool live = i < M.n_obs && obs_live(M, i, kf, lm);
+    const bool cand = live && kf != j.newkf && j.ls_cov[kf] > 0 && (M.lm_state[lm] & OV2_LM_KP3D) && !j.ls_obs[lm];
+    bool first = false;
+    if (cand && !ld_int(j.ls_mark + lm)) first = atomicExch(&j.ls_mark[lm], 1) == 0;
+    const unsigned long long bal = __ballot(first);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&j.hdr[LH_NFRESH], __popcll(bal));
+}
+
+// marks the ids of a stored set (pool[start .. start + count)); returns how many this lane marked first
+__device__ __forceinline__ int li_mark_list(const map_job &j, int start, int count)
+{
+    int added = 0;
+    for (int t = threadIdx.x; t < count; t += 1024) {
+        const int id = j.ls_pool[start + t];
+        if ((unsigned)id < (unsigned)j.M.max_lm && atomicExch(&j.ls_mark[id], 1) == 0) ++added;
+    }
+    return added;
+}
+
+// One workgroup per map: the covisibility lists in ascending kfid (a block scan over the keyframes, 1024 per step), then the
+// two rules on the device counts -- the store rule of updateFrameCovisibility (:185-189) over the stored set of the new
+// keyframe, the size gate of matchingToLocalMap (:481-497) over the stored set of the oldest covisible keyframe -- each
+// marking the ids it lets in.  Everything that decides the control flow is uniform over the workgroup.
+__global__ __launch_bounds__(1024) void li_lists_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const int max_kf = j.M.max_kf;
+    __shared__ int wsum[16], carry_s, s_added;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int *out_kf = j.hdr_out + MH_N, *out_score = out_kf + j.ls_kcap;
+    if (tid == 0) { carry_s = 0; s_added = 0; }
+    __syncthreads();
+    for (int base = 0; base < max_kf; base += 1024) {
+        const int k = base + tid;
+        const int score = k < max_kf ? j.ls_cov[k] : 0;
+        const int f = score > 0 ? 1 : 0;
+        int x = f;
+        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
+        if (lane == 63) wsum[wv] = x;
+        __syncthreads();
+        int off = carry_s;
+        for (int w = 0; w < wv; ++w) off += wsum[w];
+        if (f && off + x - 1 < j.ls_kcap) { out_kf[off + x - 1] = k; out_score[off + x - 1] = score; }
+        __syncthreads();
+        if (tid == 1023) carry_s = off + x;
+        __syncthreads();
+    }
+    const int ncov = carry_s;
+    const int nfresh = j.hdr[LH_NFRESH];
+    const int oldest = ncov ? ANCH_TOP - j.hdr[LH_OLDMAX] : -1;
+    const int nold = j.ls_count[j.newkf];
+    const bool swapped = 2ll * nfresh > (long long)nold;
+    int added = swapped ? 0 : li_mark_list(j, j.ls_start[j.newkf], nold);
+    for (int o = 32; o; o >>= 1) added += __shfl_xor(added, o);
+    if (lane == 0 && added) atomicAdd(&s_added, added);
+    __syncthreads();
+    const bool extended = j.ls_extend && ncov > 0 && nfresh + s_added < j.ls_nmax;
+    if (extended) (void)li_mark_list(j, j.ls_start[oldest], j.ls_count[oldest]);   // a keyframe without a stored set has count 0
+    if (tid == 0) {
+        j.hdr[LH_NCOV] = ncov; j.hdr[LH_OLDEST] = oldest; j.hdr[LH_SWAPPED] = swapped; j.hdr[LH_EXTENDED] = extended;
+    }
+}
+
+// the marked landmarks in ascending lmid, to the pool segment of the new keyframe's set and to the gathered copy; the first
+// thread hands the header over and enters the set into the per-keyframe tables
+__global__ __launch_bounds__(256) void li_emit_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l < j.M.max_lm && j.ls_mark[l]) {
+        const int pos = j.ls_pos[l];
+        if (pos < j.ls_room) {   // ls_room entries are reserved in the pool and in the gathered copy (never exceeded: the host sized it)
+            j.ls_pool[j.ls_pool_off + pos] = l;
+            j.hdr_out[MH_N + 2 * j.ls_kcap + pos] = l;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int t = 0; t < MH_N; ++t) j.hdr_out[t] = j.hdr[t];
+        j.ls_start[j.newkf] = j.ls_pool_off;
+        j.ls_count[j.newkf] = min(j.hdr[LH_NLOCAL], j.ls_room);
     }
 }
 
@@ -2404,9 +2557,45 @@ static void free_match_columns(ov2_map *m)
     m->obs_px = nullptr; m->obs_desc = m->obs_hasdesc = nullptr; m->mg_srow = nullptr; m->gt_seen_h = nullptr;
 }
 
+// the per-keyframe tables of the local id sets and the scratch of ov2_map_local_ids_batch at the current capacities
+// (ov2_map_enable_local_sets, and every growth of a map that has them): no keyframe has a set; pointers must be null on entry.
+// The id pool does not follow the capacities and is not touched here.
+static ov2_status alloc_local_sets(ov2_map *m)
+{
+    ov2_ctx *c = m->c;
+    ov2_status s = OV2_OK;
+    const size_t K = m->max_kf, L = m->max_lm;
+    if (s == OV2_OK) s = dmalloc(c, &m->ls_start, K);
+    if (s == OV2_OK) s = dmalloc(c, &m->ls_count, K);
+    if (s == OV2_OK) s = dmalloc(c, &m->ls_pos, L);
+    m->ls_zero_bytes = (sizeof(int) * (MH_N + K + L) + L + 15) & ~(size_t)15;
+    if (s == OV2_OK) s = dmalloc(c, &m->ls_zero, m->ls_zero_bytes);
+    if (s == OV2_OK) {
+        m->ls_cov = reinterpret_cast<int *>(m->ls_zero) + MH_N; m->ls_mark = m->ls_cov + K;
+        m->ls_obs = reinterpret_cast<unsigned char *>(m->ls_mark + L);
+        m->ls_start_h = (int *)calloc(std::max<size_t>(K, 1), sizeof(int));
+        m->ls_count_h = (int *)calloc(std::max<size_t>(K, 1), sizeof(int));
+        if (!m->ls_start_h || !m->ls_count_h) s = ov2_set_err(c, OV2_ERR_NOMEM, "map local-set tables of %zu entries", K);
+    }
+    if (s != OV2_OK) return s;
+    OV2_HIP(c, hipMemsetAsync(m->ls_start, 0, K * sizeof(int), c->stream));
+    OV2_HIP(c, hipMemsetAsync(m->ls_count, 0, K * sizeof(int), c->stream));
+    return OV2_OK;
+}
+
+static void free_local_sets(ov2_map *m)
+{
+    void *dev[] = {m->ls_start, m->ls_count, m->ls_pos, m->ls_zero};
+    for (void *p : dev) if (p) (void)hipFree(p);
+    free(m->ls_start_h); free(m->ls_count_h);
+    m->ls_start = m->ls_count = m->ls_pos = m->ls_cov = m->ls_mark = nullptr; m->ls_zero = m->ls_obs = nullptr;
+    m->ls_start_h = m->ls_count_h = nullptr;
+}
+
 static void free_capacity_arrays(ov2_map *m)
 {
     free_match_columns(m);
+    free_local_sets(m);
     void *dev[] = {m->kf_pose, m->kf_state, m->lm_xyz, m->lm_state, m->obs_kf, m->obs_lm, m->obs_scale, m->obs_uv, m->obs_ruv,
                    m->obs_flag, m->zero_blk, m->kf_idx, m->lm_flag, m->lm_pack, m->lm_pidx, m->obs_cnt, m->obs_off, m->blk,
                    m->tt_zero, m->tt_int, m->tt_dbl, m->fl_zero, m->fl_start, m->fl_rows, m->fl_unset,
@@ -2430,8 +2619,11 @@ static ov2_status ensure_capacity(ov2_map *m, int need_kf, int need_lm, int need
     m->fl_zero = nullptr; m->fl_start = m->fl_rows = m->fl_unset = nullptr;
     m->mg_zero = nullptr; m->mg_start = m->mg_rows = nullptr;
     m->obs_px = nullptr; m->obs_desc = m->obs_hasdesc = nullptr; m->mg_srow = nullptr; m->gt_seen_h = nullptr;
+    m->ls_start = m->ls_count = m->ls_pos = m->ls_cov = m->ls_mark = nullptr; m->ls_zero = m->ls_obs = nullptr;
+    m->ls_start_h = m->ls_count_h = nullptr;
     ov2_status s = alloc_tables(m);
     if (s == OV2_OK && old.obs_hasdesc) s = alloc_match_columns(m);   // a map that has the columns keeps them
+    if (s == OV2_OK && old.ls_on) s = alloc_local_sets(m);            // ... and one that has the local sets keeps those (the pool stays)
     unsigned char *alive = s == OV2_OK ? (unsigned char *)calloc((size_t)m->max_kf, 1) : nullptr;
     if (s == OV2_OK && !alive) s = ov2_set_err(c, OV2_ERR_NOMEM, "map keyframe list of %d entries", m->max_kf);
     if (s != OV2_OK) {
@@ -2451,6 +2643,10 @@ static ov2_status ensure_capacity(ov2_map *m, int need_kf, int need_lm, int need
     CP(kf_pose, 7 * K); CP(kf_state, K); CP(lm_xyz, 3 * L); CP(lm_state, L);
     CP(obs_kf, N); CP(obs_lm, N); CP(obs_scale, N); CP(obs_uv, 2 * N); CP(obs_ruv, 2 * N); CP(obs_flag, N);
     if (old.obs_hasdesc) { CP(obs_px, 2 * N); CP(obs_desc, 32 * N); CP(obs_hasdesc, N); }
+    if (old.ls_on) {   // the per-keyframe columns of the local sets travel with the keyframe capacity
+        CP(ls_start, K); CP(ls_count, K);
+        memcpy(m->ls_start_h, old.ls_start_h, K * sizeof(int)); memcpy(m->ls_count_h, old.ls_count_h, K * sizeof(int));
+    }
 #undef CP
     OV2_HIP(c, hipStreamSynchronize(st));
     free_capacity_arrays(&old);
@@ -2591,6 +2787,8 @@ static void free_tables(ov2_map *m)
     if (m->hdr_host) (void)hipHostFree(m->hdr_host);
     if (m->fl_removed_h) (void)hipHostFree(m->fl_removed_h);
     if (m->sb_ws) (void)hipFree(m->sb_ws);
+    if (m->ls_pool) (void)hipFree(m->ls_pool);
+    if (m->ls_out_h) (void)hipHostFree(m->ls_out_h);
     free(m->kf_alive_h); free(m->snap_kf_alive_h);
 }
 
@@ -2627,6 +2825,153 @@ extern "C" ov2_status ov2_map_enable_match_columns(ov2_map *m)
     const ov2_status s = alloc_match_columns(m);
     if (s != OV2_OK) { free_match_columns(m); return s; }
     OV2_HIP(c, hipStreamSynchronize(c->stream));
+    return OV2_OK;
+}
+
+// ---- the per-keyframe local id sets (Frame::set_local_mapids_) -------------------------------------------------------------
+// Sets are appended to the pool; a replaced set and the set of a removed keyframe stay behind as garbage.  The pool is
+// squeezed under the observation table's rule (squeeze_due): fewer than half of >= MAP_COMPACT_MIN_ROWS appended entries
+// belong to a set that counts.
+static bool ls_squeeze_due(const ov2_map *m)
+{
+    return m->ls_pool_used >= MAP_COMPACT_MIN_ROWS && 2ll * m->ls_live < (long long)m->ls_pool_used;
+}
+
+// room for `need` more entries behind the used part of the pool, before anything that appends is enqueued: a squeeze when one
+// is due (the sets that count, in ascending kfid, into a fresh pool), a larger pool when it is still short (a rare event;
+// one synchronisation either way)
+static ov2_status ls_reserve(ov2_map *m, int need)
+{
+    ov2_ctx *c = m->c;
+    const bool squeeze = ls_squeeze_due(m);
+    const long long used = squeeze ? m->ls_live : m->ls_pool_used;
+    if (!squeeze && used + need <= m->ls_pool_cap) return OV2_OK;
+    long long cap = m->ls_pool_cap;
+    if (used + need > cap) cap = std::max(used + need, cap + cap / 2 + 16);
+    if (cap > 0x7fffffffll) return ov2_set_err(c, OV2_ERR_NOMEM, "local-set pool of %lld entries", cap);
+    int *fresh = nullptr;
+    ov2_status s = dmalloc(c, &fresh, (size_t)cap);
+    if (s != OV2_OK) return s;
+    hipStream_t st = c->stream;
+    std::vector<int> start;
+    hipError_t e = hipSuccess;
+    if (squeeze) {
+        start.assign((size_t)m->max_kf, 0);
+        int o = 0;
+        for (int k = 0; k < m->max_kf && e == hipSuccess; ++k) {
+            const int n = m->ls_count_h[k];
+            if (!n) continue;
+            e = hipMemcpyAsync(fresh + o, m->ls_pool + m->ls_start_h[k], (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st);
+            start[k] = o; o += n;
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(m->ls_start, start.data(), (size_t)m->max_kf * sizeof(int), hipMemcpyHostToDevice, st);
+    } else if (m->ls_pool_used) {
+        e = hipMemcpyAsync(fresh, m->ls_pool, (size_t)m->ls_pool_used * sizeof(int), hipMemcpyDeviceToDevice, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipFree(fresh);
+        return ov2_set_err(c, OV2_ERR_HIP, "local-set pool copy failed: %s", hipGetErrorString(e));
+    }
+    if (m->ls_pool) (void)hipFree(m->ls_pool);
+    m->ls_pool = fresh; m->ls_pool_cap = (int)cap;
+    if (squeeze) {
+        memcpy(m->ls_start_h, start.data(), (size_t)m->max_kf * sizeof(int));
+        m->ls_pool_used = m->ls_live;
+        m->ls_squeezes++;
+    }
+    return OV2_OK;
+}
+
+// the set of a keyframe that left the map: unreadable from here on, its entries garbage
+static ov2_status ls_forget(ov2_map *m, int kfid)
+{
+    if (!m->ls_on || !m->ls_count_h[kfid]) return OV2_OK;
+    m->ls_live -= m->ls_count_h[kfid];
+    m->ls_count_h[kfid] = 0;
+    OV2_HIP(m->c, hipMemsetAsync(m->ls_count + kfid, 0, sizeof(int), m->c->stream));
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_map_enable_local_sets(ov2_map *m, int pool_hint)
+{
+    if (!m || !m->c) return OV2_ERR_INVALID;
+    ov2_ctx *c = m->c;
+    if (pool_hint < 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_enable_local_sets: negative pool size %d", pool_hint);
+    if (m->ls_on) return OV2_OK;
+    OV2_HIP(c, hipSetDevice(c->device));
+    ov2_status s = alloc_local_sets(m);
+    if (s == OV2_OK) s = dmalloc(c, &m->ls_pool, (size_t)pool_hint);
+    if (s != OV2_OK) {
+        free_local_sets(m);
+        if (m->ls_pool) (void)hipFree(m->ls_pool);
+        m->ls_pool = nullptr;
+        return s;
+    }
+    m->ls_pool_cap = pool_hint; m->ls_pool_used = m->ls_live = m->ls_squeezes = 0;
+    m->ls_on = 1;
+    OV2_HIP(c, hipStreamSynchronize(c->stream));
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_map_local_pool(const ov2_map *m, int *used, int *capacity, int *live, int *squeezes)
+{
+    if (!m || !m->ls_on) return OV2_ERR_INVALID;
+    if (used) *used = m->ls_pool_used;
+    if (capacity) *capacity = m->ls_pool_cap;
+    if (live) *live = m->ls_live;
+    if (squeezes) *squeezes = m->ls_squeezes;
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_map_set_local_set(ov2_map *m, int kfid, int n, const int32_t *lmid)
+{
+    if (!m || !m->c) return OV2_ERR_INVALID;
+    ov2_ctx *c = m->c;
+    if (!m->ls_on) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_set_local_set: the map has no local sets");
+    if (n < 0 || (n && !lmid)) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_set_local_set: null argument");
+    if (kfid < 0 || kfid >= m->max_kf || !m->kf_alive_h[kfid]) return ov2_set_err(c, OV2_ERR_INVALID, "keyframe %d is not alive in the map", kfid);
+    std::vector<int32_t> ids(lmid, lmid + n);
+    std::sort(ids.begin(), ids.end());
+    if (n && ids[0] < 0) return ov2_set_err(c, OV2_ERR_INVALID, "negative lmid %d", ids[0]);
+    // the landmark tables grow to cover the largest id (below): one stray id must not ask for gigabytes
+    if (n && (long long)ids[n - 1] >= (long long)m->max_lm + OV2_LOCAL_SET_LMID_SPAN)
+        return ov2_set_err(c, OV2_ERR_INVALID, "lmid %d lies too far beyond the landmark capacity %d", ids[n - 1], m->max_lm);
+    for (int i = 1; i < n; ++i)
+        if (ids[i] == ids[i - 1]) return ov2_set_err(c, OV2_ERR_INVALID, "lmid %d appears twice in the set", ids[i]);
+    OV2_HIP(c, hipSetDevice(c->device));
+    ov2_status s;
+    // a stored id indexes the per-landmark marks of ov2_map_local_ids_batch: the landmark capacity covers it
+    if (n && (s = ensure_capacity(m, m->max_kf, ids[n - 1] + 1, m->n_obs)) != OV2_OK) return s;
+    if ((s = ls_reserve(m, n)) != OV2_OK) return s;
+    stager S{c};
+    if ((s = S.begin((size_t)n * sizeof(int) + 64)) != OV2_OK) return s;
+    const int entry[2] = {m->ls_pool_used, n};
+    const int *de = S.put(entry, 2), *dl = S.put(ids.data(), (size_t)n);
+    if ((s = S.flush()) != OV2_OK) return s;
+    hipStream_t st = c->stream;
+    if (n) OV2_HIP(c, hipMemcpyAsync(m->ls_pool + m->ls_pool_used, dl, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st));
+    OV2_HIP(c, hipMemcpyAsync(m->ls_start + kfid, de, sizeof(int), hipMemcpyDeviceToDevice, st));
+    OV2_HIP(c, hipMemcpyAsync(m->ls_count + kfid, de + 1, sizeof(int), hipMemcpyDeviceToDevice, st));
+    m->ls_live += n - m->ls_count_h[kfid];
+    m->ls_start_h[kfid] = m->ls_pool_used; m->ls_count_h[kfid] = n;
+    m->ls_pool_used += n;
+    OV2_HIP(c, hipStreamSynchronize(st));   // the staging block is free again
+    return OV2_OK;
+}
+
+extern "C" ov2_status ov2_map_get_local_set(ov2_map *m, int kfid, int cap, int32_t *lmid, int *n)
+{
+    if (!m || !m->c) return OV2_ERR_INVALID;
+    ov2_ctx *c = m->c;
+    if (!m->ls_on) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_get_local_set: the map has no local sets");
+    if (!n || cap < 0 || (cap && !lmid)) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_get_local_set: null argument");
+    if (kfid < 0 || kfid >= m->max_kf || !m->kf_alive_h[kfid]) return ov2_set_err(c, OV2_ERR_INVALID, "keyframe %d is not alive in the map", kfid);
+    OV2_HIP(c, hipSetDevice(c->device));
+    OV2_HIP(c, hipStreamSynchronize(c->stream));
+    *n = m->ls_count_h[kfid];
+    const int take = std::min(cap, *n);
+    if (take > 0) OV2_HIP(c, hipMemcpy(lmid, m->ls_pool + m->ls_start_h[kfid], (size_t)take * sizeof(int), hipMemcpyDeviceToHost));
     return OV2_OK;
 }
 
@@ -2847,7 +3192,7 @@ extern "C" ov2_status ov2_map_remove_keyframe(ov2_map *m, int kfid)
     OV2_HIP(c, hipSetDevice(c->device));
     OV2_HIP(c, hipMemsetAsync(m->kf_state + kfid, 0, 1, c->stream));
     m->kf_alive_h[kfid] = 0;
-    return OV2_OK;
+    return ls_forget(m, kfid);
 }
 
 // ---- set-up of B maps: the whole chain of launches without a synchronisation, then one for the gathered headers ----
@@ -3397,8 +3742,97 @@ extern "C" ov2_status ov2_map_filter_keyframes_batch(ov2_ctx *c, int B, ov2_map 
             const int k = H[MH_N + i];
             m->fl_removed_h[i] = k;
             m->kf_alive_h[k] = 0;
+            if ((s = ls_forget(m, k)) != OV2_OK) return s;   // its local id set goes with it
         }
         m->last_valid = 0;   // its tables changed under the last set-up: no update stage from it any more
+    }
+    return OV2_OK;
+}
+
+// ---- local-map selection of B maps: nine launches whatever B, one synchronisation for the headers and the lists ----------
+extern "C" ov2_status ov2_map_local_ids_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf, int extend, int nmax_local,
+                                              ov2_map_local_ids *out)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps || !newkf || !out) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_local_ids_batch: null argument");
+    if (nmax_local < 0) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_local_ids_batch: nmax_local %d", nmax_local);
+    ov2_status s;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
+        if (!m->ls_on) return ov2_set_err(c, OV2_ERR_INVALID, "map %d of the batch has no local sets", b);
+        if ((s = batch_kf_alive(c, m, newkf[b], b)) != OV2_OK) return s;
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
+    }
+    memset(out, 0, (size_t)B * sizeof(*out));
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // The host knows every count: the new set is a subset of S + old + extension, all distinct ids below max_lm.  That many
+    // entries are reserved in the pool and in the gathered copy before anything is enqueued.
+    int nmax = 0, lmax = 0, kmax = 0, room_max = 0; unsigned zmax = 0;
+    std::vector<int> room((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = maps[b];
+        int top = 0;
+        for (int k = 0; k < m->max_kf; ++k) top = std::max(top, m->ls_count_h[k]);
+        room[b] = (int)std::min<long long>(m->max_lm, (long long)m->n_obs + m->ls_count_h[newkf[b]] + top);
+        if ((s = ls_reserve(m, room[b])) != OV2_OK) return s;
+        nmax = std::max(nmax, m->n_obs); lmax = std::max(lmax, m->max_lm); kmax = std::max(kmax, m->max_kf);
+        room_max = std::max(room_max, room[b]);
+        zmax = std::max(zmax, (unsigned)(m->ls_zero_bytes / 16));
+    }
+    for (int b = 0; b < B; ++b) {   // the pinned lists of the map: two covisibility lists and the ids
+        ov2_map *m = maps[b];
+        const int need = 2 * m->max_kf + room[b];
+        if (m->ls_out_cap >= need) continue;
+        if (m->ls_out_h) OV2_HIP(c, hipHostFree(m->ls_out_h));
+        m->ls_out_h = nullptr; m->ls_out_cap = 0;
+        if (hipHostMalloc((void **)&m->ls_out_h, (size_t)need * sizeof(int), hipHostMallocDefault) != hipSuccess)
+            return ov2_set_err(c, OV2_ERR_NOMEM, "pinned local-map lists of %d entries", need);
+        m->ls_out_cap = need;
+    }
+    job_table JT;
+    if ((s = JT.begin(c, B, 2 * kmax + room_max)) != OV2_OK) return s;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        map_job j = job_of(m, newkf[b], -1);
+        stage_block(j, m->ls_zero, m->ls_zero_bytes);
+        j.ls_on = 1; j.ls_extend = extend != 0; j.ls_nmax = nmax_local; j.ls_kcap = kmax; j.ls_room = room[b];
+        j.ls_pool_off = m->ls_pool_used;
+        j.ls_cov = m->ls_cov; j.ls_mark = m->ls_mark; j.ls_obs = m->ls_obs; j.ls_pos = m->ls_pos;
+        j.ls_pool = m->ls_pool; j.ls_start = m->ls_start; j.ls_count = m->ls_count;
+        JT.set(b, j);
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), gL((lmax + 255) / 256, B), one(1, B), b256(256);
+    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::min(64u, (zmax + 255) / 256), B), b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, li_obs_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, li_cov_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, li_fresh_kernel, gN, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, li_lists_kernel, one, dim3(1024), 0, st, JT.dev);
+    if ((s = exclusive_scan<int>(c, JT, SC_LS, lmax)) != OV2_OK) return s;
+    // lmax >= 1 (ov2_map_create refuses a capacity of 0 and the tables only grow): the grid is never empty, and its first
+    // thread hands the header over whatever the marks hold
+    OV2_LAUNCH(c, OV2_K_MAP, li_emit_kernel, gL, b256, 0, st, JT.dev);
+    if ((s = JT.fetch_headers()) != OV2_OK) return s;
+    for (int b = 0; b < B; ++b) {
+        ov2_map *m = maps[b];
+        const int *H = JT.hdr_host + (size_t)b * JT.stride;
+        const int k = newkf[b], n_cov = H[LH_NCOV], n_local = H[LH_NLOCAL];
+        if (n_local > room[b] || n_cov > kmax) return ov2_set_err(c, OV2_ERR_HIP, "map %d: a local-map list outgrew its reserve", b);
+        int *cov_kfid = m->ls_out_h, *cov_score = cov_kfid + m->max_kf, *lmid = cov_score + m->max_kf;
+        memcpy(cov_kfid, H + MH_N, (size_t)n_cov * sizeof(int));
+        memcpy(cov_score, H + MH_N + kmax, (size_t)n_cov * sizeof(int));
+        memcpy(lmid, H + MH_N + 2 * kmax, (size_t)n_local * sizeof(int));
+        out[b].n_cov = n_cov; out[b].oldest_cov = H[LH_OLDEST]; out[b].n_fresh = H[LH_NFRESH]; out[b].n_local = n_local;
+        out[b].swapped = H[LH_SWAPPED]; out[b].extended = H[LH_EXTENDED];
+        out[b].cov_kfid = cov_kfid; out[b].cov_score = cov_score; out[b].lmid = lmid;
+        // the set stands where the kernels appended it; what it replaced is garbage
+        m->ls_live += n_local - m->ls_count_h[k];
+        m->ls_start_h[k] = m->ls_pool_used; m->ls_count_h[k] = n_local;
+        out[b].d_lmid = m->ls_pool + m->ls_pool_used; out[b].d_n_local = m->ls_count + k;
+        m->ls_pool_used += n_local;
     }
     return OV2_OK;
 }
@@ -4229,6 +4663,10 @@ extern "C" ov2_status ov2_map_restore_state_batch(ov2_ctx *c, int B, ov2_map *co
     if ((s = JT.begin(c, B)) != OV2_OK) return s;
     for (int b = 0; b < B; ++b) {
         JT.set(b, job_of(maps[b], -1, -1)); maps[b]->last_valid = 0;
+        // a keyframe the restore takes out of the map (one that entered after the save) loses its local id set like any
+        // removed keyframe; the sets of the others are not part of the saved state and stay
+        for (int k = 0; maps[b]->ls_on && k < maps[b]->max_kf; ++k)
+            if (maps[b]->kf_alive_h[k] && !maps[b]->snap_kf_alive_h[k] && (s = ls_forget(maps[b], k)) != OV2_OK) return s;
         memcpy(maps[b]->kf_alive_h, maps[b]->snap_kf_alive_h, (size_t)maps[b]->max_kf);
     }
     if ((s = JT.upload()) != OV2_OK) return s;

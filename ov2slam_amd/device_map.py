@@ -36,6 +36,12 @@ class FilterC(C.Structure):
                 ("removed_kfid", C.c_void_p), ("unset3d_lmid", C.c_void_p)]
 
 
+class LocalIdsC(C.Structure):
+    """ov2_map_local_ids"""
+    _fields_ = [(n, C.c_int32) for n in ("n_cov", "oldest_cov", "n_fresh", "n_local", "swapped", "extended")] + [
+        (n, C.c_void_p) for n in ("cov_kfid", "cov_score", "lmid", "d_lmid", "d_n_local")]
+
+
 class PgUpdateC(C.Structure):
     """ov2_map_pg_update"""
     _fields_ = [("n_kf_chain", C.c_int32), ("n_kf_younger", C.c_int32), ("n_lm_moved", C.c_int32), ("T_corr", C.c_double * 7)]
@@ -282,6 +288,36 @@ class DeviceMap:
     def remove_keyframe(self, kfid):
         _check(self.ctx.h, self.L.ov2_map_remove_keyframe(self.h, int(kfid)))
 
+    def enable_local_sets(self, pool_hint=0):
+        """ov2_map_enable_local_sets: the map keeps a local id set (Frame::set_local_mapids_) per keyframe from here on"""
+        _check(self.ctx.h, self.L.ov2_map_enable_local_sets(self.h, int(pool_hint)))
+
+    def set_local_set(self, kfid, lmids):
+        """ov2_map_set_local_set: the set of keyframe kfid becomes `lmids` (any order; stored ascending; duplicates refused)"""
+        a = np.ascontiguousarray(lmids, np.int32).reshape(-1)
+        _check(self.ctx.h, self.L.ov2_map_set_local_set(self.h, int(kfid), len(a), self._p(a)))
+
+    def get_local_set(self, kfid, cap=None):
+        """ov2_map_get_local_set: the stored set of keyframe kfid (ascending), read back from the device.  cap: the entries asked
+        for (default: all, in two calls); returns the array, or (array of min(cap, n) ids, n) when cap is given"""
+        n = C.c_int()
+        if cap is None:
+            _check(self.ctx.h, self.L.ov2_map_get_local_set(self.h, int(kfid), 0, None, C.byref(n)))
+        out = np.zeros(max(n.value if cap is None else int(cap), 1), np.int32)
+        want = n.value if cap is None else int(cap)
+        _check(self.ctx.h, self.L.ov2_map_get_local_set(self.h, int(kfid), want, self._p(out), C.byref(n)))
+        return out[:n.value].copy() if cap is None else (out[:min(want, n.value)].copy(), n.value)
+
+    def local_pool(self):
+        """ov2_map_local_pool: dict(used, capacity, live, squeezes) of the id pool"""
+        v = [C.c_int() for _ in range(4)]
+        _check(self.ctx.h, self.L.ov2_map_local_pool(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("used", "capacity", "live", "squeezes"), [x.value for x in v]))
+
+    def local_ids_batch(self, others=(), newkf=None, extend=True, nmax_local=0):
+        """ov2_map_local_ids_batch on this map and `others` in one call; see local_ids_batch"""
+        return local_ids_batch(self.ctx, [self] + list(others), newkf, extend, nmax_local)
+
     def filter_keyframes_batch(self, others=(), newkf=None, nmin_covscore=25, ratio=0.9):
         """ov2_map_filter_keyframes_batch on this map and `others` in one call; see filter_keyframes_batch"""
         return filter_keyframes_batch(self.ctx, [self] + list(others), newkf, nmin_covscore, ratio)
@@ -448,6 +484,38 @@ def filter_keyframes_batch(ctx, maps, newkf=None, nmin_covscore=25, ratio=0.9):
             _check(ctx.h, ctx.lib.ov2_memcpy_d2h(ctx.h, un.ctypes.data_as(C.c_void_p), f.unset3d_lmid, un.nbytes))
         res.append(dict(candidates=f.n_candidates, few3d=f.n_few3d, removed=rm.tolist(), unset3d=np.sort(un).tolist()))
     return res
+
+
+def local_ids_batch(ctx, maps, newkf=None, extend=True, nmax_local=0, raw=False):
+    """MapManager::updateFrameCovisibility + the set assembly of Mapper::matchingToLocalMap on the tables of the maps (DeviceMap
+    objects or raw ov2_map handles, all with local sets), keyframe newkf[b] (default: each map's newkf) as the new keyframe
+    (ov2_map_local_ids_batch).  Returns per map dict(cov_kfid, cov_score, oldest_cov, n_fresh, swapped, extended, lmid: the
+    stored set of the keyframe, ascending, d_lmid / d_n_local: the device addresses of the same list and of its count);
+    raw=True: the LocalIdsC array itself"""
+    B = len(maps)
+    hs = (C.c_void_p * max(B, 1))(*[getattr(m, "h", m) for m in maps])
+    nk = np.ascontiguousarray([m.newkf for m in maps] if newkf is None else newkf, np.int32)
+    out = (LocalIdsC * max(B, 1))()
+    _check(ctx.h, ctx.lib.ov2_map_local_ids_batch(ctx.h, B, hs, nk.ctypes.data_as(C.c_void_p), int(bool(extend)), int(nmax_local), out))
+    if raw:
+        return out
+
+    def pinned(ptr, n):
+        return np.ctypeslib.as_array(C.cast(ptr, i32p), (n,)).copy() if n else np.zeros(0, np.int32)
+    return [dict(cov_kfid=pinned(u.cov_kfid, u.n_cov), cov_score=pinned(u.cov_score, u.n_cov), oldest_cov=u.oldest_cov, n_fresh=u.n_fresh,
+                 swapped=u.swapped, extended=u.extended, lmid=pinned(u.lmid, u.n_local), d_lmid=u.d_lmid, d_n_local=u.d_n_local)
+            for u in out[:B]]
+
+
+def match_local_from_mirror(ctx, maps, newkf, nb3dkps, kp_lists, grids, camera, extend=True, nmax_local=0, cam=None, fmaxprojerr=2.0,
+                            fdistratio=0.2, pairs=False, dev=False):
+    """Mapper::matchingToLocalMap on mirror-only maps from the new keyframes' keypoint ids and grids alone: local_ids_batch
+    builds (and stores) every keyframe's local set, match_local_batch takes the returned lists as its cand_lists.  Returns
+    (what match_local_batch returns, the local_ids_batch records).  Arrays are passed on, nothing is computed here."""
+    ids = local_ids_batch(ctx, maps, newkf, extend, nmax_local)
+    res = match_local_batch(ctx, maps, newkf, nb3dkps, kp_lists, grids, [r["lmid"] for r in ids], camera, cam, fmaxprojerr, fdistratio,
+                            pairs, dev)
+    return res, ids
 
 
 def pose_graph_update_batch(ctx, maps, newkf=None, chain_kfid=(), chain_Twc=(), want_header=True):

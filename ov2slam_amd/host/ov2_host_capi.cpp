@@ -209,6 +209,59 @@ int ov2h_map_set_covscore(void *p, int kfid, int other, int score)
     return 0;
 }
 
+// ---- the local map of a keyframe (MapManager::updateFrameCovisibility, the set assembly of Mapper::matchingToLocalMap); no
+// hook below needs a GPU context.  Returns are 0 (or the value named) or a negative number: -1 = the keyframe is not in the map
+// MapManager::updateFrameCovisibility on keyframe kfid: Frame::map_covkfs_ and Frame::set_local_mapids_ of the keyframe
+int ov2h_update_frame_covisibility(void *p, int kfid)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kfid);
+    if (!f) return -1;
+    m->map->updateFrameCovisibility(*f);
+    return 0;
+}
+
+// SlamManager::extendLocalMap on keyframe kfid: 1 = the extension branch was taken, 0 = it was not
+int ov2h_extend_local_map(void *p, int kfid, int nmax_local)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kfid);
+    if (!f || nmax_local < 0) return f ? -2 : -1;
+    return SlamManager::extendLocalMap(*m->map, *f, (size_t)nmax_local) ? 1 : 0;
+}
+
+// Frame::set_local_mapids_ of keyframe kfid in its own iteration order: *n = its size, the first min(cap, *n) ids in out
+int ov2h_frame_local_ids(void *p, int kfid, int cap, int *out, int *n)
+{
+    auto f = ((HostMap *)p)->map->getKeyframe(kfid);
+    if (!f) return -1;
+    int i = 0;
+    for (int l : f->set_local_mapids_) { if (i < cap) out[i] = l; ++i; }
+    *n = i;
+    return 0;
+}
+
+// Frame::set_local_mapids_ of keyframe kfid becomes the n ids (duplicates collapse, as in any set)
+int ov2h_frame_set_local_ids(void *p, int kfid, int n, const int *ids)
+{
+    auto f = ((HostMap *)p)->map->getKeyframe(kfid);
+    if (!f || n < 0) return f ? -2 : -1;
+    f->set_local_mapids_.clear();
+    f->set_local_mapids_.insert(ids, ids + n);
+    return 0;
+}
+
+// Frame::map_covkfs_ of keyframe kfid, ascending kfid: *n = its size, the first min(cap, *n) entries in kfids / scores
+int ov2h_frame_cov_map(void *p, int kfid, int cap, int *kfids, int *scores, int *n)
+{
+    auto f = ((HostMap *)p)->map->getKeyframe(kfid);
+    if (!f) return -1;
+    int i = 0;
+    for (const auto &c : f->map_covkfs_) { if (i < cap) { kfids[i] = c.first; scores[i] = c.second; } ++i; }
+    *n = i;
+    return 0;
+}
+
 // what LoopCloser::knnMatching assembles for the pair (newkf, lckf) in front of the matcher, no GPU context needed: query
 // lmids, train lmids and identity pairs (one lmid each) in the mirror's own iteration order, capacity cap each; n[3] = their
 // counts.  query_desc / train_desc (cap x 32, may be NULL): the rows the matcher would receive

@@ -377,19 +377,23 @@ ov2_status SlamManager::mapperRun(const Keyframe &kf)
     return s;
 }
 
+bool SlamManager::extendLocalMap(MapManager &map, Frame &frame, size_t nmax_localplms)
+{   // src/mapper.cpp:475-517
+    auto cov_map = frame.getCovisibleKfMap();
+    if (cov_map.empty() || frame.set_local_mapids_.size() >= nmax_localplms) return false;
+    int kfid = cov_map.begin()->first;
+    auto pkf = map.getKeyframe(kfid);
+    while (!pkf && kfid > 0) { kfid--; pkf = map.getKeyframe(kfid); }
+    if (pkf) frame.set_local_mapids_.insert(pkf->set_local_mapids_.begin(), pkf->set_local_mapids_.end());
+    // "another round" (:499-516) asks for getKeyframe(pkf->kfid_) -- the SAME keyframe -- and inserts its ids again: no effect
+    return true;
+}
+
 ov2_status SlamManager::matchingToLocalMap(Frame &frame)
 {   // src/mapper.cpp:469-554 (bnewkfavailable_ = false: one call processes a keyframe to the end); the merges run here, before
     // the local BA, where the reference detaches a thread that takes optim_mutex_
-    const size_t nmax_localplms = (size_t)pslamstate_->nbmaxkps_ * 10;
-    auto cov_map = frame.getCovisibleKfMap();
-    if (cov_map.empty()) return OV2_OK;   // (the reference dereferences begin() of an empty map here)
-    if (frame.set_local_mapids_.size() < nmax_localplms) {
-        int kfid = cov_map.begin()->first;
-        auto pkf = pmap_->getKeyframe(kfid);
-        while (!pkf && kfid > 0) { kfid--; pkf = pmap_->getKeyframe(kfid); }
-        if (pkf) frame.set_local_mapids_.insert(pkf->set_local_mapids_.begin(), pkf->set_local_mapids_.end());
-        // "another round" (:499-516) asks for getKeyframe(pkf->kfid_) -- the SAME keyframe -- and inserts its ids again: no effect
-    }
+    if (frame.getCovisibleKfMap().empty()) return OV2_OK;   // (the reference dereferences begin() of an empty map here)
+    extendLocalMap(*pmap_, frame, (size_t)pslamstate_->nbmaxkps_ * 10);
     last_.n_local = (int)frame.set_local_mapids_.size();
     std::map<int, int> map_previd_newid;
     const ov2_status s = matchToMap(frame, pslamstate_->fmax_proj_pxdist_, pslamstate_->fmax_desc_dist_, frame.set_local_mapids_, map_previd_newid);

@@ -151,6 +151,12 @@ public:
     // the flag is ignored.
     static ov2_status matchToLocalMaps(ov2_ctx *ctx, std::vector<MatchJob> &jobs, float fmaxprojerr, float fdistratio, bool merge, bool single,
                                        MatchBatchStats &stats, bool mirror = false);
+    // The set assembly of Mapper::matchingToLocalMap (src/mapper.cpp:475-517), what it does in front of matchToMap: with an
+    // empty covisibility map nothing happens (the reference dereferences begin() of an empty map); otherwise, when the
+    // frame's local set holds fewer than nmax_localplms ids, the stored set of the oldest covisible keyframe joins it (a
+    // keyframe that left the map: the next older one that is there, :485-488).  Returns whether that branch was taken.
+    // Static so that a bare MapManager (tests) can run it too; ov2_map_local_ids_batch is its mirror form.
+    static bool extendLocalMap(MapManager &map, Frame &frame, size_t nmax_localplms);
     // the ids of a job for the mirror path: kp_lmid / grid as assembleMatchToMap lists them, cand_lmid = the local set as it iterates
     static void assembleMatchIds(const Frame &frame, const std::unordered_set<int> &set_local_lmids, MatchJob &job);
     std::vector<SlamStats> stats_;

@@ -182,6 +182,11 @@ def lib():
                                             ip, ip, ip]
         L.ov2h_match_local_maps_mirror.argtypes = L.ov2h_match_local_maps.argtypes
         L.ov2h_map_enable_match_columns.argtypes = [C.c_void_p]
+        L.ov2h_update_frame_covisibility.argtypes = [C.c_void_p, C.c_int]
+        L.ov2h_extend_local_map.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ov2h_frame_local_ids.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip]
+        L.ov2h_frame_set_local_ids.argtypes = [C.c_void_p, C.c_int, C.c_int, ip]
+        L.ov2h_frame_cov_map.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, ip]
         _lib = L
     return _lib
 
@@ -331,6 +336,41 @@ class HostMap:
     def remove_keyframe(self, kfid):
         """MapManager::removeKeyframe"""
         assert lib().ov2h_map_remove_keyframe(self.h, int(kfid)) == 0
+
+    def update_frame_covisibility(self, kfid):
+        """MapManager::updateFrameCovisibility on keyframe kfid (no GPU context): returns its Frame::map_covkfs_ as
+        {covisible kfid: score}; the keyframe's local id set is updated by the store rule (local_ids reads it)"""
+        L = lib()
+        if L.ov2h_update_frame_covisibility(self.h, int(kfid)) != 0:
+            raise RuntimeError(f"keyframe {kfid} is not in the map")
+        ip, n = C.POINTER(C.c_int), C.c_int()
+        assert L.ov2h_frame_cov_map(self.h, int(kfid), 0, None, None, C.byref(n)) == 0
+        k, s = np.zeros(max(n.value, 1), np.int32), np.zeros(max(n.value, 1), np.int32)
+        assert L.ov2h_frame_cov_map(self.h, int(kfid), n.value, k.ctypes.data_as(ip), s.ctypes.data_as(ip), C.byref(n)) == 0
+        return dict(zip(k[:n.value].tolist(), s[:n.value].tolist()))
+
+    def extend_local_map(self, kfid, nmax_local):
+        """the set assembly of Mapper::matchingToLocalMap on keyframe kfid (SlamManager::extendLocalMap, no GPU context):
+        True when the extension branch was taken"""
+        rc = lib().ov2h_extend_local_map(self.h, int(kfid), int(nmax_local))
+        if rc < 0:
+            raise RuntimeError(f"ov2h_extend_local_map: status {rc}")
+        return bool(rc)
+
+    def local_ids(self, kfid):
+        """Frame::set_local_mapids_ of keyframe kfid, in its own iteration order"""
+        L, ip, n = lib(), C.POINTER(C.c_int), C.c_int()
+        if L.ov2h_frame_local_ids(self.h, int(kfid), 0, None, C.byref(n)) != 0:
+            raise RuntimeError(f"keyframe {kfid} is not in the map")
+        out = np.zeros(max(n.value, 1), np.int32)
+        assert L.ov2h_frame_local_ids(self.h, int(kfid), n.value, out.ctypes.data_as(ip), C.byref(n)) == 0
+        return out[:n.value].tolist()
+
+    def set_local_ids(self, kfid, ids):
+        """Frame::set_local_mapids_ of keyframe kfid becomes `ids`"""
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        if lib().ov2h_frame_set_local_ids(self.h, int(kfid), len(a), a.ctypes.data_as(C.POINTER(C.c_int))) != 0:
+            raise RuntimeError(f"keyframe {kfid} is not in the map")
 
     def set_cur_frame(self, kfid):
         """MapManager::pcurframe_ becomes a Frame of its own with keyframe kfid's id, pose and keypoints (None: no current
@@ -1038,9 +1078,10 @@ class LoopMap:
             v = s["kps"][k]
             lm, uv = np.ascontiguousarray(v["lmid"], np.int32), np.ascontiguousarray(v["uv"], np.float32)
             kp3d = np.ascontiguousarray(v["kp3d"], np.uint8)
+            lm3d = np.ascontiguousarray(v.get("lm3d", kp3d), np.uint8)   # MapPoint::is3d_ where it differs from the keypoint's flag
             xyz = np.ascontiguousarray(v["xyz"], np.float64) if "xyz" in v else np.zeros((len(lm), 3))   # world points, where the scene has them
             assert L.ov2h_map_add_kps(self.h, int(k), len(lm), lm.ctypes.data_as(ip), uv.ctypes.data_as(fp), kp3d.ctypes.data_as(u8),
-                                      kp3d.ctypes.data_as(u8), _dp(xyz)) == 0
+                                      lm3d.ctypes.data_as(u8), _dp(xyz)) == 0
         for l, d in s["desc"].items():
             d = np.ascontiguousarray(d, np.uint8)
             kfid = min(k for k in s["kfids"] if l in s["kps"][k]["lmid"])
@@ -1257,6 +1298,13 @@ class LoopMap:
     loose_ba = HostMap.loose_ba
     pose = HostMap.pose
     landmark = HostMap.landmark
+    remove_obs = HostMap.remove_obs
+    remove_landmark = HostMap.remove_landmark
+    remove_keyframe = HostMap.remove_keyframe
+    update_frame_covisibility = HostMap.update_frame_covisibility
+    extend_local_map = HostMap.extend_local_map
+    local_ids = HostMap.local_ids
+    set_local_ids = HostMap.set_local_ids
 
     def merge_points(self, prevlmid, newlmid):
         """MapManager::mergeMapPoints"""
