@@ -970,7 +970,9 @@ ov2_status ov2_map_local_ba_setup_batch(ov2_ctx *ctx, int B, ov2_map *const *map
  *  - ov2_map_add_keyframe: new keyframes, and rows appended to a keyframe already in the map (matchToMap / merges) --
  *    within the capacities,
  *  - ov2_map_remove_obs, ov2_map_set_obs_stereo, ov2_map_remove_landmarks, ov2_map_set_landmarks (isobs_ flips),
- *  - ov2_map_triangulate_temporal_batch (below): landmarks it turns 3D, observations of its new keyframe it removes.
+ *  - ov2_map_triangulate_temporal_batch (below): landmarks it turns 3D, observations of its new keyframe it removes,
+ *  - ov2_map_set_obs_stereo_batch_dev and ov2_map_triangulate_stereo_batch (below): stereo flags and right pixels set on the
+ *    rows of a keyframe, landmarks turned 3D, stereo flags of its new keyframe cleared.
  * The observers of every landmark of the window, its oldest observer (MapPoint::kfid_; with inverse depth: the keyframe
  * whose solved pose and pixel turn rho into the world point, :822-838), isobs_ and liveness are read from the tables at
  * the update; only the set-up's rows are checked for flagged blocks, and a row that died since is neither removed again
@@ -1027,6 +1029,64 @@ typedef struct ov2_map_temporal {
 ov2_status ov2_map_triangulate_temporal_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf,
                                               const double *calib_l /* B x 4 */, int stereo, float max_reproj_err,
                                               ov2_map_temporal *out /* B, or NULL */);
+
+/* The Frame::updateKeypointStereo loop that ends MapManager::stereoMatching (src/map_manager.cpp:583-604, src/frame.cpp:405-433)
+ * on the rows of keyframe kfid[b] of B map mirrors, from DEVICE arrays laid out as ov2_stereo_matching_dev leaves them:
+ * n[b] entries (host count) of d_lmid[b] (the caller's id list), d_status[b] (the matcher's status bytes) and d_rxy[b] (its
+ * RAW right pixels, float x 2).  For every entry with status != 0 the live row (kfid[b], lmid) gets its stereo flag and
+ * runpx = (double) of the float pair ov2_cam_undistort(right_cam[b], rxy) returns (right_cam NULL or model 0: identity) -- the
+ * bits the host computes, so the table is bitwise what ov2_map_set_obs_stereo makes of the same entries with the undistortion
+ * done on the host.  An entry with status 0 leaves its row as it is (the reference does not call updateKeypointStereo for it);
+ * an entry without a live row is passed over, as ov2_map_set_obs_stereo passes it over; an lmid outside [0, capacity) is passed
+ * over and indexes nothing (the list is device-resident: the host cannot validate it); of several entries that name one
+ * landmark the last counts, as in a loop over the list.
+ * map = blockIdx.y of every launch, three launches whatever B, NO synchronisation: the call is asynchronous and the arrays
+ * must stay valid until the stream has passed it.  The scratch is the stereo stage's own; the last set-up of a map stays
+ * updatable (see the list of edits allowed between set-up and update above).
+ * Refused with OV2_ERR_INVALID, tables untouched: kfid[b] not alive in map b, a map listed twice, n[b] < 0, a NULL list with
+ * n[b] > 0. */
+ov2_status ov2_map_set_obs_stereo_batch_dev(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *kfid, const int32_t *n,
+                                            const int32_t *const *d_lmid, const uint8_t *const *d_status,
+                                            const float *const *d_rxy, const ov2_cam_model *right_cam /* B, or NULL */);
+
+/* Mapper::triangulateStereo (src/mapper.cpp:346-461, called at :85-104) on the tables of B map mirrors, one SLAM instance
+ * each: the stereo keypoints of keyframe newkf[b] that have no 3D point yet -- live rows (newkf, l) that carry the stereo flag
+ * and whose landmark is OV2_LM_ALIVE with neither OV2_LM_3D nor OV2_LM_KP3D -- are triangulated between the two cameras:
+ *  - bearings ((u-cx)/fx, (v-cy)/fy, 1) normalised from the rows' unpx / runpx (held as float, as Frame::computeKeypoint and
+ *    Frame::updateKeypointStereo keep them) with Kl for the left and Kr for the right view; then the arithmetic of
+ *    ov2_triangulate_pairs in its order with T_ab = Tlr: OV2_TRI_MIDPOINT, or with rig.rectified the disparity form
+ *    (OV2_TRI_RECTIFIED, :410-422: negative-disparity exit, depth kept as float), depth gate 0.1 in both views, float
+ *    reprojection distances against max_reproj_err, Twc(newkf) * X;
+ *  - OV2_TRI_OK: lm_xyz = world point, lm_state |= OV2_LM_3D | OV2_LM_KP3D (MapManager::updateMapPoint, :450);
+ *    anything else: the row loses its stereo flag, runpx stays (Frame::removeStereoKeypointById, :414, :431, :443).
+ * Rows of other keyframes are never touched, no observation dies and no landmark is removed.
+ * Deviations from the reference: it selects by Keypoint::is3d_ alone (:383); the mirror keeps ONE keypoint flag per landmark
+ * (OV2_LM_KP3D) and asks for a 2D map point too, the rule of the temporal stage above -- a 2D keypoint of a 3D map point,
+ * which MapManager::updateMapPoint would only move, is not offered; an observation of a dead landmark is not live in the
+ * mirror (obs_live) and is not selected; cameras without distortion past the intake.  The reference's gates in front of the
+ * call (nb2dkps_ > 0 && nb_stereo_kps_ > 0, :85-104) need no counterpart: a map with no such row gives a zero header.
+ * One lane per observation row, map = blockIdx.y, sizes come from device memory, two launches whatever B.  The scratch and
+ * the lists are the stage's own: the last set-up of a map and what its ov2_map_local_ba_update_batch reads stay as they are.
+ * Refused with OV2_ERR_INVALID, tables untouched: newkf[b] not alive in map b, a map listed twice, rig == NULL.
+ * out == NULL: fully asynchronous.  out != NULL: one synchronisation for the B headers; the lists are DEVICE arrays of the
+ * map, valid until its next call of this function (or a growth of its tables), order arbitrary.  The host replays
+ * MapPoint::invdepth_ / Frame::nb_stereo_kps_ from them. */
+typedef struct ov2_stereo_rig {      /* per map */
+    double Kl[4], Kr[4];             /* fx fy cx cy */
+    double Tlr[7];                   /* right camera in the left frame (CameraCalibration::Tc0ci_), t then qx qy qz qw */
+    int32_t rectified;               /* bdo_stereo_rect_: the disparity form (:410-422) instead of the mid-point method */
+} ov2_stereo_rig;
+typedef struct ov2_map_stereo_tri {
+    int32_t n_selected, n_good, n_demoted;
+    const int32_t *good_lmid;        /* n_good: MapManager::updateMapPoint(lmid, good_wpt, good_invdepth) */
+    const double *good_wpt;          /* n_good x 3 */
+    const double *good_invdepth;     /* n_good: 1 / left_pt.z */
+    const int32_t *demoted_lmid;     /* n_demoted: Frame::removeStereoKeypointById(lmid) on keyframe newkf */
+    const uint8_t *demoted_why;      /* n_demoted: OV2_TRI_BEHIND / _REPROJ / _NEG_DISP */
+} ov2_map_stereo_tri;
+ov2_status ov2_map_triangulate_stereo_batch(ov2_ctx *ctx, int B, ov2_map *const *maps, const int32_t *newkf,
+                                            const ov2_stereo_rig *rig /* B */, float max_reproj_err,
+                                            ov2_map_stereo_tri *out /* B, or NULL */);
 
 /* Estimator::mapFiltering (src/estimator.cpp:101-183) with MapManager::removeKeyframe (src/map_manager.cpp:885-919) and
  * MapPoint::isBad (src/map_point.cpp:215-234) on the tables of B map mirrors, one SLAM instance each, as they are at the

@@ -129,6 +129,8 @@ SIGNATURES = {
     "ov2_map_local_ba_setup_batch": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ov2_map_local_ba_update_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
     "ov2_map_triangulate_temporal_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_float, vp]),
+    "ov2_map_set_obs_stereo_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "ov2_map_triangulate_stereo_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_float, vp]),
     "ov2_map_filter_keyframes_batch": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_float, vp]),
     "ov2_map_enable_local_sets": (C.c_int, [vp, C.c_int]),
     "ov2_map_set_local_set": (C.c_int, [vp, C.c_int, C.c_int, vp]),

@@ -15,6 +15,7 @@
 #include <new>
 #include <vector>
 
+#include "ov2_cam.h"
 #include "ov2_internal.h"
 #include "ov2_se3.h"
 #include "ov2_wave.h"
@@ -58,6 +59,12 @@ struct ov2_map {
     int *tt_nobs, *tt_old, *tt_nrow;                                // [max_lm] observers, ANCH_TOP - oldest observer, row of the new keyframe + 1
     int *tt_int;                                                    // [3 max_lm] row of the oldest observer | good_lmid | removed_lmid
     double *tt_dbl;                                                 // [4 max_lm] good_wpt (x3) | good_invdepth
+    // ov2_map_triangulate_stereo_batch / ov2_map_set_obs_stereo_batch_dev: scratch and output lists of their own as well
+    unsigned char *ts_zero; size_t ts_zero_bytes;                   // hdr (MH_N ints) | ts_mark: the stage clears the header, the intake both
+    int *ts_mark;                                                   // [max_lm] entry of the intake's list + 1 (the last one that names the landmark)
+    int *ts_int;                                                    // [2 max_lm] good_lmid | demoted_lmid
+    double *ts_dbl;                                                 // [4 max_lm] good_wpt (x3) | good_invdepth
+    unsigned char *ts_why;                                          // [max_lm] demoted_why
     // host copy of kf_state (which keyframes live), so that a call can refuse a dead keyframe without a synchronisation
     unsigned char *kf_alive_h, *snap_kf_alive_h;
     // ov2_map_filter_keyframes_batch: scratch of its own as well
@@ -236,6 +243,15 @@ struct map_job {
     // temporal triangulation (hdr / zero_blk point at the stage's own block in its job records)
     int *tt_nobs, *tt_old, *tt_nrow, *tt_arow, *tt_good_lmid, *tt_rm_lmid;
     double *tt_good_wpt, *tt_good_inv;
+    // stereo triangulation and the intake of the matcher's verdicts (hdr / zero_blk point at the stage's own block in its job records)
+    double st_Kr[4], st_Tlr[7]; int st_rect;     // the rig: K holds the left intrinsics, these the right ones, Tlr and bdo_stereo_rect_
+    int *ts_mark, *ts_good_lmid, *ts_dem_lmid;
+    double *ts_good_wpt, *ts_good_inv;
+    unsigned char *ts_why;
+    double *obs_ruv_w;                           // writable twin of obs_ruv (the intake)
+    int si_n;                                    // the intake's list of this map: entries, ids, status bytes, raw right pixels
+    const int *si_lmid; const unsigned char *si_status; const float *si_rxy;
+    ov2_cam_model si_cam;                        // the right camera's lens model (model 0: identity)
     // keyframe filter (hdr / zero_blk point at the stage's own block in its job records; hdr_out is followed by the removed list)
     int fl_active;                               // 0: gated map (ratio >= 1 or newkf < 20), zero header and no work
     int *fl_nobs, *fl_cov, *fl_n3d, *fl_cnt, *fl_fill, *fl_start, *fl_rows, *fl_unset;
@@ -1030,6 +1046,97 @@ __global__ __launch_bounds__(256) void mt_tri_kernel(const map_job *__restrict__
     if (rm) {     // MapManager::removeMapPointObs(lmid, newkf)
         j.obs_flag_w[nr - 1] = 0;
         j.tt_rm_lmid[s_base[1] + rr] = l;
+    }
+}
+
+// ---- Mapper::triangulateStereo (src/mapper.cpp:346-461) on the tables ------------------------------------------------
+// The intake first: the Frame::updateKeypointStereo loop that ends MapManager::stereoMatching (src/map_manager.cpp:583-604)
+// from the matcher's device arrays.  Scatter: the landmark remembers the last entry that names it with a non-zero status
+// (atomicMax: list order decides, as it does in map_edit_obs_kernel); an id outside [0, max_lm) indexes nothing.
+__global__ __launch_bounds__(256) void si_scatter_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= j.si_n || !j.si_status[i]) return;
+    const int l = j.si_lmid[i];
+    if (l < 0 || l >= j.M.max_lm) return;
+    atomicMax(&j.ts_mark[l], i + 1);
+}
+
+// row scan: the live row (kfid, l) of a marked landmark takes the flag and the undistorted right pixel, held as the double of
+// the float Frame::updateKeypointStereo keeps (src/frame.cpp:405-433)
+__global__ __launch_bounds__(256) void si_rows_kernel(const map_job *__restrict__ J)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= M.n_obs || !(M.obs_flag[i] & OBS_ALIVE) || M.obs_kf[i] != j.newkf) return;
+    const int l = M.obs_lm[i];
+    const int e = (l >= 0 && l < M.max_lm) ? j.ts_mark[l] : 0;
+    if (!e) return;
+    float ru, rv;
+    ov2_cam_undistort(j.si_cam, j.si_rxy[2 * (size_t)(e - 1)], j.si_rxy[2 * (size_t)(e - 1) + 1], ru, rv);
+    j.obs_flag_w[i] = M.obs_flag[i] | OBS_STEREO;
+    j.obs_ruv_w[2 * (size_t)i] = (double)ru; j.obs_ruv_w[2 * (size_t)i + 1] = (double)rv;
+}
+
+// Header of the stage (its own block, cleared per call): what ov2_map_stereo_tri reports.
+enum { SH_SELECTED = 0, SH_GOOD, SH_DEMOTED };
+
+// one lane per observation row: the stereo rows of the new keyframe whose landmark is still 2D (:383), tri_kernel's
+// arithmetic in its order (tri_pair.h) and the bookkeeping of its verdict (:413-450).  One live row per (keyframe, landmark):
+// every landmark and every row is read and written by one lane only.
+__global__ __launch_bounds__(256) void mst_tri_kernel(const map_job *__restrict__ J, float max_err)
+{
+    const map_job &j = J[blockIdx.y];
+    const map_view &M = j.M;
+    if ((int)blockIdx.x * 256 >= M.n_obs) return;   // uniform per workgroup
+    __shared__ int s_cnt[3], s_base[2];
+    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int kf = -1, l = 0;
+    const bool sel = i < M.n_obs && obs_live(M, i, kf, l) && kf == j.newkf && (M.obs_flag[i] & OBS_STEREO) && lm_is_2d(M, l);
+    int st = OV2_TRI_OK;
+    double wpt[3] = {0., 0., 0.}, invdepth = 0.;
+    if (sel) {
+        float ua, va, ub, vb;
+        double f1[3], f2[3], f2u[3], R[9], X[3];
+        bearing_of(j.K, M.obs_uv + 2 * (size_t)i, ua, va, f1);
+        bearing_of(j.st_Kr, M.obs_ruv + 2 * (size_t)i, ub, vb, f2);
+        ov2se3::tri_quat_R(j.st_Tlr, R);
+        ov2tri::rotate(R, f2, f2u);
+        bool have = true;
+        if (j.st_rect) have = ov2tri::rectified(j.st_Tlr, j.K, ua, va, ub, X);   // :410-422
+        else ov2tri::midpoint(j.st_Tlr, f1, f2u, X);                             // :424
+        st = have ? ov2tri::gates(j.st_Tlr, R, X, j.K, j.st_Kr, ua, va, ub, vb, max_err) : OV2_TRI_NEG_DISP;
+        if (st == OV2_TRI_OK) {
+            ov2se3::tri_apply(M.kf_pose + 7 * (size_t)j.newkf, X, wpt);          // Frame::projCamToWorld (:448)
+            invdepth = 1. / X[2];
+        }
+    }
+    const bool good = sel && st == OV2_TRI_OK, dem = sel && st != OV2_TRI_OK;
+    if (sel) atomicAdd(&s_cnt[SH_SELECTED], 1);
+    const int rg = good ? atomicAdd(&s_cnt[SH_GOOD], 1) : 0, rd = dem ? atomicAdd(&s_cnt[SH_DEMOTED], 1) : 0;
+    __syncthreads();
+    if (threadIdx.x < 3 && s_cnt[threadIdx.x]) {   // one global atomic per workgroup and counter
+        const int base = atomicAdd(&j.hdr[threadIdx.x], s_cnt[threadIdx.x]);
+        if (threadIdx.x >= SH_GOOD) s_base[threadIdx.x - SH_GOOD] = base;
+    }
+    __syncthreads();
+    if (good) {   // MapManager::updateMapPoint (:450): the point turns 3D with its keypoints
+        j.lm_xyz_w[3 * (size_t)l] = wpt[0]; j.lm_xyz_w[3 * (size_t)l + 1] = wpt[1]; j.lm_xyz_w[3 * (size_t)l + 2] = wpt[2];
+        j.lm_state_w[l] = M.lm_state[l] | OV2_LM_3D | OV2_LM_KP3D;
+        const int o = s_base[0] + rg;
+        if (o < M.max_lm) {   // always, with one live row per (keyframe, landmark); the lists hold max_lm entries
+            j.ts_good_lmid[o] = l; j.ts_good_inv[o] = invdepth;
+            j.ts_good_wpt[3 * (size_t)o] = wpt[0]; j.ts_good_wpt[3 * (size_t)o + 1] = wpt[1]; j.ts_good_wpt[3 * (size_t)o + 2] = wpt[2];
+        }
+    }
+    if (dem) {    // Frame::removeStereoKeypointById (:414, :431, :443): the right pixel stays where it is
+        j.obs_flag_w[i] = M.obs_flag[i] & ~OBS_STEREO;
+        const int o = s_base[1] + rd;
+        if (o < M.max_lm) { j.ts_dem_lmid[o] = l; j.ts_why[o] = (unsigned char)st; }
     }
 }
 
@@ -2397,7 +2504,7 @@ map_job job_of(const ov2_map *m, int newkf, int cur_kfid)
     j.snap_kf_pose = m->snap_kf_pose; j.snap_lm_xyz = m->snap_lm_xyz; j.snap_kf_state = m->snap_kf_state;
     j.snap_lm_state = m->snap_lm_state; j.snap_obs_flag = m->snap_obs_flag;
     j.snap_kf = m->snap_kf; j.snap_lm = m->snap_lm; j.snap_obs = m->snap_obs;
-    j.obs_lm_w = m->obs_lm;
+    j.obs_lm_w = m->obs_lm; j.obs_ruv_w = m->obs_ruv;
     j.obs_desc_w = reinterpret_cast<uint4 *>(m->obs_desc); j.obs_hasdesc_w = m->obs_hasdesc; j.mg_srow = m->mg_srow;
     return j;
 }
@@ -2511,6 +2618,9 @@ static ov2_status alloc_tables(ov2_map *m)
     if (s == OV2_OK) {
         m->tt_nobs = reinterpret_cast<int *>(m->tt_zero) + MH_N; m->tt_old = m->tt_nobs + L; m->tt_nrow = m->tt_old + L;
     }
+    m->ts_zero_bytes = (sizeof(int) * (MH_N + L) + 15) & ~(size_t)15;
+    A(ts_zero, m->ts_zero_bytes); A(ts_int, 2 * L); A(ts_dbl, 4 * L); A(ts_why, L);
+    if (s == OV2_OK) m->ts_mark = reinterpret_cast<int *>(m->ts_zero) + MH_N;
     m->fl_zero_bytes = (sizeof(int) * (MH_N + L + 4 * K) + L + 15) & ~(size_t)15;
     A(fl_zero, m->fl_zero_bytes); A(fl_start, K); A(fl_rows, N); A(fl_unset, L);
     if (s == OV2_OK) {
@@ -2598,7 +2708,8 @@ static void free_capacity_arrays(ov2_map *m)
     free_local_sets(m);
     void *dev[] = {m->kf_pose, m->kf_state, m->lm_xyz, m->lm_state, m->obs_kf, m->obs_lm, m->obs_scale, m->obs_uv, m->obs_ruv,
                    m->obs_flag, m->zero_blk, m->kf_idx, m->lm_flag, m->lm_pack, m->lm_pidx, m->obs_cnt, m->obs_off, m->blk,
-                   m->tt_zero, m->tt_int, m->tt_dbl, m->fl_zero, m->fl_start, m->fl_rows, m->fl_unset,
+                   m->tt_zero, m->tt_int, m->tt_dbl, m->ts_zero, m->ts_int, m->ts_dbl, m->ts_why,
+                   m->fl_zero, m->fl_start, m->fl_rows, m->fl_unset,
                    m->mg_zero, m->mg_start, m->mg_rows};
     for (void *p : dev) if (p) (void)hipFree(p);
 }
@@ -2616,6 +2727,7 @@ static ov2_status ensure_capacity(ov2_map *m, int need_kf, int need_lm, int need
     m->obs_kf = m->obs_lm = m->obs_scale = nullptr; m->obs_uv = m->obs_ruv = nullptr; m->obs_flag = nullptr;
     m->zero_blk = nullptr; m->kf_idx = m->lm_flag = m->obs_cnt = m->obs_off = m->blk = nullptr; m->lm_pack = m->lm_pidx = nullptr;
     m->tt_zero = nullptr; m->tt_int = nullptr; m->tt_dbl = nullptr;
+    m->ts_zero = nullptr; m->ts_int = nullptr; m->ts_dbl = nullptr; m->ts_why = nullptr;
     m->fl_zero = nullptr; m->fl_start = m->fl_rows = m->fl_unset = nullptr;
     m->mg_zero = nullptr; m->mg_start = m->mg_rows = nullptr;
     m->obs_px = nullptr; m->obs_desc = m->obs_hasdesc = nullptr; m->mg_srow = nullptr; m->gt_seen_h = nullptr;
@@ -3677,6 +3789,95 @@ extern "C" ov2_status ov2_map_triangulate_temporal_batch(ov2_ctx *c, int B, ov2_
         out[b].n_selected = H[TH_SELECTED]; out[b].n_candidates = H[TH_CANDIDATES]; out[b].n_good = H[TH_GOOD]; out[b].n_removed = H[TH_REMOVED];
         out[b].good_lmid = m->tt_int + m->max_lm; out[b].removed_lmid = m->tt_int + 2 * (size_t)m->max_lm;
         out[b].good_wpt = m->tt_dbl; out[b].good_invdepth = m->tt_dbl + 3 * (size_t)m->max_lm;
+    }
+    return OV2_OK;
+}
+
+// ---- the stereo matcher's verdicts onto the rows of B maps: three launches, no synchronisation ---------------------------
+extern "C" ov2_status ov2_map_set_obs_stereo_batch_dev(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *kfid, const int32_t *n,
+                                                       const int32_t *const *d_lmid, const uint8_t *const *d_status,
+                                                       const float *const *d_rxy, const ov2_cam_model *right_cam)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps || !kfid || !n || !d_lmid || !d_status || !d_rxy)
+        return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_set_obs_stereo_batch_dev: null argument");
+    ov2_status s;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
+        if ((s = batch_kf_alive(c, m, kfid[b], b)) != OV2_OK) return s;
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
+        if (n[b] < 0) return ov2_set_err(c, OV2_ERR_INVALID, "map %d: a list of %d entries", b, n[b]);
+        if (n[b] > 0 && (!d_lmid[b] || !d_status[b] || !d_rxy[b])) return ov2_set_err(c, OV2_ERR_INVALID, "map %d: a null list of %d entries", b, n[b]);
+    }
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    job_table JT;
+    if ((s = JT.begin(c, B)) != OV2_OK) return s;
+    int nmax = 0, emax = 0; unsigned zmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        map_job j = job_of(m, kfid[b], -1);
+        stage_block(j, m->ts_zero, m->ts_zero_bytes);
+        j.ts_mark = m->ts_mark;
+        j.si_n = n[b]; j.si_lmid = d_lmid[b]; j.si_status = d_status[b]; j.si_rxy = d_rxy[b];
+        j.si_cam = ov2_cam_normalised(right_cam ? right_cam + b : nullptr);
+        JT.set(b, j);
+        nmax = std::max(nmax, m->n_obs); emax = std::max(emax, n[b]); zmax = std::max(zmax, j.zero_vec16);
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), gE((std::max(emax, 1) + 255) / 256, B), b256(256);
+    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(std::min(64u, (zmax + 255) / 256), B), b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, si_scatter_kernel, gE, b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, si_rows_kernel, gN, b256, 0, st, JT.dev);
+    return OV2_OK;
+}
+
+// ---- stereo triangulation of B maps: two launches, no synchronisation unless the lists are asked for ---------------------
+extern "C" ov2_status ov2_map_triangulate_stereo_batch(ov2_ctx *c, int B, ov2_map *const *maps, const int32_t *newkf,
+                                                       const ov2_stereo_rig *rig, float max_reproj_err, ov2_map_stereo_tri *out)
+{
+    if (!c) return OV2_ERR_INVALID;
+    if (B == 0) return OV2_OK;
+    if (B < 0 || !maps || !newkf || !rig) return ov2_set_err(c, OV2_ERR_INVALID, "ov2_map_triangulate_stereo_batch: null argument");
+    ov2_status s;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        if ((s = batch_map_ok(c, m, b)) != OV2_OK) return s;
+        if ((s = batch_kf_alive(c, m, newkf[b], b)) != OV2_OK) return s;
+        if ((s = batch_map_once(c, maps, b)) != OV2_OK) return s;
+    }
+    OV2_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    job_table JT;
+    if ((s = JT.begin(c, B)) != OV2_OK) return s;
+    int nmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        map_job j = job_of(m, newkf[b], -1);
+        stage_block(j, m->ts_zero, MH_N * sizeof(int));   // the header alone: the intake's marks are of no use here
+        j.ts_good_lmid = m->ts_int; j.ts_dem_lmid = m->ts_int + m->max_lm; j.ts_why = m->ts_why;
+        j.ts_good_wpt = m->ts_dbl; j.ts_good_inv = m->ts_dbl + 3 * (size_t)m->max_lm;
+        for (int k = 0; k < 4; ++k) { j.K[k] = rig[b].Kl[k]; j.st_Kr[k] = rig[b].Kr[k]; }
+        for (int k = 0; k < 7; ++k) j.st_Tlr[k] = rig[b].Tlr[k];
+        j.st_rect = rig[b].rectified ? 1 : 0;
+        JT.set(b, j);
+        nmax = std::max(nmax, m->n_obs);
+    }
+    if ((s = JT.upload()) != OV2_OK) return s;
+    const dim3 gN((std::max(nmax, 1) + 255) / 256, B), b256(256);
+    OV2_LAUNCH(c, OV2_K_MAP, mb_zero_kernel, dim3(1, B), b256, 0, st, JT.dev);
+    OV2_LAUNCH(c, OV2_K_MAP, mst_tri_kernel, gN, b256, 0, st, JT.dev, max_reproj_err);
+    if (!out) return OV2_OK;   // asynchronous: the caller did not ask for what to replay
+    OV2_LAUNCH(c, OV2_K_MAP, mb_hdr_gather_kernel, dim3(1, B), dim3(64), 0, st, JT.dev);
+    if ((s = JT.fetch_headers()) != OV2_OK) return s;
+    for (int b = 0; b < B; ++b) {
+        const ov2_map *m = maps[b];
+        const int *H = JT.hdr_host + (size_t)b * MH_N;
+        out[b].n_selected = H[SH_SELECTED]; out[b].n_good = std::min(H[SH_GOOD], m->max_lm); out[b].n_demoted = std::min(H[SH_DEMOTED], m->max_lm);
+        out[b].good_lmid = m->ts_int; out[b].good_wpt = m->ts_dbl; out[b].good_invdepth = m->ts_dbl + 3 * (size_t)m->max_lm;
+        out[b].demoted_lmid = m->ts_int + m->max_lm; out[b].demoted_why = m->ts_why;
     }
     return OV2_OK;
 }

@@ -45,18 +45,12 @@ __global__ __launch_bounds__(256) void tri_kernel(tri_args A)
     if (A.parallax) A.parallax[i] = parallax_px(A.Kb, f2u, ua, va);
     double X[3];
     if (A.method == OV2_TRI_RECTIFIED) {
-        const float disp = ua - ub;
-        if (disp < 0.f) {
+        if (!rectified(T, A.Ka, ua, va, ub, X)) {
             A.status[i] = OV2_TRI_NEG_DISP;
             A.pt_a[3 * i] = A.pt_a[3 * i + 1] = A.pt_a[3 * i + 2] = 0.0;
             if (A.wpt) A.wpt[3 * i] = A.wpt[3 * i + 1] = A.wpt[3 * i + 2] = 0.0;
             return;
         }
-        const double base = __dsqrt_rn(T[0] * T[0] + T[1] * T[1] + T[2] * T[2]);
-        const float z = (float)(A.Ka[0] * base / fabs((double)disp));
-        X[0] = (double)z * ((double)ua / A.Ka[0] - A.Ka[2] / A.Ka[0]);
-        X[1] = (double)z * ((double)va / A.Ka[1] - A.Ka[3] / A.Ka[1]);
-        X[2] = (double)z;
     } else {
         midpoint(T, f1, f2u, X);
     }

@@ -60,6 +60,20 @@ __device__ __forceinline__ void midpoint(const double *T, const double f1[3], co
     X[2] = (l0 * f1[2] + (T[2] + l1 * f2u[2])) / 2.;
 }
 
+// the rectified disparity form (src/mapper.cpp:410-422): depth fx * |t| / |disp| kept as the float the reference holds, the
+// left pixel back-projected with iK.  false: negative disparity (:413-416), X untouched
+__device__ __forceinline__ bool rectified(const double *T, const double Ka[4], float ua, float va, float ub, double X[3])
+{
+    const float disp = ua - ub;
+    if (disp < 0.f) return false;
+    const double base = __dsqrt_rn(T[0] * T[0] + T[1] * T[1] + T[2] * T[2]);
+    const float z = (float)(Ka[0] * base / fabs((double)disp));
+    X[0] = (double)z * ((double)ua / Ka[0] - Ka[2] / Ka[0]);
+    X[1] = (double)z * ((double)va / Ka[1] - Ka[3] / Ka[1]);
+    X[2] = (double)z;
+    return true;
+}
+
 // the mapper's acceptance gates (src/mapper.cpp:307-329, :425-445): depth >= 0.1 in both views, then the float
 // reprojection distances against max_err.  T / R: view b in the frame of view a
 __device__ __forceinline__ int gates(const double *T, const double R[9], const double X[3], const double Ka[4], const double Kb[4],

@@ -30,6 +30,24 @@ class TemporalC(C.Structure):
                 ("good_lmid", C.c_void_p), ("good_wpt", C.c_void_p), ("good_invdepth", C.c_void_p), ("removed_lmid", C.c_void_p)]
 
 
+class StereoRigC(C.Structure):
+    """ov2_stereo_rig"""
+    _fields_ = [("Kl", C.c_double * 4), ("Kr", C.c_double * 4), ("Tlr", C.c_double * 7), ("rectified", C.c_int32)]
+
+    @classmethod
+    def of(cls, m):
+        """the rig of anything with K4 (left), Kr, Tlr, rectified (a synth_stereo_tri map)"""
+        r = cls()
+        r.Kl[:], r.Kr[:], r.Tlr[:], r.rectified = list(m["K4"]), list(m["Kr"]), list(m["Tlr"]), int(m["rectified"])
+        return r
+
+
+class StereoTriC(C.Structure):
+    """ov2_map_stereo_tri"""
+    _fields_ = [("n_selected", C.c_int32), ("n_good", C.c_int32), ("n_demoted", C.c_int32), ("good_lmid", C.c_void_p),
+                ("good_wpt", C.c_void_p), ("good_invdepth", C.c_void_p), ("demoted_lmid", C.c_void_p), ("demoted_why", C.c_void_p)]
+
+
 class FilterC(C.Structure):
     """ov2_map_filter"""
     _fields_ = [("n_candidates", C.c_int32), ("n_removed", C.c_int32), ("n_few3d", C.c_int32), ("n_unset3d", C.c_int32),
@@ -412,6 +430,39 @@ class DeviceMap:
         """ov2_map_triangulate_temporal_batch on this map and `others` in one call; see triangulate_temporal_batch"""
         return triangulate_temporal_batch(self.ctx, [self] + list(others), newkf, calib_l, stereo, max_reproj_err, want_lists)
 
+    @classmethod
+    def from_stereo_tri_map(cls, ctx, m, spare=(8, 8, 64), with_stereo=True):
+        """the mirror of a synth_stereo_tri.make_map dict through the public hooks, rows in the dict's order: dead rows and dead
+        landmarks included (added alive, then removed).  with_stereo=False: no row carries a stereo flag or a right pixel"""
+        dm = cls(ctx, m["n_kf"] + spare[0], m["n_lm"] + spare[1], len(m["obs_kf"]) + spare[2])
+        dm.newkf = int(m["newkf"])
+        seen = np.unique(m["obs_lm"]).astype(np.int32)
+        is3d = m["lm_3d"][seen].astype(bool)
+        st = np.where(is3d, LM_ALIVE | LM_OBS | LM_3D | LM_KP3D, LM_ALIVE | LM_OBS).astype(np.uint8)
+        dm.set_landmarks(seen, np.where(is3d[:, None], m["lm_xyz"][seen], 0.0), st)
+        for k in range(m["n_kf"]):
+            sel = m["obs_kf"] == k
+            on = m["obs_stereo"][sel] if with_stereo else np.zeros(int(sel.sum()), np.uint8)
+            run = np.where(on[:, None] != 0, m["obs_rpx"][sel].astype(np.float64), 0.0)
+            dm.add_keyframe(k, m["poses"][k], m["obs_lm"][sel], m["obs_uv"][sel].astype(np.float64), run, on)
+        dead = m["obs_alive"] == 0
+        if dead.any():
+            dm.remove_obs(m["obs_kf"][dead], m["obs_lm"][dead])
+        gone = (m["lm_alive"][seen] == 0) | ~np.isin(seen, m["obs_lm"][~dead])   # (a landmark whose every row died goes with them)
+        if gone.any():
+            dm.remove_landmarks(seen[gone])
+        return dm
+
+    def set_obs_stereo(self, kfid, lmid, is_stereo, runpx):
+        """ov2_map_set_obs_stereo: flag and undistorted right pixel (float64) of the live rows (kfid[i], lmid[i])"""
+        c = np.ascontiguousarray
+        k, l, s, r = c(kfid, np.int32), c(lmid, np.int32), c(is_stereo, np.uint8), c(runpx, np.float64)
+        _check(self.ctx.h, self.L.ov2_map_set_obs_stereo(self.h, len(k), self._p(k), self._p(l), self._p(s), self._p(r)))
+
+    def triangulate_stereo_batch(self, others=(), newkf=None, rigs=None, max_reproj_err=3.0, want_lists=True):
+        """ov2_map_triangulate_stereo_batch on this map and `others` in one call; see triangulate_stereo_batch"""
+        return triangulate_stereo_batch(self.ctx, [self] + list(others), newkf, rigs, max_reproj_err, want_lists)
+
     def download(self):
         """dict of the tables (host copies)"""
         nk, nl, no = C.c_int(), C.c_int(), C.c_int()
@@ -465,6 +516,56 @@ def triangulate_temporal_batch(ctx, maps, newkf=None, calib_l=None, stereo=True,
         res.append(dict(selected=t.n_selected, candidates=t.n_candidates, good_lmid=gl[o], good_wpt=gw[o], good_invdepth=gi[o],
                         removed_lmid=np.sort(rl)))
     return res
+
+
+def triangulate_stereo_batch(ctx, maps, newkf=None, rigs=None, max_reproj_err=3.0, want_lists=True):
+    """Mapper::triangulateStereo on the tables of the maps (DeviceMap objects or raw ov2_map handles), keyframe newkf[b]
+    (default: each map's newkf) with the rigs (one StereoRigC for all maps, or one per map).  Returns per map dict(selected,
+    good_lmid, good_wpt, good_invdepth, demoted_lmid, demoted_why), the lists sorted by lmid -- or None (want_lists=False:
+    asynchronous)"""
+    B = len(maps)
+    hs = (C.c_void_p * max(B, 1))(*[getattr(m, "h", m) for m in maps])
+    nk = np.ascontiguousarray([m.newkf for m in maps] if newkf is None else newkf, np.int32)
+    rg = None
+    if rigs is not None:
+        rg = (StereoRigC * max(B, 1))(*(list(rigs) if isinstance(rigs, (list, tuple)) else [rigs] * B))
+    out = (StereoTriC * max(B, 1))() if want_lists else None
+    _check(ctx.h, ctx.lib.ov2_map_triangulate_stereo_batch(ctx.h, B, hs, nk.ctypes.data_as(C.c_void_p), rg, float(max_reproj_err), out))
+    if not want_lists:
+        return None
+
+    def fetch(ptr, shape, dt):
+        a = np.zeros(shape, dt)
+        if a.nbytes:
+            _check(ctx.h, ctx.lib.ov2_memcpy_d2h(ctx.h, a.ctypes.data_as(C.c_void_p), ptr, a.nbytes))
+        return a
+    res = []
+    for t in out[:B]:
+        gl, dl = fetch(t.good_lmid, t.n_good, np.int32), fetch(t.demoted_lmid, t.n_demoted, np.int32)
+        gw, gi = fetch(t.good_wpt, (t.n_good, 3), np.float64), fetch(t.good_invdepth, t.n_good, np.float64)
+        dw = fetch(t.demoted_why, t.n_demoted, np.uint8)
+        o, q = np.argsort(gl), np.argsort(dl)
+        res.append(dict(selected=t.n_selected, good_lmid=gl[o], good_wpt=gw[o], good_invdepth=gi[o], demoted_lmid=dl[q],
+                        demoted_why=dw[q]))
+    return res
+
+
+def set_obs_stereo_batch_dev(ctx, maps, kfid, d_lmid, d_status, d_rxy, n=None, right_cam=None):
+    """ov2_map_set_obs_stereo_batch_dev: the stereo matcher's verdicts onto the rows of keyframe kfid[b] of the maps, from
+    device arrays (frontend.DeviceArray, or None with n[b] = 0): d_lmid[b] int32 (n,), d_status[b] uint8 (n,), d_rxy[b] float32
+    (n, 2) raw right pixels.  n: entries per map (default: the length of d_lmid[b]).  right_cam: None, one ba_types.CamModelC for
+    all maps or one per map.  Asynchronous; the arrays must outlive the stream's passage"""
+    B = len(maps)
+    hs = (C.c_void_p * max(B, 1))(*[getattr(m, "h", m) for m in maps])
+    kf = np.ascontiguousarray(kfid, np.int32)
+    nn = np.ascontiguousarray([0 if a is None else a.shape[0] for a in d_lmid] if n is None else n, np.int32)
+    ptrs = [(C.c_void_p * max(B, 1))(*[None if a is None else a.ptr for a in arr]) for arr in (d_lmid, d_status, d_rxy)]
+    cam = None
+    if right_cam is not None:
+        cams = list(right_cam) if isinstance(right_cam, (list, tuple)) else [right_cam] * B
+        cam = (type(cams[0]) * max(B, 1))(*cams)
+    _check(ctx.h, ctx.lib.ov2_map_set_obs_stereo_batch_dev(ctx.h, B, hs, kf.ctypes.data_as(C.c_void_p), nn.ctypes.data_as(C.c_void_p),
+                                                           ptrs[0], ptrs[1], ptrs[2], cam))
 
 
 def filter_keyframes_batch(ctx, maps, newkf=None, nmin_covscore=25, ratio=0.9):

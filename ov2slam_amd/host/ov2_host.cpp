@@ -711,6 +711,7 @@ ov2_status MapManager::attachDevice(ov2_ctx *ctx, int max_kf, int max_lm, int ma
     for (const auto &kv : map_pkfs_)
         if ((s = addKeyframeToDevice(*kv.second)) != OV2_OK) return s;
     dev_lm_dirty_.clear(); dev_pose_dirty_.clear(); dev_rm_kf_.clear(); dev_rm_lm_.clear(); dev_st_kf_.clear(); dev_st_lm_.clear();
+    dev_son_.clear();
     dev_match_cols_ = false; dev_desc_dirty_.clear();   // a fresh mirror has no match columns until enableMatchColumns
     return OV2_OK;
 }
@@ -764,6 +765,20 @@ ov2_status MapManager::flushDevice()
         }
         dev_desc_dirty_.clear();
         if (!kfid.empty() && (s = ov2_map_set_obs_desc(dev_, (int)kfid.size(), kfid.data(), lmid.data(), nullptr, desc.data(), has.data())) != OV2_OK)
+            return s;
+    }
+    if (!dev_son_.empty()) {
+        std::vector<int32_t> kfid, lmid; std::vector<uint8_t> on; std::vector<double> run;
+        for (const auto &e : dev_son_) {
+            auto pkf = getKeyframe(e.first);
+            if (!pkf) continue;
+            const Keypoint kp = pkf->getKeypointById(e.second);
+            if (kp.lmid_ != e.second) continue;   // removed since
+            kfid.push_back(e.first); lmid.push_back(e.second); on.push_back(1);
+            run.push_back(kp.runpx_.x); run.push_back(kp.runpx_.y);
+        }
+        dev_son_.clear();
+        if (!kfid.empty() && (s = ov2_map_set_obs_stereo(dev_, (int)kfid.size(), kfid.data(), lmid.data(), on.data(), run.data())) != OV2_OK)
             return s;
     }
     if (!dev_st_kf_.empty()) {

@@ -210,6 +210,10 @@ public:
     void touchMapPoint(int lmid) { if (dev_) dev_lm_dirty_.push_back(lmid); }
     void touchPose(int kfid) { if (dev_) dev_pose_dirty_.push_back(kfid); }
     void touchStereoOff(int kfid, int lmid) { if (dev_) { dev_st_kf_.push_back(kfid); dev_st_lm_.push_back(lmid); } }
+    // Frame::updateKeypointStereo on a keyframe the mirror already holds: the next flush sets the row's flag and right pixel
+    // (in front of the queued touchStereoOff entries, so a keypoint matched and then demoted ends mono with its pixel kept)
+    void touchStereoOn(int kfid, int lmid) { if (dev_ && dev_kfs_.count(kfid)) dev_son_.emplace_back(kfid, lmid); }
+    std::vector<std::pair<int, int>> dev_son_;
     // Match columns of the mirror (ov2_map_enable_match_columns): after enableMatchColumns, rows go up with Keypoint::px_ and
     // the descriptor their map point holds for the keyframe, and a MapPoint::addDesc is forwarded with the next flush
     // (ov2_map_set_obs_desc) -- whoever calls addDesc on a map point of this map says so with touchDesc.  Without it nothing
@@ -331,6 +335,11 @@ struct TemporalStats {   // Mapper::triangulateTemporal on the last keyframe
     int ran = 0;
     int n_kps = 0, n_candidates = 0, n_good = 0, n_removed = 0;   // 2D keypoints offered, candidates, good, observations removed
     std::vector<int> lmid, branch;                               // per offered keypoint, ids ascending: its TemporalBranch
+};
+
+struct StereoTriStats {   // Mapper::triangulateStereo (src/mapper.cpp:346-461) on one keyframe
+    int n_kps = 0, n_good = 0, n_demoted = 0;   // stereo 2D keypoints offered, landmarks turned 3D, stereo flags cleared
+    std::vector<int> lmid, verdict;             // per offered keypoint, ids ascending: its OV2_TRI_* verdict
 };
 
 struct EpiStats {   // what VisualFrontEnd::epipolar2d2dFiltering did on the last frame

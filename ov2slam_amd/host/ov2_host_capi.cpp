@@ -167,6 +167,49 @@ int ov2h_triangulate_temporal(void *p, void *ctx, int kfid, float max_reproj_err
     return ts.n_kps;
 }
 
+// ---- Mapper::triangulateStereo on a host map ----
+// Frame::updateKeypointStereo(lmid[i], rxy[i]) on keyframe kfid for n keypoints (raw right pixels; the right camera of the map
+// undistorts them); a keyframe the device mirror already holds gets the rows with the next flush
+int ov2h_map_set_kp_stereo(void *p, int kfid, int n, const int *lmid, const float *rxy)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kfid);
+    if (!f || n < 0) return f ? -2 : -1;
+    for (int i = 0; i < n; ++i) {
+        if (!f->isObservingKp(lmid[i])) continue;
+        f->updateKeypointStereo(lmid[i], Point2f{rxy[2 * i], rxy[2 * i + 1]});
+        m->map->touchStereoOn(kfid, lmid[i]);
+    }
+    return 0;
+}
+
+// the right camera of the map: intrinsics, extrinsic (Tc0ci_, t then qx qy qz qw) and SlamParams::bdo_stereo_rect_
+int ov2h_map_set_right_cam(void *p, const double *Kr, const double *T_lr7, int rectified)
+{
+    HostMap *m = (HostMap *)p;
+    m->cr->fx_ = Kr[0]; m->cr->fy_ = Kr[1]; m->cr->cx_ = Kr[2]; m->cr->cy_ = Kr[3];
+    for (int i = 0; i < 7; ++i) m->cr->Tc0ci_.v[i] = T_lr7[i];
+    m->st->bdo_stereo_rect_ = rectified != 0;
+    return 0;
+}
+
+// Mapper::triangulateStereo on keyframe kfid.  lmid / verdict (capacity cap): the keypoints offered, ids ascending, and the
+// OV2_TRI_* verdict of each; stats[3]: stereo 2D keypoints offered, good, demoted.  Returns the number of keypoints offered,
+// or -1 - status
+int ov2h_triangulate_stereo(void *p, void *ctx, int kfid, float max_reproj_err, int cap, int *lmid, int *verdict, double *stats)
+{
+    HostMap *m = (HostMap *)p;
+    auto f = m->map->getKeyframe(kfid);
+    if (!f) return -1 - (int)OV2_ERR_INVALID;
+    m->st->fmax_reproj_err_ = max_reproj_err;
+    StereoTriStats ts;
+    const ov2_status s = SlamManager::triangulateStereo((ov2_ctx *)ctx, *m->map, *m->st, *f, ts);
+    if (s != OV2_OK) return -1 - (int)s;
+    for (int i = 0; i < ts.n_kps && i < cap; ++i) { lmid[i] = ts.lmid[i]; verdict[i] = ts.verdict[i]; }
+    if (stats) { stats[0] = ts.n_kps; stats[1] = ts.n_good; stats[2] = ts.n_demoted; }
+    return ts.n_kps;
+}
+
 // Estimator::mapFiltering on a host map with keyframe newkf as the new keyframe (no GPU context needed; with a device mirror
 // attached the removals reach it through MapManager::removeKeyframe).  removed_kfid (capacity cap): removed ids in order;
 // stats[4]: ran, candidates examined, removed by the nb3dkps_ rule, landmarks whose is3d_ isBad() cleared.  Returns the number

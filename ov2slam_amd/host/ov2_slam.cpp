@@ -679,20 +679,25 @@ ov2_status SlamManager::matchToLocalMaps(ov2_ctx *ctx, std::vector<MatchJob> &jo
     return OV2_OK;
 }
 
-ov2_status SlamManager::triangulateStereo(Frame &frame)
+ov2_status SlamManager::triangulateStereo(ov2_ctx *ctx, MapManager &map, const SlamParams &st, Frame &frame, StereoTriStats &ts,
+                                          bool midpoint_always, bool demote)
 {   // src/mapper.cpp:346-461: the per-keypoint body (triangulation, depth and reprojection gates, world point) is
     // ov2_triangulate_pairs; what stays here is the selection and the bookkeeping of its verdicts
+    ts = StereoTriStats();
     std::vector<Keypoint> vkps;
     for (const auto &kv : frame.mapkps_)
         if (kv.second.is_stereo_ && !kv.second.is3d_) vkps.push_back(kv.second);
     if (vkps.empty()) return OV2_OK;
     std::sort(vkps.begin(), vkps.end(), [](const Keypoint &a, const Keypoint &b) { return a.lmid_ < b.lmid_; });
     const size_t n = vkps.size();
+    ts.n_kps = (int)n;
+    ts.lmid.resize(n); ts.verdict.assign(n, OV2_TRI_OK);
     std::vector<double> bvl(3 * n), bvr(3 * n), pt(3 * n), wpt(3 * n);
     std::vector<float> ul(2 * n), ur(2 * n);
     std::vector<uint8_t> status(n);
     for (size_t i = 0; i < n; ++i) {
         const Keypoint &k = vkps[i];
+        ts.lmid[i] = k.lmid_;
         bvl[3 * i] = k.bv_.x; bvl[3 * i + 1] = k.bv_.y; bvl[3 * i + 2] = k.bv_.z;
         bvr[3 * i] = k.rbv_.x; bvr[3 * i + 1] = k.rbv_.y; bvr[3 * i + 2] = k.rbv_.z;
         ul[2 * i] = k.unpx_.x; ul[2 * i + 1] = k.unpx_.y; ur[2 * i] = k.runpx_.x; ur[2 * i + 1] = k.runpx_.y;
@@ -700,16 +705,18 @@ ov2_status SlamManager::triangulateStereo(Frame &frame)
     const CameraCalibration &cl = *frame.pcalib_leftcam_, &cr = *frame.pcalib_rightcam_;
     const double Kl[4] = {cl.fx_, cl.fy_, cl.cx_, cl.cy_}, Kr[4] = {cr.fx_, cr.fy_, cr.cx_, cr.cy_};
     const SE3 Tlr = cr.Tc0ci_, Twc = frame.getTwc();
-    const int method = (pslamstate_->bdo_stereo_rect_ && !policy_.midpoint_stereo) ? OV2_TRI_RECTIFIED : OV2_TRI_MIDPOINT;
-    const ov2_status s = ov2_triangulate_pairs(ctx_, (int)n, method, 1, Tlr.v.data(), Twc.v.data(), nullptr, bvl.data(), bvr.data(), ul.data(),
-                                               ur.data(), Kl, Kr, pslamstate_->fmax_reproj_err_, pt.data(), wpt.data(), nullptr, status.data());
+    const int method = (st.bdo_stereo_rect_ && !midpoint_always) ? OV2_TRI_RECTIFIED : OV2_TRI_MIDPOINT;
+    const ov2_status s = ov2_triangulate_pairs(ctx, (int)n, method, 1, Tlr.v.data(), Twc.v.data(), nullptr, bvl.data(), bvr.data(), ul.data(),
+                                               ur.data(), Kl, Kr, st.fmax_reproj_err_, pt.data(), wpt.data(), nullptr, status.data());
     if (s != OV2_OK) return s;
     for (size_t i = 0; i < n; ++i) {
-        if (status[i] != OV2_TRI_OK) {
-            if (!policy_.midpoint_stereo) { frame.removeStereoKeypointById(vkps[i].lmid_); pmap_->touchStereoOff(frame.kfid_, vkps[i].lmid_); }
+        ts.verdict[i] = status[i];
+        if (status[i] != OV2_TRI_OK) {   // :413-416, :430-433, :441-445
+            if (demote) { frame.removeStereoKeypointById(vkps[i].lmid_); map.touchStereoOff(frame.kfid_, vkps[i].lmid_); ++ts.n_demoted; }
             continue;
         }
-        pmap_->updateMapPoint(vkps[i].lmid_, Vec3{wpt[3 * i], wpt[3 * i + 1], wpt[3 * i + 2]}, 1. / pt[3 * i + 2]);
+        map.updateMapPoint(vkps[i].lmid_, Vec3{wpt[3 * i], wpt[3 * i + 1], wpt[3 * i + 2]}, 1. / pt[3 * i + 2]);   // :450
+        ++ts.n_good;
     }
     return OV2_OK;
 }

@@ -134,6 +134,13 @@ public:
     // tests hold exact counts recorded without the stage.  Selection and bookkeeping run here, the per-pair arithmetic is one
     // ov2_triangulate_pairs call over all source keyframes.  Static so that a bare MapManager (tests) can run it too.
     static ov2_status triangulateTemporal(ov2_ctx *ctx, MapManager &map, const SlamParams &st, Frame &frame, TemporalStats &stats);
+    // Mapper::triangulateStereo (src/mapper.cpp:346-461): the stereo keypoints of a new keyframe that are not 3D yet.  Selection
+    // and bookkeeping run here, the per-pair arithmetic is one ov2_triangulate_pairs call (mid-point, or the disparity form with
+    // SlamParams::bdo_stereo_rect_ unless midpoint_always).  demote: a failed keypoint loses its stereo flag, as in the
+    // reference (LoopPolicy::midpoint_stereo keeps it).  Static so that a bare MapManager (tests) can run it too;
+    // ov2_map_triangulate_stereo_batch is its mirror form.
+    static ov2_status triangulateStereo(ov2_ctx *ctx, MapManager &map, const SlamParams &st, Frame &frame, StereoTriStats &stats,
+                                        bool midpoint_always = false, bool demote = true);
     // Mapper::matchToMap (src/mapper.cpp:576-774) in three parts.  assembleMatchToMap reads job.pmap, `frame` and the local set and fills the flat
     // arrays (no GPU context needed); the library call is ov2_match_to_map on matchInput(job), or ov2_match_to_map_batch on several
     // jobs at once; applyMatches turns match_cand (one entry per keypoint of the job) into job.map_previd_newid.
@@ -181,7 +188,11 @@ private:
     const uint8_t *imraw_ = nullptr; int imw_ = 0, imh_ = 0, imstride_ = 0;
     void addKeyframe();
     ov2_status mapperRun(const Keyframe &kf);                                                          // src/mapper.cpp:38-189
-    ov2_status triangulateStereo(Frame &frame);                                                        // :346-461
+    ov2_status triangulateStereo(Frame &frame)                                                         // :346-461
+    {
+        StereoTriStats ts;
+        return triangulateStereo(ctx_, *pmap_, *pslamstate_, frame, ts, policy_.midpoint_stereo, !policy_.midpoint_stereo);
+    }
     ov2_status triangulateTemporal(Frame &frame) { return triangulateTemporal(ctx_, *pmap_, *pslamstate_, frame, last_temporal_); }   // :191-344
     ov2_status fixedWindowBA();                                                                        // LoopPolicy::ba_window
     int nkfid_ = 0, nlmid_ = 0;

@@ -89,6 +89,9 @@ def lib():
         L.ov2h_map_forget_keyframe.argtypes = [C.c_void_p, C.c_int]
         L.ov2h_map_forget_kp.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ov2h_triangulate_temporal.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, ip, ip, dp]
+        L.ov2h_map_set_kp_stereo.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, fp]
+        L.ov2h_map_set_right_cam.argtypes = [C.c_void_p, dp, dp, C.c_int]
+        L.ov2h_triangulate_stereo.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, ip, ip, dp]
         L.ov2h_map_filtering.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, ip, dp]
         L.ov2h_map_export_graph.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]
         L.ov2h_slam_set_kf_filtering.argtypes = [C.c_void_p, C.c_float]
@@ -1045,6 +1048,42 @@ class TemporalMap(HostMap):
 
     def invdepth(self, lmid):
         return float(lib().ov2h_landmark_invdepth(self.h, int(lmid)))
+
+
+class StereoTriMap(TemporalMap):
+    """the C++ host map of an ov2slam_amd.synth_stereo_tri.make_map dict -- keyframes with 2D / 3D keypoints, stereo keypoints
+    with their right pixels (Frame::updateKeypointStereo), the right camera of the rig -- to run Mapper::triangulateStereo
+    (SlamManager::triangulateStereo) on its new keyframe.  The dead rows and dead landmarks of the dict are not built."""
+
+    def __init__(self, m, with_stereo=True):
+        alive = (m["obs_alive"] != 0) & (m["lm_alive"][m["obs_lm"]] != 0)
+        TemporalMap.__init__(self, dict(m, obs_kf=m["obs_kf"][alive], obs_lm=m["obs_lm"][alive], obs_uv=m["obs_uv"][alive],
+                                        forget_kp=(), forget_lm=(), forget_kf=()), True)
+        self.m = m
+        assert lib().ov2h_map_set_right_cam(self.h, _dp(np.ascontiguousarray(m["Kr"], np.float64)),
+                                            _dp(np.ascontiguousarray(m["Tlr"], np.float64)), int(m["rectified"])) == 0
+        if with_stereo:
+            st = alive & (m["obs_stereo"] != 0)
+            for k in np.unique(m["obs_kf"][st]):
+                sel = st & (m["obs_kf"] == k)
+                self.set_kp_stereo(int(k), m["obs_lm"][sel], m["obs_rpx"][sel])
+
+    def set_kp_stereo(self, kfid, lmid, rxy):
+        """Frame::updateKeypointStereo(lmid[i], rxy[i]) on keyframe kfid (raw right pixels)"""
+        lmid, rxy = np.ascontiguousarray(lmid, np.int32), np.ascontiguousarray(rxy, np.float32)
+        assert lib().ov2h_map_set_kp_stereo(self.h, int(kfid), len(lmid), lmid.ctypes.data_as(C.POINTER(C.c_int)),
+                                            rxy.ctypes.data_as(C.POINTER(C.c_float))) == 0
+
+    def triangulate_stereo(self, ctx, max_reproj_err=3.0):
+        """the stage on keyframe newkf: (lmid ascending, OV2_TRI_* verdict per keypoint, stats dict)"""
+        cap = self.m["n_lm"]
+        lm, vd, st = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(3)
+        ip = C.POINTER(C.c_int)
+        n = lib().ov2h_triangulate_stereo(self.h, ctx.h, self.newkf, float(max_reproj_err), cap, lm.ctypes.data_as(ip),
+                                          vd.ctypes.data_as(ip), _dp(st))
+        if n < 0:
+            raise RuntimeError(f"triangulateStereo: status {-1 - n}")
+        return lm[:n].copy(), vd[:n].copy(), dict(selected=int(st[0]), good=int(st[1]), demoted=int(st[2]))
 
 
 class FilterMap(TemporalMap):
